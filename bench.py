@@ -411,7 +411,12 @@ def main():
                     "region, for the held-out top-1 retrieval figure (0 = skip; single-GPU runs only; default 6000 for c2, 0 otherwise)")
     ap.add_argument("--stamps", action="store_true", help="diagnostic: in-graph phase stamps of the step (adds 13 tiny nodes; "
                     "prints a phase table to stderr, the JSON line is then not a valid benchmark)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step "
+                    "computed (rank 0) as DIR/<name>.npy: the returned loss and top-1 accuracies, the L2-normalised embeddings "
+                    "and the model's state after the step (see snapshot_outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     cfg = CONFIGS[args.config]
     VOL = cfg["vol"]
     if args.fit_steps is None:
@@ -500,6 +505,7 @@ def main():
     dt = time.perf_counter() - t0
     gc.enable()
     loss_timed = out["loss"].item()           # read before any other step overwrites the trainer's result buffer
+    dumped = snapshot_outputs(tr, out) if args.dump_outputs and rank == 0 else None
     tr_capture_mode = tr.capture_mode
     dt = max_over_ranks(dt)
 
@@ -656,7 +662,38 @@ def main():
         line["collectives_us"] = coll_us
     if world == 1 and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline(PAIRS_PER_GPU, cfg)
+    if dumped is not None:
+        write_outputs(args.dump_outputs, dumped)
     print(json.dumps(line), flush=True)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def snapshot_outputs(tr, out):
+    """host copies of what the last timed step handed its caller: the step's result scalars (loss, top-1 both ways),
+    the L2-normalised embeddings it computed (EEG | fMRI, one row per pair) and the model's state after the step
+    (every parameter and BatchNorm running statistic, named e. / f. / h. for the EEG encoder, the fMRI encoder and the
+    bridge head).  Floating tensors as float32, integer counters as float64.  -> {name: np.ndarray}"""
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in out.items()}
+    if tr._cap is not None:
+        arrays["embeddings"] = tr._cap["z"].detach().float().cpu().numpy()
+    for pre, m in (("e.", tr.eeg_encoder), ("f.", tr.fmri_encoder), ("h.", tr.head)):
+        for k, v in m.state_dict().items():
+            v = v.detach().cpu()
+            arrays["state." + pre + k] = (v.float() if v.is_floating_point() else v.double()).numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"bench.py --dump-outputs: {total / 2**20:.1f} MB of outputs, more than the {DUMP_LIMIT_BYTES >> 20} MB limit")
+    return arrays
+
+
+def write_outputs(path, arrays):
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    print(f"bench.py: {len(arrays)} arrays of the last timed step written to {path}", file=sys.stderr)
 
 
 def host_fed_loop(tr, dev_batches, steps, warm, sync):

@@ -145,12 +145,39 @@ def _oracle_grads(fn, m, *inputs, gy, emulate):
     return out.detach(), {k: v.grad for k, v in sd.items() if v.requires_grad and v.grad is not None}
 
 
-def _worst(named_params, want, skip_below=1e-4):
+def bn_cancelled_biases(module, prefix=""):
+    """names of the conv biases that feed a train-mode BatchNorm directly.  The normalisation subtracts their per-channel
+    constant again, so their exact gradient is 0; an oracle's value for it is rounding noise whose size depends on the
+    host's summation order (thread count), so it is no yardstick for a relative error."""
+    out = set()
+    for name, mod in module.named_modules():
+        if not isinstance(mod, torch.nn.Sequential):
+            continue
+        kids = list(mod.named_children())
+        for (k, conv), (_, bn) in zip(kids, kids[1:]):
+            if (isinstance(conv, torch.nn.modules.conv._ConvNd) and conv.bias is not None
+                    and isinstance(bn, torch.nn.modules.batchnorm._BatchNorm) and bn.training):
+                out.add(f"{prefix}{name + '.' if name else ''}{k}.bias")
+    return out
+
+
+def zero_grad_err(got, want_weight_grad):
+    """error of a gradient whose exact value is 0 (bn_cancelled_biases): its norm relative to the oracle's gradient of
+    the same layer's weight"""
+    return (got.double().norm() / want_weight_grad.double().norm()).item()
+
+
+def _worst(named_params, want, skip_below=1e-4, zero=()):
+    """worst rel-L2 error of the parameter gradients against the oracle's; names in ``zero`` are held to their exact value
+    0 instead (zero_grad_err), whatever rounding noise the oracle computed for them"""
     worst = ("", 0.0)
     for n, p in named_params:
-        if n not in want or want[n].norm() < skip_below:
+        if n in zero:
+            e = zero_grad_err(p.grad.cpu(), want[n[:-len("bias")] + "weight"])
+        elif n not in want or want[n].norm() < skip_below:
             continue
-        e = rel_err(p.grad.cpu(), want[n])
+        else:
+            e = rel_err(p.grad.cpu(), want[n])
         if e > worst[1]:
             worst = (n, e)
     return worst
@@ -169,8 +196,9 @@ def test_volume_encoder_train_grads_vs_oracle():
     y = mg(x.cuda())
     y.backward(gy.cuda())
     assert cos_min(y.detach().cpu(), out32) >= 1 - COS_TOL
-    w16 = _worst(mg.named_parameters(), g16)
-    w32 = _worst(mg.named_parameters(), g32)
+    zero = bn_cancelled_biases(mg)
+    w16 = _worst(mg.named_parameters(), g16, zero=zero)
+    w32 = _worst(mg.named_parameters(), g32, zero=zero)
     assert w16[1] <= 5e-2, ("vs bf16-operand oracle", w16)
     assert w32[1] <= 2e-1, ("vs fp32 oracle", w32)
     # against the UNMODIFIED fp32 oracle with the arg-max flips isolated: the gradients of layer 3 and of the head are formed
@@ -178,7 +206,7 @@ def test_volume_encoder_train_grads_vs_oracle():
     # loose bound above absorbs is confined to layers 1 and 2 (whose gradients pass through the pools' routing)
     no_pool = [(n, q) for n, q in mg.named_parameters() if n.startswith(("conv_layers.10", "conv_layers.11", "output_proj"))]
     assert len(no_pool) == 6
-    wnp = _worst(no_pool, g32)
+    wnp = _worst(no_pool, g32, zero=zero)
     assert wnp[1] <= 5e-2, ("layer 3 / head vs the unmodified fp32 oracle", wnp)
 
 
@@ -210,7 +238,7 @@ def test_volume_encoder_grads_vs_unmodified_fp32_oracle_with_hip_routing(shape, 
     out.backward(gy)
     want = {k: v.grad for k, v in sd.items() if v.requires_grad and v.grad is not None}
     assert cos_min(y.detach().cpu(), out.detach()) >= 1 - COS_TOL
-    w = _worst(mg.named_parameters(), want)
+    w = _worst(mg.named_parameters(), want, zero=bn_cancelled_biases(mg))
     assert w[1] <= 5e-2, ("every layer vs the unmodified fp32 oracle routed as the HIP path", w)
     # the routing is the oracle's own arg-max except at near-ties: per pooled element, the member the HIP path took holds
     # the window maximum of the ORACLE's pre-pool activations up to a small gap
@@ -237,8 +265,9 @@ def test_volume_encoder_train_grads_at_config4_size_vs_oracle():
     y = mg(x.cuda())
     y.backward(gy.cuda())
     assert cos_min(y.detach().cpu(), out32) >= 1 - COS_TOL
-    w16 = _worst(mg.named_parameters(), g16)
-    w32 = _worst(mg.named_parameters(), g32)
+    zero = bn_cancelled_biases(mg)
+    w16 = _worst(mg.named_parameters(), g16, zero=zero)
+    w32 = _worst(mg.named_parameters(), g32, zero=zero)
     assert w16[1] <= 6e-2, ("vs bf16-operand oracle", w16)
     assert w32[1] <= 2e-1, ("vs fp32 oracle", w32)
 
@@ -608,7 +637,7 @@ def test_a4_power_encoder_train_grads_vs_oracle():
     y = mg(xg)
     y.backward(gy.cuda())
     assert cos_min(y.detach().cpu(), out32) >= 1 - COS_TOL
-    w16 = _worst(mg.named_parameters(), g16)
+    w16 = _worst(mg.named_parameters(), g16, zero=bn_cancelled_biases(mg))
     assert w16[1] <= 5e-2, ("vs bf16-operand oracle", w16)
     _grad_check("dx", xg.grad.cpu(), xe.grad, 8e-2)
     for name in ("conv_scale1.1", "conv_scale2.1", "conv_scale3.1", "fusion.1"):
