@@ -63,7 +63,7 @@ struct L1Args {
     uint8_t* arg;          // mode 1 with ARG: the pooling window's winner j = (dd << 2) | (hh << 1) | ww per output element
     float* dw;             // mode 3: [27][32] (tap-major, channel-contiguous); mode 4: A1
     float* dbias;          // mode 3
-    float* gram;           // gram kernel: accumulator workspace [32][32] (tap, tap)
+    float* gram;           // gram kernel: accumulator workspace [32][32] (tap, tap); mode 4 (train): read, S[tap] = G[tap][27]
     MmBnFin fin;           // mode 1 with FIN: the layer's BatchNorm finalize in the kernel's prologue (out4 written, not read)
     int B, D, H, W, train;
     uint32_t thresh, seed; float inv_keep, inv_count;
@@ -190,6 +190,7 @@ __global__ __launch_bounds__(256, MODE <= 1 ? 3 : L1_BWD_WAVES) void conv3d_l1_k
     // form z identically - the window winner is decided on it)
     const float shb = fmaf(bias, sc, sh);
     float acc1 = 0.f, acc2 = 0.f;          // per-lane channel sums (modes 0, 2, 4) / dbias (mode 3)
+    float acc3 = 0.f;                      // mode 4: sum of the bf16-rounded dz the A1 MFMA multiplies
     f32x16 dwacc;                          // modes 3, 4: D[tap][n]
 #pragma unroll
     for (int r = 0; r < 16; ++r) dwacc[r] = 0.f;
@@ -250,6 +251,7 @@ __global__ __launch_bounds__(256, MODE <= 1 ? 3 : L1_BWD_WAVES) void conv3d_l1_k
         // dy (mode 3) / dz (mode 4) fragments of the two conv tiles ip, ip + 2 that one pass of the ip loop completes;
         // their weight-gradient MFMAs run at the end of that pass, so only two tiles' fragments are ever live
         union DyFrag { bf16x8 v; uint32_t u[4]; } dyf[2][2];
+        DyFrag dyl[2][2];                  // mode 3: dy - bf16(dy), the second bf16 term of dy (see the MFMAs below)
         // flat index of this lane's first pooled output of the tile (32-bit: the host checks the tensor size)
         const uint32_t obase = ((((uint32_t)b * Do + (d0 >> 1)) * Ho + (h0 >> 1)) * Wo + (w0 >> 1) + 4 * wave + 2 * lh) * 32 + lr;
 #pragma unroll
@@ -327,8 +329,10 @@ __global__ __launch_bounds__(256, MODE <= 1 ? 3 : L1_BWD_WAVES) void conv3d_l1_k
                                 const int ti = ip + 2 * (j >> 2), r = r0 + 4 * ((j >> 1) & 1) + (j & 1);
                                 dyf[ti >> 1][r >> 3].v[r & 7] = (bf16)(js == j ? dzs : 0.f);
                             }
+                            acc3 += (float)(bf16)dzs;
                         } else {
                             const bf16 db = (bf16)dzs;
+                            acc3 += (float)db;
                             const uint32_t pairval = (uint32_t)(*reinterpret_cast<const unsigned short*>(&db)) << ((js & 1) << 4);
                             const int jp = js >> 1;
 #pragma unroll
@@ -344,7 +348,9 @@ __global__ __launch_bounds__(256, MODE <= 1 ? 3 : L1_BWD_WAVES) void conv3d_l1_k
                             const int d = d0 + (ti >> 1), h = h0 + 4 * (ti & 1) + (r >> 2), w = w0 + wbase + (r & 3) + 4 * lh;
                             if (!FULLT && !(d < a.D && h < a.H && w < a.W)) dy = 0.f;
                             acc1 += dy;
-                            dyf[ti >> 1][r >> 3].v[r & 7] = (bf16)dy;
+                            const bf16 dh = (bf16)dy;
+                            dyf[ti >> 1][r >> 3].v[r & 7] = dh;
+                            dyl[ti >> 1][r >> 3].v[r & 7] = (bf16)(dy - (float)dh);
                         }
                     }
                 }
@@ -364,6 +370,9 @@ __global__ __launch_bounds__(256, MODE <= 1 ? 3 : L1_BWD_WAVES) void conv3d_l1_k
                             fr.u[j] = hb[vb + my_tap_off];
                         }
                         dwacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fr.v, dyf[tq][s].v, dwacc, 0, 0, 0);
+                        // mode 3's dy is dense and carries sc (c0 + xhat c1) on every voxel: its bf16 rounding error,
+                        // multiplied by the input's mean, does not cancel - the remainder goes through a second MFMA
+                        if (MODE == 3) dwacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fr.v, dyl[tq][s].v, dwacc, 0, 0, 0);
                     }
             }
         }
@@ -391,16 +400,39 @@ __global__ __launch_bounds__(256, MODE <= 1 ? 3 : L1_BWD_WAVES) void conv3d_l1_k
         }
     }
     if (MODE == 3 || MODE == 4) {
+        // mode 4, train: A1 = x^T bf16(dz) carries x^T (bf16(dz) - dz), whose mean component mu sum (bf16(dz) - dz) the
+        // combine step's c0 S = (S1 / M) S (S1 = sum of the UNROUNDED dz) does not cancel - the weight gradient's error grew
+        // like mu / sigma 2^-9 (tests/test_conv3d_l1_gpu.py).  Every workgroup removes it from its own share:
+        // A1 -= (its sum bf16(dz) - its sum dz) S / M, which is linear, so the whole is A1 - (sum bf16(dz) - S1) S / M.
+        // Only for an input whose mean matters: mean^2 > var / 16 (centre tap, from G).  Below that the mean component is
+        // under a quarter of the dz rounding's own error, and the pass keeps the arithmetic it had without the correction.
+        // mode 2 runs this instance with dw == NULL: the sums alone, bit for bit those of mode 4.
+        __shared__ float s_S[(MODE == 4) ? 28 : 1];
+        const bool fixmean = MODE == 4 && a.train && a.dw;
+        if (MODE == 4) acc3 += __shfl_xor(acc3, 32, 64);
         __syncthreads();
 #pragma unroll
         for (int r = 0; r < 16; ++r) {                            // every wave parks its tile: no LDS atomics
             const int tap = (r & 3) + 8 * (r >> 2) + 4 * lh;      // D row
             if (tap < 27) wred[wave][tap][lr] = dwacc[r];
         }
+        if (fixmean) {
+            if (lh == 0) red[wave][lr] = acc3 - acc1;             // acc1: this lane pair's sum dz (red's readers passed the barrier)
+            if (tid < 28)                                         // S[tap] / M, and G[13][13] / M in slot 27
+                s_S[tid] = acc_val<MM_ACC_STAT>(acc_sum(a.gram, 1024, tid < 27 ? tid * 32 + 27 : 13 * 32 + 13)) * a.inv_count;
+        }
         __syncthreads();
+        if (!a.dw) return;
+        const bool mean_matters = fixmean && 16.f * s_S[13] * s_S[13] > s_S[27] - s_S[13] * s_S[13];
         mm_acc_t* dwr = acc_rep(a.dw, blockIdx.x % MM_ACC_REPL, 27 * 32);
-        for (int i = tid; i < 27 * 32; i += 256)
-            acc_add<MM_ACC_GRAD>(&dwr[i], ((&wred[0][0][0])[i] + (&wred[1][0][0])[i]) + ((&wred[2][0][0])[i] + (&wred[3][0][0])[i]));
+        for (int i = tid; i < 27 * 32; i += 256) {
+            float v = ((&wred[0][0][0])[i] + (&wred[1][0][0])[i]) + ((&wred[2][0][0])[i] + (&wred[3][0][0])[i]);
+            if (mean_matters) {
+                const int n = i & 31;
+                v -= ((red[0][n] + red[1][n]) + (red[2][n] + red[3][n])) * s_S[i >> 5];
+            }
+            acc_add<MM_ACC_GRAD>(&dwr[i], v);
+        }
     }
 }
 
@@ -614,7 +646,9 @@ __global__ __launch_bounds__(256) void l1_tapsum_kernel(const float* __restrict_
 
 // dW[n][tap] += sc (A1 - c0 S - c1 A3);  dbias[n] += train ? 0 : sc S1, with S[tap] = G[tap][27] and
 // A3[tap][n] = rstd_n ((G w_n)[tap] + (b_n - mean_n) S[tap]) from the Gram accumulator workspace of the forward pass
-// (upper triangle, MM_ACC_REPL replicas); a1 / sums: fixed-point accumulators x MM_ACC_REPL.  One output per 16 lanes,
+// (upper triangle, MM_ACC_REPL replicas); a1 / sums: fixed-point accumulators x MM_ACC_REPL.
+// (A1 arrives with the mean component of its bf16 rounding removed by the backward pass: conv3d_l1_kernel<4>.)
+// (G w)[tap] and (b - mean) S[tap] both grow like M mu^2 and cancel: A3 is formed in double.  One output per 16 lanes,
 // one REPLICA per lane: lane r forms its replica's share of (G w_n)[tap] and S[tap] in double (27 independent loads), the
 // 16 shares are summed by a fixed butterfly.  gram may be null when train == 0 (c0 = c1 = 0: frozen BatchNorm).
 __global__ void l1_combine_kernel(const float* __restrict__ a1, const float* __restrict__ gram, const bf16* __restrict__ wimg,
@@ -651,10 +685,10 @@ __global__ void l1_combine_kernel(const float* __restrict__ a1, const float* __r
     const float sc = out4[n], mu = out4[64 + n], rs = out4[96 + n];
     float corr = 0.f;
     if (train) {
-        const float b = bias ? bias[n] : 0.f;
-        const float Stf = bad ? __builtin_nanf("") : (float)St;
-        const float A3 = rs * ((float)gw + (b - mu) * Stf);
-        corr = s0 * inv_count * Stf + s1 * inv_count * A3;
+        const double b = bias ? (double)bias[n] : 0.0;
+        const double Sd = bad ? (double)__builtin_nanf("") : St;
+        const double A3 = (double)rs * (gw + (b - (double)mu) * Sd);
+        corr = (float)((double)(s0 * inv_count) * Sd + (double)(s1 * inv_count) * A3);
     }
     dw[i] += sc * (A1 - corr);
     if (tap == 0 && dbias && !train) dbias[n] += sc * s0;      // train: sum dy == 0 identically
@@ -714,8 +748,10 @@ int mm_conv3d_l1(int mode, const float* x, const void* wimg, const float* bias, 
         case 1: hipLaunchKernelGGL((conv3d_l1_kernel<0, true>), dim3(g3), dim3(256), 0, st, a); break;
         case 2: hipLaunchKernelGGL((conv3d_l1_kernel<1, false>), dim3(g3), dim3(256), 0, st, a); break;
         case 3: hipLaunchKernelGGL((conv3d_l1_kernel<1, true>), dim3(g3), dim3(256), 0, st, a); break;
-        case 4: hipLaunchKernelGGL((conv3d_l1_kernel<2, false>), dim3(g2), dim3(256), 0, st, a); break;
-        case 5: hipLaunchKernelGGL((conv3d_l1_kernel<2, true>), dim3(g2), dim3(256), 0, st, a); break;
+        // mode 2 = mode 4's pass without its A1 output (dw = NULL): the sums are then those of mm_conv3d_l1_bwd bit for bit
+        // (a separate instance rounded dz and the sums differently - the compiler fused different products)
+        case 4: a.dw = nullptr; hipLaunchKernelGGL((conv3d_l1_kernel<4, false>), dim3(g2), dim3(256), 0, st, a); break;
+        case 5: a.dw = nullptr; hipLaunchKernelGGL((conv3d_l1_kernel<4, true>), dim3(g2), dim3(256), 0, st, a); break;
         case 6: hipLaunchKernelGGL((conv3d_l1_kernel<3, false>), dim3(g2), dim3(256), 0, st, a); break;
         default: hipLaunchKernelGGL((conv3d_l1_kernel<3, true>), dim3(g2), dim3(256), 0, st, a); break;
     }
@@ -788,7 +824,7 @@ int mm_conv3d_l1_bwd(const float* x, const void* wimg, const float* bias, const 
     MM_REQUIRE(l1_fits(B, D, H, W), "conv3d_l1_bwd: more than 2^31 pooled output elements");
     L1Args a;
     l1_fill(a, x, wimg, bias, out4, B, D, H, W, train, drop_p, seed, seed_epoch);
-    a.dout = (const bf16*)dout; a.stats = sums_out; a.dw = a1;
+    a.dout = (const bf16*)dout; a.stats = sums_out; a.dw = a1; a.gram = const_cast<float*>(gram);
     const int grid = l1_grid(l1_tiles(B, D, H, W), L1_BWD_WAVES);
     if (H % 8 == 0 && W % 32 == 0) hipLaunchKernelGGL((conv3d_l1_kernel<4, true>), dim3(grid), dim3(256), 0, st, a);
     else hipLaunchKernelGGL((conv3d_l1_kernel<4, false>), dim3(grid), dim3(256), 0, st, a);
