@@ -347,11 +347,14 @@ int mm_conv3d_wgrad(const void* dy, const void* x, float* dw, float* dbias, int 
 /* slot_mode as in mm_conv1d_wgrad; *slots_host (HOST int) = slots a slot-mode launch writes */
 int mm_conv3d_wgrad_slots(int B, int D, int H, int W, int Cin, int Cout, int* slots_host, hipStream_t stream);
 /* y bf16 [B][D][H][W][N] (the convolution's pre-BatchNorm output) -> act(BN(y)) -> MaxPool3d(2) -> dropout ->
- * bf16 [B][D/2][H/2][W/2][N].  N % 8 == 0.  Training also keeps, per pooled element, the winner's pre-BN
+ * bf16 [B][D/2][H/2][W/2][N] (floors, as torch: D, H, W >= 2, odd extents allowed).  N % 8 == 0.  Training also keeps, per pooled element, the winner's pre-BN
  * value (ysel bf16) and its index in the 2x2x2 window (arg, one byte: 4 d + 2 h + w); both null in eval.
  * The reduction of the BatchNorm gradient sums then reads only pooled data (gradients vanish off the
  * winners) and the apply pass (dy bf16, full volume) takes the argmax from `arg`; its `sums` is the reduce pass's
- * accumulator workspace (sums_nrep = 32) or a compact fp32 [2][N] (sums_nrep = 1), as for mm_bn_act_bwd_apply. */
+ * accumulator workspace (sums_nrep = 32) or a compact fp32 [2][N] (sums_nrep = 1), as for mm_bn_act_bwd_apply.
+ * Tail rule (odd extents): the last plane / row / column that no window covers counts in the BatchNorm statistics
+ * (count = B D H W) and gets no gradient through the pool; the apply pass writes every element of dy, the tail's with
+ * scale * (0 - c0 - c1 xhat) in train mode and 0 under frozen BatchNorm (train == 0). */
 int mm_pool3d_bn_act_fwd(const void* y, const float* out4, void* out_bf16, void* ysel, void* arg, int B, int D,
                          int H, int W, int N, int act, float drop_p, uint32_t seed, const uint32_t* seed_epoch,
                          hipStream_t stream);
@@ -368,12 +371,14 @@ int mm_pool3d_bn_act_bwd_apply(const void* y, const void* arg, const float* out4
  * stored.  mode 0: stats[2][32] += {sum, sumsq} of conv+bias; mode 1: forward
  * (out bf16 [B][D/2][H/2][W/2][32]); mode 2: stats += {sum dz, sum dz*xhat};
  * mode 3: dw_tapmajor[27][32] += x^T dy, dbias += sum dy.  wimg = bf16 [32][32]
- * (n, tap) from mm_prep_conv_weight(w as (32,27,1)). */
+ * (n, tap) from mm_prep_conv_weight(w as (32,27,1)).  D, H, W >= 2; pooled extents are floors (as torch), and the
+ * tail rule of mm_pool3d_bn_act_* holds: statistics (modes 0 and the Gram kernel) and mode 3's dense dy cover all
+ * B D H W conv outputs, the pooling windows (modes 1, 2 and the backward) the 2[D/2] x 2[H/2] x 2[W/2] corner. */
 int mm_conv3d_l1(int mode, const float* x, const void* wimg, const float* bias, const float* out4,
                  const void* dout, const float* sums, float* stats, void* out, float* dw_tapmajor,
                  float* dbias, int B, int D, int H, int W, int train, float drop_p, uint32_t seed,
                  const uint32_t* seed_epoch, hipStream_t stream);
-/* mode 1 (the forward) with one more output: arg u8 [B][D/2][H/2][W/2][32] = which member of each 2x2x2 pooling
+/* mode 1 (the forward) with one more output: arg u8 [B][D/2][H/2][W/2][32] (floors) = which member of each 2x2x2 pooling
  * window won, j = (dd << 2) | (hh << 1) | ww (the convention of mm_pool3d_bn_act_fwd's `arg`).  The training path
  * recomputes the winners in its backward and never stores them; this entry point lets a caller inspect the routing
  * (the parity tests evaluate the fp32 oracle with the HIP path's routing: an arg-max flip between two near-equal
@@ -382,7 +387,7 @@ int mm_conv3d_l1_fwd_winners(const float* x, const void* wimg, const float* bias
                              void* arg, int B, int D, int H, int W, int train, float drop_p, uint32_t seed,
                              const uint32_t* seed_epoch, hipStream_t stream);
 /* Training forward of the same layer without a statistics pass over the convolution: the Gram matrix of the im2col
- * matrix, G[t][t'] = sum over output voxels of xcol[v][t] * xcol[v][t'] for the 27 taps plus a column of ones (bf16-
+ * matrix, G[t][t'] = sum over ALL B D H W output voxels (odd tails included) of xcol[v][t] * xcol[v][t'] for the 27 taps plus a column of ones (bf16-
  * rounded, zero-padded volume - what the convolution sees), holds everything the layer needs from the input:
  *   sum_v y_n = w_n . S + M b_n,  sum_v y_n^2 = w_n^T G w_n + 2 b_n w_n . S + M b_n^2   (S[t] = G[t][27], M = G[27][27])
  * and, in the backward, A3[t][n] = sum_v xcol[v][t] xhat[v][n] = rstd_n ((G w_n)[t] + (b_n - mean_n) S[t]).

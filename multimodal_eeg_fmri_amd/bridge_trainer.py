@@ -160,6 +160,7 @@ class BridgeTrainer(nn.Module):
         first use (one graph at world 1; three segments around the two
         collectives otherwise); "manual" runs the same autograd-free tape eagerly;
         "autograd" goes through the public nn.Module / torch.autograd surface."""
+        ops.check_volume_shape(fmri.shape)                 # before the first launch of the step (or of its capture)
         if self.mode == "autograd":
             return self._step_autograd(eeg, fmri)
         if self.mode == "manual":

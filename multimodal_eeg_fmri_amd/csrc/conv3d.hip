@@ -263,11 +263,16 @@ __global__ void pack_vol_kernel(const float* __restrict__ x, bf16* __restrict__ 
 //   * the apply pass evaluates one act' per pooled element and never re-derives
 //     the argmax.
 // One thread = 4 channels of one pooled voxel (8 x 16-byte loads).
+// Odd extents: the pooled extent is [D/2] x [H/2] x [W/2] (floors, as torch) and the windows walk it with the full
+// volume's strides.  The tail - the last plane / row / column of an odd axis, in no window - is in the BatchNorm
+// statistics (the convolution's accumulators count all B D H W voxels) and gets no gradient through the pool: the
+// apply pass writes its dy = sc (0 - c0 - c1 xhat) (train) or 0 (frozen BatchNorm) in a tail phase of its own, so
+// that every element of dy is written by the launch.
 // ---------------------------------------------------------------------------
 struct Pool3Args {
     const bf16* y; const float* out4; const bf16* dout; const float* sums;
     bf16* out; float* sums_out; bf16* dy;
-    bf16* ysel; uint8_t* arg;                  // pooled [B][D/2][H/2][W/2][N]
+    bf16* ysel; uint8_t* arg;                  // pooled [B][D/2][H/2][W/2][N] (floors)
     int B, D, H, W, N, act, train;
     uint32_t thresh, seed; float inv_keep, inv_count;
     const uint32_t* epoch;
@@ -388,6 +393,30 @@ __global__ __launch_bounds__(256) void pool3_bn_act_kernel(Pool3Args a) {
             }
         }
     }
+    if (MODE == 2) {
+        // tail phase: per sample, the last plane (odd D: H W voxels), then the last row of the window planes (odd H:
+        // 2[D/2] W), then the last column of the window rows (odd W: 2[D/2] 2[H/2]) - disjoint, and empty for even extents
+        const int Dw = 2 * Do, Hw = 2 * Ho;
+        const unsigned nd = (a.D & 1) ? (unsigned)(a.H * a.W) : 0u, nh = (a.H & 1) ? (unsigned)(Dw * a.W) : 0u,
+                       nw = (a.W & 1) ? (unsigned)(Dw * Hw) : 0u, per = nd + nh + nw;
+        const size_t ntail = (size_t)a.B * per;
+        for (size_t row = (size_t)blockIdx.x * rows_per_blk + ri; row < ntail; row += (size_t)gridDim.x * rows_per_blk) {
+            const unsigned b = (unsigned)(row / per), t = (unsigned)(row - (size_t)b * per);
+            int d, h, w;
+            if (t < nd) { d = a.D - 1; h = (int)(t / (unsigned)a.W); w = (int)(t % (unsigned)a.W); }
+            else if (t < nd + nh) { const unsigned u = t - nd; d = (int)(u / (unsigned)a.W); h = a.H - 1; w = (int)(u % (unsigned)a.W); }
+            else { const unsigned u = t - nd - nh; d = (int)(u / (unsigned)Hw); h = (int)(u % (unsigned)Hw); w = a.W - 1; }
+            const size_t idx = ((((size_t)b * a.D + d) * a.H + h) * a.W + w) * a.N + n8;
+            const bf16x8 tv = *reinterpret_cast<const bf16x8*>(a.y + idx);
+            bf16x8 o;
+#pragma unroll
+            for (int c = 0; c < 8; ++c) {
+                const float xh = ((float)tv[c] - mu[c]) * rs[c];
+                o[c] = (bf16)(a.train ? sc[c] * (0.f - c0[c] - xh * c1[c]) : 0.f);
+            }
+            *reinterpret_cast<bf16x8*>(a.dy + idx) = o;
+        }
+    }
 }
 
 // BN-gradient partial sums from the pooled winners only:  sums[0][n] += dz, sums[1][n] += dz * xhat
@@ -443,7 +472,7 @@ __global__ __launch_bounds__(256) void pool3_bwd_reduce_kernel(Pool3Args a) {
 inline uint32_t thresh3(float p) { return p > 0.f ? (uint32_t)((double)p * 4294967296.0) : 0u; }
 
 int pool3_launch(int mode, Pool3Args a, float drop_p, hipStream_t st, bool with_fin = false) {
-    MM_REQUIRE(a.out4 && a.B > 0 && a.D % 2 == 0 && a.H % 2 == 0 && a.W % 2 == 0, "pool3d_bn_act: dims must be even");
+    MM_REQUIRE(a.out4 && a.B > 0 && a.D >= 2 && a.H >= 2 && a.W >= 2, "pool3d_bn_act: D,H,W must be >= 2 (MaxPool3d(2) floors odd extents)");
     MM_REQUIRE(a.N % 8 == 0 && a.N <= 1024, "pool3d_bn_act: N must be a multiple of 8");
     a.thresh = thresh3(drop_p); a.inv_keep = drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f;
     a.inv_count = 1.f / ((float)a.B * a.D * a.H * a.W);

@@ -29,6 +29,16 @@
 // i + 1 into registers during tile i was measured and is off: two other workgroups per CU already cover the load.
 // GELU is evaluated once per window when max(z) >= 0 (GELU is monotone on [-0.7518, inf) and negative left of 0,
 // so the window max is GELU(max z)); otherwise at the largest and the smallest member.  Both branches are exact.
+//
+// Odd extents (MaxPool3d(2) floors them, as torch): every kernel keeps two extents apart.
+//   volume extent D x H x W       : halo bounds, strides, the convolution's zero padding; the tiles of the Gram kernel
+//                                   and of modes 0 / 3, which need every conv output (the BatchNorm statistics count
+//                                   all B D H W voxels, the tail too; mode 3's dense dy is non-zero on the tail).
+//   window extent 2[D/2] x 2[H/2] x 2[W/2]: the tiles of modes 1, 2, 4 - only voxels inside a pooling window can win.
+// The tail (the last plane / row / column of an odd axis) gets no gradient through the pool; with train-mode
+// BatchNorm it still gets dy = sc (0 - c0 - c1 xhat).  The mode-4 backward needs no tail pass for it: its
+// dW = sc (A1 - c0 S - c1 A3) takes every non-winner term, tail included, from S and A3, i.e. from G - which is why
+// the Gram kernel must cover the whole volume extent.  Even extents have an empty tail: both extents coincide.
 #include "common.h"
 
 // ablation builds (tools/abl_stream.sh with ABL_FILE=conv3d_l1 ABL_MACRO=L1_ABL; product = 0; profiles/r04_l1_ablation.txt):
@@ -56,7 +66,7 @@ struct L1Args {
     const bf16* wimg;      // [32][32] (n, tap; taps 27..31 zero)
     const float* bias;     // [32] or nullptr (eval: folded into out4 shift)
     const float* out4;     // [4][32] scale, shift, mean, rstd  (modes 1-4)
-    const bf16* dout;      // [B][D/2][H/2][W/2][32]            (modes 2-4)
+    const bf16* dout;      // [B][D/2][H/2][W/2][32] (floors)   (modes 2-4)
     const float* sums;     // [2][32]                           (mode 3)
     float* stats;          // mode 0: [2][32];  modes 2, 4: sums_out
     bf16* out;             // mode 1
@@ -146,8 +156,10 @@ __device__ __forceinline__ const float* tile_ptr(const float* x, const TileCoord
     return x + ((((size_t)c.b * D + c.d0) * H + c.h0) * W + c.w0);
 }
 
-// FULLT: H % 8 == 0 and W % 32 == 0, i.e. every 2 x 8 x 32 tile lies inside the volume: the per-voxel bounds tests
-// (three compares and the index arithmetic behind them, per voxel and channel) are compiled out.
+// FULLT: every 2 x 8 x 32 tile of the kernel's tile space lies inside it (l1_full: the volume extent for the Gram
+// kernel and modes 0 / 3, the window extent for modes 1, 2, 4): the per-voxel bounds tests (three compares and the
+// index arithmetic behind them, per voxel and channel) are compiled out.  Halo loads are always bounds-checked
+// against the volume extent (with odd H, row H - 1 is real data next to the last window row).
 // ARG (mode 1): also write the window winners (inspection output of the parity tests, mm_conv3d_l1_fwd_winners).
 // FIN (mode 1): the train-mode BatchNorm finalize as the prologue (csrc/common.h: bn_fin_channel).
 template <int MODE, bool FULLT = false, bool ARG = false, bool FIN = false>
@@ -158,7 +170,10 @@ __global__ __launch_bounds__(256, MODE <= 1 ? 3 : L1_BWD_WAVES) void conv3d_l1_k
     __shared__ float wred[(MODE == 3 || MODE == 4) ? 4 : 1][27][32];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int lr = lane & 31, lh = lane >> 5;
-    const int tw = (a.W + 31) / 32, th = (a.H + 7) / 8, td = a.D / 2;
+    // tile space: modes 0 and 3 the volume extent, modes 1, 2, 4 the window extent (the same for even extents)
+    constexpr bool VOL = MODE == 0 || MODE == 3;
+    const int De = VOL ? a.D + 1 : a.D, He = VOL ? a.H : a.H & ~1, We = VOL ? a.W : a.W & ~1;
+    const int tw = (We + 31) / 32, th = (He + 7) / 8, td = De / 2;
     const int ntiles = a.B * td * th * tw;
     const int Do = a.D / 2, Ho = a.H / 2, Wo = a.W / 2;
 
@@ -262,7 +277,7 @@ __global__ __launch_bounds__(256, MODE <= 1 ? 3 : L1_BWD_WAVES) void conv3d_l1_k
                 for (int rb = 0; rb < 2; ++rb) {
                     const int r0 = 8 * ra + 2 * rb;
                     const int oh = (h0 >> 1) + 2 * ip + ra, ow = (w0 >> 1) + 4 * wave + rb + 2 * lh;
-                    const bool ok = FULLT || (oh < Ho && ow < Wo);
+                    const bool ok = FULLT || (oh < Ho && ow < Wo && (!VOL || (d0 >> 1) < Do));   // (mode 3: a tail tile)
                     float z[8];
 #pragma unroll
                     for (int j = 0; j < 8; ++j) {           // j = (dd << 2) | (hh << 1) | ww
@@ -436,7 +451,8 @@ __global__ __launch_bounds__(256, MODE <= 1 ? 3 : L1_BWD_WAVES) void conv3d_l1_k
     }
 }
 
-// G[t][t'] = sum over output voxels v of xcol[v][t] xcol[v][t'] for the 27 taps and the constant column 27 (ones):
+// G[t][t'] = sum over ALL output voxels v (the volume extent, tail included) of xcol[v][t] xcol[v][t'] for the 27
+// taps and the constant column 27 (ones):
 // the Gram matrix of the im2col matrix of the zero-padded, bf16-rounded volume.  A wave owns 2 x 8 x 8 voxels per tile
 // = 8 MFMA K-steps of 16 voxels; the A operand (row = tap lr, k = 8 consecutive voxels of one row) and the B operand
 // (k = voxel, column = tap lr) of G += Xcol^T Xcol are the SAME registers.  One accumulator for the whole kernel.
@@ -451,7 +467,7 @@ __global__ __launch_bounds__(256, 3) void l1_gram_kernel(L1Args a) {
     __shared__ double part[8][2][32];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int lr = lane & 31, lh = lane >> 5;
-    const int tw = (a.W + 31) / 32, th = (a.H + 7) / 8, td = a.D / 2;
+    const int tw = (a.W + 31) / 32, th = (a.H + 7) / 8, td = (a.D + 1) / 2;      // the volume extent: M = B D H W
     const int ntiles = a.B * td * th * tw;
     const int my_tap_off = tap_off(lr);
     for (int i = tid; i < 32 * 27; i += 256)                    // the bf16 weights the convolution multiplies with
@@ -482,6 +498,7 @@ __global__ __launch_bounds__(256, 3) void l1_gram_kernel(L1Args a) {
 #pragma unroll
         for (int s = 0; s < 8; ++s) {
             // K-step s: voxels m = 16 s + 8 lh + j, j = 0..7: depth s >> 2, row (2 s + lh) & 7, columns wbase + j
+            if (!FULLT && s == 4 && tc.d0 + 1 == a.D) break;   // odd D: the last depth tile has one plane (wave-uniform)
             const int hrow = (2 * s + lh) & 7;
             const int vb = ((s >> 2) * 10 + hrow) * HP + wbase;
             union { uint32_t u[4]; bf16x8 v; } fr;
@@ -714,7 +731,14 @@ inline void l1_fill(L1Args& a, const float* x, const void* wimg, const float* bi
     a.inv_count = 1.f / ((float)B * D * H * W);
     a.epoch = seed_epoch;
 }
-inline int l1_tiles(int B, int D, int H, int W) { return B * (D / 2) * ceil_div(H, 8) * ceil_div(W, 32); }
+// tile counts and the FULLT test of the two tile spaces (see the file header): the volume extent (vol = true: the Gram
+// kernel, modes 0 and 3) or the window extent 2[D/2] x 2[H/2] x 2[W/2]
+inline int l1_tiles(int B, int D, int H, int W, bool vol) {
+    return vol ? B * ceil_div(D, 2) * ceil_div(H, 8) * ceil_div(W, 32) : B * (D / 2) * ceil_div(H & ~1, 8) * ceil_div(W & ~1, 32);
+}
+inline bool l1_full(int D, int H, int W, bool vol) {
+    return vol ? D % 2 == 0 && H % 8 == 0 && W % 32 == 0 : (H & ~1) % 8 == 0 && (W & ~1) % 32 == 0;
+}
 // persistent grids: `per_cu` resident workgroups on each of the 256 CUs (the register budget of the instance decides)
 inline int l1_grid(int ntiles, int per_cu) { const int cap = 256 * per_cu; return ntiles < cap ? ntiles : cap; }
 // pooled output indices are formed in 32 bits (they also seed the dropout hash)
@@ -729,7 +753,7 @@ int mm_conv3d_l1(int mode, const float* x, const void* wimg, const float* bias, 
                  int B, int D, int H, int W, int train, float drop_p, uint32_t seed, const uint32_t* seed_epoch,
                  hipStream_t st) {
     MM_REQUIRE(x && wimg && B > 0 && D > 0 && H > 0 && W > 0, "conv3d_l1: null/invalid");
-    MM_REQUIRE(D % 2 == 0 && H % 2 == 0 && W % 2 == 0, "conv3d_l1: D,H,W must be even (MaxPool3d(2))");
+    MM_REQUIRE(D >= 2 && H >= 2 && W >= 2, "conv3d_l1: D,H,W must be >= 2 (MaxPool3d(2) floors odd extents)");
     MM_REQUIRE(l1_fits(B, D, H, W), "conv3d_l1: more than 2^31 pooled output elements");
     MM_REQUIRE(mode >= 0 && mode <= 3, "conv3d_l1: mode");  /* mode 4 has its own entry point */
     MM_REQUIRE(mode == 0 ? stats != nullptr : out4 != nullptr, "conv3d_l1: stats/out4");
@@ -740,8 +764,9 @@ int mm_conv3d_l1(int mode, const float* x, const void* wimg, const float* bias, 
     L1Args a;
     l1_fill(a, x, wimg, bias, out4, B, D, H, W, train, drop_p, seed, seed_epoch);
     a.dout = (const bf16*)dout; a.sums = sums; a.stats = stats; a.out = (bf16*)out; a.dw = dw_tapmajor; a.dbias = dbias;
-    const int ntiles = l1_tiles(B, D, H, W);
-    const bool full = H % 8 == 0 && W % 32 == 0;
+    const bool vol = mode == 0 || mode == 3;                 // statistics / dense dy: every conv output, the tail too
+    const int ntiles = l1_tiles(B, D, H, W, vol);
+    const bool full = l1_full(D, H, W, vol);
     const int g3 = l1_grid(ntiles, 3), g2 = l1_grid(ntiles, 2);
     switch (mode * 2 + (full ? 1 : 0)) {
         case 0: hipLaunchKernelGGL((conv3d_l1_kernel<0, false>), dim3(g3), dim3(256), 0, st, a); break;
@@ -762,13 +787,13 @@ int mm_conv3d_l1_fwd_winners(const float* x, const void* wimg, const float* bias
                              int B, int D, int H, int W, int train, float drop_p, uint32_t seed,
                              const uint32_t* seed_epoch, hipStream_t st) {
     MM_REQUIRE(x && wimg && out4 && out && arg && B > 0 && D > 0 && H > 0 && W > 0, "conv3d_l1_fwd_winners: null/invalid");
-    MM_REQUIRE(D % 2 == 0 && H % 2 == 0 && W % 2 == 0, "conv3d_l1_fwd_winners: D,H,W must be even (MaxPool3d(2))");
+    MM_REQUIRE(D >= 2 && H >= 2 && W >= 2, "conv3d_l1_fwd_winners: D,H,W must be >= 2 (MaxPool3d(2) floors odd extents)");
     MM_REQUIRE(l1_fits(B, D, H, W), "conv3d_l1_fwd_winners: more than 2^31 pooled output elements");
     L1Args a;
     l1_fill(a, x, wimg, bias, out4, B, D, H, W, train, drop_p, seed, seed_epoch);
     a.out = (bf16*)out; a.arg = (uint8_t*)arg;
-    const int grid = l1_grid(l1_tiles(B, D, H, W), 3);
-    if (H % 8 == 0 && W % 32 == 0) hipLaunchKernelGGL((conv3d_l1_kernel<1, true, true>), dim3(grid), dim3(256), 0, st, a);
+    const int grid = l1_grid(l1_tiles(B, D, H, W, false), 3);
+    if (l1_full(D, H, W, false)) hipLaunchKernelGGL((conv3d_l1_kernel<1, true, true>), dim3(grid), dim3(256), 0, st, a);
     else hipLaunchKernelGGL((conv3d_l1_kernel<1, false, true>), dim3(grid), dim3(256), 0, st, a);
     return mm_check_launch("conv3d_l1_fwd_winners");
 }
@@ -776,14 +801,14 @@ int mm_conv3d_l1_fwd_winners(const float* x, const void* wimg, const float* bias
 int mm_conv3d_l1_fwd_fin(const float* x, const void* wimg, const float* bias, const void* bn_fin_host, void* out, int B, int D,
                          int H, int W, float drop_p, uint32_t seed, const uint32_t* seed_epoch, hipStream_t st) {
     MM_REQUIRE(x && wimg && out && B > 0 && D > 0 && H > 0 && W > 0, "conv3d_l1_fwd_fin: null/invalid");
-    MM_REQUIRE(D % 2 == 0 && H % 2 == 0 && W % 2 == 0, "conv3d_l1_fwd_fin: D,H,W must be even (MaxPool3d(2))");
+    MM_REQUIRE(D >= 2 && H >= 2 && W >= 2, "conv3d_l1_fwd_fin: D,H,W must be >= 2 (MaxPool3d(2) floors odd extents)");
     MM_REQUIRE(l1_fits(B, D, H, W), "conv3d_l1_fwd_fin: more than 2^31 pooled output elements");
     L1Args a;
     l1_fill(a, x, wimg, bias, nullptr, B, D, H, W, 1, drop_p, seed, seed_epoch);
     MM_REQUIRE(bn_fin_from_host(a.fin, bn_fin_host, 32), "conv3d_l1_fwd_fin: incomplete mm_bn_fin_t (null pointer or count < 1)");
     a.out4 = a.fin.out4; a.out = (bf16*)out;
-    const int grid = l1_grid(l1_tiles(B, D, H, W), 3);
-    if (H % 8 == 0 && W % 32 == 0) hipLaunchKernelGGL((conv3d_l1_kernel<1, true, false, true>), dim3(grid), dim3(256), 0, st, a);
+    const int grid = l1_grid(l1_tiles(B, D, H, W, false), 3);
+    if (l1_full(D, H, W, false)) hipLaunchKernelGGL((conv3d_l1_kernel<1, true, false, true>), dim3(grid), dim3(256), 0, st, a);
     else hipLaunchKernelGGL((conv3d_l1_kernel<1, false, false, true>), dim3(grid), dim3(256), 0, st, a);
     return mm_check_launch("conv3d_l1_fwd_fin");
 }
@@ -791,12 +816,12 @@ int mm_conv3d_l1_fwd_fin(const float* x, const void* wimg, const float* bias, co
 int mm_conv3d_l1_gram(const float* x, const void* wimg, const float* bias, float* gram, float* stats, int B, int D, int H,
                       int W, hipStream_t st) {
     MM_REQUIRE(x && wimg && gram && stats && B > 0 && D > 0 && H > 0 && W > 0, "conv3d_l1_gram: null/invalid");
-    MM_REQUIRE(D % 2 == 0 && H % 2 == 0 && W % 2 == 0, "conv3d_l1_gram: D,H,W must be even (MaxPool3d(2))");
+    MM_REQUIRE(D >= 2 && H >= 2 && W >= 2, "conv3d_l1_gram: D,H,W must be >= 2 (MaxPool3d(2) floors odd extents)");
     L1Args a;
     l1_fill(a, x, wimg, bias, nullptr, B, D, H, W, 1, 0.f, 0, nullptr);
     a.gram = gram; a.stats = stats;
-    const int grid = l1_grid(l1_tiles(B, D, H, W), 3);
-    if (H % 8 == 0 && W % 32 == 0) hipLaunchKernelGGL((l1_gram_kernel<true>), dim3(grid), dim3(256), 0, st, a);
+    const int grid = l1_grid(l1_tiles(B, D, H, W, true), 3);
+    if (l1_full(D, H, W, true)) hipLaunchKernelGGL((l1_gram_kernel<true>), dim3(grid), dim3(256), 0, st, a);
     else hipLaunchKernelGGL((l1_gram_kernel<false>), dim3(grid), dim3(256), 0, st, a);
     return mm_check_launch("conv3d_l1_gram");
 }
@@ -820,13 +845,13 @@ int mm_conv3d_l1_bwd(const float* x, const void* wimg, const float* bias, const 
                      hipStream_t st) {
     MM_REQUIRE(x && wimg && out4 && dout && sums_out && a1 && dw && B > 0, "conv3d_l1_bwd: null/invalid");
     MM_REQUIRE(!train || gram, "conv3d_l1_bwd: train-mode BatchNorm needs the Gram workspace of the forward pass");
-    MM_REQUIRE(D % 2 == 0 && H % 2 == 0 && W % 2 == 0, "conv3d_l1_bwd: D,H,W must be even (MaxPool3d(2))");
+    MM_REQUIRE(D >= 2 && H >= 2 && W >= 2, "conv3d_l1_bwd: D,H,W must be >= 2 (MaxPool3d(2) floors odd extents)");
     MM_REQUIRE(l1_fits(B, D, H, W), "conv3d_l1_bwd: more than 2^31 pooled output elements");
     L1Args a;
     l1_fill(a, x, wimg, bias, out4, B, D, H, W, train, drop_p, seed, seed_epoch);
     a.dout = (const bf16*)dout; a.stats = sums_out; a.dw = a1; a.gram = const_cast<float*>(gram);
-    const int grid = l1_grid(l1_tiles(B, D, H, W), L1_BWD_WAVES);
-    if (H % 8 == 0 && W % 32 == 0) hipLaunchKernelGGL((conv3d_l1_kernel<4, true>), dim3(grid), dim3(256), 0, st, a);
+    const int grid = l1_grid(l1_tiles(B, D, H, W, false), L1_BWD_WAVES);      // window extent: no tail pass (file header)
+    if (l1_full(D, H, W, false)) hipLaunchKernelGGL((conv3d_l1_kernel<4, true>), dim3(grid), dim3(256), 0, st, a);
     else hipLaunchKernelGGL((conv3d_l1_kernel<4, false>), dim3(grid), dim3(256), 0, st, a);
     hipLaunchKernelGGL(l1_combine_kernel, dim3(ceil_div(32 * 27 * 16, 256)), dim3(256), 0, st, a1, gram,
                        (const bf16*)wimg, bias, sums_out, out4, dw, dbias, a.inv_count, train);

@@ -117,6 +117,12 @@ class fMRIVolumeEncoder3D(nn.Module):
     with a mean offset up to mu / sigma = 8 (and zero-background, non-negative ones) with bf16 operands; beyond that
     the bf16 input itself stops resolving the signal (one run at mu / sigma = 30 measured a weight-gradient error of
     2.5e-3 rel-L2, tests/test_conv3d_l1_gpu.py).
+
+    Accepted shapes: any D, H, W >= 4 (an axis shorter than 4 raises ``ValueError`` before any launch: the second
+    pool would be empty), odd extents included - MNI152 at 2 mm (91 x 109 x 91) or 3 mm (61 x 73 x 61), EPI with an
+    odd slice count - with torch's semantics and no cropping or padding.  Both MaxPool3d(2) floor odd extents; the tail
+    (the last plane / row / column no pooling window covers) still counts in the train-mode BatchNorm statistics, gets
+    no gradient through the pool, and in training receives BatchNorm's backward term.
     """
 
     def __init__(self, in_channels: int = 1, out_dim: int = 64,

@@ -883,6 +883,16 @@ def conv3d_l1_bn_act(x: torch.Tensor, conv, bn, *, training: bool, drop_p: float
     return out, saved
 
 
+def check_volume_shape(shape):
+    """(B, C, D, H, W) with every spatial extent >= 4: the encoder's two MaxPool3d(2) floor odd extents, as torch, and
+    an axis shorter than 4 leaves the second pool empty (torch raises on it too)."""
+    if len(shape) != 5:
+        raise ValueError(f"fMRIVolumeEncoder3D: expected a (B, C, D, H, W) volume batch, got shape {tuple(shape)}")
+    if min(shape[2:]) < 4:
+        raise ValueError(f"fMRIVolumeEncoder3D: every spatial extent must be >= 4 (two MaxPool3d(2) layers), "
+                         f"got D, H, W = {tuple(shape[2:])}")
+
+
 def _vol_forward_impl(m, x: torch.Tensor, training: bool, need_dgrad: bool, save=None, need_dx: bool = False, winners=None):
     """``save`` (default = training): keep what a backward needs; eval + save = frozen BatchNorm.  ``need_dx``: the
     caller wants d / d volume - layer 1 then runs as an ordinary implicit GEMM on the channel-padded volume (the
@@ -893,8 +903,9 @@ def _vol_forward_impl(m, x: torch.Tensor, training: bool, need_dgrad: bool, save
     p = m.drop_p
     saved = []
     B, C, D, H, W = x.shape
+    check_volume_shape(x.shape)
     x = x.contiguous()
-    if C == 1 and cl[0].out_channels == 32 and D % 2 == 0 and H % 2 == 0 and W % 2 == 0 and not need_dx:
+    if C == 1 and cl[0].out_channels == 32 and not need_dx:
         h, s = conv3d_l1_bn_act(x, cl[0], cl[1], training=training, drop_p=p, save=save, winners=winners)
     else:
         h, s = conv3d_bn_act(pack_volume(x), cl[0], cl[1], pool=True, training=training, drop_p=p,
@@ -913,6 +924,7 @@ def _vol_forward_impl(m, x: torch.Tensor, training: bool, need_dgrad: bool, save
 
 
 def volume_encoder_forward(m, x: torch.Tensor) -> torch.Tensor:
+    check_volume_shape(x.shape)
     _need_gpu(x)
     if m.training or _wants_grad(m, x):
         from .autograd import VolumeEncoderFn
