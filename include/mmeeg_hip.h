@@ -18,12 +18,12 @@
  *   - `void*` tensors are bf16, `float*` fp32; channels-last layouts:
  *     1-D activations [B][T][C], tokens [M][D], volumes [B][D][H][W][C];
  *   - results are BIT-REPRODUCIBLE: no floating-point atomics anywhere.  Per-channel accumulators
- *     written by many workgroups (`stats`, `sums_out`, `dbias`, dgamma/dbeta scratch, `tapsum`, ...) are
+ *     written by many workgroups (`stats`, `sums_out`, `dbias`, dgamma/dbeta scratch, ...) are
  *     ACCUMULATOR WORKSPACES: the caller allocates and ZEROES 32 x n fp32-sized elements (written
  *     "[32][...]" below) and hands them to the consumer untouched; their content is opaque - 16 replicas
  *     of n 64-bit fixed-point sums (integer atomics are order-free; a workgroup adds rint(v * 2^k) into
  *     replica blockIdx % 16; k = 28 for activation statistics, 40 for gradient sums: csrc/common.h).
- *     mm_bn_finalize, the *_bwd_apply passes, mm_conv3d_l1_bwd and mm_transpose_add read them directly;
+ *     mm_bn_finalize, the *_bwd_apply passes and mm_conv3d_l1_bwd read them directly;
  *     everything else goes through mm_acc_reduce / mm_reduce_many (-> fp32).  Weight gradients use
  *     per-workgroup SLOTS (one writer per element) summed in slot order by mm_wgrad_scatter;
  *   - activation codes: 0 none, 1 GELU(erf), 2 ReLU, 3 tanh, 4 sigmoid;
@@ -42,6 +42,10 @@ extern "C" {
 #endif
 
 typedef struct ihipStream_t* hipStream_t;
+
+/* what mm_abi_version() returns: bumped whenever the argument list of an entry point that remains changes
+ * (removing an entry point leaves it as it is) */
+#define MM_ABI_VERSION 5
 
 const char* mm_last_error(void);
 int mm_abi_version(void);
@@ -119,7 +123,7 @@ int mm_add_pe(const float* x, const float* pe, float* out_f32, void* out_bf16, i
 /* debugging: buf[idx] = 100 MHz wall clock, written in stream order (tools/ and bench --stamps) */
 int mm_debug_stamp(void* buf, int idx, hipStream_t stream);
 /* mm_prep_conv_weight for ndesc tensors in one launch per 64 descriptors; desc_host = HOST array
- * of {const float* w; void* w_fwd; void* w_dgrad /*nullable*/; int32 Cout, Cin, k, Cinp, Coutp, 0}
+ * of {const float* w; void* w_fwd; void* w_dgrad (nullable); int32 Cout, Cin, k, Cinp, Coutp, 0}
  * (48 bytes each), copied into the kernel arguments (capturable in a hipGraph) */
 int mm_prep_many(const void* desc_host, int ndesc, hipStream_t stream);
 /* the same, and the launch also zeroes `nzero` floats at `zero` (16-byte aligned, nzero % 4 == 0): a training step's
@@ -318,13 +322,11 @@ int mm_colsum(const void* a_bf16, const float* a_f32, float* out, int M, int N, 
 /* AdaptiveAvgPool1d(1)+Flatten (enhanced_models_v4.py:162-163) on fp32 tokens */
 int mm_meanpool_fwd(const float* x, float* out_f32, void* out_bf16, int B, int L, int D, hipStream_t stream);
 int mm_meanpool_bwd(const float* g, float* dx, int B, int L, int D, hipStream_t stream);
-int mm_cast_bf16(const float* x, void* y, int64_t n, hipStream_t stream);
 /* A training step's inputs into the static buffers a captured step reads, ONE launch: mm_pack_nct_bf16(eeg ->
  * eeg_packed_bf16) [+ an fp32 copy of the EEG batch into eeg_copy, nullable] + an fp32 copy of the fMRI batch
  * (fmri_n floats, a multiple of 4, 16-byte aligned).  The captured step then starts at the first convolution. */
 int mm_stage_inputs(const float* eeg, void* eeg_packed_bf16, float* eeg_copy, int B, int C, int T, int Cp,
                     float* fmri_dst, const float* fmri_src, int64_t fmri_n, hipStream_t stream);
-int mm_cast_f32(const void* x, float* y, int64_t n, hipStream_t stream);
 /* out = bf16( g * dropout_mask * act'(z) ) */
 int mm_act_bwd(const float* g_f32, const void* g_bf16, const void* z, void* out, int64_t n, int act,
                float drop_p, uint32_t seed, const uint32_t* seed_epoch, hipStream_t stream);
@@ -401,16 +403,13 @@ int mm_conv3d_l1_fwd_winners(const float* x, const void* wimg, const float* bias
  * Zeroed accumulator workspaces: sums_out [32][2][32] (also the BatchNorm parameter gradients: dbeta = S1,
  * dgamma = S2), a1 [32][27][32].  dw (PyTorch layout [32][1][3][3][3]) and dbias are ADDED to (dbias only when
  * train == 0; it is identically 0 otherwise).  gram may be NULL when train == 0 (frozen BatchNorm: the two correction
- * terms vanish).  mm_conv3d_l1_tapsum (S alone, by row sums) remains for callers that want it. */
+ * terms vanish). */
 int mm_conv3d_l1_gram(const float* x, const void* wimg, const float* bias, float* gram, float* stats, int B, int D,
                       int H, int W, hipStream_t stream);
-int mm_conv3d_l1_tapsum(const float* x, float* tapsum, int B, int D, int H, int W, hipStream_t stream);
 int mm_conv3d_l1_bwd(const float* x, const void* wimg, const float* bias, const float* out4, const void* dout,
                      float* sums_out, float* a1, const float* gram, float* dw, float* dbias, int B, int D,
                      int H, int W, int train, float drop_p, uint32_t seed, const uint32_t* seed_epoch,
                      hipStream_t stream);
-/* dst[c][r] += fp32(sum over replicas of src[rep][r][c]); src = gradient accumulator workspace [32][R][C], nrep = 16 */
-int mm_transpose_add(const float* src, float* dst, int R, int C, int nrep, hipStream_t stream);
 
 /* ---- small fp32 row kernels (projection bridge, tabular fMRI/conn MLPs) ------
  * y = dropout(act((x W^T + b) * scale + shift)) (scale/shift = folded eval
@@ -446,10 +445,6 @@ int mm_proj_heads_bwd(const float* dz, const float* z, const float* nrm, const f
                       float* db_e, float* dg_e, float* dbe_e, float* dx_f, float* dW_f, float* db_f, float* dg_f,
                       float* dbe_f, int B, int N, float drop_p, uint32_t seed_e, uint32_t seed_f,
                       const uint32_t* seed_epoch, hipStream_t stream);
-/* F.normalize(h, dim=1): z = h / max(||h||, 1e-12)  (extension a-X2) */
-int mm_l2norm_fwd(const float* h, float* z, float* nrm, int B, int N, int ldz, hipStream_t stream);
-int mm_l2norm_bwd(const float* dz, const float* z, const float* nrm, float* dh, int B, int N, int ldz,
-                  hipStream_t stream);
 /* batch-pairwise cosine-similarity matrix + symmetric InfoNCE, bit-reproducible (no float atomics).
  * Embeddings are packed rows [ze (N) | zf (N)]: z_all [Bg][2N] = the all-gathered global batch, this rank's
  * pairs at rows [row0, row0+B).  C[r][j] = ze_r . zf_j; e->f = row softmax of exp(logit_scale) C, f->e =

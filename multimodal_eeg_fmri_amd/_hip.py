@@ -56,12 +56,20 @@ def parse_header(path: str = None) -> Dict[str, str]:
     return sigs
 
 
+def header_abi_version(path: str = None) -> int:
+    """the header's ``MM_ABI_VERSION``: what ``mm_abi_version()`` of a library built from it returns"""
+    m = re.search(r"^#define\s+MM_ABI_VERSION\s+(\d+)", open(path or header_path()).read(), flags=re.M)
+    if m is None:
+        raise ValueError("include/mmeeg_hip.h defines no MM_ABI_VERSION")
+    return int(m.group(1))
+
+
 class HipLibraryError(RuntimeError):
     pass
 
 
 def lib_path() -> str:
-    """in-tree library; MMEEG_HIP_LIB points tools/kbench.py at an ablation build instead"""
+    """in-tree library; MMEEG_HIP_LIB points tools/kbench.py at another build instead (A/B of two libraries)"""
     return os.environ.get("MMEEG_HIP_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), _LIB_NAME)
 
 
@@ -78,6 +86,9 @@ def load():
     lib = ctypes.CDLL(path)
     lib.mm_last_error.restype = ctypes.c_char_p
     lib.mm_abi_version.restype = ctypes.c_int
+    abi, want = lib.mm_abi_version(), header_abi_version()
+    if abi != want:
+        raise HipLibraryError(f"{path} is stale: ABI {abi}, header {want}; rebuild it")
     _SIGS.update(parse_header())
     missing = [n for n in _SIGS if not hasattr(lib, n)]
     if missing:

@@ -885,7 +885,7 @@ class ClipLossFn(torch.autograd.Function):
         need_grad = z.requires_grad or logit_scale.requires_grad
         scal = _empty((4,), _F32, z)
         dz = _empty((B, N2), _F32, z) if need_grad else None
-        ws = _empty((6 * world * B,), _F32, z)
+        ws = _empty((ops.clip_loss_ws_floats(B, world * B),), _F32, z)
         ls = logit_scale.detach().reshape(1).float().contiguous()
         _hip.call("mm_clip_loss_own_rows", z_all, ls, scal, dz, ws, B, world * B, N, rank * B)
         if need_grad:

@@ -70,9 +70,6 @@ class BridgeTrainer(nn.Module):
         self._arena_need = None                       # floats of scratch one step uses (None: clear all)
         self.stamps = None                            # int64[16] device buffer when phase stamps are wanted
         self.force_segments = False                   # rehearsal: run the N > 1 segmented step even at world 1
-        import os
-        # MM_ONE_STREAM=1 (diagnostic): run the fMRI branch on the main stream after the EEG branch
-        self._one_stream = bool(os.environ.get("MM_ONE_STREAM"))
         self._side_stream = None                      # created on first use (the host logic also constructs on CPU)
         self.lr, self.weight_decay, self.grad_clip = lr, weight_decay, grad_clip
         self.betas, self.eps = betas, eps
@@ -99,9 +96,6 @@ class BridgeTrainer(nn.Module):
         else:
             layout = [("eeg encoder + heads", "main", list(self.eeg_encoder.parameters()) + head_params)]
         layout.append(("fmri encoder", "fmri", list(self.fmri_encoder.parameters())))
-        # MM_DP_GROUPS=2 (A/B knob): the round-3 split - the fMRI slice early, everything else after the chain
-        if os.environ.get("MM_DP_GROUPS", "4") == "2" and len(layout) > 2:
-            layout = [("eeg encoder + heads", "main", [p for _, _, ps in layout[:-1] for p in ps]), layout[-1]]
         self.bucket = FlatBucket([p for _, _, ps in layout for p in ps])
         self.groups = []                              # (name, ready point, lo, hi) over the flat bucket, in bucket order
         off = 0
@@ -122,8 +116,6 @@ class BridgeTrainer(nn.Module):
 
     @property
     def _side(self):
-        if self._one_stream:
-            return torch.cuda.current_stream()
         if self._side_stream is None:
             self._side_stream = torch.cuda.Stream()
         return self._side_stream
@@ -250,7 +242,7 @@ class BridgeTrainer(nn.Module):
         N2 = z_all.shape[1]
         B = dz.shape[0]
         ls = self.head.logit_scale.detach().reshape(1)
-        ws = ops._empty((6 * z_all.shape[0],), torch.float32, z_all)
+        ws = ops._empty((ops.clip_loss_ws_floats(B, z_all.shape[0]),), torch.float32, z_all)
         _hip.call("mm_clip_loss_own_rows", z_all, ls, scal, dz, ws, B, z_all.shape[0], N2 // 2, dp.rank(self.group) * B)
         self._stamp(6)
 

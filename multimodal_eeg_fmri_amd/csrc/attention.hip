@@ -21,9 +21,6 @@ namespace {
 
 constexpr int DH = 32;
 constexpr int KCH = 128;                 // keys staged per chunk
-#ifndef ATTN_PIPE_BWD
-#define ATTN_PIPE_BWD 0                  // 1: the backward kernels prefetch the next tile's fragments too (A/B: stand-alone neutral, the STEP 1 % slower)
-#endif
 constexpr int KS = DH + 8;               // K row stride (elements): 80 B
 
 constexpr int VR = DH;                   // row stride (elements) of a row-major tile read through ds_read_b64_tr_b16: 64 B, NO
@@ -339,25 +336,18 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const bf16* __restrict
         }
         __syncthreads();
         if (k0 + KCH < L) load_chunk(k0 + KCH);
-        // software pipeline as in the forward: K / V fragments of tile t + 1 and the transposed K fragments of tile t are
-        // requested before tile t's element-wise work
-        bf16x8 kfr[2], vfr[2];
-        if (ATTN_PIPE_BWD)
-#pragma unroll
-            for (int s = 0; s < 2; ++s) {
-                kfr[s] = *reinterpret_cast<const bf16x8*>(Ks + lr * KS + 16 * s + 8 * lh);
-                vfr[s] = *reinterpret_cast<const bf16x8*>(Vs + lr * KS + 16 * s + 8 * lh);
-            }
+        // the transposed K fragments of tile t are requested before tile t's element-wise work (prefetching tile t + 1's
+        // K / V fragments as well, as the forward does, left the step 1 % slower)
         for (int kt = 0; kt < kn32; kt += 32) {
             f32x16 sacc, dp;
 #pragma unroll
             for (int r = 0; r < 16; ++r) { sacc[r] = 0.f; dp[r] = 0.f; }
-            if (!ATTN_PIPE_BWD)
+            bf16x8 kfr[2], vfr[2];
 #pragma unroll
-                for (int s = 0; s < 2; ++s) {
-                    kfr[s] = *reinterpret_cast<const bf16x8*>(Ks + (kt + lr) * KS + 16 * s + 8 * lh);
-                    vfr[s] = *reinterpret_cast<const bf16x8*>(Vs + (kt + lr) * KS + 16 * s + 8 * lh);
-                }
+            for (int s = 0; s < 2; ++s) {
+                kfr[s] = *reinterpret_cast<const bf16x8*>(Ks + (kt + lr) * KS + 16 * s + 8 * lh);
+                vfr[s] = *reinterpret_cast<const bf16x8*>(Vs + (kt + lr) * KS + 16 * s + 8 * lh);
+            }
 #pragma unroll
             for (int s = 0; s < 2; ++s) {
                 sacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kfr[s], qf[s], sacc, 0, 0, 0);
@@ -366,12 +356,6 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const bf16* __restrict
             bf16x8 ktfr[2];
 #pragma unroll
             for (int s = 0; s < 2; ++s) ktfr[s] = tr_frag32(Kr, kt + 16 * s, lane);
-            if (ATTN_PIPE_BWD && kt + 32 < kn32)
-#pragma unroll
-                for (int s = 0; s < 2; ++s) {
-                    kfr[s] = *reinterpret_cast<const bf16x8*>(Ks + (kt + 32 + lr) * KS + 16 * s + 8 * lh);
-                    vfr[s] = *reinterpret_cast<const bf16x8*>(Vs + (kt + 32 + lr) * KS + 16 * s + 8 * lh);
-                }
             bf16x8 dsf[2];
             bool kp[16];
             if (DROP)
@@ -480,26 +464,19 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(const bf16* __restric
         if (tid < qn32) { Ls[tid] = lreg * 1.4426950408889634f; Dl[tid] = dlreg; }
         __syncthreads();
         if (q0 + QCH < L) load_chunk(q0 + QCH);
-        // software pipeline as in the forward: the Q / dO fragments of tile t + 1 and the transposed fragments of tile t
-        // are requested before tile t's element-wise work
-        bf16x8 qar[2], dar[2];
-        if (ATTN_PIPE_BWD)
-#pragma unroll
-            for (int s = 0; s < 2; ++s) {
-                qar[s] = *reinterpret_cast<const bf16x8*>(Qs + lr * KS + 16 * s + 8 * lh);
-                dar[s] = *reinterpret_cast<const bf16x8*>(Ds + lr * KS + 16 * s + 8 * lh);
-            }
+        // the transposed fragments of tile t are requested before tile t's element-wise work (prefetching tile t + 1's
+        // Q / dO fragments as well, as the forward does, left the step 1 % slower)
         for (int qt = 0; qt < qn32; qt += 32) {
             // S[q][key] and dP[q][key]: rows = q (registers), column = this lane's key
             f32x16 sacc, dp;
 #pragma unroll
             for (int r = 0; r < 16; ++r) { sacc[r] = 0.f; dp[r] = 0.f; }
-            if (!ATTN_PIPE_BWD)
+            bf16x8 qar[2], dar[2];
 #pragma unroll
-                for (int s = 0; s < 2; ++s) {
-                    qar[s] = *reinterpret_cast<const bf16x8*>(Qs + (qt + lr) * KS + 16 * s + 8 * lh);
-                    dar[s] = *reinterpret_cast<const bf16x8*>(Ds + (qt + lr) * KS + 16 * s + 8 * lh);
-                }
+            for (int s = 0; s < 2; ++s) {
+                qar[s] = *reinterpret_cast<const bf16x8*>(Qs + (qt + lr) * KS + 16 * s + 8 * lh);
+                dar[s] = *reinterpret_cast<const bf16x8*>(Ds + (qt + lr) * KS + 16 * s + 8 * lh);
+            }
 #pragma unroll
             for (int s = 0; s < 2; ++s) {
                 sacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qar[s], kf[s], sacc, 0, 0, 0);
@@ -511,12 +488,6 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(const bf16* __restric
                 dtar[s] = tr_frag32(Dr, qt + 16 * s, lane);
                 qtar[s] = tr_frag32(Qr, qt + 16 * s, lane);
             }
-            if (ATTN_PIPE_BWD && qt + 32 < qn32)
-#pragma unroll
-                for (int s = 0; s < 2; ++s) {
-                    qar[s] = *reinterpret_cast<const bf16x8*>(Qs + (qt + 32 + lr) * KS + 16 * s + 8 * lh);
-                    dar[s] = *reinterpret_cast<const bf16x8*>(Ds + (qt + 32 + lr) * KS + 16 * s + 8 * lh);
-                }
             bf16x8 pf[2], dsf[2];
             bool kp[16];
             if (DROP)

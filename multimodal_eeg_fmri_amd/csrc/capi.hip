@@ -1,5 +1,6 @@
 // Error reporting + version for the C-ABI library.
 #include "common.h"
+#include "mmeeg_hip.h"
 #include <stdarg.h>
 #include <stdio.h>
 
@@ -21,5 +22,5 @@ int mm_check_launch(const char* what) {
 
 extern "C" {
 const char* mm_last_error(void) { return g_err; }
-int mm_abi_version(void) { return 5; }
+int mm_abi_version(void) { return MM_ABI_VERSION; }
 }

@@ -13,14 +13,14 @@
 //            sum_v y_n   = w_n . S + M b_n                       (S[t] = G[t][ones], M = G[ones][ones])
 //            sum_v y_n^2 = w_n^T G w_n + 2 b_n w_n . S + M b_n^2     -> BatchNorm statistics (formed per workgroup: linear in G)
 //            A3[t][n] = sum_v xcol[v][t] xhat[v][n] = rstd_n ((G w_n)[t] + (b_n - mean_n) S[t])   (backward)
-//          It replaces the statistics pass (mode 0: a full recompute with a per-channel epilogue) AND the tap-sum
-//          kernel, and takes the second MFMA product out of the backward.
+//          It replaces the statistics pass (mode 0: a full recompute with a per-channel epilogue) and the tap sums, and
+//          takes the second MFMA product out of the backward.
 //   mode 1 apply        : BN -> GELU -> 2x2x2 max -> dropout -> bf16
 // Training backward (one recompute pass, mode 4): BatchNorm's backward is linear in S1 = sum dz, S2 = sum dz xhat, so
 //   dW = sc (A1 - c0 S - c1 A3),  A1 = x^T dz,  c0 = S1 / M, c1 = S2 / M: the pass yields S1, S2 and A1 (one MFMA
 //   product with the sparse dz fragments), l1_combine_kernel finishes from the Gram workspace.
 // Kept for callers of the C ABI / frozen-weight paths: mode 0 (statistics by recompute), mode 2 (S1, S2 only),
-// mode 3 (two-pass weight gradient), l1_tapsum_kernel.
+// mode 3 (two-pass weight gradient).
 //
 // One wave owns a 2 x 8 x 8 block of conv outputs (= 1 x 4 x 4 pooled voxels) x 32 channels: all 8 members of
 // every pooling window sit in the same lane.  A workgroup (4 waves) walks tiles of 2 x 8 x 32 voxels persistently
@@ -41,20 +41,11 @@
 // the Gram kernel must cover the whole volume extent.  Even extents have an empty tail: both extents coincide.
 #include "common.h"
 
-// ablation builds (tools/abl_stream.sh with ABL_FILE=conv3d_l1 ABL_MACRO=L1_ABL; product = 0; profiles/r04_l1_ablation.txt):
-// 1 wave-uniform branch (ballot) in front of the all-negative-window path, 2 fmaxf / fminf trees instead of v_max3 / v_min3,
-// 4 dz fragments built member by member, 8 halo of tile i + 1 prefetched into registers during tile i.
-// Measured on one box, alternating: 1 and 8 make the backward 0.7 / 1.5 us SLOWER (and are off), 2 and 4 are what the
-// product does NOT do (they cost 0.3 / 1.3 us).
-#ifndef L1_BWD_WAVES
-#define L1_BWD_WAVES 2          // workgroups per CU (= waves per SIMD) of the backward kernels (A/B builds: 3)
-#endif
-#ifndef L1_ABL
-#define L1_ABL 0
-#endif
-
 namespace {
 
+// workgroups per CU (= waves per SIMD) of the backward kernels: three were -3.6 % for the kernel alone and nothing in the
+// step (A/B of commit 2b0bced; the other variants measured against this kernel: profiles/r04_l1_ablation.txt)
+constexpr int L1_BWD_WAVES = 2;
 constexpr int HP = 36;                 // halo row pitch (34 used)
 constexpr int HROWS1 = 4 * 10;         // (2+2) depth x (8+2) height rows
 constexpr int HSZ = HROWS1 * HP;
@@ -99,11 +90,9 @@ __device__ __forceinline__ float min3f(float a, float b, float c) {
     return r;
 }
 __device__ __forceinline__ float max8f(const float (&z)[8]) {
-    if (L1_ABL & 2) return fmaxf(fmaxf(fmaxf(z[0], z[1]), fmaxf(z[2], z[3])), fmaxf(fmaxf(z[4], z[5]), fmaxf(z[6], z[7])));
     return max3f(max3f(z[0], z[1], z[2]), max3f(z[3], z[4], z[5]), max3f(z[6], z[7], z[7]));
 }
 __device__ __forceinline__ float min8f(const float (&z)[8]) {
-    if (L1_ABL & 2) return fminf(fminf(fminf(z[0], z[1]), fminf(z[2], z[3])), fminf(fminf(z[4], z[5]), fminf(z[6], z[7])));
     return min3f(min3f(z[0], z[1], z[2]), min3f(z[3], z[4], z[5]), min3f(z[6], z[7], z[7]));
 }
 
@@ -223,13 +212,9 @@ __global__ __launch_bounds__(256, MODE <= 1 ? 3 : L1_BWD_WAVES) void conv3d_l1_k
         const TileCoord tc = tile_coord(tile, tw, th, td);
         const int b = tc.b, d0 = tc.d0, h0 = tc.h0, w0 = tc.w0;
         unsigned short* hb = halo[buf];
-        if (!(L1_ABL & 8) && tile != (int)blockIdx.x) halo_load(hv, tile_ptr(a.x, tc, a.D, a.H, a.W), plan, d0, h0, w0, a.D, a.H, a.W);
+        if (tile != (int)blockIdx.x) halo_load(hv, tile_ptr(a.x, tc, a.D, a.H, a.W), plan, d0, h0, w0, a.D, a.H, a.W);
         halo_store(hb, plan, hv);
         __syncthreads();                                    // (the other buffer's readers passed the previous barrier)
-        if ((L1_ABL & 8) && tile + (int)gridDim.x < ntiles) {    // ablation: next tile's halo in flight during this tile's compute
-            const TileCoord c = tile_coord(tile + gridDim.x, tw, th, td);
-            halo_load(hv, tile_ptr(a.x, c, a.D, a.H, a.W), plan, c.d0, c.h0, c.w0, a.D, a.H, a.W);
-        }
         const int wbase = 8 * wave;                         // this wave's w-block inside the tile
         // ---- conv: acc[i] (rows m = 32 i + ..., voxel = (m>>6, (m>>3)&7, m&7))
         f32x16 acc[4];
@@ -291,16 +276,14 @@ __global__ __launch_bounds__(256, MODE <= 1 ? 3 : L1_BWD_WAVES) void conv3d_l1_k
                     // to find the winner, the forward one.
                     // The winner is the FIRST member that equals the extreme value (as PyTorch's max-pool).
                     // (A wave-uniform branch in front of the all-negative case - no lane of the wave in ~78 % of the windows -
-                    // measured 0.7 us slower than letting the compiler predicate it: L1_ABL bit 1.)
+                    // measured 0.7 us slower than letting the compiler predicate it.)
                     float zsel = max8f(z);
                     float best = MODE == 1 ? gelu_erf(zsel) : 0.f;
-                    if (!(L1_ABL & 1) || __builtin_amdgcn_ballot_w64(zsel < 0.f) != 0) {
-                        if (zsel < 0.f) {
-                            const float zmin = min8f(z);
-                            if (MODE != 1) best = gelu_erf(zsel);
-                            const float amin = gelu_erf(zmin);
-                            if (amin > best) { best = amin; zsel = zmin; }
-                        }
+                    if (zsel < 0.f) {
+                        const float zmin = min8f(z);
+                        if (MODE != 1) best = gelu_erf(zsel);
+                        const float amin = gelu_erf(zmin);
+                        if (amin > best) { best = amin; zsel = zmin; }
                     }
                     const uint32_t oidx = obase + ((uint32_t)(2 * ip + ra) * Wo + rb) * 32;
                     if (MODE == 1) {
@@ -338,21 +321,12 @@ __global__ __launch_bounds__(256, MODE <= 1 ? 3 : L1_BWD_WAVES) void conv3d_l1_k
                         // the window's 8 members are 4 packed bf16 pairs of the dz fragments - (dd, hh) -> register rb + 2 hh
                         // of fragment [dd][ra], low / high half = ww - and exactly one member is non-zero (a window that
                         // is not in the volume has g = 0): one converted value, shifted to its half, selected into its pair
-                        if (L1_ABL & 4) {
+                        const bf16 db = (bf16)dzs;
+                        acc3 += (float)db;
+                        const uint32_t pairval = (uint32_t)(*reinterpret_cast<const unsigned short*>(&db)) << ((js & 1) << 4);
+                        const int jp = js >> 1;
 #pragma unroll
-                            for (int j = 0; j < 8; ++j) {
-                                const int ti = ip + 2 * (j >> 2), r = r0 + 4 * ((j >> 1) & 1) + (j & 1);
-                                dyf[ti >> 1][r >> 3].v[r & 7] = (bf16)(js == j ? dzs : 0.f);
-                            }
-                            acc3 += (float)(bf16)dzs;
-                        } else {
-                            const bf16 db = (bf16)dzs;
-                            acc3 += (float)db;
-                            const uint32_t pairval = (uint32_t)(*reinterpret_cast<const unsigned short*>(&db)) << ((js & 1) << 4);
-                            const int jp = js >> 1;
-#pragma unroll
-                            for (int k = 0; k < 4; ++k) dyf[k >> 1][ra].u[rb + 2 * (k & 1)] = jp == k ? pairval : 0u;
-                        }
+                        for (int k = 0; k < 4; ++k) dyf[k >> 1][ra].u[rb + 2 * (k & 1)] = jp == k ? pairval : 0u;
                     } else if (MODE == 3) {
 #pragma unroll
                         for (int j = 0; j < 8; ++j) {
@@ -487,13 +461,9 @@ __global__ __launch_bounds__(256, 3) void l1_gram_kernel(L1Args a) {
     for (; tile < ntiles; tile += gridDim.x, buf ^= 1) {
         const TileCoord tc = tile_coord(tile, tw, th, td);
         unsigned short* hb = halo[buf];
-        if (!(L1_ABL & 8) && tile != (int)blockIdx.x) halo_load(hv, tile_ptr(a.x, tc, a.D, a.H, a.W), plan, tc.d0, tc.h0, tc.w0, a.D, a.H, a.W);
+        if (tile != (int)blockIdx.x) halo_load(hv, tile_ptr(a.x, tc, a.D, a.H, a.W), plan, tc.d0, tc.h0, tc.w0, a.D, a.H, a.W);
         halo_store(hb, plan, hv);
         __syncthreads();
-        if ((L1_ABL & 8) && tile + (int)gridDim.x < ntiles) {
-            const TileCoord c = tile_coord(tile + gridDim.x, tw, th, td);
-            halo_load(hv, tile_ptr(a.x, c, a.D, a.H, a.W), plan, c.d0, c.h0, c.w0, a.D, a.H, a.W);
-        }
         const int wbase = 8 * wave;
 #pragma unroll
         for (int s = 0; s < 8; ++s) {
@@ -572,95 +542,6 @@ __global__ __launch_bounds__(256, 3) void l1_gram_kernel(L1Args a) {
     }
 }
 
-// S[tap] = sum over output voxels v of x~[v + tap - 1] (zero padded, bf16-rounded as the conv sees it):
-// input voxel u = (d, h, w) feeds tap (kd, kh, kw) iff u - (k - 1) is inside the volume, i.e. the
-// indicator factorises per axis.  Per (b, d, h) row: three row sums (all w, all but the last, all but
-// the first) and nine conditional adds of them - 27 adds per ROW, not per voxel.  (The training path takes S from the
-// Gram matrix; this kernel serves callers of mm_conv3d_l1_tapsum.)
-// W % 4 == 0: eight lanes share a row (one float4 each per 32 voxels: a wave reads 8 rows x 128 contiguous bytes
-// per instruction; a thread per row read 64 different cache lines per instruction and took 12 us for 4 MB), the
-// row sum is a 3-step shuffle and lane 0 of the group keeps the tap sums.  Otherwise: a thread per row.
-__global__ __launch_bounds__(256) void l1_tapsum_kernel(const float* __restrict__ x, float* __restrict__ out /* [REPL][32] */,
-                                                        int B, int D, int H, int W) {
-    const size_t nrows = (size_t)B * D * H;
-    float s[27];
-#pragma unroll
-    for (int t = 0; t < 27; ++t) s[t] = 0.f;
-    auto add_row = [&](size_t row, float all, float first, float last) __attribute__((always_inline)) {
-        const unsigned rq = (unsigned)row / (unsigned)H;            // 32-bit divisions: rows = B D H < 2^31 (host-checked)
-        const int h = (int)((unsigned)row - rq * (unsigned)H), d = (int)(rq % (unsigned)D);
-        const float rw[3] = {all - last, all, all - first};         // kw = 0, 1, 2
-#pragma unroll
-        for (int kd = 0; kd < 3; ++kd) {
-            const bool okd = (kd == 0) ? d <= D - 2 : (kd == 2 ? d >= 1 : true);
-#pragma unroll
-            for (int kh = 0; kh < 3; ++kh) {
-                const bool okh = (kh == 0) ? h <= H - 2 : (kh == 2 ? h >= 1 : true);
-                if (okd && okh)
-#pragma unroll
-                    for (int kw = 0; kw < 3; ++kw) s[(kd * 3 + kh) * 3 + kw] += rw[kw];
-            }
-        }
-    };
-    if ((W & 3) == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0) {
-        const int sub = threadIdx.x & 7, W4 = W >> 2;
-        const size_t g0 = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 3, gstep = ((size_t)gridDim.x * blockDim.x) >> 3;
-        const size_t nloop = (nrows + gstep - 1) / gstep;           // same trip count for the 8 lanes of a group AND the wave (shuffles)
-        for (size_t it = 0; it < nloop; ++it) {
-            const size_t row = g0 + it * gstep;
-            const bool ok = row < nrows;
-            const float4* xr = reinterpret_cast<const float4*>(x + (ok ? row : 0) * W);
-            float part = 0.f, first = 0.f, last = 0.f;
-            for (int w4 = sub; w4 < W4; w4 += 8) {
-                const float4 v = xr[w4];
-                const float a = (float)(bf16)v.x, b = (float)(bf16)v.y, c = (float)(bf16)v.z, e = (float)(bf16)v.w;
-                part += (a + b) + (c + e);
-                if (w4 == 0) first = a;
-                if (w4 == W4 - 1) last = e;
-            }
-#pragma unroll
-            for (int o = 1; o < 8; o <<= 1) {
-                part += __shfl_xor(part, o, 64);
-                first += __shfl_xor(first, o, 64);                  // one owner each, zeros elsewhere
-                last += __shfl_xor(last, o, 64);
-            }
-            if (ok && sub == 0) add_row(row, part, first, last);
-        }
-    } else {
-        for (size_t row = (size_t)blockIdx.x * blockDim.x + threadIdx.x; row < nrows; row += (size_t)gridDim.x * blockDim.x) {
-            const float* xr = x + row * W;
-            float all = 0.f;
-            for (int w = 0; w < W; ++w) all += (float)(bf16)xr[w];
-            add_row(row, all, (float)(bf16)xr[0], (float)(bf16)xr[W - 1]);
-        }
-    }
-    // block sum of the 27 x (32 or 256) partials through LDS in a fixed order (27 wave_sum()s were 162 dependent
-    // ds_bpermute round trips per wave: ~9 us, the whole kernel, whatever the grid)
-    const bool fast = (W & 3) == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0;
-    const int holders = fast ? 32 : 256;               // fast path: lane 0 of every 8-lane group holds the sums
-    __shared__ float red[256 * 28];
-    __shared__ float red2[8][28];
-    if (!fast || (threadIdx.x & 7) == 0) {
-        float* dst = red + (fast ? threadIdx.x >> 3 : threadIdx.x) * 28;
-#pragma unroll
-        for (int t = 0; t < 27; ++t) dst[t] = s[t];
-    }
-    __syncthreads();
-    if (threadIdx.x < 27 * 8) {
-        const int tap = threadIdx.x % 27, part = threadIdx.x / 27, per = holders / 8;
-        float a = 0.f;
-        for (int i = 0; i < per; ++i) a += red[(part * per + i) * 28 + tap];
-        red2[part][tap] = a;
-    }
-    __syncthreads();
-    if (threadIdx.x < 27) {
-        float a = 0.f;
-#pragma unroll
-        for (int part = 0; part < 8; ++part) a += red2[part][threadIdx.x];
-        acc_add<MM_ACC_STAT>(acc_rep(out, blockIdx.x % MM_ACC_REPL, 32) + threadIdx.x, a);
-    }
-}
-
 // dW[n][tap] += sc (A1 - c0 S - c1 A3);  dbias[n] += train ? 0 : sc S1, with S[tap] = G[tap][27] and
 // A3[tap][n] = rstd_n ((G w_n)[tap] + (b_n - mean_n) S[tap]) from the Gram accumulator workspace of the forward pass
 // (upper triangle, MM_ACC_REPL replicas); a1 / sums: fixed-point accumulators x MM_ACC_REPL.
@@ -709,15 +590,6 @@ __global__ void l1_combine_kernel(const float* __restrict__ a1, const float* __r
     }
     dw[i] += sc * (A1 - corr);
     if (tap == 0 && dbias && !train) dbias[n] += sc * s0;      // train: sum dy == 0 identically
-}
-
-// dst[c][r] += sum_rep acc[rep][r][c]   (acc: MM_ACC_REPL fixed-point gradient accumulators)
-__global__ void transpose_add_kernel(const float* __restrict__ src, float* __restrict__ dst, int R, int C) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < R * C) {
-        const int r = i / C, c = i % C;
-        dst[(size_t)c * R + r] += acc_val<MM_ACC_GRAD>(acc_sum(src, (size_t)R * C, i));
-    }
 }
 
 inline uint32_t thresh_l1(float p) { return p > 0.f ? (uint32_t)((double)p * 4294967296.0) : 0u; }
@@ -826,19 +698,6 @@ int mm_conv3d_l1_gram(const float* x, const void* wimg, const float* bias, float
     return mm_check_launch("conv3d_l1_gram");
 }
 
-static int l1_tapsum_grid(int B, int D, int H, int W) {
-    const long rows = (long)B * D * H, threads = (W & 3) == 0 ? rows * 8 : rows;
-    const long g = (threads + 255) / 256;
-    return (int)(g < 1024 ? g : 1024);
-}
-
-int mm_conv3d_l1_tapsum(const float* x, float* tapsum, int B, int D, int H, int W, hipStream_t st) {
-    MM_REQUIRE(x && tapsum && B > 0 && D > 0 && H > 0 && W > 0, "conv3d_l1_tapsum: null/invalid");
-    hipLaunchKernelGGL(l1_tapsum_kernel, dim3(l1_tapsum_grid(B, D, H, W)), dim3(256), 0, st,
-                       x, tapsum, B, D, H, W);
-    return mm_check_launch("conv3d_l1_tapsum");
-}
-
 int mm_conv3d_l1_bwd(const float* x, const void* wimg, const float* bias, const float* out4, const void* dout,
                      float* sums_out, float* a1, const float* gram, float* dw, float* dbias, int B,
                      int D, int H, int W, int train, float drop_p, uint32_t seed, const uint32_t* seed_epoch,
@@ -856,13 +715,6 @@ int mm_conv3d_l1_bwd(const float* x, const void* wimg, const float* bias, const 
     hipLaunchKernelGGL(l1_combine_kernel, dim3(ceil_div(32 * 27 * 16, 256)), dim3(256), 0, st, a1, gram,
                        (const bf16*)wimg, bias, sums_out, out4, dw, dbias, a.inv_count, train);
     return mm_check_launch("conv3d_l1_bwd");
-}
-
-int mm_transpose_add(const float* src, float* dst, int R, int C, int nrep, hipStream_t st) {
-    MM_REQUIRE(src && dst && R > 0 && C > 0, "transpose_add: null");
-    MM_REQUIRE(nrep == MM_ACC_REPL, "transpose_add: src is an accumulator workspace of %d replicas", MM_ACC_REPL);
-    hipLaunchKernelGGL(transpose_add_kernel, dim3(ceil_div(R * C, 256)), dim3(256), 0, st, src, dst, R, C);
-    return mm_check_launch("transpose_add");
 }
 
 }  // extern "C"

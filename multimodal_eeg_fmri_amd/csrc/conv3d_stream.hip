@@ -32,10 +32,6 @@
 //    pipeline puts them (one unit ahead); the B loads are ordinary loads, the compiler counts vmcnt.
 #include "conv3d_args.h"
 
-#ifndef STREAM_ABL      // diagnostic builds (tools/abl_stream.sh): 1 no B loads in the loop, 2 no MFMAs, 4 no fragment reads
-#define STREAM_ABL 0
-#endif
-
 namespace {
 
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
@@ -80,13 +76,6 @@ __global__ __launch_bounds__(256) void conv3d_stream_kernel(Conv3dArgs a) {
     using C = StreamCfg<CIN, COUT, NW_, DEPTH_>;
     constexpr int KS = C::KS, NW = C::NW, WK = C::WK, NU = C::NU, NUW = C::NUW, DEPTH = C::DEPTH, OWN = C::OWN;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-#ifdef STREAM_STAMPS
-    const long long t_begin = __builtin_readcyclecounter(), r_begin = wall_clock64();
-    float tl[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-#define ST_TL(i) tl[i] = (float)(__builtin_readcyclecounter() - t_begin);
-#else
-#define ST_TL(i)
-#endif
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wn = wave % NW, kg = wave / NW;
@@ -187,11 +176,8 @@ __global__ __launch_bounds__(256) void conv3d_stream_kernel(Conv3dArgs a) {
         return ((kh & 1) ? lane_a1 : lane_a0) + ks * HKS + tap_off(tap) +
                ((i >> 2) * SDP + (4 * ((i >> 1) & 1)) * SWP + 4 * (i & 1)) * SROWB;
     };
-
-    ST_TL(0)
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();                              // the halo (all waves' writes) is in LDS
-    ST_TL(1)
 
     u32x4 fa[2][8];                                            // A fragments: unit u lives in fa[u & 1], no copies
 #pragma unroll
@@ -209,10 +195,10 @@ __global__ __launch_bounds__(256) void conv3d_stream_kernel(Conv3dArgs a) {
         u32x4 cb[2];
 #pragma unroll
         for (int j = 0; j < 2; ++j) cb[j] = bq[u % DEPTH][j];
-        if (u + DEPTH < NUW && !(STREAM_ABL & 1)) load_b(u + DEPTH, bq[u % DEPTH]);
+        if (u + DEPTH < NUW) load_b(u + DEPTH, bq[u % DEPTH]);
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
-            if (u + 1 < NUW && !(STREAM_ABL & 4)) {
+            if (u + 1 < NUW) {
                 nxt[i] = lds_read128(a_addr(u + 1, i));
                 asm volatile("s_waitcnt lgkmcnt(8)" : "+v"(cur[i]));
             } else {
@@ -228,7 +214,7 @@ __global__ __launch_bounds__(256) void conv3d_stream_kernel(Conv3dArgs a) {
                 }
             }
             __builtin_amdgcn_sched_barrier(0);
-            if (valid && !(STREAM_ABL & 2)) {
+            if (valid) {
 #pragma unroll
                 for (int j = 0; j < 2; ++j)
                     acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, cur[i]), __builtin_bit_cast(bf16x8, cb[j]),
@@ -237,8 +223,6 @@ __global__ __launch_bounds__(256) void conv3d_stream_kernel(Conv3dArgs a) {
             __builtin_amdgcn_sched_barrier(0);
         }
     }
-
-    ST_TL(2)
     // ---- K-groups: every wave parks its partial wave tile, wave (wn, kg) then owns row tiles i = kg OWN .. + OWN - 1
     f32x4 res[OWN][2];
     if constexpr (WK == 1) {
@@ -264,8 +248,6 @@ __global__ __launch_bounds__(256) void conv3d_stream_kernel(Conv3dArgs a) {
                 res[o][j] = t4;
             }
     }
-
-    ST_TL(3)
     // ---- epilogue: register r of lane (lc, lg) in row tile i is face i >> 2, voxel (h, w) = (4 ((i >> 1) & 1) + lg,
     // 4 (i & 1) + r), channels n0 and n0 + 1
     float s1[2] = {0.f, 0.f}, s2[2] = {0.f, 0.f};
@@ -289,16 +271,6 @@ __global__ __launch_bounds__(256) void conv3d_stream_kernel(Conv3dArgs a) {
             }
         }
     }
-    ST_TL(4)
-#ifdef STREAM_STAMPS
-    if (a.stats && tid == 0 && blockIdx.y == 0) {
-        float* o = a.stats + MM_REPL * 2 * COUT + blockIdx.x * 8;
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        o[0] = tl[0]; o[1] = tl[1]; o[2] = tl[2]; o[3] = tl[3]; o[4] = tl[4];
-        o[5] = (float)(__builtin_readcyclecounter() - t_begin);
-        o[6] = (float)(r_begin & 0xFFFFFF); o[7] = (float)(wall_clock64() & 0xFFFFFF);
-    }
-#endif
     if (a.stats) {
         float* sstat = reinterpret_cast<float*>(smem + C::S_OFF);       // [wave][2][32]
 #pragma unroll

@@ -89,13 +89,6 @@ static_assert(18 % (W3_LA + 1) == 0 && 2 * W3_LA + 2 <= 15, "fragment ring");
 
 __global__ __launch_bounds__(256) void conv3d_wgrad_kernel(Wgrad3dArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-#ifdef STREAM_STAMPS       // diagnostic builds (tools/abl_stream.sh s0): cycle stamps into the first floats of the slot
-    const long long t_begin = __builtin_readcyclecounter();
-    float tl[4] = {0.f, 0.f, 0.f, 0.f};
-#define W3_TL(i) tl[i] = (float)(__builtin_readcyclecounter() - t_begin);
-#else
-#define W3_TL(i)
-#endif
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int kd = blockIdx.z % 3, cblk = blockIdx.z / 3;
@@ -215,7 +208,6 @@ __global__ __launch_bounds__(256) void conv3d_wgrad_kernel(Wgrad3dArgs a) {
     // reads it, and that every wave has left stage st - 1, whose buffer the W3_NP DMA instructions of stage st + W3_ST - 1 -
     // spread over the gaps of units 10 .. 15 - then refill.  (With the barrier and the fill in front of each stage and the
     // pipeline restarted behind it a stage took 1 640 cycles for 576 of MFMA work.)
-    W3_TL(0)
     asm volatile("s_waitcnt vmcnt(%0)" : : "n"((W3_ST - 2) * W3_NP) : "memory");
     __builtin_amdgcn_s_barrier();                          // stage 0 is in LDS
     Frag af[2], bfq[W3_LA + 1];
@@ -268,7 +260,6 @@ __global__ __launch_bounds__(256) void conv3d_wgrad_kernel(Wgrad3dArgs a) {
         pya = pya_n; pxa = pxa_n; pxb = pxb_n;
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     // the look-ahead past the last stage
-    W3_TL(1)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");         // the ring's last (out-of-range) fills target this workgroup's LDS
     if (do_bias) {
         bsum += __shfl_xor(bsum, 32, 64);
@@ -317,14 +308,6 @@ __global__ __launch_bounds__(256) void conv3d_wgrad_kernel(Wgrad3dArgs a) {
             }
         }
     }
-    W3_TL(2)
-#ifdef STREAM_STAMPS
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (tid == 0 && kd == 2) {
-        float* o = a.dw + (size_t)blockIdx.x * a.rep_stride;
-        o[0] = tl[0]; o[1] = tl[1]; o[2] = tl[2]; o[3] = (float)(__builtin_readcyclecounter() - t_begin);
-    }
-#endif
 }
 
 // faces per workgroup: one workgroup per CU (96 KB of LDS ring), every one at least 2 W3_ST faces deep so that the ring
@@ -332,9 +315,8 @@ __global__ __launch_bounds__(256) void conv3d_wgrad_kernel(Wgrad3dArgs a) {
 int wgrad3d_tiles_per_wg(int B, int D, int H, int W, int Cin, int Cout) {
     const int tiles_total = B * D * ceil_div(H, 8) * ceil_div(W, 8);
     const int par = ceil_div(Cout, 32) * 3 * ceil_div(Cin, 32);
-    // workgroups (= CUs: 96 KB of LDS each) to spread over.  MM_W3_CUS (A/B runs): fewer than 256 leaves whole CUs to the kernels of
-    // the other stream, which cannot co-reside with a 96 KB workgroup
-    static const int cus = getenv("MM_W3_CUS") ? atoi(getenv("MM_W3_CUS")) : 256;
+    // workgroups (= CUs: 96 KB of LDS each) to spread over (192 / 128, leaving whole CUs to the other stream: within noise)
+    constexpr int cus = 256;
     int chunks = cus / par;
     if (chunks > tiles_total / (2 * W3_ST)) chunks = tiles_total / (2 * W3_ST);
     if (chunks < 1) chunks = 1;

@@ -37,11 +37,7 @@
 //    neighbouring tiles' halos are fetched into that XCD's L2 once (PMC: 1.06x the algorithmic bytes; round 1:
 //    2.0x).  Placement is a speed assumption only; any placement computes the same result.
 #include "conv3d_args.h"
-#ifdef WRES_ASM_INC                              // ablation builds (tools/abl_build.sh) substitute a variant stream
-#include WRES_ASM_INC
-#else
 #include "conv3d_wres_asm.inc"
-#endif
 
 #include <mutex>
 
@@ -68,20 +64,6 @@ struct Tile { int b, d, h0, w0; };               // d = tile index along the dep
 
 __global__ __launch_bounds__(256) void conv3d_wres_kernel(Conv3dArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-#ifdef WRES_STAMPS      // diagnostic builds only (tools/abl_build.sh s*): shader-clock timeline of the workgroup
-    const long long t_begin = __builtin_readcyclecounter(), r_begin = wall_clock64();
-    long long kcyc = 0;
-    float tl[12] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-#define WR_TL(i) tl[i] = (float)(__builtin_readcyclecounter() - t_begin);
-#define WR_T0 const long long t0_ = __builtin_readcyclecounter();
-#define WR_T1 kcyc += __builtin_readcyclecounter() - t0_;
-#define WR_TLK if (tl[4] == 0.f) { WR_TL(4) } else if (tl[5] == 0.f) { WR_TL(5) }
-#else
-#define WR_TL(i)
-#define WR_T0
-#define WR_T1
-#define WR_TLK
-#endif
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);     // wave-uniform: tile addressing stays in SGPRs
     const int lc = lane & 15, lg = lane >> 4;                       // MFMA lane = (row / column 0-15, group 0-3)
@@ -136,7 +118,6 @@ __global__ __launch_bounds__(256) void conv3d_wres_kernel(Conv3dArgs a) {
         }
         asm volatile(WRES_INIT : : [g0] "v"(goffp[0]), [g1] "v"(goffp[1]), [s0] "v"(selp[0]), [s1] "v"(selp[1]) : WRES_CLOBBERS);
     }
-    WR_TL(2)
     auto range_mask = [](int lo_, int hi_, int n) __attribute__((always_inline)) {      // bits [max(lo,0), min(hi,n))
         lo_ = lo_ < 0 ? 0 : lo_;
         hi_ = hi_ > n ? n : hi_;
@@ -166,7 +147,6 @@ __global__ __launch_bounds__(256) void conv3d_wres_kernel(Conv3dArgs a) {
         asm volatile(WRES_PREFETCH : : [off0] "s"(pf.off0), [planeb] "s"(planeb), [pvalid] "s"(pf.pvalid), [mhw] "s"(pf.mhw),
                      [rsrc] "s"(xrsrc) : "memory", WRES_CLOBBERS);
     }
-    WR_TL(0)
     // ---- weights: global -> LDS by LDS-DMA.  LDS image [tap][rho][slot] x 16 B; a DMA writes wave-uniform base +
     // 16 * lane, so wave w, instruction k covers tap k, rows rho = 16 w + (lane >> 2), slot = lane & 3.  LDS row rho
     // holds output channel n = 4 (rho & 15) + (rho >> 4) (column tile j = rho >> 4, lane column c = rho & 15 <->
@@ -192,7 +172,6 @@ __global__ __launch_bounds__(256) void conv3d_wres_kernel(Conv3dArgs a) {
         }
         wsrc9 = wlane + 9 * CIN;
     }
-    WR_TL(1)
     float sh[4] = {0.f, 0.f, 0.f, 0.f};                              // a lane's four channels 4 lc + j: read from LDS after the first boundary
 
     // ---- per-lane fragment bases (absolute LDS byte addresses).  Lane (lc, lg) of MFMA tile i reads the halo row
@@ -296,7 +275,6 @@ __global__ __launch_bounds__(256) void conv3d_wres_kernel(Conv3dArgs a) {
             sh[0] = b4[0]; sh[1] = b4[1]; sh[2] = b4[2]; sh[3] = b4[3];
         }
         asm volatile(WRES_INIT_BIAS : : [sh0] "v"(sh[0]), [sh1] "v"(sh[1]), [sh2] "v"(sh[2]), [sh3] "v"(sh[3]) : WRES_CLOBBERS);
-        WR_TL(3)
         int cur = 0, tile = lo;
         while (tile < hi) {
             // ---- a column segment: tiles `tile` .. `tile + nseg - 1` walk down one (b, h, w) column.  What changes
@@ -325,7 +303,6 @@ __global__ __launch_bounds__(256) void conv3d_wres_kernel(Conv3dArgs a) {
                 for (int kd = 0; kd < 3; ++kd) { ab[kd][0] = lane_a0 + sw[kd]; ab[kd][1] = lane_a1 + sw[kd]; }
                 const bf16* pbase = base_prev;
                 const bool me_full = hw_full && d0 + TD <= a.D;
-                WR_T0
                 if (!last) {
                     // new planes d0 + 6 .. d0 + 9 take the slots of planes d0 .. d0 + 3 as those die
                     int nv = a.D - (d0 + 5);                         // how many of the four new planes lie inside the volume
@@ -365,8 +342,6 @@ __global__ __launch_bounds__(256) void conv3d_wres_kernel(Conv3dArgs a) {
                     }
                     if (has_next) full_boundary(nx, epi && me_full);
                 }
-                WR_T1
-                WR_TLK
                 if (!last && !me_full) {
                     Tile me = col; me.d = col.d + k;
                     store_ragged(cur, me);
@@ -383,26 +358,14 @@ __global__ __launch_bounds__(256) void conv3d_wres_kernel(Conv3dArgs a) {
                 sw[0] = sw[4]; sw[1] = sw[5]; sw[4] = sw[2]; sw[5] = sw[3]; sw[2] = u0; sw[3] = u1;
             }
         }
-        WR_TL(6)
         if (pending) {
             const bf16* pbase = base_prev;
             if (last_in_x) asm volatile(WRES_FLUSH_X : : WR_EPI : "memory", WRES_CLOBBERS);
             else asm volatile(WRES_FLUSH_Y : : WR_EPI : "memory", WRES_CLOBBERS);
         }
-        WR_TL(7)
     } else {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");             // the weight DMA targets this workgroup's LDS
     }
-#ifdef WRES_STAMPS
-    if (a.stats && tid == 0) {          // [32][2][64] statistics, then per workgroup {K-loop cycles, kernel cycles, kernel 100 MHz ticks, tiles, 12 timeline stamps}
-        float* o = a.stats + MM_REPL * 2 * BN + blockIdx.x * 16;
-        o[0] = (float)kcyc; o[1] = (float)(__builtin_readcyclecounter() - t_begin);
-        o[2] = (float)(wall_clock64() - r_begin); o[3] = (float)(hi - lo);
-#pragma unroll
-        for (int i = 0; i < 12; ++i) o[4 + i] = tl[i];
-        o[12] = (float)(r_begin & 0xFFFFFF); o[13] = (float)(wall_clock64() & 0xFFFFFF);     // absolute 100 MHz ticks: start stagger and span over workgroups
-    }
-#endif
     if (a.stats) {
         float* sstat = reinterpret_cast<float*>(smem + S_OFF);
         float st[8];

@@ -523,13 +523,6 @@ __global__ void meanpool_bwd_kernel(const float* __restrict__ g, float* __restri
     }
 }
 
-__global__ void cast_bf16_kernel(const float* __restrict__ x, bf16* __restrict__ y, size_t n) {
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) y[i] = (bf16)x[i];
-}
-__global__ void cast_f32_kernel(const bf16* __restrict__ x, float* __restrict__ y, size_t n) {
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) y[i] = (float)x[i];
-}
-
 // dz = g * dropout_mask * act'(z): elementwise gradient through act+dropout
 __global__ void act_bwd_kernel(const float* __restrict__ g_f32, const bf16* __restrict__ g_bf16,
                                const bf16* __restrict__ z, bf16* __restrict__ out, size_t n, int act,
@@ -686,7 +679,7 @@ static int bn_bwd_common(bool apply, const float* y, const float* out4, const vo
     const int rpb = 256 / (N / 4) > 0 ? 256 / (N / 4) : 1;
     const size_t rows = (size_t)R * (S / pool);
     int grid = (int)((rows + rpb - 1) / rpb);
-    { static const int cap = getenv("MM_BN_GRID") ? atoi(getenv("MM_BN_GRID")) : 768; if (grid > cap) grid = cap; }   // three workgroups per CU (sweep 256..1024: profiles/r03_second_half_ab.txt)
+    if (grid > 768) grid = 768;   // three workgroups per CU (sweep 256..1024: profiles/r03_second_half_ab.txt)
     // GELU with pool 1 / 2 (every BatchNorm of the encoders on the training path) is compiled in; anything else is generic
     if (act == MM_ACT_GELU && pool == 1) {
         if (apply) hipLaunchKernelGGL((bn_act_bwd_kernel<true, MM_ACT_GELU, 1>), dim3(grid), dim3(256), 0, st, a);
@@ -795,18 +788,6 @@ int mm_meanpool_bwd(const float* g, float* dx, int B, int L, int D, hipStream_t 
     MM_REQUIRE(g && dx, "meanpool_bwd: null");
     hipLaunchKernelGGL(meanpool_bwd_kernel, dim3(grid_for((size_t)B * L * D)), dim3(256), 0, st, g, dx, B, L, D);
     return mm_check_launch("meanpool_bwd");
-}
-
-int mm_cast_bf16(const float* x, void* y, int64_t n, hipStream_t st) {
-    MM_REQUIRE(x && y && n > 0, "cast_bf16: null");
-    hipLaunchKernelGGL(cast_bf16_kernel, dim3(grid_for((size_t)n)), dim3(256), 0, st, x, (bf16*)y, (size_t)n);
-    return mm_check_launch("cast_bf16");
-}
-
-int mm_cast_f32(const void* x, float* y, int64_t n, hipStream_t st) {
-    MM_REQUIRE(x && y && n > 0, "cast_f32: null");
-    hipLaunchKernelGGL(cast_f32_kernel, dim3(grid_for((size_t)n)), dim3(256), 0, st, (const bf16*)x, y, (size_t)n);
-    return mm_check_launch("cast_f32");
 }
 
 int mm_act_bwd(const float* g_f32, const void* g_bf16, const void* z, void* out, int64_t n, int act, float drop_p,

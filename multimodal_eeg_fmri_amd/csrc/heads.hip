@@ -99,31 +99,6 @@ __global__ void colstats_kernel(const float* __restrict__ x, float* __restrict__
     acc[N + n] = acc_encode<MM_ACC_STAT>(q);
 }
 
-// z = h / max(||h||, eps); one wave per row
-__global__ void l2norm_fwd_kernel(const float* __restrict__ h, float* __restrict__ z, float* __restrict__ nrm, int B, int N, int ldz) {
-    const int row = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    if (row >= B) return;
-    float q = 0.f;
-    for (int n = lane; n < N; n += 64) { const float v = h[(size_t)row * N + n]; q += v * v; }
-    const float nr = fmaxf(sqrtf(wave_sum(q)), 1e-12f);
-    for (int n = lane; n < N; n += 64) z[(size_t)row * ldz + n] = h[(size_t)row * N + n] / nr;
-    if (lane == 0) nrm[row] = nr;
-}
-// dh = (dz - z (z . dz)) / ||h||
-__global__ void l2norm_bwd_kernel(const float* __restrict__ dz, const float* __restrict__ z, const float* __restrict__ nrm,
-                                  float* __restrict__ dh, int B, int N, int ldz) {
-    const int row = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    if (row >= B) return;
-    float d = 0.f;
-    for (int n = lane; n < N; n += 64) d += dz[(size_t)row * ldz + n] * z[(size_t)row * ldz + n];
-    d = wave_sum(d);
-    const float inv = 1.f / nrm[row];
-    for (int n = lane; n < N; n += 64)
-        dh[(size_t)row * N + n] = (dz[(size_t)row * ldz + n] - z[(size_t)row * ldz + n] * d) * inv;
-}
-
 
 // ---------------------------------------------------------------------------
 // Both projection heads of the contrastive bridge in ONE launch each way
@@ -1702,18 +1677,6 @@ int mm_proj_heads_bwd(const float* dz, const float* z, const float* nrm, const f
     return mm_check_launch("proj_heads_bwd");
 }
 
-int mm_l2norm_fwd(const float* h, float* z, float* nrm, int B, int N, int ldz, hipStream_t st) {
-    MM_REQUIRE(h && z && nrm && B > 0 && N > 0 && ldz >= N, "l2norm_fwd: null");
-    hipLaunchKernelGGL(l2norm_fwd_kernel, dim3(ceil_div(B, 4)), dim3(256), 0, st, h, z, nrm, B, N, ldz);
-    return mm_check_launch("l2norm_fwd");
-}
-
-int mm_l2norm_bwd(const float* dz, const float* z, const float* nrm, float* dh, int B, int N, int ldz, hipStream_t st) {
-    MM_REQUIRE(dz && z && nrm && dh && B > 0 && N > 0 && ldz >= N, "l2norm_bwd: null");
-    hipLaunchKernelGGL(l2norm_bwd_kernel, dim3(ceil_div(B, 4)), dim3(256), 0, st, dz, z, nrm, dh, B, N, ldz);
-    return mm_check_launch("l2norm_bwd");
-}
-
 int mm_clip_loss_ws_floats(int B, int Bg, int* floats_host, hipStream_t) {
     MM_REQUIRE(floats_host && B > 0 && Bg >= B, "clip_loss_ws_floats: bad args");
     *floats_host = 6 * Bg;
@@ -1870,7 +1833,7 @@ int mm_stft_power(const float* x, void* out_bf16, float* out_f32, int B, int C, 
     const int frames = T / hop + 1;
     const int F = nfft / 2 + 1;
     MM_REQUIRE(ch_off >= 0 && ch_off + C * F <= ch_total, "stft_power: channel window");
-    if (nfft <= 256 && !getenv("MM_STFT_DFT")) {                // the FFT form (MM_STFT_DFT=1: the direct DFT, for A/B)
+    if (nfft <= 256) {                // the FFT form
         const dim3 grid(1, C, B);
         switch (nfft) {
             case 8: hipLaunchKernelGGL((stft_power_fft_kernel<3>), grid, dim3(256), 0, st, x, (bf16*)out_bf16, out_f32, C, T, hop, frames, ch_off, ch_total); break;

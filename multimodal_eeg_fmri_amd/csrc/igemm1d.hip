@@ -725,12 +725,11 @@ int launch_fwd_feat(const ConvArgs& a, hipStream_t st) {
     return mm_check_launch("conv1d_fwd");
 }
 
-// the combinations of the contrastive training step (logged with MM_EPI_LOG=1), each on the tile shape it runs on;
+// the combinations of the contrastive training step, each on the tile shape it runs on;
 // everything else takes the generic epilogue
 template <int BM, int BN, int WM, int WN, int KCT>
 int launch_fwd(const ConvArgs& a, hipStream_t st) {
     const unsigned m = epi_mask(a.e);
-    if (getenv("MM_EPI_LOG")) fprintf(stderr, "EPI %d %d %d mask %06x K=%d N=%d taps=%d\n", BM, BN, KCT, m, a.Cin, a.Cout, a.taps);
     if (getenv("MM_EPI_GENERIC") || a.partial) return launch_fwd_feat<BM, BN, WM, WN, KCT, EF_ANY>(a, st);      // tests: generic vs compiled-in epilogues; split-K
 #define EPI_CASE(mask) case mask: return launch_fwd_feat<BM, BN, WM, WN, KCT, mask, LT>(a, st);
     if constexpr (BM == 64 && BN == 128 && KCT == 128) {
@@ -1664,7 +1663,7 @@ int mm_linear_dgrad_ln_bwd_bn_reduce(const void* dy, const void* w, int M, int K
 static int wgrad_rows_per_wg(int B, int T, int Cin, int Cout, int taps, int slot_mode) {
     const int tiles = ceil_div(Cout, 64) * ceil_div(Cin, 64);
     const int tilesT = ceil_div(T, WG_MK);
-    static const int slot_target = getenv("MM_WG_TARGET") ? atoi(getenv("MM_WG_TARGET")) : 128;   // slot mode, k > 1: 384 1.116, 192 1.107, 128 1.106, 64 1.111 ms/step
+    constexpr int slot_target = 128;   // slot mode, k > 1: 384 1.116, 192 1.107, 128 1.106, 64 1.111 ms/step
     int want_chunks = ceil_div((taps > 1 && !slot_mode) ? 112 : (taps > 1 ? slot_target : 384), tiles * B);
     if (want_chunks < 1) want_chunks = 1;
     if (want_chunks > tilesT) want_chunks = tilesT;
@@ -1687,14 +1686,11 @@ static int wgrad_bgroup(int B, int T, int Cin, int Cout, int taps, int slot_mode
 // 64 1.120, 32 1.158 ms/step; end of round 2, with the launch on the side stream beside the chain: 128 0.880, 96 0.873,
 // 64 0.870, 48 0.866, 32 0.865, 24 0.864, 16 0.887 - fewer workgroups also leave more of the chip to the chain), i.e. 12x less
 // slot memory to write and to sum afterwards
-static int wgrad_many_target() {
-    static const int t = getenv("MM_WGM_TARGET") ? atoi(getenv("MM_WGM_TARGET")) : 32;
-    return t;
-}
+constexpr int WGRAD_MANY_TARGET = 32;
 static int wgrad_many_rows_per_wg(int T, int Cin, int Cout) {
     const int tiles = ceil_div(Cout, 128) * ceil_div(Cin, 128);
     const int tilesT = ceil_div(T, WG_MK);
-    int want_chunks = ceil_div(wgrad_many_target(), tiles);
+    int want_chunks = ceil_div(WGRAD_MANY_TARGET, tiles);
     if (want_chunks < 1) want_chunks = 1;
     if (want_chunks > tilesT) want_chunks = tilesT;
     return ceil_div(tilesT, want_chunks) * WG_MK;

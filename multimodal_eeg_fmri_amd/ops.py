@@ -125,7 +125,6 @@ def _zeros(shape, like, dtype=_F32):
     return torch.zeros(shape, dtype=dtype, device=like.device)
 
 
-_NO_SPLITK = bool(os.environ.get("MM_NO_SPLITK"))
 _NO_FFN1_FUSE = not os.environ.get("MM_FFN1_FUSE")        # the first FFN Linear inside the out-projection's launch: measured, not
                                                            # faster (2-byte column stores of 2 x 16 MB) - off unless MM_FFN1_FUSE=1
 _NO_QKV_FUSE = bool(os.environ.get("MM_NO_QKV_FUSE"))     # A/B knob: the next block's QKV projection as its own launch
@@ -328,8 +327,8 @@ _SPLITK_PLANS: Dict[tuple, tuple] = {}
 
 
 def _splitk_plan(B: int, T: int, cin: int, cout: int, taps: int):
-    """(slices, workspace floats) of mm_conv1d_fwd_splitk_plan, cached per shape; MM_NO_SPLITK=1 turns it off (A/B)"""
-    if taps == 1 or _NO_SPLITK:
+    """(slices, workspace floats) of mm_conv1d_fwd_splitk_plan, cached per shape"""
+    if taps == 1:
         return 1, 0
     key = (B, T, cin, cout, taps)
     plan = _SPLITK_PLANS.get(key)
@@ -339,6 +338,22 @@ def _splitk_plan(B: int, T: int, cin: int, cout: int, taps: int):
         _hip.call("mm_conv1d_fwd_splitk_plan", B, T, cin, cout, taps, ctypes.addressof(n), ctypes.addressof(ws))
         plan = _SPLITK_PLANS[key] = (n.value, ws.value)
     return plan
+
+
+_CLIP_WS: Dict[tuple, int] = {}
+
+
+def clip_loss_ws_floats(B: int, Bg: int) -> int:
+    """floats of mm_clip_loss_own_rows' scratch for B own rows of a Bg-row gathered batch (mm_clip_loss_ws_floats:
+    the kernel file owns the layout), cached per shape"""
+    key = (B, Bg)
+    n = _CLIP_WS.get(key)
+    if n is None:
+        import ctypes
+        c = ctypes.c_int(0)
+        _hip.call("mm_clip_loss_ws_floats", B, Bg, ctypes.addressof(c))
+        n = _CLIP_WS[key] = c.value
+    return n
 
 
 def linear_rows(x2d: torch.Tensor, weight: torch.Tensor, bias, *, act="none", residual=None,
@@ -370,9 +385,6 @@ def bn_finalize_train(bn, stats, count) -> torch.Tensor:
     _hip.call("mm_bn_finalize", stats, bn.weight, bn.bias, bn.running_mean, bn.running_var,
               None, out4, n, float(count), mom, float(bn.eps), 0, bn.num_batches_tracked)
     return out4
-
-
-_NO_FIN_FOLD = bool(os.environ.get("MM_NO_FIN_FOLD"))      # A/B knob: BatchNorm finalize as its own launch (round 3)
 
 
 def bn_fin_desc(bn, stats, count):
@@ -475,7 +487,7 @@ def conv_bn_act(xb: torch.Tensor, conv, bn, *, act="gelu", pool=1, training=Fals
     stats = _zeros((REPL, 2, cout), xb) if training else None
     y = igemm(xb, wf, k, pad, cout, shift=conv.bias, stats=stats, out_f32=True, out_bf16=False)["f32"]
     # train mode, GELU, <= 256 channels: the finalize (mean / rstd / running statistics) runs in the apply pass's prologue
-    fold = training and act == "gelu" and cout <= 256 and not _NO_FIN_FOLD and isinstance(bn.running_mean, torch.Tensor)
+    fold = training and act == "gelu" and cout <= 256 and isinstance(bn.running_mean, torch.Tensor)
     fin = None
     if fold:
         fin, out4 = bn_fin_desc(bn, stats, B * T)
@@ -802,7 +814,7 @@ def conv3d_bn_act(xv: torch.Tensor, conv, bn, *, pool: bool, training: bool, dro
         _hip.call("mm_conv3d_fwd", xv, wf, B, D, H, W, cinp, cout, conv.bias, stats, yf, yb)
         if end is not None:
             end.record()
-        if cout <= 256 and not _NO_FIN_FOLD:           # the finalize runs in the prologue of the apply pass below
+        if cout <= 256:                                # the finalize runs in the prologue of the apply pass below
             fin, out4 = bn_fin_desc(bn, stats, B * D * H * W)
         else:
             out4 = bn_finalize_train(bn, stats, B * D * H * W)
@@ -858,7 +870,7 @@ def conv3d_l1_bn_act(x: torch.Tensor, conv, bn, *, training: bool, drop_p: float
         stats = _zeros((REPL, 2, 32), x)
         _hip.call("mm_conv3d_l1_gram", x, wimg, conv.bias, gram, stats, B, D, H, W)
         gramc = gram                                   # (the accumulator workspace itself: the backward's combine step reads it)
-        if not _NO_FIN_FOLD and winners is None:       # the finalize runs in the forward kernel's prologue
+        if winners is None:                            # the finalize runs in the forward kernel's prologue
             fin, out4 = bn_fin_desc(bn, stats, B * D * H * W)
         else:
             out4 = bn_finalize_train(bn, stats, B * D * H * W)

@@ -33,6 +33,27 @@ def test_library_exports_every_declared_symbol():
     assert lib.mm_abi_version() == 5
 
 
+def test_library_of_another_abi_version_is_refused(tmp_path, monkeypatch):
+    """a library whose mm_abi_version() differs from the header's MM_ABI_VERSION would be called with shifted
+    arguments: load() refuses it before it binds any entry point."""
+    assert os.path.exists(_hip.lib_path()), "run __graft_entry__.build() first"
+    assert _hip.header_abi_version() == 5
+    text = open(_hip.header_path()).read()
+    assert "#define MM_ABI_VERSION 5\n" in text
+    other = tmp_path / "mmeeg_hip.h"
+    other.write_text(text.replace("#define MM_ABI_VERSION 5\n", "#define MM_ABI_VERSION 6\n"))
+    sigs = dict(_hip._SIGS)
+    monkeypatch.setattr(_hip, "header_path", lambda: str(other))
+    monkeypatch.setattr(_hip, "_lib", None)
+    try:
+        with pytest.raises(_hip.HipLibraryError, match=r"is stale: ABI 5, header 6; rebuild it"):
+            _hip.load()
+        assert _hip._lib is None
+    finally:
+        _hip._SIGS.clear()
+        _hip._SIGS.update(sigs)
+
+
 def test_argument_errors_are_reported_not_crashed():
     """entry points validate before touching the device: callable without a GPU."""
     lib = _hip.load()

@@ -37,18 +37,9 @@ Scratch VGPRs v[224:255] and SGPRs s[90:93] are named literally too (clobbers; d
 import os
 import sys
 
-# ablation builds (tools/abl_build.sh): 1 no epilogue instructions, 2 no ds_reads inside the K loop, 4 no MFMAs,
-# 8 no global stores, 64 no halo prefetch, 128 no in-loop barriers, 256 no in-loop vmcnt waits.  0 in the product.
-ABL = int(os.environ.get("WRES_ABL", "0"))
-# schedule / epilogue experiments (A/B builds, profiles/r03_wres_ab.txt; 0 in the product): 1 packed fp32 math
-# (v_pk_*) for the bias add and the BatchNorm sums inside the K loop (measured: +12 % K-loop cycles - a v_pk_* in an
-# MFMA's shadow costs more than the two instructions it replaces), 2 a side instruction ALSO in the MFMA gaps that
-# carry a ds_read (round 2's schedule; one instruction per gap is 2 % fewer K-loop cycles)
-OPT = int(os.environ.get("WRES_OPT", "0"))
 # cache policy of the output stores: write-through ("sc0 sc1") - the 16.8 MB leave the XCD's L2 while the kernel
 # still computes instead of as one write-back burst at the kernel boundary (measured at C2, graph-replayed:
 # plain 17.9 us, sc1 / nt 16.6, sc0 sc1 15.8); the consumer is on another XCD's L2 anyway.
-STORE_BITS = os.environ.get("WRES_STORE_BITS", "sc0 sc1")
 OUT = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
                    "multimodal_eeg_fmri_amd", "csrc", "conv3d_wres_asm.inc")
 ACC = {"X": 64, "Y": 128}
@@ -117,9 +108,7 @@ class Stream:
         elif op.startswith("ds_write"):
             self.ds.append("W")
 
-    def read(self, t, which, base=None, force=False):
-        if (ABL & 2) and not force:
-            return
+    def read(self, t, which, base=None):
         self.lines.append(a_read(t, int(which[1]), base) if which[0] == "A" else b_read(t, int(which[1])))
         self.ds.append((t, which))
 
@@ -157,21 +146,15 @@ def epilogue_group(prev, q, bias=True):
     4 channels x 4 voxel rows per lane quad: 19 instructions (15 without a bias)"""
     i, r = q >> 2, q & 3
     out = [f"v_accvgpr_read_b32 {TT[j]}, a{ACC[prev] + 4 * (4 * i + j) + r}" for j in range(4)]
+    # scalar fp32 math: packed v_pk_* for the bias add and the sums measured +12 % K-loop cycles (profiles/r03_wres_ab.txt:
+    # a v_pk_* in an MFMA's shadow costs more than the two instructions it replaces)
     if bias:
-        if OPT & 1:
-            out += ["v_pk_add_f32 v[236:237], v[236:237], v[232:233]", "v_pk_add_f32 v[238:239], v[238:239], v[234:235]"]
-        else:
-            out += [f"v_add_f32 {TT[j]}, {TT[j]}, {SH[j]}" for j in range(4)]
+        out += [f"v_add_f32 {TT[j]}, {TT[j]}, {SH[j]}" for j in range(4)]
     out += [f"v_cvt_pk_bf16_f32 v240, {TT[0]}, {TT[1]}", f"v_cvt_pk_bf16_f32 v241, {TT[2]}, {TT[3]}"]
-    if not (ABL & 8):
-        voff = VOFA if (i >> 1) == 0 else VOFB
-        out.append(f"global_store_dwordx2 {voff}, {PK}, %[pbase] offset:{(4 * (i & 1) + r) * BN * 2} {STORE_BITS}".rstrip())
-    if OPT & 1:
-        out += ["v_pk_add_f32 v[224:225], v[224:225], v[236:237]", "v_pk_add_f32 v[226:227], v[226:227], v[238:239]",
-                "v_pk_fma_f32 v[228:229], v[236:237], v[236:237], v[228:229]", "v_pk_fma_f32 v[230:231], v[238:239], v[238:239], v[230:231]"]
-    else:
-        for j in range(4):
-            out += [f"v_add_f32 {S1[j]}, {S1[j]}, {TT[j]}", f"v_fmac_f32 {S2[j]}, {TT[j]}, {TT[j]}"]
+    voff = VOFA if (i >> 1) == 0 else VOFB
+    out.append(f"global_store_dwordx2 {voff}, {PK}, %[pbase] offset:{(4 * (i & 1) + r) * BN * 2} sc0 sc1")
+    for j in range(4):
+        out += [f"v_add_f32 {S1[j]}, {S1[j]}, {TT[j]}", f"v_fmac_f32 {S2[j]}, {TT[j]}, {TT[j]}"]
     return out
 
 
@@ -246,9 +229,9 @@ def kloop(cur, prev=None, march=True, bias=True, first=False):
         side += ["s_mov_b32 m0, s93"]
     for t in range(TAPS):
         s = t & 1
-        if not (ABL & 64) and t < nplanes:
+        if t < nplanes:
             side += prefetch_plane(t)
-        if prev is not None and not (ABL & 1) and e0 <= t <= e1:
+        if prev is not None and e0 <= t <= e1:
             want = ((t - e0 + 1) * 16 + (e1 - e0)) // (e1 - e0 + 1)       # groups due by the end of tap t
             while ngroups < min(want, 16):
                 side += epilogue_group(prev, ngroups, bias)
@@ -257,13 +240,12 @@ def kloop(cur, prev=None, march=True, bias=True, first=False):
         for g, (i, j) in enumerate(MFMA_ORDER):
             st.need(t, {"A%d" % i, "B%d" % j})
             c = "0" if t == 0 else acc(cur, i, j)
-            if not (ABL & 4):
-                st.emit(f"v_mfma_f32_16x16x32_bf16 {acc(cur, i, j)}, {frag(s, 'A%d' % i)}, {frag(s, 'B%d' % j)}, {c}")
+            st.emit(f"v_mfma_f32_16x16x32_bf16 {acc(cur, i, j)}, {frag(s, 'A%d' % i)}, {frag(s, 'B%d' % j)}, {c}")
             budget = 2
             # the reads of tap t + 1 go to the OTHER fragment set, whose last readers (tap t - 1's MFMAs) have issued
             if nxt and g < 8:
                 st.read(t + 1, nxt.pop(0))
-                budget -= 1 if (OPT & 2) else 2
+                budget = 0                           # (one side instruction beside the read too: +2 % K-loop cycles)
             if first and t == 7 and g == 8:
                 # the first tile of a workgroup started with only taps 0-8 of the weights in LDS: wait for this wave's 18
                 # pieces issued above (the next tile's halo loads issued after them may stay in flight); the barrier
@@ -276,13 +258,10 @@ def kloop(cur, prev=None, march=True, bias=True, first=False):
                 # end of a kd phase.  Every fragment of this tap has landed (so no wave still reads the dying plane
                 # once all have passed the barrier); the new plane's loads have landed; then overwrite.
                 mine = [i_ for i_, e in enumerate(st.ds) if e != "W" and e[0] == t]
-                if mine:                             # (none in the no-ds_read ablation build)
-                    st.wait_ds(max(mine))
+                st.wait_ds(max(mine))
                 planes = {8: [0], 17: [1], 26: [2, 3]}[t]
-                if not (ABL & 64) and not (ABL & 256):
-                    st.need_vm(is_plane_load(planes[-1]))
-                if not (ABL & 128):
-                    st.emit("s_barrier")
+                st.need_vm(is_plane_load(planes[-1]))
+                st.emit("s_barrier")
                 w = []
                 for pp in planes:
                     w += plane_write(pp, f"sb{pp}")
@@ -291,7 +270,7 @@ def kloop(cur, prev=None, march=True, bias=True, first=False):
             while side and budget > 0:
                 st.emit(side.pop(0))
                 budget -= 1
-    assert ngroups == 16 or prev is None or (ABL & 1)
+    assert ngroups == 16 or prev is None
     for ins in side:                                 # (the last plane writes of a marching tile may spill over)
         st.emit(ins)
     if march:
@@ -300,9 +279,7 @@ def kloop(cur, prev=None, march=True, bias=True, first=False):
         for w in READ_ORDER:
             st.lines.append(a_read(0, int(w[1]), "%[abn]") if w[0] == "A" else b_read(0, int(w[1])))
     else:
-        if st.ds_done != len(st.ds):
-            assert ABL, "a fragment was read but never waited for"
-            st.emit("s_waitcnt lgkmcnt(0)")
+        assert st.ds_done == len(st.ds), "a fragment was read but never waited for"
     if prev is not None:
         for ins in epi_save_state():
             st.emit(ins)
@@ -320,7 +297,7 @@ def flush_group(prev, q, base):
             f"v_pk_add_f32 v[{base + 2}:{base + 3}], v[{base + 2}:{base + 3}], v[234:235]",
             f"v_cvt_pk_bf16_f32 v{base + 4}, {t[0]}, {t[1]}", f"v_cvt_pk_bf16_f32 v{base + 5}, {t[2]}, {t[3]}"]
     voff = VOFA if (i >> 1) == 0 else VOFB
-    out.append(f"global_store_dwordx2 {voff}, {p}, %[pbase] offset:{(4 * (i & 1) + r) * BN * 2} {STORE_BITS}".rstrip())
+    out.append(f"global_store_dwordx2 {voff}, {p}, %[pbase] offset:{(4 * (i & 1) + r) * BN * 2} sc0 sc1")
     out += [f"v_pk_add_f32 v[224:225], v[224:225], v[{base}:{base + 1}]", f"v_pk_add_f32 v[226:227], v[226:227], v[{base + 2}:{base + 3}]",
             f"v_pk_fma_f32 v[228:229], v[{base}:{base + 1}], v[{base}:{base + 1}], v[228:229]",
             f"v_pk_fma_f32 v[230:231], v[{base + 2}:{base + 3}], v[{base + 2}:{base + 3}], v[230:231]"]

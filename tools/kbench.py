@@ -150,64 +150,8 @@ def conv3d_case(B, S, Cin, Cout, wgrad=True, fwd=True):
     def fn2():
         _hip.call("mm_conv3d_wgrad", dy, x, ws, None, B, S, S, S, Cin, Cout, Cin, 27 * Cin, 1, Cin, n.value, Cout * 27 * Cin, 1)
     us = graph_time(fn2)
-    if os.environ.get("W3_DBG"):
-        torch.cuda.synchronize()
-        v = ws.view(n.value, -1)[:, :4].cpu()
-        print(f"    cycles (kd = 2 workgroups): set-up + ring prologue {v[:, 0].mean():.0f} | tile loop done {v[:, 1].mean():.0f} | "
-              f"K-split sum done {v[:, 2].mean():.0f} | stores drained {v[:, 3].mean():.0f}")
     print(f"wgrad3d B={B} {S}^3 Cin={Cin} Cout={Cout}: {us:8.1f} us  {fl / us / 1e6:8.1f} TF/s ({fl / us / 1e6 / 2500:.3f} of 2.5 PF; "
           f"{n.value} slots, graph-replayed)")
-
-
-def stamp_case(B, D, H, W):
-    """in-kernel cycle stamps of a WRES_STAMPS build (tools/abl_build.sh s0; MMEEG_HIP_LIB=.../abl_s0.so)"""
-    Cin, Cout = 32, 64
-    x = torch.randn(B, D, H, W, Cin, device="cuda").to(BF)
-    w = torch.randn(Cout, Cin, 27, device="cuda") / math.sqrt(Cin * 27)
-    wf = torch.empty(Cout, 27, Cin, dtype=BF, device="cuda")
-    _hip.call("mm_prep_conv_weight", w.contiguous(), wf, None, Cout, Cin, 27, Cin, 0)
-    of = torch.empty(B, D, H, W, Cout, device="cuda", dtype=BF)
-    stats = torch.zeros(32 * 2 * Cout + 256 * 16, device="cuda")
-    b = torch.randn(Cout, device="cuda")
-    for _ in range(20):
-        _hip.call("mm_conv3d_fwd", x, wf, B, D, H, W, Cin, Cout, b, stats, None, of)
-    torch.cuda.synchronize()
-    st = stats[32 * 2 * Cout:].view(256, 16).cpu().double()
-    k, tot, ticks, tiles = st[:, 0], st[:, 1], st[:, 2], st[:, 3]
-    ghz = (tot / (ticks / 100.0)).mean() / 1e3
-    print(f"stamps B={B} {D}x{H}x{W}: tiles/WG {tiles.mean():.1f}; kernel {tot.mean():.0f} cyc = {(ticks / 100).mean():.2f} us "
-          f"({ghz:.2f} GHz); K loops {k.mean():.0f} cyc = {(k / tiles).mean():.0f} per tile (6912 = MFMA-bound); "
-          f"outside K loops {(tot - k).mean():.0f} cyc = {((tot - k) / tiles).mean():.0f} per tile; per-WG kernel cyc min {tot.min():.0f} max {tot.max():.0f}")
-    b0, e0 = st[:, 12], st[:, 13]
-    if (e0.max() > b0.min()):
-        print(f"    absolute 100 MHz clock: first start -> last end {(e0.max() - b0.min()) / 100:.2f} us; start stagger {(b0.max() - b0.min()) / 100:.2f} us; "
-              f"end stagger {(e0.max() - e0.min()) / 100:.2f} us")
-    names = ["halo 0 prefetch issued", "weight DMA issued", "halo constants parked", "first boundary done (halo 0 + W in LDS)",
-             "K loop 1 issued", "K loop 2 issued", "last K loop issued", "flush issued"]
-    for i, nm in enumerate(names):
-        c = st[:, 4 + i]
-        print(f"    {nm:40s} {c.mean():8.0f} cyc (min {c.min():.0f} max {c.max():.0f})")
-
-
-def stream_stamp_case(B, D, H, W, Cin, Cout):
-    """in-kernel cycle stamps of a STREAM_STAMPS build (tools/abl_stream.sh s0; MMEEG_HIP_LIB=.../sabl_0-DSTREAM_STAMPS.so)"""
-    x = torch.randn(B, D, H, W, Cin, device="cuda").to(BF)
-    w = torch.randn(Cout, Cin, 27, device="cuda") / math.sqrt(Cin * 27)
-    wf = torch.empty(Cout, 27, Cin, dtype=BF, device="cuda")
-    _hip.call("mm_prep_conv_weight", w.contiguous(), wf, None, Cout, Cin, 27, Cin, 0)
-    of = torch.empty(B, D, H, W, Cout, device="cuda", dtype=BF)
-    ntiles = B * ((D + 1) // 2) * ((H + 7) // 8) * ((W + 7) // 8)
-    stats = torch.zeros(32 * 2 * Cout + ntiles * 8, device="cuda")
-    for _ in range(20):
-        _hip.call("mm_conv3d_fwd", x, wf, B, D, H, W, Cin, Cout, None, stats, None, of)
-    torch.cuda.synchronize()
-    st = stats[32 * 2 * Cout:].view(ntiles, 8).cpu().double()
-    names = ["halo loads + writes issued", "halo + first stages in LDS (barrier)", "K loop done", "K-groups summed", "outputs stored", "stores drained"]
-    print(f"stream stamps B={B} {D}x{H}x{W} {Cin}->{Cout}: {ntiles} workgroups; first start -> last end {(st[:, 7].max() - st[:, 6].min()) / 100:.2f} us; "
-          f"start stagger {(st[:, 6].max() - st[:, 6].min()) / 100:.2f} us; mean workgroup {((st[:, 7] - st[:, 6]) / 100).mean():.2f} us")
-    for i, nm in enumerate(names):
-        c = st[:, i]
-        print(f"    {nm:40s} {c.mean():8.0f} cyc (min {c.min():.0f} max {c.max():.0f})")
 
 
 def attn_case(B=32, L=512, H=4, p=0.1):
@@ -227,18 +171,19 @@ def attn_case(B=32, L=512, H=4, p=0.1):
 
 def floor_case():
     x = torch.zeros(64, device="cuda")
-    y = torch.zeros(64, dtype=BF, device="cuda")
-    us = timeit(lambda: _hip.call("mm_cast_bf16", x, y, 64))
-    print(f"harness floor (64-element cast through _hip.call): {us:8.1f} us")
+    y = torch.zeros(64, device="cuda")
+    act = ops.ACT["none"]
+    us = timeit(lambda: _hip.call("mm_act_f32", x, y, 64, act, 0.0, 0, None))
+    print(f"harness floor (64-element copy through _hip.call): {us:8.1f} us")
     g = torch.cuda.CUDAGraph()
     s = torch.cuda.Stream()
     s.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(s):
-        _hip.call("mm_cast_bf16", x, y, 64)
+        _hip.call("mm_act_f32", x, y, 64, act, 0.0, 0, None)
     torch.cuda.current_stream().wait_stream(s)
     with torch.cuda.graph(g):
         for _ in range(20):
-            _hip.call("mm_cast_bf16", x, y, 64)
+            _hip.call("mm_act_f32", x, y, 64, act, 0.0, 0, None)
     us = timeit(g.replay, iters=5) / 20
     print(f"same, 20 launches per hipGraph replay: {us:8.1f} us per kernel")
 
@@ -338,7 +283,6 @@ def l1_case(B=32, D=32, H=32, W=32, p=0.3):
     sums, a1 = torch.zeros(32, 2, 32, device="cuda"), torch.zeros(32, 27, 32, device="cuda")
     gram = torch.zeros(32, 32, 32, device="cuda")
     gramc = s["gramc"].clone()
-    tapsum = torch.zeros(32, 32, device="cuda")
     dw, db = torch.zeros(32, 1, 3, 3, 3, device="cuda"), torch.zeros(32, device="cuda")
     fl = 2.0 * 27 * 32 * B * D * H * W
     tg = timeit(lambda: _hip.call("mm_conv3d_l1_gram", x, wimg, conv.bias, gram, stats, B, D, H, W))
@@ -348,11 +292,10 @@ def l1_case(B=32, D=32, H=32, W=32, p=0.3):
                                   B, D, H, W, 1, float(p), 123, None))
     t4 = timeit(lambda: _hip.call("mm_conv3d_l1_bwd", x, wimg, conv.bias, out4, dout, sums, a1, gramc, dw, db,
                                   B, D, H, W, 1, float(p), 123, None))
-    tt = timeit(lambda: _hip.call("mm_conv3d_l1_tapsum", x, tapsum, B, D, H, W))
     inb, outb = x.numel() * 4, out.numel() * 2
     for name, t, byts in (("Gram matrix + BatchNorm sums", tg, inb),
                           ("stats by recompute (mode 0, ABI)", t0, inb), ("forward (mode 1)", t1, inb + outb),
-                          ("backward (mode 4 + combine)", t4, inb + outb), ("tap sums (ABI)", tt, inb)):
+                          ("backward (mode 4 + combine)", t4, inb + outb)):
         print(f"conv3d_l1 {name:34s} B={B} {D}x{H}x{W}: {t:7.1f} us  {fl / t / 1e6:6.1f} TF/s (of 157 fp32 / 2500 bf16)  "
               f"{byts / 1e6:5.1f} MB compulsory -> {byts / t / 1e6:6.2f} TB/s of 8")
 
@@ -416,11 +359,7 @@ def main():
     if "pmc3d" in flt:
         conv3d_case(32, 16, 32, 64, wgrad=False)
         return
-    if flt == "stamp":
-        stamp_case(32, 32, 32, 24)
-        stamp_case(32, 16, 16, 16)
-        return
-    if "c4b" in flt:                # the two roofline shapes only (ablation sweeps)
+    if "c4b" in flt:                # the two roofline shapes only
         conv3d_dims_case(32, 32, 32, 24, 32, 64)
         conv3d_dims_case(32, 16, 16, 16, 32, 64)
         return
@@ -439,10 +378,6 @@ def main():
     if flt == "pmcs":               # layer 3 forward only (PMC passes of the streaming kernel)
         conv3d_dims_case(32, 8, 8, 8, 64, 128)
         return
-    if flt == "sstamp":
-        stream_stamp_case(32, 8, 8, 8, 64, 128)
-        stream_stamp_case(32, 8, 8, 8, 128, 64)
-        stream_stamp_case(32, 16, 16, 16, 64, 32)
     if "stream" in flt:
         # conv3d_stream.hip: layer 3 forward, its data gradient, layer 2's data gradient (C2, then config #4 volumes)
         conv3d_dims_case(32, 8, 8, 8, 64, 128)
