@@ -459,6 +459,26 @@ int mm_clip_loss_own_rows(const float* z_all, const float* logit_scale, float* s
                           int B, int Bg, int N, int row0, hipStream_t stream);
 int mm_clip_loss_ws_floats(int B, int Bg, int* floats_host, hipStream_t stream);
 
+/* ---- gallery-scale retrieval (csrc/retrieval.hip) ---------------------------
+ * For each query row q of Q [Nq][D] against gallery G [Ng][D] (fp32, row-major, 16-byte aligned; callers pass
+ * L2-normalised rows): s(q, j) = the ascending-d fmaf chain over d = 0..D-1 starting from +0 (what
+ * v_mfma_f32_32x32x2_f32 computes bit for bit; no bf16 anywhere: a rank is a comparison).
+ * ranks (nullable) int32 [Nq]: 1 + #{ j != pos[q] : s(q, j) >= s(q, pos[q]) } - ties count AGAINST the query, so an
+ *        encoder that scores every pair alike ranks Ng (mm_clip_loss_own_rows' in-batch top-1 counts a tie FOR it);
+ *        pos (nullable -> pos[q] = q, which needs Nq <= Ng) int32 [Nq] in [0, Ng).  A NaN s(q, pos[q]) (or a pos
+ *        outside the gallery) -> rank Ng; a NaN s(q, j) never counts.
+ * topk_idx int32 / topk_score fp32 [Nq][k] (k = 0: none, pointers may be NULL): the k best j by score descending,
+ *        equal scores by lower j; NaN never selected; unfilled slots (-1, -inf).  k <= MM_RETRIEVAL_KMAX, k <= Ng.
+ * ws = mm_retrieval_ws_floats(Nq, Ng, D, k) floats of scratch, no initialisation.  D % 4 == 0, 4 <= D <= 1024,
+ * 1 <= Nq, Ng <= MM_RETRIEVAL_NMAX.  Needs ranks or k > 0.  No Nq x Ng storage: scores live in accumulators and LDS.
+ * Deterministic: same inputs -> bit-identical outputs (integer counts, no float atomics).  Three launches on `stream`.
+ * Extension: the reference has no retrieval evaluator. */
+#define MM_RETRIEVAL_KMAX 16
+#define MM_RETRIEVAL_NMAX (1 << 20)
+int mm_retrieval(const float* Q, const float* G, const int* pos, int* ranks, int* topk_idx, float* topk_score,
+                 float* ws, int Nq, int Ng, int D, int k, hipStream_t stream);
+int mm_retrieval_ws_floats(int Nq, int Ng, int D, int k, int* floats_host, hipStream_t stream);
+
 /* ---- EnhancedPowerEncoder: its three Conv1d(C -> 64, k = 3 | 5 | 7) + BatchNorm1d(64) branches
  * (enhanced_models_v4.py:210-234, forward :258-266: torch.cat of the three) as ONE Conv1d(C -> 192, k = 7, p = 3) +
  * BatchNorm1d(192).  desc_host = HOST pointer to this descriptor (read at call time, like the tables of mm_prep_many):

@@ -33,7 +33,7 @@ import torch.nn as nn
 
 from . import _hip, dp, ops
 from .autograd import GradBag, contrastive_embed_bwd, deferred, erp_encoder_bwd, power_encoder_bwd, volume_encoder_bwd
-from .bridge_utils import EEGfMRIContrastiveBridge
+from .bridge_utils import EEGfMRIContrastiveBridge, retrieval_metrics
 from .enhanced_models_v4 import EnhancedERPEncoder
 from .fmri_utils import fMRIVolumeEncoder3D
 from .optim import FlatBucket
@@ -658,6 +658,56 @@ class BridgeTrainer(nn.Module):
         finally:
             self.train(was)
         return {"loss": loss, "top1_e2f": acc_e, "top1_f2e": acc_f}
+
+    @staticmethod
+    def _chunks(x: torch.Tensor, batch_size: int, device):
+        for i in range(0, x.shape[0], batch_size):
+            yield x[i:i + batch_size].to(device, non_blocking=True)
+
+    @torch.no_grad()
+    def embed(self, eeg: Optional[torch.Tensor] = None, fmri: Optional[torch.Tensor] = None, batch_size: int = 256):
+        """L2-normalised eval-mode embeddings of one or both modalities: ``ze`` (N_eeg, bridge_dim) and / or ``zf``
+        (N_fmri, bridge_dim) fp32 on this trainer's device (None for a modality not given).  Host or device input,
+        encoded ``batch_size`` items at a time; the projection head is the paired path's kernel with this modality's
+        head in both halves, so a row is the same bits as in the paired eval embedding of the same batch.  Restores the
+        train / eval state; draws no dropout seeds."""
+        if eeg is None and fmri is None:
+            raise ValueError("embed: give eeg and / or fmri")
+        if batch_size < 1:
+            raise ValueError("embed: batch_size must be >= 1")
+        dev = self._scal.device
+        br = self.head.bridge
+        was = self.training
+        self.eval()
+        ops.weights_changed()                      # graph replays bypass the python-side version counter
+        try:
+            ze = zf = None
+            if eeg is not None:
+                ze = torch.cat([ops.proj_embed_one(br, self.eeg_encoder(x), "eeg")
+                                for x in self._chunks(eeg, batch_size, dev)])
+            if fmri is not None:
+                zf = torch.cat([ops.proj_embed_one(br, self.fmri_encoder(x), "fmri")
+                                for x in self._chunks(fmri, batch_size, dev)])
+        finally:
+            self.train(was)
+        return ze, zf
+
+    @torch.no_grad()
+    def evaluate_retrieval(self, eeg, fmri, batch_size: int = 256, ks=(1, 5, 10), k: int = 0):
+        """held-out gallery retrieval: ``embed`` both modalities, then ``retrieval_metrics`` (pair i is the positive of
+        query i, both directions).  k > 0 adds ``topk``: {"eeg_to_fmri": (idx, score), "fmri_to_eeg": (idx, score)},
+        each (N, k).  Single process only: a sharded gallery is not supported."""
+        if self.world > 1:
+            raise ValueError("evaluate_retrieval: the gallery is not sharded; run it on one process (world size 1)")
+        if eeg.shape[0] != fmri.shape[0]:
+            raise ValueError(f"evaluate_retrieval: {eeg.shape[0]} EEG epochs but {fmri.shape[0]} fMRI volumes")
+        ze, zf = self.embed(eeg, fmri, batch_size)
+        out = retrieval_metrics(ze, zf, ks)
+        if k > 0:
+            _, ie, se = ops.retrieval(ze, zf, k=k, ranks=False)
+            _, if_, sf = ops.retrieval(zf, ze, k=k, ranks=False)
+            out["topk"] = {"eeg_to_fmri": (ie, se), "fmri_to_eeg": (if_, sf)}
+        return out
 
 
 class HostFeeder:

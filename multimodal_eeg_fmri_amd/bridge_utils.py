@@ -89,6 +89,31 @@ class EEGfMRIContrastiveBridge(nn.Module):
         return ops.clip_loss(ze, zf, self.logit_scale, group)
 
 
+def rank_summary(ranks: torch.Tensor, ks=(1, 5, 10)) -> dict:
+    """R@k (fraction of queries whose positive ranks <= k), median rank (numpy's convention: the mean of the two
+    middle values for an even count), mean rank and mean reciprocal rank of a vector of 1-based ranks."""
+    r = ranks.detach().cpu().double()
+    out = {f"R@{int(k)}": (r <= int(k)).double().mean().item() for k in ks}
+    out["median_rank"] = float(torch.quantile(r, 0.5).item()) if r.numel() else float("nan")
+    out["mean_rank"] = r.mean().item()
+    out["mrr"] = (1.0 / r).mean().item()
+    return out
+
+
+def retrieval_metrics(ze: torch.Tensor, zf: torch.Tensor, ks=(1, 5, 10)) -> dict:
+    """Gallery-scale CLIP-style retrieval of paired embeddings: pair i is the positive of query i.  Every EEG
+    embedding queries all fMRI embeddings and vice versa (mm_retrieval twice, Q and G swapped; no N x N score matrix).
+    A tie with the positive counts against the query (a collapsed encoder ranks N, not 1).
+    -> {"eeg_to_fmri": {R@k..., median_rank, mean_rank, mrr}, "fmri_to_eeg": {...}, "n": N, "chance": 1 / N}"""
+    if ze.shape != zf.shape or ze.dim() != 2:
+        raise ValueError(f"retrieval_metrics: ze {tuple(ze.shape)} and zf {tuple(zf.shape)} must be equal (N, D)")
+    ze, zf = ze.detach().float().contiguous(), zf.detach().float().contiguous()
+    r_ef, _, _ = ops.retrieval(ze, zf)
+    r_fe, _, _ = ops.retrieval(zf, ze)
+    n = ze.shape[0]
+    return {"eeg_to_fmri": rank_summary(r_ef, ks), "fmri_to_eeg": rank_summary(r_fe, ks), "n": n, "chance": 1.0 / n}
+
+
 class BridgeFeatureDataset(Dataset):
     """Aligns dict-of-tensor EEG/fMRI features and labels on ``int(subject)``."""
 

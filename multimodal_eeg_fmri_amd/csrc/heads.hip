@@ -406,6 +406,8 @@ __global__ __launch_bounds__(256) void clip_lse_kernel(const float* __restrict__
         ws[r] = lse_r;
         ws[Bg + r] = lse_c;
         ws[2 * Bg + r] = 0.5f * ((lse_r - s * diag) + (lse_c - s * sh.cc[r]));
+        // top-1: a tie with the row maximum counts FOR the pair (diag >= max).  mm_retrieval's rank counts a tie
+        // AGAINST the query (csrc/retrieval.hip), so a collapsed encoder ranks Ng there but scores top-1 = 1 here.
         ws[3 * Bg + r] = diag >= mxr ? 1.f : 0.f;
         ws[4 * Bg + r] = sh.cc[r] >= mxc ? 1.f : 0.f;
         // d loss_r / d logit_scale = s * 0.5 * (E_row[cos] - cos_rr + E_col[cos] - cos_rr)

@@ -1000,6 +1000,100 @@ def contrastive_embed_impl(bridge, eeg: torch.Tensor, fmri: torch.Tensor, traini
     return z, dict(xe=xe, xf=xf, z1=z1, hn=hn, stat=stat, z=z, nrm=nrm, B=B, N=N, p=p, seeds=(se, sf), bridge=bridge)
 
 
+def proj_embed_one(bridge, x: torch.Tensor, modality: str) -> torch.Tensor:
+    """eval-mode L2-normalised embedding (B, bridge_dim) of ONE modality's encoder features.  mm_proj_heads_fwd
+    unchanged, with that modality's head in both halves: each half is computed on its own, so the result is the
+    same bits as the same half of the paired embedding (contrastive_embed_impl); no dropout, no seed drawn."""
+    _need_gpu(x)
+    if modality not in ("eeg", "fmri"):
+        raise ValueError(f"proj_embed_one: modality must be 'eeg' or 'fmri', got {modality!r}")
+    B = x.shape[0]
+    N = bridge.bridge_dim
+    xc = x.detach().float().contiguous()
+    lin, ln = (bridge.eeg_proj if modality == "eeg" else bridge.fmri_proj)[:2]
+    z = _empty((B, 2 * N), _F32, x)
+    nrm = _empty((2, B), _F32, x)
+    z1 = _empty((2, B, N), _F32, x)
+    hn = _empty((2, B, N), _F32, x)
+    stat = _empty((2, B, 2), _F32, x)
+    _hip.call("mm_proj_heads_fwd", xc, lin.weight, lin.bias, ln.weight, ln.bias, xc.shape[1],
+              xc, lin.weight, lin.bias, ln.weight, ln.bias, xc.shape[1],
+              z1, hn, stat, z, nrm, B, N, float(ln.eps), 0.0, 0, 0, EP())
+    return z[:, :N].contiguous()
+
+
+_RETR_WS: Dict[Tuple[int, int, int, int], int] = {}
+
+
+def retrieval_ws_floats(nq: int, ng: int, d: int, k: int) -> int:
+    """floats of mm_retrieval's scratch (mm_retrieval_ws_floats: the kernel file owns the layout), cached per shape"""
+    key = (nq, ng, d, k)
+    n = _RETR_WS.get(key)
+    if n is None:
+        import ctypes
+        c = ctypes.c_int(0)
+        _hip.call("mm_retrieval_ws_floats", nq, ng, d, k, ctypes.addressof(c))
+        n = _RETR_WS[key] = c.value
+    return n
+
+
+def retrieval_kmax() -> int:
+    import re
+    m = re.search(r"^#define\s+MM_RETRIEVAL_KMAX\s+(\d+)", open(_hip.header_path()).read(), flags=re.M)
+    return int(m.group(1))
+
+
+def retrieval(q: torch.Tensor, g: torch.Tensor, positives: Optional[torch.Tensor] = None, k: int = 0,
+              ranks: bool = True):
+    """Rank of each query's positive among all gallery rows and / or its top-k matches (mm_retrieval), without an
+    Nq x Ng score matrix.  q (Nq, D), g (Ng, D): contiguous fp32 on the GPU (L2-normalised rows for cosine retrieval).
+    positives: int tensor (Nq,) of gallery indices (None: query i's positive is gallery row i).  Scores are exact fp32
+    dot products; a tie with the positive counts AGAINST the query (rank = 1 + #{j != pos : s_j >= s_pos}).
+    -> (ranks int64 (Nq,) | None, topk_idx int64 (Nq, k) | None, topk_score fp32 (Nq, k) | None); top-k is score
+    descending, equal scores by lower index, unfilled slots (-1, -inf)."""
+    for name, t in (("q", q), ("g", g)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 2:
+            raise ValueError(f"retrieval: {name} must be a 2-D tensor")
+        if not t.is_cuda:
+            raise _hip.HipLibraryError(f"retrieval: {name} is a CPU tensor; the HIP path has no CPU fallback")
+        if t.dtype != torch.float32:
+            raise ValueError(f"retrieval: {name} must be float32 (got {t.dtype})")
+        if not t.is_contiguous():
+            raise ValueError(f"retrieval: {name} must be contiguous")
+    _hip.load()
+    nq, d = q.shape
+    ng = g.shape[0]
+    if g.shape[1] != d:
+        raise ValueError(f"retrieval: q has D = {d}, g has D = {g.shape[1]}")
+    if q.device != g.device:
+        raise ValueError("retrieval: q and g are on different devices")
+    k = int(k)
+    if not 0 <= k <= min(retrieval_kmax(), ng):
+        raise ValueError(f"retrieval: k must be in [0, min({retrieval_kmax()}, Ng = {ng})] (got {k})")
+    if not ranks and k == 0:
+        raise ValueError("retrieval: nothing to compute (ranks=False and k = 0)")
+    pos = None
+    if ranks:
+        if positives is None:
+            if nq > ng:
+                raise ValueError(f"retrieval: without positives query i pairs with gallery row i, so Nq ({nq}) <= Ng ({ng})")
+        else:
+            if positives.shape != (nq,):
+                raise ValueError(f"retrieval: positives must have shape ({nq},)")
+            if positives.dtype.is_floating_point or positives.dtype == torch.bool:
+                raise ValueError("retrieval: positives must be an integer tensor")
+            pos = positives.to(device=q.device, dtype=torch.int32).contiguous()
+            if nq and bool(((pos < 0) | (pos >= ng)).any()):
+                raise ValueError(f"retrieval: positives must lie in [0, {ng})")
+    ws = torch.empty(retrieval_ws_floats(nq, ng, d, k), dtype=_F32, device=q.device)
+    r32 = torch.empty(nq, dtype=torch.int32, device=q.device) if ranks else None
+    ti = torch.empty((nq, k), dtype=torch.int32, device=q.device) if k else None
+    ts = torch.empty((nq, k), dtype=_F32, device=q.device) if k else None
+    with torch.cuda.device(q.device):
+        _hip.call("mm_retrieval", q, g, pos, r32, ti, ts, ws, nq, ng, d, k)
+    return (r32.long() if ranks else None, ti.long() if k else None, ts)
+
+
 def contrastive_embed(bridge, eeg, fmri, training):
     _need_gpu(eeg, fmri)
     from .autograd import ContrastiveEmbedFn

@@ -317,8 +317,51 @@ def step_case(config="c2", steps=4):
     print(f"step case {config}: {steps} steps, loss {out['loss'].item():.4f}")
 
 
+FP32_MFMA_PEAK_TF = 157.3      # MI355X fp32-input MFMA peak (MI355X_MICROARCH.md)
+
+
+def retr_case(nq, ng, d, k, vs_torch=False):
+    """mm_retrieval (ranks + top-k): time, TF/s = 2 Nq Ng D / time, share of the fp32 MFMA peak.  vs_torch: also the
+    torch composition (fp32 q @ g.T, comparison, topk) and a check that its ranks agree within the fp64 tie band"""
+    gen = torch.Generator(device="cuda").manual_seed(7)
+    q = torch.nn.functional.normalize(torch.randn(nq, d, device="cuda", generator=gen), dim=1).contiguous()
+    g = torch.nn.functional.normalize(torch.randn(ng, d, device="cuda", generator=gen), dim=1).contiguous()
+    us = timeit(lambda: ops.retrieval(q, g, k=k), iters=5, rounds=3)
+    tf = 2.0 * nq * ng * d / (us * 1e-6) / 1e12
+    print(f"retr Nq={nq} Ng={ng} D={d} k={k}: {us:9.1f} us  {tf:6.1f} TF/s  {tf / FP32_MFMA_PEAK_TF:5.3f} of fp32 MFMA peak")
+    # where the time goes: the same launch with one epilogue only
+    ur = timeit(lambda: ops.retrieval(q, g), iters=5, rounds=3)
+    uk = timeit(lambda: ops.retrieval(q, g, k=k, ranks=False), iters=5, rounds=3)
+    print(f"  ranks only: {ur:9.1f} us ({2.0 * nq * ng * d / (ur * 1e-6) / 1e12:6.1f} TF/s)   top-k only: {uk:9.1f} us")
+    if not vs_torch:
+        return
+
+    def torch_way():
+        s = q @ g.T
+        sp = s.diagonal()
+        r = 1 + (s >= sp[:, None]).sum(1) - 1
+        return r, s.topk(k, dim=1)
+    ut = timeit(torch_way, iters=5, rounds=3)
+    print(f"  torch composition (fp32 GEMM + compare + topk): {ut:9.1f} us  -> kernel {ut / us:4.2f}x faster")
+    r, _, _ = ops.retrieval(q, g)
+    rt, _ = torch_way()
+    rows = torch.arange(0, nq, max(1, nq // 512), device="cuda")
+    S = q[rows].double() @ g.double().T
+    sp = S[torch.arange(len(rows), device="cuda"), rows]
+    lo = 1 + (S > sp[:, None] + 1e-6).sum(1)
+    hi = (S >= sp[:, None] - 1e-6).sum(1)
+    ok = all(((x[rows] >= lo) & (x[rows] <= hi)).all().item() for x in (r, rt))
+    print(f"  ranks of kernel and torch within the fp64 tie band on {len(rows)} queries: {ok}; "
+          f"equal on {(r == rt).float().mean().item():.6f} of all queries")
+    assert ok
+
+
 def main():
     flt = sys.argv[1] if len(sys.argv) > 1 else ""
+    if flt == "retr":
+        retr_case(16384, 16384, 128, 10, vs_torch=True)
+        retr_case(65536, 65536, 128, 10)
+        return
     if flt in ("step", "step5"):
         step_case("c5" if flt == "step5" else "c2")
         return
