@@ -445,3 +445,45 @@ def test_bench_self_launch_relays_a_failing_rank():
     assert r.returncode != 0, r.stdout[-800:] + r.stderr[-800:]
     assert not [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert "AssertionError" not in r.stderr, r.stderr[-1500:]
+
+
+# every `int mm_*` of include/mmeeg_hip.h is called by name in some tests/test_*_gpu.py, or is listed here with the reason
+KERNEL_TEST_EXEMPT = {
+    "mm_abi_version": "host-only: returns a constant (test_library_exports_every_declared_symbol)",
+    "mm_debug_stamp": "diagnostic: wall-clock stamps for bench --stamps and tools/",
+    "mm_clip_loss_ws_floats": "host-only: workspace size",
+    "mm_retrieval_ws_floats": "host-only: workspace size (tests/test_retrieval_host.py)",
+    "mm_retrieval": "covered by test_exact_contract_on_representable_inputs (through ops.retrieval)",
+    "mm_scatter_many": "covered by test_batched_launches_equal_their_single_forms",
+    "mm_reduce_many": "covered by test_batched_launches_equal_their_single_forms",
+    "mm_add_pe": "covered by test_a1_positional_encoding_standalone_vs_reference_golden (through ops.add_positional)",
+    "mm_power_merge": "covered by test_power_merge_modes (through ops.power_merge_call)",
+}
+
+
+def _header_entry_points():
+    import re
+    text = re.sub(r"/\*.*?\*/", " ", open(_hip.header_path()).read(), flags=re.S)
+    return set(re.findall(r"\bint\s+(mm_\w+)\s*\(", text))
+
+
+def test_every_entry_point_has_a_kernel_level_test_or_a_listed_reason():
+    """a new entry point without a GPU test that names it fails here, on the CPU; so does an exemption for a symbol the
+    header no longer declares, or one whose named covering test does not exist"""
+    import glob
+    import re
+    declared = _header_entry_points()
+    assert set(_hip.parse_header()) <= declared and "mm_abi_version" in declared
+    stale = sorted(set(KERNEL_TEST_EXEMPT) - declared)
+    assert not stale, f"exemptions for symbols the header does not declare: {stale}"
+    sources = {}
+    for path in glob.glob(os.path.join(ROOT, "tests", "test_*.py")):
+        sources[os.path.basename(path)] = open(path).read()
+    gpu_text = "".join(t for name, t in sources.items() if name.endswith("_gpu.py"))
+    untested = sorted(n for n in declared if f'"{n}"' not in gpu_text and n not in KERNEL_TEST_EXEMPT)
+    assert not untested, f"entry points no tests/test_*_gpu.py calls by name and no exemption covers: {untested}"
+    for name, reason in KERNEL_TEST_EXEMPT.items():
+        assert reason.split(":")[0] in ("host-only", "diagnostic") or reason.startswith("covered by test_"), (name, reason)
+        if reason.startswith("covered by "):
+            test = reason.split()[2]
+            assert any(re.search(rf"^def {test}\(", t, flags=re.M) for t in sources.values()), (name, test)
