@@ -1,0 +1,384 @@
+"""Checkpoint, resume and the epoch loop of the contrastive bridge trainer (`BridgeTrainer`).
+
+The file is the container of the reference's loops and of `FlexibleTrainer.save_checkpoint` -
+``{epoch, model_state_dict, optimizer_state_dict, scheduler_state_dict, metrics}`` - plus one key,
+``bridge_trainer_state``, that holds what the reference's containers cannot express and an exact resume needs:
+
+* ``model_state_dict``: the trainer's unchanged ``nn.Module.state_dict()`` (CPU copies);
+* ``optimizer_state_dict``: the layout of ``torch.optim.AdamW.state_dict()`` over
+  ``[p for p in trainer.parameters() if p.requires_grad]`` in ``parameters()`` order (the flat bucket is laid out by
+  layer group, so its slices are mapped back to that order); the frozen half of the bridge has no entry;
+* ``bridge_trainer_state``: the optimizer words (step count, lr, ...), the hyperparameters, the EEG branch kind, the
+  model's shapes, the world size, the bucket layout, the dropout stream and the state of `fit`.
+
+The step itself is untouched: saving and loading are copies, `fit` only calls `train_step` and `embed`.
+
+Reference behaviour: the epoch loop with schedule, evaluation, early stop and best-state restore
+(run_training_lite.py:465-520); best-state copy / restore (_test_bridge.py:876-892); loading ``model_state_dict`` or
+a bare state dict (_test_bridge.py:499-504).
+"""
+from __future__ import annotations
+
+import math
+import os
+import tempfile
+from typing import Callable, Optional, Union
+
+import torch
+
+from . import dp, ops
+
+FORMAT = 1
+CONTAINER_KEYS = ("epoch", "model_state_dict", "optimizer_state_dict", "scheduler_state_dict", "metrics",
+                  "bridge_trainer_state")
+
+
+class _LRWord(dict):
+    """``param_groups[0]`` of the optimizer the schedule steps: setting ``"lr"`` writes the trainer's LR word"""
+
+    def __init__(self, trainer):
+        super().__init__(lr=float(trainer.lr))
+        self._trainer = trainer
+
+    def __setitem__(self, key, value):
+        super().__setitem__(key, value)
+        if key == "lr":
+            self._trainer.set_lr(float(value))
+
+
+class _LROptimizer:
+    def __init__(self, trainer):
+        self.param_groups = [_LRWord(trainer)]
+
+
+def _cpu(t: torch.Tensor) -> torch.Tensor:
+    return t.detach().to("cpu", copy=True)
+
+
+def monitor_value(metrics: dict, monitor: Union[str, Callable[[dict], float]]) -> float:
+    """``"mean_R@1"``: the mean of R@1 over both retrieval directions; ``"<direction>.<key>"`` (e.g.
+    ``"fmri_to_eeg.mrr"``): one entry of `retrieval_metrics`; a callable: ``monitor(metrics)``"""
+    if callable(monitor):
+        return float(monitor(metrics))
+    if monitor == "mean_R@1":
+        return 0.5 * (metrics["eeg_to_fmri"]["R@1"] + metrics["fmri_to_eeg"]["R@1"])
+    d, _, k = monitor.partition(".")
+    return float(metrics[d][k] if k else metrics[d])
+
+
+class TrainerCheckpointMixin:
+    """`BridgeTrainer`'s checkpoint / resume / `fit` surface (the trainer's attributes are used directly)."""
+
+    # ------------------------------------------------------------------ layout
+    def optimizer_param_map(self):
+        """[(index in the AdamW layout, name, parameter, slice of the flat bucket)]: the trainable parameters in
+        ``parameters()`` order, each with its range of ``bucket.p / m / v`` (the bucket is in layer-group order)"""
+        offs, o = {}, 0
+        for p in self.bucket.params:
+            offs[id(p)] = slice(o, o + p.numel())
+            o += p.numel()
+        names = {id(p): n for n, p in self.named_parameters()}
+        trainable = [p for p in self.parameters() if p.requires_grad]
+        if {id(p) for p in trainable} != set(offs):
+            raise RuntimeError("BridgeTrainer: the trainable parameters and the flat bucket disagree")
+        return [(i, names[id(p)], p, offs[id(p)]) for i, p in enumerate(trainable)]
+
+    def _layout(self) -> dict:
+        return {"eeg_kind": self._eeg_kind,
+                "shapes": {k: list(v.shape) for k, v in self.state_dict().items()},
+                "bucket_n": int(self.bucket.n),
+                "groups": [[n, r, int(lo), int(hi)] for n, r, lo, hi in self.groups],
+                "world": int(self.world)}
+
+    # ------------------------------------------------------------------ dropout stream
+    def _dropout_stream_state(self) -> dict:
+        """Graph mode with a captured step: the seeds were fixed when the capture began (its two warm-up steps draw
+        first), so the counter at that point + the device epoch word the replays mix in.  Otherwise: the counter."""
+        c = self._cap
+        if self.mode == "graph" and c is not None and "seed_step" in c:
+            return {"kind": "graph", "base": int(c["seed_base"]), "step": int(c["seed_step"]),
+                    "epoch_word": int(c["epoch"].item())}
+        return {"kind": "counter", "base": int(ops._seed_state["base"]), "step": int(ops._seed_state["step"]),
+                "epoch_word": None}
+
+    def _drop_capture(self):
+        """forget the captured step (the next graph-mode `train_step` captures anew); its epoch word is uninstalled"""
+        c = self._cap
+        if c is None:
+            return
+        if torch.cuda.is_available():
+            torch.cuda.synchronize()
+        if ops.EP() is c["epoch"]:
+            ops.set_seed_epoch(None)
+        self._cap = None
+        self._works = []
+        self.capture_mode = None
+
+    # ------------------------------------------------------------------ state
+    def checkpoint_state(self, epoch: Optional[int] = None, metrics: Optional[dict] = None, scheduler=None) -> dict:
+        """the checkpoint container (CPU tensors, dicts, lists and Python scalars: loads with ``weights_only=True``)"""
+        b = self.bucket
+        words = _cpu(b.state)
+        step = float(words[0])
+        state = {}
+        for i, _, p, sl in self.optimizer_param_map():
+            state[i] = {"step": torch.tensor(step, dtype=torch.float32),
+                        "exp_avg": _cpu(b.m[sl]).view(p.shape), "exp_avg_sq": _cpu(b.v[sl]).view(p.shape)}
+        group = {"lr": float(self.lr), "betas": (float(self.betas[0]), float(self.betas[1])), "eps": float(self.eps),
+                 "weight_decay": float(self.weight_decay), "amsgrad": False, "maximize": False, "foreach": None,
+                 "capturable": False, "differentiable": False, "fused": None, "decoupled_weight_decay": True,
+                 "params": list(range(len(state)))}
+        bts = {"format": FORMAT, "optimizer_words": words, "step": step, "lr": float(self.lr),
+               "hyper": {"betas": [float(self.betas[0]), float(self.betas[1])], "eps": float(self.eps),
+                         "weight_decay": float(self.weight_decay), "grad_clip": float(self.grad_clip)},
+               "dropout": self._dropout_stream_state(), "fit": getattr(self, "_fit_state", None)}
+        bts.update(self._layout())
+        return {"epoch": epoch, "model_state_dict": {k: _cpu(v) for k, v in self.state_dict().items()},
+                "optimizer_state_dict": {"state": state, "param_groups": [group]},
+                "scheduler_state_dict": scheduler.state_dict() if scheduler is not None else None,
+                "metrics": metrics, "bridge_trainer_state": bts}
+
+    def _check_compatible(self, sd: dict):
+        """ValueError naming the first field that differs; touches nothing"""
+        missing = [k for k in CONTAINER_KEYS if k not in sd]
+        if missing:
+            raise ValueError(f"load_checkpoint_state: not a BridgeTrainer checkpoint (missing {missing})")
+        bts = sd["bridge_trainer_state"]
+        if bts.get("format") != FORMAT:
+            raise ValueError(f"load_checkpoint_state: format {bts.get('format')} (this trainer reads {FORMAT})")
+        mine = self._layout()
+
+        def same(*fields):
+            for field in fields:
+                if bts.get(field) != mine[field]:
+                    raise ValueError(f"load_checkpoint_state: {field} differs: checkpoint {bts.get(field)!r}, "
+                                     f"trainer {mine[field]!r}")
+        same("eeg_kind", "world")
+        theirs = bts.get("shapes", {})
+        for k, shp in mine["shapes"].items():
+            if theirs.get(k) != shp:
+                raise ValueError(f"load_checkpoint_state: shapes differ at {k}: checkpoint {theirs.get(k)}, trainer {shp}")
+        if set(theirs) != set(mine["shapes"]):
+            raise ValueError(f"load_checkpoint_state: shapes differ: extra keys {sorted(set(theirs) - set(mine['shapes']))}")
+        same("bucket_n", "groups")
+        msd = sd["model_state_dict"]
+        for k, shp in mine["shapes"].items():
+            if k not in msd or list(msd[k].shape) != shp:
+                raise ValueError(f"load_checkpoint_state: model_state_dict differs at {k}")
+        osd = sd["optimizer_state_dict"]
+        pmap = self.optimizer_param_map()
+        if len(osd["param_groups"]) != 1 or len(osd["param_groups"][0]["params"]) != len(pmap):
+            raise ValueError("load_checkpoint_state: optimizer_state_dict has a different parameter group")
+        for i, name, p, _ in pmap:
+            st = osd["state"].get(i)
+            if st is None or tuple(st["exp_avg"].shape) != tuple(p.shape) or tuple(st["exp_avg_sq"].shape) != tuple(p.shape):
+                raise ValueError(f"load_checkpoint_state: optimizer state differs at parameter {i} ({name})")
+        if tuple(bts["optimizer_words"].shape) != tuple(self.bucket.state.shape):
+            raise ValueError("load_checkpoint_state: optimizer_words differ in size")
+
+    @torch.no_grad()
+    def _copy_model_state(self, msd: dict):
+        """in place: parameters are views of ``bucket.p`` and captured graphs hold the pointers"""
+        for k, t in self.state_dict(keep_vars=True).items():
+            t.copy_(msd[k])
+
+    @torch.no_grad()
+    def load_checkpoint_state(self, sd: dict) -> None:
+        """continue bit for bit from `checkpoint_state`: parameters, BatchNorm buffers, Adam moments, optimizer words,
+        hyperparameters and the dropout stream, all copied in place.  Any captured step is dropped; the next
+        graph-mode `train_step` captures again with the checkpoint's seeds and epoch word.  The process-global dropout
+        counter (``ops._seed_state``) is set from the checkpoint.  A checkpoint of another EEG branch, shape, bucket
+        layout or world size raises ValueError before anything is touched."""
+        self._check_compatible(sd)
+        bts = sd["bridge_trainer_state"]
+        b = self.bucket
+        self._drop_capture()
+        self._copy_model_state(sd["model_state_dict"])
+        st = sd["optimizer_state_dict"]["state"]
+        for i, _, _, sl in self.optimizer_param_map():
+            b.m[sl].copy_(st[i]["exp_avg"].reshape(-1))
+            b.v[sl].copy_(st[i]["exp_avg_sq"].reshape(-1))
+        b.state.copy_(bts["optimizer_words"])
+        b.g.zero_()
+        h = bts["hyper"]
+        self.betas, self.eps = (h["betas"][0], h["betas"][1]), h["eps"]
+        self.weight_decay, self.grad_clip = h["weight_decay"], h["grad_clip"]
+        self.lr = float(bts["lr"])
+        d = bts["dropout"]
+        ops._seed_state["base"] = int(d["base"])
+        ops._seed_state["step"] = int(d["step"])
+        self._pending_epoch_word = d["epoch_word"] if d["kind"] == "graph" else None
+        ops.weights_changed()
+
+    # ------------------------------------------------------------------ files
+    def _barrier(self):
+        if dp.world_size(self.group) > 1:
+            import torch.distributed as dist
+            dist.barrier(group=dp._control_group(self.group))
+
+    def save_checkpoint(self, path: str, epoch: int, metrics: Optional[dict] = None, scheduler=None) -> None:
+        """write `checkpoint_state` to ``path`` atomically (a temporary file in the same directory, then
+        ``os.replace``).  Under data parallelism this is collective: rank 0 writes (parameters and moments are the
+        same on every rank; the BatchNorm running statistics saved are rank 0's), then all ranks meet at a barrier."""
+        if dp.rank(self.group) == 0:
+            ck = self.checkpoint_state(epoch, metrics, scheduler)
+            d = os.path.dirname(os.path.abspath(path))
+            fd, tmp = tempfile.mkstemp(prefix="." + os.path.basename(path) + ".", suffix=".tmp", dir=d)
+            try:
+                with os.fdopen(fd, "wb") as f:
+                    torch.save(ck, f)
+                    f.flush()
+                    os.fsync(f.fileno())
+                os.replace(tmp, path)
+            except BaseException:
+                if os.path.exists(tmp):
+                    os.unlink(tmp)
+                raise
+        self._barrier()
+
+    def load_checkpoint(self, path: str, scheduler=None):
+        """-> (epoch, metrics).  A `save_checkpoint` file restores everything (`load_checkpoint_state`); a
+        reference-style container without ``bridge_trainer_state`` or a bare state dict restores the model only.
+        ``scheduler``: receives ``scheduler_state_dict`` when the file has one."""
+        ck = torch.load(path, map_location="cpu", weights_only=True)
+        if "model_state_dict" not in ck:                       # a bare state dict (_test_bridge.py:499-504)
+            self.load_state_dict(ck)
+            ops.weights_changed()
+            return None, None
+        if "bridge_trainer_state" in ck:
+            self.load_checkpoint_state(ck)
+        else:
+            self.load_state_dict(ck["model_state_dict"])
+            ops.weights_changed()
+        if scheduler is not None and ck.get("scheduler_state_dict") is not None:
+            scheduler.load_state_dict(ck["scheduler_state_dict"])
+        return ck.get("epoch"), ck.get("metrics")
+
+    # ------------------------------------------------------------------ epoch loop
+    def _best_copy(self):
+        return self.bucket.p.clone(), [t.clone() for t in self.buffers()]
+
+    def _best_copy_from(self, msd: dict):
+        names = {id(p): n for n, p in self.named_parameters()}
+        dev = self.bucket.p.device
+        p = torch.cat([msd[names[id(q)]].reshape(-1) for q in self.bucket.params]).to(dev)
+        return p, [msd[n].to(dev) for n, _ in self.named_buffers()]
+
+    @torch.no_grad()
+    def _restore_best(self, best):
+        p, bufs = best
+        self.bucket.p.copy_(p)
+        for t, s in zip(self.buffers(), bufs):
+            t.copy_(s)
+        ops.weights_changed()
+
+    def _validate(self, val, monitor, batch_size):
+        from .bridge_utils import retrieval_metrics
+        s0 = ops._seed_state["step"]
+        ze, zf = self.embed(val[0], val[1], batch_size)
+        metrics = retrieval_metrics(ze, zf)
+        assert ops._seed_state["step"] == s0, "validation drew dropout seeds"
+        return metrics, monitor_value(metrics, monitor)
+
+    def fit(self, train, epochs: int, *, val=None, warmup_epochs: int = 3, min_lr: float = 1e-6,
+            monitor: Union[str, Callable[[dict], float]] = "mean_R@1", mode: str = "max", patience: int = 15,
+            min_delta: float = 1e-3, eval_every: int = 1, checkpoint_dir: Optional[str] = None, resume: bool = False,
+            val_batch_size: int = 256):
+        """The reference's epoch loop (run_training_lite.py:465-520) on the contrastive step -> per-epoch history.
+
+        ``train``: an iterable of (eeg, fmri) batches re-iterated every epoch, or ``epoch -> iterable`` (1-based).  Every
+        batch goes through `train_step`; in graph mode keep one batch shape (a new shape captures the step again).
+        Schedule: `CosineAnnealingWarmup(warmup_epochs, epochs, min_lr)` from the trainer's current lr, stepped after each
+        epoch's training as the reference does (epoch 1 runs at the base rate, epoch e > 1 at ``_lr_at(e - 1)``).
+        ``val = (eeg, fmri)``: every ``eval_every`` epochs (and after the last) `embed` + `retrieval_metrics`; the
+        monitored value (``monitor_value``; ``mode`` "max" or "min") drives `EarlyStopping(patience, min_delta)` and the
+        best state: on a strict improvement a device copy of the parameters and buffers is kept (and ``best.pt`` written
+        when ``checkpoint_dir`` is set); the best model is restored in place at the end (the optimizer state is not,
+        as in the reference).  ``last.pt`` is written after every epoch; ``resume=True`` continues from it at the
+        epoch boundary (the same ``train``, ``val`` and arguments must be given).
+        Data parallel: rank 0 validates and broadcasts the metrics, the monitored value and its decisions; every rank
+        acts on them.  Pass the same ``val`` on every rank (only rank 0 reads it)."""
+        from .crossmodal_v4_enhancements import CosineAnnealingWarmup, EarlyStopping
+        if epochs < 1 or warmup_epochs < 0 or warmup_epochs >= epochs:
+            raise ValueError(f"fit: need 0 <= warmup_epochs < epochs (got {warmup_epochs}, {epochs})")
+        if eval_every < 1:
+            raise ValueError("fit: eval_every must be >= 1")
+        if mode not in ("max", "min"):
+            raise ValueError("fit: mode is 'max' or 'min'")
+        if resume and checkpoint_dir is None:
+            raise ValueError("fit: resume=True needs checkpoint_dir")
+        if checkpoint_dir is not None and dp.rank(self.group) == 0:
+            os.makedirs(checkpoint_dir, exist_ok=True)
+        last = os.path.join(checkpoint_dir, "last.pt") if checkpoint_dir else None
+        best_path = os.path.join(checkpoint_dir, "best.pt") if checkpoint_dir else None
+        sched = CosineAnnealingWarmup(_LROptimizer(self), warmup_epochs, epochs, min_lr)
+        stopper = EarlyStopping(patience, min_delta, mode)
+        history, best_score, best_epoch, best, start, stopped = [], None, None, None, 1, False
+        if resume and os.path.exists(last):
+            ck = torch.load(last, map_location="cpu", weights_only=True)
+            fs = ck.get("bridge_trainer_state", {}).get("fit")
+            if fs is None:
+                raise ValueError(f"fit: {last} was not written by fit")
+            self.load_checkpoint_state(ck)
+            ss = ck["scheduler_state_dict"]
+            sched.current_epoch, sched.base_lr = ss["current_epoch"], ss["base_lr"]
+            stopper.counter, stopper.best_score, stopper.should_stop = fs["stopper"]
+            history, best_score, best_epoch, stopped = list(fs["history"]), fs["best_score"], fs["best_epoch"], fs["stopped"]
+            start = ck["epoch"] + 1
+            if best_epoch is not None:
+                best = self._best_copy_from(torch.load(best_path, map_location="cpu", weights_only=True)["model_state_dict"])
+        dev = self.bucket.p.device
+        try:
+            for epoch in range(start, epochs + 1):
+                if stopped:
+                    break
+                lr = float(self.lr)
+                total = torch.zeros((), dtype=torch.float64, device=dev)
+                n = 0
+                for eeg, fmri in (train(epoch) if callable(train) else train):
+                    total += self.train_step(eeg, fmri)["loss"]
+                    n += 1
+                sched.step()
+                entry = {"epoch": epoch, "lr": lr, "steps": n, "train_loss": total.item() / max(n, 1),
+                         "val": None, "monitor": None, "improved": False, "stop": False}
+                if val is not None and (epoch % eval_every == 0 or epoch == epochs):
+                    entry.update(self._decide(val, monitor, mode, val_batch_size, stopper, best_score))
+                    if entry["improved"]:
+                        best_score, best_epoch = entry["monitor"], epoch
+                        best = self._best_copy()
+                    stopped = entry["stop"]
+                history.append(entry)
+                self._fit_state = {"history": history, "best_score": best_score, "best_epoch": best_epoch,
+                                   "stopped": stopped, "epochs": epochs,
+                                   "stopper": [stopper.counter, stopper.best_score, stopper.should_stop]}
+                if checkpoint_dir is not None:
+                    if entry["improved"]:
+                        self.save_checkpoint(best_path, epoch, entry["val"], sched)
+                    self.save_checkpoint(last, epoch, entry["val"], sched)
+        finally:
+            self._fit_state = None
+        if best is not None:
+            self._restore_best(best)
+        return history
+
+    def _decide(self, val, monitor, mode, batch_size, stopper, best_score) -> dict:
+        """rank 0 validates; every rank takes rank 0's metrics, monitored value, improvement and stop"""
+        metrics = score = None
+        if dp.rank(self.group) == 0:
+            metrics, score = self._validate(val, monitor, batch_size)
+        if dp.world_size(self.group) > 1:
+            import torch.distributed as dist
+            ctrl = dp._control_group(self.group)
+            box = [metrics, score]
+            dist.broadcast_object_list(box, src=dist.get_global_rank(ctrl, 0), group=ctrl)
+            metrics, score = box
+        improved = not math.isnan(score) and (best_score is None or (score > best_score if mode == "max" else score < best_score))
+        stop = bool(stopper(score))
+        if dp.world_size(self.group) > 1:
+            import torch.distributed as dist
+            ctrl = dp._control_group(self.group)
+            flags = torch.tensor([int(improved), int(stop)], dtype=torch.int64)
+            dist.broadcast(flags, src=dist.get_global_rank(ctrl, 0), group=ctrl)
+            improved, stop = bool(flags[0]), bool(flags[1])
+            stopper.should_stop = stop
+        return {"val": metrics, "monitor": score, "improved": improved, "stop": stop}

@@ -33,13 +33,14 @@ import torch.nn as nn
 
 from . import _hip, dp, ops
 from .autograd import GradBag, contrastive_embed_bwd, deferred, erp_encoder_bwd, power_encoder_bwd, volume_encoder_bwd
+from .bridge_checkpoint import TrainerCheckpointMixin
 from .bridge_utils import EEGfMRIContrastiveBridge, retrieval_metrics
 from .enhanced_models_v4 import EnhancedERPEncoder
 from .fmri_utils import fMRIVolumeEncoder3D
 from .optim import FlatBucket
 
 
-class BridgeTrainer(nn.Module):
+class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
     def __init__(self, eeg_channels: int = 64, hidden_dim: int = 128, fmri_dim: int = 64,
                  bridge_dim: int = 128, dropout: float = 0.3, lr: float = 1e-4,
                  weight_decay: float = 1e-4, grad_clip: float = 1.0, betas=(0.9, 0.999),
@@ -66,6 +67,8 @@ class BridgeTrainer(nn.Module):
         self.two_streams = True
         self.mode = mode
         self._cap = None
+        self._pending_epoch_word = None               # dropout epoch word for the next capture (load_checkpoint_state)
+        self._fit_state = None                        # early-stopping / best-metric state while `fit` runs
         self._weight_list = None                      # recorded by the first manual step
         self._arena_need = None                       # floats of scratch one step uses (None: clear all)
         self.stamps = None                            # int64[16] device buffer when phase stamps are wanted
@@ -541,7 +544,13 @@ class BridgeTrainer(nn.Module):
 
     def _step_graph(self, eeg, fmri):
         if self._cap is None or self._cap["eeg"].shape != eeg.shape or self._cap["fmri"].shape != fmri.shape:
+            step0, base0 = ops._seed_state["step"], ops._seed_state["base"]
             self._capture(eeg, fmri)
+            # the dropout seeds of this capture were drawn from here on (checkpoint_state)
+            self._cap["seed_step"], self._cap["seed_base"] = step0, base0
+            if self._pending_epoch_word is not None:      # resumed: the replays go on from the saved epoch word
+                self._cap["epoch"].fill_(self._pending_epoch_word)
+                self._pending_epoch_word = None
         c = self._cap
         ce, cf = eeg.data_ptr() != c["eeg"].data_ptr(), fmri.data_ptr() != c["fmri"].data_ptr()
         if (c["xb"] is not None and ce and cf and eeg.dtype == torch.float32 and fmri.dtype == torch.float32 and eeg.is_cuda and fmri.is_cuda

@@ -80,6 +80,14 @@ class CosineAnnealingWarmup:
     def get_lr(self) -> float:
         return self.optimizer.param_groups[0]["lr"]
 
+    def state_dict(self) -> dict:
+        return {"warmup_epochs": self.warmup_epochs, "total_epochs": self.total_epochs, "min_lr": self.min_lr,
+                "base_lr": self.base_lr, "current_epoch": self.current_epoch}
+
+    def load_state_dict(self, sd: dict) -> None:
+        for k in ("warmup_epochs", "total_epochs", "min_lr", "base_lr", "current_epoch"):
+            setattr(self, k, sd[k])
+
 
 class EarlyStopping:
     """Stop after ``patience`` calls without a > ``min_delta`` improvement."""
