@@ -214,7 +214,7 @@ int mm_bn_act_bwd_apply(const float* y, const float* out4, const void* dout_bf16
                         int S, int N, int act, int pool, int drop_first, float drop_p, uint32_t seed,
                         float drop2_p, uint32_t seed2, const uint32_t* seed_epoch, int train, int sums_nrep, hipStream_t stream);
 
-/* ---- LayerNorm (nn.LayerNorm, enhanced_models_v4.py:80-81; bridge_utils.py:36,42,62) */
+/* ---- LayerNorm (nn.LayerNorm, enhanced_models_v4.py:80-81; bridge_utils.py:36,42,62); D = a multiple of 32 up to 512, or 1024 */
 int mm_layernorm_fwd(const float* x, const float* gamma, const float* beta, void* out_bf16,
                      float* out_f32, float* stat, int M, int D, float eps, hipStream_t stream);
 /* dgb_repl = zeroed accumulator workspace [32][2][D]: {dgamma, dbeta} partial sums;
@@ -316,6 +316,16 @@ int mm_attn_bwd(const void* qkv, const void* out, const void* dout, const float*
                 float* delta_ws, int B, int L, int H, int head_dim, float scale, float drop_p,
                 uint32_t seed, const uint32_t* seed_epoch, const float* attn_mask, int attn_mask_per_head,
                 hipStream_t stream);
+/* The same for every head_dim that is a multiple of 8 in [16, 64] (32 included): same arguments, layouts, mask forms
+ * and dropout mask as mm_attn_fwd / mm_attn_bwd.  Any other head_dim is refused (MM_ERR_ARG, "head_dim" in
+ * mm_last_error()) before anything is launched. */
+int mm_attn_fwd_hd(const void* qkv, void* out, float* lse, int B, int L, int H, int head_dim,
+                   float scale, float drop_p, uint32_t seed, const uint32_t* seed_epoch,
+                   const float* attn_mask, int attn_mask_per_head, hipStream_t stream);
+int mm_attn_bwd_hd(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv,
+                   float* delta_ws, int B, int L, int H, int head_dim, float scale, float drop_p,
+                   uint32_t seed, const uint32_t* seed_epoch, const float* attn_mask, int attn_mask_per_head,
+                   hipStream_t stream);
 
 /* ---- small reductions / elementwise --------------------------------------- */
 int mm_colsum(const void* a_bf16, const float* a_f32, float* out, int M, int N, hipStream_t stream);

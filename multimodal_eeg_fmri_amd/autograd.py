@@ -416,7 +416,8 @@ def transformer_block_bwd(bag: GradBag, s: dict, dx2: torch.Tensor, dy2=None, em
     delta = _empty((B, blk.nhead, L), _F32, dx2)
     dh = D // blk.nhead
     pa, sa = s.get("attn_drop", (0.0, 0))
-    _hip.call("mm_attn_bwd", s["qkv"], s["o"], do, s["lse"], dqkv, delta, B, L, blk.nhead, dh, float(dh) ** -0.5,
+    entry = ops.attn_entry(D, blk.nhead, "bwd")
+    _hip.call(entry, s["qkv"], s["o"], do, s["lse"], dqkv, delta, B, L, blk.nhead, dh, float(dh) ** -0.5,
               float(pa), int(sa), ops.EP(), s.get("mask"), ops.attn_mask_per_head(s.get("mask"), B, blk.nhead, L))
     dx0 = _empty((M, D), _F32, dx2)
     emit = _empty((M, D), _BF, dx2) if emit_for is not None else None

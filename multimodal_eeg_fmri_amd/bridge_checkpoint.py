@@ -9,7 +9,8 @@ The file is the container of the reference's loops and of `FlexibleTrainer.save_
   ``[p for p in trainer.parameters() if p.requires_grad]`` in ``parameters()`` order (the flat bucket is laid out by
   layer group, so its slices are mapped back to that order); the frozen half of the bridge has no entry;
 * ``bridge_trainer_state``: the optimizer words (step count, lr, ...), the hyperparameters, the EEG branch kind, the
-  model's shapes, the world size, the bucket layout, the dropout stream and the state of `fit`.
+  model's shapes, the head count of every transformer block, the world size, the bucket layout, the dropout stream
+  and the state of `fit`.
 
 The step itself is untouched: saving and loading are copies, `fit` only calls `train_step` and `embed`.
 
@@ -27,6 +28,7 @@ from typing import Callable, Optional, Union
 import torch
 
 from . import dp, ops
+from .enhanced_models_v4 import TemporalTransformerBlock
 
 FORMAT = 1
 CONTAINER_KEYS = ("epoch", "model_state_dict", "optimizer_state_dict", "scheduler_state_dict", "metrics",
@@ -83,8 +85,13 @@ class TrainerCheckpointMixin:
             raise RuntimeError("BridgeTrainer: the trainable parameters and the flat bucket disagree")
         return [(i, names[id(p)], p, offs[id(p)]) for i, p in enumerate(trainable)]
 
+    def _block_heads(self) -> list:
+        """[[module name, heads]] of every transformer block: 128 wide with 4 or 8 heads has the same shapes"""
+        return [[n, int(m.nhead)] for n, m in self.named_modules() if isinstance(m, TemporalTransformerBlock)]
+
     def _layout(self) -> dict:
         return {"eeg_kind": self._eeg_kind,
+                "heads": self._block_heads(),
                 "shapes": {k: list(v.shape) for k, v in self.state_dict().items()},
                 "bucket_n": int(self.bucket.n),
                 "groups": [[n, r, int(lo), int(hi)] for n, r, lo, hi in self.groups],
@@ -154,6 +161,10 @@ class TrainerCheckpointMixin:
                     raise ValueError(f"load_checkpoint_state: {field} differs: checkpoint {bts.get(field)!r}, "
                                      f"trainer {mine[field]!r}")
         same("eeg_kind", "world")
+        # a checkpoint written before the head counts were recorded comes from a trainer whose blocks all had 4 heads
+        heads = bts.get("heads", [[n, 4] for n, _ in mine["heads"]])
+        if heads != mine["heads"]:
+            raise ValueError(f"load_checkpoint_state: heads differ: checkpoint {heads!r}, trainer {mine['heads']!r}")
         theirs = bts.get("shapes", {})
         for k, shp in mine["shapes"].items():
             if theirs.get(k) != shp:

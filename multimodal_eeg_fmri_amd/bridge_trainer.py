@@ -44,12 +44,16 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
     def __init__(self, eeg_channels: int = 64, hidden_dim: int = 128, fmri_dim: int = 64,
                  bridge_dim: int = 128, dropout: float = 0.3, lr: float = 1e-4,
                  weight_decay: float = 1e-4, grad_clip: float = 1.0, betas=(0.9, 0.999),
-                 eps: float = 1e-8, group=None, device="cuda", mode: str = "graph", eeg_encoder: Optional[nn.Module] = None):
-        """``eeg_encoder``: the EEG branch when it is not the default ``EnhancedERPEncoder(eeg_channels, hidden_dim, 2, 4,
-        dropout)`` - an ``EnhancedPowerEncoder`` (enhanced_models_v4.py:196-285) or a ``MultiScaleSTFTPowerEncoder``
-        (BASELINE config #5: raw EEG -> multi-scale STFT power -> a4); it must end in ``hidden_dim`` features."""
+                 eps: float = 1e-8, group=None, device="cuda", mode: str = "graph", eeg_encoder: Optional[nn.Module] = None,
+                 num_heads: int = 4, num_layers: int = 2):
+        """``eeg_encoder``: the EEG branch when it is not the default ``EnhancedERPEncoder(eeg_channels, hidden_dim,
+        num_layers, num_heads, dropout)`` - an ``EnhancedPowerEncoder`` (enhanced_models_v4.py:196-285) or a
+        ``MultiScaleSTFTPowerEncoder`` (BASELINE config #5: raw EEG -> multi-scale STFT power -> a4); it must end in
+        ``hidden_dim`` features.  The attention kernels run head dims ``hidden_dim / num_heads`` of 16, 24, ..., 64
+        (checked at the first step, not here: a trainer built on the CPU to read weights takes any shape)."""
         super().__init__()
-        self.eeg_encoder = EnhancedERPEncoder(eeg_channels, hidden_dim, 2, 4, dropout) if eeg_encoder is None else eeg_encoder
+        self.eeg_encoder = (EnhancedERPEncoder(eeg_channels, hidden_dim, num_layers, num_heads, dropout)
+                            if eeg_encoder is None else eeg_encoder)
         from .crossmodal_v4_enhancements import MultiScaleSTFTPowerEncoder
         from .enhanced_models_v4 import EnhancedPowerEncoder
         if isinstance(self.eeg_encoder, EnhancedERPEncoder):

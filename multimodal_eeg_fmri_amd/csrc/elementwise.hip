@@ -284,28 +284,29 @@ __global__ void bn_act_bwd_kernel(BnBwdArgs a) {
 }
 
 // ---------------------------------------------------------------------------
-// LayerNorm over the last dim (D % 64 == 0, D <= 1024): one wave per row.
+// LayerNorm over the last dim (D % 32 == 0, D <= 512, or D = 1024): one wave per row.
 // ---------------------------------------------------------------------------
-template <int VPL>   // values per lane = D / 64
+template <int VPL, int DW = VPL * 64>   // values per lane = ceil(D / 64); DW = D (columns >= DW of the last slot idle)
 __global__ void layernorm_fwd_kernel(const float* __restrict__ x, const float* __restrict__ g, const float* __restrict__ b,
                                      bf16* __restrict__ out_bf16, float* __restrict__ out_f32,
                                      float* __restrict__ stat /* [M][2] mean,rstd */, int M, float eps) {
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     if (row >= M) return;
-    constexpr int D = VPL * 64;
+    constexpr int D = DW;
     float v[VPL];
     float s = 0.f;
 #pragma unroll
-    for (int i = 0; i < VPL; ++i) { v[i] = x[(size_t)row * D + i * 64 + lane]; s += v[i]; }
+    for (int i = 0; i < VPL; ++i) { v[i] = i * 64 + lane < D ? x[(size_t)row * D + i * 64 + lane] : 0.f; s += v[i]; }
     const float mean = wave_sum(s) * (1.f / D);
     float q = 0.f;
 #pragma unroll
-    for (int i = 0; i < VPL; ++i) { const float d = v[i] - mean; q += d * d; }
+    for (int i = 0; i < VPL; ++i) { const float d = i * 64 + lane < D ? v[i] - mean : 0.f; q += d * d; }
     const float rstd = rsqrtf(wave_sum(q) * (1.f / D) + eps);
 #pragma unroll
     for (int i = 0; i < VPL; ++i) {
         const int c = i * 64 + lane;
+        if (c >= D) continue;
         const float o = (v[i] - mean) * rstd * g[c] + b[c];
         if (out_bf16) out_bf16[(size_t)row * D + c] = (bf16)o;
         if (out_f32) out_f32[(size_t)row * D + c] = o;
@@ -316,7 +317,7 @@ __global__ void layernorm_fwd_kernel(const float* __restrict__ x, const float* _
 // dx = dres + rstd * (gh - mean(gh) - xhat * mean(gh * xhat)),  gh = dy * gamma
 // dgamma += sum_rows dy * xhat ; dbeta += sum_rows dy       (block partial + atomics)
 // optional second output: bf16(dx * dropout_mask) for the next GEMM operand.
-template <int VPL>
+template <int VPL, int DW = VPL * 64>
 __global__ void layernorm_bwd_kernel(const bf16* __restrict__ dy_bf16, const float* __restrict__ dy_f32,
                                      const float* __restrict__ x, const float* __restrict__ stat,
                                      const float* __restrict__ g, const float* __restrict__ dres,
@@ -324,13 +325,13 @@ __global__ void layernorm_bwd_kernel(const bf16* __restrict__ dy_bf16, const flo
                                      float* __restrict__ dgb, int M, int rows_per_wave, uint32_t thresh,
                                      uint32_t seed, float inv_keep, const uint32_t* epoch) {
     seed = mm_eff_seed(seed, epoch);
-    constexpr int D = VPL * 64;
+    constexpr int D = DW;
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
     const int wpb = blockDim.x >> 6;
     float ag[VPL], ab[VPL], gam[VPL];
 #pragma unroll
-    for (int i = 0; i < VPL; ++i) { ag[i] = 0.f; ab[i] = 0.f; gam[i] = g[i * 64 + lane]; }
+    for (int i = 0; i < VPL; ++i) { ag[i] = 0.f; ab[i] = 0.f; gam[i] = i * 64 + lane < D ? g[i * 64 + lane] : 0.f; }
     const int row0 = (blockIdx.x * wpb + wave) * rows_per_wave;
     for (int rr = 0; rr < rows_per_wave; ++rr) {
         const int row = row0 + rr;
@@ -341,8 +342,9 @@ __global__ void layernorm_bwd_kernel(const bf16* __restrict__ dy_bf16, const flo
 #pragma unroll
         for (int i = 0; i < VPL; ++i) {
             const size_t idx = (size_t)row * D + i * 64 + lane;
-            dyv[i] = dy_bf16 ? (float)dy_bf16[idx] : dy_f32[idx];
-            xh[i] = (x[idx] - mean) * rstd;
+            const bool ok = i * 64 + lane < D;         // idle columns: dy = 0, gamma = 0 -> they add nothing
+            dyv[i] = !ok ? 0.f : dy_bf16 ? (float)dy_bf16[idx] : dy_f32[idx];
+            xh[i] = ok ? (x[idx] - mean) * rstd : 0.f;
             const float gh = dyv[i] * gam[i];
             s1 += gh; s2 += gh * xh[i];
             ag[i] += dyv[i] * xh[i]; ab[i] += dyv[i];
@@ -351,6 +353,7 @@ __global__ void layernorm_bwd_kernel(const bf16* __restrict__ dy_bf16, const flo
         s2 = wave_sum(s2) * (1.f / D);
 #pragma unroll
         for (int i = 0; i < VPL; ++i) {
+            if (i * 64 + lane >= D) continue;
             const size_t idx = (size_t)row * D + i * 64 + lane;
             float o = rstd * (dyv[i] * gam[i] - s1 - xh[i] * s2);
             if (dres) o += dres[idx];
@@ -364,6 +367,7 @@ __global__ void layernorm_bwd_kernel(const bf16* __restrict__ dy_bf16, const flo
         __shared__ float red[4][2][D];
 #pragma unroll
         for (int i = 0; i < VPL; ++i) {
+            if (i * 64 + lane >= D) continue;
             red[wave][0][i * 64 + lane] = ag[i];
             red[wave][1][i * 64 + lane] = ab[i];
         }
@@ -727,14 +731,17 @@ int mm_bn_act_bwd_apply_bcast(const float* y, const float* out4, const float* do
                          seed_epoch, train, sums_nrep, st, 1, scale);
 }
 
-#define LN_DISPATCH(D, CALL)                                   \
-    switch ((D) / 64) {                                        \
-        case 1: { constexpr int V = 1; CALL; } break;          \
-        case 2: { constexpr int V = 2; CALL; } break;          \
-        case 4: { constexpr int V = 4; CALL; } break;          \
-        case 8: { constexpr int V = 8; CALL; } break;          \
-        case 16: { constexpr int V = 16; CALL; } break;        \
-        default: return mm_fail(MM_ERR_UNSUPPORTED, "layernorm: D=%d (need 64,128,256,512,1024)", (D)); \
+// V = values per lane, W = the row width.  (The switch used to be on D / 64 alone, so that a width that is not a multiple
+// of 64 - 96, 160, 224: encoder widths with 4 heads of 24, 40, 56 - ran the kernel of a narrower row.)
+#define LN_CASE(DV, ...) case DV: { constexpr int V = (DV + 63) / 64, W = DV; __VA_ARGS__; } break;
+#define LN_DISPATCH(D, ...)                                                                                         \
+    switch (D) {                                                                                                    \
+        LN_CASE(32, __VA_ARGS__) LN_CASE(64, __VA_ARGS__) LN_CASE(96, __VA_ARGS__) LN_CASE(128, __VA_ARGS__)        \
+        LN_CASE(160, __VA_ARGS__) LN_CASE(192, __VA_ARGS__) LN_CASE(224, __VA_ARGS__) LN_CASE(256, __VA_ARGS__)     \
+        LN_CASE(288, __VA_ARGS__) LN_CASE(320, __VA_ARGS__) LN_CASE(352, __VA_ARGS__) LN_CASE(384, __VA_ARGS__)     \
+        LN_CASE(416, __VA_ARGS__) LN_CASE(448, __VA_ARGS__) LN_CASE(480, __VA_ARGS__) LN_CASE(512, __VA_ARGS__)     \
+        LN_CASE(1024, __VA_ARGS__)                                                                                  \
+        default: return mm_fail(MM_ERR_UNSUPPORTED, "layernorm: D=%d (need a multiple of 32 up to 512, or 1024)", (D)); \
     }
 
 int mm_layernorm_fwd(const float* x, const float* gamma, const float* beta, void* out_bf16, float* out_f32,
@@ -746,7 +753,7 @@ int mm_layernorm_fwd(const float* x, const float* gamma, const float* beta, void
         return mm_check_launch("layernorm128_fwd");
     }
     const dim3 grid(ceil_div(M, 4)), block(256);
-    LN_DISPATCH(D, hipLaunchKernelGGL(layernorm_fwd_kernel<V>, grid, block, 0, st, x, gamma, beta, (bf16*)out_bf16,
+    LN_DISPATCH(D, hipLaunchKernelGGL((layernorm_fwd_kernel<V, W>), grid, block, 0, st, x, gamma, beta, (bf16*)out_bf16,
                                       out_f32, stat, M, eps));
     return mm_check_launch("layernorm_fwd");
 }
@@ -764,7 +771,7 @@ int mm_layernorm_bwd(const void* dy_bf16, const float* dy_f32, const float* x, c
     }
     const int rpw = M >= 8192 ? 8 : (M >= 1024 ? 2 : 1);
     const dim3 grid(ceil_div(M, 4 * rpw)), block(256);
-    LN_DISPATCH(D, hipLaunchKernelGGL(layernorm_bwd_kernel<V>, grid, block, 0, st, (const bf16*)dy_bf16, dy_f32, x,
+    LN_DISPATCH(D, hipLaunchKernelGGL((layernorm_bwd_kernel<V, W>), grid, block, 0, st, (const bf16*)dy_bf16, dy_f32, x,
                                       stat, gamma, dres, dx, (bf16*)dx_bf16, dgb_repl, M, rpw, thresh_of(drop_p), seed,
                                       drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f, seed_epoch));
     return mm_check_launch("layernorm_bwd");

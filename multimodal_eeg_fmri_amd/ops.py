@@ -412,7 +412,7 @@ def layernorm(x2d: torch.Tensor, ln, want_stat: bool):
 
 
 def attn_effective_dropout(p: float) -> float:
-    """the attention-probability dropout rate the kernels apply for a requested ``p``: csrc/attention.hip decides a 2 x 2 block
+    """the attention-probability dropout rate the kernels apply for a requested ``p``: csrc/attention{,_hd}.hip decide a 2 x 2 block
     of scores with one 32-bit hash and 8-bit fields, so the rate is quantised to round(256 p) / 256 (p = 0.1 -> 0.1016,
     the keep scale is that of the quantised rate: the mask stays unbiased); 0 < p < 1/512 rounds to NO dropout"""
     return round(256.0 * float(p)) / 256.0
@@ -425,12 +425,27 @@ def attention(qkv: torch.Tensor, nhead: int, want_lse: bool, drop_p: float = 0.0
                       "is applied (nn.MultiheadAttention(dropout=p) would drop with probability p)")
     B, L, E3 = qkv.shape
     E = E3 // 3
+    entry = attn_entry(E, nhead, "fwd")
     dh = E // nhead
     out = _empty((B, L, E), _BF, qkv)
     lse = _empty((B, nhead, L), _F32, qkv) if want_lse else None
-    _hip.call("mm_attn_fwd", qkv, out, lse, B, L, nhead, dh, 1.0 / math.sqrt(dh), float(drop_p), int(seed), EP(), mask,
+    _hip.call(entry, qkv, out, lse, B, L, nhead, dh, 1.0 / math.sqrt(dh), float(drop_p), int(seed), EP(), mask,
               attn_mask_per_head(mask, B, nhead, L))
     return out, lse
+
+
+ATTN_HEAD_DIMS = tuple(range(16, 65, 8))        # the head widths the self-attention kernels run (16, 24, ..., 64)
+
+
+def attn_entry(d_model: int, nhead: int, which: str) -> str:
+    """the C-ABI entry point of the self-attention ``which`` pass ("fwd" / "bwd") for a ``d_model``-wide, ``nhead``-head
+    layer: head_dim 32 (the default model) runs csrc/attention.hip (mm_attn_fwd / mm_attn_bwd), every other supported
+    head_dim runs csrc/attention_hd.hip (mm_attn_fwd_hd / mm_attn_bwd_hd).  Anything else raises ValueError before a launch."""
+    dh = d_model // nhead if nhead > 0 else 0
+    if nhead <= 0 or d_model % nhead or dh not in ATTN_HEAD_DIMS:
+        raise ValueError(f"self-attention: (d_model, nhead) = ({d_model}, {nhead}) gives a head dim the kernels do not run; "
+                         f"supported head dims: {', '.join(map(str, ATTN_HEAD_DIMS))}")
+    return f"mm_attn_{which}" if dh == 32 else f"mm_attn_{which}_hd"
 
 
 def attn_mask_per_head(mask, B: int, nhead: int, L: int) -> int:

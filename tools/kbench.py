@@ -154,19 +154,24 @@ def conv3d_case(B, S, Cin, Cout, wgrad=True, fwd=True):
           f"{n.value} slots, graph-replayed)")
 
 
-def attn_case(B=32, L=512, H=4, p=0.1):
-    E = H * 32
+def attn_case(B=32, L=512, H=4, p=0.1, head_dim=32):
+    """self-attention forward / backward at ``head_dim`` (16, 24, ..., 64): the entry point the model would call
+    (mm_attn_* at 32, mm_attn_*_hd otherwise)"""
+    from multimodal_eeg_fmri_amd import ops
+    E = H * head_dim
+    fwd, bwd = ops.attn_entry(E, H, "fwd"), ops.attn_entry(E, H, "bwd")
     qkv = (torch.randn(B, L, 3 * E, device="cuda") * 0.5).to(BF)
     out = torch.empty(B, L, E, dtype=BF, device="cuda")
     lse = torch.empty(B, H, L, device="cuda")
     dout = torch.randn(B, L, E, device="cuda").to(BF)
     dqkv = torch.empty_like(qkv)
     delta = torch.empty(B, H, L, device="cuda")
-    sc = 1 / math.sqrt(32)
-    f = timeit(lambda: _hip.call("mm_attn_fwd", qkv, out, lse, B, L, H, 32, sc, p, 77, None, None, 0))
-    b = timeit(lambda: _hip.call("mm_attn_bwd", qkv, out, dout, lse, dqkv, delta, B, L, H, 32, sc, p, 77, None, None, 0))
-    fl = 4.0 * B * H * L * L * 32
-    print(f"attention B={B} L={L} H={H} p={p}: fwd {f:6.1f} us ({fl / f / 1e6:6.1f} TF/s)   bwd (dq + dkv) {b:6.1f} us")
+    sc = 1 / math.sqrt(head_dim)
+    f = timeit(lambda: _hip.call(fwd, qkv, out, lse, B, L, H, head_dim, sc, p, 77, None, None, 0))
+    b = timeit(lambda: _hip.call(bwd, qkv, out, dout, lse, dqkv, delta, B, L, H, head_dim, sc, p, 77, None, None, 0))
+    fl = 4.0 * B * H * L * L * head_dim
+    print(f"attention B={B} L={L} H={H} dh={head_dim} p={p} ({fwd}): fwd {f:6.1f} us ({fl / f / 1e6:6.1f} TF/s)   "
+          f"bwd (dq + dkv) {b:6.1f} us")
 
 
 def floor_case():
@@ -409,9 +414,11 @@ def main():
     if "pmc4" in flt:               # BASELINE config #4: layer 2 at 32 x 32 x 24
         conv3d_dims_case(32, 32, 32, 24, 32, 64)
         return
-    if "attn" in flt:
-        for p_ in (0.0, 0.1, 0.3):
-            attn_case(p=p_)
+    if "attn" in flt:               # attn[:dh,dh,...]: head dims to time (default 32), e.g. attn:16,32,64
+        dims = [int(d) for d in flt.split(":", 1)[1].split(",")] if ":" in flt else [32]
+        for dh in dims:
+            for p_ in (0.0, 0.1, 0.3):
+                attn_case(p=p_, head_dim=dh)
         return
     if "c4" in flt:                 # full-resolution fMRI (64x64x48): layer 2 runs at 32x32x24
         for B in (4, 8, 32):
