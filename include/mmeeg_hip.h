@@ -468,6 +468,15 @@ int mm_proj_heads_bwd(const float* dz, const float* z, const float* nrm, const f
 int mm_clip_loss_own_rows(const float* z_all, const float* logit_scale, float* scal4, float* dz_local, float* ws,
                           int B, int Bg, int N, int row0, hipStream_t stream);
 int mm_clip_loss_ws_floats(int B, int Bg, int* floats_host, hipStream_t stream);
+/* the same loss with subject-grouped positives.  gid_all int32 [Bg] (gathered like z_all): pairs with equal ids are
+ * positives of each other, P(r) = {j : gid_j = gid_r} (always holds r).  Per row, "log of the positive mass" (MIL-NCE):
+ * l_row(r) = LSE_j(s C[r][j]) - LSE_{j in P(r)}(s C[r][j]), l_col(r) the same over column r, loss_r = (l_row + l_col) / 2.
+ * dz_local and scal4 as above; top-1 counts row r when max_{j in P(r)} C[r][j] >= max_j C[r][j] (a tie FOR it).  With
+ * all-distinct ids this is mm_clip_loss_own_rows' loss.  ws = mm_clip_loss_grouped_ws_floats(B, Bg) floats, no
+ * initialisation.  N % 4 == 0.  Two launches on `stream`; same inputs -> bit-identical outputs. */
+int mm_clip_loss_own_rows_grouped(const float* z_all, const int* gid_all, const float* logit_scale, float* scal4,
+                                  float* dz_local, float* ws, int B, int Bg, int N, int row0, hipStream_t stream);
+int mm_clip_loss_grouped_ws_floats(int B, int Bg, int* floats_host, hipStream_t stream);
 
 /* ---- gallery-scale retrieval (csrc/retrieval.hip) ---------------------------
  * For each query row q of Q [Nq][D] against gallery G [Ng][D] (fp32, row-major, 16-byte aligned; callers pass
@@ -488,6 +497,16 @@ int mm_clip_loss_ws_floats(int B, int Bg, int* floats_host, hipStream_t stream);
 int mm_retrieval(const float* Q, const float* G, const int* pos, int* ranks, int* topk_idx, float* topk_score,
                  float* ws, int Nq, int Ng, int D, int k, hipStream_t stream);
 int mm_retrieval_ws_floats(int Nq, int Ng, int D, int k, int* floats_host, hipStream_t stream);
+/* ranks with grouped positives: qgid int32 [Nq], ggid int32 [Ng] (e.g. subject ids); gallery row j is a positive of
+ * query q when ggid[j] == qgid[q].  s*(q) = max over the positives of s(q, j) (NaN scores ignored), scored by the same
+ * MFMA chain as mm_retrieval, and ranks[q] = 1 + #{ j : ggid[j] != qgid[q], s(q, j) >= s*(q) }: the rank of the
+ * best-placed positive, the other positives never count; a tie with s* counts AGAINST the query, a NaN s(q, j) never
+ * counts, a query without a positive (or with only NaN positive scores) ranks Ng.  ws =
+ * mm_retrieval_grouped_ws_floats(Nq, Ng, D) floats, no initialisation; shape limits as mm_retrieval.  No Nq x Ng
+ * storage, integer counts: deterministic.  Four launches on `stream`.  Top-k does not depend on groups: mm_retrieval. */
+int mm_retrieval_grouped(const float* Q, const float* G, const int* qgid, const int* ggid, int* ranks, float* ws,
+                         int Nq, int Ng, int D, hipStream_t stream);
+int mm_retrieval_grouped_ws_floats(int Nq, int Ng, int D, int* floats_host, hipStream_t stream);
 
 /* ---- EnhancedPowerEncoder: its three Conv1d(C -> 64, k = 3 | 5 | 7) + BatchNorm1d(64) branches
  * (enhanced_models_v4.py:210-234, forward :258-266: torch.cat of the three) as ONE Conv1d(C -> 192, k = 7, p = 3) +

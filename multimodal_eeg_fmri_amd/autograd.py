@@ -876,7 +876,8 @@ class ClipLossFn(torch.autograd.Function):
     gathered gradients would deliver - and the usual gradient all-reduce of data parallelism completes it."""
 
     @staticmethod
-    def forward(ctx, z, logit_scale, group):
+    def forward(ctx, z, logit_scale, group, gid=None):
+        """``gid``: (B,) int32 device group ids (ops.group_ids) -> the grouped loss; gathered like the embeddings"""
         from . import dp
         z = z.contiguous().float()
         B, N2 = z.shape
@@ -886,9 +887,14 @@ class ClipLossFn(torch.autograd.Function):
         need_grad = z.requires_grad or logit_scale.requires_grad
         scal = _empty((4,), _F32, z)
         dz = _empty((B, N2), _F32, z) if need_grad else None
-        ws = _empty((ops.clip_loss_ws_floats(B, world * B),), _F32, z)
         ls = logit_scale.detach().reshape(1).float().contiguous()
-        _hip.call("mm_clip_loss_own_rows", z_all, ls, scal, dz, ws, B, world * B, N, rank * B)
+        if gid is None:
+            ws = _empty((ops.clip_loss_ws_floats(B, world * B),), _F32, z)
+            _hip.call("mm_clip_loss_own_rows", z_all, ls, scal, dz, ws, B, world * B, N, rank * B)
+        else:
+            gid_all = dp.gather_embeddings(gid.view(B, 1), group).view(-1)
+            ws = _empty((ops.clip_loss_grouped_ws_floats(B, world * B),), _F32, z)
+            _hip.call("mm_clip_loss_own_rows_grouped", z_all, gid_all, ls, scal, dz, ws, B, world * B, N, rank * B)
         if need_grad:
             ctx.save_for_backward(dz, scal)
         return scal[0].clone(), scal[1].clone(), scal[2].clone()
@@ -896,4 +902,4 @@ class ClipLossFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_loss, g_a, g_b):
         dz, scal = ctx.saved_tensors
-        return dz * g_loss, (scal[3] * g_loss).reshape(()), None
+        return dz * g_loss, (scal[3] * g_loss).reshape(()), None, None

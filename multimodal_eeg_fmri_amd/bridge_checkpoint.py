@@ -287,7 +287,7 @@ class TrainerCheckpointMixin:
         from .bridge_utils import retrieval_metrics
         s0 = ops._seed_state["step"]
         ze, zf = self.embed(val[0], val[1], batch_size)
-        metrics = retrieval_metrics(ze, zf)
+        metrics = retrieval_metrics(ze, zf, groups=val[2] if len(val) > 2 else None)
         assert ops._seed_state["step"] == s0, "validation drew dropout seeds"
         return metrics, monitor_value(metrics, monitor)
 
@@ -297,11 +297,14 @@ class TrainerCheckpointMixin:
             val_batch_size: int = 256):
         """The reference's epoch loop (run_training_lite.py:465-520) on the contrastive step -> per-epoch history.
 
-        ``train``: an iterable of (eeg, fmri) batches re-iterated every epoch, or ``epoch -> iterable`` (1-based).  Every
-        batch goes through `train_step`; in graph mode keep one batch shape (a new shape captures the step again).
+        ``train``: an iterable of (eeg, fmri) or (eeg, fmri, groups) batches re-iterated every epoch, or ``epoch ->
+        iterable`` (1-based).  Every batch goes through `train_step` (``groups``: subject ids, pairs of one subject are
+        positives of each other); in graph mode keep one batch shape and one kind (a new shape, or a switch between
+        grouped and ungrouped batches, captures the step again).
         Schedule: `CosineAnnealingWarmup(warmup_epochs, epochs, min_lr)` from the trainer's current lr, stepped after each
         epoch's training as the reference does (epoch 1 runs at the base rate, epoch e > 1 at ``_lr_at(e - 1)``).
-        ``val = (eeg, fmri)``: every ``eval_every`` epochs (and after the last) `embed` + `retrieval_metrics`; the
+        ``val = (eeg, fmri[, groups])``: every ``eval_every`` epochs (and after the last) `embed` + `retrieval_metrics`
+        (grouped ranks with ``groups``); the
         monitored value (``monitor_value``; ``mode`` "max" or "min") drives `EarlyStopping(patience, min_delta)` and the
         best state: on a strict improvement a device copy of the parameters and buffers is kept (and ``best.pt`` written
         when ``checkpoint_dir`` is set); the best model is restored in place at the end (the optimizer state is not,
@@ -346,8 +349,8 @@ class TrainerCheckpointMixin:
                 lr = float(self.lr)
                 total = torch.zeros((), dtype=torch.float64, device=dev)
                 n = 0
-                for eeg, fmri in (train(epoch) if callable(train) else train):
-                    total += self.train_step(eeg, fmri)["loss"]
+                for batch in (train(epoch) if callable(train) else train):
+                    total += self.train_step(*batch)["loss"]
                     n += 1
                 sched.step()
                 entry = {"epoch": epoch, "lr": lr, "steps": n, "train_loss": total.item() / max(n, 1),

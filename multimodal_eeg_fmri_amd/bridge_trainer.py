@@ -136,12 +136,14 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
         self.lr = lr
         self.bucket.state[2] = lr
 
-    def forward(self, eeg: torch.Tensor, fmri: torch.Tensor):
+    def forward(self, eeg: torch.Tensor, fmri: torch.Tensor, groups: Optional[torch.Tensor] = None):
         """the two encoders are independent until the heads: they run on two HIP
         streams (autograd replays each backward on its forward stream), so the
-        many sub-chip kernels of one branch overlap the other's latency."""
+        many sub-chip kernels of one branch overlap the other's latency.
+        ``groups``: (B,) integer ids, pairs with equal ids are positives of each other (ops.clip_loss)."""
+        gid = ops.group_ids(groups, eeg.shape[0], eeg.device, "BridgeTrainer")
         if not self.two_streams:
-            return self.head(self.eeg_encoder(eeg), self.fmri_encoder(fmri), self.group)
+            return self.head(self.eeg_encoder(eeg), self.fmri_encoder(fmri), self.group, gid)
         main = torch.cuda.current_stream()
         self._side.wait_stream(main)
         with torch.cuda.stream(self._side):
@@ -149,28 +151,31 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
         fe = self.eeg_encoder(eeg)
         main.wait_stream(self._side)
         ff.record_stream(main)
-        return self.head(fe, ff, self.group)
+        return self.head(fe, ff, self.group, gid)
 
     # ------------------------------------------------------------------ step
-    def train_step(self, eeg: torch.Tensor, fmri: torch.Tensor) -> Dict[str, torch.Tensor]:
+    def train_step(self, eeg: torch.Tensor, fmri: torch.Tensor, groups: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
         """zero_grad -> forward -> backward -> (all-reduce) -> clip + AdamW.
 
         ``mode``: "graph" (default) replays the step from hipGraphs captured on
         first use (one graph at world 1; three segments around the two
         collectives otherwise); "manual" runs the same autograd-free tape eagerly;
-        "autograd" goes through the public nn.Module / torch.autograd surface."""
+        "autograd" goes through the public nn.Module / torch.autograd surface.
+        ``groups``: (B,) integer ids (e.g. subjects; ``ops.group_ids``): pairs with equal ids are positives of each
+        other (mm_clip_loss_own_rows_grouped).  In graph mode a grouped step is its own capture, as a new shape is."""
         ops.check_volume_shape(fmri.shape)                 # before the first launch of the step (or of its capture)
+        gid = ops.group_ids(groups, eeg.shape[0], None if self.mode == "graph" else eeg.device, "train_step")
         if self.mode == "autograd":
-            return self._step_autograd(eeg, fmri)
+            return self._step_autograd(eeg, fmri, gid)
         if self.mode == "manual":
             with torch.no_grad():
-                return self._step_manual(eeg, fmri)
-        return self._step_graph(eeg, fmri)
+                return self._step_manual(eeg, fmri, gid)
+        return self._step_graph(eeg, fmri, gid)
 
-    def _step_autograd(self, eeg, fmri):
+    def _step_autograd(self, eeg, fmri, gid=None):
         b = self.bucket
         b.zero_grad()
-        loss, acc_e, acc_f = self.forward(eeg, fmri)
+        loss, acc_e, acc_f = self.forward(eeg, fmri, gid)
         loss.backward()
         b.absorb_autograd_grads()
         self._seg_optimizer()
@@ -242,15 +247,21 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
         spec = ops.stft_front_end(eeg, enc.n_ffts, enc.hop, enc.normalize)
         return ops._power_forward_impl(enc.encoder, spec, True, False)
 
-    def _seg_loss(self, z_all, scal, dz):
+    def _seg_loss(self, z_all, scal, dz, gid_all=None):
         """symmetric InfoNCE of this rank's rows against the gathered batch, gradient w.r.t. ITS rows only
         (``mm_clip_loss_own_rows``: every rank evaluates all rows of the gathered batch, so no reduce-scatter
-        of column gradients is needed).  ``scal`` = the trainer's own 4-float result buffer, ``dz`` (B, 2N): both written with plain stores."""
+        of column gradients is needed).  ``scal`` = the trainer's own 4-float result buffer, ``dz`` (B, 2N): both written with plain stores.
+        ``gid_all``: the gathered int32 group ids -> the grouped loss (``mm_clip_loss_own_rows_grouped``)."""
         N2 = z_all.shape[1]
         B = dz.shape[0]
         ls = self.head.logit_scale.detach().reshape(1)
-        ws = ops._empty((ops.clip_loss_ws_floats(B, z_all.shape[0]),), torch.float32, z_all)
-        _hip.call("mm_clip_loss_own_rows", z_all, ls, scal, dz, ws, B, z_all.shape[0], N2 // 2, dp.rank(self.group) * B)
+        if gid_all is None:
+            ws = ops._empty((ops.clip_loss_ws_floats(B, z_all.shape[0]),), torch.float32, z_all)
+            _hip.call("mm_clip_loss_own_rows", z_all, ls, scal, dz, ws, B, z_all.shape[0], N2 // 2, dp.rank(self.group) * B)
+        else:
+            ws = ops._empty((ops.clip_loss_grouped_ws_floats(B, z_all.shape[0]),), torch.float32, z_all)
+            _hip.call("mm_clip_loss_own_rows_grouped", z_all, gid_all, ls, scal, dz, ws, B, z_all.shape[0], N2 // 2,
+                      dp.rank(self.group) * B)
         self._stamp(6)
 
     def _reduce_group(self, ready: str):
@@ -364,40 +375,48 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
         ops.arena.end()
         self._stamp(12)
 
-    def _step_manual(self, eeg, fmri):
+    def _step_manual(self, eeg, fmri, gid=None):
         recording = self._weight_list is None
         if recording:                                 # first step: note every weight image the tape asks for
             ops.weights.start_recording()
         try:
-            return self._step_manual_body(eeg, fmri)
+            return self._step_manual_body(eeg, fmri, gid)
         finally:
             if recording:
                 self._weight_list = ops.weights.stop_recording()
 
-    def _step_manual_body(self, eeg, fmri):
+    def _step_manual_body(self, eeg, fmri, gid=None):
+        gid_all = None if gid is None else dp.gather_embeddings(gid.view(-1, 1), self.group).view(-1)
         z, saved = self._seg_forward(eeg, fmri)
         z_all = dp.gather_embeddings(z, self.group)
         scal, dz = self._scal, ops._empty(tuple(z.shape), torch.float32, z)
-        self._seg_loss(z_all, scal, dz)
+        self._seg_loss(z_all, scal, dz, gid_all)
         early = dp.active(self.group)
         self._seg_backward(saved, dz, scal, reduce=early)
         self._seg_optimizer(reduced=early)
         return {"loss": scal[0], "top1_e2f": scal[1], "top1_f2e": scal[2]}
 
     # ---- hipGraph capture ------------------------------------------------------
-    def _capture(self, eeg, fmri):
+    def _capture(self, eeg, fmri, gid=None):
         dev = eeg.device
         world = self.world
         c = {"epoch": torch.zeros(1, dtype=torch.int32, device=dev)}
-        # the step's static inputs are two views of ONE flat buffer `c["in"]` = [EEG operand | fMRI volumes fp32], so that a
-        # host-fed loop fills them with a single copy (`train_step_packed`).  EEG operand: the first convolution's packed
-        # bf16 (B, T, Cp) image (the STFT front-end reads the raw fp32 batch instead and keeps that)
+        # the step's static inputs are views of ONE flat buffer `c["in"]` = [EEG operand | fMRI volumes fp32 | group ids
+        # int32 (grouped captures only)], so that a host-fed loop fills them with a single copy (`train_step_packed`).
+        # EEG operand: the first convolution's packed bf16 (B, T, Cp) image (the STFT front-end reads the raw fp32 batch
+        # instead and keeps that)
         stft = self._eeg_kind == "stft"
         Bx, Cx, Tx = eeg.shape
         n_e = eeg.numel() * 4 if stft else Bx * Tx * ops.cpad(Cx) * 2
-        c["in"] = torch.empty(n_e + fmri.numel() * 4, dtype=torch.uint8, device=dev)
-        c["fmri"] = c["in"][n_e:].view(torch.float32).view(fmri.shape)
+        n_f = fmri.numel() * 4
+        c["grouped"] = gid is not None
+        c["in"] = torch.empty(n_e + n_f + (Bx * 4 if c["grouped"] else 0), dtype=torch.uint8, device=dev)
+        c["fmri"] = c["in"][n_e:n_e + n_f].view(torch.float32).view(fmri.shape)
         c["fmri"].copy_(fmri)
+        c["gid"] = c["gid_all"] = None
+        if c["grouped"]:
+            c["gid"] = c["in"][n_e + n_f:].view(torch.int32)
+            c["gid"].copy_(gid)
         if stft:
             c["eeg"], c["xb"] = c["in"][:n_e].view(torch.float32).view(eeg.shape), None
             c["eeg"].copy_(eeg)
@@ -416,7 +435,7 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side), torch.no_grad():
             for _ in range(2):
-                self._step_manual(c["eeg"], c["fmri"])
+                self._step_manual(c["eeg"], c["fmri"], c["gid"])
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
         with torch.no_grad():
@@ -447,12 +466,16 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
         c["scal"] = self._scal
         import os
         dist_step = not (world == 1 and not (self.force_segments and self.group is not None))
+        # a grouped step gathers its ids when it issues collectives (world > 1, or MM_DP_FORCE); else they are the local ones
+        c["gid_gather"] = c["grouped"] and dist_step and dp.active(self.group)
+        if c["grouped"]:
+            c["gid_all"] = torch.empty(world * B, dtype=torch.int32, device=dev) if c["gid_gather"] else c["gid"]
         if not dist_step:
             def whole():
                 z, saved = self._seg_forward(c["eeg"], c["fmri"], xb=c["xb"])
                 c["z"] = z
                 c["dz"] = ops._empty(tuple(z.shape), torch.float32, z)
-                self._seg_loss(z, c["scal"], c["dz"])
+                self._seg_loss(z, c["scal"], c["dz"], c["gid_all"])
                 self._seg_backward(saved, c["dz"], c["scal"])
                 self._grad_probe()
                 self._seg_adamw()
@@ -469,7 +492,7 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
             c["z_all"] = torch.empty(world * B, N2, device=dev)
 
             def seg2():
-                self._seg_loss(c["z_all"], c["scal"], c["dz"])
+                self._seg_loss(c["z_all"], c["scal"], c["dz"], c["gid_all"])
                 self._seg_backward(c["saved"], c["dz"], c["scal"])
             record(seg2)
 
@@ -502,11 +525,12 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
         torch.cuda.synchronize()
 
         def whole_dp():
+            self._gather_group_ids(c)
             z, saved = self._seg_forward(c["eeg"], c["fmri"], xb=c["xb"])
             c["z"] = z
             c["dz"] = ops._empty((B, N2), torch.float32, z)
             dp.all_gather_into(c["z_all"], z, self.group)
-            self._seg_loss(c["z_all"], c["scal"], c["dz"])
+            self._seg_loss(c["z_all"], c["scal"], c["dz"], c["gid_all"])
             self._seg_backward(saved, c["dz"], c["scal"], reduce=True)
             for w in self._works:
                 dp.wait(w)
@@ -546,10 +570,20 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
         ops.weights_changed()
         return False
 
-    def _step_graph(self, eeg, fmri):
-        if self._cap is None or self._cap["eeg"].shape != eeg.shape or self._cap["fmri"].shape != fmri.shape:
+    def _gather_group_ids(self, c):
+        """the all-gather of a grouped step's ids: issued at the start of the step on the side stream (off the EEG chain;
+        the fMRI branch that follows it there is joined before the loss), skipped when the step issues no collectives"""
+        if not c["gid_gather"]:
+            return
+        self._side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(self._side):
+            dp.all_gather_into(c["gid_all"].view(-1, 1), c["gid"].view(-1, 1), self.group)
+
+    def _step_graph(self, eeg, fmri, gid=None):
+        if (self._cap is None or self._cap["eeg"].shape != eeg.shape or self._cap["fmri"].shape != fmri.shape
+                or self._cap["grouped"] != (gid is not None)):
             step0, base0 = ops._seed_state["step"], ops._seed_state["base"]
-            self._capture(eeg, fmri)
+            self._capture(eeg, fmri, gid)
             # the dropout seeds of this capture were drawn from here on (checkpoint_state)
             self._cap["seed_step"], self._cap["seed_base"] = step0, base0
             if self._pending_epoch_word is not None:      # resumed: the replays go on from the saved epoch word
@@ -572,6 +606,8 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
             if c["xb"] is not None:
                 Bx, Cx, Tx = c["eeg"].shape
                 _hip.call("mm_pack_nct_bf16", c["eeg"], c["xb"], Bx, Cx, Tx, c["xb"].shape[2])
+        if gid is not None and gid.data_ptr() != c["gid"].data_ptr():
+            c["gid"].copy_(gid)
         return self._replay()
 
     def _replay(self):
@@ -580,6 +616,8 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
         if len(g) == 1:
             g[0].replay()
         else:
+            if c["gid_gather"]:
+                dp.all_gather_into(c["gid_all"].view(-1, 1), c["gid"].view(-1, 1), self.group)
             g[0].replay()                                              # forward
             dp.all_gather_into(c["z_all"], c["z"], self.group)
             g[1].replay()                                              # loss on the gathered batch + backward
@@ -588,13 +626,16 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
         return {"loss": c["scal"][0], "top1_e2f": c["scal"][1], "top1_f2e": c["scal"][2]}
 
     # ---- host-fed input path ---------------------------------------------------
-    def pack_host_batch(self, eeg: torch.Tensor, fmri: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def pack_host_batch(self, eeg: torch.Tensor, fmri: torch.Tensor, out: Optional[torch.Tensor] = None,
+                        groups: Optional[torch.Tensor] = None) -> torch.Tensor:
         """CPU side of the host-fed loop (a data loader's job, off the step's critical path): one (EEG, fMRI) batch as
         ONE flat pinned byte buffer in the layout of the step's static inputs - the EEG epochs already in the first
         convolution's operand format (channels-last (B, T, Cp) bf16, zero-padded channels: half the bytes of fp32, and
         no pack launch on the device; raw fp32 for the STFT front-end) followed by the fp32 volumes.  Round-to-nearest-
         even on the host = what mm_pack_nct_bf16 does on the device: the step's arithmetic is bit-identical.
+        ``groups``: a grouped batch's (B,) ids, appended as int32 (the layout of a grouped capture's inputs).
         Reference counterpart: the ``.to(device)`` of each batch, run_training_lite.py:480-481."""
+        gid = ops.group_ids(groups.detach().cpu() if groups is not None else None, eeg.shape[0], None, "pack_host_batch")
         eeg, fmri = eeg.detach().cpu().float(), fmri.detach().cpu().float().contiguous()
         if self._eeg_kind == "stft":
             e_bytes = eeg.contiguous().view(-1).view(torch.uint8)
@@ -605,11 +646,14 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
             xb[:, :, :C] = eeg.permute(0, 2, 1)
             e_bytes = xb.view(-1).view(torch.uint8)
         f_bytes = fmri.view(-1).view(torch.uint8)
-        n = e_bytes.numel() + f_bytes.numel()
+        g_bytes = gid.view(torch.uint8) if gid is not None else torch.empty(0, dtype=torch.uint8)
+        n_e, n_f = e_bytes.numel(), f_bytes.numel()
+        n = n_e + n_f + g_bytes.numel()
         if out is None:
             out = torch.empty(n, dtype=torch.uint8).pin_memory()
-        out[:e_bytes.numel()].copy_(e_bytes)
-        out[e_bytes.numel():].copy_(f_bytes)
+        out[:n_e].copy_(e_bytes)
+        out[n_e:n_e + n_f].copy_(f_bytes)
+        out[n_e + n_f:n].copy_(g_bytes)
         return out
 
     def train_step_packed(self, flat: torch.Tensor) -> Dict[str, torch.Tensor]:
@@ -662,12 +706,13 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
         return None if self._cap is None else (self._cap["eeg"], self._cap["fmri"])
 
     @torch.no_grad()
-    def evaluate(self, eeg, fmri):
+    def evaluate(self, eeg, fmri, groups=None):
+        """eval-mode loss and in-batch top-1 of one batch (``groups``: as in `train_step`)"""
         was = self.training
         self.eval()
         ops.weights_changed()                      # graph replays bypass the python-side version counter
         try:
-            loss, acc_e, acc_f = self.forward(eeg, fmri)
+            loss, acc_e, acc_f = self.forward(eeg, fmri, groups)
         finally:
             self.train(was)
         return {"loss": loss, "top1_e2f": acc_e, "top1_f2e": acc_f}
@@ -706,16 +751,18 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
         return ze, zf
 
     @torch.no_grad()
-    def evaluate_retrieval(self, eeg, fmri, batch_size: int = 256, ks=(1, 5, 10), k: int = 0):
+    def evaluate_retrieval(self, eeg, fmri, batch_size: int = 256, ks=(1, 5, 10), k: int = 0, groups=None):
         """held-out gallery retrieval: ``embed`` both modalities, then ``retrieval_metrics`` (pair i is the positive of
-        query i, both directions).  k > 0 adds ``topk``: {"eeg_to_fmri": (idx, score), "fmri_to_eeg": (idx, score)},
-        each (N, k).  Single process only: a sharded gallery is not supported."""
+        query i, both directions; with ``groups`` (N,) every pair of the query's group, the best-placed one ranked).
+        k > 0 adds ``topk``: {"eeg_to_fmri": (idx, score), "fmri_to_eeg": (idx, score)}, each (N, k).  Single process
+        only: a sharded gallery is not supported."""
         if self.world > 1:
             raise ValueError("evaluate_retrieval: the gallery is not sharded; run it on one process (world size 1)")
         if eeg.shape[0] != fmri.shape[0]:
             raise ValueError(f"evaluate_retrieval: {eeg.shape[0]} EEG epochs but {fmri.shape[0]} fMRI volumes")
+        ops.group_ids(groups, eeg.shape[0], None, "evaluate_retrieval")      # bad ids fail before the encoders run
         ze, zf = self.embed(eeg, fmri, batch_size)
-        out = retrieval_metrics(ze, zf, ks)
+        out = retrieval_metrics(ze, zf, ks, groups)
         if k > 0:
             _, ie, se = ops.retrieval(ze, zf, k=k, ranks=False)
             _, if_, sf = ops.retrieval(zf, ze, k=k, ranks=False)
@@ -797,3 +844,24 @@ def synthetic_pairs(batch: int, eeg_channels: int = 64, samples: int = 1024, vol
     eeg = (z @ A_e.t()).unsqueeze(-1) * 0.5 + torch.randn(batch, eeg_channels, samples, generator=g)
     fmri = (z @ A_f.t()).view(batch, 1, *vol) + torch.randn(batch, 1, *vol, generator=g)
     return eeg.to(device), fmri.to(device)
+
+
+def synthetic_subject_pairs(subjects: int, per_subject: int, eeg_channels: int = 64, samples: int = 1024, vol=(32, 32, 32),
+                            seed: int = 1234, device="cuda", latent: int = 16, epoch_noise: float = 0.5):
+    """``synthetic_pairs`` with the structure of real recordings: several EEG epochs per subject, one fMRI volume per
+    subject.  Subject s has one latent z_s and one volume A_f z_s + N(0,1), repeated for every pair of the subject;
+    each EEG epoch is built from z_s + ``epoch_noise`` N(0,1) as in ``synthetic_pairs``.  Pairs are subject-major.
+    -> (eeg (S*E, C, T), fmri (S*E, 1, *vol), groups int32 (S*E,) = the subject index), all on ``device``."""
+    if subjects < 1 or per_subject < 1:
+        raise ValueError("synthetic_subject_pairs: need subjects >= 1 and per_subject >= 1")
+    g = torch.Generator().manual_seed(seed)
+    gm = torch.Generator().manual_seed(99)
+    A_e = torch.randn(eeg_channels, latent, generator=gm)
+    A_f = torch.randn(vol[0] * vol[1] * vol[2], latent, generator=gm) / latent ** 0.5
+    z = torch.randn(subjects, latent, generator=g)
+    fmri_s = (z @ A_f.t()).view(subjects, 1, *vol) + torch.randn(subjects, 1, *vol, generator=g)
+    groups = torch.arange(subjects).repeat_interleave(per_subject)
+    z_ep = z[groups] + epoch_noise * torch.randn(subjects * per_subject, latent, generator=g)
+    eeg = (z_ep @ A_e.t()).unsqueeze(-1) * 0.5 + torch.randn(subjects * per_subject, eeg_channels, samples, generator=g)
+    fmri = fmri_s[groups]
+    return eeg.to(device), fmri.to(device), groups.to(torch.int32).to(device)

@@ -82,11 +82,14 @@ class EEGfMRIContrastiveBridge(nn.Module):
         """L2-normalised (ze, zf), each (B, bridge_dim) fp32."""
         return ops.contrastive_embed(self.bridge, eeg_feats, fmri_feats, self.training)
 
-    def forward(self, eeg_feats, fmri_feats, group=None):
+    def forward(self, eeg_feats, fmri_feats, group=None, groups=None):
         """-> (loss, top1_eeg_to_fmri, top1_fmri_to_eeg).  With a process
-        ``group`` the columns are the all-gathered global batch."""
+        ``group`` the columns are the all-gathered global batch.  ``groups``:
+        (B,) integer ids (e.g. subjects); pairs with equal ids are positives of
+        each other (ops.clip_loss)."""
+        gid = ops.group_ids(groups, eeg_feats.shape[0], eeg_feats.device, "EEGfMRIContrastiveBridge")
         ze, zf = self.embed(eeg_feats, fmri_feats)
-        return ops.clip_loss(ze, zf, self.logit_scale, group)
+        return ops.clip_loss(ze, zf, self.logit_scale, group, gid)
 
 
 def rank_summary(ranks: torch.Tensor, ks=(1, 5, 10)) -> dict:
@@ -100,16 +103,19 @@ def rank_summary(ranks: torch.Tensor, ks=(1, 5, 10)) -> dict:
     return out
 
 
-def retrieval_metrics(ze: torch.Tensor, zf: torch.Tensor, ks=(1, 5, 10)) -> dict:
+def retrieval_metrics(ze: torch.Tensor, zf: torch.Tensor, ks=(1, 5, 10), groups=None) -> dict:
     """Gallery-scale CLIP-style retrieval of paired embeddings: pair i is the positive of query i.  Every EEG
     embedding queries all fMRI embeddings and vice versa (mm_retrieval twice, Q and G swapped; no N x N score matrix).
     A tie with the positive counts against the query (a collapsed encoder ranks N, not 1).
+    ``groups`` (N,) integer ids (e.g. subjects): every pair of the query's group is a positive, and both directions rank
+    the best-placed one (ops.retrieval with q_groups = g_groups = groups).
     -> {"eeg_to_fmri": {R@k..., median_rank, mean_rank, mrr}, "fmri_to_eeg": {...}, "n": N, "chance": 1 / N}"""
     if ze.shape != zf.shape or ze.dim() != 2:
         raise ValueError(f"retrieval_metrics: ze {tuple(ze.shape)} and zf {tuple(zf.shape)} must be equal (N, D)")
+    gid = ops.group_ids(groups, ze.shape[0], ze.device, "retrieval_metrics")
     ze, zf = ze.detach().float().contiguous(), zf.detach().float().contiguous()
-    r_ef, _, _ = ops.retrieval(ze, zf)
-    r_fe, _, _ = ops.retrieval(zf, ze)
+    r_ef, _, _ = ops.retrieval(ze, zf, q_groups=gid, g_groups=gid)
+    r_fe, _, _ = ops.retrieval(zf, ze, q_groups=gid, g_groups=gid)
     n = ze.shape[0]
     return {"eeg_to_fmri": rank_summary(r_ef, ks), "fmri_to_eeg": rank_summary(r_fe, ks), "n": n, "chance": 1.0 / n}
 

@@ -468,6 +468,126 @@ __global__ __launch_bounds__(256) void clip_rows_kernel(const float* __restrict_
 }
 
 // ---------------------------------------------------------------------------
+// the same InfoNCE with subject-grouped positives (MIL-NCE, "log of the positive mass").  gid[Bg] int32: pairs with
+// equal ids are positives of each other; P(r) = {j : gid_j = gid_r} always holds r.
+//   l_row(r) = LSE_j(s C[r][j]) - LSE_{j in P(r)}(s C[r][j]),  l_col(r) the same over column r,  loss_r = 0.5 (l_row + l_col)
+//   dL/dC[r][j] = 0.5/B * s * (P_row + P_col - [gid_r = gid_j] (Q_row + Q_col))[r][j]
+// Q = the softmax restricted to the positive set: Q_row[r][j] = exp(s C[r][j] - LSE_P(row r)), Q_col[r][j] =
+// exp(s C[r][j] - LSE_P(column j)).  Same two launches and rules as above; ws[8][Bg] = the six rows of the ungrouped
+// layout (row / column LSE, loss, top-1 flags, d loss / d logit_scale) + the positive-set LSE of every row and column.
+// With all-distinct ids every positive-set LSE is s C[r][r] + log 1 and the result is the ungrouped one.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ void clip_max2(float& a, float& c, float* red) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    a = wave_max(a); c = wave_max(c);
+    if (lane == 0) { red[wave] = a; red[4 + wave] = c; }
+    __syncthreads();
+    a = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+    c = fmaxf(fmaxf(red[4], red[5]), fmaxf(red[6], red[7]));
+    __syncthreads();
+}
+
+__global__ __launch_bounds__(256) void clip_lse_grouped_kernel(const float* __restrict__ z_all, const int* __restrict__ gid,
+                                                               const float* __restrict__ logit_scale, float* __restrict__ ws,
+                                                               int Bg, int N) {
+    extern __shared__ float sm[];
+    const ClipShared sh = clip_shared(sm, N, Bg);
+    const int r = blockIdx.x, tid = threadIdx.x;
+    const float s = __expf(logit_scale[0]);
+    const int gr = gid[r];
+    float mxr, mxc;
+    clip_cosines(z_all, r, Bg, N, sh, mxr, mxc);
+    float pmr = -INFINITY, pmc = -INFINITY;                  // maxima over the positive set (the top-1 test and the stable LSE)
+    for (int j = tid; j < Bg; j += 256)
+        if (gid[j] == gr) { pmr = fmaxf(pmr, sh.cr[j]); pmc = fmaxf(pmc, sh.cc[j]); }
+    clip_max2(pmr, pmc, sh.red);
+    float se = 0.f, sf = 0.f, ee = 0.f, ef = 0.f;           // all columns: sum exp, sum exp * cos
+    float qe = 0.f, qf = 0.f, qee = 0.f, qef = 0.f;         // the positive set
+    for (int j = tid; j < Bg; j += 256) {
+        const float a = sh.cr[j], c = sh.cc[j];
+        const float pa = __expf(s * (a - mxr)), pc = __expf(s * (c - mxc));
+        se += pa; sf += pc; ee += pa * a; ef += pc * c;
+        if (gid[j] == gr) {
+            const float qa = __expf(s * (a - pmr)), qc = __expf(s * (c - pmc));
+            qe += qa; qf += qc; qee += qa * a; qef += qc * c;
+        }
+    }
+    clip_sum2(se, sf, sh.red);
+    clip_sum2(ee, ef, sh.red);
+    clip_sum2(qe, qf, sh.red);
+    clip_sum2(qee, qef, sh.red);
+    if (tid == 0) {
+        const float lse_r = s * mxr + __logf(se), lse_c = s * mxc + __logf(sf);
+        const float lsp_r = s * pmr + __logf(qe), lsp_c = s * pmc + __logf(qf);
+        ws[r] = lse_r;
+        ws[Bg + r] = lse_c;
+        ws[2 * Bg + r] = 0.5f * ((lse_r - lsp_r) + (lse_c - lsp_c));
+        ws[3 * Bg + r] = pmr >= mxr ? 1.f : 0.f;             // the best positive reaches the row maximum (a tie counts FOR it)
+        ws[4 * Bg + r] = pmc >= mxc ? 1.f : 0.f;
+        ws[5 * Bg + r] = s * 0.5f * ((ee / se - qee / qe) + (ef / sf - qef / qf));
+        ws[6 * Bg + r] = lsp_r;
+        ws[7 * Bg + r] = lsp_c;
+    }
+}
+
+__global__ __launch_bounds__(256) void clip_rows_grouped_kernel(const float* __restrict__ z_all, const int* __restrict__ gid,
+                                                                const float* __restrict__ logit_scale,
+                                                                const float* __restrict__ ws, float* __restrict__ scal,
+                                                                float* __restrict__ dz, int B, int Bg, int N, int row0) {
+    extern __shared__ float sm[];
+    const ClipShared sh = clip_shared(sm, N, Bg);
+    const int i = blockIdx.x, gi = row0 + i, tid = threadIdx.x, LD = 2 * N;
+    const float s = __expf(logit_scale[0]);
+    const float invB = 1.f / (float)B;
+    if (i == 0 && tid < 64) {                               // the own rows' scalars, summed in a fixed order
+        float acc[4] = {0.f, 0.f, 0.f, 0.f};
+        for (int r0 = 0; r0 < B; r0 += 64) {
+            float v[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) v[q] = (r0 + tid < B) ? ws[(size_t)(2 + q) * Bg + row0 + r0 + tid] : 0.f;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) acc[q] += wave_sum(v[q]);
+        }
+        if (tid < 4) scal[tid] = (tid == 0 ? acc[0] : tid == 1 ? acc[1] : tid == 2 ? acc[2] : acc[3]) * invB;
+    }
+    if (!dz) return;
+    float mxr, mxc;
+    clip_cosines(z_all, gi, Bg, N, sh, mxr, mxc);
+    // dL/dC[gi][j] -> cr[j],  dL/dC[j][gi] -> cc[j]
+    const float lse_rg = ws[gi], lse_cg = ws[Bg + gi], lsp_rg = ws[6 * Bg + gi], lsp_cg = ws[7 * Bg + gi];
+    const int g = gid[gi];
+    const float k = 0.5f * invB * s;
+    for (int j = tid; j < Bg; j += 256) {
+        const float a = s * sh.cr[j], c = s * sh.cc[j];
+        float ga = __expf(a - lse_rg) + __expf(a - ws[Bg + j]);          // P_row[gi][j] + P_col[gi][j]
+        float gc = __expf(c - ws[j]) + __expf(c - lse_cg);               // P_row[j][gi] + P_col[j][gi]
+        if (gid[j] == g) {
+            ga -= __expf(a - lsp_rg) + __expf(a - ws[7 * Bg + j]);       // Q_row[gi][j] + Q_col[gi][j]
+            gc -= __expf(c - ws[6 * Bg + j]) + __expf(c - lsp_cg);       // Q_row[j][gi] + Q_col[j][gi]
+        }
+        sh.cr[j] = k * ga; sh.cc[j] = k * gc;
+    }
+    __syncthreads();
+    float* orow = dz + (size_t)i * LD;
+    for (int n = tid; n < 2 * N; n += 256) {                // first half: dze (columns of zf), second half: dzf
+        const bool first = n < N;
+        const float* gr = first ? sh.cr : sh.cc;
+        const float* col = z_all + (first ? N + n : n - N);
+        float acc = 0.f;
+        int j = 0;
+        for (; j + 8 <= Bg; j += 8) {                       // 8 loads in flight, summed in order
+            float v[8];
+#pragma unroll
+            for (int q = 0; q < 8; ++q) v[q] = col[(size_t)(j + q) * LD];
+#pragma unroll
+            for (int q = 0; q < 8; ++q) acc += gr[j + q] * v[q];
+        }
+        for (; j < Bg; ++j) acc += gr[j] * col[(size_t)j * LD];
+        orow[n] = acc;
+    }
+}
+
+// ---------------------------------------------------------------------------
 // fused AdamW (decoupled weight decay) + global-norm clip on a flat fp32 bucket.
 // state[0] = step counter (float, incremented on device so the launch can live
 // in a hipGraph), state[2] = learning rate (host-updatable), state[3] = last clip
@@ -1697,6 +1817,27 @@ int mm_clip_loss_own_rows(const float* z_all, const float* logit_scale, float* s
     if (rc) return rc;
     hipLaunchKernelGGL(clip_rows_kernel, dim3(B), dim3(256), lds, st, z_all, logit_scale, ws, scal4, dz_local, B, Bg, N, row0);
     return mm_check_launch("clip_loss_own_rows(rows)");
+}
+
+int mm_clip_loss_grouped_ws_floats(int B, int Bg, int* floats_host, hipStream_t) {
+    MM_REQUIRE(floats_host && B > 0 && Bg >= B, "clip_loss_grouped_ws_floats: bad args");
+    *floats_host = 8 * Bg;
+    return 0;
+}
+
+int mm_clip_loss_own_rows_grouped(const float* z_all, const int* gid_all, const float* logit_scale, float* scal4, float* dz_local,
+                                  float* ws, int B, int Bg, int N, int row0, hipStream_t st) {
+    MM_REQUIRE(z_all && gid_all && logit_scale && scal4 && ws, "clip_loss_own_rows_grouped: null");
+    MM_REQUIRE(B > 0 && Bg >= B && row0 >= 0 && row0 + B <= Bg && N > 0, "clip_loss_own_rows_grouped: B=%d Bg=%d row0=%d", B, Bg, row0);
+    MM_REQUIRE(N % 4 == 0, "clip_loss_own_rows_grouped: N=%d must be a multiple of 4 (16-byte row loads)", N);
+    const size_t lds = (size_t)(2 * N + 2 * Bg + 32) * sizeof(float);
+    MM_REQUIRE(lds <= 64 * 1024, "clip_loss_own_rows_grouped: N/Bg too large for LDS");
+    hipLaunchKernelGGL(clip_lse_grouped_kernel, dim3(Bg), dim3(256), lds, st, z_all, gid_all, logit_scale, ws, Bg, N);
+    int rc = mm_check_launch("clip_loss_own_rows_grouped(lse)");
+    if (rc) return rc;
+    hipLaunchKernelGGL(clip_rows_grouped_kernel, dim3(B), dim3(256), lds, st, z_all, gid_all, logit_scale, ws, scal4, dz_local,
+                       B, Bg, N, row0);
+    return mm_check_launch("clip_loss_own_rows_grouped(rows)");
 }
 
 int mm_sumsq(const float* g, float* state, int64_t n, hipStream_t st) {

@@ -16,6 +16,12 @@
 //   placed).  At the end of the slice: per-(slice, query) count and list to the workspace.
 // Pass 3 (retr_finish_kernel): one thread per query adds its slices' counts (integers) and merges their lists in slice
 //   order.  No float atomics: same inputs -> same bits.
+//
+// Grouped positives (mm_retrieval_grouped): gallery row j is a positive of query q when ggid[j] == qgid[q], and the rank
+// is that of the best-placed positive.  Pass 1 becomes a sweep of the same tiles (retr_tile_kernel<false, false,
+// GRP_MAX>): per (slice, query) the maximum score over the slice's positives; retr_best_kernel folds the slices into
+// s*(q).  The counting sweep (GRP_COUNT) then counts {j : ggid[j] != qgid[q], s >= s*} and pass 3 is unchanged.  Both
+// sweeps score with the same MFMA chain, so a duplicate of the best positive ties with it bit for bit.
 #include "common.h"
 #include "mmeeg_hip.h"
 #include <limits.h>
@@ -31,6 +37,15 @@ constexpr int KMAX = MM_RETRIEVAL_KMAX;
 constexpr int LSTR = KMAX + 1;          // per-row list stride in LDS (odd: one thread per row, no 16-way conflicts)
 constexpr int CAP = 16;                 // top-k candidates per row per merge round
 constexpr int TARGET_WG = 512;          // 2 workgroups per CU on 256 CUs
+constexpr int GRP_NONE = 0, GRP_MAX = 1, GRP_COUNT = 2;     // retr_tile_kernel's group modes (see the file comment)
+
+// max that ignores NaN: a NaN b leaves a; NaN only when both are
+__device__ __forceinline__ float nanmax(float a, float b) { return (b > a || a != a) ? b : a; }
+__device__ __forceinline__ float half32_nanmax(float v) {      // over each aligned group of 32 lanes (fixed pairing)
+#pragma unroll
+    for (int o = 1; o < 32; o <<= 1) v = nanmax(v, __shfl_xor(v, o, 64));
+    return v;
+}
 
 __device__ __forceinline__ bool beats(float s, int j, float ts, int tj) {
     // total order of the top-k lists: score descending, then index ascending; NaN never beats anything
@@ -90,13 +105,15 @@ static RetrPlan retr_plan(int Nq, int Ng) {
 
 struct RetrArgs {
     const float* Q; const float* G; const int* pos; const float* spos;
+    const int* qgid; const int* ggid;       // grouped positives (GRP_MAX / GRP_COUNT), else null
+    float* smax;       // [nslices][Nq] per-slice maxima over the positives (GRP_MAX)
     int* cnt;          // [nslices][Nq]
     float* tks;        // [nslices][Nq][k]
     int* tki;          // [nslices][Nq][k]
     int Nq, Ng, D, k, tps, ntiles;
 };
 
-template <bool RANK, bool TOPK>
+template <bool RANK, bool TOPK, int GRP = GRP_NONE>
 __global__ __launch_bounds__(256, TOPK ? 1 : 2) void retr_tile_kernel(RetrArgs a) {
     __shared__ float qs[KC * LDS_STRIDE];
     __shared__ float gs[KC * LDS_STRIDE];
@@ -107,7 +124,8 @@ __global__ __launch_bounds__(256, TOPK ? 1 : 2) void retr_tile_kernel(RetrArgs a
     __shared__ int ccount[TOPK ? QB : 1];
     __shared__ int part[RANK ? 2 * QB : 1];
     __shared__ float sp_s[RANK ? QB : 1];
-    __shared__ int pq_s[RANK ? QB : 1];
+    __shared__ int pq_s[RANK || GRP ? QB : 1];         // the positive's index, or the query's group id
+    __shared__ float pmax[GRP == GRP_MAX ? 2 * QB : 1];
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int li = lane & 31, h = lane >> 5;
@@ -121,11 +139,20 @@ __global__ __launch_bounds__(256, TOPK ? 1 : 2) void retr_tile_kernel(RetrArgs a
     // rows this lane's accumulator registers hold: tile row of (rt, reg) = wr * 64 + 32 rt + (reg & 3) + 8 (reg >> 2) + 4 h.
     // Positive score / index per row in LDS (read per tile: registers go to the accumulators and the counts)
     int cnt[2][16];
+    float mx[2][16];
+    if constexpr (GRP == GRP_MAX) {
+        if (tid < QB) pq_s[tid] = a.qgid[min(q0 + tid, a.Nq - 1)];
+#pragma unroll
+        for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) mx[rt][r] = __builtin_nanf("");
+    }
     if (RANK) {
         if (tid < QB) {
             const int q = min(q0 + tid, a.Nq - 1);
             sp_s[tid] = a.spos[q];
-            pq_s[tid] = a.pos ? a.pos[q] : q;
+            if constexpr (GRP == GRP_COUNT) pq_s[tid] = a.qgid[q];
+            else pq_s[tid] = a.pos ? a.pos[q] : q;
         }
 #pragma unroll
         for (int rt = 0; rt < 2; ++rt)
@@ -164,6 +191,12 @@ __global__ __launch_bounds__(256, TOPK ? 1 : 2) void retr_tile_kernel(RetrArgs a
     fetch(t_begin, 0);
     for (int t = t_begin; t < t_end; ++t) {
         f32x16 acc[2][2] = {};
+        int gg[2] = {0, 0};                        // group ids of this lane's two columns (loaded under the MFMA loop)
+        if constexpr (GRP != GRP_NONE) {
+            const int j0 = t * GB + wc * 64 + li;
+            gg[0] = j0 < a.Ng ? a.ggid[j0] : 0;
+            gg[1] = j0 + 32 < a.Ng ? a.ggid[j0 + 32] : 0;
+        }
         for (int c = 0; c < nchunk; ++c) {
             __syncthreads();                       // every wave is done reading the previous chunk
             stash();
@@ -193,7 +226,21 @@ __global__ __launch_bounds__(256, TOPK ? 1 : 2) void retr_tile_kernel(RetrArgs a
                     const int row = wr * 64 + 32 * rt + (r & 3) + 8 * (r >> 2) + 4 * h;
                     const float sp = sp_s[row];
                     const int pq = pq_s[row];
-                    cnt[rt][r] += (in0 & (acc[rt][0][r] >= sp) & (jb != pq)) + (in1 & (acc[rt][1][r] >= sp) & (jb + 32 != pq));
+                    if constexpr (GRP == GRP_COUNT)
+                        cnt[rt][r] += (in0 & (acc[rt][0][r] >= sp) & (gg[0] != pq)) + (in1 & (acc[rt][1][r] >= sp) & (gg[1] != pq));
+                    else
+                        cnt[rt][r] += (in0 & (acc[rt][0][r] >= sp) & (jb != pq)) + (in1 & (acc[rt][1][r] >= sp) & (jb + 32 != pq));
+                }
+        }
+        if constexpr (GRP == GRP_MAX) {
+            const bool in0 = jb < a.Ng, in1 = jb + 32 < a.Ng;
+#pragma unroll
+            for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int pq = pq_s[wr * 64 + 32 * rt + (r & 3) + 8 * (r >> 2) + 4 * h];
+                    if (in0 && gg[0] == pq) mx[rt][r] = nanmax(mx[rt][r], acc[rt][0][r]);
+                    if (in1 && gg[1] == pq) mx[rt][r] = nanmax(mx[rt][r], acc[rt][1][r]);
                 }
         }
         if (TOPK) {
@@ -248,6 +295,18 @@ __global__ __launch_bounds__(256, TOPK ? 1 : 2) void retr_tile_kernel(RetrArgs a
         __syncthreads();
         if (tid < QB && q0 + tid < a.Nq) a.cnt[(size_t)slice * a.Nq + q0 + tid] = part[tid] + part[QB + tid];
     }
+    if constexpr (GRP == GRP_MAX) {
+        // the 32 lanes of a half hold the same rows: fold over them, then over the two column waves
+#pragma unroll
+        for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const float v = half32_nanmax(mx[rt][r]);
+                if (li == 0) pmax[wc * QB + wr * 64 + 32 * rt + (r & 3) + 8 * (r >> 2) + 4 * h] = v;
+            }
+        __syncthreads();
+        if (tid < QB && q0 + tid < a.Nq) a.smax[(size_t)slice * a.Nq + q0 + tid] = nanmax(pmax[tid], pmax[QB + tid]);
+    }
     if (TOPK) {
         __syncthreads();
         for (int e = tid; e < QB * k; e += 256) {
@@ -293,6 +352,15 @@ __global__ __launch_bounds__(64) void retr_finish_kernel(RetrArgs a, int nslices
             topk_score[(size_t)q * k + m] = filled ? l_s[m] : -INFINITY;
         }
     }
+}
+
+// one thread per query: s*(q) = the slices' maxima folded in slice order (NaN: no positive with a number for a score)
+__global__ __launch_bounds__(64) void retr_best_kernel(const float* __restrict__ smax, float* __restrict__ spos, int nslices, int Nq) {
+    const int q = blockIdx.x * 64 + threadIdx.x;
+    if (q >= Nq) return;
+    float v = __builtin_nanf("");
+    for (int s = 0; s < nslices; ++s) v = nanmax(v, smax[(size_t)s * Nq + q]);
+    spos[q] = v;
 }
 
 static int64_t retr_ws(const RetrPlan& p, int Nq, int k) {
@@ -351,4 +419,41 @@ extern "C" int mm_retrieval(const float* Q, const float* G, const int* pos, int*
     if (int e = mm_check_launch("mm_retrieval: tiles")) return e;
     retr_finish_kernel<<<ceil_div(Nq, 64), 64, 0, stream>>>(a, p.nslices, ranks, k > 0 ? topk_idx : nullptr, topk_score);
     return mm_check_launch("mm_retrieval: finish");
+}
+
+extern "C" int mm_retrieval_grouped_ws_floats(int Nq, int Ng, int D, int* floats_host, hipStream_t) {
+    MM_REQUIRE(floats_host, "mm_retrieval_grouped_ws_floats: null floats_host");
+    const int rc = retr_check_shape("mm_retrieval_grouped_ws_floats", Nq, Ng, D, 0);
+    if (rc) return rc;
+    *floats_host = (int)retr_ws(retr_plan(Nq, Ng), Nq, 0);
+    return MM_OK;
+}
+
+extern "C" int mm_retrieval_grouped(const float* Q, const float* G, const int* qgid, const int* ggid, int* ranks, float* ws,
+                                    int Nq, int Ng, int D, hipStream_t stream) {
+    MM_REQUIRE(Q && G && qgid && ggid && ranks && ws, "mm_retrieval_grouped: null argument");
+    const int rc = retr_check_shape("mm_retrieval_grouped", Nq, Ng, D, 0);
+    if (rc) return rc;
+    MM_REQUIRE(((uintptr_t)Q % 16) == 0 && ((uintptr_t)G % 16) == 0, "mm_retrieval_grouped: Q and G must be 16-byte aligned");
+
+    const RetrPlan p = retr_plan(Nq, Ng);
+    RetrArgs a = {};
+    a.Q = Q; a.G = G; a.qgid = qgid; a.ggid = ggid;
+    float* spos = ws;
+    // the per-slice maxima and the per-slice counts share one region: retr_best_kernel has read the maxima before the
+    // counting sweep writes its counts (stream order)
+    a.smax = ws + Nq;
+    a.cnt = reinterpret_cast<int*>(ws + Nq);
+    a.spos = spos;
+    a.Nq = Nq; a.Ng = Ng; a.D = D; a.k = 0; a.tps = p.tps; a.ntiles = p.ntiles;
+
+    const dim3 grid(p.qblocks, p.nslices);
+    retr_tile_kernel<false, false, GRP_MAX><<<grid, 256, 0, stream>>>(a);
+    if (int e = mm_check_launch("mm_retrieval_grouped: positive maxima")) return e;
+    retr_best_kernel<<<ceil_div(Nq, 64), 64, 0, stream>>>(a.smax, spos, p.nslices, Nq);
+    if (int e = mm_check_launch("mm_retrieval_grouped: best positive")) return e;
+    retr_tile_kernel<true, false, GRP_COUNT><<<grid, 256, 0, stream>>>(a);
+    if (int e = mm_check_launch("mm_retrieval_grouped: tiles")) return e;
+    retr_finish_kernel<<<ceil_div(Nq, 64), 64, 0, stream>>>(a, p.nslices, ranks, nullptr, nullptr);
+    return mm_check_launch("mm_retrieval_grouped: finish");
 }

@@ -356,6 +356,45 @@ def clip_loss_ws_floats(B: int, Bg: int) -> int:
     return n
 
 
+def clip_loss_grouped_ws_floats(B: int, Bg: int) -> int:
+    """floats of mm_clip_loss_own_rows_grouped's scratch (mm_clip_loss_grouped_ws_floats), cached per shape"""
+    key = ("grouped", B, Bg)
+    n = _CLIP_WS.get(key)
+    if n is None:
+        import ctypes
+        c = ctypes.c_int(0)
+        _hip.call("mm_clip_loss_grouped_ws_floats", B, Bg, ctypes.addressof(c))
+        n = _CLIP_WS[key] = c.value
+    return n
+
+
+def group_ids(groups, n: int, device=None, who: str = "groups") -> Optional[torch.Tensor]:
+    """Validate a (n,) vector of group ids (e.g. subject indices; compared for equality only) -> int32 on ``device``, or
+    None for None.  A host tensor of any integer dtype is range-checked and converted; a device tensor must already be
+    int32 (checking its values would synchronise a replayed step).  Anything else raises ValueError before any launch."""
+    if groups is None:
+        return None
+    if not isinstance(groups, torch.Tensor):
+        raise ValueError(f"{who}: group ids must be a torch.Tensor (got {type(groups).__name__})")
+    if groups.dim() != 1 or groups.shape[0] != n:
+        raise ValueError(f"{who}: group ids must have shape ({n},) (got {tuple(groups.shape)})")
+    if groups.dtype.is_floating_point or groups.dtype.is_complex or groups.dtype == torch.bool:
+        raise ValueError(f"{who}: group ids must be an integer tensor (got {groups.dtype})")
+    if groups.is_cuda:
+        if groups.dtype != torch.int32:
+            raise ValueError(f"{who}: group ids on the device must be int32 (got {groups.dtype}); host tensors of any integer "
+                             "dtype are converted")
+        if device is not None and groups.device != torch.device(device):
+            raise ValueError(f"{who}: group ids are on {groups.device}, the batch on {device}")
+        return groups.contiguous()
+    if n and groups.dtype != torch.int32:
+        g64 = groups.long()
+        if bool((g64 < -2 ** 31).any()) or bool((g64 >= 2 ** 31).any()):
+            raise ValueError(f"{who}: group ids must fit in int32")
+    g32 = groups.to(torch.int32).contiguous()
+    return g32 if device is None else g32.to(device)
+
+
 def linear_rows(x2d: torch.Tensor, weight: torch.Tensor, bias, *, act="none", residual=None,
                 out_f32=False, out_bf16=True, out_pre=False, drop_p=0.0, seed=0, need_dgrad=False):
     """(M, K) bf16 @ weight(N, K)^T + bias with a fused epilogue (taps == 1)."""
@@ -1058,14 +1097,40 @@ def retrieval_kmax() -> int:
     return int(m.group(1))
 
 
+_RETR_GWS: Dict[Tuple[int, int, int], int] = {}
+
+
+def retrieval_grouped_ws_floats(nq: int, ng: int, d: int) -> int:
+    """floats of mm_retrieval_grouped's scratch (mm_retrieval_grouped_ws_floats), cached per shape"""
+    key = (nq, ng, d)
+    n = _RETR_GWS.get(key)
+    if n is None:
+        import ctypes
+        c = ctypes.c_int(0)
+        _hip.call("mm_retrieval_grouped_ws_floats", nq, ng, d, ctypes.addressof(c))
+        n = _RETR_GWS[key] = c.value
+    return n
+
+
 def retrieval(q: torch.Tensor, g: torch.Tensor, positives: Optional[torch.Tensor] = None, k: int = 0,
-              ranks: bool = True):
+              ranks: bool = True, q_groups: Optional[torch.Tensor] = None, g_groups: Optional[torch.Tensor] = None):
     """Rank of each query's positive among all gallery rows and / or its top-k matches (mm_retrieval), without an
     Nq x Ng score matrix.  q (Nq, D), g (Ng, D): contiguous fp32 on the GPU (L2-normalised rows for cosine retrieval).
     positives: int tensor (Nq,) of gallery indices (None: query i's positive is gallery row i).  Scores are exact fp32
     dot products; a tie with the positive counts AGAINST the query (rank = 1 + #{j != pos : s_j >= s_pos}).
     -> (ranks int64 (Nq,) | None, topk_idx int64 (Nq, k) | None, topk_score fp32 (Nq, k) | None); top-k is score
-    descending, equal scores by lower index, unfilled slots (-1, -inf)."""
+    descending, equal scores by lower index, unfilled slots (-1, -inf).
+    q_groups (Nq,) / g_groups (Ng,) integer group ids (both or neither; not with ``positives``; ranks only, k = 0): every
+    gallery row of the query's group is a positive, and the rank is that of the best-placed one (mm_retrieval_grouped:
+    1 + #{j outside the group : s_j >= max over the group}; a query without a positive ranks Ng)."""
+    grouped = q_groups is not None or g_groups is not None
+    if grouped:
+        if q_groups is None or g_groups is None:
+            raise ValueError("retrieval: give both q_groups and g_groups, or neither")
+        if positives is not None:
+            raise ValueError("retrieval: positives and group ids are exclusive")
+        if not ranks or int(k) != 0:
+            raise ValueError("retrieval: with group ids only ranks are computed (ranks=True, k = 0; top-k does not depend on groups)")
     for name, t in (("q", q), ("g", g)):
         if not isinstance(t, torch.Tensor) or t.dim() != 2:
             raise ValueError(f"retrieval: {name} must be a 2-D tensor")
@@ -1082,6 +1147,14 @@ def retrieval(q: torch.Tensor, g: torch.Tensor, positives: Optional[torch.Tensor
         raise ValueError(f"retrieval: q has D = {d}, g has D = {g.shape[1]}")
     if q.device != g.device:
         raise ValueError("retrieval: q and g are on different devices")
+    if grouped:
+        qg = group_ids(q_groups, nq, q.device, "retrieval: q_groups")
+        gg = group_ids(g_groups, ng, q.device, "retrieval: g_groups")
+        ws = torch.empty(retrieval_grouped_ws_floats(nq, ng, d), dtype=_F32, device=q.device)
+        r32 = torch.empty(nq, dtype=torch.int32, device=q.device)
+        with torch.cuda.device(q.device):
+            _hip.call("mm_retrieval_grouped", q, g, qg, gg, r32, ws, nq, ng, d)
+        return r32.long(), None, None
     k = int(k)
     if not 0 <= k <= min(retrieval_kmax(), ng):
         raise ValueError(f"retrieval: k must be in [0, min({retrieval_kmax()}, Ng = {ng})] (got {k})")
@@ -1117,11 +1190,14 @@ def contrastive_embed(bridge, eeg, fmri, training):
     return z[:, :N], z[:, N:]
 
 
-def clip_loss(ze, zf, logit_scale, group=None):
-    """symmetric InfoNCE over the (all-gathered) batch -> (loss, top1 e->f, top1 f->e)."""
+def clip_loss(ze, zf, logit_scale, group=None, groups=None):
+    """symmetric InfoNCE over the (all-gathered) batch -> (loss, top1 e->f, top1 f->e).  ``groups`` (B,) integer ids
+    (``group_ids``): pairs with equal ids are positives of each other (mm_clip_loss_own_rows_grouped); None: pair i is
+    the only positive of query i."""
     _need_gpu(ze)
+    gid = group_ids(groups, ze.shape[0], ze.device, "clip_loss")
     from .autograd import ClipLossFn
-    return ClipLossFn.apply(_packed_pair(ze, zf), logit_scale, group)
+    return ClipLossFn.apply(_packed_pair(ze, zf), logit_scale, group, gid)
 
 
 def _packed_pair(ze: torch.Tensor, zf: torch.Tensor) -> torch.Tensor:

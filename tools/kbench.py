@@ -361,8 +361,49 @@ def retr_case(nq, ng, d, k, vs_torch=False):
     assert ok
 
 
+def groups_case(step_iters=30):
+    """subject-grouped positives vs the ungrouped path: the loss kernel pair (graph-replayed launches) at (B, Bg, N) =
+    (32, 32, 128) and (32, 256, 128), the rank pass at Nq = Ng = 8192 and 65536 (D = 128), and the C2 graph step
+    (B = 32: 8 subjects x 4 epochs) with and without ids, interleaved rounds"""
+    for B, Bg, N in ((32, 32, 128), (32, 256, 128)):
+        z = torch.nn.functional.normalize(torch.randn(Bg, 2 * N, device="cuda"), dim=1).contiguous()
+        gid = (torch.arange(Bg, device="cuda", dtype=torch.int32) // 4).contiguous()
+        ls = torch.full((1,), math.log(1 / 0.07), device="cuda")
+        scal, dz = torch.empty(4, device="cuda"), torch.empty(B, 2 * N, device="cuda")
+        ws_u = torch.empty(ops.clip_loss_ws_floats(B, Bg), device="cuda")
+        ws_g = torch.empty(ops.clip_loss_grouped_ws_floats(B, Bg), device="cuda")
+        tu = graph_time(lambda: _hip.call("mm_clip_loss_own_rows", z, ls, scal, dz, ws_u, B, Bg, N, 0))
+        tg = graph_time(lambda: _hip.call("mm_clip_loss_own_rows_grouped", z, gid, ls, scal, dz, ws_g, B, Bg, N, 0))
+        print(f"clip loss B={B} Bg={Bg} N={N}: ungrouped {tu:7.2f} us  grouped {tg:7.2f} us  (+{tg - tu:5.2f} us)")
+    for n in (8192, 65536):
+        q = torch.nn.functional.normalize(torch.randn(n, 128, device="cuda"), dim=1).contiguous()
+        g = torch.nn.functional.normalize(torch.randn(n, 128, device="cuda"), dim=1).contiguous()
+        ids = torch.randint(0, n // 8, (n,), device="cuda", dtype=torch.int32)
+        tu = timeit(lambda: ops.retrieval(q, g), iters=5, rounds=5)
+        tg = timeit(lambda: ops.retrieval(q, g, q_groups=ids, g_groups=ids), iters=5, rounds=5)
+        print(f"ranks Nq=Ng={n} D=128: ungrouped {tu:9.1f} us  grouped {tg:9.1f} us  ({tg / tu:4.2f}x)")
+    from multimodal_eeg_fmri_amd.bridge_trainer import BridgeTrainer, synthetic_subject_pairs
+    eeg, fmri, groups = synthetic_subject_pairs(8, 4, 64, 1024, (32, 32, 32))
+    trs = []
+    for grouped in (False, True):
+        ops.set_seed_epoch(None)
+        torch.manual_seed(0)
+        tr = BridgeTrainer(eeg_channels=64, dropout=0.3).train()
+        tr.train_step(eeg, fmri, groups if grouped else None)
+        trs.append((tr, groups if grouped else None))
+    times = ([], [])
+    for _ in range(5):
+        for i, (tr, gr) in enumerate(trs):
+            times[i].append(timeit(lambda: tr.train_step(eeg, fmri, gr), iters=step_iters, rounds=1))
+    tu, tg = statistics.median(times[0]), statistics.median(times[1])
+    print(f"C2 graph step B=32: ungrouped {tu:7.1f} us  grouped {tg:7.1f} us  ({100 * (tg / tu - 1):+.2f} %)")
+
+
 def main():
     flt = sys.argv[1] if len(sys.argv) > 1 else ""
+    if flt == "groups":
+        groups_case()
+        return
     if flt == "retr":
         retr_case(16384, 16384, 128, 10, vs_torch=True)
         retr_case(65536, 65536, 128, 10)
