@@ -126,3 +126,18 @@ def call(name: str, *args):
     rc = fn(*conv)
     if rc != 0:
         raise HipLibraryError(f"{name} failed ({rc}): {lib.mm_last_error().decode()}")
+
+
+_HOST_INTS: Dict[tuple, int] = {}
+
+
+def host_int(name: str, *args) -> int:
+    """the ``int*`` result of a host-only entry point (workspace sizes, slot counts: its last argument before the
+    stream), cached per (name, args)"""
+    key = (name,) + args
+    n = _HOST_INTS.get(key)
+    if n is None:
+        c = ctypes.c_int(0)
+        call(name, *args, ctypes.addressof(c))
+        n = _HOST_INTS[key] = c.value
+    return n

@@ -65,25 +65,16 @@ def scatter_desc(ws, dw, cout, cin, taps, cinp, nrep, window=None):
     return (ws.data_ptr() + 4 * n0 * ws_taps * cinp, dw.data_ptr(), cout, cin, taps | (tap0 << 8) | (ws_taps << 16), cinp, nrep, ws_cout)
 
 
-_SLOTS = {}
-
-
 def _wgrad_slots(dy, x, dw, dbr, B, T, cinp, N, k, pad, cin, parts=None):
     """conv / linear weight gradient without atomics: every row-chunk workgroup stores its partial
     dW[n][tap][c] into its own slot of a workspace; the (deferred, batched) scatter sums the slots
     into the parameter layout."""
-    import ctypes
     bag = _BAG["cur"]
     grouped = bag is not None and k == 1
-    key = (B, T, cinp, N, k, grouped)
-    slots = _SLOTS.get(key)
-    if slots is None:
-        out = ctypes.c_int(0)
-        if grouped:
-            _hip.call("mm_conv1d_wgrad_many_slots", B, T, cinp, N, ctypes.addressof(out))
-        else:
-            _hip.call("mm_conv1d_wgrad_slots", B, T, cinp, N, k, ctypes.addressof(out))
-        slots = _SLOTS[key] = int(out.value)
+    if grouped:
+        slots = _hip.host_int("mm_conv1d_wgrad_many_slots", B, T, cinp, N)
+    else:
+        slots = _hip.host_int("mm_conv1d_wgrad_slots", B, T, cinp, N, k)
     ws = _empty((slots, N, k, cinp), _F32, dy)                   # every element has exactly one writer: no memset
     if grouped:
         # a Linear's weight gradient feeds nothing but the final slot sum: collect it; the bag issues
@@ -725,13 +716,7 @@ def conv3d_bn_act_bwd(bag: GradBag, s: dict, dout, need_dx=True):
         cinp_x = xv.shape[4]
         db = bag.target(conv.bias)
         dbr = _zeros((REPL, N), y) if db is not None else None
-        import ctypes
-        key = ("3d", B, D, H, W, cinp_x, N)
-        slots = _SLOTS.get(key)
-        if slots is None:
-            out = ctypes.c_int(0)
-            _hip.call("mm_conv3d_wgrad_slots", B, D, H, W, cinp_x, N, ctypes.addressof(out))
-            slots = _SLOTS[key] = int(out.value)
+        slots = _hip.host_int("mm_conv3d_wgrad_slots", B, D, H, W, cinp_x, N)
         ws = _empty((slots, N, 27, cinp_x), _F32, y)           # one writer per element: no atomics, no memset
         end = ops.kernel_timer.bracket(f"conv3d_wgrad_c{cinp_x}")     # (bench.py's roofline_family; off by default)
         _hip.call("mm_conv3d_wgrad", dy, xv, ws, dbr, B, D, H, W, cinp_x, N, cinp_x,
@@ -881,20 +866,14 @@ class ClipLossFn(torch.autograd.Function):
         from . import dp
         z = z.contiguous().float()
         B, N2 = z.shape
-        N = N2 // 2
-        world, rank = dp.world_size(group), dp.rank(group)
+        rank = dp.rank(group)
         z_all = dp.gather_embeddings(z, group)
         need_grad = z.requires_grad or logit_scale.requires_grad
         scal = _empty((4,), _F32, z)
         dz = _empty((B, N2), _F32, z) if need_grad else None
         ls = logit_scale.detach().reshape(1).float().contiguous()
-        if gid is None:
-            ws = _empty((ops.clip_loss_ws_floats(B, world * B),), _F32, z)
-            _hip.call("mm_clip_loss_own_rows", z_all, ls, scal, dz, ws, B, world * B, N, rank * B)
-        else:
-            gid_all = dp.gather_embeddings(gid.view(B, 1), group).view(-1)
-            ws = _empty((ops.clip_loss_grouped_ws_floats(B, world * B),), _F32, z)
-            _hip.call("mm_clip_loss_own_rows_grouped", z_all, gid_all, ls, scal, dz, ws, B, world * B, N, rank * B)
+        gid_all = None if gid is None else dp.gather_embeddings(gid.view(B, 1), group).view(-1)
+        ops.clip_loss_own_rows(z_all, gid_all, ls, scal, dz, B, rank * B)
         if need_grad:
             ctx.save_for_backward(dz, scal)
         return scal[0].clone(), scal[1].clone(), scal[2].clone()

@@ -252,16 +252,8 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
         (``mm_clip_loss_own_rows``: every rank evaluates all rows of the gathered batch, so no reduce-scatter
         of column gradients is needed).  ``scal`` = the trainer's own 4-float result buffer, ``dz`` (B, 2N): both written with plain stores.
         ``gid_all``: the gathered int32 group ids -> the grouped loss (``mm_clip_loss_own_rows_grouped``)."""
-        N2 = z_all.shape[1]
-        B = dz.shape[0]
         ls = self.head.logit_scale.detach().reshape(1)
-        if gid_all is None:
-            ws = ops._empty((ops.clip_loss_ws_floats(B, z_all.shape[0]),), torch.float32, z_all)
-            _hip.call("mm_clip_loss_own_rows", z_all, ls, scal, dz, ws, B, z_all.shape[0], N2 // 2, dp.rank(self.group) * B)
-        else:
-            ws = ops._empty((ops.clip_loss_grouped_ws_floats(B, z_all.shape[0]),), torch.float32, z_all)
-            _hip.call("mm_clip_loss_own_rows_grouped", z_all, gid_all, ls, scal, dz, ws, B, z_all.shape[0], N2 // 2,
-                      dp.rank(self.group) * B)
+        ops.clip_loss_own_rows(z_all, gid_all, ls, scal, dz, dz.shape[0], dp.rank(self.group) * dz.shape[0])
         self._stamp(6)
 
     def _reduce_group(self, ready: str):

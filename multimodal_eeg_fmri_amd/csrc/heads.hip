@@ -332,6 +332,17 @@ __global__ __launch_bounds__(1024) void proj_heads_bwd_kernel(HeadsArgs a) {
 //                     ws, writes dz[own row] with plain stores; workgroup 0 also sums the own rows'
 //                     scalars in a fixed order into scal[4] = {loss, top1 e->f, top1 f->e, d/d logit_scale}.
 // Every sum runs in a fixed order (lane-strided partials, xor-shuffle trees, fixed wave order).
+//
+// GROUPED: the same InfoNCE with subject-grouped positives (MIL-NCE, "log of the positive mass").  gid[Bg] int32: pairs
+// with equal ids are positives of each other; P(r) = {j : gid_j = gid_r} always holds r.
+//   l_row(r) = LSE_j(s C[r][j]) - LSE_{j in P(r)}(s C[r][j]),  l_col(r) the same over column r,  loss_r = 0.5 (l_row + l_col)
+//   dL/dC[r][j] = 0.5/B * s * (P_row + P_col - [gid_r = gid_j] (Q_row + Q_col))[r][j]
+// Q = the softmax restricted to the positive set: Q_row[r][j] = exp(s C[r][j] - LSE_P(row r)), Q_col[r][j] =
+// exp(s C[r][j] - LSE_P(column j)).  Same two launches and rules as above; ws[8][Bg] = the six rows of the ungrouped
+// layout (row / column LSE, loss, top-1 flags, d loss / d logit_scale) + the positive-set LSE of every row and column.
+// With all-distinct ids every positive-set LSE is s C[r][r] + log 1 and the result is the ungrouped one (in exact
+// arithmetic: the ungrouped instantiation keeps its own formulas).  gid is the LAST kernel argument: the ungrouped
+// instantiation never reads it (null there), and its other arguments keep their offsets.
 // ---------------------------------------------------------------------------
 struct ClipShared {
     float *qe, *qf, *cr, *cc, *red;
@@ -373,7 +384,7 @@ __device__ __forceinline__ void clip_cosines(const float* __restrict__ z_all, in
     mxc = fmaxf(fmaxf(sh.red[4], sh.red[5]), fmaxf(sh.red[6], sh.red[7]));
     __syncthreads();
 }
-// fixed-order workgroup sum of two values (4 waves)
+// fixed-order workgroup sum / maximum of two values (4 waves)
 __device__ __forceinline__ void clip_sum2(float& a, float& c, float* red) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     a = wave_sum(a); c = wave_sum(c);
@@ -383,41 +394,85 @@ __device__ __forceinline__ void clip_sum2(float& a, float& c, float* red) {
     c = (red[4] + red[5]) + (red[6] + red[7]);
     __syncthreads();
 }
+__device__ __forceinline__ void clip_max2(float& a, float& c, float* red) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    a = wave_max(a); c = wave_max(c);
+    if (lane == 0) { red[wave] = a; red[4 + wave] = c; }
+    __syncthreads();
+    a = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+    c = fmaxf(fmaxf(red[4], red[5]), fmaxf(red[6], red[7]));
+    __syncthreads();
+}
 
+template <bool GROUPED>
 __global__ __launch_bounds__(256) void clip_lse_kernel(const float* __restrict__ z_all, const float* __restrict__ logit_scale,
-                                                       float* __restrict__ ws, int Bg, int N) {
+                                                       float* __restrict__ ws, int Bg, int N, const int* __restrict__ gid) {
     extern __shared__ float sm[];
     const ClipShared sh = clip_shared(sm, N, Bg);
     const int r = blockIdx.x, tid = threadIdx.x;
     const float s = __expf(logit_scale[0]);
+    int gr = 0;
+    if constexpr (GROUPED) gr = gid[r];
     float mxr, mxc;
     clip_cosines(z_all, r, Bg, N, sh, mxr, mxc);
-    float se = 0.f, sf = 0.f, ee = 0.f, ef = 0.f;           // sum exp, sum exp * cos
+    float pmr = -INFINITY, pmc = -INFINITY;                  // maxima over the positive set (the top-1 test and the stable LSE)
+    if constexpr (GROUPED) {
+        for (int j = tid; j < Bg; j += 256)
+            if (gid[j] == gr) { pmr = fmaxf(pmr, sh.cr[j]); pmc = fmaxf(pmc, sh.cc[j]); }
+        clip_max2(pmr, pmc, sh.red);
+    }
+    float se = 0.f, sf = 0.f, ee = 0.f, ef = 0.f;           // all columns: sum exp, sum exp * cos
+    float qe = 0.f, qf = 0.f, qee = 0.f, qef = 0.f;         // the positive set
     for (int j = tid; j < Bg; j += 256) {
         const float a = sh.cr[j], c = sh.cc[j];
         const float pa = __expf(s * (a - mxr)), pc = __expf(s * (c - mxc));
         se += pa; sf += pc; ee += pa * a; ef += pc * c;
+        if constexpr (GROUPED) {
+            if (gid[j] == gr) {
+                const float qa = __expf(s * (a - pmr)), qc = __expf(s * (c - pmc));
+                qe += qa; qf += qc; qee += qa * a; qef += qc * c;
+            }
+        }
     }
     clip_sum2(se, sf, sh.red);
     clip_sum2(ee, ef, sh.red);
+    if constexpr (GROUPED) {
+        clip_sum2(qe, qf, sh.red);
+        clip_sum2(qee, qef, sh.red);
+    }
     if (tid == 0) {
-        const float diag = sh.cr[r];
-        const float lse_r = s * mxr + __logf(se), lse_c = s * mxc + __logf(sf);
-        ws[r] = lse_r;
-        ws[Bg + r] = lse_c;
-        ws[2 * Bg + r] = 0.5f * ((lse_r - s * diag) + (lse_c - s * sh.cc[r]));
-        // top-1: a tie with the row maximum counts FOR the pair (diag >= max).  mm_retrieval's rank counts a tie
-        // AGAINST the query (csrc/retrieval.hip), so a collapsed encoder ranks Ng there but scores top-1 = 1 here.
-        ws[3 * Bg + r] = diag >= mxr ? 1.f : 0.f;
-        ws[4 * Bg + r] = sh.cc[r] >= mxc ? 1.f : 0.f;
-        // d loss_r / d logit_scale = s * 0.5 * (E_row[cos] - cos_rr + E_col[cos] - cos_rr)
-        ws[5 * Bg + r] = s * 0.5f * ((ee / se - diag) + (ef / sf - sh.cc[r]));
+        if constexpr (GROUPED) {
+            const float lse_r = s * mxr + __logf(se), lse_c = s * mxc + __logf(sf);
+            const float lsp_r = s * pmr + __logf(qe), lsp_c = s * pmc + __logf(qf);
+            ws[r] = lse_r;
+            ws[Bg + r] = lse_c;
+            ws[2 * Bg + r] = 0.5f * ((lse_r - lsp_r) + (lse_c - lsp_c));
+            ws[3 * Bg + r] = pmr >= mxr ? 1.f : 0.f;         // the best positive reaches the row maximum (a tie counts FOR it)
+            ws[4 * Bg + r] = pmc >= mxc ? 1.f : 0.f;
+            ws[5 * Bg + r] = s * 0.5f * ((ee / se - qee / qe) + (ef / sf - qef / qf));
+            ws[6 * Bg + r] = lsp_r;
+            ws[7 * Bg + r] = lsp_c;
+        } else {
+            const float diag = sh.cr[r];
+            const float lse_r = s * mxr + __logf(se), lse_c = s * mxc + __logf(sf);
+            ws[r] = lse_r;
+            ws[Bg + r] = lse_c;
+            ws[2 * Bg + r] = 0.5f * ((lse_r - s * diag) + (lse_c - s * sh.cc[r]));
+            // top-1: a tie with the row maximum counts FOR the pair (diag >= max).  mm_retrieval's rank counts a tie
+            // AGAINST the query (csrc/retrieval.hip), so a collapsed encoder ranks Ng there but scores top-1 = 1 here.
+            ws[3 * Bg + r] = diag >= mxr ? 1.f : 0.f;
+            ws[4 * Bg + r] = sh.cc[r] >= mxc ? 1.f : 0.f;
+            // d loss_r / d logit_scale = s * 0.5 * (E_row[cos] - cos_rr + E_col[cos] - cos_rr)
+            ws[5 * Bg + r] = s * 0.5f * ((ee / se - diag) + (ef / sf - sh.cc[r]));
+        }
     }
 }
 
+template <bool GROUPED>
 __global__ __launch_bounds__(256) void clip_rows_kernel(const float* __restrict__ z_all, const float* __restrict__ logit_scale,
                                                         const float* __restrict__ ws, float* __restrict__ scal,
-                                                        float* __restrict__ dz, int B, int Bg, int N, int row0) {
+                                                        float* __restrict__ dz, int B, int Bg, int N, int row0,
+                                                        const int* __restrict__ gid) {
     extern __shared__ float sm[];
     const ClipShared sh = clip_shared(sm, N, Bg);
     const int i = blockIdx.x, gi = row0 + i, tid = threadIdx.x, LD = 2 * N;
@@ -439,12 +494,22 @@ __global__ __launch_bounds__(256) void clip_rows_kernel(const float* __restrict_
     clip_cosines(z_all, gi, Bg, N, sh, mxr, mxc);
     // dL/dC[gi][j] -> cr[j],  dL/dC[j][gi] -> cc[j]
     const float lse_rg = ws[gi], lse_cg = ws[Bg + gi];
+    float lsp_rg = 0.f, lsp_cg = 0.f;
+    int gg = 0;
+    if constexpr (GROUPED) { lsp_rg = ws[6 * Bg + gi]; lsp_cg = ws[7 * Bg + gi]; gg = gid[gi]; }
     const float k = 0.5f * invB * s;
     for (int j = tid; j < Bg; j += 256) {
         const float a = s * sh.cr[j], c = s * sh.cc[j];
         float ga = __expf(a - lse_rg) + __expf(a - ws[Bg + j]);          // P_row[gi][j] + P_col[gi][j]
         float gc = __expf(c - ws[j]) + __expf(c - lse_cg);               // P_row[j][gi] + P_col[j][gi]
-        if (j == gi) { ga -= 2.f; gc -= 2.f; }
+        if constexpr (GROUPED) {
+            if (gid[j] == gg) {
+                ga -= __expf(a - lsp_rg) + __expf(a - ws[7 * Bg + j]);   // Q_row[gi][j] + Q_col[gi][j]
+                gc -= __expf(c - ws[6 * Bg + j]) + __expf(c - lsp_cg);   // Q_row[j][gi] + Q_col[j][gi]
+            }
+        } else {
+            if (j == gi) { ga -= 2.f; gc -= 2.f; }
+        }
         sh.cr[j] = k * ga; sh.cc[j] = k * gc;
     }
     __syncthreads();
@@ -463,126 +528,6 @@ __global__ __launch_bounds__(256) void clip_rows_kernel(const float* __restrict_
             for (int q = 0; q < 8; ++q) acc += g[j + q] * v[q];
         }
         for (; j < Bg; ++j) acc += g[j] * col[(size_t)j * LD];
-        orow[n] = acc;
-    }
-}
-
-// ---------------------------------------------------------------------------
-// the same InfoNCE with subject-grouped positives (MIL-NCE, "log of the positive mass").  gid[Bg] int32: pairs with
-// equal ids are positives of each other; P(r) = {j : gid_j = gid_r} always holds r.
-//   l_row(r) = LSE_j(s C[r][j]) - LSE_{j in P(r)}(s C[r][j]),  l_col(r) the same over column r,  loss_r = 0.5 (l_row + l_col)
-//   dL/dC[r][j] = 0.5/B * s * (P_row + P_col - [gid_r = gid_j] (Q_row + Q_col))[r][j]
-// Q = the softmax restricted to the positive set: Q_row[r][j] = exp(s C[r][j] - LSE_P(row r)), Q_col[r][j] =
-// exp(s C[r][j] - LSE_P(column j)).  Same two launches and rules as above; ws[8][Bg] = the six rows of the ungrouped
-// layout (row / column LSE, loss, top-1 flags, d loss / d logit_scale) + the positive-set LSE of every row and column.
-// With all-distinct ids every positive-set LSE is s C[r][r] + log 1 and the result is the ungrouped one.
-// ---------------------------------------------------------------------------
-__device__ __forceinline__ void clip_max2(float& a, float& c, float* red) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    a = wave_max(a); c = wave_max(c);
-    if (lane == 0) { red[wave] = a; red[4 + wave] = c; }
-    __syncthreads();
-    a = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-    c = fmaxf(fmaxf(red[4], red[5]), fmaxf(red[6], red[7]));
-    __syncthreads();
-}
-
-__global__ __launch_bounds__(256) void clip_lse_grouped_kernel(const float* __restrict__ z_all, const int* __restrict__ gid,
-                                                               const float* __restrict__ logit_scale, float* __restrict__ ws,
-                                                               int Bg, int N) {
-    extern __shared__ float sm[];
-    const ClipShared sh = clip_shared(sm, N, Bg);
-    const int r = blockIdx.x, tid = threadIdx.x;
-    const float s = __expf(logit_scale[0]);
-    const int gr = gid[r];
-    float mxr, mxc;
-    clip_cosines(z_all, r, Bg, N, sh, mxr, mxc);
-    float pmr = -INFINITY, pmc = -INFINITY;                  // maxima over the positive set (the top-1 test and the stable LSE)
-    for (int j = tid; j < Bg; j += 256)
-        if (gid[j] == gr) { pmr = fmaxf(pmr, sh.cr[j]); pmc = fmaxf(pmc, sh.cc[j]); }
-    clip_max2(pmr, pmc, sh.red);
-    float se = 0.f, sf = 0.f, ee = 0.f, ef = 0.f;           // all columns: sum exp, sum exp * cos
-    float qe = 0.f, qf = 0.f, qee = 0.f, qef = 0.f;         // the positive set
-    for (int j = tid; j < Bg; j += 256) {
-        const float a = sh.cr[j], c = sh.cc[j];
-        const float pa = __expf(s * (a - mxr)), pc = __expf(s * (c - mxc));
-        se += pa; sf += pc; ee += pa * a; ef += pc * c;
-        if (gid[j] == gr) {
-            const float qa = __expf(s * (a - pmr)), qc = __expf(s * (c - pmc));
-            qe += qa; qf += qc; qee += qa * a; qef += qc * c;
-        }
-    }
-    clip_sum2(se, sf, sh.red);
-    clip_sum2(ee, ef, sh.red);
-    clip_sum2(qe, qf, sh.red);
-    clip_sum2(qee, qef, sh.red);
-    if (tid == 0) {
-        const float lse_r = s * mxr + __logf(se), lse_c = s * mxc + __logf(sf);
-        const float lsp_r = s * pmr + __logf(qe), lsp_c = s * pmc + __logf(qf);
-        ws[r] = lse_r;
-        ws[Bg + r] = lse_c;
-        ws[2 * Bg + r] = 0.5f * ((lse_r - lsp_r) + (lse_c - lsp_c));
-        ws[3 * Bg + r] = pmr >= mxr ? 1.f : 0.f;             // the best positive reaches the row maximum (a tie counts FOR it)
-        ws[4 * Bg + r] = pmc >= mxc ? 1.f : 0.f;
-        ws[5 * Bg + r] = s * 0.5f * ((ee / se - qee / qe) + (ef / sf - qef / qf));
-        ws[6 * Bg + r] = lsp_r;
-        ws[7 * Bg + r] = lsp_c;
-    }
-}
-
-__global__ __launch_bounds__(256) void clip_rows_grouped_kernel(const float* __restrict__ z_all, const int* __restrict__ gid,
-                                                                const float* __restrict__ logit_scale,
-                                                                const float* __restrict__ ws, float* __restrict__ scal,
-                                                                float* __restrict__ dz, int B, int Bg, int N, int row0) {
-    extern __shared__ float sm[];
-    const ClipShared sh = clip_shared(sm, N, Bg);
-    const int i = blockIdx.x, gi = row0 + i, tid = threadIdx.x, LD = 2 * N;
-    const float s = __expf(logit_scale[0]);
-    const float invB = 1.f / (float)B;
-    if (i == 0 && tid < 64) {                               // the own rows' scalars, summed in a fixed order
-        float acc[4] = {0.f, 0.f, 0.f, 0.f};
-        for (int r0 = 0; r0 < B; r0 += 64) {
-            float v[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) v[q] = (r0 + tid < B) ? ws[(size_t)(2 + q) * Bg + row0 + r0 + tid] : 0.f;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) acc[q] += wave_sum(v[q]);
-        }
-        if (tid < 4) scal[tid] = (tid == 0 ? acc[0] : tid == 1 ? acc[1] : tid == 2 ? acc[2] : acc[3]) * invB;
-    }
-    if (!dz) return;
-    float mxr, mxc;
-    clip_cosines(z_all, gi, Bg, N, sh, mxr, mxc);
-    // dL/dC[gi][j] -> cr[j],  dL/dC[j][gi] -> cc[j]
-    const float lse_rg = ws[gi], lse_cg = ws[Bg + gi], lsp_rg = ws[6 * Bg + gi], lsp_cg = ws[7 * Bg + gi];
-    const int g = gid[gi];
-    const float k = 0.5f * invB * s;
-    for (int j = tid; j < Bg; j += 256) {
-        const float a = s * sh.cr[j], c = s * sh.cc[j];
-        float ga = __expf(a - lse_rg) + __expf(a - ws[Bg + j]);          // P_row[gi][j] + P_col[gi][j]
-        float gc = __expf(c - ws[j]) + __expf(c - lse_cg);               // P_row[j][gi] + P_col[j][gi]
-        if (gid[j] == g) {
-            ga -= __expf(a - lsp_rg) + __expf(a - ws[7 * Bg + j]);       // Q_row[gi][j] + Q_col[gi][j]
-            gc -= __expf(c - ws[6 * Bg + j]) + __expf(c - lsp_cg);       // Q_row[j][gi] + Q_col[j][gi]
-        }
-        sh.cr[j] = k * ga; sh.cc[j] = k * gc;
-    }
-    __syncthreads();
-    float* orow = dz + (size_t)i * LD;
-    for (int n = tid; n < 2 * N; n += 256) {                // first half: dze (columns of zf), second half: dzf
-        const bool first = n < N;
-        const float* gr = first ? sh.cr : sh.cc;
-        const float* col = z_all + (first ? N + n : n - N);
-        float acc = 0.f;
-        int j = 0;
-        for (; j + 8 <= Bg; j += 8) {                       // 8 loads in flight, summed in order
-            float v[8];
-#pragma unroll
-            for (int q = 0; q < 8; ++q) v[q] = col[(size_t)(j + q) * LD];
-#pragma unroll
-            for (int q = 0; q < 8; ++q) acc += gr[j + q] * v[q];
-        }
-        for (; j < Bg; ++j) acc += gr[j] * col[(size_t)j * LD];
         orow[n] = acc;
     }
 }
@@ -769,36 +714,9 @@ __global__ void learned_fusion_kernel(const float* __restrict__ f0, const float*
 
 // bridge cross-attention core (bridge_utils.py:75-82): one query (EEG token) over two
 // keys [EEG, fMRI], nhead heads of dh.  pe / pf = in_proj outputs [B][3E] (q|k|v) of the
-// two tokens.  ctx [B][E], attw [B][2] = head-averaged probabilities.
-__global__ void attn_1x2_kernel(const float* __restrict__ pe, const float* __restrict__ pf,
-                                float* __restrict__ ctx, float* __restrict__ attw, int B, int E, int nhead) {
-    const int b = blockIdx.x;
-    const int dh = E / nhead;
-    __shared__ float p0s[16], p1s[16];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const float* q = pe + (size_t)b * 3 * E;
-    const float* ke = q + E; const float* ve = q + 2 * E;
-    const float* kf = pf + (size_t)b * 3 * E + E; const float* vf = kf + E;
-    for (int h = wave; h < nhead; h += (blockDim.x >> 6)) {
-        float s0 = 0.f, s1 = 0.f;
-        for (int d = lane; d < dh; d += 64) { s0 += q[h * dh + d] * ke[h * dh + d]; s1 += q[h * dh + d] * kf[h * dh + d]; }
-        s0 = wave_sum(s0) * rsqrtf((float)dh); s1 = wave_sum(s1) * rsqrtf((float)dh);
-        const float m = fmaxf(s0, s1);
-        const float e0 = __expf(s0 - m), e1 = __expf(s1 - m);
-        const float p0 = e0 / (e0 + e1), p1 = e1 / (e0 + e1);
-        for (int d = lane; d < dh; d += 64) ctx[(size_t)b * E + h * dh + d] = p0 * ve[h * dh + d] + p1 * vf[h * dh + d];
-        if (lane == 0) { p0s[h] = p0; p1s[h] = p1; }
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float a0 = 0.f, a1 = 0.f;
-        for (int h = 0; h < nhead; ++h) { a0 += p0s[h]; a1 += p1s[h]; }
-        attw[2 * b] = a0 / nhead; attw[2 * b + 1] = a1 / nhead;
-    }
-}
-
-// backward of attn_1x2 (attention-probability dropout p applied to the two
-// probabilities before mixing, recomputed from (seed, b, h, key)):
+// two tokens.  ctx [B][E], attw [B][2] = head-averaged probabilities.  Attention-probability
+// dropout p (thresh != 0) is applied to the two probabilities before mixing, recomputed from
+// (seed, b, h, key).  backward:
 //   d proj_e [B][3E] = [dq | dk_e | dv_e],  d proj_f [B][3E] = [0 | dk_f | dv_f]
 __global__ void attn_1x2_fused_kernel(const float* __restrict__ pe, const float* __restrict__ pf,
                                       const float* __restrict__ dctx, float* __restrict__ ctx,
@@ -1799,45 +1717,50 @@ int mm_proj_heads_bwd(const float* dz, const float* z, const float* nrm, const f
     return mm_check_launch("proj_heads_bwd");
 }
 
+// floats-per-Bg rows of the loss workspace: the only place the count is written (layout: see clip_lse_kernel)
+static int clip_ws_rows(bool grouped) { return grouped ? 8 : 6; }
+
+// the checks and the two launches of both loss entry points; gid = nullptr: the ungrouped loss
+static int clip_loss_launch(const char* who, const float* z_all, const int* gid, const float* logit_scale, float* scal4,
+                            float* dz_local, float* ws, int B, int Bg, int N, int row0, hipStream_t st) {
+    MM_REQUIRE(B > 0 && Bg >= B && row0 >= 0 && row0 + B <= Bg && N > 0, "%s: B=%d Bg=%d row0=%d", who, B, Bg, row0);
+    MM_REQUIRE(N % 4 == 0, "%s: N=%d must be a multiple of 4 (16-byte row loads)", who, N);
+    const size_t lds = (size_t)(2 * N + 2 * Bg + 32) * sizeof(float);
+    MM_REQUIRE(lds <= 64 * 1024, "%s: N/Bg too large for LDS", who);
+    const auto lse = gid ? clip_lse_kernel<true> : clip_lse_kernel<false>;
+    const auto rows = gid ? clip_rows_kernel<true> : clip_rows_kernel<false>;
+    hipLaunchKernelGGL(lse, dim3(Bg), dim3(256), lds, st, z_all, logit_scale, ws, Bg, N, gid);
+    char what[64];
+    snprintf(what, sizeof what, "%s(lse)", who);
+    int rc = mm_check_launch(what);
+    if (rc) return rc;
+    hipLaunchKernelGGL(rows, dim3(B), dim3(256), lds, st, z_all, logit_scale, ws, scal4, dz_local, B, Bg, N, row0, gid);
+    snprintf(what, sizeof what, "%s(rows)", who);
+    return mm_check_launch(what);
+}
+
 int mm_clip_loss_ws_floats(int B, int Bg, int* floats_host, hipStream_t) {
     MM_REQUIRE(floats_host && B > 0 && Bg >= B, "clip_loss_ws_floats: bad args");
-    *floats_host = 6 * Bg;
+    *floats_host = clip_ws_rows(false) * Bg;
     return 0;
 }
 
 int mm_clip_loss_own_rows(const float* z_all, const float* logit_scale, float* scal4, float* dz_local, float* ws, int B,
                           int Bg, int N, int row0, hipStream_t st) {
     MM_REQUIRE(z_all && logit_scale && scal4 && ws, "clip_loss_own_rows: null");
-    MM_REQUIRE(B > 0 && Bg >= B && row0 >= 0 && row0 + B <= Bg && N > 0, "clip_loss_own_rows: B=%d Bg=%d row0=%d", B, Bg, row0);
-    MM_REQUIRE(N % 4 == 0, "clip_loss_own_rows: N=%d must be a multiple of 4 (16-byte row loads)", N);
-    const size_t lds = (size_t)(2 * N + 2 * Bg + 32) * sizeof(float);
-    MM_REQUIRE(lds <= 64 * 1024, "clip_loss_own_rows: N/Bg too large for LDS");
-    hipLaunchKernelGGL(clip_lse_kernel, dim3(Bg), dim3(256), lds, st, z_all, logit_scale, ws, Bg, N);
-    int rc = mm_check_launch("clip_loss_own_rows(lse)");
-    if (rc) return rc;
-    hipLaunchKernelGGL(clip_rows_kernel, dim3(B), dim3(256), lds, st, z_all, logit_scale, ws, scal4, dz_local, B, Bg, N, row0);
-    return mm_check_launch("clip_loss_own_rows(rows)");
+    return clip_loss_launch("clip_loss_own_rows", z_all, nullptr, logit_scale, scal4, dz_local, ws, B, Bg, N, row0, st);
 }
 
 int mm_clip_loss_grouped_ws_floats(int B, int Bg, int* floats_host, hipStream_t) {
     MM_REQUIRE(floats_host && B > 0 && Bg >= B, "clip_loss_grouped_ws_floats: bad args");
-    *floats_host = 8 * Bg;
+    *floats_host = clip_ws_rows(true) * Bg;
     return 0;
 }
 
 int mm_clip_loss_own_rows_grouped(const float* z_all, const int* gid_all, const float* logit_scale, float* scal4, float* dz_local,
                                   float* ws, int B, int Bg, int N, int row0, hipStream_t st) {
     MM_REQUIRE(z_all && gid_all && logit_scale && scal4 && ws, "clip_loss_own_rows_grouped: null");
-    MM_REQUIRE(B > 0 && Bg >= B && row0 >= 0 && row0 + B <= Bg && N > 0, "clip_loss_own_rows_grouped: B=%d Bg=%d row0=%d", B, Bg, row0);
-    MM_REQUIRE(N % 4 == 0, "clip_loss_own_rows_grouped: N=%d must be a multiple of 4 (16-byte row loads)", N);
-    const size_t lds = (size_t)(2 * N + 2 * Bg + 32) * sizeof(float);
-    MM_REQUIRE(lds <= 64 * 1024, "clip_loss_own_rows_grouped: N/Bg too large for LDS");
-    hipLaunchKernelGGL(clip_lse_grouped_kernel, dim3(Bg), dim3(256), lds, st, z_all, gid_all, logit_scale, ws, Bg, N);
-    int rc = mm_check_launch("clip_loss_own_rows_grouped(lse)");
-    if (rc) return rc;
-    hipLaunchKernelGGL(clip_rows_grouped_kernel, dim3(B), dim3(256), lds, st, z_all, gid_all, logit_scale, ws, scal4, dz_local,
-                       B, Bg, N, row0);
-    return mm_check_launch("clip_loss_own_rows_grouped(rows)");
+    return clip_loss_launch("clip_loss_own_rows_grouped", z_all, gid_all, logit_scale, scal4, dz_local, ws, B, Bg, N, row0, st);
 }
 
 int mm_sumsq(const float* g, float* state, int64_t n, hipStream_t st) {
@@ -1898,7 +1821,8 @@ int mm_learned_fusion(const float* f0, const float* f1, const float* f2, const f
 int mm_attn_1x2(const float* proj_e, const float* proj_f, float* ctx, float* attw, int B, int E, int nhead,
                 hipStream_t st) {
     MM_REQUIRE(proj_e && proj_f && ctx && attw && B > 0 && nhead > 0 && nhead <= 16 && E % nhead == 0, "attn_1x2: bad args");
-    hipLaunchKernelGGL(attn_1x2_kernel, dim3(B), dim3(256), 0, st, proj_e, proj_f, ctx, attw, B, E, nhead);
+    hipLaunchKernelGGL(attn_1x2_fused_kernel, dim3(B), dim3(256), 0, st, proj_e, proj_f, nullptr, ctx, attw, nullptr, nullptr,
+                       B, E, nhead, 0u, 0u, 1.f, nullptr, 0);          // no dropout, forward
     return mm_check_launch("attn_1x2");
 }
 

@@ -13,10 +13,11 @@ Conventions
 """
 from __future__ import annotations
 
+import functools
 import math
 import os
 import weakref
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, List, Optional
 
 import torch
 
@@ -340,32 +341,26 @@ def _splitk_plan(B: int, T: int, cin: int, cout: int, taps: int):
     return plan
 
 
-_CLIP_WS: Dict[tuple, int] = {}
-
-
-def clip_loss_ws_floats(B: int, Bg: int) -> int:
-    """floats of mm_clip_loss_own_rows' scratch for B own rows of a Bg-row gathered batch (mm_clip_loss_ws_floats:
-    the kernel file owns the layout), cached per shape"""
-    key = (B, Bg)
-    n = _CLIP_WS.get(key)
-    if n is None:
-        import ctypes
-        c = ctypes.c_int(0)
-        _hip.call("mm_clip_loss_ws_floats", B, Bg, ctypes.addressof(c))
-        n = _CLIP_WS[key] = c.value
-    return n
+def clip_loss_ws_floats(B: int, Bg: int, grouped: bool = False) -> int:
+    """floats of the scratch of mm_clip_loss_own_rows (``grouped``: mm_clip_loss_own_rows_grouped) for B own rows of a
+    Bg-row gathered batch; the kernel file owns the layout"""
+    return _hip.host_int("mm_clip_loss_grouped_ws_floats" if grouped else "mm_clip_loss_ws_floats", B, Bg)
 
 
 def clip_loss_grouped_ws_floats(B: int, Bg: int) -> int:
-    """floats of mm_clip_loss_own_rows_grouped's scratch (mm_clip_loss_grouped_ws_floats), cached per shape"""
-    key = ("grouped", B, Bg)
-    n = _CLIP_WS.get(key)
-    if n is None:
-        import ctypes
-        c = ctypes.c_int(0)
-        _hip.call("mm_clip_loss_grouped_ws_floats", B, Bg, ctypes.addressof(c))
-        n = _CLIP_WS[key] = c.value
-    return n
+    """clip_loss_ws_floats(B, Bg, grouped=True) under its earlier name (tests/test_clip_groups_gpu.py and callers of the previous version use it)"""
+    return clip_loss_ws_floats(B, Bg, grouped=True)
+
+
+def clip_loss_own_rows(z_all, gid_all, logit_scale1, scal, dz, B: int, row0: int):
+    """symmetric InfoNCE of rows [row0, row0 + B) of the gathered batch z_all (Bg, 2N) -> scal (4,), dz (B, 2N) or None;
+    gid_all (Bg,) int32 group ids: the grouped loss, None: pair i is its own positive.  Allocates the workspace."""
+    Bg, N2 = z_all.shape
+    ws = _empty((clip_loss_ws_floats(B, Bg, gid_all is not None),), _F32, z_all)
+    if gid_all is None:
+        _hip.call("mm_clip_loss_own_rows", z_all, logit_scale1, scal, dz, ws, B, Bg, N2 // 2, row0)
+    else:
+        _hip.call("mm_clip_loss_own_rows_grouped", z_all, gid_all, logit_scale1, scal, dz, ws, B, Bg, N2 // 2, row0)
 
 
 def group_ids(groups, n: int, device=None, who: str = "groups") -> Optional[torch.Tensor]:
@@ -1076,40 +1071,21 @@ def proj_embed_one(bridge, x: torch.Tensor, modality: str) -> torch.Tensor:
     return z[:, :N].contiguous()
 
 
-_RETR_WS: Dict[Tuple[int, int, int, int], int] = {}
-
-
 def retrieval_ws_floats(nq: int, ng: int, d: int, k: int) -> int:
-    """floats of mm_retrieval's scratch (mm_retrieval_ws_floats: the kernel file owns the layout), cached per shape"""
-    key = (nq, ng, d, k)
-    n = _RETR_WS.get(key)
-    if n is None:
-        import ctypes
-        c = ctypes.c_int(0)
-        _hip.call("mm_retrieval_ws_floats", nq, ng, d, k, ctypes.addressof(c))
-        n = _RETR_WS[key] = c.value
-    return n
+    """floats of mm_retrieval's scratch (mm_retrieval_ws_floats: the kernel file owns the layout)"""
+    return _hip.host_int("mm_retrieval_ws_floats", nq, ng, d, k)
 
 
+@functools.lru_cache(maxsize=None)
 def retrieval_kmax() -> int:
     import re
     m = re.search(r"^#define\s+MM_RETRIEVAL_KMAX\s+(\d+)", open(_hip.header_path()).read(), flags=re.M)
     return int(m.group(1))
 
 
-_RETR_GWS: Dict[Tuple[int, int, int], int] = {}
-
-
 def retrieval_grouped_ws_floats(nq: int, ng: int, d: int) -> int:
-    """floats of mm_retrieval_grouped's scratch (mm_retrieval_grouped_ws_floats), cached per shape"""
-    key = (nq, ng, d)
-    n = _RETR_GWS.get(key)
-    if n is None:
-        import ctypes
-        c = ctypes.c_int(0)
-        _hip.call("mm_retrieval_grouped_ws_floats", nq, ng, d, ctypes.addressof(c))
-        n = _RETR_GWS[key] = c.value
-    return n
+    """floats of mm_retrieval_grouped's scratch (mm_retrieval_grouped_ws_floats)"""
+    return _hip.host_int("mm_retrieval_grouped_ws_floats", nq, ng, d)
 
 
 def retrieval(q: torch.Tensor, g: torch.Tensor, positives: Optional[torch.Tensor] = None, k: int = 0,

@@ -371,7 +371,7 @@ def groups_case(step_iters=30):
         ls = torch.full((1,), math.log(1 / 0.07), device="cuda")
         scal, dz = torch.empty(4, device="cuda"), torch.empty(B, 2 * N, device="cuda")
         ws_u = torch.empty(ops.clip_loss_ws_floats(B, Bg), device="cuda")
-        ws_g = torch.empty(ops.clip_loss_grouped_ws_floats(B, Bg), device="cuda")
+        ws_g = torch.empty(ops.clip_loss_ws_floats(B, Bg, grouped=True), device="cuda")
         tu = graph_time(lambda: _hip.call("mm_clip_loss_own_rows", z, ls, scal, dz, ws_u, B, Bg, N, 0))
         tg = graph_time(lambda: _hip.call("mm_clip_loss_own_rows_grouped", z, gid, ls, scal, dz, ws_g, B, Bg, N, 0))
         print(f"clip loss B={B} Bg={Bg} N={N}: ungrouped {tu:7.2f} us  grouped {tg:7.2f} us  (+{tg - tu:5.2f} us)")
