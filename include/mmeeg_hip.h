@@ -649,6 +649,32 @@ int mm_adamw_clip(float* p, float* g, float* m, float* v, float* state, int64_t 
                   float beta2, float eps, float weight_decay, float max_norm, float grad_scale,
                   int zero_grad, uint32_t* seed_epoch, hipStream_t stream);
 
+/* ---- attribution (EEG_CODE/eeg_xai_analysis.py:88-236: GradientSaliency, IntegratedGradients) ---------------
+ * The reference walks its n_steps interpolation points one forward/backward at a time with a numpy round trip
+ * each; here `steps` of them are one batch.  All tensors fp32, contiguous; `rows` samples of `inner` values.
+ * `base` / `base_rows`: NULL / 0 = the zero baseline, 1 = one sample broadcast over the batch (the 'mean'
+ * baseline), rows = one baseline per sample.
+ * mm_xai_interp: out[s - s0][r][i] = base[r][i] + alpha_s * (x[r][i] - base[r][i]) for s in [s0, s0 + steps),
+ * alpha_s = np.linspace(0, 1, n_steps)[s] rounded to fp32 (n_steps == 1: alpha = 0); subtraction, product and sum
+ * are each rounded on their own, so the bits are torch's `base + alpha * (x - base)` (:196-198).
+ * mm_xai_accum: acc[i] = ((acc[i] + grad[0][i]) + grad[1][i]) + ... over `steps` slices of n values, in that order
+ * (the per-step gradient list of :217-225 without leaving the device; the order makes the sum independent of how
+ * the steps were cut into chunks).
+ * mm_xai_finish: attr[b][c][t] from x, base and acc (all (B, C, T)) -
+ *   mode 0  |(x - base) * (acc / n_steps)|   integrated gradients (:224-229; base NULL = the connectivity rule :233-234)
+ *   mode 1  |acc|                            vanilla gradient (:128-129)
+ *   mode 2  |acc| * |x|                      gradient x input (:145-146)
+ * and, when `chan` (B, C) is not NULL, chan[b][c] = mean_t attr[b][c][t], added in a fixed order (what
+ * ChannelImportanceExtractor.extract_channel_importance averages first, :422).
+ * mm_xai_pair_score: z (B, 2N) = [ze | zf] L2-normalised embeddings -> score[b] = ze_b . zf_b, the matching score
+ * of pair b, and (nullable) seed (B, 2N) = [zf | ze] = d score / d z, the gradient a backward starts from. */
+int mm_xai_interp(const float* x, const float* base, int base_rows, float* out, int n_steps, int s0, int steps,
+                  int64_t rows, int64_t inner, hipStream_t stream);
+int mm_xai_accum(const float* grad, float* acc, int steps, int64_t n, hipStream_t stream);
+int mm_xai_finish(const float* x, const float* base, int base_rows, const float* acc, float* attr, float* chan,
+                  int B, int C, int64_t T, int n_steps, int mode, hipStream_t stream);
+int mm_xai_pair_score(const float* z, float* score, float* seed, int B, int N, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

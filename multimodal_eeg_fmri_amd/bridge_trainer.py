@@ -761,6 +761,88 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
             out["topk"] = {"eeg_to_fmri": (ie, se), "fmri_to_eeg": (if_, sf)}
         return out
 
+    def explain(self, eeg: torch.Tensor, fmri: torch.Tensor, method: str = "integrated_gradients", n_steps: int = 50,
+                baseline: str = "zero", chunk_steps: Optional[int] = None) -> Dict[str, torch.Tensor]:
+        """Which channels, time points and voxels make EEG epoch i match volume i: attributes each pair's eval-mode
+        cosine similarity ``ze_i . zf_i`` - the matching score the contrastive step optimises (dropout off, frozen
+        BatchNorm, projection heads followed by the L2 normalisation) - to the raw EEG and the raw volume.
+        ``method``: "integrated_gradients" (``n_steps`` interpolation points from the ``baseline`` "zero" or "mean" = the
+        batch mean, batched by ``ops.integrated_gradients``; ``chunk_steps`` overrides its memory rule), "gradient"
+        (|d score / d input|) or "gradient_x_input".
+        -> {"eeg": (B, C, T), "eeg_channels": (B, C) = the mean over time, "fmri": (B, 1, D, H, W), "scores": (B,)}, fp32
+        on the trainer's device.  The training state is left as it was, bit for bit: parameters, Adam moments, optimizer
+        words, BatchNorm buffers, the gradient bucket, the dropout seed counter and a captured graph (no seed is drawn in
+        eval mode; the gradient bucket, into which the backward kernels add their parameter gradients, is restored).
+        Costs and side effects to know: the existing module-level backward functions are reused whole, so every chunk also
+        runs their weight-gradient kernels - work that attribution does not need - and those kernels add into the trainer's
+        gradient bucket: the bit-for-bit guarantee rests on `explain` cloning the bucket before and copying it back after
+        (one bucket-sized copy each way).  Every module's own train / eval flag is put back individually.  With
+        ``chunk_steps=None`` the engine measures one step's memory with ``torch.cuda.reset_peak_memory_stats``, which
+        resets the caller's peak-memory statistics of this device (`ops.integrated_gradients`)."""
+        if method not in ops.XAI_MODES:
+            raise ValueError(f"explain: method must be one of {sorted(ops.XAI_MODES)}, got {method!r}")
+        if baseline not in ("zero", "mean"):
+            raise ValueError(f"explain: baseline must be 'zero' or 'mean', got {baseline!r}")
+        ig = method == "integrated_gradients"
+        eeg, fmri, bases, accs, scores = self._pair_gradients(eeg, fmri, int(n_steps) if ig else 1,
+                                                              baseline if ig else None, chunk_steps)
+        steps = int(n_steps) if ig else 1
+        attr_e, chan = ops.xai_finish(eeg, bases[0], accs[0], steps, method, channels=True)
+        attr_f, _ = ops.xai_finish(fmri, bases[1], accs[1], steps, method)
+        return {"eeg": attr_e, "eeg_channels": chan, "fmri": attr_f, "scores": scores}
+
+    def _pair_gradients(self, eeg, fmri, steps: int, baseline: Optional[str], chunk_steps: Optional[int] = None):
+        """the signed sums behind `explain`: -> (eeg, fmri on the device, [baseline or None] x 2, [sum over the ``steps``
+        interpolation points of d (ze_i . zf_i) / d eeg, ... / d fmri], scores (B,) at the inputs).  ``baseline`` None:
+        ONE evaluation at the inputs themselves (the plain gradient)."""
+        if eeg.shape[0] != fmri.shape[0]:
+            raise ValueError(f"explain: {eeg.shape[0]} EEG epochs but {fmri.shape[0]} fMRI volumes")
+        if steps < 1:
+            raise ValueError("explain: n_steps must be >= 1")
+        ops.check_volume_shape(fmri.shape)
+        dev = self._scal.device
+        eeg = eeg.detach().to(dev).float().contiguous()
+        fmri = fmri.detach().to(dev).float().contiguous()
+        B = eeg.shape[0]
+        if baseline is None:
+            steps, path, bases = 1, [eeg, fmri], [None, None]          # one step from the input itself = the input
+        elif baseline == "mean":
+            path = bases = [eeg.mean(dim=0, keepdim=True), fmri.mean(dim=0, keepdim=True)]
+        else:
+            path = bases = [None, None]
+        scores = {}
+
+        def forward(e, f):
+            ze, zf = self.head.embed(self.eeg_encoder(e), self.fmri_encoder(f))
+            return ops._packed_pair(ze, zf)
+
+        def seed(z, s0, k):
+            score, g = ops.xai_pair_score(z)
+            if s0 + k == steps:                               # the last step is the input itself (alpha = 1)
+                scores["at_input"] = score[-B:].clone()
+            return g
+        modes = [(m, m.training) for m in self.modules()]      # restored module by module (a frozen sub-module stays frozen)
+        saved_seed = dict(ops._seed_state)
+        g0 = self.bucket.g.clone()                            # the backward kernels add parameter gradients into the bucket
+        self.eval()
+        ops.weights_changed()                                 # graph replays bypass the python-side version counter
+        try:
+            accs, _ = ops.integrated_gradients(forward, [eeg, fmri], path, steps, seed,
+                                               chunk_steps=1 if baseline is None else chunk_steps)
+            if baseline is not None and steps == 1:           # a single step is the BASELINE (alpha = 0), not the input:
+                with torch.enable_grad(), ops.attribution_mode():      # the scores at the inputs, through the same kernels
+                    z = forward(eeg.clone().requires_grad_(True), fmri.clone().requires_grad_(True))
+                scores["at_input"] = ops.xai_pair_score(z, want_seed=False)[0]
+                ops._release_tape(z)
+                del z
+        finally:
+            for m, mode in modes:
+                m.training = mode
+            self.bucket.g.copy_(g0)
+            ops._seed_state.update(saved_seed)
+            ops.weights_changed()
+        return eeg, fmri, bases, accs, scores["at_input"]
+
 
 class HostFeeder:
     """Feeds `BridgeTrainer.train_step_packed` from packed pinned host buffers (`pack_host_batch`), one H2D copy per

@@ -14,6 +14,8 @@ for src in "$here"/*.hip; do
     # attention (attention.hip, attention_hd.hip): MFMA results straight into VGPRs (the softmax is VALU work on every score: no v_accvgpr_read per
     # score).  Per file only: A/B in the training step, profiles/r03_attention_ab.txt (as a global flag it cost 25 %)
     [[ "$(basename "$src")" == attention*.hip ]] && extra=(-mllvm -amdgpu-mfma-vgpr-form=1)
+    # xai.hip: its contract is torch's bits of `base + alpha * (x - base)`, every fp32 operation rounded on its own: no FMA contraction
+    [[ "$(basename "$src")" == xai.hip ]] && extra=(-ffp-contract=off)
     # -fno-slp-vectorize: no compiler-formed v_pk_{fma,mul,add}_f32.  With them (op_sel-selected register halves, SGPR-pair
     # operands) the BatchNorm-reduce epilogue of igemm1d.hip gave run-to-run different sums in ~5 % of its workgroups
     # whenever it ran inside the two-stream training graph (never stand-alone); scalar fp32 code is bit-stable and the

@@ -1199,7 +1199,7 @@ def learned_fusion(m, feats: List[torch.Tensor], training: bool, autograd: bool 
     """LearnedFusionModule.forward -> (fused (B, H), weights (B, M)).  ``autograd``: differentiable
     composition even in eval mode (its gate dropout is then off)."""
     _need_gpu(*feats)
-    if training or autograd:
+    if training or autograd or attribution_active():
         from . import small_autograd as sa
         g = sa.linear(torch.cat(list(feats), dim=1), m.gate_net[0], "gelu", m.gate_net[2].p if training else 0.0)
         dyn = sa.linear(g, m.gate_net[3])
@@ -1311,7 +1311,8 @@ def bidirectional_cross_attention_forward(m, e, w):
     wa, _ = sa.mha_1xk(m.pw_to_erp_attn, [w, e], tr)       # softmax over the same two keys: order is immaterial
 
     def gated(feat, att, gate, norm):
-        g = sa.linear(torch.cat([_f32c(feat), att], dim=1), gate[0], "sigmoid")
+        # (attribution: the gate reads the feature with its tape, so d / d input holds every path of the reference)
+        g = sa.linear(torch.cat([feat.float() if attribution_active() else _f32c(feat), att], dim=1), gate[0], "sigmoid")
         upd = sa.ActFn.apply(sa.MulFn.apply(g, att), "none", p)
         return sa.LayerNormFn.apply(sa.AddFn.apply(feat, upd), norm.weight, norm.bias, norm.eps)
     return gated(e, ea, m.erp_gate, m.norm_erp), gated(w, wa, m.pw_gate, m.norm_pw)
@@ -1379,13 +1380,13 @@ def fmri_fusion_forward(m, activation, connectivity):
 
 def conn_encoder_forward(m, x):
     _need_gpu(x)
-    if m.training:
+    if m.training or attribution_active():                   # (attribution: eval mode on the tape - frozen BatchNorm, no dropout)
         from . import small_autograd as sa
-        p = m.drop_p
-        h = sa.linear_bn_act(x, m.proj1[0], m.proj1[1], "gelu", p)
-        h = sa.linear_bn_act(h, m.proj2[0], m.proj2[1], "gelu", p)
+        p, fz = (m.drop_p, False) if m.training else (0.0, True)
+        h = sa.linear_bn_act(x, m.proj1[0], m.proj1[1], "gelu", p, frozen=fz)
+        h = sa.linear_bn_act(h, m.proj2[0], m.proj2[1], "gelu", p, frozen=fz)
         gate = sa.linear(sa.linear(h, m.attention[0], "tanh"), m.attention[2], "sigmoid")
-        return sa.linear_bn_act(sa.MulFn.apply(h, gate), m.output[0], m.output[1], "gelu", p)
+        return sa.linear_bn_act(sa.MulFn.apply(h, gate), m.output[0], m.output[1], "gelu", p, frozen=fz)
     with torch.no_grad():
         h, _ = small_linear(_f32c(x), m.proj1[0], act="gelu", bn=m.proj1[1])
         h, _ = small_linear(h, m.proj2[0], act="gelu", bn=m.proj2[1])
@@ -1399,12 +1400,12 @@ def conn_encoder_forward(m, x):
 
 def hybrid_fusion_forward(m, erp, pw, conn):
     _need_gpu(erp, pw, conn)
-    if m.training:
+    if m.training or attribution_active():
         from . import small_autograd as sa
-        p = m.drop_p
+        p, fz = (m.drop_p, False) if m.training else (0.0, True)
         g = sa.linear(sa.linear(torch.cat([erp, pw], dim=1), m.erp_pw_gate[0], "gelu", p), m.erp_pw_gate[3])
         comb, gate = sa.Gate2MixFn.apply(g, erp, pw, conn, float(m.conn_boost))
-        return sa.linear_bn_act(comb, m.late_fusion[0], m.late_fusion[1], "gelu", p), gate
+        return sa.linear_bn_act(comb, m.late_fusion[0], m.late_fusion[1], "gelu", p, frozen=fz), gate
     with torch.no_grad():
         e, p, c = _f32c(erp), _f32c(pw), _f32c(conn)
         B, H = e.shape
@@ -1435,10 +1436,10 @@ def bn_classifier_forward(seq, fused, drop_p, training):
 def lite_encoder_forward(m, x):
     """LiteERPEncoder / LitePowerEncoder (crossmodal_v4_enhancements.py:817-877)."""
     _need_gpu(x)
-    if m.training:
+    if m.training or attribution_active():
         from . import small_autograd as sa
         pooled = sa.LiteConvFn.apply(m, x, *list(m.conv_layers.parameters()))
-        return sa.linear(pooled, m.output[1], "gelu", m.drop_p)
+        return sa.linear(pooled, m.output[1], "gelu", m.drop_p if m.training else 0.0)
     with torch.no_grad():
         cl = m.conv_layers
         xb = pack_nct(x.float())
@@ -1633,3 +1634,227 @@ def smoothed_cross_entropy(pred, target, smoothing):
     _need_gpu(pred, target)
     from . import small_autograd as sa
     return sa.SmoothedCEFn.apply(pred, target, float(smoothing))
+
+
+# ------------------------------------------------- attribution (EEG_CODE/eeg_xai_analysis.py:88-236)
+_ATTRIBUTION = {"depth": 0}
+
+
+class attribution_mode:
+    """context of the attribution engine: an EVAL-mode forward issued inside keeps a differentiable tape from the
+    logits down to the raw inputs in the glue layers that otherwise run their no-grad eval kernels (learned fusion,
+    gated cross attention, connectivity / Lite encoders, hybrid fusion): frozen BatchNorm, every dropout off.
+
+    Why a context and not the test this file uses elsewhere (``torch.is_grad_enabled() and x.requires_grad``, as in
+    `_mlp_bn_act` / `bn_classifier_forward`): at a glue layer that test cannot tell an attribution from an ordinary eval
+    forward.  The encoders put their output on the tape whenever a PARAMETER asks for a gradient (`_wants_grad`), so in
+    eval mode with autograd on - every evaluation not wrapped in no_grad - the features reaching the fusion layers
+    already require grad.  Switching on that would move those existing calls from the fused eval kernels to the
+    differentiable compositions, i.e. change what they compute today.  The context is entered in ONE place
+    (`integrated_gradients`) and read in five forwards; nothing changes outside it or in train mode.
+    Supported models = those whose eval forward reaches the inputs on a tape inside the context: the V4 / V4-Lite
+    classifiers, the bridge net, the encoders and `BridgeTrainer`.  A model that detaches on the way (the tabular fMRI nets,
+    the notebook classes) is refused by the engine - it raises when an input gets no gradient - not attributed as zero."""
+
+    def __enter__(self):
+        _ATTRIBUTION["depth"] += 1
+        return self
+
+    def __exit__(self, *exc):
+        _ATTRIBUTION["depth"] -= 1
+        return False
+
+
+def attribution_active() -> bool:
+    return _ATTRIBUTION["depth"] > 0
+
+
+def xai_alphas(n_steps: int):
+    """the interpolation constants of mm_xai_interp as the kernel forms them: ``np.linspace(0, 1, n_steps)`` - arange(n)
+    times the fp64 step 1 / (n - 1), the last point exactly 1, a single point 0 - rounded to fp32"""
+    import numpy as np
+    if n_steps < 1:
+        raise ValueError("xai_alphas: n_steps must be >= 1")
+    if n_steps == 1:
+        return np.zeros(1, dtype=np.float32)
+    step = 1.0 / float(n_steps - 1)
+    a = [float(s) * step for s in range(n_steps)]
+    a[-1] = 1.0
+    return np.asarray(a, dtype=np.float64).astype(np.float32)
+
+
+XAI_BUDGET_BYTES = 2 << 30
+
+
+def ig_chunk_steps(n_steps: int, step_bytes: int, budget_bytes: int = XAI_BUDGET_BYTES) -> int:
+    """THE MEMORY RULE of the batched integrated-gradients engine: how many interpolation steps S_c go through the
+    model as one batch of S_c * B rows.  ``step_bytes`` = the device memory ONE step needs at its peak (its B
+    interpolated rows of every input, their gradients, and everything the model's tape keeps for the backward);
+    eval mode has no batch statistics, so k steps need k times that.  S_c = floor(budget / step_bytes), at least 1
+    (a single step always runs) and at most n_steps.  It does not depend on n_steps otherwise: 50 steps of a
+    (32, 64, 1024) input are 419 MB in fp32 for that one interpolated tensor alone, before any activation.
+    `integrated_gradients` measures ``step_bytes`` on its first step (alpha = 0, run on its own)."""
+    if n_steps < 1 or step_bytes < 1 or budget_bytes < 1:
+        raise ValueError("ig_chunk_steps: n_steps, step_bytes and budget_bytes must be positive")
+    return max(1, min(int(n_steps), int(budget_bytes) // int(step_bytes)))
+
+
+def ig_chunks(n_steps: int, chunk_steps: int, first_alone: bool = False):
+    """[(s0, steps), ...] covering [0, n_steps) in ascending order; ``first_alone``: step 0 is its own chunk (the
+    engine measures one step's memory there) and the rule's S_c applies from step 1 on"""
+    out, s = [], 0
+    if first_alone and n_steps > 0:
+        out.append((0, 1))
+        s = 1
+    while s < n_steps:
+        k = min(chunk_steps, n_steps - s)
+        out.append((s, k))
+        s += k
+    return out
+
+
+def _xai_base(x: torch.Tensor, base):
+    """(baseline tensor or None, base_rows) for the kernels: None | (B, ...) | (1, ...) / (...) broadcast"""
+    if base is None:
+        return None, 0
+    b = base.detach().to(x.device).float().contiguous()
+    if b.numel() == x.numel():
+        return b, x.shape[0]
+    if b.numel() * x.shape[0] == x.numel():
+        return b, 1
+    raise ValueError(f"attribution baseline of shape {tuple(base.shape)} for an input of shape {tuple(x.shape)}")
+
+
+def xai_interpolate(x: torch.Tensor, base, n_steps: int, s0: int, steps: int) -> torch.Tensor:
+    """(steps * B, ...) fp32: rows [k * B, (k + 1) * B) = base + alpha_{s0 + k} * (x - base) (mm_xai_interp)"""
+    _need_gpu(x)
+    xc = x.detach().float().contiguous()
+    b, rows = _xai_base(xc, base)
+    B = xc.shape[0]
+    out = _empty((steps * B,) + tuple(xc.shape[1:]), _F32, xc)
+    _hip.call("mm_xai_interp", xc, b, rows, out, int(n_steps), int(s0), int(steps), B, xc.numel() // B)
+    return out
+
+
+def xai_accumulate(acc: torch.Tensor, grad: torch.Tensor, steps: int):
+    """acc (B, ...) += the ``steps`` slices of grad (steps * B, ...), in ascending step order (mm_xai_accum)"""
+    g = grad.detach().float().contiguous()
+    if g.numel() != steps * acc.numel():
+        raise ValueError(f"xai_accumulate: {steps} steps of {tuple(acc.shape)} against a gradient of {tuple(grad.shape)}")
+    _hip.call("mm_xai_accum", g, acc, int(steps), acc.numel())
+    return acc
+
+
+XAI_MODES = {"integrated_gradients": 0, "gradient": 1, "gradient_x_input": 2}
+
+
+def xai_finish(x: torch.Tensor, base, acc: torch.Tensor, n_steps: int, method: str, channels: bool = False):
+    """-> (attr like x, chan (B, C) or None): mm_xai_finish.  ``channels``: x is (B, C, T) and the per-channel means
+    over T are wanted as well."""
+    _need_gpu(x, acc)
+    xc = x.detach().float().contiguous()
+    b, rows = _xai_base(xc, base)
+    B = xc.shape[0]
+    if channels:
+        if xc.dim() != 3:
+            raise ValueError("xai_finish: per-channel means need a (B, C, T) input")
+        C, T = xc.shape[1], xc.shape[2]
+    else:
+        C, T = 1, xc.numel() // B
+    attr = torch.empty_like(xc)
+    chan = _empty((B, C), _F32, xc) if channels else None
+    _hip.call("mm_xai_finish", xc, b, rows, acc.contiguous(), attr, chan, B, C, T, int(n_steps), XAI_MODES[method])
+    return attr, chan
+
+
+def xai_pair_score(z: torch.Tensor, want_seed: bool = True):
+    """z (B, 2N) packed [ze | zf] -> (score (B,) = ze . zf per pair, seed (B, 2N) = [zf | ze] = d score / d z)"""
+    zc = z.detach().float().contiguous()
+    B, N2 = zc.shape
+    score = _empty((B,), _F32, zc)
+    seed = torch.empty_like(zc) if want_seed else None
+    _hip.call("mm_xai_pair_score", zc, score, seed, B, N2 // 2)
+    return score, seed
+
+
+def _release_tape(out: torch.Tensor):
+    """The module-level autograd functions keep what their backward needs as plain Python attributes of the graph node
+    (``ctx.saved = ...``), the node's own output among it: node -> attribute -> output -> node, a reference cycle that
+    only Python's garbage collector frees - and it does not count device bytes, so chunk after chunk of activations
+    would pile up behind the engine's memory rule (15.9 GiB instead of 1.9 GiB at the C2 shape).  Once the chunk's
+    backward has run the tape is dead: EVERY Python attribute of every custom node is dropped, whatever its name (built-in
+    nodes have no attribute dictionary and free their saved tensors themselves)."""
+    stack, seen = [out.grad_fn], set()
+    while stack:
+        fn = stack.pop()
+        if fn is None or id(fn) in seen:
+            continue
+        seen.add(id(fn))
+        stack.extend(n for n, _ in fn.next_functions)
+        attrs = getattr(fn, "__dict__", None)
+        if attrs:
+            attrs.clear()
+
+
+def integrated_gradients(forward, inputs, baselines, n_steps: int, seed_fn, constants=(), chunk_steps: Optional[int] = None,
+                         budget_bytes: int = XAI_BUDGET_BYTES):
+    """The batched integrated-gradients engine.  The reference (eeg_xai_analysis.py:196-221) runs ``n_steps``
+    forward/backward passes one at a time and carries every gradient to the host; here S_c steps are interpolated
+    into ONE batch of S_c * B rows (mm_xai_interp), go through ``forward`` and its backward once, and the input
+    gradients are folded into one device accumulator per input (mm_xai_accum).  Eval mode has no batch statistics,
+    so the rows of the big batch are independent.
+
+    ``forward(*interpolated, *repeated_constants)`` -> the model output (S_c * B, ...) on the autograd tape;
+    ``seed_fn(output detached, s0, steps)`` -> the gradient the backward starts from (same shape) - it sees the chunks
+    in ascending order, the first one starting at alpha = 0 (where the reference fixes its target class);
+    ``inputs`` / ``baselines``: tensors (B, ...) and None | (B, ...) | (1, ...); ``constants``: inputs that are NOT
+    interpolated (the reference's connectivity features): repeated for every step, their gradient accumulated alike.
+    ``chunk_steps``: S_c given by the caller; None: step 0 runs alone, its peak memory is measured, and
+    `ig_chunk_steps` (the memory rule) sizes the remaining chunks - that measurement calls
+    ``torch.cuda.reset_peak_memory_stats``, so the caller's peak-memory statistics of this device start over.  Parameter
+    ``.grad`` fields are not touched.  An input (or constant) the output does not depend on through the tape RAISES: a model
+    that detaches on the way would otherwise be attributed as all zeros.
+    -> (accumulators for inputs + constants: the SUM over the steps of d output . seed / d input, chunks [(s0, steps)])."""
+    inputs = [t.detach().float().contiguous() for t in inputs]
+    constants = [t.detach().float().contiguous() for t in constants]
+    _need_gpu(*inputs, *constants)
+    if n_steps < 1:
+        raise ValueError("integrated_gradients: n_steps must be >= 1")
+    accs = [torch.zeros_like(t) for t in inputs + constants]
+    dev = inputs[0].device
+    floor = torch.cuda.memory_allocated(dev)                 # what is held before the first chunk
+    probe = chunk_steps is None
+    plan = ig_chunks(n_steps, 1 if probe else int(chunk_steps), first_alone=probe)
+    done = []
+    i = 0
+    while i < len(plan):
+        s0, k = plan[i]
+        if probe and i == 0:
+            torch.cuda.synchronize(dev)
+            before = torch.cuda.memory_allocated(dev)
+            torch.cuda.reset_peak_memory_stats(dev)
+        xs = [xai_interpolate(x, b, n_steps, s0, k).requires_grad_(True) for x, b in zip(inputs, baselines)]
+        cs = [c.repeat((k,) + (1,) * (c.dim() - 1)).requires_grad_(True) for c in constants]
+        with torch.enable_grad(), attribution_mode():
+            out = forward(*xs, *cs)
+            seed = seed_fn(out.detach(), s0, k)
+            grads = torch.autograd.grad(out, xs + cs, seed, allow_unused=True)
+        missing = [i for i, g in enumerate(grads) if g is None]
+        if missing:
+            raise _hip.HipLibraryError(
+                f"attribution: input(s) {missing} of {len(grads)} get no gradient - the model's eval-mode forward detaches "
+                "before it reaches them (no differentiable HIP path for this model; see ops.attribution_mode)")
+        for acc, g in zip(accs, grads):
+            xai_accumulate(acc, g, k)
+        _release_tape(out)
+        del out, seed, grads, xs, cs
+        if torch.cuda.memory_allocated(dev) - floor > budget_bytes:     # other cycles left activations behind: collect them
+            import gc
+            gc.collect()
+        done.append((s0, k))
+        if probe and i == 0:
+            torch.cuda.synchronize(dev)
+            step_bytes = max(1, torch.cuda.max_memory_allocated(dev) - before)
+            plan = plan[:1] + [(s + 1, n) for s, n in ig_chunks(n_steps - 1, ig_chunk_steps(n_steps, step_bytes, budget_bytes))]
+        i += 1
+    return accs, done

@@ -140,17 +140,18 @@ class Gate2MixFn(torch.autograd.Function):
 
 
 class LiteConvFn(torch.autograd.Function):
-    """conv part of LiteERPEncoder / LitePowerEncoder (train mode):
-    Conv-BN-GELU-Drop-MaxPool2 -> Conv-BN-GELU-Drop -> mean over time : (B,C,T) -> (B,H) fp32"""
+    """conv part of LiteERPEncoder / LitePowerEncoder (train mode, or eval mode with a backward to follow - attribution:
+    frozen BatchNorm, no dropout): Conv-BN-GELU-Drop-MaxPool2 -> Conv-BN-GELU-Drop -> mean over time : (B,C,T) -> (B,H) fp32"""
 
     @staticmethod
     def forward(ctx, m, x, *params):
         cl = m.conv_layers
-        p = m.drop_p
+        tr = bool(m.training)
+        p = m.drop_p if tr else 0.0
         xb = ops.pack_nct(_f(x))
-        r1, s1 = ops.conv_bn_act(xb, cl[0], cl[1], pool=2, training=True, drop_p=p, drop_first=True, need_dgrad=False)
-        r2, s2 = ops.conv_bn_act(r1["bf16"], cl[5], cl[6], training=True, drop_p=p, want_f32=True,
-                                 want_bf16=False, need_dgrad=True)
+        r1, s1 = ops.conv_bn_act(xb, cl[0], cl[1], pool=2, training=tr, drop_p=p, drop_first=True, need_dgrad=False, save=True)
+        r2, s2 = ops.conv_bn_act(r1["bf16"], cl[5], cl[6], training=tr, drop_p=p, want_f32=True,
+                                 want_bf16=False, need_dgrad=True, save=True)
         h = r2["f32"]
         B, T2, N = h.shape
         pooled = _empty((B, N), _F32, h)

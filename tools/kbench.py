@@ -399,8 +399,112 @@ def groups_case(step_iters=30):
     print(f"C2 graph step B=32: ungrouped {tu:7.1f} us  grouped {tg:7.1f} us  ({100 * (tg / tu - 1):+.2f} %)")
 
 
+def xai_case(B=32, C=64, T=1024, vol=(32, 32, 32), n_steps=50, rounds=5):
+    """attribution (csrc/xai.hip, BridgeTrainer.explain) at the C2 shape.  (1) the three streaming kernels alone: GB/s of
+    the bytes each must move, beside the ~6.3 TB/s a float4 copy reaches on this part.  (2) integrated gradients of the
+    matching score, n_steps points, through the SAME trainer: the reference's protocol (eeg_xai_analysis.py:196-225: one
+    forward/backward per step, every gradient carried to the host as numpy, mean and |.| on the host) against the batched
+    engine; HIP events, the two forms interleaved round by round, medians."""
+    import numpy as np
+    from multimodal_eeg_fmri_amd.bridge_trainer import BridgeTrainer, synthetic_pairs
+    HBM = 6.3e3                                                  # GB/s, achievable (float4 copy)
+    n = B * C * T
+    base = torch.randn(1, C, T, device="cuda")
+
+    def ring(make, nbytes):
+        """enough copies that a pass over them all is well beyond the 256 MB Infinity Cache: every launch reads and writes
+        buffers the previous ~1 GiB of launches did not touch, so the figure is an HBM figure"""
+        return [make() for _ in range(max(2, int(math.ceil((1 << 30) / nbytes))))]
+
+    def rotating(call, *rings):
+        state = {"i": 0}
+
+        def fn():
+            i = state["i"]
+            state["i"] = i + 1
+            call(*[r[i % len(r)] for r in rings])
+        return fn
+    xs = ring(lambda: torch.randn(B, C, T, device="cuda"), n * 4)
+    for S in (1, 9, 25):
+        outs = ring(lambda: torch.empty(S * B, C, T, device="cuda"), S * n * 4)
+        us = timeit(rotating(lambda x, out: _hip.call("mm_xai_interp", x, base, 1, out, n_steps, 0, S, B, C * T), xs, outs))
+        gb = (S + 1) * n * 4 / 1e9
+        print(f"xai_interp  S={S:2d} ({B},{C},{T}) mean baseline, {len(xs)} / {len(outs)} rotating buffers: {us:8.1f} us  {gb / us * 1e6:7.0f} GB/s ({gb / us * 1e6 / HBM * 100:4.1f} % of {HBM:.0f})")
+        accs = ring(lambda: torch.zeros(B, C, T, device="cuda"), n * 4)
+        us = timeit(rotating(lambda out, acc: _hip.call("mm_xai_accum", out, acc, S, n), outs, accs))
+        gb = (S + 2) * n * 4 / 1e9
+        print(f"xai_accum   S={S:2d}: {us:8.1f} us  {gb / us * 1e6:7.0f} GB/s ({gb / us * 1e6 / HBM * 100:4.1f} %)")
+        del outs
+    accs = ring(lambda: torch.randn(B, C, T, device="cuda"), n * 4)
+    attrs = ring(lambda: torch.empty(B, C, T, device="cuda"), n * 4)
+    chan = torch.empty(B, C, device="cuda")
+    for label, ch in (("rows + channel means", chan), ("flat", None)):
+        us = timeit(rotating(lambda x, acc, attr: _hip.call("mm_xai_finish", x, base, 1, acc, attr, ch, B, C, T, n_steps, 0), xs, accs, attrs))
+        gb = 3 * n * 4 / 1e9
+        print(f"xai_finish  {label}: {us:8.1f} us  {gb / us * 1e6:7.0f} GB/s ({gb / us * 1e6 / HBM * 100:4.1f} %)")
+    del xs, accs, attrs
+    torch.manual_seed(0)
+    tr = BridgeTrainer(eeg_channels=C, dropout=0.3, mode="manual").train()
+    eeg, fmri = synthetic_pairs(B, C, T, vol)
+
+    def reference_protocol():
+        tr.eval()
+        ops.weights_changed()
+        g0 = tr.bucket.g.clone()
+        ge, gf = [], []
+        for alpha in np.linspace(0, 1, n_steps):
+            e = (float(alpha) * eeg).requires_grad_(True)
+            f = (float(alpha) * fmri).requires_grad_(True)
+            ze, zf = tr.head.embed(tr.eeg_encoder(e), tr.fmri_encoder(f))
+            z = ops._packed_pair(ze, zf)
+            a, b = torch.autograd.grad(z, [e, f], ops.xai_pair_score(z)[1])
+            ge.append(a.detach().cpu().numpy())
+            gf.append(b.detach().cpu().numpy())
+        res = np.abs(eeg.cpu().numpy() * np.mean(ge, axis=0)), np.abs(fmri.cpu().numpy() * np.mean(gf, axis=0))
+        tr.train()
+        tr.bucket.g.copy_(g0)
+        return res
+
+    def batched():
+        out = tr.explain(eeg, fmri, n_steps=n_steps)
+        return out["eeg"].cpu().numpy(), out["fmri"].cpu().numpy()
+    ra, rb = reference_protocol(), batched()                     # warm-up of both, and the two results side by side
+    for k, name in enumerate(("eeg", "fmri")):
+        print(f"batched vs per-step result, {name}: rel-L2 {np.linalg.norm(ra[k] - rb[k]) / np.linalg.norm(ra[k]):.2e}")
+    import gc
+
+    def peak_of(fn):
+        """peak allocation of one call above what is held before it (the per-step protocol's dead tapes collected first)"""
+        gc.collect()
+        torch.cuda.synchronize()
+        held = torch.cuda.memory_allocated()
+        torch.cuda.reset_peak_memory_stats()
+        fn()
+        torch.cuda.synchronize()
+        return (torch.cuda.max_memory_allocated() - held) / 2 ** 20
+    for cs in (1, 2, 4, 8):
+        print(f"batched, chunk_steps={cs}: peak {peak_of(lambda: tr.explain(eeg, fmri, n_steps=n_steps, chunk_steps=cs)):.0f} MiB above what was held")
+    print(f"batched, memory rule (budget {ops.XAI_BUDGET_BYTES / 2 ** 20:.0f} MiB per chunk): peak {peak_of(batched):.0f} MiB above what was held")
+    times = {"per-step + host round trips": [], "batched engine": []}
+    for _ in range(rounds):
+        for label, fn in (("per-step + host round trips", reference_protocol), ("batched engine", batched)):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            torch.cuda.synchronize()
+            times[label].append(a.elapsed_time(b))
+    for label, t in times.items():
+        print(f"integrated gradients B={B} {C}x{T} {vol} n_steps={n_steps}, {label}: median {statistics.median(t):8.1f} ms  (rounds {[round(v, 1) for v in t]})")
+    m = {k: statistics.median(v) for k, v in times.items()}
+    print(f"speed-up of the batched engine: {m['per-step + host round trips'] / m['batched engine']:.2f} x")
+
+
 def main():
     flt = sys.argv[1] if len(sys.argv) > 1 else ""
+    if flt == "xai":
+        xai_case()
+        return
     if flt == "groups":
         groups_case()
         return
