@@ -9,9 +9,9 @@ pids=()
 for src in "$here"/*.hip; do
   obj="$here/build/$(basename "${src%.hip}").o"
   objs+=("$obj")
-  if [[ ! -f "$obj" ]] || ! [[ "$src" -ot "$obj" ]] || ! [[ "$here/common.h" -ot "$obj" ]] || ! [[ "$here/attention_common.h" -ot "$obj" ]] || ! [[ "$0" -ot "$obj" ]]; then
+  if [[ ! -f "$obj" ]] || ! [[ "$src" -ot "$obj" ]] || ! [[ "$here/common.h" -ot "$obj" ]] || ! [[ "$0" -ot "$obj" ]]; then
     extra=()
-    # attention (attention.hip, attention_hd.hip): MFMA results straight into VGPRs (the softmax is VALU work on every score: no v_accvgpr_read per
+    # attention (attention.hip): MFMA results straight into VGPRs (the softmax is VALU work on every score: no v_accvgpr_read per
     # score).  Per file only: A/B in the training step, profiles/r03_attention_ab.txt (as a global flag it cost 25 %)
     [[ "$(basename "$src")" == attention*.hip ]] && extra=(-mllvm -amdgpu-mfma-vgpr-form=1)
     # xai.hip: its contract is torch's bits of `base + alpha * (x - base)`, every fp32 operation rounded on its own: no FMA contraction

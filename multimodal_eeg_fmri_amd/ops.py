@@ -446,7 +446,7 @@ def layernorm(x2d: torch.Tensor, ln, want_stat: bool):
 
 
 def attn_effective_dropout(p: float) -> float:
-    """the attention-probability dropout rate the kernels apply for a requested ``p``: csrc/attention{,_hd}.hip decide a 2 x 2 block
+    """the attention-probability dropout rate the kernels apply for a requested ``p``: csrc/attention.hip decides a 2 x 2 block
     of scores with one 32-bit hash and 8-bit fields, so the rate is quantised to round(256 p) / 256 (p = 0.1 -> 0.1016,
     the keep scale is that of the quantised rate: the mask stays unbiased); 0 < p < 1/512 rounds to NO dropout"""
     return round(256.0 * float(p)) / 256.0
@@ -473,8 +473,9 @@ ATTN_HEAD_DIMS = tuple(range(16, 65, 8))        # the head widths the self-atten
 
 def attn_entry(d_model: int, nhead: int, which: str) -> str:
     """the C-ABI entry point of the self-attention ``which`` pass ("fwd" / "bwd") for a ``d_model``-wide, ``nhead``-head
-    layer: head_dim 32 (the default model) runs csrc/attention.hip (mm_attn_fwd / mm_attn_bwd), every other supported
-    head_dim runs csrc/attention_hd.hip (mm_attn_fwd_hd / mm_attn_bwd_hd).  Anything else raises ValueError before a launch."""
+    layer: head_dim 32 (the default model) runs the kernels of csrc/attention.hip compiled for exactly that width
+    (mm_attn_fwd / mm_attn_bwd), every other supported head_dim runs the same kernels with a runtime head_dim
+    (mm_attn_fwd_hd / mm_attn_bwd_hd).  Anything else raises ValueError before a launch."""
     dh = d_model // nhead if nhead > 0 else 0
     if nhead <= 0 or d_model % nhead or dh not in ATTN_HEAD_DIMS:
         raise ValueError(f"self-attention: (d_model, nhead) = ({d_model}, {nhead}) gives a head dim the kernels do not run; "

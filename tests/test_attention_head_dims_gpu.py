@@ -1,4 +1,4 @@
-"""GPU: multi-head self-attention at every head dim the kernels run (csrc/attention_hd.hip through mm_attn_fwd_hd /
+"""GPU: multi-head self-attention at every head dim the kernels run (csrc/attention.hip through mm_attn_fwd_hd /
 mm_attn_bwd_hd: dh = 16, 24, ..., 64) against an fp64 reference on the kernels' bf16 operands:
 softmax(q k^T / sqrt(dh) + mask) * keep @ v, keep from the host replica of the kernels' dropout block hash
 (oracle/dropout_replica.py: attn_keep_scale), and its autograd gradients for the bf16 dout.
