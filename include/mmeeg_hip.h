@@ -675,6 +675,35 @@ int mm_xai_finish(const float* x, const float* base, int base_rows, const float*
                   int B, int C, int64_t T, int n_steps, int mode, hipStream_t stream);
 int mm_xai_pair_score(const float* z, float* score, float* seed, int B, int N, hipStream_t stream);
 
+/* ---- GATv2 graph attention over one static graph (EEG_CODE/enhanced_models_v4.py:292-413: the layer of
+ * GNNConnectivityEncoder; Brody et al., "How Attentive are Graph Attention Networks?") -------------------------
+ * Every sample of the batch shares the graph; a layer is one launch, a workgroup per (sample, head).
+ *   xl, xr   [B*N][ld] fp32, row stride ld >= H*C: the two linear images of the node features, head h in columns
+ *            [h*C, (h+1)*C).  (The halves of ONE (B*N, 2*H*C) linear with W_l | W_r stacked: xr = xl + H*C, ld = 2*H*C.)
+ *   att [H][C], bias [H*C] (nullable)
+ *   graph    CSR by TARGET: rowptr [N+1], col [E] = source of each edge, int32 on the device, every node with at
+ *            least its self-loop (E >= N); for the backward also the CSC view: colptr [N+1], row [E] = target,
+ *            perm [E] = position of that edge in CSR order, sources ascending, CSR order within a source.
+ *   e[i<-j] = sum_c att[h][c] * leaky_relu(xl[j][h][c] + xr[i][h][c], slope);  alpha = softmax over the edges of i;
+ *   out[b][i][h*C + c] = act(sum_j alpha * keep / (1 - drop_p) * xl[j][h][c] + bias[h*C + c])      [B][N][H*C]
+ *   keep: the counter-hash mask at element (b*H + h)*E + e, e the edge's CSR position (no renormalisation).
+ *   alpha [B][H][E] (required): the softmax before dropout, what the backward reads; pre [B][N][H*C] (nullable): the
+ *   value before `act` (the backward of an activation epilogue needs it).
+ * mm_gatv2_bwd: dxl, dxr [B*N][ld] (written), datt [H][C] and dbias [H*C] (nullable, ACCUMULATED into) from dout
+ *   [B][N][H*C]; same mask as the forward.  Workspaces (content opaque): ds_ws [B][H][E], part_ws [B][2][H*C], and
+ *   dz_ws [B][N][H*C] when act != 0 (pre is then required too).  Sums run in a fixed order (targets of a source in
+ *   CSR order, nodes, then batch): no atomics, two runs give the same bits.
+ * Supported: 1 <= N <= 128, C in {16, 32, 64}, H*C <= 256, B*H*E < 2^32; anything else (or a null pointer) is
+ * refused with MM_ERR_ARG before a launch. */
+int mm_gatv2_fwd(const float* xl, const float* xr, int ld, const float* att, const float* bias, const int* rowptr,
+                 const int* col, float* out, float* pre, float* alpha, int B, int N, int H, int C, int E,
+                 float slope, int act, float drop_p, uint32_t seed, const uint32_t* seed_epoch, hipStream_t stream);
+int mm_gatv2_bwd(const float* dout, const float* pre, const float* xl, const float* xr, int ld, const float* att,
+                 const float* alpha, const int* rowptr, const int* col, const int* colptr, const int* row,
+                 const int* perm, float* dxl, float* dxr, float* datt, float* dbias, float* ds_ws, float* dz_ws,
+                 float* part_ws, int B, int N, int H, int C, int E, float slope, int act, float drop_p,
+                 uint32_t seed, const uint32_t* seed_epoch, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

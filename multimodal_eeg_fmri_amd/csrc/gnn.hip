@@ -1,0 +1,303 @@
+// GATv2 graph attention (Brody et al. 2022) over ONE static graph shared by every sample of the batch: the layer
+// of GNNConnectivityEncoder (EEG_CODE/enhanced_models_v4.py:292-413).  The reference walks the batch one sample per
+// call; here a layer is one launch with a workgroup per (sample, head).
+//
+//   e[i <- j]  = sum_c att[h][c] * leaky_relu(xl[j][h][c] + xr[i][h][c])
+//   alpha      = softmax over the incoming edges of i  (* dropout keep / (1 - p), not renormalised)
+//   out[i][h]  = act(sum_j alpha * xl[j][h] + bias[h])
+//
+// fp32 throughout; this is VALU / latency work (N <= 128 nodes, C <= 64 channels per head), no MFMA.  The graph
+// comes in as CSR by target (rowptr, col = source) and, for the backward, a CSC view of the same edges (colptr,
+// row = target, perm = CSR position), so that every sum - over the sources of a target, the targets of a source,
+// nodes and batch - is formed in a fixed order without atomics: two runs give the same bits.
+//
+// Workgroup = 4 waves; the (sample, head) slice of xl sits in LDS with rows padded to C + 1 words (score phase:
+// one lane per edge, every lane walks the channels of its own source row - the odd stride spreads the rows over the
+// banks).  A wave owns one target at a time:
+//   score phase      lane = edge           e, running max / sum through wave reductions
+//   aggregate phase  lane = (group, c)     64 / C groups split the edges of a 64-edge chunk, rows read contiguously
+// LDS: N (C + 1) + C + 4 x 64 x 4 words  <= 128 x 65 x 4 + 256 + 4096 B = 37.6 KB.
+#include "common.h"
+
+namespace {
+
+constexpr int GAT_WAVES = 4;
+
+struct GatArgs {
+    const float* xl; const float* xr; int ld;
+    const float* att; const float* bias;
+    const int* rowptr; const int* col;
+    const int* colptr; const int* row; const int* perm;
+    float* out; float* pre; float* alpha;                  // forward outputs (alpha: read by the backward)
+    const float* dout; float* dxl; float* dxr;             // backward
+    float* ds; float* dz; float* part;                     // backward workspaces
+    int B, N, H, C, E; float slope; int act;
+    uint32_t thresh, seed; float inv_keep; const uint32_t* epoch;
+};
+
+__device__ __forceinline__ void wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// sum over the 64 / C lane groups (lanes c, c + C, c + 2 C, ...): every lane ends with the total, fixed pairing
+template <int C> __device__ __forceinline__ float group_sum(float v) {
+#pragma unroll
+    for (int off = C; off < 64; off <<= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+
+template <int C> __device__ __forceinline__ void load_slice(const GatArgs& a, int b, int h, float* xs, float* atts) {
+    constexpr int LDC = C + 1;
+    for (int idx = threadIdx.x; idx < a.N * C; idx += blockDim.x) {
+        const int n = idx / C, c = idx % C;
+        xs[n * LDC + c] = a.xl[((size_t)b * a.N + n) * a.ld + h * C + c];
+    }
+    if (threadIdx.x < C) atts[threadIdx.x] = a.att[h * C + threadIdx.x];
+}
+
+template <int C>
+__global__ __launch_bounds__(64 * GAT_WAVES) void gatv2_fwd_kernel(GatArgs a) {
+    constexpr int LDC = C + 1, G = 64 / C;
+    extern __shared__ float smem[];
+    float* xs = smem;                                      // [N][C + 1]
+    float* atts = xs + a.N * LDC;                          // [C]
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    float* xri = atts + C + wave * 256;                    // per wave: xr row of the target [64]
+    float* wa = xri + 64;                                  //           alpha * keep of a chunk [64]
+    int* wj = reinterpret_cast<int*>(wa + 64);             //           source of a chunk [64]
+    const int bh = blockIdx.x, b = bh / a.H, h = bh % a.H;
+    const uint32_t seed = mm_eff_seed(a.seed, a.epoch);
+    load_slice<C>(a, b, h, xs, atts);
+    __syncthreads();
+    const int g = lane / C, c = lane % C, HC = a.H * C;
+    float* alpha = a.alpha + (size_t)bh * a.E;
+    for (int i = wave; i < a.N; i += GAT_WAVES) {
+        const int e0 = a.rowptr[i], e1 = a.rowptr[i + 1];
+        const size_t node = (size_t)b * a.N + i;
+        if (lane < C) xri[lane] = a.xr[node * a.ld + h * C + lane];
+        wave_sync();
+        float m = -INFINITY;
+        for (int e = e0 + lane; e < e1; e += 64) {
+            const float* xj = xs + a.col[e] * LDC;
+            float s = 0.f;
+#pragma unroll 8
+            for (int k = 0; k < C; ++k) {
+                const float z = xj[k] + xri[k];
+                s += atts[k] * (z > 0.f ? z : a.slope * z);
+            }
+            alpha[e] = s;
+            m = fmaxf(m, s);
+        }
+        m = wave_max(m);
+        float sum = 0.f;
+        for (int e = e0 + lane; e < e1; e += 64) sum += expf(alpha[e] - m);
+        sum = wave_sum(sum);
+        const float inv = 1.f / sum;
+        float acc = 0.f;
+        for (int base = e0; base < e1; base += 64) {
+            const int e = base + lane;
+            if (e < e1) {
+                const float p = expf(alpha[e] - m) * inv;
+                alpha[e] = p;
+                const float keep = a.thresh ? dropout_scale(seed, (uint32_t)((size_t)bh * a.E + e), a.thresh, a.inv_keep) : 1.f;
+                wa[lane] = p * keep;
+                wj[lane] = a.col[e];
+            }
+            wave_sync();
+            const int cnt = e1 - base < 64 ? e1 - base : 64;
+            for (int t = g; t < cnt; t += G) acc += wa[t] * xs[wj[t] * LDC + c];
+            wave_sync();
+        }
+        acc = group_sum<C>(acc);
+        if (lane < C) {
+            float v = acc + (a.bias ? a.bias[h * C + c] : 0.f);
+            const size_t o = node * HC + h * C + c;
+            if (a.pre) a.pre[o] = v;
+            a.out[o] = apply_act(v, a.act);
+        }
+    }
+}
+
+// backward, one launch: phase 1 walks the targets (d alpha -> d score, d xr, d att, d bias), phase 2 the sources
+// (d xl).  d score of every edge crosses from phase 1 to phase 2 through `ds` (global, the workgroup's own slice).
+template <int C>
+__global__ __launch_bounds__(64 * GAT_WAVES) void gatv2_bwd_kernel(GatArgs a) {
+    constexpr int LDC = C + 1, G = 64 / C;
+    extern __shared__ float smem[];
+    float* xs = smem;
+    float* atts = xs + a.N * LDC;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    float* red = atts + C;                                 // [GAT_WAVES][2][C] block combine of d att / d bias (<= 512 words)
+    float* xri = red + 512 + wave * 256;
+    float* dpi = xri + 64;                                 // d pre-activation row of the target [64]
+    float* wa = dpi + 64;
+    int* wj = reinterpret_cast<int*>(wa + 64);
+    const int bh = blockIdx.x, b = bh / a.H, h = bh % a.H;
+    const uint32_t seed = mm_eff_seed(a.seed, a.epoch);
+    load_slice<C>(a, b, h, xs, atts);
+    __syncthreads();
+    const int g = lane / C, c = lane % C, HC = a.H * C;
+    const float* alpha = a.alpha + (size_t)bh * a.E;
+    float* ds = a.ds + (size_t)bh * a.E;
+    const float* dzsrc = a.act != MM_ACT_NONE ? a.dz : a.dout;
+    float datt = 0.f, dbias = 0.f;
+    for (int i = wave; i < a.N; i += GAT_WAVES) {
+        const int e0 = a.rowptr[i], e1 = a.rowptr[i + 1];
+        const size_t node = (size_t)b * a.N + i;
+        if (lane < C) {
+            xri[lane] = a.xr[node * a.ld + h * C + lane];
+            const size_t o = node * HC + h * C + lane;
+            float d = a.dout[o];
+            if (a.act != MM_ACT_NONE) {
+                d *= act_grad(a.pre[o], a.act);
+                a.dz[o] = d;
+            }
+            dpi[lane] = d;
+            dbias += d;
+        }
+        wave_sync();
+        // d (alpha * keep) of every edge, and S = sum alpha * d alpha
+        float S = 0.f;
+        for (int e = e0 + lane; e < e1; e += 64) {
+            const float* xj = xs + a.col[e] * LDC;
+            float s = 0.f;
+#pragma unroll 8
+            for (int k = 0; k < C; ++k) s += dpi[k] * xj[k];
+            if (a.thresh) s *= dropout_scale(seed, (uint32_t)((size_t)bh * a.E + e), a.thresh, a.inv_keep);
+            ds[e] = s;
+            S += alpha[e] * s;
+        }
+        S = wave_sum(S);
+        float dxr = 0.f;
+        for (int base = e0; base < e1; base += 64) {
+            const int e = base + lane;
+            if (e < e1) {
+                const float d = alpha[e] * (ds[e] - S);
+                ds[e] = d;
+                wa[lane] = d;
+                wj[lane] = a.col[e];
+            }
+            wave_sync();
+            const int cnt = e1 - base < 64 ? e1 - base : 64;
+            const float xr_c = xri[c];
+            for (int t = g; t < cnt; t += G) {
+                const float z = xs[wj[t] * LDC + c] + xr_c;
+                dxr += wa[t] * (z > 0.f ? 1.f : a.slope);
+                datt += wa[t] * (z > 0.f ? z : a.slope * z);
+            }
+            wave_sync();
+        }
+        dxr = group_sum<C>(dxr);
+        if (lane < C) a.dxr[node * a.ld + h * C + c] = dxr * atts[c];
+    }
+    datt = group_sum<C>(datt);
+    if (lane < C) {
+        red[(wave * 2 + 0) * C + c] = datt;
+        red[(wave * 2 + 1) * C + c] = dbias;
+    }
+    __threadfence_block();
+    __syncthreads();
+    if (threadIdx.x < 2 * C) {
+        const int k = threadIdx.x / C, cc = threadIdx.x % C;
+        float s = 0.f;
+#pragma unroll
+        for (int w = 0; w < GAT_WAVES; ++w) s += red[(w * 2 + k) * C + cc];
+        a.part[((size_t)b * 2 + k) * HC + h * C + cc] = s;
+    }
+    // phase 2: d xl[j] = sum over the edges j -> i of alpha keep d pre[i] + d score att leaky'(xl[j] + xr[i])
+    for (int j = wave; j < a.N; j += GAT_WAVES) {
+        const int t0 = a.colptr[j], t1 = a.colptr[j + 1];
+        const float xl_c = xs[j * LDC + c], att_c = atts[c];
+        float acc = 0.f;
+        for (int t = t0 + g; t < t1; t += G) {
+            const int i = a.row[t], e = a.perm[t];
+            const size_t node = (size_t)b * a.N + i;
+            float am = alpha[e];
+            if (a.thresh) am *= dropout_scale(seed, (uint32_t)((size_t)bh * a.E + e), a.thresh, a.inv_keep);
+            const float z = xl_c + a.xr[node * a.ld + h * C + c];
+            acc += am * dzsrc[node * HC + h * C + c] + ds[e] * att_c * (z > 0.f ? 1.f : a.slope);
+        }
+        acc = group_sum<C>(acc);
+        if (lane < C) a.dxl[((size_t)b * a.N + j) * a.ld + h * C + c] = acc;
+    }
+}
+
+// d att / d bias += sum over the batch of the per-(sample, head) partial sums, in batch order
+__global__ void gatv2_param_grads_kernel(const float* __restrict__ part, float* __restrict__ datt,
+                                         float* __restrict__ dbias, int B, int HC) {
+    const int k = threadIdx.x;
+    if (k >= HC) return;
+    float sa = 0.f, sb = 0.f;
+    for (int b = 0; b < B; ++b) {
+        sa += part[((size_t)b * 2 + 0) * HC + k];
+        sb += part[((size_t)b * 2 + 1) * HC + k];
+    }
+    if (datt) datt[k] += sa;
+    if (dbias) dbias[k] += sb;
+}
+
+int gat_check(const char* who, int B, int N, int H, int C, int E, int ld, int act, float drop_p) {
+    MM_REQUIRE(B > 0 && H > 0, "%s: B=%d H=%d", who, B, H);
+    MM_REQUIRE(N >= 1 && N <= 128, "%s: N=%d outside [1, 128]", who, N);
+    MM_REQUIRE(C == 16 || C == 32 || C == 64, "%s: C=%d is not 16, 32 or 64", who, C);
+    MM_REQUIRE(H * C <= 256, "%s: H*C=%d above 256", who, H * C);
+    MM_REQUIRE(E >= N, "%s: E=%d edges for N=%d nodes (every node carries a self-loop)", who, E, N);
+    MM_REQUIRE((unsigned long long)B * H * (unsigned long long)E < (1ull << 32), "%s: B*H*E does not fit the 32-bit mask index", who);
+    MM_REQUIRE(ld >= H * C, "%s: ld=%d below H*C=%d", who, ld, H * C);
+    MM_REQUIRE(act >= MM_ACT_NONE && act <= MM_ACT_SIGMOID, "%s: act=%d", who, act);
+    MM_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "%s: drop_p=%f", who, (double)drop_p);
+    return MM_OK;
+}
+
+inline uint32_t gat_thresh(float p) { return p > 0.f ? (uint32_t)((double)p * 4294967296.0) : 0u; }
+
+}  // namespace
+
+extern "C" {
+
+int mm_gatv2_fwd(const float* xl, const float* xr, int ld, const float* att, const float* bias, const int* rowptr,
+                 const int* col, float* out, float* pre, float* alpha, int B, int N, int H, int C, int E,
+                 float slope, int act, float drop_p, uint32_t seed, const uint32_t* seed_epoch, hipStream_t st) {
+    MM_REQUIRE(xl && xr && att && rowptr && col && out && alpha, "gatv2_fwd: null pointer");
+    if (int rc = gat_check("gatv2_fwd", B, N, H, C, E, ld, act, drop_p)) return rc;
+    GatArgs a{};
+    a.xl = xl; a.xr = xr; a.ld = ld; a.att = att; a.bias = bias; a.rowptr = rowptr; a.col = col;
+    a.out = out; a.pre = pre; a.alpha = alpha;
+    a.B = B; a.N = N; a.H = H; a.C = C; a.E = E; a.slope = slope; a.act = act;
+    a.thresh = gat_thresh(drop_p); a.seed = seed; a.inv_keep = drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f; a.epoch = seed_epoch;
+    const size_t lds = ((size_t)N * (C + 1) + C + GAT_WAVES * 256) * sizeof(float);
+    const dim3 grid(B * H), block(64 * GAT_WAVES);
+    if (C == 16) hipLaunchKernelGGL(gatv2_fwd_kernel<16>, grid, block, lds, st, a);
+    else if (C == 32) hipLaunchKernelGGL(gatv2_fwd_kernel<32>, grid, block, lds, st, a);
+    else hipLaunchKernelGGL(gatv2_fwd_kernel<64>, grid, block, lds, st, a);
+    return mm_check_launch("gatv2_fwd");
+}
+
+int mm_gatv2_bwd(const float* dout, const float* pre, const float* xl, const float* xr, int ld, const float* att,
+                 const float* alpha, const int* rowptr, const int* col, const int* colptr, const int* row,
+                 const int* perm, float* dxl, float* dxr, float* datt, float* dbias, float* ds_ws, float* dz_ws,
+                 float* part_ws, int B, int N, int H, int C, int E, float slope, int act, float drop_p,
+                 uint32_t seed, const uint32_t* seed_epoch, hipStream_t st) {
+    MM_REQUIRE(dout && xl && xr && att && alpha && rowptr && col && colptr && row && perm && dxl && dxr && ds_ws && part_ws,
+               "gatv2_bwd: null pointer");
+    if (int rc = gat_check("gatv2_bwd", B, N, H, C, E, ld, act, drop_p)) return rc;
+    MM_REQUIRE(act == MM_ACT_NONE || (pre && dz_ws), "gatv2_bwd: an activation epilogue needs pre and dz_ws");
+    GatArgs a{};
+    a.xl = xl; a.xr = xr; a.ld = ld; a.att = att; a.rowptr = rowptr; a.col = col; a.colptr = colptr; a.row = row; a.perm = perm;
+    a.pre = const_cast<float*>(pre); a.alpha = const_cast<float*>(alpha); a.dout = dout; a.dxl = dxl; a.dxr = dxr;
+    a.ds = ds_ws; a.dz = dz_ws; a.part = part_ws;
+    a.B = B; a.N = N; a.H = H; a.C = C; a.E = E; a.slope = slope; a.act = act;
+    a.thresh = gat_thresh(drop_p); a.seed = seed; a.inv_keep = drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f; a.epoch = seed_epoch;
+    const size_t lds = ((size_t)N * (C + 1) + C + 512 + GAT_WAVES * 256) * sizeof(float);
+    const dim3 grid(B * H), block(64 * GAT_WAVES);
+    if (C == 16) hipLaunchKernelGGL(gatv2_bwd_kernel<16>, grid, block, lds, st, a);
+    else if (C == 32) hipLaunchKernelGGL(gatv2_bwd_kernel<32>, grid, block, lds, st, a);
+    else hipLaunchKernelGGL(gatv2_bwd_kernel<64>, grid, block, lds, st, a);
+    if (datt || dbias)
+        hipLaunchKernelGGL(gatv2_param_grads_kernel, dim3(1), dim3(256), 0, st, part_ws, datt, dbias, B, H * C);
+    return mm_check_launch("gatv2_bwd");
+}
+
+}  // extern "C"

@@ -3,7 +3,8 @@
 Drop-in class surface for the reference's ``EEG_CODE/enhanced_models_v4.py``
 (PositionalEncoding :30-55, TemporalTransformerBlock :58-107,
 EnhancedERPEncoder :114-193, EnhancedPowerEncoder :196-285,
-LearnedFusionModule :420-488): same class names, constructor signatures,
+GNNConnectivityEncoder :292-413, LearnedFusionModule :420-488,
+EnhancedTriModalFusionNet :495-657, get_fusion_weights :829-841): same class names, constructor signatures,
 ``forward`` conventions and ``state_dict`` keys/shapes, so the reference's
 ``best_*_fold*.pt`` checkpoints load unchanged.
 
@@ -17,7 +18,7 @@ raises.
 from __future__ import annotations
 
 import math
-from typing import List, Optional
+from typing import Dict, List, Optional, Tuple
 
 import torch
 import torch.nn as nn
@@ -159,3 +160,127 @@ class LearnedFusionModule(nn.Module):
     def forward(self, modality_features: List[torch.Tensor], return_weights: bool = False):
         fused, w = ops.learned_fusion(self, list(modality_features), self.training)
         return (fused, w) if return_weights else fused
+
+
+def _glorot(t: torch.Tensor) -> None:
+    a = math.sqrt(6.0 / (t.size(-2) + t.size(-1)))
+    with torch.no_grad():
+        t.uniform_(-a, a)
+
+
+class GATv2Conv(nn.Module):
+    """GATv2 graph attention (Brody et al. 2022) with the parameter names and shapes of torch_geometric's layer of
+    the same name - ``att`` (1, H, C), ``bias`` (H*C), ``lin_l`` / ``lin_r`` Linear(in, H*C) - so that a state dict
+    trained with it loads.  ``x`` is (N, in) or (B, N, in); every sample shares ``edge_index`` (2, E) =
+    [source; target].  Runs on ``mm_gatv2_fwd`` / ``mm_gatv2_bwd``: at most 128 nodes, H*C <= 256, C in {16, 32, 64}."""
+
+    def __init__(self, in_channels: int, out_channels: int, heads: int = 1, concat: bool = True,
+                 negative_slope: float = 0.2, dropout: float = 0.0, add_self_loops: bool = True, bias: bool = True,
+                 edge_dim: Optional[int] = None, share_weights: bool = False):
+        super().__init__()
+        if not concat:
+            raise NotImplementedError("GATv2Conv: concat=False (head averaging) is not implemented")
+        if share_weights:
+            raise NotImplementedError("GATv2Conv: share_weights=True is not implemented")
+        if edge_dim is not None:
+            raise NotImplementedError("GATv2Conv: edge features are not implemented")
+        if not add_self_loops:
+            raise NotImplementedError("GATv2Conv: add_self_loops=False is not implemented")
+        if not isinstance(in_channels, int):
+            raise NotImplementedError("GATv2Conv: bipartite (source, target) input sizes are not implemented")
+        self.in_channels, self.out_channels, self.heads = in_channels, out_channels, heads
+        self.concat, self.negative_slope, self.dropout, self.add_self_loops = concat, negative_slope, dropout, add_self_loops
+        self.lin_l = nn.Linear(in_channels, heads * out_channels, bias=bias)
+        self.lin_r = nn.Linear(in_channels, heads * out_channels, bias=bias)
+        self.att = nn.Parameter(torch.empty(1, heads, out_channels))
+        if bias:
+            self.bias = nn.Parameter(torch.empty(heads * out_channels))
+        else:
+            self.register_parameter("bias", None)
+        self.reset_parameters()
+
+    def reset_parameters(self) -> None:
+        for lin in (self.lin_l, self.lin_r):
+            _glorot(lin.weight)
+            if lin.bias is not None:
+                nn.init.zeros_(lin.bias)
+        _glorot(self.att)
+        if self.bias is not None:
+            nn.init.zeros_(self.bias)
+
+    def forward(self, x: torch.Tensor, edge_index: torch.Tensor, edge_attr=None, return_attention_weights=None):
+        if edge_attr is not None or return_attention_weights is not None:
+            raise NotImplementedError("GATv2Conv: edge_attr / return_attention_weights are not implemented")
+        return ops.gatv2_conv_forward(self, x, edge_index)
+
+
+class GNNConnectivityEncoder(nn.Module):
+    """(B, nodes, nodes, conn_types) connectivity (or any shape that flattens to (B, nodes, -1)) -> (B, hidden_dim):
+    per-node Linear-BN-GELU -> ``num_gat_layers`` x [GATv2Conv + GELU] over the shared electrode graph -> mean over
+    nodes -> Linear-BN-GELU."""
+
+    def __init__(self, num_nodes: int, num_conn_types: int = 3, hidden_dim: int = 128, num_gat_layers: int = 2,
+                 num_heads: int = 4, dropout: float = 0.3):
+        super().__init__()
+        self.num_nodes = num_nodes
+        self.num_conn_types = num_conn_types
+        self.node_proj = nn.Sequential(nn.Linear(num_nodes * num_conn_types, hidden_dim), nn.BatchNorm1d(hidden_dim),
+                                       nn.GELU(), _drop(dropout))
+        self.gat_layers = nn.ModuleList([
+            GATv2Conv(hidden_dim, hidden_dim // num_heads, heads=num_heads, dropout=dropout, concat=True)
+            for _ in range(num_gat_layers)])
+        self.output_proj = nn.Sequential(nn.Linear(hidden_dim, hidden_dim), nn.BatchNorm1d(hidden_dim),
+                                         nn.GELU(), _drop(dropout))
+        self.drop_p = dropout
+
+    def create_graph_from_connectivity(self, conn_matrix: torch.Tensor,
+                                       threshold: float = 0.5) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(batch, nodes, nodes) strengths -> (edge_index (2, E), edge_attr (E, 1)): the pairs whose batch mean
+        exceeds ``threshold``.  Graph set-up, once per model: plain tensor indexing."""
+        avg = conn_matrix.detach().mean(dim=0)
+        edges = (avg > threshold).nonzero(as_tuple=False)
+        return edges.t().contiguous(), avg[edges[:, 0], edges[:, 1]].unsqueeze(1)
+
+    def forward(self, x: torch.Tensor, edge_index: torch.Tensor) -> torch.Tensor:
+        return ops.gnn_conn_encoder_forward(self, x, edge_index)
+
+
+class EnhancedTriModalFusionNet(nn.Module):
+    """ERP + Power transformer encoders, GNN (``use_gnn``) or MLP connectivity encoder, ERP-queries-all cross
+    attention, learned 3-way fusion, BN-MLP classifier (reference :495-657; same child names and state_dict).
+    ``edge_index`` is made from the first batch and kept as a plain attribute (it is not part of the state dict)."""
+
+    def __init__(self, erp_channels: int, pw_channels: int, num_conn_nodes: int, num_conn_types: int = 3,
+                 hidden_dim: int = 128, num_classes: int = 2, dropout: float = 0.3,
+                 num_transformer_layers: int = 2, num_heads: int = 4, use_gnn: bool = True):
+        super().__init__()
+        self.use_gnn = use_gnn
+        self.erp_encoder = EnhancedERPEncoder(erp_channels, hidden_dim, num_transformer_layers, num_heads, dropout)
+        self.pw_encoder = EnhancedPowerEncoder(pw_channels, hidden_dim, num_transformer_layers, num_heads, dropout)
+
+        def mlp_bn(i, o):
+            return [nn.Linear(i, o), nn.BatchNorm1d(o), nn.GELU(), _drop(dropout)]
+        if use_gnn:
+            self.conn_encoder = GNNConnectivityEncoder(num_conn_nodes, num_conn_types, hidden_dim, num_gat_layers=2,
+                                                       num_heads=num_heads, dropout=dropout)
+        else:
+            self.conn_encoder = nn.Sequential(*mlp_bn(num_conn_nodes * num_conn_nodes * num_conn_types, 256),
+                                              *mlp_bn(256, hidden_dim))
+        self.fusion = LearnedFusionModule(num_modalities=3, hidden_dim=hidden_dim, use_temperature=True)
+        self.cross_attn = nn.MultiheadAttention(hidden_dim, num_heads=num_heads, dropout=dropout, batch_first=True)
+        self.classifier = nn.Sequential(*mlp_bn(hidden_dim, hidden_dim), *mlp_bn(hidden_dim, hidden_dim // 2),
+                                        nn.Linear(hidden_dim // 2, num_classes))
+        self.edge_index = None
+        self.drop_p = dropout
+
+    def forward(self, erp: torch.Tensor, pw: torch.Tensor, conn: torch.Tensor, return_fusion_weights: bool = False):
+        logits, weights, _ = ops.trimodal_forward(self, erp, pw, conn)
+        return (logits, weights) if return_fusion_weights else logits
+
+
+def get_fusion_weights(model: EnhancedTriModalFusionNet) -> Dict[str, float]:
+    """the static fusion weights softmax(fusion_logits / temperature) and the temperature, as floats"""
+    with torch.no_grad():                                # three scalars for a report, as get_fusion_weights_from_model
+        temp = model.fusion.temperature
+        w = torch.softmax(model.fusion.fusion_logits / temp, dim=0).tolist()
+    return {"erp_weight": w[0], "pw_weight": w[1], "conn_weight": w[2], "temperature": temp.item()}

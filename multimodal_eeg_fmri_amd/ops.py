@@ -1399,6 +1399,153 @@ def conn_encoder_forward(m, x):
     return out
 
 
+# ------------------------------------------------- GATv2 over one static graph (csrc/gnn.hip)
+class GatGraph:
+    """the graph ``mm_gatv2_fwd`` / ``mm_gatv2_bwd`` read, int32 on the device of the ``edge_index`` it came from:
+    CSR by target (``rowptr`` (N + 1), ``col`` (E') = source) and the CSC view of the same edges (``colptr`` (N + 1),
+    ``row`` (E') = target, ``perm`` (E') = CSR position; CSR order within a source)."""
+
+    def __init__(self, num_nodes, rowptr, col, colptr, row, perm):
+        self.num_nodes, self.num_edges = int(num_nodes), int(col.numel())
+        self.rowptr, self.col, self.colptr, self.row, self.perm = rowptr, col, colptr, row, perm
+
+
+def _build_gat_graph(edge_index: torch.Tensor, num_nodes: int) -> GatGraph:
+    N = int(num_nodes)
+    if N < 1:
+        raise ValueError(f"gat_graph: num_nodes={num_nodes}")
+    if edge_index.dim() != 2 or edge_index.size(0) != 2:
+        raise ValueError(f"gat_graph: edge_index must be (2, E), got {tuple(edge_index.shape)}")
+    if edge_index.is_floating_point() or edge_index.dtype == torch.bool:
+        raise ValueError(f"gat_graph: edge_index must hold integers, got {edge_index.dtype}")
+    ei = edge_index.detach().to("cpu", torch.int64)
+    if ei.numel() and (int(ei.min()) < 0 or int(ei.max()) >= N):
+        raise ValueError(f"gat_graph: edge_index must lie in [0, {N}), got [{int(ei.min())}, {int(ei.max())}]")
+    # GATv2Conv(add_self_loops=True): listed self-loops go, one per node is appended; duplicates stay
+    keep = ei[0] != ei[1]
+    loops = torch.arange(N, dtype=torch.int64)
+    src = torch.cat([ei[0][keep], loops])
+    dst = torch.cat([ei[1][keep], loops])
+    order = torch.sort(dst, stable=True).indices                    # CSR by target, listed order within a target
+    col, tgt = src[order], dst[order]
+    perm = torch.sort(col, stable=True).indices                     # CSC: by source, CSR order within a source
+
+    def ptr(keys):
+        out = torch.zeros(N + 1, dtype=torch.int64)
+        out[1:] = torch.cumsum(torch.bincount(keys, minlength=N), 0)
+        return out
+    dev = edge_index.device
+    i32 = [t.to(torch.int32).contiguous().to(dev) for t in (ptr(tgt), col, ptr(col), tgt[perm], perm)]
+    return GatGraph(N, *i32)
+
+
+def gat_graph(edge_index: torch.Tensor, num_nodes: int) -> GatGraph:
+    """``GatGraph`` of ``edge_index`` (2, E) = [source; target] with GATv2Conv's self-loop rule, built once per
+    ``edge_index`` tensor (and again only after an in-place change of it).  ValueError for a malformed graph."""
+    key = (int(num_nodes), edge_index._version)
+    hit = getattr(edge_index, "_mm_gat_graph", None)
+    if hit is not None and hit[0] == key:
+        return hit[1]
+    g = _build_gat_graph(edge_index, num_nodes)
+    edge_index._mm_gat_graph = (key, g)
+    return g
+
+
+def _gat_cat(conv):
+    """W_l | W_r stacked, so that both linear images of the node features come from one launch"""
+    W = torch.cat([conv.lin_l.weight, conv.lin_r.weight], dim=0)
+    b = torch.cat([conv.lin_l.bias, conv.lin_r.bias], dim=0) if conv.lin_l.bias is not None else None
+    return W, b
+
+
+def gatv2_forward(conv, x: torch.Tensor, graph: GatGraph, act: str = "none") -> torch.Tensor:
+    """inference path of one GATv2Conv layer: x (B, N, in) fp32 -> act(out) (B, N, heads * out_channels)"""
+    _need_gpu(x, graph.col)
+    B, N, F = x.shape
+    if N != graph.num_nodes:
+        raise ValueError(f"gatv2_forward: x has {N} nodes, the graph {graph.num_nodes}")
+    H, C = conv.heads, conv.out_channels
+    with torch.no_grad():
+        W, b = _gat_cat(conv)
+        xlr, _ = small_linear(_f32c(x).view(B * N, F), None, weight=W, bias=b)
+        out = _empty((B, N, H * C), _F32, x)
+        alpha = _empty((B, H, graph.num_edges), _F32, x)
+        _hip.call("mm_gatv2_fwd", xlr, xlr.data_ptr() + 4 * H * C, 2 * H * C, _f32c(conv.att),
+                  None if conv.bias is None else _f32c(conv.bias), graph.rowptr, graph.col, out, None, alpha,
+                  B, N, H, C, graph.num_edges, float(conv.negative_slope), ACT[act], 0.0, 0, None)
+    return out
+
+
+def gatv2_conv_forward(conv, x, edge_index):
+    """GATv2Conv.forward: x (N, in) or (B, N, in) -> (N, H*C) / (B, N, H*C); the autograd path in train mode and
+    whenever a gradient can be asked for (the input or a parameter requires one), the inference path otherwise"""
+    _need_gpu(x, edge_index)
+    if x.dim() not in (2, 3):
+        raise ValueError(f"GATv2Conv: x must be (N, in) or (B, N, in), got {tuple(x.shape)}")
+    x3 = x.unsqueeze(0) if x.dim() == 2 else x
+    graph = gat_graph(edge_index, x3.size(1))
+    if conv.training or (torch.is_grad_enabled() and (x.requires_grad or any(q.requires_grad for q in conv.parameters()))):
+        from . import small_autograd as sa
+        out = sa.gatv2(conv, x3, graph, "none", conv.training)
+    else:
+        out = gatv2_forward(conv, x3, graph)
+    return out.squeeze(0) if x.dim() == 2 else out
+
+
+def gnn_conn_encoder_forward(m, x, edge_index):
+    """GNNConnectivityEncoder.forward (enhanced_models_v4.py:367-413): node_proj per node row -> GATv2 + GELU layers ->
+    mean over nodes -> output_proj.  The reference applies node_proj sample by sample, so in train mode its
+    BatchNorm1d takes statistics over the N nodes of ONE sample and updates the running statistics B times in
+    sequence: kept, as a loop over samples (the GAT layers run the whole batch per launch)."""
+    _need_gpu(x, edge_index)
+    B, N = x.size(0), m.num_nodes
+    x = x.reshape(B, N, -1)
+    graph = gat_graph(edge_index, N)
+    lin, bn = m.node_proj[0], m.node_proj[1]
+    if m.training or attribution_active() or (torch.is_grad_enabled() and x.requires_grad):
+        from . import small_autograd as sa
+        p, fz = (m.drop_p, False) if m.training else (0.0, True)   # eval on the tape: frozen BatchNorm, no dropout
+        if m.training:
+            h = torch.stack([sa.linear_bn_act(x[i], lin, bn, "gelu", p) for i in range(B)], dim=0)
+        else:
+            h = sa.linear_bn_act(x.reshape(B * N, -1), lin, bn, "gelu", 0.0, frozen=True).view(B, N, -1)
+        for conv in m.gat_layers:
+            h = sa.gatv2(conv, h, graph, "gelu", m.training)
+        return sa.linear_bn_act(sa.MeanRowsFn.apply(h), m.output_proj[0], m.output_proj[1], "gelu", p, frozen=fz)
+    with torch.no_grad():
+        h, _ = small_linear(_f32c(x).view(B * N, -1), lin, act="gelu", bn=bn)
+        h = h.view(B, N, -1)
+        for conv in m.gat_layers:
+            h = gatv2_forward(conv, h, graph, "gelu")
+        pooled = _empty((B, h.shape[2]), _F32, h)
+        _hip.call("mm_meanpool_fwd", h, pooled, None, B, N, h.shape[2])
+        out, _ = small_linear(pooled, m.output_proj[0], act="gelu", bn=m.output_proj[1])
+    return out
+
+
+def trimodal_forward(m, erp, pw, conn):
+    """EnhancedTriModalFusionNet.forward (enhanced_models_v4.py:590-657) -> (logits, fusion weights (B, 3), fused (B, H))"""
+    _need_gpu(erp, pw, conn)
+    from . import small_autograd as sa
+    tr, p = m.training, m.drop_p
+    e = m.erp_encoder(erp)
+    w = m.pw_encoder(pw)
+    if m.use_gnn:
+        if m.edge_index is None:                                 # the graph comes from the first batch's first sample (:614-624)
+            c0 = conn.detach()
+            cm = c0[0, :, :, 0] if c0.dim() == 4 else c0[0].reshape(c0.size(1), c0.size(1))
+            m.edge_index = m.conn_encoder.create_graph_from_connectivity(cm.unsqueeze(0))[0].to(conn.device)
+        c = m.conn_encoder(conn, m.edge_index)
+    else:
+        ce = m.conn_encoder
+        c = _mlp_bn_act(conn.reshape(conn.size(0), -1), ce[0], ce[1], "gelu", p, tr)
+        c = _mlp_bn_act(c, ce[4], ce[5], "gelu", p, tr)
+    tape = torch.is_grad_enabled() and any(t.requires_grad for t in (e, w, c))
+    enh, _ = sa.mha_1xk(m.cross_attn, [e, w, c], tr)
+    fused, weights = learned_fusion(m.fusion, [enh, w, c], tr, autograd=tape)
+    return _v4_classifier(m.classifier, fused, p, tr), weights, fused
+
+
 def hybrid_fusion_forward(m, erp, pw, conn):
     _need_gpu(erp, pw, conn)
     if m.training or attribution_active():

@@ -460,6 +460,77 @@ class FocalLossFn(torch.autograd.Function):
         return dl * (g * ctx.factor), None, None, None, None
 
 
+class GATv2Fn(torch.autograd.Function):
+    """one GATv2 layer over a static graph (``mm_gatv2_fwd`` / ``mm_gatv2_bwd``): xlr (B, N, 2 H C) = the node
+    features through W_l | W_r -> act(out) (B, N, H C).  Saved: xlr, the softmax alpha (B, H, E') and, under an
+    activation epilogue, the pre-activation; the dropout mask is recomputed from its seed."""
+
+    @staticmethod
+    def forward(ctx, xlr, att, bias, graph, H, C, slope, act, drop_p):
+        xlr = _f(xlr)
+        B, N, _ = xlr.shape
+        HC, E = H * C, graph.num_edges
+        seed = ops._next_seed() if drop_p > 0 else 0
+        out = _empty((B, N, HC), _F32, xlr)
+        pre = _empty((B, N, HC), _F32, xlr) if act != "none" else None
+        alpha = _empty((B, H, E), _F32, xlr)
+        _hip.call("mm_gatv2_fwd", xlr, xlr.data_ptr() + 4 * HC, 2 * HC, att, bias, graph.rowptr, graph.col, out, pre,
+                  alpha, B, N, H, C, E, float(slope), ACT[act], float(drop_p), seed, ops.EP())
+        ctx.save_for_backward(xlr, alpha, pre)
+        ctx.att, ctx.bias, ctx.graph = att, bias, graph
+        ctx.meta = (H, C, float(slope), act, float(drop_p), seed)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        xlr, alpha, pre = ctx.saved_tensors
+        H, C, slope, act, p, seed = ctx.meta
+        g, att, bias = ctx.graph, ctx.att, ctx.bias
+        B, N, _ = xlr.shape
+        HC, E = H * C, g.num_edges
+        dxlr = torch.empty_like(xlr)
+        ds = _empty((B, H, E), _F32, xlr)
+        dz = _empty((B, N, HC), _F32, xlr) if act != "none" else None
+        part = _empty((B, 2, HC), _F32, xlr)
+        bag = GradBag()
+        _hip.call("mm_gatv2_bwd", _f(dout), pre, xlr, xlr.data_ptr() + 4 * HC, 2 * HC, att, alpha, g.rowptr, g.col,
+                  g.colptr, g.row, g.perm, dxlr, dxlr.data_ptr() + 4 * HC, bag.target(att), bag.target(bias), ds, dz,
+                  part, B, N, H, C, E, slope, ACT[act], p, seed, ops.EP())
+        return dxlr, bag.result(att), (bag.result(bias) if bias is not None else None), None, None, None, None, None, None
+
+
+class MeanRowsFn(torch.autograd.Function):
+    """mean over dim 1 of fp32 (B, L, D): the global pooling over the nodes of a graph"""
+
+    @staticmethod
+    def forward(ctx, x):
+        x = _f(x)
+        B, L, D = x.shape
+        out = _empty((B, D), _F32, x)
+        _hip.call("mm_meanpool_fwd", x, out, None, B, L, D)
+        ctx.dims = (B, L, D)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        B, L, D = ctx.dims
+        dx = _empty((B, L, D), _F32, g)
+        _hip.call("mm_meanpool_bwd", _f(g), dx, B, L, D)
+        return dx
+
+
+def gatv2(conv, x, graph, act="none", training: bool = False):
+    """GATv2Conv on (B, N, in) rows, differentiable: both linears as one ``SmallLinearFn`` with W_l | W_r stacked,
+    then ``GATv2Fn`` (``act`` = its epilogue; attention dropout only when ``training``)"""
+    B, N, K = x.shape
+    if N != graph.num_nodes:
+        raise ValueError(f"gatv2: x has {N} nodes, the graph {graph.num_nodes}")
+    W, b = ops._gat_cat(conv)
+    xlr = SmallLinearFn.apply(x.reshape(B * N, K), W, b, "none", 0.0)
+    return GATv2Fn.apply(xlr.view(B, N, -1), conv.att, conv.bias, graph, conv.heads, conv.out_channels,
+                         float(conv.negative_slope), act, float(conv.dropout) if training else 0.0)
+
+
 def proj_head(x, seq, drop_p):
     """Linear -> LayerNorm -> GELU -> Dropout (bridge_utils.py:34-45)"""
     return ActFn.apply(LayerNormFn.apply(linear(x, seq[0]), seq[1].weight, seq[1].bias, seq[1].eps), "gelu", float(drop_p))

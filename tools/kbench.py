@@ -500,8 +500,66 @@ def xai_case(B=32, C=64, T=1024, vol=(32, 32, 32), n_steps=50, rounds=5):
     print(f"speed-up of the batched engine: {m['per-step + host round trips'] / m['batched engine']:.2f} x")
 
 
+def gat_case(B=32, N=64, H=4, C=32, dense=True):
+    """one GATv2 layer (csrc/gnn.hip) on the all-pairs graph, forward and backward, the W_l | W_r linear beside it, and
+    a GNNConnectivityEncoder eval forward for the whole batch vs one sample per call (the reference's loop shape)"""
+    import multimodal_eeg_fmri_amd.enhanced_models_v4 as E
+    adj = ~torch.eye(N, dtype=torch.bool) if dense else torch.rand(N, N) < 0.1
+    ei = adj.nonzero().t().contiguous().cuda()
+    g = ops.gat_graph(ei, N)
+    HC, Eg = H * C, g.num_edges
+    x = torch.randn(B * N, HC, device="cuda")
+    W = torch.randn(2 * HC, HC, device="cuda") / math.sqrt(HC)
+    b = torch.randn(2 * HC, device="cuda")
+    att = torch.randn(H, C, device="cuda") / math.sqrt(C)
+    bias = torch.randn(HC, device="cuda")
+    xlr = torch.empty(B * N, 2 * HC, device="cuda")
+    out, pre, dout = (torch.empty(B, N, HC, device="cuda") for _ in range(3))
+    dout.normal_()
+    alpha, ds = torch.empty(B, H, Eg, device="cuda"), torch.empty(B, H, Eg, device="cuda")
+    dz, part = torch.empty(B, N, HC, device="cuda"), torch.empty(B, 2, HC, device="cuda")
+    dxlr, dx = torch.empty_like(xlr), torch.empty_like(x)
+    dW, db, datt, dbias = torch.zeros_like(W), torch.zeros_like(b), torch.zeros_like(att), torch.zeros_like(bias)
+    xr, dxr = xlr.data_ptr() + 4 * HC, dxlr.data_ptr() + 4 * HC
+    act = ops.ACT["gelu"]
+
+    def lin_f():
+        _hip.call("mm_small_linear_fwd", x, W, b, None, None, xlr, None, B * N, HC, 2 * HC, 0, 0.0, 0, None)
+
+    def lin_b():
+        _hip.call("mm_small_linear_bwd", dxlr, x, W, dx, dW, db, B * N, HC, 2 * HC)
+
+    def fwd(p=0.0):
+        _hip.call("mm_gatv2_fwd", xlr, xr, 2 * HC, att, bias, g.rowptr, g.col, out, pre, alpha, B, N, H, C, Eg, 0.2, act, p, 7, None)
+
+    def bwd(p=0.0):
+        _hip.call("mm_gatv2_bwd", dout, pre, xlr, xr, 2 * HC, att, alpha, g.rowptr, g.col, g.colptr, g.row, g.perm, dxlr,
+                  dxr, datt, dbias, ds, dz, part, B, N, H, C, Eg, 0.2, act, p, 7, None)
+    lin_f()
+    tag = f"gat B={B} N={N} H={H} C={C} E'={Eg}"
+    rows = B * N * HC * 4
+    fb = 2 * rows + 2 * rows + B * H * Eg * 4                        # xl, xr in; out, pre out; alpha out
+    bb = 2 * rows + 2 * rows + 2 * rows + 2 * rows + 3 * B * H * Eg * 4   # xl, xr, dout, pre in; dz, dxl, dxr out (+ dz back in); alpha in, ds out + in
+    for name, fn, nbytes in (("linear W_l|W_r fwd", lin_f, B * N * 3 * HC * 4), ("gatv2 fwd p=0", fwd, fb),
+                             ("gatv2 fwd p=0.3", lambda: fwd(0.3), fb), ("gatv2 bwd p=0", bwd, bb),
+                             ("gatv2 bwd p=0.3", lambda: bwd(0.3), bb), ("linear W_l|W_r bwd", lin_b, B * N * 4 * HC * 4)):
+        us = timeit(fn)
+        print(f"{tag} {name:22s}: {us:8.1f} us   {nbytes / 1e6:6.2f} MB moved  {nbytes / us / 1e3:7.1f} GB/s")
+    enc = E.GNNConnectivityEncoder(num_nodes=N, num_conn_types=3, hidden_dim=HC, num_heads=H).cuda().eval()
+    conn = torch.rand(B, N, N, 3, device="cuda")
+    with torch.no_grad():
+        whole = timeit(lambda: enc(conn, ei), iters=5)
+        singles = [conn[i:i + 1].contiguous() for i in range(B)]
+        loop = timeit(lambda: [enc(c1, ei) for c1 in singles], iters=2)
+    print(f"{tag} encoder eval forward: whole batch {whole:8.1f} us   one sample per call x {B} {loop:8.1f} us   ({loop / whole:.1f} x)")
+
+
 def main():
     flt = sys.argv[1] if len(sys.argv) > 1 else ""
+    if flt.startswith("gat"):          # gat[:B,N,H,C]
+        dims = [int(d) for d in flt.split(":", 1)[1].split(",")] if ":" in flt and flt.split(":", 1)[1] else []
+        gat_case(*dims)
+        return
     if flt == "xai":
         xai_case()
         return
