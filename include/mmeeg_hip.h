@@ -704,6 +704,37 @@ int mm_gatv2_bwd(const float* dout, const float* pre, const float* xl, const flo
                  float* part_ws, int B, int N, int H, int C, int E, float slope, int act, float drop_p,
                  uint32_t seed, const uint32_t* seed_epoch, hipStream_t stream);
 
+/* ---- GATv2 with edge features (torch_geometric's GATv2Conv(edge_dim = D)): the raw attributes enter the score only,
+ *   e[i<-j] = sum_c att[h][c] * leaky_relu((xl[j][h][c] + xr[i][h][c]) + sum_d w_edge[h*C + c][d] * edge_attr[e][d], slope)
+ * everything else as mm_gatv2_fwd / mm_gatv2_bwd (w_edge = 0 gives their bits).
+ *   w_edge     [H*C][D] = lin_edge.weight, 1 <= D <= 8
+ *   edge_attr  [B][E][D] (ea_batched != 0) or [E][D] shared by the batch, in CSR order with the self-loop rows filled:
+ *              the output of mm_gatv2_edge_pack.  The projection runs inside the score loop; no [B][E][H*C] image.
+ * mm_gatv2_edge_bwd adds: dw_edge [H*C][D] (nullable, ACCUMULATED into, batch order), dedge_attr [B | 1][E][D]
+ *   (nullable, written: the per-head partials added in head order, for shared attributes over the batch too).
+ *   Workspaces: wpart_ws [B][H*C][D]; epart_ws [B][H][E][D], required when dedge_attr is given.  No atomics.
+ * mm_gatv2_edge_pack: listed [Bo][El][D] (rows aligned with the listed edge_index) -> csr [Bo][E][D].  eid [E] = listed
+ *   edge of each CSR position, -1 for an appended self-loop; indeg [N] = in-degree without loops.  The loop of node i
+ *   gets the mean of the listed attributes into i (0 without any) when fill_mean != 0, else fill_value.
+ * mm_gatv2_edge_pack_bwd: dlisted [Bo][El][D] (written) = dcsr[pos] + dcsr[loop of tgt] / indeg[tgt] (the second term
+ *   only when fill_mean != 0); pos [El] = CSR position of a listed edge, -1 for a dropped self-loop (gradient 0),
+ *   tgt [El] = its target. */
+int mm_gatv2_edge_fwd(const float* xl, const float* xr, int ld, const float* att, const float* bias,
+                      const float* w_edge, const float* edge_attr, int ea_batched, const int* rowptr, const int* col,
+                      float* out, float* pre, float* alpha, int B, int N, int H, int C, int E, int D, float slope,
+                      int act, float drop_p, uint32_t seed, const uint32_t* seed_epoch, hipStream_t stream);
+int mm_gatv2_edge_bwd(const float* dout, const float* pre, const float* xl, const float* xr, int ld, const float* att,
+                      const float* w_edge, const float* edge_attr, int ea_batched, const float* alpha,
+                      const int* rowptr, const int* col, const int* colptr, const int* row, const int* perm,
+                      float* dxl, float* dxr, float* datt, float* dbias, float* dw_edge, float* dedge_attr,
+                      float* ds_ws, float* dz_ws, float* part_ws, float* wpart_ws, float* epart_ws, int B, int N,
+                      int H, int C, int E, int D, float slope, int act, float drop_p, uint32_t seed,
+                      const uint32_t* seed_epoch, hipStream_t stream);
+int mm_gatv2_edge_pack(const float* listed, const int* eid, const int* rowptr, const int* indeg, float* csr, int Bo,
+                       int N, int El, int E, int D, int fill_mean, float fill_value, hipStream_t stream);
+int mm_gatv2_edge_pack_bwd(const float* dcsr, const int* pos, const int* tgt, const int* rowptr, const int* indeg,
+                           float* dlisted, int Bo, int N, int El, int E, int D, int fill_mean, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

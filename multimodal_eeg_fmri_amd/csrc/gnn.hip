@@ -17,6 +17,14 @@
 //   score phase      lane = edge           e, running max / sum through wave reductions
 //   aggregate phase  lane = (group, c)     64 / C groups split the edges of a 64-edge chunk, rows read contiguously
 // LDS: N (C + 1) + C + 4 x 64 x 4 words  <= 128 x 65 x 4 + 256 + 4096 B = 37.6 KB.
+//
+// Edge features (template parameter DP > 0, the mm_gatv2_edge_* entry points): the score becomes
+//   e[i <- j]  = sum_c att[h][c] * leaky_relu((xl[j][h][c] + xr[i][h][c]) + sum_d We[h][c][d] * ea[e][d])
+// with ea (B | 1, E', D) the raw attributes in CSR order (D <= 8; DP = D rounded up to 1, 2, 4 or 8, the tail zero) and
+// We = lin_edge.weight.  The head's We slice [C][DP] sits in LDS in front of xs (<= 2 KB; every lane of the score loop
+// reads the same word: a broadcast), the D attributes of a lane's edge in registers: the projection happens inside
+// the score loop, a (B, E', H C) image is never formed.  z is (xl + xr) + edge term in that order, so We = 0 gives
+// the bits of the plain kernel.  The backward also stages the attributes of a 64-edge chunk per wave ([64][DP]).
 #include "common.h"
 
 namespace {
@@ -33,6 +41,9 @@ struct GatArgs {
     float* ds; float* dz; float* part;                     // backward workspaces
     int B, N, H, C, E; float slope; int act;
     uint32_t thresh, seed; float inv_keep; const uint32_t* epoch;
+    // edge variant only (DP > 0)
+    const float* we; const float* ea; size_t ea_bs; int D;  // We [H*C][D]; ea [B | 1][E][D], batch stride ea_bs (0: shared)
+    float* dea; float* pwe;                                // backward: per-head d ea [B][H][E][D] (nullable), d We partials [B][H*C][D]
 };
 
 __device__ __forceinline__ void wave_sync() {
@@ -57,11 +68,48 @@ template <int C> __device__ __forceinline__ void load_slice(const GatArgs& a, in
     if (threadIdx.x < C) atts[threadIdx.x] = a.att[h * C + threadIdx.x];
 }
 
-template <int C>
+// ---- edge variant helpers: We slice [C][DP] at the start of the dynamic LDS (16-byte aligned rows)
+template <int C, int DP> __device__ __forceinline__ void load_we(const GatArgs& a, int h, float* wes) {
+    for (int idx = threadIdx.x; idx < C * DP; idx += blockDim.x) {
+        const int k = idx / DP, d = idx % DP;
+        wes[idx] = d < a.D ? a.we[(size_t)(h * C + k) * a.D + d] : 0.f;
+    }
+}
+
+template <int DP> __device__ __forceinline__ void load_row(const float* __restrict__ p, float (&w)[DP]) {
+    if constexpr (DP == 1) {
+        w[0] = p[0];
+    } else if constexpr (DP == 2) {
+        const float2 v = *reinterpret_cast<const float2*>(p);
+        w[0] = v.x; w[1] = v.y;
+    } else {
+#pragma unroll
+        for (int q = 0; q < DP; q += 4) {
+            const float4 v = *reinterpret_cast<const float4*>(p + q);
+            w[q] = v.x; w[q + 1] = v.y; w[q + 2] = v.z; w[q + 3] = v.w;
+        }
+    }
+}
+
+// the D raw attributes of CSR edge e of sample b (global), zero beyond D
+template <int DP> __device__ __forceinline__ void load_ea(const GatArgs& a, int b, int e, float (&ev)[DP]) {
+    const float* p = a.ea + (size_t)b * a.ea_bs + (size_t)e * a.D;
+#pragma unroll
+    for (int d = 0; d < DP; ++d) ev[d] = d < a.D ? p[d] : 0.f;
+}
+
+template <int DP> __device__ __forceinline__ float edge_term(const float (&w)[DP], const float (&ev)[DP]) {
+    float t = w[0] * ev[0];
+#pragma unroll
+    for (int d = 1; d < DP; ++d) t += w[d] * ev[d];
+    return t;
+}
+
+template <int C, int DP = 0>
 __global__ __launch_bounds__(64 * GAT_WAVES) void gatv2_fwd_kernel(GatArgs a) {
     constexpr int LDC = C + 1, G = 64 / C;
     extern __shared__ float smem[];
-    float* xs = smem;                                      // [N][C + 1]
+    float* xs = smem + C * DP;                             // [N][C + 1]  (edge variant: We slice [C][DP] in front)
     float* atts = xs + a.N * LDC;                          // [C]
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     float* xri = atts + C + wave * 256;                    // per wave: xr row of the target [64]
@@ -70,6 +118,7 @@ __global__ __launch_bounds__(64 * GAT_WAVES) void gatv2_fwd_kernel(GatArgs a) {
     const int bh = blockIdx.x, b = bh / a.H, h = bh % a.H;
     const uint32_t seed = mm_eff_seed(a.seed, a.epoch);
     load_slice<C>(a, b, h, xs, atts);
+    if constexpr (DP > 0) load_we<C, DP>(a, h, smem);
     __syncthreads();
     const int g = lane / C, c = lane % C, HC = a.H * C;
     float* alpha = a.alpha + (size_t)bh * a.E;
@@ -82,10 +131,21 @@ __global__ __launch_bounds__(64 * GAT_WAVES) void gatv2_fwd_kernel(GatArgs a) {
         for (int e = e0 + lane; e < e1; e += 64) {
             const float* xj = xs + a.col[e] * LDC;
             float s = 0.f;
+            if constexpr (DP > 0) {
+                float ev[DP], w[DP];
+                load_ea<DP>(a, b, e, ev);
+#pragma unroll 4
+                for (int k = 0; k < C; ++k) {
+                    load_row<DP>(smem + k * DP, w);
+                    const float z = (xj[k] + xri[k]) + edge_term<DP>(w, ev);
+                    s += atts[k] * (z > 0.f ? z : a.slope * z);
+                }
+            } else {
 #pragma unroll 8
-            for (int k = 0; k < C; ++k) {
-                const float z = xj[k] + xri[k];
-                s += atts[k] * (z > 0.f ? z : a.slope * z);
+                for (int k = 0; k < C; ++k) {
+                    const float z = xj[k] + xri[k];
+                    s += atts[k] * (z > 0.f ? z : a.slope * z);
+                }
             }
             alpha[e] = s;
             m = fmaxf(m, s);
@@ -122,11 +182,17 @@ __global__ __launch_bounds__(64 * GAT_WAVES) void gatv2_fwd_kernel(GatArgs a) {
 
 // backward, one launch: phase 1 walks the targets (d alpha -> d score, d xr, d att, d bias), phase 2 the sources
 // (d xl).  d score of every edge crosses from phase 1 to phase 2 through `ds` (global, the workgroup's own slice).
-template <int C>
+//
+// Edge variant: LDS starts with the We slice [C][DP] and a per-wave stage of a chunk's attributes [64][DP]; a lane of
+// the aggregate loop keeps the We row of its channel in registers.  d We: per-lane sums over the edges, group_sum,
+// block combine through the (then idle) stages, one partial per (sample, head) to `pwe`.  d ea crosses heads, which
+// are separate workgroups: lane = edge forms sum_c d z[e][c] We[c][d] for its head and writes it to `dea`
+// [B][H][E][D]; gatv2_edge_dea_kernel adds the heads in order.
+template <int C, int DP = 0>
 __global__ __launch_bounds__(64 * GAT_WAVES) void gatv2_bwd_kernel(GatArgs a) {
     constexpr int LDC = C + 1, G = 64 / C;
     extern __shared__ float smem[];
-    float* xs = smem;
+    float* xs = smem + (C + 64 * GAT_WAVES) * DP;
     float* atts = xs + a.N * LDC;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     float* red = atts + C;                                 // [GAT_WAVES][2][C] block combine of d att / d bias (<= 512 words)
@@ -137,8 +203,16 @@ __global__ __launch_bounds__(64 * GAT_WAVES) void gatv2_bwd_kernel(GatArgs a) {
     const int bh = blockIdx.x, b = bh / a.H, h = bh % a.H;
     const uint32_t seed = mm_eff_seed(a.seed, a.epoch);
     load_slice<C>(a, b, h, xs, atts);
+    if constexpr (DP > 0) load_we<C, DP>(a, h, smem);
     __syncthreads();
     const int g = lane / C, c = lane % C, HC = a.H * C;
+    [[maybe_unused]] float* wea = smem + (C + 64 * wave) * DP;              // edge variant, per wave: attributes of a chunk [64][DP]
+    [[maybe_unused]] float wc[DP > 0 ? DP : 1], dwe[DP > 0 ? DP : 1];       // We row of channel c; d We[c][:] / att[c] of this lane's edges
+    if constexpr (DP > 0) {
+        load_row<DP>(smem + c * DP, wc);
+#pragma unroll
+        for (int d = 0; d < DP; ++d) dwe[d] = 0.f;
+    }
     const float* alpha = a.alpha + (size_t)bh * a.E;
     float* ds = a.ds + (size_t)bh * a.E;
     const float* dzsrc = a.act != MM_ACT_NONE ? a.dz : a.dout;
@@ -178,12 +252,44 @@ __global__ __launch_bounds__(64 * GAT_WAVES) void gatv2_bwd_kernel(GatArgs a) {
                 ds[e] = d;
                 wa[lane] = d;
                 wj[lane] = a.col[e];
+                if constexpr (DP > 0) {
+                    float ev[DP];
+                    load_ea<DP>(a, b, e, ev);
+#pragma unroll
+                    for (int q = 0; q < DP; ++q) wea[lane * DP + q] = ev[q];
+                    if (a.dea) {                           // d ea[e][:] of this head = sum_c d z[e][c] We[c][:]
+                        const float* xj = xs + a.col[e] * LDC;
+                        float de[DP], w[DP];
+#pragma unroll
+                        for (int q = 0; q < DP; ++q) de[q] = 0.f;
+#pragma unroll 4
+                        for (int k = 0; k < C; ++k) {
+                            load_row<DP>(smem + k * DP, w);
+                            const float z = (xj[k] + xri[k]) + edge_term<DP>(w, ev);
+                            const float gz = d * atts[k] * (z > 0.f ? 1.f : a.slope);
+#pragma unroll
+                            for (int q = 0; q < DP; ++q) de[q] += gz * w[q];
+                        }
+                        float* o = a.dea + ((size_t)bh * a.E + e) * a.D;
+#pragma unroll
+                        for (int q = 0; q < DP; ++q)
+                            if (q < a.D) o[q] = de[q];
+                    }
+                }
             }
             wave_sync();
             const int cnt = e1 - base < 64 ? e1 - base : 64;
             const float xr_c = xri[c];
             for (int t = g; t < cnt; t += G) {
-                const float z = xs[wj[t] * LDC + c] + xr_c;
+                float z = xs[wj[t] * LDC + c] + xr_c;
+                if constexpr (DP > 0) {
+                    float ev[DP];
+                    load_row<DP>(wea + t * DP, ev);
+                    z += edge_term<DP>(wc, ev);
+                    const float gz = wa[t] * (z > 0.f ? 1.f : a.slope);
+#pragma unroll
+                    for (int q = 0; q < DP; ++q) dwe[q] += gz * ev[q];
+                }
                 dxr += wa[t] * (z > 0.f ? 1.f : a.slope);
                 datt += wa[t] * (z > 0.f ? z : a.slope * z);
             }
@@ -197,8 +303,24 @@ __global__ __launch_bounds__(64 * GAT_WAVES) void gatv2_bwd_kernel(GatArgs a) {
         red[(wave * 2 + 0) * C + c] = datt;
         red[(wave * 2 + 1) * C + c] = dbias;
     }
+    if constexpr (DP > 0) {                                // the wave's stage is idle now: its d We partial [C][DP]
+#pragma unroll
+        for (int q = 0; q < DP; ++q) {
+            const float v = group_sum<C>(dwe[q]);
+            if (lane < C) wea[c * DP + q] = v;
+        }
+    }
     __threadfence_block();
     __syncthreads();
+    if constexpr (DP > 0) {
+        for (int idx = threadIdx.x; idx < C * DP; idx += blockDim.x) {
+            const int cc = idx / DP, q = idx % DP;
+            float s = 0.f;
+#pragma unroll
+            for (int w = 0; w < GAT_WAVES; ++w) s += smem[(C + 64 * w) * DP + idx];
+            if (q < a.D) a.pwe[((size_t)b * HC + h * C + cc) * a.D + q] = s * atts[cc];
+        }
+    }
     if (threadIdx.x < 2 * C) {
         const int k = threadIdx.x / C, cc = threadIdx.x % C;
         float s = 0.f;
@@ -216,7 +338,12 @@ __global__ __launch_bounds__(64 * GAT_WAVES) void gatv2_bwd_kernel(GatArgs a) {
             const size_t node = (size_t)b * a.N + i;
             float am = alpha[e];
             if (a.thresh) am *= dropout_scale(seed, (uint32_t)((size_t)bh * a.E + e), a.thresh, a.inv_keep);
-            const float z = xl_c + a.xr[node * a.ld + h * C + c];
+            float z = xl_c + a.xr[node * a.ld + h * C + c];
+            if constexpr (DP > 0) {
+                float ev[DP];
+                load_ea<DP>(a, b, e, ev);
+                z += edge_term<DP>(wc, ev);
+            }
             acc += am * dzsrc[node * HC + h * C + c] + ds[e] * att_c * (z > 0.f ? 1.f : a.slope);
         }
         acc = group_sum<C>(acc);
@@ -238,6 +365,69 @@ __global__ void gatv2_param_grads_kernel(const float* __restrict__ part, float* 
     if (dbias) dbias[k] += sb;
 }
 
+// d lin_edge.weight += sum over the batch of the per-(sample, head) partials [B][H*C*D], in batch order
+__global__ void gatv2_edge_wgrad_kernel(const float* __restrict__ part, float* __restrict__ dwe, int B, int n) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    float s = 0.f;
+    for (int b = 0; b < B; ++b) s += part[(size_t)b * n + k];
+    dwe[k] += s;
+}
+
+// d ea (CSR order) = the per-head partials [B][H][E*D] added in head order; shared attributes (Bo = 1): over the
+// batch too, sample by sample
+__global__ void gatv2_edge_dea_kernel(const float* __restrict__ part, float* __restrict__ dea, int B, int Bo, int H, int n) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    const int bo = blockIdx.y;
+    float s = 0.f;
+    for (int b = (Bo == 1 ? 0 : bo); b < (Bo == 1 ? B : bo + 1); ++b)
+        for (int h = 0; h < H; ++h) s += part[((size_t)b * H + h) * n + k];
+    dea[(size_t)bo * n + k] = s;
+}
+
+// listed attributes [Bo][El][D] -> CSR order [Bo][E][D]; the appended self-loop of node i (the last edge of row i)
+// gets the mean of the listed edges into i (0 without any) or a constant.  One thread per (sample, node, d).
+__global__ void gatv2_edge_pack_kernel(const float* __restrict__ listed, const int* __restrict__ eid,
+                                       const int* __restrict__ rowptr, const int* __restrict__ indeg,
+                                       float* __restrict__ csr, int N, int El, int E, int D, int fill_mean, float fill) {
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= N * D) return;
+    const int i = idx / D, d = idx % D;
+    const float* src = listed + (size_t)blockIdx.y * El * D;
+    float* dst = csr + (size_t)blockIdx.y * E * D;
+    float s = 0.f;
+    for (int e = rowptr[i]; e < rowptr[i + 1]; ++e) {
+        const int l = eid[e];
+        if (l >= 0) {
+            const float v = src[(size_t)l * D + d];
+            dst[(size_t)e * D + d] = v;
+            s += v;
+        } else {
+            dst[(size_t)e * D + d] = fill_mean ? (indeg[i] > 0 ? s / (float)indeg[i] : 0.f) : fill;
+        }
+    }
+}
+
+// d listed[l] = d csr[pos(l)] + d csr[loop of l's target] / indeg  (0 for a dropped listed self-loop): a gather
+__global__ void gatv2_edge_pack_bwd_kernel(const float* __restrict__ dcsr, const int* __restrict__ pos,
+                                           const int* __restrict__ tgt, const int* __restrict__ rowptr,
+                                           const int* __restrict__ indeg, float* __restrict__ dlisted, int El, int E,
+                                           int D, int fill_mean) {
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= El * D) return;
+    const int l = idx / D, d = idx % D;
+    const float* src = dcsr + (size_t)blockIdx.y * E * D;
+    const int e = pos[l];
+    float v = 0.f;
+    if (e >= 0) {
+        v = src[(size_t)e * D + d];
+        const int i = tgt[l];
+        if (fill_mean) v += src[(size_t)(rowptr[i + 1] - 1) * D + d] / (float)indeg[i];
+    }
+    dlisted[(size_t)blockIdx.y * El * D + idx] = v;
+}
+
 int gat_check(const char* who, int B, int N, int H, int C, int E, int ld, int act, float drop_p) {
     MM_REQUIRE(B > 0 && H > 0, "%s: B=%d H=%d", who, B, H);
     MM_REQUIRE(N >= 1 && N <= 128, "%s: N=%d outside [1, 128]", who, N);
@@ -253,6 +443,22 @@ int gat_check(const char* who, int B, int N, int H, int C, int E, int ld, int ac
 
 inline uint32_t gat_thresh(float p) { return p > 0.f ? (uint32_t)((double)p * 4294967296.0) : 0u; }
 
+inline int gat_dp(int D) { return D <= 2 ? D : D <= 4 ? 4 : 8; }
+
+template <int DP> void launch_fwd(const GatArgs& a, size_t lds, hipStream_t st) {
+    const dim3 grid(a.B * a.H), block(64 * GAT_WAVES);
+    if (a.C == 16) hipLaunchKernelGGL((gatv2_fwd_kernel<16, DP>), grid, block, lds, st, a);
+    else if (a.C == 32) hipLaunchKernelGGL((gatv2_fwd_kernel<32, DP>), grid, block, lds, st, a);
+    else hipLaunchKernelGGL((gatv2_fwd_kernel<64, DP>), grid, block, lds, st, a);
+}
+
+template <int DP> void launch_bwd(const GatArgs& a, size_t lds, hipStream_t st) {
+    const dim3 grid(a.B * a.H), block(64 * GAT_WAVES);
+    if (a.C == 16) hipLaunchKernelGGL((gatv2_bwd_kernel<16, DP>), grid, block, lds, st, a);
+    else if (a.C == 32) hipLaunchKernelGGL((gatv2_bwd_kernel<32, DP>), grid, block, lds, st, a);
+    else hipLaunchKernelGGL((gatv2_bwd_kernel<64, DP>), grid, block, lds, st, a);
+}
+
 }  // namespace
 
 extern "C" {
@@ -267,12 +473,30 @@ int mm_gatv2_fwd(const float* xl, const float* xr, int ld, const float* att, con
     a.out = out; a.pre = pre; a.alpha = alpha;
     a.B = B; a.N = N; a.H = H; a.C = C; a.E = E; a.slope = slope; a.act = act;
     a.thresh = gat_thresh(drop_p); a.seed = seed; a.inv_keep = drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f; a.epoch = seed_epoch;
-    const size_t lds = ((size_t)N * (C + 1) + C + GAT_WAVES * 256) * sizeof(float);
-    const dim3 grid(B * H), block(64 * GAT_WAVES);
-    if (C == 16) hipLaunchKernelGGL(gatv2_fwd_kernel<16>, grid, block, lds, st, a);
-    else if (C == 32) hipLaunchKernelGGL(gatv2_fwd_kernel<32>, grid, block, lds, st, a);
-    else hipLaunchKernelGGL(gatv2_fwd_kernel<64>, grid, block, lds, st, a);
+    launch_fwd<0>(a, ((size_t)N * (C + 1) + C + GAT_WAVES * 256) * sizeof(float), st);
     return mm_check_launch("gatv2_fwd");
+}
+
+int mm_gatv2_edge_fwd(const float* xl, const float* xr, int ld, const float* att, const float* bias,
+                      const float* w_edge, const float* edge_attr, int ea_batched, const int* rowptr, const int* col,
+                      float* out, float* pre, float* alpha, int B, int N, int H, int C, int E, int D, float slope,
+                      int act, float drop_p, uint32_t seed, const uint32_t* seed_epoch, hipStream_t st) {
+    MM_REQUIRE(xl && xr && att && w_edge && edge_attr && rowptr && col && out && alpha, "gatv2_edge_fwd: null pointer");
+    if (int rc = gat_check("gatv2_edge_fwd", B, N, H, C, E, ld, act, drop_p)) return rc;
+    MM_REQUIRE(D >= 1 && D <= 8, "gatv2_edge_fwd: D=%d outside [1, 8]", D);
+    GatArgs a{};
+    a.xl = xl; a.xr = xr; a.ld = ld; a.att = att; a.bias = bias; a.rowptr = rowptr; a.col = col;
+    a.out = out; a.pre = pre; a.alpha = alpha;
+    a.B = B; a.N = N; a.H = H; a.C = C; a.E = E; a.slope = slope; a.act = act;
+    a.thresh = gat_thresh(drop_p); a.seed = seed; a.inv_keep = drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f; a.epoch = seed_epoch;
+    a.we = w_edge; a.ea = edge_attr; a.ea_bs = ea_batched ? (size_t)E * D : 0; a.D = D;
+    const int DP = gat_dp(D);
+    const size_t lds = ((size_t)N * (C + 1) + C + GAT_WAVES * 256 + C * DP) * sizeof(float);
+    if (DP == 1) launch_fwd<1>(a, lds, st);
+    else if (DP == 2) launch_fwd<2>(a, lds, st);
+    else if (DP == 4) launch_fwd<4>(a, lds, st);
+    else launch_fwd<8>(a, lds, st);
+    return mm_check_launch("gatv2_edge_fwd");
 }
 
 int mm_gatv2_bwd(const float* dout, const float* pre, const float* xl, const float* xr, int ld, const float* att,
@@ -290,14 +514,73 @@ int mm_gatv2_bwd(const float* dout, const float* pre, const float* xl, const flo
     a.ds = ds_ws; a.dz = dz_ws; a.part = part_ws;
     a.B = B; a.N = N; a.H = H; a.C = C; a.E = E; a.slope = slope; a.act = act;
     a.thresh = gat_thresh(drop_p); a.seed = seed; a.inv_keep = drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f; a.epoch = seed_epoch;
-    const size_t lds = ((size_t)N * (C + 1) + C + 512 + GAT_WAVES * 256) * sizeof(float);
-    const dim3 grid(B * H), block(64 * GAT_WAVES);
-    if (C == 16) hipLaunchKernelGGL(gatv2_bwd_kernel<16>, grid, block, lds, st, a);
-    else if (C == 32) hipLaunchKernelGGL(gatv2_bwd_kernel<32>, grid, block, lds, st, a);
-    else hipLaunchKernelGGL(gatv2_bwd_kernel<64>, grid, block, lds, st, a);
+    launch_bwd<0>(a, ((size_t)N * (C + 1) + C + 512 + GAT_WAVES * 256) * sizeof(float), st);
     if (datt || dbias)
         hipLaunchKernelGGL(gatv2_param_grads_kernel, dim3(1), dim3(256), 0, st, part_ws, datt, dbias, B, H * C);
     return mm_check_launch("gatv2_bwd");
+}
+
+int mm_gatv2_edge_bwd(const float* dout, const float* pre, const float* xl, const float* xr, int ld, const float* att,
+                      const float* w_edge, const float* edge_attr, int ea_batched, const float* alpha,
+                      const int* rowptr, const int* col, const int* colptr, const int* row, const int* perm,
+                      float* dxl, float* dxr, float* datt, float* dbias, float* dw_edge, float* dedge_attr,
+                      float* ds_ws, float* dz_ws, float* part_ws, float* wpart_ws, float* epart_ws, int B, int N,
+                      int H, int C, int E, int D, float slope, int act, float drop_p, uint32_t seed,
+                      const uint32_t* seed_epoch, hipStream_t st) {
+    MM_REQUIRE(dout && xl && xr && att && w_edge && edge_attr && alpha && rowptr && col && colptr && row && perm && dxl &&
+               dxr && ds_ws && part_ws && wpart_ws, "gatv2_edge_bwd: null pointer");
+    if (int rc = gat_check("gatv2_edge_bwd", B, N, H, C, E, ld, act, drop_p)) return rc;
+    MM_REQUIRE(D >= 1 && D <= 8, "gatv2_edge_bwd: D=%d outside [1, 8]", D);
+    MM_REQUIRE(act == MM_ACT_NONE || (pre && dz_ws), "gatv2_edge_bwd: an activation epilogue needs pre and dz_ws");
+    MM_REQUIRE(!dedge_attr || epart_ws, "gatv2_edge_bwd: dedge_attr needs epart_ws");
+    GatArgs a{};
+    a.xl = xl; a.xr = xr; a.ld = ld; a.att = att; a.rowptr = rowptr; a.col = col; a.colptr = colptr; a.row = row; a.perm = perm;
+    a.pre = const_cast<float*>(pre); a.alpha = const_cast<float*>(alpha); a.dout = dout; a.dxl = dxl; a.dxr = dxr;
+    a.ds = ds_ws; a.dz = dz_ws; a.part = part_ws;
+    a.B = B; a.N = N; a.H = H; a.C = C; a.E = E; a.slope = slope; a.act = act;
+    a.thresh = gat_thresh(drop_p); a.seed = seed; a.inv_keep = drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f; a.epoch = seed_epoch;
+    a.we = w_edge; a.ea = edge_attr; a.ea_bs = ea_batched ? (size_t)E * D : 0; a.D = D;
+    a.dea = dedge_attr ? epart_ws : nullptr; a.pwe = wpart_ws;
+    const int DP = gat_dp(D);
+    const size_t lds = ((size_t)N * (C + 1) + C + 512 + GAT_WAVES * 256 + (C + 64 * GAT_WAVES) * DP) * sizeof(float);
+    if (DP == 1) launch_bwd<1>(a, lds, st);
+    else if (DP == 2) launch_bwd<2>(a, lds, st);
+    else if (DP == 4) launch_bwd<4>(a, lds, st);
+    else launch_bwd<8>(a, lds, st);
+    if (datt || dbias)
+        hipLaunchKernelGGL(gatv2_param_grads_kernel, dim3(1), dim3(256), 0, st, part_ws, datt, dbias, B, H * C);
+    if (dw_edge)
+        hipLaunchKernelGGL(gatv2_edge_wgrad_kernel, dim3((H * C * D + 255) / 256), dim3(256), 0, st, wpart_ws, dw_edge, B,
+                           H * C * D);
+    if (dedge_attr)
+        hipLaunchKernelGGL(gatv2_edge_dea_kernel, dim3((E * D + 255) / 256, ea_batched ? B : 1), dim3(256), 0, st, epart_ws,
+                           dedge_attr, B, ea_batched ? B : 1, H, E * D);
+    return mm_check_launch("gatv2_edge_bwd");
+}
+
+int mm_gatv2_edge_pack(const float* listed, const int* eid, const int* rowptr, const int* indeg, float* csr, int Bo,
+                       int N, int El, int E, int D, int fill_mean, float fill_value, hipStream_t st) {
+    MM_REQUIRE(eid && rowptr && indeg && csr && (listed || El == 0), "gatv2_edge_pack: null pointer");
+    MM_REQUIRE(Bo >= 1 && Bo <= 65535, "gatv2_edge_pack: B=%d outside [1, 65535]", Bo);
+    MM_REQUIRE(N >= 1 && N <= 128, "gatv2_edge_pack: N=%d outside [1, 128]", N);
+    MM_REQUIRE(D >= 1 && D <= 8, "gatv2_edge_pack: D=%d outside [1, 8]", D);
+    MM_REQUIRE(El >= 0 && E >= N && E <= El + N, "gatv2_edge_pack: E=%d CSR edges for %d listed edges and N=%d nodes", E, El, N);
+    hipLaunchKernelGGL(gatv2_edge_pack_kernel, dim3((N * D + 255) / 256, Bo), dim3(256), 0, st, listed, eid, rowptr, indeg,
+                       csr, N, El, E, D, fill_mean, fill_value);
+    return mm_check_launch("gatv2_edge_pack");
+}
+
+int mm_gatv2_edge_pack_bwd(const float* dcsr, const int* pos, const int* tgt, const int* rowptr, const int* indeg,
+                           float* dlisted, int Bo, int N, int El, int E, int D, int fill_mean, hipStream_t st) {
+    MM_REQUIRE(dcsr && rowptr && indeg && ((pos && tgt && dlisted) || El == 0), "gatv2_edge_pack_bwd: null pointer");
+    MM_REQUIRE(Bo >= 1 && Bo <= 65535, "gatv2_edge_pack_bwd: B=%d outside [1, 65535]", Bo);
+    MM_REQUIRE(N >= 1 && N <= 128, "gatv2_edge_pack_bwd: N=%d outside [1, 128]", N);
+    MM_REQUIRE(D >= 1 && D <= 8, "gatv2_edge_pack_bwd: D=%d outside [1, 8]", D);
+    MM_REQUIRE(El >= 0 && E >= N && E <= El + N, "gatv2_edge_pack_bwd: E=%d CSR edges for %d listed edges and N=%d nodes", E, El, N);
+    if (El == 0) return MM_OK;
+    hipLaunchKernelGGL(gatv2_edge_pack_bwd_kernel, dim3((El * D + 255) / 256, Bo), dim3(256), 0, st, dcsr, pos, tgt, rowptr,
+                       indeg, dlisted, El, E, D, fill_mean);
+    return mm_check_launch("gatv2_edge_pack_bwd");
 }
 
 }  // extern "C"

@@ -246,6 +246,33 @@ class ChannelImportanceExtractor:
         return sorted(conn_importance.items(), key=lambda kv: kv[1], reverse=True)[:k]
 
 
+def attention_connectivity_importance(encoder, x: torch.Tensor, edge_index: torch.Tensor, channel_names: List[str],
+                                      edge_attr: Optional[torch.Tensor] = None) -> Dict[Tuple[str, str], float]:
+    """which electrode pairs a ``GNNConnectivityEncoder`` attends to: {(source name, target name): share}.  The
+    eval-mode attention alpha[target <- source] of the GATv2 layers (the softmax the kernels save, no dropout),
+    averaged over batch, heads and layers; self-loops left out, the copies of a duplicated edge summed; normalised to
+    sum 1 as ``ChannelImportanceExtractor.extract_connectivity_importance`` does, so ``get_top_connections`` takes it."""
+    if len(channel_names) != encoder.num_nodes:
+        raise ValueError(f"attention_connectivity_importance: {len(channel_names)} channel names for {encoder.num_nodes} nodes")
+    was_training = encoder.training
+    encoder.eval()
+    try:
+        with torch.no_grad():
+            alphas: List[torch.Tensor] = []
+            ops.gnn_conn_encoder_forward(encoder, x, edge_index, edge_attr, attn_sink=alphas)
+            graph = ops.gat_graph(edge_index, encoder.num_nodes)
+            pairs, _ = ops.gat_attention_output(graph, alphas[0])
+            mean = torch.stack([ops.gat_attention_output(graph, a)[1].mean(dim=(0, 2)) for a in alphas]).mean(dim=0)
+    finally:
+        encoder.train(was_training)
+    raw: Dict[Tuple[str, str], float] = defaultdict(float)
+    for (s, t), v in zip(pairs.t().tolist(), mean.tolist()):
+        if s != t:
+            raw[(channel_names[s], channel_names[t])] += v
+    total = sum(raw.values()) + 1e-8
+    return {pair: v / total for pair, v in raw.items()}
+
+
 class EEGExplainer:
     """several attribution methods + channel-level summaries behind one object (reference :498-693)"""
 

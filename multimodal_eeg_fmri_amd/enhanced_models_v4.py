@@ -168,30 +168,20 @@ def _glorot(t: torch.Tensor) -> None:
         t.uniform_(-a, a)
 
 
-class GATv2Conv(nn.Module):
-    """GATv2 graph attention (Brody et al. 2022) with the parameter names and shapes of torch_geometric's layer of
-    the same name - ``att`` (1, H, C), ``bias`` (H*C), ``lin_l`` / ``lin_r`` Linear(in, H*C) - so that a state dict
-    trained with it loads.  ``x`` is (N, in) or (B, N, in); every sample shares ``edge_index`` (2, E) =
-    [source; target].  Runs on ``mm_gatv2_fwd`` / ``mm_gatv2_bwd``: at most 128 nodes, H*C <= 256, C in {16, 32, 64}."""
+class _GATv2Base(nn.Module):
+    """parameters and initialisation shared by GATv2Conv and GATv2EdgeConv: ``att`` (1, H, C), ``bias`` (H*C),
+    ``lin_l`` / ``lin_r`` Linear(in, H*C) and, with ``edge_dim``, ``lin_edge`` Linear(edge_dim, H*C, bias=False) -
+    torch_geometric's names and shapes, glorot weights, zero biases."""
 
-    def __init__(self, in_channels: int, out_channels: int, heads: int = 1, concat: bool = True,
-                 negative_slope: float = 0.2, dropout: float = 0.0, add_self_loops: bool = True, bias: bool = True,
-                 edge_dim: Optional[int] = None, share_weights: bool = False):
+    def __init__(self, in_channels, out_channels, heads, negative_slope, dropout, bias, edge_dim):
         super().__init__()
-        if not concat:
-            raise NotImplementedError("GATv2Conv: concat=False (head averaging) is not implemented")
-        if share_weights:
-            raise NotImplementedError("GATv2Conv: share_weights=True is not implemented")
-        if edge_dim is not None:
-            raise NotImplementedError("GATv2Conv: edge features are not implemented")
-        if not add_self_loops:
-            raise NotImplementedError("GATv2Conv: add_self_loops=False is not implemented")
-        if not isinstance(in_channels, int):
-            raise NotImplementedError("GATv2Conv: bipartite (source, target) input sizes are not implemented")
         self.in_channels, self.out_channels, self.heads = in_channels, out_channels, heads
-        self.concat, self.negative_slope, self.dropout, self.add_self_loops = concat, negative_slope, dropout, add_self_loops
+        self.concat, self.negative_slope, self.dropout, self.add_self_loops = True, negative_slope, dropout, True
+        self.edge_dim = edge_dim
         self.lin_l = nn.Linear(in_channels, heads * out_channels, bias=bias)
         self.lin_r = nn.Linear(in_channels, heads * out_channels, bias=bias)
+        if edge_dim is not None:
+            self.lin_edge = nn.Linear(edge_dim, heads * out_channels, bias=False)
         self.att = nn.Parameter(torch.empty(1, heads, out_channels))
         if bias:
             self.bias = nn.Parameter(torch.empty(heads * out_channels))
@@ -204,30 +194,91 @@ class GATv2Conv(nn.Module):
             _glorot(lin.weight)
             if lin.bias is not None:
                 nn.init.zeros_(lin.bias)
+        if self.edge_dim is not None:
+            _glorot(self.lin_edge.weight)
         _glorot(self.att)
         if self.bias is not None:
             nn.init.zeros_(self.bias)
 
+
+class GATv2Conv(_GATv2Base):
+    """GATv2 graph attention (Brody et al. 2022) with the parameter names and shapes of torch_geometric's layer of
+    the same name - ``att`` (1, H, C), ``bias`` (H*C), ``lin_l`` / ``lin_r`` Linear(in, H*C) - so that a state dict
+    trained with it loads.  ``x`` is (N, in) or (B, N, in); every sample shares ``edge_index`` (2, E) =
+    [source; target].  Runs on ``mm_gatv2_fwd`` / ``mm_gatv2_bwd``: at most 128 nodes, H*C <= 256, C in {16, 32, 64}.
+
+    Edge features live in a class of their own, ``GATv2EdgeConv``: this one keeps refusing ``edge_dim`` and
+    ``edge_attr`` with NotImplementedError (tests/test_gnn_host.py pins that), so code that relied on the refusal is
+    not silently given another layer.  ``return_attention_weights=True`` -> ``(out, (edge_index', alpha))``:
+    ``edge_index'`` (2, E') in torch_geometric's order (the listed non-loop edges in listed order, then the N
+    self-loops), ``alpha`` (E', H) for 2-D ``x`` and (B, E', H) for 3-D ``x``.  Deviation: alpha is the softmax BEFORE
+    attention dropout (what the kernel saves); torch_geometric returns it after dropout."""
+
+    def __init__(self, in_channels: int, out_channels: int, heads: int = 1, concat: bool = True,
+                 negative_slope: float = 0.2, dropout: float = 0.0, add_self_loops: bool = True, bias: bool = True,
+                 edge_dim: Optional[int] = None, share_weights: bool = False):
+        if not concat:
+            raise NotImplementedError("GATv2Conv: concat=False (head averaging) is not implemented")
+        if share_weights:
+            raise NotImplementedError("GATv2Conv: share_weights=True is not implemented")
+        if edge_dim is not None:
+            raise NotImplementedError("GATv2Conv: edge features are not implemented here: use GATv2EdgeConv")
+        if not add_self_loops:
+            raise NotImplementedError("GATv2Conv: add_self_loops=False is not implemented")
+        if not isinstance(in_channels, int):
+            raise NotImplementedError("GATv2Conv: bipartite (source, target) input sizes are not implemented")
+        super().__init__(in_channels, out_channels, heads, negative_slope, dropout, bias, None)
+
     def forward(self, x: torch.Tensor, edge_index: torch.Tensor, edge_attr=None, return_attention_weights=None):
-        if edge_attr is not None or return_attention_weights is not None:
-            raise NotImplementedError("GATv2Conv: edge_attr / return_attention_weights are not implemented")
-        return ops.gatv2_conv_forward(self, x, edge_index)
+        if edge_attr is not None:
+            raise NotImplementedError("GATv2Conv: edge_attr is not implemented here: use GATv2EdgeConv")
+        return ops.gatv2_conv_forward(self, x, edge_index, None, return_attention_weights)
+
+
+class GATv2EdgeConv(_GATv2Base):
+    """GATv2Conv with edge features, torch_geometric's ``GATv2Conv(edge_dim=D)``: its state dict loads (the extra key
+    is ``lin_edge.weight`` (H*C, D)).  The attributes enter the score only, not the message:
+
+        e[i<-j] = a^T leaky_relu(W_l h_j + W_r h_i + W_e a_ij)
+
+    ``edge_attr`` is (E,) or (E, D) when the batch shares it, (B, E, D) per sample, its rows aligned with the listed
+    ``edge_index``; D = ``edge_dim`` in 1..8.  Listed self-loops are dropped together with their attributes; the
+    appended loop of node i gets ``fill_value``: 'mean' = the mean attribute of the remaining listed edges into i (0
+    without any), or a constant.  A missing ``edge_attr``, a wrong D, E or B is a ValueError before any launch.
+    ``return_attention_weights`` as in ``GATv2Conv``.  Runs on ``mm_gatv2_edge_fwd`` / ``mm_gatv2_edge_bwd``."""
+
+    def __init__(self, in_channels: int, out_channels: int, heads: int = 1, edge_dim: int = 1,
+                 negative_slope: float = 0.2, dropout: float = 0.0, bias: bool = True, fill_value="mean"):
+        if isinstance(edge_dim, bool) or not isinstance(edge_dim, int) or not 1 <= edge_dim <= 8:
+            raise ValueError(f"GATv2EdgeConv: edge_dim={edge_dim!r}, supported 1..8")
+        ops._fill_args(fill_value)
+        super().__init__(in_channels, out_channels, heads, negative_slope, dropout, bias, edge_dim)
+        self.fill_value = fill_value
+
+    def forward(self, x: torch.Tensor, edge_index: torch.Tensor, edge_attr: torch.Tensor = None,
+                return_attention_weights=None):
+        return ops.gatv2_conv_forward(self, x, edge_index, edge_attr, return_attention_weights)
 
 
 class GNNConnectivityEncoder(nn.Module):
     """(B, nodes, nodes, conn_types) connectivity (or any shape that flattens to (B, nodes, -1)) -> (B, hidden_dim):
     per-node Linear-BN-GELU -> ``num_gat_layers`` x [GATv2Conv + GELU] over the shared electrode graph -> mean over
-    nodes -> Linear-BN-GELU."""
+    nodes -> Linear-BN-GELU.  With ``edge_dim`` the layers are ``GATv2EdgeConv`` and ``forward`` takes ``edge_attr``
+    ((E,), (E, D) or (B, E, D)); without one every sample's own connectivity is its edge feature,
+    ea[b, e, :] = x[b, source e, target e, :], which needs the 4-D form and ``edge_dim == num_conn_types``."""
 
     def __init__(self, num_nodes: int, num_conn_types: int = 3, hidden_dim: int = 128, num_gat_layers: int = 2,
-                 num_heads: int = 4, dropout: float = 0.3):
+                 num_heads: int = 4, dropout: float = 0.3, edge_dim: Optional[int] = None):
         super().__init__()
         self.num_nodes = num_nodes
         self.num_conn_types = num_conn_types
+        self.edge_dim = edge_dim
         self.node_proj = nn.Sequential(nn.Linear(num_nodes * num_conn_types, hidden_dim), nn.BatchNorm1d(hidden_dim),
                                        nn.GELU(), _drop(dropout))
         self.gat_layers = nn.ModuleList([
             GATv2Conv(hidden_dim, hidden_dim // num_heads, heads=num_heads, dropout=dropout, concat=True)
+            if edge_dim is None else
+            GATv2EdgeConv(hidden_dim, hidden_dim // num_heads, heads=num_heads, edge_dim=edge_dim, dropout=dropout)
             for _ in range(num_gat_layers)])
         self.output_proj = nn.Sequential(nn.Linear(hidden_dim, hidden_dim), nn.BatchNorm1d(hidden_dim),
                                          nn.GELU(), _drop(dropout))
@@ -241,18 +292,21 @@ class GNNConnectivityEncoder(nn.Module):
         edges = (avg > threshold).nonzero(as_tuple=False)
         return edges.t().contiguous(), avg[edges[:, 0], edges[:, 1]].unsqueeze(1)
 
-    def forward(self, x: torch.Tensor, edge_index: torch.Tensor) -> torch.Tensor:
-        return ops.gnn_conn_encoder_forward(self, x, edge_index)
+    def forward(self, x: torch.Tensor, edge_index: torch.Tensor, edge_attr: Optional[torch.Tensor] = None) -> torch.Tensor:
+        return ops.gnn_conn_encoder_forward(self, x, edge_index, edge_attr)
 
 
 class EnhancedTriModalFusionNet(nn.Module):
     """ERP + Power transformer encoders, GNN (``use_gnn``) or MLP connectivity encoder, ERP-queries-all cross
     attention, learned 3-way fusion, BN-MLP classifier (reference :495-657; same child names and state_dict).
-    ``edge_index`` is made from the first batch and kept as a plain attribute (it is not part of the state dict)."""
+    ``edge_index`` is made from the first batch and kept as a plain attribute (it is not part of the state dict).
+    ``gnn_edge_features``: the GNN encoder is built with ``edge_dim=num_conn_types`` and reads every sample's own
+    connectivity strengths as the features of its edges."""
 
     def __init__(self, erp_channels: int, pw_channels: int, num_conn_nodes: int, num_conn_types: int = 3,
                  hidden_dim: int = 128, num_classes: int = 2, dropout: float = 0.3,
-                 num_transformer_layers: int = 2, num_heads: int = 4, use_gnn: bool = True):
+                 num_transformer_layers: int = 2, num_heads: int = 4, use_gnn: bool = True,
+                 gnn_edge_features: bool = False):
         super().__init__()
         self.use_gnn = use_gnn
         self.erp_encoder = EnhancedERPEncoder(erp_channels, hidden_dim, num_transformer_layers, num_heads, dropout)
@@ -262,7 +316,8 @@ class EnhancedTriModalFusionNet(nn.Module):
             return [nn.Linear(i, o), nn.BatchNorm1d(o), nn.GELU(), _drop(dropout)]
         if use_gnn:
             self.conn_encoder = GNNConnectivityEncoder(num_conn_nodes, num_conn_types, hidden_dim, num_gat_layers=2,
-                                                       num_heads=num_heads, dropout=dropout)
+                                                       num_heads=num_heads, dropout=dropout,
+                                                       edge_dim=num_conn_types if gnn_edge_features else None)
         else:
             self.conn_encoder = nn.Sequential(*mlp_bn(num_conn_nodes * num_conn_nodes * num_conn_types, 256),
                                               *mlp_bn(256, hidden_dim))

@@ -1403,11 +1403,21 @@ def conn_encoder_forward(m, x):
 class GatGraph:
     """the graph ``mm_gatv2_fwd`` / ``mm_gatv2_bwd`` read, int32 on the device of the ``edge_index`` it came from:
     CSR by target (``rowptr`` (N + 1), ``col`` (E') = source) and the CSC view of the same edges (``colptr`` (N + 1),
-    ``row`` (E') = target, ``perm`` (E') = CSR position; CSR order within a source)."""
+    ``row`` (E') = target, ``perm`` (E') = CSR position; CSR order within a source).
 
-    def __init__(self, num_nodes, rowptr, col, colptr, row, perm):
+    For edge attributes, whose rows come aligned with the listed ``edge_index`` (``mm_gatv2_edge_pack`` / ``_pack_bwd``):
+    ``eid`` (E') = listed edge of each CSR position, -1 for an appended self-loop; ``indeg`` (N) = in-degree without
+    loops; ``pos`` (E) = CSR position of each listed edge, -1 for a dropped self-loop; ``tgt`` (E) = its target.
+    For attention output in torch_geometric's edge order (the listed non-loop edges, then the N self-loops):
+    ``attn_edge_index`` (2, E') int64 and ``attn_pos`` (E') int64 = the CSR position of each of those edges."""
+
+    def __init__(self, num_nodes, rowptr, col, colptr, row, perm, eid=None, indeg=None, pos=None, tgt=None,
+                 attn_edge_index=None, attn_pos=None):
         self.num_nodes, self.num_edges = int(num_nodes), int(col.numel())
         self.rowptr, self.col, self.colptr, self.row, self.perm = rowptr, col, colptr, row, perm
+        self.eid, self.indeg, self.pos, self.tgt = eid, indeg, pos, tgt
+        self.num_listed = None if pos is None else int(pos.numel())
+        self.attn_edge_index, self.attn_pos = attn_edge_index, attn_pos
 
 
 def _build_gat_graph(edge_index: torch.Tensor, num_nodes: int) -> GatGraph:
@@ -1434,9 +1444,17 @@ def _build_gat_graph(edge_index: torch.Tensor, num_nodes: int) -> GatGraph:
         out = torch.zeros(N + 1, dtype=torch.int64)
         out[1:] = torch.cumsum(torch.bincount(keys, minlength=N), 0)
         return out
+    # edge attributes: listed rows <-> CSR positions
+    kept = keep.nonzero().flatten()
+    eid = torch.cat([kept, torch.full((N,), -1, dtype=torch.int64)])[order]
+    inv = torch.empty_like(order)
+    inv[order] = torch.arange(order.numel())                        # [listed non-loop edges, then loops] -> CSR position
+    pos = torch.full((ei.size(1),), -1, dtype=torch.int64)
+    pos[kept] = inv[:kept.numel()]
+    indeg = torch.bincount(ei[1][keep], minlength=N)
     dev = edge_index.device
-    i32 = [t.to(torch.int32).contiguous().to(dev) for t in (ptr(tgt), col, ptr(col), tgt[perm], perm)]
-    return GatGraph(N, *i32)
+    i32 = [t.to(torch.int32).contiguous().to(dev) for t in (ptr(tgt), col, ptr(col), tgt[perm], perm, eid, indeg, pos, ei[1])]
+    return GatGraph(N, *i32, attn_edge_index=torch.stack([src, dst]).to(dev), attn_pos=inv.to(dev))
 
 
 def gat_graph(edge_index: torch.Tensor, num_nodes: int) -> GatGraph:
@@ -1458,8 +1476,56 @@ def _gat_cat(conv):
     return W, b
 
 
-def gatv2_forward(conv, x: torch.Tensor, graph: GatGraph, act: str = "none") -> torch.Tensor:
-    """inference path of one GATv2Conv layer: x (B, N, in) fp32 -> act(out) (B, N, heads * out_channels)"""
+def _fill_args(fill_value):
+    """(fill_mean, constant) of GATv2EdgeConv's ``fill_value``: 'mean' or a number"""
+    if isinstance(fill_value, str):
+        if fill_value != "mean":
+            raise ValueError(f"GATv2EdgeConv: fill_value must be 'mean' or a number, got '{fill_value}'")
+        return 1, 0.0
+    if isinstance(fill_value, bool) or not isinstance(fill_value, (int, float)):
+        raise ValueError(f"GATv2EdgeConv: fill_value must be 'mean' or a number, got {fill_value!r}")
+    return 0, float(fill_value)
+
+
+def gat_edge_attr(edge_attr, graph: GatGraph, B: int, edge_dim: int) -> torch.Tensor:
+    """``edge_attr`` (E,), (E, D) [shared by the batch] or (B, E, D) [per sample], rows aligned with the listed
+    ``edge_index`` -> (1 | B, E, D).  ValueError, before any launch, for a missing tensor, D outside 1..8 or not the
+    layer's ``edge_dim``, another E than the graph lists or another B than ``x`` has."""
+    if edge_attr is None:
+        raise ValueError(f"GATv2EdgeConv: this layer has edge_dim={edge_dim}, edge_attr is required")
+    if not torch.is_tensor(edge_attr) or not edge_attr.is_floating_point() or edge_attr.dim() not in (1, 2, 3):
+        raise ValueError("GATv2EdgeConv: edge_attr must be a floating-point (E,), (E, D) or (B, E, D) tensor")
+    ea = edge_attr.reshape(1, -1, 1) if edge_attr.dim() == 1 else edge_attr.unsqueeze(0) if edge_attr.dim() == 2 else edge_attr
+    Bo, El, D = ea.shape
+    if not 1 <= D <= 8:
+        raise ValueError(f"GATv2EdgeConv: edge_attr has D={D} features per edge, supported 1..8")
+    if D != edge_dim:
+        raise ValueError(f"GATv2EdgeConv: edge_attr has D={D} features per edge, the layer edge_dim={edge_dim}")
+    if El != graph.num_listed:
+        raise ValueError(f"GATv2EdgeConv: edge_attr has {El} rows, edge_index lists {graph.num_listed} edges")
+    if edge_attr.dim() == 3 and Bo != B:
+        raise ValueError(f"GATv2EdgeConv: edge_attr is for a batch of {Bo}, x for a batch of {B}")
+    return ea
+
+
+def gat_edge_pack(ea: torch.Tensor, graph: GatGraph, fill_value="mean") -> torch.Tensor:
+    """listed attributes (1 | B, E, D) -> CSR order with the self-loop rows filled (1 | B, E', D): ``mm_gatv2_edge_pack``"""
+    fill_mean, fill = _fill_args(fill_value)
+    _need_gpu(ea, graph.col)
+    ea = _f32c(ea)
+    Bo, El, D = ea.shape
+    csr = _empty((Bo, graph.num_edges, D), _F32, ea)
+    _hip.call("mm_gatv2_edge_pack", ea if El else None, graph.eid, graph.rowptr, graph.indeg, csr, Bo, graph.num_nodes,
+              El, graph.num_edges, D, fill_mean, fill)
+    return csr
+
+
+def gatv2_forward(conv, x: torch.Tensor, graph: GatGraph, act: str = "none", ea_csr=None, sink=None) -> torch.Tensor:
+    """inference path of one GATv2Conv / GATv2EdgeConv layer: x (B, N, in) fp32 -> act(out) (B, N, heads * out_channels).
+    ``ea_csr`` (1 | B, E', D): the packed edge attributes of an edge layer; ``sink``: a list that receives the
+    softmax alpha (B, H, E'), CSR order."""
+    if (ea_csr is None) != (getattr(conv, "edge_dim", None) is None):
+        raise ValueError("gatv2_forward: packed edge attributes go with an edge layer (GATv2EdgeConv), and only with one")
     _need_gpu(x, graph.col)
     B, N, F = x.shape
     if N != graph.num_nodes:
@@ -1470,53 +1536,101 @@ def gatv2_forward(conv, x: torch.Tensor, graph: GatGraph, act: str = "none") -> 
         xlr, _ = small_linear(_f32c(x).view(B * N, F), None, weight=W, bias=b)
         out = _empty((B, N, H * C), _F32, x)
         alpha = _empty((B, H, graph.num_edges), _F32, x)
-        _hip.call("mm_gatv2_fwd", xlr, xlr.data_ptr() + 4 * H * C, 2 * H * C, _f32c(conv.att),
-                  None if conv.bias is None else _f32c(conv.bias), graph.rowptr, graph.col, out, None, alpha,
-                  B, N, H, C, graph.num_edges, float(conv.negative_slope), ACT[act], 0.0, 0, None)
+        att, bias = _f32c(conv.att), None if conv.bias is None else _f32c(conv.bias)
+        if ea_csr is None:
+            _hip.call("mm_gatv2_fwd", xlr, xlr.data_ptr() + 4 * H * C, 2 * H * C, att, bias, graph.rowptr, graph.col,
+                      out, None, alpha, B, N, H, C, graph.num_edges, float(conv.negative_slope), ACT[act], 0.0, 0, None)
+        else:
+            _hip.call("mm_gatv2_edge_fwd", xlr, xlr.data_ptr() + 4 * H * C, 2 * H * C, att, bias,
+                      _f32c(conv.lin_edge.weight), ea_csr, int(ea_csr.size(0) != 1), graph.rowptr, graph.col, out, None,
+                      alpha, B, N, H, C, graph.num_edges, ea_csr.size(2), float(conv.negative_slope), ACT[act], 0.0, 0, None)
+    if sink is not None:
+        sink.append(alpha)
     return out
 
 
-def gatv2_conv_forward(conv, x, edge_index):
-    """GATv2Conv.forward: x (N, in) or (B, N, in) -> (N, H*C) / (B, N, H*C); the autograd path in train mode and
-    whenever a gradient can be asked for (the input or a parameter requires one), the inference path otherwise"""
-    _need_gpu(x, edge_index)
+def gat_attention_output(graph: GatGraph, alpha: torch.Tensor):
+    """the softmax alpha (B, H, E') of a layer, CSR order -> (edge_index' (2, E'), alpha (B, E', H)) in torch_geometric's
+    edge order: the listed non-loop edges in listed order, then the N self-loops.  Output formatting: an index copy."""
+    return graph.attn_edge_index, alpha.detach().permute(0, 2, 1)[:, graph.attn_pos].contiguous()
+
+
+def gatv2_conv_forward(conv, x, edge_index, edge_attr=None, return_attention_weights=None):
+    """GATv2Conv / GATv2EdgeConv.forward: x (N, in) or (B, N, in) -> (N, H*C) / (B, N, H*C); the autograd path in train
+    mode and whenever a gradient can be asked for (an input or a parameter requires one), the inference path
+    otherwise.  With ``return_attention_weights`` -> (out, (edge_index', alpha (E', H) / (B, E', H)))."""
     if x.dim() not in (2, 3):
         raise ValueError(f"GATv2Conv: x must be (N, in) or (B, N, in), got {tuple(x.shape)}")
     x3 = x.unsqueeze(0) if x.dim() == 2 else x
     graph = gat_graph(edge_index, x3.size(1))
-    if conv.training or (torch.is_grad_enabled() and (x.requires_grad or any(q.requires_grad for q in conv.parameters()))):
+    edge_dim = getattr(conv, "edge_dim", None)
+    ea = None
+    if edge_dim is not None:                                    # refusals first: they need no GPU
+        ea = gat_edge_attr(edge_attr, graph, x3.size(0), edge_dim)
+        _fill_args(conv.fill_value)
+    _need_gpu(x, edge_index, ea)
+    sink = [] if return_attention_weights else None
+    tape = conv.training or (torch.is_grad_enabled() and (x.requires_grad or (ea is not None and ea.requires_grad)
+                                                          or any(q.requires_grad for q in conv.parameters())))
+    if tape:
         from . import small_autograd as sa
-        out = sa.gatv2(conv, x3, graph, "none", conv.training)
+        if ea is None:
+            out = sa.gatv2(conv, x3, graph, "none", conv.training, sink=sink)
+        else:
+            out = sa.gatv2_edge(conv, x3, graph, sa.gat_edge_pack(ea, graph, conv.fill_value), "none", conv.training, sink=sink)
     else:
-        out = gatv2_forward(conv, x3, graph)
-    return out.squeeze(0) if x.dim() == 2 else out
+        out = gatv2_forward(conv, x3, graph, ea_csr=None if ea is None else gat_edge_pack(ea, graph, conv.fill_value), sink=sink)
+    out = out.squeeze(0) if x.dim() == 2 else out
+    if not return_attention_weights:
+        return out
+    ei, alpha = gat_attention_output(graph, sink[0])
+    return out, (ei, alpha.squeeze(0) if x.dim() == 2 else alpha)
 
 
-def gnn_conn_encoder_forward(m, x, edge_index):
+def gnn_conn_encoder_forward(m, x, edge_index, edge_attr=None, attn_sink=None):
     """GNNConnectivityEncoder.forward (enhanced_models_v4.py:367-413): node_proj per node row -> GATv2 + GELU layers ->
     mean over nodes -> output_proj.  The reference applies node_proj sample by sample, so in train mode its
     BatchNorm1d takes statistics over the N nodes of ONE sample and updates the running statistics B times in
-    sequence: kept, as a loop over samples (the GAT layers run the whole batch per launch)."""
-    _need_gpu(x, edge_index)
+    sequence: kept, as a loop over samples (the GAT layers run the whole batch per launch).
+    With ``edge_dim``: the layers take ``edge_attr``, or - without one - every sample's own connectivity
+    ea[b, e, :] = x[b, source e, target e, :] (plain indexing: on the tape the gradient reaches ``x`` through it too).
+    ``attn_sink``: a list that receives every layer's softmax alpha (B, H, E'), CSR order."""
     B, N = x.size(0), m.num_nodes
-    x = x.reshape(B, N, -1)
     graph = gat_graph(edge_index, N)
+    edge_dim = getattr(m, "edge_dim", None)
+    ea = None
+    if edge_dim is not None:
+        if edge_attr is None:
+            if x.dim() != 4 or tuple(x.shape[1:]) != (N, N, edge_dim):
+                raise ValueError(f"GNNConnectivityEncoder: edge features from the connectivity itself need x of shape "
+                                 f"(B, {N}, {N}, {edge_dim}) [edge_dim == connectivity types], got {tuple(x.shape)}")
+            edge_attr = x[:, edge_index[0], edge_index[1], :]
+        ea = gat_edge_attr(edge_attr, graph, B, edge_dim)
+    elif edge_attr is not None:
+        raise ValueError("GNNConnectivityEncoder: edge_attr needs an encoder built with edge_dim")
+    _need_gpu(x, edge_index, ea)
+    x = x.reshape(B, N, -1)
     lin, bn = m.node_proj[0], m.node_proj[1]
-    if m.training or attribution_active() or (torch.is_grad_enabled() and x.requires_grad):
+    if m.training or attribution_active() or (torch.is_grad_enabled() and (x.requires_grad or (ea is not None and ea.requires_grad))):
         from . import small_autograd as sa
         p, fz = (m.drop_p, False) if m.training else (0.0, True)   # eval on the tape: frozen BatchNorm, no dropout
         if m.training:
             h = torch.stack([sa.linear_bn_act(x[i], lin, bn, "gelu", p) for i in range(B)], dim=0)
         else:
             h = sa.linear_bn_act(x.reshape(B * N, -1), lin, bn, "gelu", 0.0, frozen=True).view(B, N, -1)
+        ea_csr = None if ea is None else sa.gat_edge_pack(ea, graph, "mean")          # once, for every layer
         for conv in m.gat_layers:
-            h = sa.gatv2(conv, h, graph, "gelu", m.training)
+            if ea is None:
+                h = sa.gatv2(conv, h, graph, "gelu", m.training, sink=attn_sink)
+            else:
+                h = sa.gatv2_edge(conv, h, graph, ea_csr, "gelu", m.training, sink=attn_sink)
         return sa.linear_bn_act(sa.MeanRowsFn.apply(h), m.output_proj[0], m.output_proj[1], "gelu", p, frozen=fz)
     with torch.no_grad():
         h, _ = small_linear(_f32c(x).view(B * N, -1), lin, act="gelu", bn=bn)
         h = h.view(B, N, -1)
+        ea_csr = None if ea is None else gat_edge_pack(ea, graph, "mean")
         for conv in m.gat_layers:
-            h = gatv2_forward(conv, h, graph, "gelu")
+            h = gatv2_forward(conv, h, graph, "gelu", ea_csr=ea_csr, sink=attn_sink)
         pooled = _empty((B, h.shape[2]), _F32, h)
         _hip.call("mm_meanpool_fwd", h, pooled, None, B, N, h.shape[2])
         out, _ = small_linear(pooled, m.output_proj[0], act="gelu", bn=m.output_proj[1])

@@ -463,10 +463,11 @@ class FocalLossFn(torch.autograd.Function):
 class GATv2Fn(torch.autograd.Function):
     """one GATv2 layer over a static graph (``mm_gatv2_fwd`` / ``mm_gatv2_bwd``): xlr (B, N, 2 H C) = the node
     features through W_l | W_r -> act(out) (B, N, H C).  Saved: xlr, the softmax alpha (B, H, E') and, under an
-    activation epilogue, the pre-activation; the dropout mask is recomputed from its seed."""
+    activation epilogue, the pre-activation; the dropout mask is recomputed from its seed.  ``sink``: a list that
+    receives alpha (for ``return_attention_weights``; readers take a copy)."""
 
     @staticmethod
-    def forward(ctx, xlr, att, bias, graph, H, C, slope, act, drop_p):
+    def forward(ctx, xlr, att, bias, graph, H, C, slope, act, drop_p, sink=None):
         xlr = _f(xlr)
         B, N, _ = xlr.shape
         HC, E = H * C, graph.num_edges
@@ -479,6 +480,8 @@ class GATv2Fn(torch.autograd.Function):
         ctx.save_for_backward(xlr, alpha, pre)
         ctx.att, ctx.bias, ctx.graph = att, bias, graph
         ctx.meta = (H, C, float(slope), act, float(drop_p), seed)
+        if sink is not None:
+            sink.append(alpha)
         return out
 
     @staticmethod
@@ -496,7 +499,78 @@ class GATv2Fn(torch.autograd.Function):
         _hip.call("mm_gatv2_bwd", _f(dout), pre, xlr, xlr.data_ptr() + 4 * HC, 2 * HC, att, alpha, g.rowptr, g.col,
                   g.colptr, g.row, g.perm, dxlr, dxlr.data_ptr() + 4 * HC, bag.target(att), bag.target(bias), ds, dz,
                   part, B, N, H, C, E, slope, ACT[act], p, seed, ops.EP())
-        return dxlr, bag.result(att), (bag.result(bias) if bias is not None else None), None, None, None, None, None, None
+        return dxlr, bag.result(att), (bag.result(bias) if bias is not None else None), None, None, None, None, None, None, None
+
+
+class GatEdgePackFn(torch.autograd.Function):
+    """listed edge attributes (1 | B, E, D) -> CSR order with the self-loop rows filled (1 | B, E', D)
+    (``mm_gatv2_edge_pack``); the backward is the gather ``mm_gatv2_edge_pack_bwd``."""
+
+    @staticmethod
+    def forward(ctx, ea, graph, fill_value):
+        ctx.graph, ctx.fill_mean, ctx.shape = graph, ops._fill_args(fill_value)[0], tuple(ea.shape)
+        return ops.gat_edge_pack(ea, graph, fill_value)
+
+    @staticmethod
+    def backward(ctx, dcsr):
+        g = ctx.graph
+        Bo, El, D = ctx.shape
+        dl = _empty((Bo, El, D), _F32, dcsr)
+        _hip.call("mm_gatv2_edge_pack_bwd", _f(dcsr), g.pos if El else None, g.tgt if El else None, g.rowptr, g.indeg,
+                  dl if El else None, Bo, g.num_nodes, El, g.num_edges, D, ctx.fill_mean)
+        return dl, None, None
+
+
+def gat_edge_pack(ea, graph, fill_value="mean"):
+    return GatEdgePackFn.apply(ea, graph, fill_value)
+
+
+class GATv2EdgeFn(torch.autograd.Function):
+    """``GATv2Fn`` with edge features in the score (``mm_gatv2_edge_fwd`` / ``mm_gatv2_edge_bwd``): ``w_edge`` (H C, D) =
+    lin_edge.weight, ``ea`` (1 | B, E', D) the packed attributes (``GatEdgePackFn``).  d ea is formed only when asked for."""
+
+    @staticmethod
+    def forward(ctx, xlr, att, bias, w_edge, ea, graph, H, C, slope, act, drop_p, sink=None):
+        xlr, ea = _f(xlr), _f(ea)
+        B, N, _ = xlr.shape
+        HC, E, D = H * C, graph.num_edges, ea.shape[2]
+        seed = ops._next_seed() if drop_p > 0 else 0
+        out = _empty((B, N, HC), _F32, xlr)
+        pre = _empty((B, N, HC), _F32, xlr) if act != "none" else None
+        alpha = _empty((B, H, E), _F32, xlr)
+        _hip.call("mm_gatv2_edge_fwd", xlr, xlr.data_ptr() + 4 * HC, 2 * HC, att, bias, w_edge, ea, int(ea.shape[0] != 1),
+                  graph.rowptr, graph.col, out, pre, alpha, B, N, H, C, E, D, float(slope), ACT[act], float(drop_p), seed,
+                  ops.EP())
+        ctx.save_for_backward(xlr, alpha, pre, ea)
+        ctx.att, ctx.bias, ctx.w_edge, ctx.graph = att, bias, w_edge, graph
+        ctx.meta = (H, C, float(slope), act, float(drop_p), seed)
+        if sink is not None:
+            sink.append(alpha)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        xlr, alpha, pre, ea = ctx.saved_tensors
+        H, C, slope, act, p, seed = ctx.meta
+        g, att, bias, w_edge = ctx.graph, ctx.att, ctx.bias, ctx.w_edge
+        B, N, _ = xlr.shape
+        HC, E = H * C, g.num_edges
+        Bo, _, D = ea.shape
+        dxlr = torch.empty_like(xlr)
+        ds = _empty((B, H, E), _F32, xlr)
+        dz = _empty((B, N, HC), _F32, xlr) if act != "none" else None
+        part = _empty((B, 2, HC), _F32, xlr)
+        wpart = _empty((B, HC, D), _F32, xlr)
+        dea = epart = None
+        if ctx.needs_input_grad[4]:
+            dea, epart = torch.empty_like(ea), _empty((B, H, E, D), _F32, xlr)
+        bag = GradBag()
+        _hip.call("mm_gatv2_edge_bwd", _f(dout), pre, xlr, xlr.data_ptr() + 4 * HC, 2 * HC, att, w_edge, ea, int(Bo != 1),
+                  alpha, g.rowptr, g.col, g.colptr, g.row, g.perm, dxlr, dxlr.data_ptr() + 4 * HC, bag.target(att),
+                  bag.target(bias), bag.target(w_edge), dea, ds, dz, part, wpart, epart, B, N, H, C, E, D, slope, ACT[act],
+                  p, seed, ops.EP())
+        return (dxlr, bag.result(att), (bag.result(bias) if bias is not None else None), bag.result(w_edge), dea,
+                None, None, None, None, None, None, None)
 
 
 class MeanRowsFn(torch.autograd.Function):
@@ -519,16 +593,27 @@ class MeanRowsFn(torch.autograd.Function):
         return dx
 
 
-def gatv2(conv, x, graph, act="none", training: bool = False):
+def gatv2(conv, x, graph, act="none", training: bool = False, sink=None):
     """GATv2Conv on (B, N, in) rows, differentiable: both linears as one ``SmallLinearFn`` with W_l | W_r stacked,
-    then ``GATv2Fn`` (``act`` = its epilogue; attention dropout only when ``training``)"""
+    then ``GATv2Fn`` (``act`` = its epilogue; attention dropout only when ``training``; ``sink`` receives alpha)"""
     B, N, K = x.shape
     if N != graph.num_nodes:
         raise ValueError(f"gatv2: x has {N} nodes, the graph {graph.num_nodes}")
     W, b = ops._gat_cat(conv)
     xlr = SmallLinearFn.apply(x.reshape(B * N, K), W, b, "none", 0.0)
     return GATv2Fn.apply(xlr.view(B, N, -1), conv.att, conv.bias, graph, conv.heads, conv.out_channels,
-                         float(conv.negative_slope), act, float(conv.dropout) if training else 0.0)
+                         float(conv.negative_slope), act, float(conv.dropout) if training else 0.0, sink)
+
+
+def gatv2_edge(conv, x, graph, ea_csr, act="none", training: bool = False, sink=None):
+    """GATv2EdgeConv on (B, N, in) rows with the packed attributes ``ea_csr`` (1 | B, E', D), differentiable"""
+    B, N, K = x.shape
+    if N != graph.num_nodes:
+        raise ValueError(f"gatv2_edge: x has {N} nodes, the graph {graph.num_nodes}")
+    W, b = ops._gat_cat(conv)
+    xlr = SmallLinearFn.apply(x.reshape(B * N, K), W, b, "none", 0.0)
+    return GATv2EdgeFn.apply(xlr.view(B, N, -1), conv.att, conv.bias, conv.lin_edge.weight, ea_csr, graph, conv.heads,
+                             conv.out_channels, float(conv.negative_slope), act, float(conv.dropout) if training else 0.0, sink)
 
 
 def proj_head(x, seq, drop_p):

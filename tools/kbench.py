@@ -501,8 +501,8 @@ def xai_case(B=32, C=64, T=1024, vol=(32, 32, 32), n_steps=50, rounds=5):
 
 
 def gat_case(B=32, N=64, H=4, C=32, dense=True):
-    """one GATv2 layer (csrc/gnn.hip) on the all-pairs graph, forward and backward, the W_l | W_r linear beside it, and
-    a GNNConnectivityEncoder eval forward for the whole batch vs one sample per call (the reference's loop shape)"""
+    """one GATv2 layer (csrc/gnn.hip) on the all-pairs graph, forward and backward, the W_l | W_r linear beside it, the
+    edge variant at D = 1 and D = 3 with its ratio to the plain kernels, and a GNNConnectivityEncoder eval forward for the whole batch vs one sample per call (the reference's loop shape)"""
     import multimodal_eeg_fmri_amd.enhanced_models_v4 as E
     adj = ~torch.eye(N, dtype=torch.bool) if dense else torch.rand(N, N) < 0.1
     ei = adj.nonzero().t().contiguous().cuda()
@@ -540,11 +540,43 @@ def gat_case(B=32, N=64, H=4, C=32, dense=True):
     rows = B * N * HC * 4
     fb = 2 * rows + 2 * rows + B * H * Eg * 4                        # xl, xr in; out, pre out; alpha out
     bb = 2 * rows + 2 * rows + 2 * rows + 2 * rows + 3 * B * H * Eg * 4   # xl, xr, dout, pre in; dz, dxl, dxr out (+ dz back in); alpha in, ds out + in
+    plain = {}
     for name, fn, nbytes in (("linear W_l|W_r fwd", lin_f, B * N * 3 * HC * 4), ("gatv2 fwd p=0", fwd, fb),
                              ("gatv2 fwd p=0.3", lambda: fwd(0.3), fb), ("gatv2 bwd p=0", bwd, bb),
                              ("gatv2 bwd p=0.3", lambda: bwd(0.3), bb), ("linear W_l|W_r bwd", lin_b, B * N * 4 * HC * 4)):
         us = timeit(fn)
+        plain[name] = us
         print(f"{tag} {name:22s}: {us:8.1f} us   {nbytes / 1e6:6.2f} MB moved  {nbytes / us / 1e3:7.1f} GB/s")
+    # edge variant (mm_gatv2_edge_*): per-sample attributes, D raw features per edge projected inside the score loop
+    for D in (1, 3):
+        we = torch.randn(HC, D, device="cuda") / math.sqrt(D)
+        listed = torch.randn(B, ei.shape[1], D, device="cuda")
+        ea, dea, dlisted = torch.empty(B, Eg, D, device="cuda"), torch.empty(B, Eg, D, device="cuda"), torch.empty_like(listed)
+        dwe, wpart, epart = torch.zeros_like(we), torch.empty(B, HC, D, device="cuda"), torch.empty(B, H, Eg, D, device="cuda")
+
+        def pack():
+            _hip.call("mm_gatv2_edge_pack", listed, g.eid, g.rowptr, g.indeg, ea, B, N, ei.shape[1], Eg, D, 1, 0.0)
+
+        def pack_b():
+            _hip.call("mm_gatv2_edge_pack_bwd", dea, g.pos, g.tgt, g.rowptr, g.indeg, dlisted, B, N, ei.shape[1], Eg, D, 1)
+
+        def efwd():
+            _hip.call("mm_gatv2_edge_fwd", xlr, xr, 2 * HC, att, bias, we, ea, 1, g.rowptr, g.col, out, pre, alpha, B, N, H, C,
+                      Eg, D, 0.2, act, 0.0, 7, None)
+
+        def ebwd(with_dea=True):
+            _hip.call("mm_gatv2_edge_bwd", dout, pre, xlr, xr, 2 * HC, att, we, ea, 1, alpha, g.rowptr, g.col, g.colptr, g.row,
+                      g.perm, dxlr, dxr, datt, dbias, dwe, dea if with_dea else None, ds, dz, part, wpart,
+                      epart if with_dea else None, B, N, H, C, Eg, D, 0.2, act, 0.0, 7, None)
+        pack()
+        eb = B * Eg * D * 4
+        for name, fn, nbytes, ref in ((f"edge D={D} pack", pack, 2 * eb, None), (f"edge D={D} fwd p=0", efwd, fb + eb, "gatv2 fwd p=0"),
+                                      (f"edge D={D} bwd p=0", ebwd, bb + 3 * eb + 2 * H * eb, "gatv2 bwd p=0"),
+                                      (f"edge D={D} bwd no d ea", lambda: ebwd(False), bb + 2 * eb, "gatv2 bwd p=0"),
+                                      (f"edge D={D} pack bwd", pack_b, 2 * eb, None)):
+            us = timeit(fn)
+            ratio = f"  {us / plain[ref]:5.2f} x plain" if ref else ""
+            print(f"{tag} {name:22s}: {us:8.1f} us   {nbytes / 1e6:6.2f} MB moved  {nbytes / us / 1e3:7.1f} GB/s{ratio}")
     enc = E.GNNConnectivityEncoder(num_nodes=N, num_conn_types=3, hidden_dim=HC, num_heads=H).cuda().eval()
     conn = torch.rand(B, N, N, 3, device="cuda")
     with torch.no_grad():
