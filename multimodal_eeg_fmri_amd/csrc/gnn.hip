@@ -428,35 +428,74 @@ __global__ void gatv2_edge_pack_bwd_kernel(const float* __restrict__ dcsr, const
     dlisted[(size_t)blockIdx.y * El * D + idx] = v;
 }
 
-int gat_check(const char* who, int B, int N, int H, int C, int E, int ld, int act, float drop_p) {
+// the fields every entry point fills; the callers add their own outputs and workspaces
+GatArgs gat_args(const float* xl, const float* xr, int ld, const float* att, const float* w_edge, const float* edge_attr,
+                 int ea_batched, const int* rowptr, const int* col, int B, int N, int H, int C, int E, int D, float slope,
+                 int act, float drop_p, uint32_t seed, const uint32_t* seed_epoch) {
+    GatArgs a{};
+    a.xl = xl; a.xr = xr; a.ld = ld; a.att = att; a.rowptr = rowptr; a.col = col;
+    a.B = B; a.N = N; a.H = H; a.C = C; a.E = E; a.slope = slope; a.act = act;
+    a.thresh = drop_p > 0.f ? (uint32_t)((double)drop_p * 4294967296.0) : 0u;
+    a.seed = seed; a.inv_keep = drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f; a.epoch = seed_epoch;
+    a.we = w_edge; a.ea = edge_attr; a.ea_bs = ea_batched ? (size_t)E * D : 0; a.D = D;
+    return a;
+}
+
+// The one place the dynamic LDS of the two kernels is priced (in floats).  It follows their pointer arithmetic:
+//   edge variant, in front:  forward  xs = smem + C * DP                       the We slice
+//                            backward xs = smem + (C + 64 * GAT_WAVES) * DP    the We slice + every wave's attribute stage
+//   then xs [N][C + 1], atts [C], backward only: red (512), and 256 words per wave (the 512 + GAT_WAVES * 256 tail)
+constexpr size_t gat_lds_floats(int N, int C, int DP, bool bwd) {
+    return (size_t)(bwd ? C + 64 * GAT_WAVES : C) * DP + (size_t)N * (C + 1) + C + (bwd ? 512 : 0) + GAT_WAVES * 256;
+}
+
+using GatKernel = void (*)(GatArgs);
+
+// the one (C, DP) dispatch over the 3 x 5 instantiations of either kernel
+template <bool BWD, int C, int DP> GatKernel gat_kernel_of() {
+    if constexpr (BWD) return gatv2_bwd_kernel<C, DP>;
+    else return gatv2_fwd_kernel<C, DP>;
+}
+
+template <bool BWD, int DP> GatKernel gat_kernel_c(int C) {
+    return C == 16 ? gat_kernel_of<BWD, 16, DP>() : C == 32 ? gat_kernel_of<BWD, 32, DP>() : gat_kernel_of<BWD, 64, DP>();
+}
+
+template <bool BWD> GatKernel gat_kernel(int C, int DP) {
+    switch (DP) {
+        case 0: return gat_kernel_c<BWD, 0>(C);
+        case 1: return gat_kernel_c<BWD, 1>(C);
+        case 2: return gat_kernel_c<BWD, 2>(C);
+        case 4: return gat_kernel_c<BWD, 4>(C);
+        default: return gat_kernel_c<BWD, 8>(C);
+    }
+}
+
+// The shared path of the four entry points; w_edge == nullptr, D = 0: the plain layer (DP = D rounded up to 1, 2, 4 or 8).
+// Backward: the kernel, then the batch sums of the parameter gradients and, where asked for, the head sums of d ea.
+int gat_run(const char* who, const GatArgs& a, float drop_p, bool bwd, hipStream_t st, float* datt = nullptr,
+            float* dbias = nullptr, float* dw_edge = nullptr, float* dedge_attr = nullptr) {
+    const int B = a.B, N = a.N, H = a.H, C = a.C, E = a.E, D = a.D, HC = H * C;
     MM_REQUIRE(B > 0 && H > 0, "%s: B=%d H=%d", who, B, H);
     MM_REQUIRE(N >= 1 && N <= 128, "%s: N=%d outside [1, 128]", who, N);
     MM_REQUIRE(C == 16 || C == 32 || C == 64, "%s: C=%d is not 16, 32 or 64", who, C);
-    MM_REQUIRE(H * C <= 256, "%s: H*C=%d above 256", who, H * C);
+    MM_REQUIRE(HC <= 256, "%s: H*C=%d above 256", who, HC);
     MM_REQUIRE(E >= N, "%s: E=%d edges for N=%d nodes (every node carries a self-loop)", who, E, N);
     MM_REQUIRE((unsigned long long)B * H * (unsigned long long)E < (1ull << 32), "%s: B*H*E does not fit the 32-bit mask index", who);
-    MM_REQUIRE(ld >= H * C, "%s: ld=%d below H*C=%d", who, ld, H * C);
-    MM_REQUIRE(act >= MM_ACT_NONE && act <= MM_ACT_SIGMOID, "%s: act=%d", who, act);
+    MM_REQUIRE(a.ld >= HC, "%s: ld=%d below H*C=%d", who, a.ld, HC);
+    MM_REQUIRE(a.act >= MM_ACT_NONE && a.act <= MM_ACT_SIGMOID, "%s: act=%d", who, a.act);
     MM_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "%s: drop_p=%f", who, (double)drop_p);
-    return MM_OK;
-}
-
-inline uint32_t gat_thresh(float p) { return p > 0.f ? (uint32_t)((double)p * 4294967296.0) : 0u; }
-
-inline int gat_dp(int D) { return D <= 2 ? D : D <= 4 ? 4 : 8; }
-
-template <int DP> void launch_fwd(const GatArgs& a, size_t lds, hipStream_t st) {
-    const dim3 grid(a.B * a.H), block(64 * GAT_WAVES);
-    if (a.C == 16) hipLaunchKernelGGL((gatv2_fwd_kernel<16, DP>), grid, block, lds, st, a);
-    else if (a.C == 32) hipLaunchKernelGGL((gatv2_fwd_kernel<32, DP>), grid, block, lds, st, a);
-    else hipLaunchKernelGGL((gatv2_fwd_kernel<64, DP>), grid, block, lds, st, a);
-}
-
-template <int DP> void launch_bwd(const GatArgs& a, size_t lds, hipStream_t st) {
-    const dim3 grid(a.B * a.H), block(64 * GAT_WAVES);
-    if (a.C == 16) hipLaunchKernelGGL((gatv2_bwd_kernel<16, DP>), grid, block, lds, st, a);
-    else if (a.C == 32) hipLaunchKernelGGL((gatv2_bwd_kernel<32, DP>), grid, block, lds, st, a);
-    else hipLaunchKernelGGL((gatv2_bwd_kernel<64, DP>), grid, block, lds, st, a);
+    MM_REQUIRE(!a.we || (D >= 1 && D <= 8), "%s: D=%d outside [1, 8]", who, D);
+    MM_REQUIRE(!bwd || a.act == MM_ACT_NONE || (a.pre && a.dz), "%s: an activation epilogue needs pre and dz_ws", who);
+    MM_REQUIRE(!dedge_attr || a.dea, "%s: dedge_attr needs epart_ws", who);
+    const int DP = D <= 2 ? D : D <= 4 ? 4 : 8, Bo = a.ea_bs ? B : 1;
+    const GatKernel k = !bwd ? gat_kernel<false>(C, DP) : gat_kernel<true>(C, DP);
+    hipLaunchKernelGGL(k, dim3(B * H), dim3(64 * GAT_WAVES), gat_lds_floats(N, C, DP, bwd) * sizeof(float), st, a);
+    if (datt || dbias) hipLaunchKernelGGL(gatv2_param_grads_kernel, dim3(1), dim3(256), 0, st, a.part, datt, dbias, B, HC);
+    if (dw_edge) hipLaunchKernelGGL(gatv2_edge_wgrad_kernel, dim3((HC * D + 255) / 256), dim3(256), 0, st, a.pwe, dw_edge, B, HC * D);
+    if (dedge_attr)
+        hipLaunchKernelGGL(gatv2_edge_dea_kernel, dim3((E * D + 255) / 256, Bo), dim3(256), 0, st, a.dea, dedge_attr, B, Bo, H, E * D);
+    return mm_check_launch(who);
 }
 
 }  // namespace
@@ -467,14 +506,9 @@ int mm_gatv2_fwd(const float* xl, const float* xr, int ld, const float* att, con
                  const int* col, float* out, float* pre, float* alpha, int B, int N, int H, int C, int E,
                  float slope, int act, float drop_p, uint32_t seed, const uint32_t* seed_epoch, hipStream_t st) {
     MM_REQUIRE(xl && xr && att && rowptr && col && out && alpha, "gatv2_fwd: null pointer");
-    if (int rc = gat_check("gatv2_fwd", B, N, H, C, E, ld, act, drop_p)) return rc;
-    GatArgs a{};
-    a.xl = xl; a.xr = xr; a.ld = ld; a.att = att; a.bias = bias; a.rowptr = rowptr; a.col = col;
-    a.out = out; a.pre = pre; a.alpha = alpha;
-    a.B = B; a.N = N; a.H = H; a.C = C; a.E = E; a.slope = slope; a.act = act;
-    a.thresh = gat_thresh(drop_p); a.seed = seed; a.inv_keep = drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f; a.epoch = seed_epoch;
-    launch_fwd<0>(a, ((size_t)N * (C + 1) + C + GAT_WAVES * 256) * sizeof(float), st);
-    return mm_check_launch("gatv2_fwd");
+    GatArgs a = gat_args(xl, xr, ld, att, nullptr, nullptr, 0, rowptr, col, B, N, H, C, E, 0, slope, act, drop_p, seed, seed_epoch);
+    a.bias = bias; a.out = out; a.pre = pre; a.alpha = alpha;
+    return gat_run("gatv2_fwd", a, drop_p, false, st);
 }
 
 int mm_gatv2_edge_fwd(const float* xl, const float* xr, int ld, const float* att, const float* bias,
@@ -482,21 +516,10 @@ int mm_gatv2_edge_fwd(const float* xl, const float* xr, int ld, const float* att
                       float* out, float* pre, float* alpha, int B, int N, int H, int C, int E, int D, float slope,
                       int act, float drop_p, uint32_t seed, const uint32_t* seed_epoch, hipStream_t st) {
     MM_REQUIRE(xl && xr && att && w_edge && edge_attr && rowptr && col && out && alpha, "gatv2_edge_fwd: null pointer");
-    if (int rc = gat_check("gatv2_edge_fwd", B, N, H, C, E, ld, act, drop_p)) return rc;
-    MM_REQUIRE(D >= 1 && D <= 8, "gatv2_edge_fwd: D=%d outside [1, 8]", D);
-    GatArgs a{};
-    a.xl = xl; a.xr = xr; a.ld = ld; a.att = att; a.bias = bias; a.rowptr = rowptr; a.col = col;
-    a.out = out; a.pre = pre; a.alpha = alpha;
-    a.B = B; a.N = N; a.H = H; a.C = C; a.E = E; a.slope = slope; a.act = act;
-    a.thresh = gat_thresh(drop_p); a.seed = seed; a.inv_keep = drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f; a.epoch = seed_epoch;
-    a.we = w_edge; a.ea = edge_attr; a.ea_bs = ea_batched ? (size_t)E * D : 0; a.D = D;
-    const int DP = gat_dp(D);
-    const size_t lds = ((size_t)N * (C + 1) + C + GAT_WAVES * 256 + C * DP) * sizeof(float);
-    if (DP == 1) launch_fwd<1>(a, lds, st);
-    else if (DP == 2) launch_fwd<2>(a, lds, st);
-    else if (DP == 4) launch_fwd<4>(a, lds, st);
-    else launch_fwd<8>(a, lds, st);
-    return mm_check_launch("gatv2_edge_fwd");
+    GatArgs a = gat_args(xl, xr, ld, att, w_edge, edge_attr, ea_batched, rowptr, col, B, N, H, C, E, D, slope, act, drop_p, seed,
+                         seed_epoch);
+    a.bias = bias; a.out = out; a.pre = pre; a.alpha = alpha;
+    return gat_run("gatv2_edge_fwd", a, drop_p, false, st);
 }
 
 int mm_gatv2_bwd(const float* dout, const float* pre, const float* xl, const float* xr, int ld, const float* att,
@@ -506,18 +529,10 @@ int mm_gatv2_bwd(const float* dout, const float* pre, const float* xl, const flo
                  uint32_t seed, const uint32_t* seed_epoch, hipStream_t st) {
     MM_REQUIRE(dout && xl && xr && att && alpha && rowptr && col && colptr && row && perm && dxl && dxr && ds_ws && part_ws,
                "gatv2_bwd: null pointer");
-    if (int rc = gat_check("gatv2_bwd", B, N, H, C, E, ld, act, drop_p)) return rc;
-    MM_REQUIRE(act == MM_ACT_NONE || (pre && dz_ws), "gatv2_bwd: an activation epilogue needs pre and dz_ws");
-    GatArgs a{};
-    a.xl = xl; a.xr = xr; a.ld = ld; a.att = att; a.rowptr = rowptr; a.col = col; a.colptr = colptr; a.row = row; a.perm = perm;
-    a.pre = const_cast<float*>(pre); a.alpha = const_cast<float*>(alpha); a.dout = dout; a.dxl = dxl; a.dxr = dxr;
-    a.ds = ds_ws; a.dz = dz_ws; a.part = part_ws;
-    a.B = B; a.N = N; a.H = H; a.C = C; a.E = E; a.slope = slope; a.act = act;
-    a.thresh = gat_thresh(drop_p); a.seed = seed; a.inv_keep = drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f; a.epoch = seed_epoch;
-    launch_bwd<0>(a, ((size_t)N * (C + 1) + C + 512 + GAT_WAVES * 256) * sizeof(float), st);
-    if (datt || dbias)
-        hipLaunchKernelGGL(gatv2_param_grads_kernel, dim3(1), dim3(256), 0, st, part_ws, datt, dbias, B, H * C);
-    return mm_check_launch("gatv2_bwd");
+    GatArgs a = gat_args(xl, xr, ld, att, nullptr, nullptr, 0, rowptr, col, B, N, H, C, E, 0, slope, act, drop_p, seed, seed_epoch);
+    a.colptr = colptr; a.row = row; a.perm = perm; a.pre = const_cast<float*>(pre); a.alpha = const_cast<float*>(alpha);
+    a.dout = dout; a.dxl = dxl; a.dxr = dxr; a.ds = ds_ws; a.dz = dz_ws; a.part = part_ws;
+    return gat_run("gatv2_bwd", a, drop_p, true, st, datt, dbias);
 }
 
 int mm_gatv2_edge_bwd(const float* dout, const float* pre, const float* xl, const float* xr, int ld, const float* att,
@@ -529,33 +544,12 @@ int mm_gatv2_edge_bwd(const float* dout, const float* pre, const float* xl, cons
                       const uint32_t* seed_epoch, hipStream_t st) {
     MM_REQUIRE(dout && xl && xr && att && w_edge && edge_attr && alpha && rowptr && col && colptr && row && perm && dxl &&
                dxr && ds_ws && part_ws && wpart_ws, "gatv2_edge_bwd: null pointer");
-    if (int rc = gat_check("gatv2_edge_bwd", B, N, H, C, E, ld, act, drop_p)) return rc;
-    MM_REQUIRE(D >= 1 && D <= 8, "gatv2_edge_bwd: D=%d outside [1, 8]", D);
-    MM_REQUIRE(act == MM_ACT_NONE || (pre && dz_ws), "gatv2_edge_bwd: an activation epilogue needs pre and dz_ws");
-    MM_REQUIRE(!dedge_attr || epart_ws, "gatv2_edge_bwd: dedge_attr needs epart_ws");
-    GatArgs a{};
-    a.xl = xl; a.xr = xr; a.ld = ld; a.att = att; a.rowptr = rowptr; a.col = col; a.colptr = colptr; a.row = row; a.perm = perm;
-    a.pre = const_cast<float*>(pre); a.alpha = const_cast<float*>(alpha); a.dout = dout; a.dxl = dxl; a.dxr = dxr;
-    a.ds = ds_ws; a.dz = dz_ws; a.part = part_ws;
-    a.B = B; a.N = N; a.H = H; a.C = C; a.E = E; a.slope = slope; a.act = act;
-    a.thresh = gat_thresh(drop_p); a.seed = seed; a.inv_keep = drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f; a.epoch = seed_epoch;
-    a.we = w_edge; a.ea = edge_attr; a.ea_bs = ea_batched ? (size_t)E * D : 0; a.D = D;
+    GatArgs a = gat_args(xl, xr, ld, att, w_edge, edge_attr, ea_batched, rowptr, col, B, N, H, C, E, D, slope, act, drop_p, seed,
+                         seed_epoch);
+    a.colptr = colptr; a.row = row; a.perm = perm; a.pre = const_cast<float*>(pre); a.alpha = const_cast<float*>(alpha);
+    a.dout = dout; a.dxl = dxl; a.dxr = dxr; a.ds = ds_ws; a.dz = dz_ws; a.part = part_ws;
     a.dea = dedge_attr ? epart_ws : nullptr; a.pwe = wpart_ws;
-    const int DP = gat_dp(D);
-    const size_t lds = ((size_t)N * (C + 1) + C + 512 + GAT_WAVES * 256 + (C + 64 * GAT_WAVES) * DP) * sizeof(float);
-    if (DP == 1) launch_bwd<1>(a, lds, st);
-    else if (DP == 2) launch_bwd<2>(a, lds, st);
-    else if (DP == 4) launch_bwd<4>(a, lds, st);
-    else launch_bwd<8>(a, lds, st);
-    if (datt || dbias)
-        hipLaunchKernelGGL(gatv2_param_grads_kernel, dim3(1), dim3(256), 0, st, part_ws, datt, dbias, B, H * C);
-    if (dw_edge)
-        hipLaunchKernelGGL(gatv2_edge_wgrad_kernel, dim3((H * C * D + 255) / 256), dim3(256), 0, st, wpart_ws, dw_edge, B,
-                           H * C * D);
-    if (dedge_attr)
-        hipLaunchKernelGGL(gatv2_edge_dea_kernel, dim3((E * D + 255) / 256, ea_batched ? B : 1), dim3(256), 0, st, epart_ws,
-                           dedge_attr, B, ea_batched ? B : 1, H, E * D);
-    return mm_check_launch("gatv2_edge_bwd");
+    return gat_run("gatv2_edge_bwd", a, drop_p, true, st, datt, dbias, dw_edge, dedge_attr);
 }
 
 int mm_gatv2_edge_pack(const float* listed, const int* eid, const int* rowptr, const int* indeg, float* csr, int Bo,

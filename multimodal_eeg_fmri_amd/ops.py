@@ -1476,6 +1476,12 @@ def _gat_cat(conv):
     return W, b
 
 
+def _gat_edge_args(w_edge, ea_csr):
+    """what an ``mm_gatv2_edge_*`` call takes beyond its plain twin: ((w_edge, edge_attr, ea_batched), (D,)); a plain
+    layer (``ea_csr`` None): ((), ())"""
+    return ((), ()) if ea_csr is None else ((w_edge, ea_csr, int(ea_csr.size(0) != 1)), (ea_csr.size(2),))
+
+
 def _fill_args(fill_value):
     """(fill_mean, constant) of GATv2EdgeConv's ``fill_value``: 'mean' or a number"""
     if isinstance(fill_value, str):
@@ -1537,13 +1543,10 @@ def gatv2_forward(conv, x: torch.Tensor, graph: GatGraph, act: str = "none", ea_
         out = _empty((B, N, H * C), _F32, x)
         alpha = _empty((B, H, graph.num_edges), _F32, x)
         att, bias = _f32c(conv.att), None if conv.bias is None else _f32c(conv.bias)
-        if ea_csr is None:
-            _hip.call("mm_gatv2_fwd", xlr, xlr.data_ptr() + 4 * H * C, 2 * H * C, att, bias, graph.rowptr, graph.col,
-                      out, None, alpha, B, N, H, C, graph.num_edges, float(conv.negative_slope), ACT[act], 0.0, 0, None)
-        else:
-            _hip.call("mm_gatv2_edge_fwd", xlr, xlr.data_ptr() + 4 * H * C, 2 * H * C, att, bias,
-                      _f32c(conv.lin_edge.weight), ea_csr, int(ea_csr.size(0) != 1), graph.rowptr, graph.col, out, None,
-                      alpha, B, N, H, C, graph.num_edges, ea_csr.size(2), float(conv.negative_slope), ACT[act], 0.0, 0, None)
+        edge, D = _gat_edge_args(None if ea_csr is None else _f32c(conv.lin_edge.weight), ea_csr)
+        _hip.call("mm_gatv2_edge_fwd" if edge else "mm_gatv2_fwd", xlr, xlr.data_ptr() + 4 * H * C, 2 * H * C, att, bias,
+                  *edge, graph.rowptr, graph.col, out, None, alpha, B, N, H, C, graph.num_edges, *D,
+                  float(conv.negative_slope), ACT[act], 0.0, 0, None)
     if sink is not None:
         sink.append(alpha)
     return out
@@ -1574,10 +1577,8 @@ def gatv2_conv_forward(conv, x, edge_index, edge_attr=None, return_attention_wei
                                                           or any(q.requires_grad for q in conv.parameters())))
     if tape:
         from . import small_autograd as sa
-        if ea is None:
-            out = sa.gatv2(conv, x3, graph, "none", conv.training, sink=sink)
-        else:
-            out = sa.gatv2_edge(conv, x3, graph, sa.gat_edge_pack(ea, graph, conv.fill_value), "none", conv.training, sink=sink)
+        ea_csr = None if ea is None else sa.gat_edge_pack(ea, graph, conv.fill_value)
+        out = sa.gatv2(conv, x3, graph, "none", conv.training, sink=sink, ea_csr=ea_csr)
     else:
         out = gatv2_forward(conv, x3, graph, ea_csr=None if ea is None else gat_edge_pack(ea, graph, conv.fill_value), sink=sink)
     out = out.squeeze(0) if x.dim() == 2 else out
@@ -1620,10 +1621,7 @@ def gnn_conn_encoder_forward(m, x, edge_index, edge_attr=None, attn_sink=None):
             h = sa.linear_bn_act(x.reshape(B * N, -1), lin, bn, "gelu", 0.0, frozen=True).view(B, N, -1)
         ea_csr = None if ea is None else sa.gat_edge_pack(ea, graph, "mean")          # once, for every layer
         for conv in m.gat_layers:
-            if ea is None:
-                h = sa.gatv2(conv, h, graph, "gelu", m.training, sink=attn_sink)
-            else:
-                h = sa.gatv2_edge(conv, h, graph, ea_csr, "gelu", m.training, sink=attn_sink)
+            h = sa.gatv2(conv, h, graph, "gelu", m.training, sink=attn_sink, ea_csr=ea_csr)
         return sa.linear_bn_act(sa.MeanRowsFn.apply(h), m.output_proj[0], m.output_proj[1], "gelu", p, frozen=fz)
     with torch.no_grad():
         h, _ = small_linear(_f32c(x).view(B * N, -1), lin, act="gelu", bn=bn)

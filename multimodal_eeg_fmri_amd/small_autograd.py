@@ -461,24 +461,28 @@ class FocalLossFn(torch.autograd.Function):
 
 
 class GATv2Fn(torch.autograd.Function):
-    """one GATv2 layer over a static graph (``mm_gatv2_fwd`` / ``mm_gatv2_bwd``): xlr (B, N, 2 H C) = the node
-    features through W_l | W_r -> act(out) (B, N, H C).  Saved: xlr, the softmax alpha (B, H, E') and, under an
-    activation epilogue, the pre-activation; the dropout mask is recomputed from its seed.  ``sink``: a list that
-    receives alpha (for ``return_attention_weights``; readers take a copy)."""
+    """one GATv2 layer over a static graph: xlr (B, N, 2 H C) = the node features through W_l | W_r -> act(out)
+    (B, N, H C).  A plain layer (``mm_gatv2_fwd`` / ``mm_gatv2_bwd``) has ``w_edge`` = ``ea`` = None; an edge layer
+    (``mm_gatv2_edge_fwd`` / ``mm_gatv2_edge_bwd``) ``w_edge`` (H C, D) = lin_edge.weight and ``ea`` (1 | B, E', D) the
+    packed attributes (``GatEdgePackFn``), and forms d ea only when asked for.  Saved: xlr, the softmax alpha
+    (B, H, E'), under an activation epilogue the pre-activation, and ea; the dropout mask is recomputed from its seed.
+    ``sink``: a list that receives alpha (for ``return_attention_weights``; readers take a copy)."""
 
     @staticmethod
-    def forward(ctx, xlr, att, bias, graph, H, C, slope, act, drop_p, sink=None):
-        xlr = _f(xlr)
+    def forward(ctx, xlr, att, bias, w_edge, ea, graph, H, C, slope, act, drop_p, sink=None):
+        xlr, ea = _f(xlr), None if ea is None else _f(ea)
         B, N, _ = xlr.shape
         HC, E = H * C, graph.num_edges
         seed = ops._next_seed() if drop_p > 0 else 0
         out = _empty((B, N, HC), _F32, xlr)
         pre = _empty((B, N, HC), _F32, xlr) if act != "none" else None
         alpha = _empty((B, H, E), _F32, xlr)
-        _hip.call("mm_gatv2_fwd", xlr, xlr.data_ptr() + 4 * HC, 2 * HC, att, bias, graph.rowptr, graph.col, out, pre,
-                  alpha, B, N, H, C, E, float(slope), ACT[act], float(drop_p), seed, ops.EP())
-        ctx.save_for_backward(xlr, alpha, pre)
-        ctx.att, ctx.bias, ctx.graph = att, bias, graph
+        edge, D = ops._gat_edge_args(w_edge, ea)
+        _hip.call("mm_gatv2_edge_fwd" if edge else "mm_gatv2_fwd", xlr, xlr.data_ptr() + 4 * HC, 2 * HC, att, bias, *edge,
+                  graph.rowptr, graph.col, out, pre, alpha, B, N, H, C, E, *D, float(slope), ACT[act], float(drop_p), seed,
+                  ops.EP())
+        ctx.save_for_backward(xlr, alpha, pre, ea)
+        ctx.att, ctx.bias, ctx.w_edge, ctx.graph = att, bias, w_edge, graph
         ctx.meta = (H, C, float(slope), act, float(drop_p), seed)
         if sink is not None:
             sink.append(alpha)
@@ -486,20 +490,27 @@ class GATv2Fn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout):
-        xlr, alpha, pre = ctx.saved_tensors
+        xlr, alpha, pre, ea = ctx.saved_tensors
         H, C, slope, act, p, seed = ctx.meta
-        g, att, bias = ctx.graph, ctx.att, ctx.bias
+        g, att, bias, w_edge = ctx.graph, ctx.att, ctx.bias, ctx.w_edge
         B, N, _ = xlr.shape
         HC, E = H * C, g.num_edges
+        edge, D = ops._gat_edge_args(w_edge, ea)
         dxlr = torch.empty_like(xlr)
         ds = _empty((B, H, E), _F32, xlr)
         dz = _empty((B, N, HC), _F32, xlr) if act != "none" else None
         part = _empty((B, 2, HC), _F32, xlr)
+        wpart = _empty((B, HC, *D), _F32, xlr) if edge else None
+        dea = epart = None
+        if edge and ctx.needs_input_grad[4]:
+            dea, epart = torch.empty_like(ea), _empty((B, H, E, *D), _F32, xlr)
         bag = GradBag()
-        _hip.call("mm_gatv2_bwd", _f(dout), pre, xlr, xlr.data_ptr() + 4 * HC, 2 * HC, att, alpha, g.rowptr, g.col,
-                  g.colptr, g.row, g.perm, dxlr, dxlr.data_ptr() + 4 * HC, bag.target(att), bag.target(bias), ds, dz,
-                  part, B, N, H, C, E, slope, ACT[act], p, seed, ops.EP())
-        return dxlr, bag.result(att), (bag.result(bias) if bias is not None else None), None, None, None, None, None, None, None
+        _hip.call("mm_gatv2_edge_bwd" if edge else "mm_gatv2_bwd", _f(dout), pre, xlr, xlr.data_ptr() + 4 * HC, 2 * HC, att,
+                  *edge, alpha, g.rowptr, g.col, g.colptr, g.row, g.perm, dxlr, dxlr.data_ptr() + 4 * HC, bag.target(att),
+                  bag.target(bias), *((bag.target(w_edge), dea) if edge else ()), ds, dz, part,
+                  *((wpart, epart) if edge else ()), B, N, H, C, E, *D, slope, ACT[act], p, seed, ops.EP())
+        return (dxlr, bag.result(att), (bag.result(bias) if bias is not None else None), bag.result(w_edge), dea,
+                None, None, None, None, None, None, None)
 
 
 class GatEdgePackFn(torch.autograd.Function):
@@ -525,54 +536,6 @@ def gat_edge_pack(ea, graph, fill_value="mean"):
     return GatEdgePackFn.apply(ea, graph, fill_value)
 
 
-class GATv2EdgeFn(torch.autograd.Function):
-    """``GATv2Fn`` with edge features in the score (``mm_gatv2_edge_fwd`` / ``mm_gatv2_edge_bwd``): ``w_edge`` (H C, D) =
-    lin_edge.weight, ``ea`` (1 | B, E', D) the packed attributes (``GatEdgePackFn``).  d ea is formed only when asked for."""
-
-    @staticmethod
-    def forward(ctx, xlr, att, bias, w_edge, ea, graph, H, C, slope, act, drop_p, sink=None):
-        xlr, ea = _f(xlr), _f(ea)
-        B, N, _ = xlr.shape
-        HC, E, D = H * C, graph.num_edges, ea.shape[2]
-        seed = ops._next_seed() if drop_p > 0 else 0
-        out = _empty((B, N, HC), _F32, xlr)
-        pre = _empty((B, N, HC), _F32, xlr) if act != "none" else None
-        alpha = _empty((B, H, E), _F32, xlr)
-        _hip.call("mm_gatv2_edge_fwd", xlr, xlr.data_ptr() + 4 * HC, 2 * HC, att, bias, w_edge, ea, int(ea.shape[0] != 1),
-                  graph.rowptr, graph.col, out, pre, alpha, B, N, H, C, E, D, float(slope), ACT[act], float(drop_p), seed,
-                  ops.EP())
-        ctx.save_for_backward(xlr, alpha, pre, ea)
-        ctx.att, ctx.bias, ctx.w_edge, ctx.graph = att, bias, w_edge, graph
-        ctx.meta = (H, C, float(slope), act, float(drop_p), seed)
-        if sink is not None:
-            sink.append(alpha)
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):
-        xlr, alpha, pre, ea = ctx.saved_tensors
-        H, C, slope, act, p, seed = ctx.meta
-        g, att, bias, w_edge = ctx.graph, ctx.att, ctx.bias, ctx.w_edge
-        B, N, _ = xlr.shape
-        HC, E = H * C, g.num_edges
-        Bo, _, D = ea.shape
-        dxlr = torch.empty_like(xlr)
-        ds = _empty((B, H, E), _F32, xlr)
-        dz = _empty((B, N, HC), _F32, xlr) if act != "none" else None
-        part = _empty((B, 2, HC), _F32, xlr)
-        wpart = _empty((B, HC, D), _F32, xlr)
-        dea = epart = None
-        if ctx.needs_input_grad[4]:
-            dea, epart = torch.empty_like(ea), _empty((B, H, E, D), _F32, xlr)
-        bag = GradBag()
-        _hip.call("mm_gatv2_edge_bwd", _f(dout), pre, xlr, xlr.data_ptr() + 4 * HC, 2 * HC, att, w_edge, ea, int(Bo != 1),
-                  alpha, g.rowptr, g.col, g.colptr, g.row, g.perm, dxlr, dxlr.data_ptr() + 4 * HC, bag.target(att),
-                  bag.target(bias), bag.target(w_edge), dea, ds, dz, part, wpart, epart, B, N, H, C, E, D, slope, ACT[act],
-                  p, seed, ops.EP())
-        return (dxlr, bag.result(att), (bag.result(bias) if bias is not None else None), bag.result(w_edge), dea,
-                None, None, None, None, None, None, None)
-
-
 class MeanRowsFn(torch.autograd.Function):
     """mean over dim 1 of fp32 (B, L, D): the global pooling over the nodes of a graph"""
 
@@ -593,27 +556,18 @@ class MeanRowsFn(torch.autograd.Function):
         return dx
 
 
-def gatv2(conv, x, graph, act="none", training: bool = False, sink=None):
-    """GATv2Conv on (B, N, in) rows, differentiable: both linears as one ``SmallLinearFn`` with W_l | W_r stacked,
-    then ``GATv2Fn`` (``act`` = its epilogue; attention dropout only when ``training``; ``sink`` receives alpha)"""
+def gatv2(conv, x, graph, act="none", training: bool = False, sink=None, ea_csr=None):
+    """GATv2Conv / GATv2EdgeConv on (B, N, in) rows, differentiable: both linears as one ``SmallLinearFn`` with
+    W_l | W_r stacked, then ``GATv2Fn`` (``act`` = its epilogue; attention dropout only when ``training``; ``sink``
+    receives alpha; ``ea_csr`` (1 | B, E', D) = the packed attributes of an edge layer)"""
     B, N, K = x.shape
     if N != graph.num_nodes:
         raise ValueError(f"gatv2: x has {N} nodes, the graph {graph.num_nodes}")
     W, b = ops._gat_cat(conv)
     xlr = SmallLinearFn.apply(x.reshape(B * N, K), W, b, "none", 0.0)
-    return GATv2Fn.apply(xlr.view(B, N, -1), conv.att, conv.bias, graph, conv.heads, conv.out_channels,
-                         float(conv.negative_slope), act, float(conv.dropout) if training else 0.0, sink)
-
-
-def gatv2_edge(conv, x, graph, ea_csr, act="none", training: bool = False, sink=None):
-    """GATv2EdgeConv on (B, N, in) rows with the packed attributes ``ea_csr`` (1 | B, E', D), differentiable"""
-    B, N, K = x.shape
-    if N != graph.num_nodes:
-        raise ValueError(f"gatv2_edge: x has {N} nodes, the graph {graph.num_nodes}")
-    W, b = ops._gat_cat(conv)
-    xlr = SmallLinearFn.apply(x.reshape(B * N, K), W, b, "none", 0.0)
-    return GATv2EdgeFn.apply(xlr.view(B, N, -1), conv.att, conv.bias, conv.lin_edge.weight, ea_csr, graph, conv.heads,
-                             conv.out_channels, float(conv.negative_slope), act, float(conv.dropout) if training else 0.0, sink)
+    return GATv2Fn.apply(xlr.view(B, N, -1), conv.att, conv.bias, None if ea_csr is None else conv.lin_edge.weight, ea_csr,
+                         graph, conv.heads, conv.out_channels, float(conv.negative_slope), act,
+                         float(conv.dropout) if training else 0.0, sink)
 
 
 def proj_head(x, seq, drop_p):
