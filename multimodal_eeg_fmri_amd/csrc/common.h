@@ -143,6 +143,14 @@ __device__ __forceinline__ uint32_t mm_eff_seed(uint32_t base, const uint32_t* e
     return epoch ? base ^ (epoch[0] * 0x85EBCA6Bu + 0xC2B2AE35u) : base;
 }
 
+// host side: a caller's drop probability as the (thresh, inv_keep) every kernel takes.  The ONE conversion: forward and
+// backward launches, in whichever file, recompute the same mask only if they agree on these bits (p in [0, 1); p = 0 is
+// thresh 0 = dropout off).  The threshold goes through double (exact), inv_keep is formed in float.
+struct DropH { uint32_t thresh; float inv_keep; };
+inline DropH mm_drop(float p) {
+    return p > 0.f ? DropH{(uint32_t)((double)p * 4294967296.0), 1.f / (1.f - p)} : DropH{0u, 1.f};
+}
+
 // BatchNorm + activation [+ pool 2] [+ dropout] backward, element level (elementwise.hip's two passes and the reduce pass
 // fused behind a data-gradient GEMM, igemm1d.hip): dz for the (up to) two inputs of one pooled output element.
 // Args carries act, pool, drop_first, thresh, seed (already mm_eff_seed'ed), inv_keep.  ACT >= 0 / POOL > 0: compiled for that activation /

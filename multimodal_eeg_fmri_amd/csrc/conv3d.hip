@@ -469,12 +469,11 @@ __global__ __launch_bounds__(256) void pool3_bwd_reduce_kernel(Pool3Args a) {
     }
 }
 
-inline uint32_t thresh3(float p) { return p > 0.f ? (uint32_t)((double)p * 4294967296.0) : 0u; }
-
 int pool3_launch(int mode, Pool3Args a, float drop_p, hipStream_t st, bool with_fin = false) {
     MM_REQUIRE(a.out4 && a.B > 0 && a.D >= 2 && a.H >= 2 && a.W >= 2, "pool3d_bn_act: D,H,W must be >= 2 (MaxPool3d(2) floors odd extents)");
     MM_REQUIRE(a.N % 8 == 0 && a.N <= 1024, "pool3d_bn_act: N must be a multiple of 8");
-    a.thresh = thresh3(drop_p); a.inv_keep = drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f;
+    const DropH d = mm_drop(drop_p);
+    a.thresh = d.thresh; a.inv_keep = d.inv_keep;
     a.inv_count = 1.f / ((float)a.B * a.D * a.H * a.W);
     const int rpb = 256 / (a.N / 8) > 0 ? 256 / (a.N / 8) : 1;
     const size_t rows = (size_t)a.B * (a.D / 2) * (a.H / 2) * (a.W / 2);

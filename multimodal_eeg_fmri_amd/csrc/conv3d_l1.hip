@@ -592,14 +592,13 @@ __global__ void l1_combine_kernel(const float* __restrict__ a1, const float* __r
     if (tap == 0 && dbias && !train) dbias[n] += sc * s0;      // train: sum dy == 0 identically
 }
 
-inline uint32_t thresh_l1(float p) { return p > 0.f ? (uint32_t)((double)p * 4294967296.0) : 0u; }
-
 inline void l1_fill(L1Args& a, const float* x, const void* wimg, const float* bias, const float* out4, int B, int D, int H,
                     int W, int train, float drop_p, uint32_t seed, const uint32_t* seed_epoch) {
     a.x = x; a.wimg = (const bf16*)wimg; a.bias = bias; a.out4 = out4; a.dout = nullptr; a.sums = nullptr;
     a.stats = nullptr; a.out = nullptr; a.arg = nullptr; a.dw = nullptr; a.dbias = nullptr; a.gram = nullptr; a.fin = MmBnFin{};
     a.B = B; a.D = D; a.H = H; a.W = W; a.train = train;
-    a.thresh = thresh_l1(drop_p); a.seed = seed; a.inv_keep = drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f;
+    const DropH d = mm_drop(drop_p);
+    a.thresh = d.thresh; a.seed = seed; a.inv_keep = d.inv_keep;
     a.inv_count = 1.f / ((float)B * D * H * W);
     a.epoch = seed_epoch;
 }

@@ -571,7 +571,6 @@ inline int grid_for(size_t n, int block = 256, int cap = 4096) {
     size_t g = (n + block - 1) / block;
     return (int)(g < (size_t)cap ? (g ? g : 1) : cap);
 }
-inline uint32_t thresh_of(float p) { return p > 0.f ? (uint32_t)((double)p * 4294967296.0) : 0u; }
 
 }  // namespace
 
@@ -601,9 +600,9 @@ static int bn_act_fwd_common(const float* y, const float* scale, const float* sh
     }
     MM_REQUIRE(y && scale && shift && (out_bf16 || out_f32), "bn_act_fwd: null");
     MM_REQUIRE(N % 4 == 0 && (pool == 1 || (pool == 2 && S % 2 == 0)), "bn_act_fwd: N%%4, pool");
+    const DropH d = mm_drop(drop_p), d2 = mm_drop(drop2_p);
     BnActArgs a{y, scale, shift, pe, (bf16*)out_bf16, out_f32, R, S, N, act, pool, drop_first,
-                thresh_of(drop_p), seed, drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f,
-                thresh_of(drop2_p), seed2, drop2_p > 0.f ? 1.f / (1.f - drop2_p) : 1.f, seed_epoch};
+                d.thresh, seed, d.inv_keep, d2.thresh, seed2, d2.inv_keep, seed_epoch};
     a.ln_gamma = ln_gamma; a.ln_beta = ln_beta; a.ln_eps = ln_eps; a.ln_out = (bf16*)ln_out; a.ln_stat = ln_stat;
     a.fin = fin;
     const size_t total = (size_t)R * (S / pool) * (N / 4);
@@ -673,10 +672,10 @@ static int bn_bwd_common(bool apply, const float* y, const float* out4, const vo
     a.y = y; a.scale = out4; a.shift = out4 + N; a.mean = out4 + 2 * N; a.rstd = out4 + 3 * N;
     a.dout_bf16 = (const bf16*)dout_bf16; a.dout_f32 = dout_f32; a.sums = sums_in; a.sums_out = sums_out;
     a.dy = (bf16*)dy; a.dy_f32 = dy_f32; a.R = R; a.S = S; a.N = N; a.act = act; a.pool = pool; a.drop_first = drop_first;
-    a.train = train; a.thresh = thresh_of(drop_p); a.seed = seed;
-    a.inv_keep = drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f;
+    const DropH d = mm_drop(drop_p), d2 = mm_drop(drop2_p);
+    a.train = train; a.thresh = d.thresh; a.seed = seed; a.inv_keep = d.inv_keep;
     a.inv_count = 1.f / ((float)R * (float)S);
-    a.thresh2 = thresh_of(drop2_p); a.seed2 = seed2; a.inv_keep2 = drop2_p > 0.f ? 1.f / (1.f - drop2_p) : 1.f;
+    a.thresh2 = d2.thresh; a.seed2 = seed2; a.inv_keep2 = d2.inv_keep;
     a.epoch = seed_epoch;
     a.sums_nrep = sums_nrep;
     a.bcast = bcast; a.bcast_scale = bcast_scale;
@@ -762,18 +761,19 @@ int mm_layernorm_bwd(const void* dy_bf16, const float* dy_f32, const float* x, c
                      const float* dres, float* dx, void* dx_bf16, float* dgb_repl, int M, int D, float drop_p,
                      uint32_t seed, const uint32_t* seed_epoch, hipStream_t st) {
     MM_REQUIRE((dy_bf16 || dy_f32) && x && stat && gamma && (dx || dx_bf16), "layernorm_bwd: null");
+    const DropH d = mm_drop(drop_p);
     if (D == 128) {
         const int rph = M >= 8192 ? 4 : 1;                 // rows per half-wave
         hipLaunchKernelGGL(layernorm128_bwd_kernel, dim3(ceil_div(M, 8 * rph)), dim3(256), 0, st, (const bf16*)dy_bf16,
-                           dy_f32, x, stat, gamma, dres, dx, (bf16*)dx_bf16, dgb_repl, M, rph, thresh_of(drop_p), seed,
-                           drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f, seed_epoch);
+                           dy_f32, x, stat, gamma, dres, dx, (bf16*)dx_bf16, dgb_repl, M, rph, d.thresh, seed, d.inv_keep,
+                           seed_epoch);
         return mm_check_launch("layernorm128_bwd");
     }
     const int rpw = M >= 8192 ? 8 : (M >= 1024 ? 2 : 1);
     const dim3 grid(ceil_div(M, 4 * rpw)), block(256);
     LN_DISPATCH(D, hipLaunchKernelGGL((layernorm_bwd_kernel<V, W>), grid, block, 0, st, (const bf16*)dy_bf16, dy_f32, x,
-                                      stat, gamma, dres, dx, (bf16*)dx_bf16, dgb_repl, M, rpw, thresh_of(drop_p), seed,
-                                      drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f, seed_epoch));
+                                      stat, gamma, dres, dx, (bf16*)dx_bf16, dgb_repl, M, rpw, d.thresh, seed,
+                                      d.inv_keep, seed_epoch));
     return mm_check_launch("layernorm_bwd");
 }
 
@@ -800,9 +800,9 @@ int mm_meanpool_bwd(const float* g, float* dx, int B, int L, int D, hipStream_t 
 int mm_act_bwd(const float* g_f32, const void* g_bf16, const void* z, void* out, int64_t n, int act, float drop_p,
                uint32_t seed, const uint32_t* seed_epoch, hipStream_t st) {
     MM_REQUIRE((g_f32 || g_bf16) && out && n > 0, "act_bwd: null");
+    const DropH d = mm_drop(drop_p);
     hipLaunchKernelGGL(act_bwd_kernel, dim3(grid_for((size_t)n)), dim3(256), 0, st, g_f32, (const bf16*)g_bf16,
-                       (const bf16*)z, (bf16*)out, (size_t)n, act, thresh_of(drop_p), seed,
-                       drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f, seed_epoch);
+                       (const bf16*)z, (bf16*)out, (size_t)n, act, d.thresh, seed, d.inv_keep, seed_epoch);
     return mm_check_launch("act_bwd");
 }
 
@@ -812,8 +812,9 @@ int mm_add_pe(const float* x, const float* pe, float* out_f32, void* out_bf16, i
     MM_REQUIRE(D % 4 == 0, "add_pe: D=%d must be a multiple of 4", D);
     MM_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "add_pe: drop_p");
     const size_t n4 = (size_t)B * L * D / 4;
+    const DropH d = mm_drop(drop_p);
     hipLaunchKernelGGL(add_pe_kernel, dim3(grid_for(n4)), dim3(256), 0, st, x, pe, out_f32, (bf16*)out_bf16, n4,
-                       L * D / 4, thresh_of(drop_p), seed, drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f, seed_epoch);
+                       L * D / 4, d.thresh, seed, d.inv_keep, seed_epoch);
     return mm_check_launch("add_pe");
 }
 

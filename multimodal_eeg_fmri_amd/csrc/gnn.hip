@@ -435,8 +435,8 @@ GatArgs gat_args(const float* xl, const float* xr, int ld, const float* att, con
     GatArgs a{};
     a.xl = xl; a.xr = xr; a.ld = ld; a.att = att; a.rowptr = rowptr; a.col = col;
     a.B = B; a.N = N; a.H = H; a.C = C; a.E = E; a.slope = slope; a.act = act;
-    a.thresh = drop_p > 0.f ? (uint32_t)((double)drop_p * 4294967296.0) : 0u;
-    a.seed = seed; a.inv_keep = drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f; a.epoch = seed_epoch;
+    const DropH d = mm_drop(drop_p);
+    a.thresh = d.thresh; a.seed = seed; a.inv_keep = d.inv_keep; a.epoch = seed_epoch;
     a.we = w_edge; a.ea = edge_attr; a.ea_bs = ea_batched ? (size_t)E * D : 0; a.D = D;
     return a;
 }

@@ -1624,7 +1624,6 @@ __global__ void meanpool_bf16_kernel(const bf16* __restrict__ x, float* __restri
     }
 }
 
-inline uint32_t thresh_h(float p) { return p > 0.f ? (uint32_t)((double)p * 4294967296.0) : 0u; }
 inline int grid_h(size_t n, int cap = 2048) { size_t g = (n + 255) / 256; return (int)(g < (size_t)cap ? (g ? g : 1) : cap); }
 
 }  // namespace
@@ -1638,8 +1637,9 @@ int mm_small_linear_fwd(const float* x, const float* W, const float* bias, const
     MM_REQUIRE((scale == nullptr) == (shift == nullptr), "small_linear_fwd: scale/shift come in pairs");
     MM_REQUIRE((size_t)K * 4 <= 64 * 1024, "small_linear_fwd: K=%d too large", K);
     const int gy = ceil_div(N, 4) < 64 ? ceil_div(N, 4) : 64;
+    const DropH d = mm_drop(drop_p);
     hipLaunchKernelGGL(small_linear_fwd_kernel, dim3(B, gy), dim3(256), K * sizeof(float), st, x, W, bias, scale, shift,
-                       y, pre, B, K, N, act, thresh_h(drop_p), seed, drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f, seed_epoch);
+                       y, pre, B, K, N, act, d.thresh, seed, d.inv_keep, seed_epoch);
     return mm_check_launch("small_linear_fwd");
 }
 
@@ -1655,16 +1655,18 @@ int mm_small_linear_bwd(const float* dy, const float* x, const float* W, float* 
 int mm_act_f32(const float* z, float* y, int64_t n, int act, float drop_p, uint32_t seed, const uint32_t* seed_epoch,
                hipStream_t st) {
     MM_REQUIRE(z && y && n > 0, "act_f32: null");
-    hipLaunchKernelGGL(act_f32_kernel, dim3(grid_h((size_t)n)), dim3(256), 0, st, z, y, (size_t)n, act, thresh_h(drop_p),
-                       seed, drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f, seed_epoch);
+    const DropH d = mm_drop(drop_p);
+    hipLaunchKernelGGL(act_f32_kernel, dim3(grid_h((size_t)n)), dim3(256), 0, st, z, y, (size_t)n, act, d.thresh, seed,
+                       d.inv_keep, seed_epoch);
     return mm_check_launch("act_f32");
 }
 
 int mm_act_bwd_f32(const float* g, const float* z, float* out, int64_t n, int act, float drop_p, uint32_t seed,
                    const uint32_t* seed_epoch, hipStream_t st) {
     MM_REQUIRE(g && out && n > 0, "act_bwd_f32: null");
+    const DropH d = mm_drop(drop_p);
     hipLaunchKernelGGL(act_bwd_f32_kernel, dim3(grid_h((size_t)n)), dim3(256), 0, st, g, z, out, (size_t)n, act,
-                       thresh_h(drop_p), seed, drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f, seed_epoch);
+                       d.thresh, seed, d.inv_keep, seed_epoch);
     return mm_check_launch("act_bwd_f32");
 }
 
@@ -1686,7 +1688,8 @@ int mm_proj_heads_fwd(const float* x_e, const float* W_e, const float* b_e, cons
     a.s[0].x = x_e; a.s[0].W = W_e; a.s[0].bias = b_e; a.s[0].gamma = g_e; a.s[0].beta = be_e; a.s[0].K = K_e; a.s[0].seed = seed_e;
     a.s[1].x = x_f; a.s[1].W = W_f; a.s[1].bias = b_f; a.s[1].gamma = g_f; a.s[1].beta = be_f; a.s[1].K = K_f; a.s[1].seed = seed_f;
     a.z1 = z1; a.hn = hn; a.stat = stat; a.z = z; a.nrm = nrm; a.B = B; a.N = N; a.eps = eps;
-    a.thresh = thresh_h(drop_p); a.inv_keep = drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f; a.epoch = seed_epoch;
+    const DropH d = mm_drop(drop_p);
+    a.thresh = d.thresh; a.inv_keep = d.inv_keep; a.epoch = seed_epoch;
     hipLaunchKernelGGL(proj_heads_fwd_kernel, dim3(B, 2), dim3(256), 0, st, a);
     return mm_check_launch("proj_heads_fwd");
 }
@@ -1707,7 +1710,8 @@ int mm_proj_heads_bwd(const float* dz, const float* z, const float* nrm, const f
     a.s[1].dx = dx_f; a.s[1].dW = dW_f; a.s[1].dbias = db_f; a.s[1].dgamma = dg_f; a.s[1].dbeta = dbe_f;
     a.z1 = const_cast<float*>(z1); a.hn = const_cast<float*>(hn); a.stat = const_cast<float*>(stat);
     a.z = const_cast<float*>(z); a.nrm = const_cast<float*>(nrm); a.dz = dz; a.B = B; a.N = N;
-    a.thresh = thresh_h(drop_p); a.inv_keep = drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f; a.epoch = seed_epoch;
+    const DropH d = mm_drop(drop_p);
+    a.thresh = d.thresh; a.inv_keep = d.inv_keep; a.epoch = seed_epoch;
     switch (ceil_div(N, 64)) {
         case 1: hipLaunchKernelGGL(proj_heads_bwd_kernel<1>, dim3(B, 2), dim3(1024), 0, st, a); break;
         case 2: hipLaunchKernelGGL(proj_heads_bwd_kernel<2>, dim3(B, 2), dim3(1024), 0, st, a); break;
@@ -1831,9 +1835,9 @@ int mm_attn_1x2_train(const float* proj_e, const float* proj_f, const float* dct
                       const uint32_t* seed_epoch, int backward, hipStream_t st) {
     MM_REQUIRE(proj_e && proj_f && B > 0 && nhead > 0 && nhead <= 16 && E % nhead == 0, "attn_1x2_train: bad args");
     MM_REQUIRE(backward ? (dctx && dproj_e && dproj_f) : (ctx != nullptr), "attn_1x2_train: outputs");
+    const DropH d = mm_drop(drop_p);
     hipLaunchKernelGGL(attn_1x2_fused_kernel, dim3(B), dim3(256), 0, st, proj_e, proj_f, dctx, ctx, attw, dproj_e,
-                       dproj_f, B, E, nhead, thresh_h(drop_p), seed, drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f,
-                       seed_epoch, backward);
+                       dproj_f, B, E, nhead, d.thresh, seed, d.inv_keep, seed_epoch, backward);
     return mm_check_launch("attn_1x2_train");
 }
 
@@ -1973,8 +1977,8 @@ int mm_attn_1xk(const float* p0, const float* p1, const float* p2, const float* 
     }
     MM_REQUIRE(backward ? dctx != nullptr : ctx != nullptr, "attn_1xk: outputs");
     a.dctx = dctx; a.ctx = ctx; a.attw = attw; a.B = B; a.E = E; a.nhead = nhead; a.K = K;
-    a.thresh = thresh_h(drop_p); a.seed = seed; a.inv_keep = drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f;
-    a.epoch = seed_epoch; a.backward = backward;
+    const DropH d = mm_drop(drop_p);
+    a.thresh = d.thresh; a.seed = seed; a.inv_keep = d.inv_keep; a.epoch = seed_epoch; a.backward = backward;
     hipLaunchKernelGGL(attn_1xk_kernel, dim3(B), dim3(256), 0, st, a);
     return mm_check_launch("attn_1xk");
 }
@@ -1997,9 +2001,9 @@ int mm_pooled_head_fwd(const float* pooled, const float* pooled_acc, const float
     MM_REQUIRE((pooled != nullptr) != (pooled_acc != nullptr) && W && out && B > 0, "pooled_head_fwd: null (exactly one of pooled / pooled_acc)");
     MM_REQUIRE(D > 0 && D <= 1024 && D % 16 == 0 && N > 0, "pooled_head_fwd: D=%d (multiple of 16, <= 1024)", D);
     MM_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "pooled_head_fwd: drop_p");
-    const uint32_t thresh = drop_p > 0.f ? (uint32_t)((double)drop_p * 4294967296.0) : 0u;
+    const DropH d = mm_drop(drop_p);
     hipLaunchKernelGGL(pooled_head_fwd_kernel, dim3(B), dim3(256), 0, st, pooled, reinterpret_cast<const mm_acc_t*>(pooled_acc), W, bias, out, (bf16*)z_pre_bf16,
-                       (bf16*)pooled_bf16, D, N, act, thresh, drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f, seed, seed_epoch);
+                       (bf16*)pooled_bf16, D, N, act, d.thresh, d.inv_keep, seed, seed_epoch);
     return mm_check_launch("pooled_head_fwd");
 }
 
@@ -2011,11 +2015,10 @@ static int pooled_head_bwd_common(const float* dout, const void* z_pre_bf16, con
     MM_REQUIRE(D > 0 && D <= 1024 && D % 4 == 0 && N > 0 && N <= 1024 && N % 4 == 0, "pooled_head_bwd: D=%d N=%d", D, N);
     MM_REQUIRE(drop_p >= 0.f && drop_p < 1.f && emit_drop_p >= 0.f && emit_drop_p < 1.f, "pooled_head_bwd: drop_p");
     const int rows = 32;
-    const uint32_t t1 = drop_p > 0.f ? (uint32_t)((double)drop_p * 4294967296.0) : 0u;
-    const uint32_t t2 = emit_drop_p > 0.f ? (uint32_t)((double)emit_drop_p * 4294967296.0) : 0u;
+    const DropH d1 = mm_drop(drop_p), d2 = mm_drop(emit_drop_p);
     hipLaunchKernelGGL(pooled_head_bwd_kernel, dim3(B, (L + rows - 1) / rows), dim3(256), 0, st, dout, (const bf16*)z_pre_bf16, W,
-                       (bf16*)dz_bf16, dx, (bf16*)dx_bf16, L, D, N, rows, act, t1, drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f, seed,
-                       t2, emit_drop_p > 0.f ? 1.f / (1.f - emit_drop_p) : 1.f, emit_seed, seed_epoch, rows_out);
+                       (bf16*)dz_bf16, dx, (bf16*)dx_bf16, L, D, N, rows, act, d1.thresh, d1.inv_keep, seed,
+                       d2.thresh, d2.inv_keep, emit_seed, seed_epoch, rows_out);
     return mm_check_launch("pooled_head_bwd");
 }
 
@@ -2040,9 +2043,9 @@ int mm_pooled_head_bwd_rows(const float* dout, const void* z_pre_bf16, const flo
 int mm_drop_path(const float* x, float* out, int64_t B, int64_t inner, float drop_p, uint32_t seed,
                  const uint32_t* seed_epoch, hipStream_t st) {
     MM_REQUIRE(x && out && B > 0 && inner > 0 && drop_p >= 0.f && drop_p < 1.f, "drop_path: bad args");
-    const uint32_t thresh = (uint32_t)fminf(drop_p * 4294967296.f, 4294967295.f);
+    const DropH d = mm_drop(drop_p);
     hipLaunchKernelGGL(drop_path_kernel, dim3(grid_h((size_t)(B * inner))), dim3(256), 0, st, x, out, (size_t)(B * inner),
-                       (size_t)inner, thresh, 1.f / (1.f - drop_p), seed, seed_epoch);
+                       (size_t)inner, d.thresh, d.inv_keep, seed, seed_epoch);
     return mm_check_launch("drop_path");
 }
 

@@ -39,40 +39,40 @@ struct BnRed {
 };
 
 struct EpiArgs {
-    const float* scale;       // [N] multiply (nullptr = 1)
-    const float* shift;       // [N] add (bias / folded BN shift) (nullptr = 0)
-    const float* residual;    // [M][N] fp32 added after activation (nullptr)
-    const float* pe;          // [>=T][N] fp32 positional table added per t (nullptr)
-    float* stats;             // [2][N] sum / sum-of-squares of v (atomics) (nullptr)
-    float* out_f32;           // [M/pool][N]
-    bf16* out_bf16;           // [M/pool][N]
-    bf16* out_pre;            // [M][N] pre-activation copy (nullptr)
-    int act;
-    int pool;                 // 1 or 2 (max over adjacent t pairs, after act)
-    uint32_t drop_thresh;     // 0 = no dropout
-    uint32_t drop_seed;
-    float drop_inv_keep;
-    const uint32_t* drop_epoch;
-    const bf16* gradz;        // backward fusion: v *= act'(gradz[idx]) (nullptr = off)
-    int gradz_act;
+    const float* scale = nullptr;       // [N] multiply (nullptr = 1)
+    const float* shift = nullptr;       // [N] add (bias / folded BN shift) (nullptr = 0)
+    const float* residual = nullptr;    // [M][N] fp32 added after activation (nullptr)
+    const float* pe = nullptr;          // [>=T][N] fp32 positional table added per t (nullptr)
+    float* stats = nullptr;             // [2][N] sum / sum-of-squares of v (atomics) (nullptr)
+    float* out_f32 = nullptr;           // [M/pool][N]
+    bf16* out_bf16 = nullptr;           // [M/pool][N]
+    bf16* out_pre = nullptr;            // [M][N] pre-activation copy (nullptr)
+    int act = 0;
+    int pool = 1;                       // 1 or 2 (max over adjacent t pairs, after act)
+    uint32_t drop_thresh = 0;           // 0 = no dropout
+    uint32_t drop_seed = 0;
+    float drop_inv_keep = 1.f;
+    const uint32_t* drop_epoch = nullptr;
+    const bf16* gradz = nullptr;        // backward fusion: v *= act'(gradz[idx]) (nullptr = off)
+    int gradz_act = 0;
     // LayerNorm-128 backward fused behind a data-gradient GEMM (ln_x != nullptr): the tile rows are
     // d(LN output); residual = gradient of the skip path; out_f32 / out_bf16 = d(LN input) (bf16 copy
     // carries the consumer's dropout mask); ln_dgb = [REPL][2][128] {dgamma, dbeta} replicas
-    const float* ln_x;
-    const float* ln_stat;     // [M][2] mean, rstd
-    const float* ln_gamma;
-    float* ln_dgb;
+    const float* ln_x = nullptr;
+    const float* ln_stat = nullptr;     // [M][2] mean, rstd
+    const float* ln_gamma = nullptr;
+    float* ln_dgb = nullptr;
     // mean over groups of pool_rows consecutive output rows, fused: pool_out[row / pool_rows][n] += out * pool_scale
-    float* pool_out;
-    int pool_rows;
-    float pool_scale;
+    float* pool_out = nullptr;
+    int pool_rows = 0;
+    float pool_scale = 0.f;
     // LayerNorm-128 of every finished output row (the NEXT sub-layer's pre-norm), fused: lnf_out bf16 rows,
     // lnf_stat [M][2] mean / rstd (nullable)
-    bf16* lnf_out;
-    float* lnf_stat;
-    const float* lnf_gamma;
-    const float* lnf_beta;
-    float lnf_eps;
+    bf16* lnf_out = nullptr;
+    float* lnf_stat = nullptr;
+    const float* lnf_gamma = nullptr;
+    const float* lnf_beta = nullptr;
+    float lnf_eps = 0.f;
     BnRed bn;
     // second GEMM behind epilogue_ln_bwd (BM = 32, BN = 128): out2 (M, 128) bf16 = out_bf16 rows @ w2 (a 128 x 128 data-
     // gradient weight image) - the data gradient of the Linear whose output, after dropout, was added to this LayerNorm's
@@ -88,9 +88,9 @@ struct EpiArgs {
 };
 
 struct ConvArgs {
-    const bf16* x;
-    const bf16* w;
-    int B, T, Cin, Cout, taps, pad;
+    const bf16* x = nullptr;
+    const bf16* w = nullptr;
+    int B = 0, T = 0, Cin = 0, Cout = 0, taps = 0, pad = 0;
     EpiArgs e;
     // split-K (few output tiles, long reduction: config #5's 192-channel k = 7 convolution over ~6 000 input channels is
     // 96 tiles of 98 chunks): workgroup z reduces input channels [z * csplit, (z + 1) * csplit) and stores its raw fp32
@@ -108,12 +108,16 @@ enum : unsigned { EF_RES = 1, EF_PE = 2, EF_PRE = 4, EF_GRADZ = 8, EF_STATS = 16
                   EF_DROP = 256, EF_SCALE = 512, EF_F32 = 1024, EF_BF16 = 2048, EF_SHIFT = 4096, EF_LNBWD = 8192,
                   EF_BNRED = 16384, EF_BNPOOL2 = 32768 /* bits 24-27: the fused BatchNorm-backward's activation */,
                   EF_GEMM2 = 1u << 28, EF_ANY = 0xFFFFFFFFu };
+// the three activation fields (4 bits each, at these bit offsets): the epilogue's own, the fused activation
+// derivative's, the fused BatchNorm-backward's
+enum : int { EFA_OUT = 16, EFA_GRADZ = 20, EFA_BN = 24 };
+constexpr unsigned ef_act(int act, int field = EFA_OUT) { return (unsigned)act << field; }
 static unsigned epi_mask(const EpiArgs& e) {
     return (e.residual ? EF_RES : 0) | (e.pe ? EF_PE : 0) | (e.out_pre ? EF_PRE : 0) | (e.gradz ? EF_GRADZ : 0) | (e.stats ? EF_STATS : 0) |
            (e.pool_out ? EF_POOLOUT : 0) | (e.lnf_out ? EF_LNF : 0) | (e.pool == 2 ? EF_POOL2 : 0) | (e.drop_thresh ? EF_DROP : 0) |
            (e.scale ? EF_SCALE : 0) | (e.out_f32 ? EF_F32 : 0) | (e.out_bf16 ? EF_BF16 : 0) | (e.shift ? EF_SHIFT : 0) | (e.ln_x ? EF_LNBWD : 0) |
-           ((unsigned)e.act << 16) | ((unsigned)(e.gradz ? e.gradz_act : 0) << 20) |
-           (e.bn.y ? (EF_BNRED | (e.bn.pool == 2 ? EF_BNPOOL2 : 0) | ((unsigned)e.bn.act << 24)) : 0) | (e.w2 ? EF_GEMM2 : 0);
+           ef_act(e.act) | ef_act(e.gradz ? e.gradz_act : 0, EFA_GRADZ) |
+           (e.bn.y ? (EF_BNRED | (e.bn.pool == 2 ? EF_BNPOOL2 : 0) | ef_act(e.bn.act, EFA_BN)) : 0) | (e.w2 ? EF_GEMM2 : 0);
 }
 
 
@@ -731,35 +735,35 @@ template <int BM, int BN, int WM, int WN, int KCT>
 int launch_fwd(const ConvArgs& a, hipStream_t st) {
     const unsigned m = epi_mask(a.e);
     if (getenv("MM_EPI_GENERIC") || a.partial) return launch_fwd_feat<BM, BN, WM, WN, KCT, EF_ANY>(a, st);      // tests: generic vs compiled-in epilogues; split-K
-#define EPI_CASE(mask) case mask: return launch_fwd_feat<BM, BN, WM, WN, KCT, mask, LT>(a, st);
+#define EPI_CASE(mask) case (mask): return launch_fwd_feat<BM, BN, WM, WN, KCT, (mask), LT>(a, st);
     if constexpr (BM == 64 && BN == 128 && KCT == 128) {
         constexpr int LT = 1;                 // the Linear layers: one tap
         if (a.taps == 1) switch (m) {
-            EPI_CASE(0x001800u)          // QKV projection: bias, bf16 out
-            EPI_CASE(0x011904u)          // FFN-1 forward: bias, GELU, dropout, pre-activation copy, bf16 out
-            EPI_CASE(0x100908u)          // FFN-2 data gradient: GELU', dropout mask, bf16 out
+            EPI_CASE(EF_SHIFT | EF_BF16)   // QKV projection: bias, bf16 out
+            EPI_CASE(EF_SHIFT | EF_BF16 | EF_DROP | EF_PRE | ef_act(MM_ACT_GELU))   // FFN-1 forward: bias, GELU, dropout, pre-activation copy, bf16 out
+            EPI_CASE(EF_BF16 | EF_DROP | EF_GRADZ | ef_act(MM_ACT_GELU, EFA_GRADZ))   // FFN-2 data gradient: GELU', dropout mask, bf16 out
             default: break;
         }
     } else if constexpr (BM == 32 && BN == 128 && KCT == 128) {
         constexpr int LT = 1;
         if (a.taps == 1) switch (m) {
-            EPI_CASE(0x001541u)          // out-proj / FFN-2 forward: bias, dropout, residual, fp32 out, LayerNorm of the result
-            EPI_CASE(0x10001541u)        // ... and the next block's QKV projection of those LayerNorm rows (second GEMM)
-            EPI_CASE(0x001521u)          // last FFN-2 forward: ... and the mean over tokens instead of the LayerNorm
-            EPI_CASE(0x000800u)          // plain data gradient, bf16 out
-            EPI_CASE(0x002d01u)          // data gradient + LayerNorm backward: skip gradient in, fp32 and masked bf16 out
-            EPI_CASE(0x10002d01u)        // ... and the data gradient of the Linear under that LayerNorm's skip path (second GEMM)
-            EPI_CASE(0x002401u)          // the same without the bf16 copy (first block)
-            EPI_CASE(0x1006401u)         // ... + the BatchNorm-backward reduce of the conv block below the stack (GELU)
+            EPI_CASE(EF_SHIFT | EF_F32 | EF_DROP | EF_RES | EF_LNF)   // out-proj / FFN-2 forward: bias, dropout, residual, fp32 out, LayerNorm of the result
+            EPI_CASE(EF_SHIFT | EF_F32 | EF_DROP | EF_RES | EF_LNF | EF_GEMM2)   // ... and the next block's QKV projection of those LayerNorm rows (second GEMM)
+            EPI_CASE(EF_SHIFT | EF_F32 | EF_DROP | EF_RES | EF_POOLOUT)   // last FFN-2 forward: ... and the mean over tokens instead of the LayerNorm
+            EPI_CASE(EF_BF16)   // plain data gradient, bf16 out
+            EPI_CASE(EF_LNBWD | EF_RES | EF_F32 | EF_BF16 | EF_DROP)   // data gradient + LayerNorm backward: skip gradient in, fp32 and masked bf16 out
+            EPI_CASE(EF_LNBWD | EF_RES | EF_F32 | EF_BF16 | EF_DROP | EF_GEMM2)   // ... and the data gradient of the Linear under that LayerNorm's skip path (second GEMM)
+            EPI_CASE(EF_LNBWD | EF_RES | EF_F32)   // the same without the bf16 copy (first block)
+            EPI_CASE(EF_LNBWD | EF_RES | EF_F32 | EF_BNRED | ef_act(MM_ACT_GELU, EFA_BN))   // ... + the BatchNorm-backward reduce of the conv block below the stack (GELU)
             default: break;
         }
     } else if constexpr (BM == 64 && BN == 64 && KCT == 64) {
         constexpr int LT = 0;                 // k = 3, 5, 7 convolutions: tap count at run time
         switch (m) {
-            EPI_CASE(0x001410u)          // conv block forward: bias, BatchNorm sums, fp32 out
-            EPI_CASE(0x000800u)          // conv data gradient, bf16 out
-            EPI_CASE(0x1004800u)         // ... + the BatchNorm-backward reduce of the layer below (GELU)
-            EPI_CASE(0x100c800u)         // ... the same below a MaxPool1d(2)
+            EPI_CASE(EF_SHIFT | EF_F32 | EF_STATS)   // conv block forward: bias, BatchNorm sums, fp32 out
+            EPI_CASE(EF_BF16)   // conv data gradient, bf16 out
+            EPI_CASE(EF_BF16 | EF_BNRED | ef_act(MM_ACT_GELU, EFA_BN))   // ... + the BatchNorm-backward reduce of the layer below (GELU)
+            EPI_CASE(EF_BF16 | EF_BNRED | EF_BNPOOL2 | ef_act(MM_ACT_GELU, EFA_BN))   // ... the same below a MaxPool1d(2)
             default: break;
         }
     }
@@ -1397,7 +1401,24 @@ int mm_conv1d_fwd_splitk_plan(int B, int T, int Cin, int Cout, int taps, int* ns
 static int conv1d_fwd_args(ConvArgs& a, const void* x, const void* w, int B, int T, int Cin, int Cout, int taps, int pad,
                            const float* scale, const float* shift, int act, const float* residual, const float* pe,
                            int pool, float* stats, float* out_f32, void* out_bf16, void* out_pre,
-                           float drop_p, uint32_t drop_seed, const uint32_t* seed_epoch, const void* gradz, int gradz_act);
+                           float drop_p, uint32_t drop_seed, const uint32_t* seed_epoch, const void* gradz, int gradz_act) {
+    MM_REQUIRE(x && w, "conv1d_fwd: null operand");
+    MM_REQUIRE(B > 0 && T > 0 && Cout > 0 && taps >= 1 && taps <= 9 && pad >= 0 && pad < taps, "conv1d_fwd: bad dims");
+    MM_REQUIRE(Cin > 0 && Cin % 16 == 0, "conv1d_fwd: Cin=%d must be a multiple of 16", Cin);
+    MM_REQUIRE(pool == 1 || (pool == 2 && T % 2 == 0), "conv1d_fwd: pool=%d T=%d", pool, T);
+    MM_REQUIRE(out_f32 || out_bf16 || out_pre, "conv1d_fwd: no output");
+    MM_REQUIRE(Cout % 4 == 0, "conv1d_fwd: Cout=%d must be a multiple of 4", Cout);
+    MM_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "conv1d_fwd: drop_p");
+    a.x = (const bf16*)x; a.w = (const bf16*)w;
+    a.B = B; a.T = T; a.Cin = Cin; a.Cout = Cout; a.taps = taps; a.pad = pad;
+    a.e.scale = scale; a.e.shift = shift; a.e.residual = residual; a.e.pe = pe; a.e.stats = stats;
+    a.e.out_f32 = out_f32; a.e.out_bf16 = (bf16*)out_bf16; a.e.out_pre = (bf16*)out_pre;
+    a.e.act = act; a.e.pool = pool;
+    const DropH d = mm_drop(drop_p);
+    a.e.drop_thresh = d.thresh; a.e.drop_inv_keep = d.inv_keep; a.e.drop_seed = drop_seed; a.e.drop_epoch = seed_epoch;
+    a.e.gradz = (const bf16*)gradz; a.e.gradz_act = gradz_act;
+    return 0;
+}
 
 int mm_conv1d_fwd_splitk(const void* x, const void* w, int B, int T, int Cin, int Cout, int taps, int pad,
                          const float* scale, const float* shift, int act, const float* residual, const float* pe,
@@ -1429,33 +1450,6 @@ int mm_conv1d_fwd(const void* x, const void* w, int B, int T, int Cin, int Cout,
     return rc ? rc : conv1d_dispatch(a, st);
 }
 
-static int conv1d_fwd_args(ConvArgs& a, const void* x, const void* w, int B, int T, int Cin, int Cout, int taps, int pad,
-                           const float* scale, const float* shift, int act, const float* residual, const float* pe,
-                           int pool, float* stats, float* out_f32, void* out_bf16, void* out_pre,
-                           float drop_p, uint32_t drop_seed, const uint32_t* seed_epoch, const void* gradz, int gradz_act) {
-    MM_REQUIRE(x && w, "conv1d_fwd: null operand");
-    MM_REQUIRE(B > 0 && T > 0 && Cout > 0 && taps >= 1 && taps <= 9 && pad >= 0 && pad < taps, "conv1d_fwd: bad dims");
-    MM_REQUIRE(Cin > 0 && Cin % 16 == 0, "conv1d_fwd: Cin=%d must be a multiple of 16", Cin);
-    MM_REQUIRE(pool == 1 || (pool == 2 && T % 2 == 0), "conv1d_fwd: pool=%d T=%d", pool, T);
-    MM_REQUIRE(out_f32 || out_bf16 || out_pre, "conv1d_fwd: no output");
-    MM_REQUIRE(Cout % 4 == 0, "conv1d_fwd: Cout=%d must be a multiple of 4", Cout);
-    MM_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "conv1d_fwd: drop_p");
-    a.x = (const bf16*)x; a.w = (const bf16*)w;
-    a.B = B; a.T = T; a.Cin = Cin; a.Cout = Cout; a.taps = taps; a.pad = pad;
-    a.e.scale = scale; a.e.shift = shift; a.e.residual = residual; a.e.pe = pe; a.e.stats = stats;
-    a.e.out_f32 = out_f32; a.e.out_bf16 = (bf16*)out_bf16; a.e.out_pre = (bf16*)out_pre;
-    a.e.act = act; a.e.pool = pool;
-    a.e.drop_thresh = drop_p > 0.f ? (uint32_t)((double)drop_p * 4294967296.0) : 0u;
-    a.e.drop_seed = drop_seed;
-    a.e.drop_epoch = seed_epoch;
-    a.e.gradz = (const bf16*)gradz; a.e.gradz_act = gradz_act;
-    a.e.drop_inv_keep = drop_p > 0.f ? 1.0f / (1.0f - drop_p) : 1.f;
-    a.e.ln_x = nullptr; a.e.ln_stat = nullptr; a.e.ln_gamma = nullptr; a.e.ln_dgb = nullptr;
-    a.e.pool_out = nullptr; a.e.pool_rows = 0; a.e.pool_scale = 0.f;
-    a.e.lnf_out = nullptr; a.e.lnf_stat = nullptr; a.e.lnf_gamma = nullptr; a.e.lnf_beta = nullptr; a.e.lnf_eps = 0.f;
-    return 0;
-}
-
 // Data-gradient convolution of a conv block (dy (B, T, Cin) bf16 x that block's dgrad weight image -> dx (B, T, Cout)
 // bf16) with the BatchNorm-backward REDUCE pass of the block below as its epilogue: dx is that block's d(out), and its
 // sums (sum dz | sum dz * xhat over the B * T * pool pre-BN rows y_below) land in sums_below exactly as
@@ -1474,20 +1468,23 @@ int mm_conv1d_dgrad_bn_reduce(const void* dy, const void* w_dgrad, int B, int T,
     ConvArgs a;
     a.x = (const bf16*)dy; a.w = (const bf16*)w_dgrad;
     a.B = B; a.T = T; a.Cin = Cin; a.Cout = Cout; a.taps = taps; a.pad = pad;
-    a.e.scale = nullptr; a.e.shift = nullptr; a.e.residual = nullptr; a.e.pe = nullptr; a.e.stats = nullptr;
-    a.e.out_f32 = nullptr; a.e.out_bf16 = (bf16*)dx_bf16; a.e.out_pre = nullptr;
-    a.e.act = 0; a.e.pool = 1;
-    a.e.drop_thresh = 0u; a.e.drop_seed = 0u; a.e.drop_epoch = nullptr; a.e.drop_inv_keep = 1.f;
-    a.e.gradz = nullptr; a.e.gradz_act = 0;
-    a.e.ln_x = nullptr; a.e.ln_stat = nullptr; a.e.ln_gamma = nullptr; a.e.ln_dgb = nullptr;
-    a.e.pool_out = nullptr; a.e.pool_rows = 0; a.e.pool_scale = 0.f;
-    a.e.lnf_out = nullptr; a.e.lnf_stat = nullptr; a.e.lnf_gamma = nullptr; a.e.lnf_beta = nullptr; a.e.lnf_eps = 0.f;
+    a.e.out_bf16 = (bf16*)dx_bf16;
     a.e.bn.y = y_below; a.e.bn.out4 = out4_below; a.e.bn.sums = sums_below;
     a.e.bn.act = act; a.e.bn.pool = pool; a.e.bn.drop_first = drop_first;
-    a.e.bn.thresh = drop_p > 0.f ? (uint32_t)((double)drop_p * 4294967296.0) : 0u;
-    a.e.bn.seed = seed; a.e.bn.inv_keep = drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f;
-    a.e.bn.epoch = seed_epoch;
+    const DropH d = mm_drop(drop_p);
+    a.e.bn.thresh = d.thresh; a.e.bn.inv_keep = d.inv_keep; a.e.bn.seed = seed; a.e.bn.epoch = seed_epoch;
     return conv1d_dispatch(a, st);
+}
+
+// a Linear with 128 outputs on the 32 x 128 tile (the fused LayerNorm epilogues hold a whole row in one workgroup),
+// at the widest chunk that divides K
+static int launch_fwd_32x128(const ConvArgs& a, hipStream_t st) {
+    switch (a.Cin % 128 == 0 ? 128 : (a.Cin % 64 == 0 ? 64 : (a.Cin % 32 == 0 ? 32 : 16))) {
+        case 16: return launch_fwd<32, 128, 1, 4, 16>(a, st);
+        case 32: return launch_fwd<32, 128, 1, 4, 32>(a, st);
+        case 64: return launch_fwd<32, 128, 1, 4, 64>(a, st);
+        default: return launch_fwd<32, 128, 1, 4, 128>(a, st);
+    }
 }
 
 // y = dropout(x W^T + b) + residual, fp32 rows of width 128 (a transformer sub-layer's output), with up to two
@@ -1506,32 +1503,20 @@ static int linear128_fwd(const void* x, const void* w, int M, int K, const float
     ConvArgs a;
     a.x = (const bf16*)x; a.w = (const bf16*)w;
     a.B = 1; a.T = M; a.Cin = K; a.Cout = 128; a.taps = 1; a.pad = 0;
-    a.e.scale = nullptr; a.e.shift = bias; a.e.residual = residual; a.e.pe = nullptr; a.e.stats = nullptr;
-    a.e.out_f32 = out_f32; a.e.out_bf16 = nullptr; a.e.out_pre = nullptr;
-    a.e.act = 0; a.e.pool = 1;
-    a.e.drop_thresh = drop_p > 0.f ? (uint32_t)((double)drop_p * 4294967296.0) : 0u;
-    a.e.drop_seed = seed; a.e.drop_epoch = seed_epoch;
-    a.e.drop_inv_keep = drop_p > 0.f ? 1.0f / (1.0f - drop_p) : 1.f;
-    a.e.gradz = nullptr; a.e.gradz_act = 0;
-    a.e.ln_x = nullptr; a.e.ln_stat = nullptr; a.e.ln_gamma = nullptr; a.e.ln_dgb = nullptr;
-    a.e.pool_out = pool_out; a.e.pool_rows = pool_out ? rows_per_group : 0;
-    a.e.pool_scale = pool_out ? 1.f / (float)rows_per_group : 0.f;
+    a.e.shift = bias; a.e.residual = residual; a.e.out_f32 = out_f32;
+    const DropH d = mm_drop(drop_p);
+    a.e.drop_thresh = d.thresh; a.e.drop_inv_keep = d.inv_keep; a.e.drop_seed = seed; a.e.drop_epoch = seed_epoch;
+    if (pool_out) { a.e.pool_out = pool_out; a.e.pool_rows = rows_per_group; a.e.pool_scale = 1.f / (float)rows_per_group; }
     a.e.lnf_out = (bf16*)ln_out; a.e.lnf_stat = ln_stat; a.e.lnf_gamma = ln_gamma; a.e.lnf_beta = ln_beta; a.e.lnf_eps = ln_eps;
     if (w2) {
         MM_REQUIRE(ln_out && out2 && n2 > 0 && n2 % 128 == 0, "linear128_fwd: the second GEMM needs the LayerNorm rows, an output and n2 %% 128 == 0 (n2=%d)", n2);
         MM_REQUIRE(drop2_p >= 0.f && drop2_p < 1.f && (size_t)M * n2 < (1ull << 32), "linear128_fwd: second GEMM dropout / 32-bit indices");
         a.e.w2 = (const bf16*)w2; a.e.bias2 = bias2; a.e.n2 = n2; a.e.out2 = (bf16*)out2;
         a.e.act2 = act2; a.e.pre2 = (bf16*)pre2;
-        a.e.thresh2 = drop2_p > 0.f ? (uint32_t)((double)drop2_p * 4294967296.0) : 0u;
-        a.e.seed2 = seed2; a.e.inv_keep2 = drop2_p > 0.f ? 1.0f / (1.0f - drop2_p) : 1.f;
+        const DropH d2 = mm_drop(drop2_p);
+        a.e.thresh2 = d2.thresh; a.e.inv_keep2 = d2.inv_keep; a.e.seed2 = seed2;
     }
-    const int kct = (K % 128 == 0) ? 128 : (K % 64 == 0 ? 64 : (K % 32 == 0 ? 32 : 16));
-    switch (kct) {
-        case 16: return launch_fwd<32, 128, 1, 4, 16>(a, st);
-        case 32: return launch_fwd<32, 128, 1, 4, 32>(a, st);
-        case 64: return launch_fwd<32, 128, 1, 4, 64>(a, st);
-        default: return launch_fwd<32, 128, 1, 4, 128>(a, st);
-    }
+    return launch_fwd_32x128(a, st);
 }
 
 int mm_linear_fwd_meanpool(const void* x, const void* w, int M, int K, const float* bias, const float* residual,
@@ -1591,27 +1576,15 @@ static int linear_dgrad_ln_bwd(const void* dy, const void* w, int M, int K, cons
     ConvArgs a;
     a.x = (const bf16*)dy; a.w = (const bf16*)w;
     a.B = 1; a.T = M; a.Cin = K; a.Cout = 128; a.taps = 1; a.pad = 0;
-    a.e.scale = nullptr; a.e.shift = nullptr; a.e.residual = dres; a.e.pe = nullptr; a.e.stats = nullptr;
-    a.e.out_f32 = dx; a.e.out_bf16 = (bf16*)dx_bf16; a.e.out_pre = nullptr;
-    a.e.act = 0; a.e.pool = 1;
-    a.e.drop_thresh = drop_p > 0.f ? (uint32_t)((double)drop_p * 4294967296.0) : 0u;
-    a.e.drop_seed = seed; a.e.drop_epoch = seed_epoch;
-    a.e.drop_inv_keep = drop_p > 0.f ? 1.0f / (1.0f - drop_p) : 1.f;
-    a.e.gradz = nullptr; a.e.gradz_act = 0;
+    a.e.residual = dres; a.e.out_f32 = dx; a.e.out_bf16 = (bf16*)dx_bf16;
+    const DropH d = mm_drop(drop_p);
+    a.e.drop_thresh = d.thresh; a.e.drop_inv_keep = d.inv_keep; a.e.drop_seed = seed; a.e.drop_epoch = seed_epoch;
     a.e.ln_x = x; a.e.ln_stat = stat; a.e.ln_gamma = gamma; a.e.ln_dgb = dgb_repl;
-    a.e.pool_out = nullptr; a.e.pool_rows = 0; a.e.pool_scale = 0.f;
-    a.e.lnf_out = nullptr; a.e.lnf_stat = nullptr; a.e.lnf_gamma = nullptr; a.e.lnf_beta = nullptr; a.e.lnf_eps = 0.f;
     if (bn) a.e.bn = *bn;
     a.e.w2 = (const bf16*)w2; a.e.out2 = (bf16*)out2;
     MM_REQUIRE(res_rows >= 0 && (!res_rows || (dres && M % res_rows == 0 && (size_t)M < (1ull << 32))), "linear_dgrad_ln_bwd: res_rows=%d", res_rows);
     a.e.res_rows = res_rows;
-    const int kct = (K % 128 == 0) ? 128 : (K % 64 == 0 ? 64 : (K % 32 == 0 ? 32 : 16));
-    switch (kct) {
-        case 16: return launch_fwd<32, 128, 1, 4, 16>(a, st);
-        case 32: return launch_fwd<32, 128, 1, 4, 32>(a, st);
-        case 64: return launch_fwd<32, 128, 1, 4, 64>(a, st);
-        default: return launch_fwd<32, 128, 1, 4, 128>(a, st);
-    }
+    return launch_fwd_32x128(a, st);
 }
 
 int mm_linear_dgrad_ln_bwd(const void* dy, const void* w, int M, int K, const float* x, const float* stat,
@@ -1649,10 +1622,9 @@ int mm_linear_dgrad_ln_bwd_bn_reduce(const void* dy, const void* w, int M, int K
     MM_REQUIRE((size_t)M * 128 < (1ull << 32), "linear_dgrad_ln_bwd_bn_reduce: 32-bit dropout indices");
     BnRed bn;
     bn.y = y_below; bn.out4 = out4_below; bn.sums = sums_below; bn.act = act; bn.pool = 1; bn.drop_first = 1;
-    bn.thresh = bn_drop_p > 0.f ? (uint32_t)((double)bn_drop_p * 4294967296.0) : 0u;
-    bn.seed = bn_seed; bn.inv_keep = bn_drop_p > 0.f ? 1.f / (1.f - bn_drop_p) : 1.f;
-    bn.thresh2 = bn_drop2_p > 0.f ? (uint32_t)((double)bn_drop2_p * 4294967296.0) : 0u;
-    bn.seed2 = bn_seed2; bn.inv_keep2 = bn_drop2_p > 0.f ? 1.f / (1.f - bn_drop2_p) : 1.f;
+    const DropH d = mm_drop(bn_drop_p), d2 = mm_drop(bn_drop2_p);
+    bn.thresh = d.thresh; bn.inv_keep = d.inv_keep; bn.seed = bn_seed;
+    bn.thresh2 = d2.thresh; bn.inv_keep2 = d2.inv_keep; bn.seed2 = bn_seed2;
     bn.epoch = seed_epoch;
     return linear_dgrad_ln_bwd(dy, w, M, K, x, stat, gamma, dres, dx, nullptr, dgb_repl, 0.f, 0u, seed_epoch, &bn, st);
 }

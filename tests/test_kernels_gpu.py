@@ -1576,3 +1576,25 @@ def test_power_merge_modes(cin):
         assert torch.equal(gw[i], want_g)
         assert torch.equal(gb[i], 1.0 + dB[64 * i:64 * i + 64] if i != 2 else torch.ones(64, device=dev))
         assert torch.equal(gg[i], 1.0 + dG[64 * i:64 * i + 64]) and torch.equal(gbe[i], 1.0 + dBe[64 * i:64 * i + 64])
+
+
+@pytest.mark.parametrize("p", [0.0, 0.1, 0.5, 0.99999994])
+def test_entry_points_in_different_files_share_one_dropout_conversion(p):
+    """Every launch converts the caller's drop_p to (thresh, inv_keep) through csrc/common.h's mm_drop.  mm_act_f32 and
+    mm_drop_path (heads.hip) and mm_act_bwd (elementwise.hip, bf16 out) all hash (seed, element index) against thresh
+    and scale by inv_keep: on ones they must draw the same mask and the same scale, the float32 1 / (1 - p).
+    0.99999994 is the largest float32 below 1."""
+    hip = _hip()
+    n, seed = 4096, 20240611
+    x = torch.ones(n, device="cuda")
+    y_act, y_path = torch.empty_like(x), torch.empty_like(x)
+    y_bf = torch.empty(n, dtype=torch.bfloat16, device="cuda")
+    hip.call("mm_act_f32", x, y_act, n, 0, p, seed, None)
+    hip.call("mm_drop_path", x, y_path, n, 1, p, seed, None)
+    hip.call("mm_act_bwd", None, x.to(torch.bfloat16), None, y_bf, n, 0, p, seed, None)
+    assert torch.equal(y_act, y_path)
+    assert torch.equal(y_bf, y_act.to(torch.bfloat16))
+    inv_keep = (torch.ones((), dtype=torch.float32) / (torch.ones((), dtype=torch.float32) - torch.tensor(p, dtype=torch.float32))).item()
+    assert bool(((y_act == 0) | (y_act == inv_keep)).all())
+    if p == 0.0:
+        assert torch.equal(y_act, x)
