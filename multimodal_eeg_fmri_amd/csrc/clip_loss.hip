@@ -1,0 +1,271 @@
+// The fused batch-pairwise cosine-similarity / symmetric InfoNCE loss of the contrastive bridge with its gradients, for
+// plain and for subject-grouped positives: one kernel pair, four entry points.  Callers: ops.clip_loss_own_rows* and
+// ops.clip_loss*_ws_floats (bridge_trainer.py's step, autograd.py's tape).
+#include "common.h"
+
+namespace {
+// ---------------------------------------------------------------------------
+// symmetric InfoNCE over the gathered batch, bit-reproducible (no float atomics).
+//   C[r][j] = ze_r . zf_j  (cosines; Bg x Bg),  s = exp(logit_scale)
+//   e->f problem = row softmax of s C, f->e problem = column softmax of s C
+//   loss_r = 0.5 * (CE(row r, target r) + CE(column r, target r))
+// This rank owns rows/columns [row0, row0 + B).  Its step loss is mean_r loss_r over its own r; the
+// gradient it needs is that of the SUM over all ranks' losses w.r.t. its own embeddings (what a
+// reduce-scatter of every rank's d loss_rank / d z_all would deliver; AdamW applies the 1/world):
+//   dL/dC[r][j] = 0.5/B * s * (P_row[r][j] + P_col[r][j] - 2 delta_rj)
+//   dze_r = sum_j dL/dC[r][j] zf_j        dzf_r = sum_j dL/dC[j][r] ze_j
+// P_col[r][j] needs column j's normaliser, P_row[j][r] row j's: a global dependency, so two launches:
+//   clip_lse_kernel  (one workgroup per GLOBAL row r): row r and column r of C -> their log-sum-exp,
+//                     the row's loss / top-1 flags / d loss_r / d logit_scale            -> ws[6][Bg]
+//   clip_rows_kernel (one workgroup per OWN row): recomputes its row and column of C, forms dL/dC from
+//                     ws, writes dz[own row] with plain stores; workgroup 0 also sums the own rows'
+//                     scalars in a fixed order into scal[4] = {loss, top1 e->f, top1 f->e, d/d logit_scale}.
+// Every sum runs in a fixed order (lane-strided partials, xor-shuffle trees, fixed wave order).
+//
+// GROUPED: the same InfoNCE with subject-grouped positives (MIL-NCE, "log of the positive mass").  gid[Bg] int32: pairs
+// with equal ids are positives of each other; P(r) = {j : gid_j = gid_r} always holds r.
+//   l_row(r) = LSE_j(s C[r][j]) - LSE_{j in P(r)}(s C[r][j]),  l_col(r) the same over column r,  loss_r = 0.5 (l_row + l_col)
+//   dL/dC[r][j] = 0.5/B * s * (P_row + P_col - [gid_r = gid_j] (Q_row + Q_col))[r][j]
+// Q = the softmax restricted to the positive set: Q_row[r][j] = exp(s C[r][j] - LSE_P(row r)), Q_col[r][j] =
+// exp(s C[r][j] - LSE_P(column j)).  Same two launches and rules as above; ws[8][Bg] = the six rows of the ungrouped
+// layout (row / column LSE, loss, top-1 flags, d loss / d logit_scale) + the positive-set LSE of every row and column.
+// With all-distinct ids every positive-set LSE is s C[r][r] + log 1 and the result is the ungrouped one (in exact
+// arithmetic: the ungrouped instantiation keeps its own formulas).  gid is the LAST kernel argument: the ungrouped
+// instantiation never reads it (null there), and its other arguments keep their offsets.
+// ---------------------------------------------------------------------------
+struct ClipShared {
+    float *qe, *qf, *cr, *cc, *red;
+};
+__device__ __forceinline__ ClipShared clip_shared(float* sm, int N, int Bg) {
+    ClipShared s;
+    s.qe = sm; s.qf = sm + N; s.cr = s.qf + N; s.cc = s.cr + Bg; s.red = s.cc + Bg;
+    return s;
+}
+// cr[j] = ze_r . zf_j, cc[j] = ze_j . zf_r for all j (8 lanes per column, float4 strides); returns the
+// two maxima in every thread
+__device__ __forceinline__ void clip_cosines(const float* __restrict__ z_all, int r, int Bg, int N, const ClipShared& sh,
+                                             float& mxr, float& mxc) {
+    const int LD = 2 * N, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    for (int n = tid; n < N; n += 256) { sh.qe[n] = z_all[(size_t)r * LD + n]; sh.qf[n] = z_all[(size_t)r * LD + N + n]; }
+    __syncthreads();
+    float a_mx = -INFINITY, c_mx = -INFINITY;
+    const int sub = tid & 7, n32 = N & ~31;                // the float4 sweep covers whole 32-element chunks only
+    for (int j = tid >> 3; j < Bg; j += 32) {
+        float a = 0.f, c = 0.f;
+        const float* re = z_all + (size_t)j * LD;
+        const float* rf = re + N;
+        for (int n = sub * 4; n < n32; n += 32) {
+            const float4 vf = *reinterpret_cast<const float4*>(rf + n);
+            const float4 ve = *reinterpret_cast<const float4*>(re + n);
+            a += sh.qe[n] * vf.x + sh.qe[n + 1] * vf.y + sh.qe[n + 2] * vf.z + sh.qe[n + 3] * vf.w;
+            c += sh.qf[n] * ve.x + sh.qf[n + 1] * ve.y + sh.qf[n + 2] * ve.z + sh.qf[n + 3] * ve.w;
+        }
+        for (int n = n32 + sub; n < N; n += 8) { a += sh.qe[n] * rf[n]; c += sh.qf[n] * re[n]; }   // N % 32 tail
+#pragma unroll
+        for (int o = 4; o > 0; o >>= 1) { a += __shfl_xor(a, o, 64); c += __shfl_xor(c, o, 64); }
+        if (sub == 0) { sh.cr[j] = a; sh.cc[j] = c; }
+        a_mx = fmaxf(a_mx, a); c_mx = fmaxf(c_mx, c);
+    }
+    a_mx = wave_max(a_mx); c_mx = wave_max(c_mx);
+    if (lane == 0) { sh.red[wave] = a_mx; sh.red[4 + wave] = c_mx; }
+    __syncthreads();
+    mxr = fmaxf(fmaxf(sh.red[0], sh.red[1]), fmaxf(sh.red[2], sh.red[3]));
+    mxc = fmaxf(fmaxf(sh.red[4], sh.red[5]), fmaxf(sh.red[6], sh.red[7]));
+    __syncthreads();
+}
+// fixed-order workgroup sum / maximum of two values (4 waves)
+__device__ __forceinline__ void clip_sum2(float& a, float& c, float* red) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    a = wave_sum(a); c = wave_sum(c);
+    if (lane == 0) { red[wave] = a; red[4 + wave] = c; }
+    __syncthreads();
+    a = (red[0] + red[1]) + (red[2] + red[3]);
+    c = (red[4] + red[5]) + (red[6] + red[7]);
+    __syncthreads();
+}
+__device__ __forceinline__ void clip_max2(float& a, float& c, float* red) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    a = wave_max(a); c = wave_max(c);
+    if (lane == 0) { red[wave] = a; red[4 + wave] = c; }
+    __syncthreads();
+    a = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+    c = fmaxf(fmaxf(red[4], red[5]), fmaxf(red[6], red[7]));
+    __syncthreads();
+}
+
+template <bool GROUPED>
+__global__ __launch_bounds__(256) void clip_lse_kernel(const float* __restrict__ z_all, const float* __restrict__ logit_scale,
+                                                       float* __restrict__ ws, int Bg, int N, const int* __restrict__ gid) {
+    extern __shared__ float sm[];
+    const ClipShared sh = clip_shared(sm, N, Bg);
+    const int r = blockIdx.x, tid = threadIdx.x;
+    const float s = __expf(logit_scale[0]);
+    int gr = 0;
+    if constexpr (GROUPED) gr = gid[r];
+    float mxr, mxc;
+    clip_cosines(z_all, r, Bg, N, sh, mxr, mxc);
+    float pmr = -INFINITY, pmc = -INFINITY;                  // maxima over the positive set (the top-1 test and the stable LSE)
+    if constexpr (GROUPED) {
+        for (int j = tid; j < Bg; j += 256)
+            if (gid[j] == gr) { pmr = fmaxf(pmr, sh.cr[j]); pmc = fmaxf(pmc, sh.cc[j]); }
+        clip_max2(pmr, pmc, sh.red);
+    }
+    float se = 0.f, sf = 0.f, ee = 0.f, ef = 0.f;           // all columns: sum exp, sum exp * cos
+    float qe = 0.f, qf = 0.f, qee = 0.f, qef = 0.f;         // the positive set
+    for (int j = tid; j < Bg; j += 256) {
+        const float a = sh.cr[j], c = sh.cc[j];
+        const float pa = __expf(s * (a - mxr)), pc = __expf(s * (c - mxc));
+        se += pa; sf += pc; ee += pa * a; ef += pc * c;
+        if constexpr (GROUPED) {
+            if (gid[j] == gr) {
+                const float qa = __expf(s * (a - pmr)), qc = __expf(s * (c - pmc));
+                qe += qa; qf += qc; qee += qa * a; qef += qc * c;
+            }
+        }
+    }
+    clip_sum2(se, sf, sh.red);
+    clip_sum2(ee, ef, sh.red);
+    if constexpr (GROUPED) {
+        clip_sum2(qe, qf, sh.red);
+        clip_sum2(qee, qef, sh.red);
+    }
+    if (tid == 0) {
+        if constexpr (GROUPED) {
+            const float lse_r = s * mxr + __logf(se), lse_c = s * mxc + __logf(sf);
+            const float lsp_r = s * pmr + __logf(qe), lsp_c = s * pmc + __logf(qf);
+            ws[r] = lse_r;
+            ws[Bg + r] = lse_c;
+            ws[2 * Bg + r] = 0.5f * ((lse_r - lsp_r) + (lse_c - lsp_c));
+            ws[3 * Bg + r] = pmr >= mxr ? 1.f : 0.f;         // the best positive reaches the row maximum (a tie counts FOR it)
+            ws[4 * Bg + r] = pmc >= mxc ? 1.f : 0.f;
+            ws[5 * Bg + r] = s * 0.5f * ((ee / se - qee / qe) + (ef / sf - qef / qf));
+            ws[6 * Bg + r] = lsp_r;
+            ws[7 * Bg + r] = lsp_c;
+        } else {
+            const float diag = sh.cr[r];
+            const float lse_r = s * mxr + __logf(se), lse_c = s * mxc + __logf(sf);
+            ws[r] = lse_r;
+            ws[Bg + r] = lse_c;
+            ws[2 * Bg + r] = 0.5f * ((lse_r - s * diag) + (lse_c - s * sh.cc[r]));
+            // top-1: a tie with the row maximum counts FOR the pair (diag >= max).  mm_retrieval's rank counts a tie
+            // AGAINST the query (csrc/retrieval.hip), so a collapsed encoder ranks Ng there but scores top-1 = 1 here.
+            ws[3 * Bg + r] = diag >= mxr ? 1.f : 0.f;
+            ws[4 * Bg + r] = sh.cc[r] >= mxc ? 1.f : 0.f;
+            // d loss_r / d logit_scale = s * 0.5 * (E_row[cos] - cos_rr + E_col[cos] - cos_rr)
+            ws[5 * Bg + r] = s * 0.5f * ((ee / se - diag) + (ef / sf - sh.cc[r]));
+        }
+    }
+}
+
+template <bool GROUPED>
+__global__ __launch_bounds__(256) void clip_rows_kernel(const float* __restrict__ z_all, const float* __restrict__ logit_scale,
+                                                        const float* __restrict__ ws, float* __restrict__ scal,
+                                                        float* __restrict__ dz, int B, int Bg, int N, int row0,
+                                                        const int* __restrict__ gid) {
+    extern __shared__ float sm[];
+    const ClipShared sh = clip_shared(sm, N, Bg);
+    const int i = blockIdx.x, gi = row0 + i, tid = threadIdx.x, LD = 2 * N;
+    const float s = __expf(logit_scale[0]);
+    const float invB = 1.f / (float)B;
+    if (i == 0 && tid < 64) {                               // the own rows' scalars, summed in a fixed order
+        float acc[4] = {0.f, 0.f, 0.f, 0.f};
+        for (int r0 = 0; r0 < B; r0 += 64) {
+            float v[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) v[q] = (r0 + tid < B) ? ws[(size_t)(2 + q) * Bg + row0 + r0 + tid] : 0.f;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) acc[q] += wave_sum(v[q]);
+        }
+        if (tid < 4) scal[tid] = (tid == 0 ? acc[0] : tid == 1 ? acc[1] : tid == 2 ? acc[2] : acc[3]) * invB;
+    }
+    if (!dz) return;
+    float mxr, mxc;
+    clip_cosines(z_all, gi, Bg, N, sh, mxr, mxc);
+    // dL/dC[gi][j] -> cr[j],  dL/dC[j][gi] -> cc[j]
+    const float lse_rg = ws[gi], lse_cg = ws[Bg + gi];
+    float lsp_rg = 0.f, lsp_cg = 0.f;
+    int gg = 0;
+    if constexpr (GROUPED) { lsp_rg = ws[6 * Bg + gi]; lsp_cg = ws[7 * Bg + gi]; gg = gid[gi]; }
+    const float k = 0.5f * invB * s;
+    for (int j = tid; j < Bg; j += 256) {
+        const float a = s * sh.cr[j], c = s * sh.cc[j];
+        float ga = __expf(a - lse_rg) + __expf(a - ws[Bg + j]);          // P_row[gi][j] + P_col[gi][j]
+        float gc = __expf(c - ws[j]) + __expf(c - lse_cg);               // P_row[j][gi] + P_col[j][gi]
+        if constexpr (GROUPED) {
+            if (gid[j] == gg) {
+                ga -= __expf(a - lsp_rg) + __expf(a - ws[7 * Bg + j]);   // Q_row[gi][j] + Q_col[gi][j]
+                gc -= __expf(c - ws[6 * Bg + j]) + __expf(c - lsp_cg);   // Q_row[j][gi] + Q_col[j][gi]
+            }
+        } else {
+            if (j == gi) { ga -= 2.f; gc -= 2.f; }
+        }
+        sh.cr[j] = k * ga; sh.cc[j] = k * gc;
+    }
+    __syncthreads();
+    float* orow = dz + (size_t)i * LD;
+    for (int n = tid; n < 2 * N; n += 256) {                // first half: dze (columns of zf), second half: dzf
+        const bool first = n < N;
+        const float* g = first ? sh.cr : sh.cc;
+        const float* col = z_all + (first ? N + n : n - N);
+        float acc = 0.f;
+        int j = 0;
+        for (; j + 8 <= Bg; j += 8) {                       // 8 loads in flight, summed in order
+            float v[8];
+#pragma unroll
+            for (int q = 0; q < 8; ++q) v[q] = col[(size_t)(j + q) * LD];
+#pragma unroll
+            for (int q = 0; q < 8; ++q) acc += g[j + q] * v[q];
+        }
+        for (; j < Bg; ++j) acc += g[j] * col[(size_t)j * LD];
+        orow[n] = acc;
+    }
+}
+}  // namespace
+
+extern "C" {
+// floats-per-Bg rows of the loss workspace: the only place the count is written (layout: see clip_lse_kernel)
+static int clip_ws_rows(bool grouped) { return grouped ? 8 : 6; }
+
+// the checks and the two launches of both loss entry points; gid = nullptr: the ungrouped loss
+static int clip_loss_launch(const char* who, const float* z_all, const int* gid, const float* logit_scale, float* scal4,
+                            float* dz_local, float* ws, int B, int Bg, int N, int row0, hipStream_t st) {
+    MM_REQUIRE(B > 0 && Bg >= B && row0 >= 0 && row0 + B <= Bg && N > 0, "%s: B=%d Bg=%d row0=%d", who, B, Bg, row0);
+    MM_REQUIRE(N % 4 == 0, "%s: N=%d must be a multiple of 4 (16-byte row loads)", who, N);
+    const size_t lds = (size_t)(2 * N + 2 * Bg + 32) * sizeof(float);
+    MM_REQUIRE(lds <= 64 * 1024, "%s: N/Bg too large for LDS", who);
+    const auto lse = gid ? clip_lse_kernel<true> : clip_lse_kernel<false>;
+    const auto rows = gid ? clip_rows_kernel<true> : clip_rows_kernel<false>;
+    hipLaunchKernelGGL(lse, dim3(Bg), dim3(256), lds, st, z_all, logit_scale, ws, Bg, N, gid);
+    char what[64];
+    snprintf(what, sizeof what, "%s(lse)", who);
+    int rc = mm_check_launch(what);
+    if (rc) return rc;
+    hipLaunchKernelGGL(rows, dim3(B), dim3(256), lds, st, z_all, logit_scale, ws, scal4, dz_local, B, Bg, N, row0, gid);
+    snprintf(what, sizeof what, "%s(rows)", who);
+    return mm_check_launch(what);
+}
+
+int mm_clip_loss_ws_floats(int B, int Bg, int* floats_host, hipStream_t) {
+    MM_REQUIRE(floats_host && B > 0 && Bg >= B, "clip_loss_ws_floats: bad args");
+    *floats_host = clip_ws_rows(false) * Bg;
+    return 0;
+}
+
+int mm_clip_loss_own_rows(const float* z_all, const float* logit_scale, float* scal4, float* dz_local, float* ws, int B,
+                          int Bg, int N, int row0, hipStream_t st) {
+    MM_REQUIRE(z_all && logit_scale && scal4 && ws, "clip_loss_own_rows: null");
+    return clip_loss_launch("clip_loss_own_rows", z_all, nullptr, logit_scale, scal4, dz_local, ws, B, Bg, N, row0, st);
+}
+
+int mm_clip_loss_grouped_ws_floats(int B, int Bg, int* floats_host, hipStream_t) {
+    MM_REQUIRE(floats_host && B > 0 && Bg >= B, "clip_loss_grouped_ws_floats: bad args");
+    *floats_host = clip_ws_rows(true) * Bg;
+    return 0;
+}
+
+int mm_clip_loss_own_rows_grouped(const float* z_all, const int* gid_all, const float* logit_scale, float* scal4, float* dz_local,
+                                  float* ws, int B, int Bg, int N, int row0, hipStream_t st) {
+    MM_REQUIRE(z_all && gid_all && logit_scale && scal4 && ws, "clip_loss_own_rows_grouped: null");
+    return clip_loss_launch("clip_loss_own_rows_grouped", z_all, gid_all, logit_scale, scal4, dz_local, ws, B, Bg, N, row0, st);
+}
+}  // extern "C"

@@ -314,6 +314,9 @@ static inline bool bn_fin_from_host(MmBnFin& f, const void* host, int N) {
 }
 
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
+// workgroups of 256 threads for a grid-stride sweep over n elements: at least one, at most `cap`.  No default cap: how far a
+// launch is allowed to spread is a decision of its call site (profiles/heads_split_ab.txt lists them)
+static inline int grid_for(size_t n, int cap) { size_t g = (n + 255) / 256; return (int)(g < (size_t)cap ? (g ? g : 1) : cap); }
 
 // ---- layout of a 3-D convolution weight image (k = 27).  Images are made by mm_prep_conv_weight / mm_prep_many and
 // consumed by mm_conv3d_fwd only, so the two agree on this function.  Plain: [row n][tap][channel c].  For the shapes

@@ -567,11 +567,6 @@ __global__ void add_pe_kernel(const float* __restrict__ x, const float* __restri
     }
 }
 
-inline int grid_for(size_t n, int block = 256, int cap = 4096) {
-    size_t g = (n + block - 1) / block;
-    return (int)(g < (size_t)cap ? (g ? g : 1) : cap);
-}
-
 }  // namespace
 
 extern "C" {
@@ -610,7 +605,7 @@ static int bn_act_fwd_common(const float* y, const float* scale, const float* sh
     // FIN: every workgroup re-reads the statistics workspace (256 N bytes) in its prologue: few, longer workgroups
     // with the finalize in the prologue every workgroup re-reads the statistics workspace, so few and longer ones:
     // three per CU (256 / 512 / 768 / 1 024 / 2 048: 0.788 / 0.770 / 0.766 / 0.771 / 0.770 ms per step, profiles/r04_fin_fold_and_third_stream_ab.txt)
-    int grid = grid_for(total, 256, with_fin ? 768 : 4096);
+    int grid = grid_for(total, with_fin ? 768 : 4096);
     if (ln_out) {
         MM_REQUIRE(N == 128 && pool == 1 && ln_gamma && ln_beta, "bn_act_fwd_ln: N=%d (128) pool=%d (1)", N, pool);
         // every 32-lane group must walk its rows together (cross-lane sums): total is a multiple of 32; a grid that
@@ -793,7 +788,7 @@ int mm_meanpool_fwd(const float* x, float* out_f32, void* out_bf16, int B, int L
 
 int mm_meanpool_bwd(const float* g, float* dx, int B, int L, int D, hipStream_t st) {
     MM_REQUIRE(g && dx, "meanpool_bwd: null");
-    hipLaunchKernelGGL(meanpool_bwd_kernel, dim3(grid_for((size_t)B * L * D)), dim3(256), 0, st, g, dx, B, L, D);
+    hipLaunchKernelGGL(meanpool_bwd_kernel, dim3(grid_for((size_t)B * L * D, 4096)), dim3(256), 0, st, g, dx, B, L, D);
     return mm_check_launch("meanpool_bwd");
 }
 
@@ -801,7 +796,7 @@ int mm_act_bwd(const float* g_f32, const void* g_bf16, const void* z, void* out,
                uint32_t seed, const uint32_t* seed_epoch, hipStream_t st) {
     MM_REQUIRE((g_f32 || g_bf16) && out && n > 0, "act_bwd: null");
     const DropH d = mm_drop(drop_p);
-    hipLaunchKernelGGL(act_bwd_kernel, dim3(grid_for((size_t)n)), dim3(256), 0, st, g_f32, (const bf16*)g_bf16,
+    hipLaunchKernelGGL(act_bwd_kernel, dim3(grid_for((size_t)n, 4096)), dim3(256), 0, st, g_f32, (const bf16*)g_bf16,
                        (const bf16*)z, (bf16*)out, (size_t)n, act, d.thresh, seed, d.inv_keep, seed_epoch);
     return mm_check_launch("act_bwd");
 }
@@ -813,7 +808,7 @@ int mm_add_pe(const float* x, const float* pe, float* out_f32, void* out_bf16, i
     MM_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "add_pe: drop_p");
     const size_t n4 = (size_t)B * L * D / 4;
     const DropH d = mm_drop(drop_p);
-    hipLaunchKernelGGL(add_pe_kernel, dim3(grid_for(n4)), dim3(256), 0, st, x, pe, out_f32, (bf16*)out_bf16, n4,
+    hipLaunchKernelGGL(add_pe_kernel, dim3(grid_for(n4, 4096)), dim3(256), 0, st, x, pe, out_f32, (bf16*)out_bf16, n4,
                        L * D / 4, d.thresh, seed, d.inv_keep, seed_epoch);
     return mm_check_launch("add_pe");
 }

@@ -5,7 +5,7 @@
 // Scores come from the exact fp32-input MFMA (v_mfma_f32_32x32x2_f32): each score is ONE ascending-d fmaf chain from
 // +0, the same bits wherever the pair sits in a tile.  The positive's score is computed by the same instruction in the
 // same order (pos_score_kernel), so an exact duplicate of the positive scores bit-equal to it and counts against the
-// query - the tie rule.  (The in-batch top-1 of heads.hip's clip_lse_kernel counts a tie FOR the query; see there.)
+// query - the tie rule.  (The in-batch top-1 of clip_loss.hip's clip_lse_kernel counts a tie FOR the query; see there.)
 //
 // Pass 1 (pos_score_kernel): s(q, pos[q]) for every query.
 // Pass 2 (retr_tile_kernel<RANK, TOPK>): workgroup (query block of 128, gallery slice) walks its slice in 128-wide

@@ -1,5 +1,5 @@
-"""GPU: the fp32 row kernels of csrc/heads.hip (and the small layout / reduction kernels next to them) against plain fp64
-references of the same operation, computed on the CPU from the kernels' own operands.
+"""GPU: the fp32 row kernels of csrc/heads.hip, fusion.hip, losses.hip and power_front.hip (and the small layout / reduction
+kernels next to them) against plain fp64 references of the same operation, computed on the CPU from the kernels' own operands.
 
   - both projection heads (mm_proj_heads_fwd / _bwd: Linear -> LayerNorm -> GELU(erf) -> Dropout -> F.normalize), every
     output and every gradient, across the backward's 32-row chunks (B > 32), all four NE = ceil(N / 64) instantiations, the
