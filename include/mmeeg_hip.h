@@ -337,6 +337,25 @@ int mm_meanpool_bwd(const float* g, float* dx, int B, int L, int D, hipStream_t 
  * (fmri_n floats, a multiple of 4, 16-byte aligned).  The captured step then starts at the first convolution. */
 int mm_stage_inputs(const float* eeg, void* eeg_packed_bf16, float* eeg_copy, int B, int C, int T, int Cp,
                     float* fmri_dst, const float* fmri_src, int64_t fmri_n, hipStream_t stream);
+/* EEG augmentation in front of a training step (reference: EEGTransforms, EEG_CODE/CrossModal_EEG_scr.ipynb, handed to
+ * the training datasets as transform=): per sample, with probability p_noise, Gaussian noise of noise_factor * std_b (the
+ * sample's unbiased standard deviation over its C * T values); with probability p_drop, n_drop channels set to 0.  The
+ * draws are counter based (csrc/augment.hip defines h(stream, index) and the five stream words the host derives from
+ * (seed, step, rank)); nothing is drawn from the dropout stream and no state lives on the device.  Two launches:
+ *   mm_eeg_augment_plan  fills `plan` (32-bit words, 8-byte aligned, plan_words of them): per sample S = 4 + ceil(C/32)
+ *     words rounded up to even - [0] noise scale fp32 (0 = off), [1] std_b fp32, [2] noise on, [3] drop on, [4..] channel
+ *     mask (bit c % 32 of word c / 32) - then, from word B * S, fp64 {sum, sum of squares} per chunk of each sample:
+ *     double[B][nchunk][2], nchunk = ceil(C*T / chunk), chunk = 4096 doubled until nchunk <= 64.  So plan_words >=
+ *     B * S + 4 * B * nchunk.  Words [0] and [1] are written by mm_stage_inputs_aug, which adds the partials in chunk order.
+ *   mm_stage_inputs_aug  = mm_stage_inputs on the augmented batch: eeg_packed_bf16 (B, T, Cp) and / or eeg_out_f32
+ *     (B, C, T) (either may be null, not both; not in place), packed == mm_pack_nct_bf16(fp32 output) bit for bit; the fMRI
+ *     copy as in mm_stage_inputs, or all three of its arguments null / 0 for the EEG alone.
+ * Refused before any launch: C * T < 2, B * C * ceil(T/2) >= 2^32, n_drop outside [1, C], a probability outside [0, 1]. */
+int mm_eeg_augment_plan(const float* x, uint32_t* plan, int64_t plan_words, int B, int C, int T, float p_noise, float p_drop,
+                        int n_drop, uint32_t s_noise, uint32_t s_drop, uint32_t s_keys, hipStream_t stream);
+int mm_stage_inputs_aug(const float* eeg, uint32_t* plan, int64_t plan_words, void* eeg_packed_bf16, float* eeg_out_f32,
+                        int B, int C, int T, int Cp, float noise_factor, uint32_t s_gauss_a, uint32_t s_gauss_b,
+                        float* fmri_dst, const float* fmri_src, int64_t fmri_n, hipStream_t stream);
 /* out = bf16( g * dropout_mask * act'(z) ) */
 int mm_act_bwd(const float* g_f32, const void* g_bf16, const void* z, void* out, int64_t n, int act,
                float drop_p, uint32_t seed, const uint32_t* seed_epoch, hipStream_t stream);

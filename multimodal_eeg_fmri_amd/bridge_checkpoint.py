@@ -9,8 +9,8 @@ The file is the container of the reference's loops and of `FlexibleTrainer.save_
   ``[p for p in trainer.parameters() if p.requires_grad]`` in ``parameters()`` order (the flat bucket is laid out by
   layer group, so its slices are mapped back to that order); the frozen half of the bridge has no entry;
 * ``bridge_trainer_state``: the optimizer words (step count, lr, ...), the hyperparameters, the EEG branch kind, the
-  model's shapes, the head count of every transformer block, the world size, the bucket layout, the dropout stream
-  and the state of `fit`.
+  model's shapes, the head count of every transformer block, the world size, the bucket layout, the dropout stream,
+  the state of `fit` and - only for a trainer with an augmenter - ``augment``: its parameters and the step index.
 
 The step itself is untouched: saving and loading are copies, `fit` only calls `train_step` and `embed`.
 
@@ -140,6 +140,8 @@ class TrainerCheckpointMixin:
                          "weight_decay": float(self.weight_decay), "grad_clip": float(self.grad_clip)},
                "dropout": self._dropout_stream_state(), "fit": getattr(self, "_fit_state", None)}
         bts.update(self._layout())
+        if getattr(self, "augment", None) is not None:             # (absent without an augmenter: the container is unchanged)
+            bts["augment"] = dict(self.augment.params(), step=int(self._aug_step))
         return {"epoch": epoch, "model_state_dict": {k: _cpu(v) for k, v in self.state_dict().items()},
                 "optimizer_state_dict": {"state": state, "param_groups": [group]},
                 "scheduler_state_dict": scheduler.state_dict() if scheduler is not None else None,
@@ -172,6 +174,15 @@ class TrainerCheckpointMixin:
         if set(theirs) != set(mine["shapes"]):
             raise ValueError(f"load_checkpoint_state: shapes differ: extra keys {sorted(set(theirs) - set(mine['shapes']))}")
         same("bucket_n", "groups")
+        aug, theirs_aug = getattr(self, "augment", None), bts.get("augment")
+        if (aug is None) != (theirs_aug is None):
+            raise ValueError(f"load_checkpoint_state: augment differs: the checkpoint was written "
+                             f"{'with' if theirs_aug is not None else 'without'} an augmenter, this trainer has "
+                             f"{'none' if aug is None else 'one'}")
+        if aug is not None:
+            mine_aug = aug.params()
+            if {k: theirs_aug.get(k) for k in mine_aug} != mine_aug:
+                raise ValueError(f"load_checkpoint_state: augment differs: checkpoint {theirs_aug!r}, trainer {mine_aug!r}")
         msd = sd["model_state_dict"]
         for k, shp in mine["shapes"].items():
             if k not in msd or list(msd[k].shape) != shp:
@@ -219,6 +230,8 @@ class TrainerCheckpointMixin:
         ops._seed_state["base"] = int(d["base"])
         ops._seed_state["step"] = int(d["step"])
         self._pending_epoch_word = d["epoch_word"] if d["kind"] == "graph" else None
+        if "augment" in bts:
+            self._aug_step = int(bts["augment"]["step"])
         ops.weights_changed()
 
     # ------------------------------------------------------------------ files

@@ -45,13 +45,22 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
                  bridge_dim: int = 128, dropout: float = 0.3, lr: float = 1e-4,
                  weight_decay: float = 1e-4, grad_clip: float = 1.0, betas=(0.9, 0.999),
                  eps: float = 1e-8, group=None, device="cuda", mode: str = "graph", eeg_encoder: Optional[nn.Module] = None,
-                 num_heads: int = 4, num_layers: int = 2):
+                 num_heads: int = 4, num_layers: int = 2, augment=None):
         """``eeg_encoder``: the EEG branch when it is not the default ``EnhancedERPEncoder(eeg_channels, hidden_dim,
         num_layers, num_heads, dropout)`` - an ``EnhancedPowerEncoder`` (enhanced_models_v4.py:196-285) or a
         ``MultiScaleSTFTPowerEncoder`` (BASELINE config #5: raw EEG -> multi-scale STFT power -> a4); it must end in
         ``hidden_dim`` features.  The attention kernels run head dims ``hidden_dim / num_heads`` of 16, 24, ..., 64
-        (checked at the first step, not here: a trainer built on the CPU to read weights takes any shape)."""
+        (checked at the first step, not here: a trainer built on the CPU to read weights takes any shape).
+        ``augment``: an ``EEGTransforms`` (crossmodal_eeg_scr.py) - every `train_step` then augments its EEG batch on the
+        device (noise + channel drop, csrc/augment.hip), drawing step index 0, 1, 2, ... from the trainer's own counter and
+        this process's rank; `evaluate`, `embed`, `evaluate_retrieval`, `explain` and `forward` never augment."""
         super().__init__()
+        if augment is not None:
+            from .crossmodal_eeg_scr import EEGTransforms
+            if not isinstance(augment, EEGTransforms):
+                raise TypeError(f"BridgeTrainer: augment must be an EEGTransforms (got {type(augment).__name__})")
+        self.augment = augment
+        self._aug_step = 0                            # step index the next train_step's augmentation draws with
         self.eeg_encoder = (EnhancedERPEncoder(eeg_channels, hidden_dim, num_layers, num_heads, dropout)
                             if eeg_encoder is None else eeg_encoder)
         from .crossmodal_v4_enhancements import MultiScaleSTFTPowerEncoder
@@ -132,6 +141,11 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
         import torch.distributed as dist
         return dist.get_world_size(self.group) if self.group is not None else 1
 
+    @property
+    def augment_step(self) -> int:
+        """the step index the next `train_step` augments with (0 after construction; restored by a checkpoint)"""
+        return self._aug_step
+
     def set_lr(self, lr: float):
         self.lr = lr
         self.bucket.state[2] = lr
@@ -165,12 +179,17 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
         other (mm_clip_loss_own_rows_grouped).  In graph mode a grouped step is its own capture, as a new shape is."""
         ops.check_volume_shape(fmri.shape)                 # before the first launch of the step (or of its capture)
         gid = ops.group_ids(groups, eeg.shape[0], None if self.mode == "graph" else eeg.device, "train_step")
+        aug_step = None
+        if self.augment is not None:                       # one step index per call, whatever the mode
+            aug_step, self._aug_step = self._aug_step, self._aug_step + 1
+            if self.mode != "graph":
+                eeg = self.augment.batch(eeg, aug_step, dp.rank(self.group))
         if self.mode == "autograd":
             return self._step_autograd(eeg, fmri, gid)
         if self.mode == "manual":
             with torch.no_grad():
                 return self._step_manual(eeg, fmri, gid)
-        return self._step_graph(eeg, fmri, gid)
+        return self._step_graph(eeg, fmri, gid, aug_step)
 
     def _step_autograd(self, eeg, fmri, gid=None):
         b = self.bucket
@@ -571,7 +590,9 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
         with torch.cuda.stream(self._side):
             dp.all_gather_into(c["gid_all"].view(-1, 1), c["gid"].view(-1, 1), self.group)
 
-    def _step_graph(self, eeg, fmri, gid=None):
+    def _step_graph(self, eeg, fmri, gid=None, aug_step=None):
+        """``aug_step``: the augmentation's step index (trainers with an augmenter).  The capture and its two warm-up steps
+        see the batch as it came; what a replay reads is staged below, augmented."""
         if (self._cap is None or self._cap["eeg"].shape != eeg.shape or self._cap["fmri"].shape != fmri.shape
                 or self._cap["grouped"] != (gid is not None)):
             step0, base0 = ops._seed_state["step"], ops._seed_state["base"]
@@ -582,6 +603,14 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
                 self._cap["epoch"].fill_(self._pending_epoch_word)
                 self._pending_epoch_word = None
         c = self._cap
+        if aug_step is None or not self._stage_augmented(c, eeg, fmri, aug_step):
+            self._stage_inputs(c, eeg if aug_step is None else self.augment.batch(eeg, aug_step, dp.rank(self.group)), fmri)
+        if gid is not None and gid.data_ptr() != c["gid"].data_ptr():
+            c["gid"].copy_(gid)
+        return self._replay()
+
+    def _stage_inputs(self, c, eeg, fmri):
+        """a batch into the captured step's static inputs"""
         ce, cf = eeg.data_ptr() != c["eeg"].data_ptr(), fmri.data_ptr() != c["fmri"].data_ptr()
         if (c["xb"] is not None and ce and cf and eeg.dtype == torch.float32 and fmri.dtype == torch.float32 and eeg.is_cuda and fmri.is_cuda
                 and eeg.is_contiguous() and fmri.is_contiguous() and eeg.numel() % 4 == 0 and fmri.numel() % 4 == 0
@@ -598,9 +627,23 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
             if c["xb"] is not None:
                 Bx, Cx, Tx = c["eeg"].shape
                 _hip.call("mm_pack_nct_bf16", c["eeg"], c["xb"], Bx, Cx, Tx, c["xb"].shape[2])
-        if gid is not None and gid.data_ptr() != c["gid"].data_ptr():
-            c["gid"].copy_(gid)
-        return self._replay()
+
+    def _stage_augmented(self, c, eeg, fmri, aug_step) -> bool:
+        """the augmented batch straight into the packed operand (and the fMRI batch into its buffer): TWO launches - the
+        plan, then the staging launch with the augmentation between its load and its transpose tile.  False when the step
+        reads the fp32 batch instead (the STFT front-end) or the batch is not a contiguous fp32 device tensor: the caller
+        then augments into a fp32 batch and stages that."""
+        if c["xb"] is None or eeg.dtype != torch.float32 or not eeg.is_cuda or not eeg.is_contiguous():
+            return False
+        cf = fmri.data_ptr() != c["fmri"].data_ptr()
+        fuse = (cf and fmri.dtype == torch.float32 and fmri.is_cuda and fmri.is_contiguous() and fmri.numel() % 4 == 0
+                and fmri.data_ptr() % 16 == 0)
+        c["aug_plan"] = ops.eeg_augment_into(eeg, c["xb"], None, step=aug_step, rank=dp.rank(self.group),
+                                             fmri_dst=c["fmri"] if fuse else None, fmri_src=fmri if fuse else None,
+                                             plan=c.get("aug_plan"), **self.augment.kernel_args(eeg.shape[1]))
+        if cf and not fuse:
+            c["fmri"].copy_(fmri)
+        return True
 
     def _replay(self):
         c = self._cap
@@ -627,6 +670,7 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
         even on the host = what mm_pack_nct_bf16 does on the device: the step's arithmetic is bit-identical.
         ``groups``: a grouped batch's (B,) ids, appended as int32 (the layout of a grouped capture's inputs).
         Reference counterpart: the ``.to(device)`` of each batch, run_training_lite.py:480-481."""
+        self._no_packed_augment("pack_host_batch")
         gid = ops.group_ids(groups.detach().cpu() if groups is not None else None, eeg.shape[0], None, "pack_host_batch")
         eeg, fmri = eeg.detach().cpu().float(), fmri.detach().cpu().float().contiguous()
         if self._eeg_kind == "stft":
@@ -651,6 +695,7 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
     def train_step_packed(self, flat: torch.Tensor) -> Dict[str, torch.Tensor]:
         """one graph-replayed step on a batch that is already in the packed layout of `pack_host_batch` and on the device
         (a staging buffer an H2D copy filled): ONE device-to-device copy into the static inputs, then the replay"""
+        self._no_packed_augment("train_step_packed")
         if self._cap is None:
             raise RuntimeError("train_step_packed: run one train_step(eeg, fmri) first (it captures the step and fixes the shapes)")
         c = self._cap
@@ -661,7 +706,14 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
 
     def host_feeder(self, depth: int = 3) -> "HostFeeder":
         """the loop that feeds `train_step_packed` from pinned host buffers (see `HostFeeder`)"""
+        self._no_packed_augment("host_feeder")
         return HostFeeder(self, depth)
+
+    def _no_packed_augment(self, who: str):
+        if self.augment is not None:
+            raise ValueError(f"{who}: this trainer has an augmenter, and a batch that is already packed to bf16 on the host "
+                             "cannot be augmented after the fact (the noise scale needs the fp32 sample); feed "
+                             "train_step(eeg, fmri) from device tensors, or build the trainer without augment=")
 
     def time_collectives(self, batch: int, iters: int = 50) -> Dict[str, float]:
         """microseconds per call of every collective one step issues, each alone at its message size (HIP events on the

@@ -10,6 +10,7 @@ losses and the optimizer step run in the HIP kernels; there is no CPU path.
 from __future__ import annotations
 
 import logging
+import numbers
 from typing import Dict, Optional
 
 import numpy as np
@@ -82,6 +83,116 @@ class ImprovedSmartFusionNet(nn.Module):
 
     def get_weight_history(self):
         return self.fusion_weight_history
+
+
+def _aug_hash(stream: int, idx: np.ndarray) -> np.ndarray:
+    """h(stream, idx) of csrc/augment.hip on a uint64 array of 32-bit indices -> uint64 array of 32-bit values"""
+    m = np.uint64(0xFFFFFFFF)
+    x = (idx.astype(np.uint64) * np.uint64(0x9E3779B1) + np.uint64(stream)) & m
+    x ^= x >> np.uint64(16)
+    x = (x * np.uint64(0x7FEB352D)) & m
+    x ^= x >> np.uint64(15)
+    x = (x + np.uint64(((stream << 16) | (stream >> 16)) & 0xFFFFFFFF)) & m
+    x = (x * np.uint64(0x846CA68B)) & m
+    x ^= x >> np.uint64(16)
+    return x
+
+
+def _aug_thresh(p: float) -> int:
+    """decision threshold of a probability, formed through double from its fp32 value (as the kernels' host code does)"""
+    p = float(np.float32(p))
+    return 0 if p <= 0.0 else 1 << 32 if p >= 1.0 else int(p * 4294967296.0)
+
+
+class EEGTransforms:
+    """The notebook's augmenter (cell 18; handed to the training datasets as ``transform=``): with probability ``p``
+    Gaussian noise of ``noise_factor * x.std()``, then with probability ``p`` ``max(1, int(0.1 * C))`` random channels
+    zeroed.  Same positional signature; ``p_noise`` / ``p_drop`` (default ``p``) and ``drop_fraction`` split what the
+    notebook ties together.
+
+    The random stream is this package's own (csrc/augment.hip), a pure function of (seed, step, rank, sample,
+    element): ``batch`` on a device tensor runs the two HIP launches of ``ops.eeg_augment``, on a CPU tensor the same
+    stream in numpy - the same decisions and dropped channels, the noise equal to fp32 rounding.  `BridgeTrainer(augment=)`
+    augments each training step's EEG batch on the device; ``__call__`` is the per-sample dataset form."""
+
+    def __init__(self, p: float = 0.3, noise_factor: float = 0.05, *, p_noise: Optional[float] = None,
+                 p_drop: Optional[float] = None, drop_fraction: float = 0.1, seed: int = 0):
+        self.p = p
+        self.p_noise = p if p_noise is None else p_noise
+        self.p_drop = p if p_drop is None else p_drop
+        self.noise_factor, self.drop_fraction, self.seed = noise_factor, drop_fraction, int(seed)
+        for name in ("p", "p_noise", "p_drop"):
+            v = getattr(self, name)
+            if not (isinstance(v, numbers.Real) and 0.0 <= v <= 1.0):
+                raise ValueError(f"EEGTransforms: {name} must lie in [0, 1] (got {v!r})")
+        if not (isinstance(noise_factor, numbers.Real) and 0.0 <= noise_factor < float("inf")):
+            raise ValueError(f"EEGTransforms: noise_factor must be a finite number >= 0 (got {noise_factor!r})")
+        if not (isinstance(drop_fraction, numbers.Real) and 0.0 < drop_fraction <= 1.0):
+            raise ValueError(f"EEGTransforms: drop_fraction must lie in (0, 1] (got {drop_fraction!r})")
+        self.calls = 0
+
+    def n_drop(self, channels: int) -> int:
+        return max(1, int(self.drop_fraction * channels))
+
+    def params(self) -> dict:
+        """what two augmenters must share to draw the same stream (the trainer's checkpoint carries it)"""
+        return {"seed": self.seed, "p_noise": float(self.p_noise), "p_drop": float(self.p_drop),
+                "noise_factor": float(self.noise_factor), "drop_fraction": float(self.drop_fraction)}
+
+    def kernel_args(self, channels: int) -> dict:
+        return dict(p_noise=float(self.p_noise), p_drop=float(self.p_drop), noise_factor=float(self.noise_factor),
+                    n_drop=self.n_drop(channels), seed=self.seed)
+
+    def batch(self, x: torch.Tensor, step: int, rank: int = 0) -> torch.Tensor:
+        """the augmented copy of a (B, C, T) batch at step index ``step`` on rank ``rank``"""
+        if x.dim() != 3:
+            raise ValueError(f"EEGTransforms.batch: expected a (B, C, T) batch, got shape {tuple(x.shape)}")
+        if x.is_cuda:
+            return ops.eeg_augment(x, step=step, rank=rank, **self.kernel_args(x.shape[1]))
+        return self._batch_cpu(x, step, rank)
+
+    def _batch_cpu(self, x: torch.Tensor, step: int, rank: int) -> torch.Tensor:
+        B, C, T = x.shape
+        n_drop = self.n_drop(C)
+        ops.eeg_augment_check(B, C, T, n_drop, "EEGTransforms")
+        a = x.detach().to(torch.float32).contiguous().numpy()
+        s = ops.augment_streams(self.seed, step, rank)
+        b = np.arange(B, dtype=np.uint64)
+        noise_on = _aug_hash(s[0], b) < np.uint64(_aug_thresh(self.p_noise))
+        drop_on = _aug_hash(s[1], b) < np.uint64(_aug_thresh(self.p_drop))
+        out = a.copy()
+        if noise_on.any():
+            std = a.astype(np.float64).std(axis=(1, 2), ddof=1).astype(np.float32)
+            scale = np.where(noise_on, np.float32(self.noise_factor) * std, np.float32(0)).astype(np.float32)
+            half = (T + 1) // 2
+            idx = np.arange(B * C * half, dtype=np.uint64)
+            u1 = (_aug_hash(s[3], idx).astype(np.float64) + 1.0) * 2.0 ** -32
+            u2 = _aug_hash(s[4], idx).astype(np.float64) * 2.0 ** -32
+            r = np.sqrt(-2.0 * np.log(u1))
+            z = np.stack([r * np.cos(2.0 * np.pi * u2), r * np.sin(2.0 * np.pi * u2)], axis=-1).reshape(B, C, 2 * half)[:, :, :T]
+            noisy = (a.astype(np.float64) + z * scale.astype(np.float64)[:, None, None]).astype(np.float32)
+            out = np.where((scale != 0)[:, None, None], noisy, a)
+        if drop_on.any():
+            keys = _aug_hash(s[2], np.arange(B * C, dtype=np.uint64)).reshape(B, C)
+            order = np.argsort(keys, axis=1, kind="stable")          # ties by channel index
+            ranks = np.empty_like(order)
+            np.put_along_axis(ranks, order, np.broadcast_to(np.arange(C), (B, C)), axis=1)
+            out[drop_on[:, None] & (ranks < n_drop)] = 0.0
+        return torch.from_numpy(np.ascontiguousarray(out)).to(x.dtype)
+
+    def __call__(self, x: torch.Tensor) -> torch.Tensor:
+        """the notebook's per-sample form: one (C, ...) sample -> a new tensor (dimension 0 is the channels, as in the
+        notebook: a flat feature vector drops single values); the call counter is the step index"""
+        if x.dim() < 1:
+            raise ValueError(f"EEGTransforms: expected a (channels, ...) sample, got shape {tuple(x.shape)}")
+        step, self.calls = self.calls, self.calls + 1
+        return self.batch(x.reshape(1, x.shape[0], -1), step).reshape(x.shape)
+
+    def state_dict(self) -> dict:
+        return {"seed": self.seed, "calls": self.calls}
+
+    def load_state_dict(self, sd: dict) -> None:
+        self.seed, self.calls = int(sd["seed"]), int(sd["calls"])
 
 
 def _channels_first(x):

@@ -304,6 +304,94 @@ def pack_nct(x: torch.Tensor) -> torch.Tensor:
     return y
 
 
+# ---- EEG augmentation (csrc/augment.hip; the reference's EEGTransforms).  The stream is counter based and has nothing
+# to do with the dropout stream above: no state here, none on the device.
+AUG_PURPOSES = ("noise_decision", "drop_decision", "channel_keys", "gauss_a", "gauss_b")
+_M64 = (1 << 64) - 1
+
+
+def augment_streams(seed: int, step: int, rank: int = 0) -> tuple:
+    """the five 32-bit stream words of one augmentation step, in `AUG_PURPOSES` order (csrc/augment.hip's header)"""
+    out = []
+    for purpose in range(len(AUG_PURPOSES)):
+        z = (int(seed) * 0x9E3779B97F4A7C15 + int(step) * 0xBF58476D1CE4E5B9 + int(rank) * 0x94D049BB133111EB
+             + (purpose + 1) * 0xD6E8FEB86659FD93) & _M64
+        z ^= z >> 30
+        z = z * 0xBF58476D1CE4E5B9 & _M64
+        z ^= z >> 27
+        z = z * 0x94D049BB133111EB & _M64
+        z ^= z >> 31
+        out.append((z ^ (z >> 32)) & 0xFFFFFFFF)
+    return tuple(out)
+
+
+def eeg_augment_check(B: int, C: int, T: int, n_drop: int, who: str = "eeg_augment"):
+    """what both the kernels and the CPU path refuse, before anything runs"""
+    if min(B, C, T) < 1 or C * T < 2:
+        raise ValueError(f"{who}: a sample needs C * T >= 2 values for its standard deviation (got C = {C}, T = {T})")
+    if B * C * ((T + 1) // 2) >= 1 << 32:
+        raise ValueError(f"{who}: B * C * ceil(T / 2) must stay below 2^32 (the random stream's index)")
+    if not 1 <= n_drop <= C:
+        raise ValueError(f"{who}: n_drop must lie in [1, {C}] (got {n_drop})")
+
+
+def eeg_augment_plan_layout(B: int, C: int, T: int):
+    """(words, words per sample, chunks per sample) of mm_eeg_augment_plan's buffer (include/mmeeg_hip.h)"""
+    stride = (4 + (C + 31) // 32 + 1) & ~1
+    chunk = 4096
+    while (C * T + chunk - 1) // chunk > 64:
+        chunk *= 2
+    nchunk = (C * T + chunk - 1) // chunk
+    return B * stride + 4 * B * nchunk, stride, nchunk
+
+
+def eeg_augment_into(x: torch.Tensor, xb: Optional[torch.Tensor], out: Optional[torch.Tensor], *, p_noise: float, p_drop: float,
+                     noise_factor: float, n_drop: int, seed: int, step: int, rank: int = 0,
+                     fmri_dst: Optional[torch.Tensor] = None, fmri_src: Optional[torch.Tensor] = None,
+                     plan: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """the two launches: the plan of batch ``x`` (B, C, T) fp32, then the augmented batch into the packed bf16 operand
+    ``xb`` (B, T, cpad(C)) and / or the fp32 ``out`` (B, C, T), with the fMRI copy of mm_stage_inputs when given.
+    ``plan``: a buffer of `eeg_augment_plan_layout` words to reuse (a training loop keeps one per batch shape).
+    -> the plan buffer (int32 words)."""
+    _need_gpu(x)
+    B, C, T = x.shape
+    eeg_augment_check(B, C, T, n_drop)
+    words, _, _ = eeg_augment_plan_layout(B, C, T)
+    if plan is None:
+        plan = torch.empty(words, dtype=torch.int32, device=x.device)
+    s = augment_streams(seed, step, rank)
+    _hip.call("mm_eeg_augment_plan", x, plan, words, B, C, T, p_noise, p_drop, n_drop, s[0], s[1], s[2])
+    _hip.call("mm_stage_inputs_aug", x, plan, words, xb, out, B, C, T, cpad(C), noise_factor, s[3], s[4],
+              fmri_dst, fmri_src, 0 if fmri_src is None else fmri_src.numel())
+    return plan
+
+
+def eeg_augment_read_plan(plan: torch.Tensor, B: int, C: int, T: int):
+    """-> (noise_on bool (B,), drop_mask bool (B, C), std fp32 (B,)) of a plan both launches have written"""
+    _, stride, _ = eeg_augment_plan_layout(B, C, T)
+    hdr = plan[:B * stride].view(B, stride)
+    nw = (C + 31) // 32
+    bits = (hdr[:, 4:4 + nw].unsqueeze(-1) >> torch.arange(32, device=plan.device, dtype=torch.int32)) & 1
+    return hdr[:, 2] != 0, bits.reshape(B, nw * 32)[:, :C] != 0, hdr[:, 1].contiguous().view(_F32)
+
+
+def eeg_augment(x: torch.Tensor, *, p_noise: float, p_drop: float, noise_factor: float, n_drop: int, seed: int, step: int,
+                rank: int = 0, packed: bool = False, return_plan: bool = False):
+    """EEGTransforms on a device batch (B, C, T): per sample, with probability ``p_noise``, Gaussian noise of
+    ``noise_factor`` x the sample's standard deviation, then with probability ``p_drop`` ``n_drop`` channels zeroed; the
+    draws are a function of (seed, step, rank) alone.  -> the augmented fp32 batch; with ``packed`` also its channels-last
+    bf16 image (B, T, cpad(C)), the first convolution's operand; with ``return_plan`` also (noise_on, drop_mask, std)."""
+    _need_gpu(x)
+    x = x.contiguous().float()
+    B, C, T = x.shape
+    out = _empty((B, C, T), _F32, x)
+    xb = _empty((B, T, cpad(C)), _BF, x) if packed else None
+    plan = eeg_augment_into(x, xb, out, p_noise=p_noise, p_drop=p_drop, noise_factor=noise_factor, n_drop=n_drop, seed=seed,
+                            step=step, rank=rank)
+    res = (out, xb) if packed else out
+    return (res, eeg_augment_read_plan(plan, B, C, T)) if return_plan else res
+
+
 def igemm(x: torch.Tensor, wf: torch.Tensor, taps: int, pad: int, cout: int, *,
           scale=None, shift=None, act="none", residual=None, pe=None, pool=1, stats=None,
           out_f32=False, out_bf16=True, out_pre=False, drop_p=0.0, seed=0, gradz=None, gradz_act="none"):

@@ -399,6 +399,52 @@ def groups_case(step_iters=30):
     print(f"C2 graph step B=32: ungrouped {tu:7.1f} us  grouped {tg:7.1f} us  ({100 * (tg / tu - 1):+.2f} %)")
 
 
+def aug_case(B=32, C=64, T=1024, vol=(32, 32, 32), step_iters=30):
+    """EEG augmentation (csrc/augment.hip) at the C2 shape: mm_stage_inputs alone against the plan + mm_stage_inputs_aug pair
+    at p = 0.3 and p = 1 - issued eagerly (what a training loop pays: host issue included) and replayed from a hipGraph
+    (the kernels alone), HIP events, interleaved rounds; bytes: the EEG batch read once / twice, the bf16 operand and the
+    fMRI batch written, the fMRI batch read - then the C2 graph step with and without an augmenter"""
+    from multimodal_eeg_fmri_amd.bridge_trainer import BridgeTrainer, synthetic_pairs
+    from multimodal_eeg_fmri_amd.crossmodal_eeg_scr import EEGTransforms
+    eeg, fmri = synthetic_pairs(B, C, T, vol)
+    cp = ops.cpad(C)
+    xb, fdst = torch.empty(B, T, cp, dtype=BF, device="cuda"), torch.empty_like(fmri)
+    step = [0]
+    plan = torch.empty(ops.eeg_augment_plan_layout(B, C, T)[0], dtype=torch.int32, device="cuda")
+
+    def aug(p):
+        step[0] += 1
+        ops.eeg_augment_into(eeg, xb, None, p_noise=p, p_drop=p, noise_factor=0.05, n_drop=max(1, int(0.1 * C)), seed=1,
+                             step=step[0], fmri_dst=fdst, fmri_src=fmri, plan=plan)
+    cases = [("mm_stage_inputs", lambda: _hip.call("mm_stage_inputs", eeg, xb, None, B, C, T, cp, fdst, fmri, fmri.numel()), 1),
+             ("plan + mm_stage_inputs_aug p = 0.3", lambda: aug(0.3), 2), ("plan + mm_stage_inputs_aug p = 1", lambda: aug(1.0), 2)]
+    times, gtimes = [[] for _ in cases], [[] for _ in cases]
+    for _ in range(5):
+        for i, (_, fn, _) in enumerate(cases):
+            times[i].append(timeit(fn, iters=200, rounds=1))
+            gtimes[i].append(graph_time(fn, n=50))
+    for (name, _, reads), t, gt in zip(cases, times, gtimes):
+        us, gus = statistics.median(t), statistics.median(gt)
+        nbytes = reads * eeg.numel() * 4 + xb.numel() * 2 + 2 * fmri.numel() * 4
+        print(f"{name:38s} eager {us:6.2f} us (min {min(t):5.2f}, max {max(t):5.2f})  in a graph {gus:6.2f} us (min {min(gt):5.2f}, "
+              f"max {max(gt):5.2f})  {nbytes / 1e6:5.1f} MB  {nbytes / gus / 1e6:5.2f} TB/s")
+    trs = []
+    for augment in (None, EEGTransforms(p=0.3, seed=1), EEGTransforms(p=1.0, seed=1)):
+        ops.set_seed_epoch(None)
+        torch.manual_seed(0)
+        tr = BridgeTrainer(eeg_channels=C, dropout=0.3, augment=augment).train()
+        tr.train_step(eeg, fmri)
+        trs.append(tr)
+    times = [[] for _ in trs]
+    for _ in range(5):
+        for i, tr in enumerate(trs):
+            times[i].append(timeit(lambda: tr.train_step(eeg, fmri), iters=step_iters, rounds=1))
+    base = statistics.median(times[0])
+    for name, t in zip(("no augmenter", "augment p = 0.3", "augment p = 1"), times):
+        us = statistics.median(t)
+        print(f"C2 graph step B={B}: {name:16s} {us:7.1f} us  (min {min(t):6.1f}, max {max(t):6.1f})  {100 * (us / base - 1):+.2f} %")
+
+
 def xai_case(B=32, C=64, T=1024, vol=(32, 32, 32), n_steps=50, rounds=5):
     """attribution (csrc/xai.hip, BridgeTrainer.explain) at the C2 shape.  (1) the three streaming kernels alone: GB/s of
     the bytes each must move, beside the ~6.3 TB/s a float4 copy reaches on this part.  (2) integrated gradients of the
@@ -594,6 +640,9 @@ def main():
         return
     if flt == "xai":
         xai_case()
+        return
+    if flt == "aug":
+        aug_case()
         return
     if flt == "groups":
         groups_case()
