@@ -261,6 +261,24 @@ int mm_linear_fwd_ln_gemm2_act(const void* x, const void* w, int M, int K, const
                                const float* ln_gamma, const float* ln_beta, float ln_eps, void* ln_out_bf16,
                                float* ln_stat, const void* w2, const float* bias2, int n2, void* out2_bf16,
                                void* pre2_bf16, int act2, float drop2_p, uint32_t seed2, hipStream_t stream);
+/* Everything row-wise between two attention kernels of a TemporalTransformerBlock (enhanced_models_v4.py:99-107), one
+ * launch: mm_linear_fwd_ln_gemm2_act (out_proj + residual + norm2, then linear1 + act1 + Dropout on norm2's rows: x1_f32,
+ * ln_out_bf16, ln_stat, g_bf16, z_bf16 as its out_f32, ln_out_bf16, ln_stat, out2_bf16, pre2_bf16) followed by
+ * y_f32 (M, 128) = dropout(g @ w2^T + bias2, drop2_p, seed2) + x1 (w2 = linear2's forward weight image, 128 rows of n1) and
+ * ONE consumer of the finished rows y:
+ *   nln_out_bf16 != NULL: LayerNorm-128 rows (+ nln_stat, nullable), as mm_linear_fwd_ln; with wq != NULL also
+ *                         q_bf16 (M, nq) = nln_out @ wq^T + biasq, as mm_linear_fwd_ln_gemm2 (the next block's in_proj);
+ *   pool_out != NULL:     the mean over groups of rows_per_group rows, as mm_linear_fwd_meanpool.
+ * The 32 x n1 hidden tile stays in the workgroup: g_bf16 and z_bf16 may both be NULL (no backward pass: the hidden tensor
+ * is never written).  K == 128, M % 32 == 0, n1 % 128 == 0, n1 <= 512 (LDS: two workgroups per CU).  Every output is
+ * bit-identical to mm_linear_fwd_ln, mm_conv1d_fwd (linear1) and mm_linear_fwd_ln / _ln_gemm2 / _meanpool in a row. */
+int mm_ffn_rows_fwd(const void* x, const void* w, int M, int K, const float* bias, const float* residual, float* x1_f32,
+                    float drop_p, uint32_t seed, const uint32_t* seed_epoch, const float* ln_gamma, const float* ln_beta,
+                    float ln_eps, void* ln_out_bf16, float* ln_stat, const void* w1, const float* bias1, int n1,
+                    void* g_bf16, void* z_bf16, int act1, float drop1_p, uint32_t seed1, const void* w2, const float* bias2,
+                    float* y_f32, float drop2_p, uint32_t seed2, const float* nln_gamma, const float* nln_beta, float nln_eps,
+                    void* nln_out_bf16, float* nln_stat, const void* wq, const float* biasq, int nq, void* q_bf16,
+                    float* pool_out, int rows_per_group, hipStream_t stream);
 /* mm_linear_dgrad_ln_bwd of norm2 / linear1 with the attention out-projection's data gradient as a second GEMM in the
  * same launch (TemporalTransformerBlock backward, enhanced_models_v4.py:99-103: x1 = x0 + dropout(out_proj(attn)),
  * norm2(x1)): do_bf16 (M, 128) = dx_bf16 @ w2, w2 = out_proj's data-gradient weight image (128 x 128), dx_bf16 = the

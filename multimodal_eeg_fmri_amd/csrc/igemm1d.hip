@@ -107,7 +107,10 @@ struct ConvArgs {
 enum : unsigned { EF_RES = 1, EF_PE = 2, EF_PRE = 4, EF_GRADZ = 8, EF_STATS = 16, EF_POOLOUT = 32, EF_LNF = 64, EF_POOL2 = 128,
                   EF_DROP = 256, EF_SCALE = 512, EF_F32 = 1024, EF_BF16 = 2048, EF_SHIFT = 4096, EF_LNBWD = 8192,
                   EF_BNRED = 16384, EF_BNPOOL2 = 32768 /* bits 24-27: the fused BatchNorm-backward's activation */,
-                  EF_GEMM2 = 1u << 28, EF_ANY = 0xFFFFFFFFu };
+                  EF_GEMM2 = 1u << 28,
+                  // the second GEMM's own epilogue: GELU, pre-activation copy, dropout (none of them: bias only)
+                  EF_G2ACT = 1u << 29, EF_G2PRE = 1u << 30, EF_G2DROP = 1u << 31, EF_G2FFN1 = EF_G2ACT | EF_G2PRE | EF_G2DROP,
+                  EF_ANY = 0xFFFFFFFFu };
 // the three activation fields (4 bits each, at these bit offsets): the epilogue's own, the fused activation
 // derivative's, the fused BatchNorm-backward's
 enum : int { EFA_OUT = 16, EFA_GRADZ = 20, EFA_BN = 24 };
@@ -117,8 +120,12 @@ static unsigned epi_mask(const EpiArgs& e) {
            (e.pool_out ? EF_POOLOUT : 0) | (e.lnf_out ? EF_LNF : 0) | (e.pool == 2 ? EF_POOL2 : 0) | (e.drop_thresh ? EF_DROP : 0) |
            (e.scale ? EF_SCALE : 0) | (e.out_f32 ? EF_F32 : 0) | (e.out_bf16 ? EF_BF16 : 0) | (e.shift ? EF_SHIFT : 0) | (e.ln_x ? EF_LNBWD : 0) |
            ef_act(e.act) | ef_act(e.gradz ? e.gradz_act : 0, EFA_GRADZ) |
-           (e.bn.y ? (EF_BNRED | (e.bn.pool == 2 ? EF_BNPOOL2 : 0) | ef_act(e.bn.act, EFA_BN)) : 0) | (e.w2 ? EF_GEMM2 : 0);
+           (e.bn.y ? (EF_BNRED | (e.bn.pool == 2 ? EF_BNPOOL2 : 0) | ef_act(e.bn.act, EFA_BN)) : 0) |
+           (e.w2 ? (EF_GEMM2 | (e.act2 ? EF_G2ACT : 0) | (e.pre2 ? EF_G2PRE : 0) | (e.thresh2 ? EF_G2DROP : 0)) : 0);
 }
+// bytes of the 32 x 128 tile's epilogue LDS: the fp32 C tile and its column sums, then the second GEMM's operand rows
+constexpr size_t CT32 = (size_t)(32 * (128 + 4) + 2 * 128) * sizeof(float), A2B = (size_t)32 * A2S * sizeof(bf16);
+static_assert(2 * A2B <= CT32, "the second GEMM's two staging tiles fit the dead C tile");
 
 
 // Epilogue through LDS: the accumulator tile is parked as fp32 [BM][BN+4], then
@@ -453,43 +460,69 @@ __device__ __forceinline__ void epilogue_ln_bwd(const float* Cs, const EpiArgs& 
 // out2[32 rows][n2] = a2[32][128] (bf16 rows this workgroup has just finished, in LDS) x w2 (+ bias2): wave wn owns columns
 // 128 j + 32 wn .. of every 128-column group j; B fragments straight from the L2-resident weight image, k ascending as the
 // main loop's, fp32 accumulate, one rounding to bf16 - bit-identical to a launch of its own on the same rows.
-__device__ __forceinline__ void second_gemm(const bf16* a2, const EpiArgs& e, size_t row0, int wn, int lr, int lh) {
+// The fragments of group j + 1 are requested before the MFMAs of group j.  A finished group is parked in LDS (the MFMA
+// layout gives a lane ONE column: straight from the registers the outputs left as 2-byte column stores) and leaves as
+// 16-byte stores, 16 lanes to a 256-byte row segment.  The staging tiles are double-buffered, so a group costs one barrier.
+//   FEAT   EF_ANY: bias / pre-activation copy / activation / dropout behind run-time tests; otherwise EF_G2ACT (GELU),
+//          EF_G2PRE and EF_G2DROP say what is compiled in (none of them: bias only)
+//   KEEP   ost is the whole 32 x n2 output tile (row stride n2 + KPAD) and stays in LDS for the caller (out2 may be null:
+//          nothing written); otherwise ost is two 32 x A2S staging tiles
+//   pst    two 32 x A2S staging tiles of the pre-activation copy (used with pre2 only)
+template <unsigned FEAT, bool KEEP>
+__device__ __forceinline__ void second_gemm(const bf16* a2, const EpiArgs& e, size_t row0, int tid, int wn, int lr, int lh,
+                                            bf16* ost, bf16* pst) {
 #pragma clang fp contract(off)
-    bf16x8 af[8];
+    constexpr bool ANY = FEAT == EF_ANY;
+    const int act = ANY ? e.act2 : ((FEAT & EF_G2ACT) ? (int)MM_ACT_GELU : 0);
+    const bool pre = ANY ? e.pre2 != nullptr : (FEAT & EF_G2PRE) != 0;
+    const bool drop = ANY ? e.thresh2 != 0 : (FEAT & EF_G2DROP) != 0;
+    const bool store_out = !KEEP || e.out2 != nullptr;
+    const int OS = KEEP ? e.n2 + KPAD : A2S;
+    const uint32_t dseed = drop ? mm_eff_seed(e.seed2, e.drop_epoch) : 0u;
+    bf16x8 af[8], bnx[8];
 #pragma unroll
     for (int ks = 0; ks < 8; ++ks) af[ks] = *reinterpret_cast<const bf16x8*>(a2 + lr * A2S + ks * 16 + lh * 8);
-    for (int j = 0; j < e.n2 / 128; ++j) {
+    const bf16* wlane = e.w2 + (size_t)(32 * wn + lr) * 128 + lh * 8;
+#pragma unroll
+    for (int ks = 0; ks < 8; ++ks) bnx[ks] = *reinterpret_cast<const bf16x8*>(wlane + ks * 16);
+    const int ng = e.n2 / 128;
+    for (int j = 0; j < ng; ++j) {
         const int n = 128 * j + 32 * wn + lr;
-        const bf16* wrow = e.w2 + (size_t)n * 128 + lh * 8;
         bf16x8 bfr[8];
 #pragma unroll
-        for (int ks = 0; ks < 8; ++ks) bfr[ks] = *reinterpret_cast<const bf16x8*>(wrow + ks * 16);
+        for (int ks = 0; ks < 8; ++ks) bfr[ks] = bnx[ks];
+        if (j + 1 < ng) {
+            const bf16* wrow = wlane + (size_t)(j + 1) * 128 * 128;
+#pragma unroll
+            for (int ks = 0; ks < 8; ++ks) bnx[ks] = *reinterpret_cast<const bf16x8*>(wrow + ks * 16);
+        }
+        const float bias = e.bias2 ? e.bias2[n] : 0.f;
         f32x16 c2;
 #pragma unroll
         for (int r = 0; r < 16; ++r) c2[r] = 0.f;
 #pragma unroll
         for (int ks = 0; ks < 8; ++ks) c2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[ks], bfr[ks], c2, 0, 0, 0);
-        const float bias = e.bias2 ? e.bias2[n] : 0.f;
-        bf16* orow = e.out2 + row0 * e.n2 + n;
-        if (!e.act2 && !e.thresh2 && !e.pre2) {
+        bf16* os = KEEP ? ost + 128 * j : ost + (j & 1) * (32 * A2S);
+        bf16* ps = pst + (j & 1) * (32 * A2S);
+        // bias -> pre-activation copy -> activation -> dropout, the arithmetic of epilogue_rows (FFN-1 forward)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = (r & 3) + 8 * (r >> 2) + 4 * lh;
-                orow[(size_t)row * e.n2] = (bf16)(e.bias2 ? c2[r] + bias : c2[r]);
-            }
-        } else {
-            // bias -> pre-activation copy -> activation -> dropout, the arithmetic of epilogue_rows (FFN-1 forward)
-            const uint32_t dseed = e.thresh2 ? mm_eff_seed(e.seed2, e.drop_epoch) : 0u;
+        for (int r = 0; r < 16; ++r) {
+            const int row = (r & 3) + 8 * (r >> 2) + 4 * lh;
+            const size_t idx = (row0 + row) * e.n2 + n;
+            const float v = e.bias2 ? c2[r] + bias : c2[r];
+            if (pre) ps[row * A2S + 32 * wn + lr] = (bf16)v;
+            float val = apply_act(v, act);
+            if (drop) val = __builtin_fmaf(val, dropout_scale(dseed, (uint32_t)idx, e.thresh2, e.inv_keep2), 0.f);
+            os[row * OS + 32 * wn + lr] = (bf16)val;
+        }
+        if (!store_out && !pre) continue;              // (uniform) the tile only stays in LDS: the caller's barrier covers it
+        __syncthreads();
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = (r & 3) + 8 * (r >> 2) + 4 * lh;
-                const size_t idx = (row0 + row) * e.n2 + n;
-                const float v = e.bias2 ? c2[r] + bias : c2[r];
-                if (e.pre2) e.pre2[idx] = (bf16)v;
-                float val = apply_act(v, e.act2);
-                if (e.thresh2) val = __builtin_fmaf(val, dropout_scale(dseed, (uint32_t)idx, e.thresh2, e.inv_keep2), 0.f);
-                orow[(size_t)row * e.n2] = (bf16)val;
-            }
+        for (int q = 0; q < 2; ++q) {
+            const int row = q * 16 + (tid >> 4), sg = (tid & 15) * 8;
+            const size_t oi = (row0 + row) * e.n2 + 128 * j + sg;
+            if (store_out) *reinterpret_cast<uint4*>(e.out2 + oi) = *reinterpret_cast<const uint4*>(os + row * OS + sg);
+            if (pre) *reinterpret_cast<uint4*>(e.pre2 + oi) = *reinterpret_cast<const uint4*>(ps + row * A2S + sg);
         }
     }
 }
@@ -646,8 +679,8 @@ __global__ __launch_bounds__(256, 2) void conv1d_fwd_kernel(ConvArgs a) {
             bf16* a2 = gemm2 ? reinterpret_cast<bf16*>(smem + (BM * LDC + 2 * BN) * sizeof(float)) : nullptr;   // behind the C tile
             epilogue_ln_bwd<BM, BN, FEAT>(Cs, a.e, tid, b, t0, a.T, sstat, a2);
             if (gemm2) {
-                __syncthreads();
-                second_gemm(a2, a.e, (size_t)b * a.T + t0, wn, lr, lh);
+                __syncthreads();                  // the C tile is dead: it stages the outputs, the copy's tiles follow a2
+                second_gemm<FEAT, false>(a2, a.e, (size_t)b * a.T + t0, tid, wn, lr, lh, reinterpret_cast<bf16*>(smem), a2 + 32 * A2S);
             }
             return;
         }
@@ -665,11 +698,110 @@ __global__ __launch_bounds__(256, 2) void conv1d_fwd_kernel(ConvArgs a) {
             bf16* a2 = reinterpret_cast<bf16*>(smem + (BM * LDC + 2 * BN) * sizeof(float));
             epilogue_rows<BM, BN, FEAT>(Cs, a.e, tid, b, t0, a.T, n0, a.Cout, sstat, a2);
             __syncthreads();
-            second_gemm(a2, a.e, (size_t)b * a.T + t0, wn, lr, lh);
+            second_gemm<FEAT, false>(a2, a.e, (size_t)b * a.T + t0, tid, wn, lr, lh, reinterpret_cast<bf16*>(smem), a2 + 32 * A2S);
             return;
         }
     }
     epilogue_rows<BM, BN, FEAT>(Cs, a.e, tid, b, t0, a.T, n0, a.Cout, sstat);
+}
+
+// Everything row-wise between two attention kernels of a width-128 transformer block, one launch: the out-projection
+// (+ dropout, residual, norm2) as conv1d_fwd_kernel<32, 128, 1, 4, 128, ..., 1> runs it, the first FFN Linear as its second
+// GEMM with the whole 32 x n1 hidden tile KEPT in LDS, then the second FFN Linear on that tile (W2's fragments from its
+// L2-resident forward image one 128-chunk ahead, k ascending in 16-steps into one accumulator: the bits of the stand-alone
+// launch's 128-chunks), whose C tile goes through the unchanged epilogue_rows with the x1 rows this workgroup has just
+// written as its residual.  c = the first launch's arguments (Cin == Cout == 128, taps 1, B 1), t = the FFN-2 epilogue's.
+struct FfnRowsArgs { ConvArgs c; const bf16* w3; EpiArgs t; };
+// SPEC: the training step's epilogue combinations compiled in (else every step behind its run-time test)
+// TAIL: what consumes the finished rows - 0 LayerNorm, 1 LayerNorm + a second GEMM on its rows, 2 the mean over tokens
+template <bool SPEC, int TAIL>
+__global__ __launch_bounds__(256, 2) void ffn_rows_fwd_kernel(FfnRowsArgs fa) {
+    constexpr int BM = 32, BN = 128, AS = 128 + KPAD, LDC = BN + 4;
+    constexpr unsigned F_HEAD = SPEC ? (EF_SHIFT | EF_F32 | EF_DROP | EF_RES | EF_LNF | EF_GEMM2 | EF_G2FFN1) : EF_ANY;
+    constexpr unsigned F_TAIL = !SPEC ? EF_ANY : (EF_SHIFT | EF_F32 | EF_DROP | EF_RES | (TAIL == 2 ? EF_POOLOUT : EF_LNF) | (TAIL == 1 ? EF_GEMM2 : 0));
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const ConvArgs& a = fa.c;
+    const int tid = threadIdx.x, lane = tid & 63, wn = tid >> 6, lr = lane & 31, lh = lane >> 5;
+    const int t0 = blockIdx.x * BM;
+    bf16* As = reinterpret_cast<bf16*>(smem);
+    bf16* Ws = As + BM * AS;
+    {   // 32 x 128 rows and the 128 x 128 weight image: one round trip (T % 32 == 0, host-checked)
+        uint4 va[2], vw[8];
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const int s = i * 256 + tid;
+            va[i] = *reinterpret_cast<const uint4*>(a.x + (size_t)(t0 + s / 16) * 128 + (s % 16) * 8);
+        }
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const int s = i * 256 + tid;
+            vw[i] = *reinterpret_cast<const uint4*>(a.w + (size_t)(s / 16) * 128 + (s % 16) * 8);
+        }
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const int s = i * 256 + tid;
+            *reinterpret_cast<uint4*>(As + (s / 16) * AS + (s % 16) * 8) = va[i];
+        }
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const int s = i * 256 + tid;
+            *reinterpret_cast<uint4*>(Ws + (s / 16) * AS + (s % 16) * 8) = vw[i];
+        }
+    }
+    __syncthreads();
+    f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+#pragma unroll
+    for (int ks = 0; ks < 128; ks += 16) {
+        const bf16x8 af = *reinterpret_cast<const bf16x8*>(As + lr * AS + ks + lh * 8);
+        const bf16x8 bfr = *reinterpret_cast<const bf16x8*>(Ws + (wn * 32 + lr) * AS + ks + lh * 8);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, bfr, acc, 0, 0, 0);
+    }
+    __syncthreads();                               // staging LDS is dead: reuse as the C tile
+    float* Cs = reinterpret_cast<float*>(smem);
+    float* sstat = Cs + BM * LDC;
+    bf16* a2 = reinterpret_cast<bf16*>(smem + CT32);   // the second GEMMs' operand rows (norm2's, then the next norm1's)
+    bf16* Gs = a2 + 32 * A2S;                          // [32][n1 + KPAD] hidden tile
+    auto park = [&]() {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) Cs[((r & 3) + 8 * (r >> 2) + 4 * lh) * LDC + wn * 32 + lr] = acc[r];
+    };
+    park();
+    __syncthreads();
+    epilogue_rows<BM, BN, F_HEAD>(Cs, a.e, tid, 0, t0, a.T, 0, 128, sstat, a2);
+    __syncthreads();                               // the C tile is dead: it stages the pre-activation copy
+    second_gemm<F_HEAD, true>(a2, a.e, (size_t)t0, tid, wn, lr, lh, Gs, reinterpret_cast<bf16*>(smem));
+    __syncthreads();                               // the hidden tile is complete; every staged copy has left
+    {
+        const int n1 = a.e.n2, GS = n1 + KPAD;
+        const bf16* wlane = fa.w3 + (size_t)(32 * wn + lr) * n1 + lh * 8;
+        bf16x8 bnx[8];
+#pragma unroll
+        for (int ks = 0; ks < 8; ++ks) bnx[ks] = *reinterpret_cast<const bf16x8*>(wlane + ks * 16);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+        for (int c0 = 0; c0 < n1; c0 += 128) {
+            bf16x8 bfr[8];
+#pragma unroll
+            for (int ks = 0; ks < 8; ++ks) bfr[ks] = bnx[ks];
+            if (c0 + 128 < n1)
+#pragma unroll
+                for (int ks = 0; ks < 8; ++ks) bnx[ks] = *reinterpret_cast<const bf16x8*>(wlane + c0 + 128 + ks * 16);
+#pragma unroll
+            for (int ks = 0; ks < 8; ++ks) {
+                const bf16x8 af = *reinterpret_cast<const bf16x8*>(Gs + lr * GS + c0 + ks * 16 + lh * 8);
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, bfr[ks], acc, 0, 0, 0);
+            }
+        }
+    }
+    park();
+    __syncthreads();
+    epilogue_rows<BM, BN, F_TAIL>(Cs, fa.t, tid, 0, t0, a.T, 0, 128, sstat, TAIL == 1 ? a2 : nullptr);
+    if constexpr (TAIL == 1) {
+        __syncthreads();
+        second_gemm<SPEC ? EF_GEMM2 : EF_ANY, false>(a2, fa.t, (size_t)t0, tid, wn, lr, lh, reinterpret_cast<bf16*>(smem), nullptr);
+    }
 }
 
 // second half of a split-K launch: the slices are added in slice order (same bits every run) into the C tile, then the
@@ -709,7 +841,9 @@ int launch_fwd_feat(const ConvArgs& a, hipStream_t st) {
     const size_t stage = (size_t)(BM + a.taps - 1 + BN * a.taps) * (KCT + KPAD) * sizeof(bf16);
     const size_t ctile = (size_t)(BM * (BN + 4) + 2 * BN) * sizeof(float);
     size_t need = stage > ctile ? stage : ctile;
-    if (a.e.w2 && need < ctile + (size_t)BM * A2S * sizeof(bf16)) need = ctile + (size_t)BM * A2S * sizeof(bf16);
+    // second GEMM: its operand rows behind the C tile, then (pre-activation copy only) that copy's two staging tiles
+    const size_t g2 = ctile + A2B + (a.e.pre2 ? 2 * A2B : 0);
+    if (a.e.w2 && need < g2) need = g2;
     if (need > 160 * 1024) return mm_fail(MM_ERR_UNSUPPORTED, "conv1d_fwd: LDS %zu B > 160 KiB", need);
     auto kern = conv1d_fwd_kernel<BM, BN, WM, WN, KCT, FEAT, TAPS>;
     if (need > 64 * 1024)
@@ -734,7 +868,7 @@ int launch_fwd_feat(const ConvArgs& a, hipStream_t st) {
 template <int BM, int BN, int WM, int WN, int KCT>
 int launch_fwd(const ConvArgs& a, hipStream_t st) {
     const unsigned m = epi_mask(a.e);
-    if (getenv("MM_EPI_GENERIC") || a.partial) return launch_fwd_feat<BM, BN, WM, WN, KCT, EF_ANY>(a, st);      // tests: generic vs compiled-in epilogues; split-K
+    if (getenv("MM_EPI_GENERIC") || a.partial || (a.e.w2 && a.e.act2 && a.e.act2 != MM_ACT_GELU)) return launch_fwd_feat<BM, BN, WM, WN, KCT, EF_ANY>(a, st);      // tests: generic vs compiled-in epilogues; split-K
 #define EPI_CASE(mask) case (mask): return launch_fwd_feat<BM, BN, WM, WN, KCT, (mask), LT>(a, st);
     if constexpr (BM == 64 && BN == 128 && KCT == 128) {
         constexpr int LT = 1;                 // the Linear layers: one tap
@@ -749,6 +883,7 @@ int launch_fwd(const ConvArgs& a, hipStream_t st) {
         if (a.taps == 1) switch (m) {
             EPI_CASE(EF_SHIFT | EF_F32 | EF_DROP | EF_RES | EF_LNF)   // out-proj / FFN-2 forward: bias, dropout, residual, fp32 out, LayerNorm of the result
             EPI_CASE(EF_SHIFT | EF_F32 | EF_DROP | EF_RES | EF_LNF | EF_GEMM2)   // ... and the next block's QKV projection of those LayerNorm rows (second GEMM)
+            EPI_CASE(EF_SHIFT | EF_F32 | EF_DROP | EF_RES | EF_LNF | EF_GEMM2 | EF_G2FFN1)   // out-projection, norm2 and the first FFN Linear of those rows (second GEMM: GELU, dropout, pre-activation copy)
             EPI_CASE(EF_SHIFT | EF_F32 | EF_DROP | EF_RES | EF_POOLOUT)   // last FFN-2 forward: ... and the mean over tokens instead of the LayerNorm
             EPI_CASE(EF_BF16)   // plain data gradient, bf16 out
             EPI_CASE(EF_LNBWD | EF_RES | EF_F32 | EF_BF16 | EF_DROP)   // data gradient + LayerNorm backward: skip gradient in, fp32 and masked bf16 out
@@ -1494,7 +1629,8 @@ static int linear128_fwd(const void* x, const void* w, int M, int K, const float
                          float* out_f32, float drop_p, uint32_t seed, const uint32_t* seed_epoch, float* pool_out,
                          int rows_per_group, const float* ln_gamma, const float* ln_beta, float ln_eps, void* ln_out,
                          float* ln_stat, hipStream_t st, const void* w2 = nullptr, const float* bias2 = nullptr, int n2 = 0,
-                         void* out2 = nullptr, int act2 = 0, float drop2_p = 0.f, uint32_t seed2 = 0, void* pre2 = nullptr) {
+                         void* out2 = nullptr, int act2 = 0, float drop2_p = 0.f, uint32_t seed2 = 0, void* pre2 = nullptr,
+                         ConvArgs* args_only = nullptr) {
     MM_REQUIRE(x && w && out_f32 && M > 0 && M % 32 == 0 && K > 0 && K % 16 == 0, "linear128_fwd: M=%d (x32) K=%d (x16)", M, K);
     MM_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "linear128_fwd: drop_p");
     MM_REQUIRE(!pool_out || (rows_per_group > 0 && rows_per_group % 32 == 0 && M % rows_per_group == 0),
@@ -1509,13 +1645,14 @@ static int linear128_fwd(const void* x, const void* w, int M, int K, const float
     if (pool_out) { a.e.pool_out = pool_out; a.e.pool_rows = rows_per_group; a.e.pool_scale = 1.f / (float)rows_per_group; }
     a.e.lnf_out = (bf16*)ln_out; a.e.lnf_stat = ln_stat; a.e.lnf_gamma = ln_gamma; a.e.lnf_beta = ln_beta; a.e.lnf_eps = ln_eps;
     if (w2) {
-        MM_REQUIRE(ln_out && out2 && n2 > 0 && n2 % 128 == 0, "linear128_fwd: the second GEMM needs the LayerNorm rows, an output and n2 %% 128 == 0 (n2=%d)", n2);
+        MM_REQUIRE(ln_out && (out2 || args_only) && n2 > 0 && n2 % 128 == 0, "linear128_fwd: the second GEMM needs the LayerNorm rows, an output and n2 %% 128 == 0 (n2=%d)", n2);
         MM_REQUIRE(drop2_p >= 0.f && drop2_p < 1.f && (size_t)M * n2 < (1ull << 32), "linear128_fwd: second GEMM dropout / 32-bit indices");
         a.e.w2 = (const bf16*)w2; a.e.bias2 = bias2; a.e.n2 = n2; a.e.out2 = (bf16*)out2;
         a.e.act2 = act2; a.e.pre2 = (bf16*)pre2;
         const DropH d2 = mm_drop(drop2_p);
         a.e.thresh2 = d2.thresh; a.e.inv_keep2 = d2.inv_keep; a.e.seed2 = seed2;
     }
+    if (args_only) { *args_only = a; return 0; }           // mm_ffn_rows_fwd launches the two halves itself
     return launch_fwd_32x128(a, st);
 }
 
@@ -1559,6 +1696,47 @@ int mm_linear_fwd_ln_gemm2_act(const void* x, const void* w, int M, int K, const
     MM_REQUIRE(ln_out_bf16 && w2 && out2_bf16, "linear_fwd_ln_gemm2_act: null");
     return linear128_fwd(x, w, M, K, bias, residual, out_f32, drop_p, seed, seed_epoch, nullptr, 0, ln_gamma, ln_beta, ln_eps,
                          ln_out_bf16, ln_stat, st, w2, bias2, n2, out2_bf16, act2, drop2_p, seed2, pre2_bf16);
+}
+
+// mm_linear_fwd_ln_gemm2_act followed, inside the launch, by the second FFN Linear on the hidden rows and that Linear's
+// own consumers: y = dropout(g W2^T + b2) + x1, then LayerNorm rows (+ stats) of y, optionally their projection wq (the next
+// block's in_proj), or - pool_out != NULL - the mean over groups of rows_per_group rows.  The 32 x n1 hidden tile never
+// leaves the workgroup: g_out / z_out (both nullable) are written only for a backward pass.  See include/mmeeg_hip.h.
+int mm_ffn_rows_fwd(const void* x, const void* w, int M, int K, const float* bias, const float* residual, float* x1_f32,
+                    float drop_p, uint32_t seed, const uint32_t* seed_epoch, const float* ln_gamma, const float* ln_beta,
+                    float ln_eps, void* ln_out_bf16, float* ln_stat, const void* w1, const float* bias1, int n1,
+                    void* g_bf16, void* z_bf16, int act1, float drop1_p, uint32_t seed1, const void* w2, const float* bias2,
+                    float* y_f32, float drop2_p, uint32_t seed2, const float* nln_gamma, const float* nln_beta, float nln_eps,
+                    void* nln_out_bf16, float* nln_stat, const void* wq, const float* biasq, int nq, void* q_bf16,
+                    float* pool_out, int rows_per_group, hipStream_t st) {
+    MM_REQUIRE(ln_out_bf16 && w1 && w2 && y_f32 && x1_f32, "ffn_rows_fwd: null");
+    MM_REQUIRE(K == 128, "ffn_rows_fwd: the out-projection is 128 -> 128 (K=%d)", K);
+    MM_REQUIRE(n1 > 0 && n1 % 128 == 0, "ffn_rows_fwd: n1=%d must be a multiple of 128", n1);
+    MM_REQUIRE((pool_out != nullptr) != (nln_out_bf16 != nullptr), "ffn_rows_fwd: one consumer - LayerNorm rows or pool_out");
+    MM_REQUIRE(!wq || (nln_out_bf16 && q_bf16), "ffn_rows_fwd: the projection needs the LayerNorm rows and an output");
+    FfnRowsArgs fa;
+    int rc = linear128_fwd(x, w, M, K, bias, residual, x1_f32, drop_p, seed, seed_epoch, nullptr, 0, ln_gamma, ln_beta, ln_eps,
+                           ln_out_bf16, ln_stat, st, w1, bias1, n1, g_bf16, act1, drop1_p, seed1, z_bf16, &fa.c);
+    if (rc) return rc;
+    ConvArgs t;
+    rc = linear128_fwd(g_bf16 ? g_bf16 : w2 /* never read: the operand is the LDS tile */, w2, M, n1, bias2, x1_f32, y_f32, drop2_p,
+                       seed2, seed_epoch, pool_out, rows_per_group, nln_gamma, nln_beta, nln_eps, nln_out_bf16, nln_stat, st, wq,
+                       biasq, nq, q_bf16, 0, 0.f, 0, nullptr, &t);
+    if (rc) return rc;
+    fa.t = t.e; fa.w3 = (const bf16*)w2;
+    const size_t stage = (size_t)(32 + 128) * (128 + KPAD) * sizeof(bf16);
+    size_t need = CT32 + A2B + (size_t)32 * (n1 + KPAD) * sizeof(bf16);
+    if (need < stage) need = stage;
+    MM_REQUIRE(need <= 64 * 1024, "ffn_rows_fwd: n1=%d needs %zu B of LDS (two workgroups per CU: 64 KiB each)", n1, need);
+    const EpiArgs& h = fa.c.e;
+    const bool spec = !getenv("MM_EPI_GENERIC") && h.shift && h.residual && h.drop_thresh && h.act2 == MM_ACT_GELU && h.pre2 &&
+                      h.thresh2 && fa.t.shift && fa.t.drop_thresh;
+    const int tail = pool_out ? 2 : (wq ? 1 : 0);
+    const dim3 grid(M / 32);
+#define FFN_CASE(S, T_) if (spec == S && tail == T_) hipLaunchKernelGGL((ffn_rows_fwd_kernel<S, T_>), grid, dim3(256), need, st, fa);
+    FFN_CASE(true, 0) FFN_CASE(true, 1) FFN_CASE(true, 2) FFN_CASE(false, 0) FFN_CASE(false, 1) FFN_CASE(false, 2)
+#undef FFN_CASE
+    return mm_check_launch("ffn_rows_fwd");
 }
 
 // dx = LayerNorm128_backward(dy @ W^T) + dres in one launch: the data-gradient GEMM of the Linear that

@@ -126,8 +126,8 @@ def _zeros(shape, like, dtype=_F32):
     return torch.zeros(shape, dtype=dtype, device=like.device)
 
 
-_NO_FFN1_FUSE = not os.environ.get("MM_FFN1_FUSE")        # the first FFN Linear inside the out-projection's launch: measured, not
-                                                           # faster (2-byte column stores of 2 x 16 MB) - off unless MM_FFN1_FUSE=1
+_NO_FFN1_FUSE = bool(os.environ.get("MM_NO_FFN1_FUSE"))   # A/B knob: the first FFN Linear as its own launch, not behind the out-projection
+_NO_FFN_ROWS = bool(os.environ.get("MM_NO_FFN_ROWS"))     # A/B knob: the second FFN Linear (and its consumers) as its own launch
 _NO_QKV_FUSE = bool(os.environ.get("MM_NO_QKV_FUSE"))     # A/B knob: the next block's QKV projection as its own launch
 _seed_state = {"base": 0x1234567, "step": 0, "epoch": None}
 
@@ -673,7 +673,8 @@ def transformer_block_fwd(x: torch.Tensor, blk, training: bool, need_dgrad: bool
     its input (``prenorm`` = (norm1(x) bf16, stats) handed in by the block below, ``next_norm`` = the next
     block's norm1, whose output is then returned in ``saved['next_prenorm']`` / as third result).  With ``next_blk`` the
     same launch also runs that block's QKV projection on those rows (a second GEMM: the third result then carries the
-    packed q | k | v as its third element)."""
+    packed q | k | v as its third element).  With a consumer for the finished rows (``pool_out`` or ``next_norm``) and an
+    FFN width that is a multiple of 128 up to 512, everything after attention is ONE launch (``mm_ffn_rows_fwd``)."""
     B, L, D = x.shape
     M = B * L
     save = training if save is None else save
@@ -692,6 +693,8 @@ def transformer_block_fwd(x: torch.Tensor, blk, training: bool, need_dgrad: bool
     s1 = _next_seed() if p > 0 else 0
     f1 = None
     s2 = None
+    rows = False
+    nxt = None
     if fuse_ln:
         wf, _, cinp, _ = weights.get(blk.self_attn.out_proj.weight, need_dgrad)
         x1 = _empty((M, D), _F32, x)
@@ -702,11 +705,41 @@ def transformer_block_fwd(x: torch.Tensor, blk, training: bool, need_dgrad: bool
         if c1 == 128 and n1 % 128 == 0 and M * n1 < (1 << 32) and not _NO_FFN1_FUSE:
             # the first FFN Linear (GELU, Dropout, pre-activation copy) runs on norm2's rows inside the out-projection's launch
             s2 = _next_seed() if p > 0 else 0
-            g1 = _empty((M, n1), _BF, x)
             z1 = _empty((M, n1), _BF, x) if save else None
-            _hip.call("mm_linear_fwd_ln_gemm2_act", o.view(M, D), wf, M, cinp, blk.self_attn.out_proj.bias, x2, x1, float(p),
-                      int(s1), EP(), blk.norm2.weight, blk.norm2.bias, float(blk.norm2.eps), h2, st2, w1, blk.linear1.bias,
-                      n1, g1, z1, ACT[blk._act], float(p), int(s2))
+            w2, _, c2, _ = weights.get(blk.linear2.weight, need_dgrad)
+            rows = (cinp == 128 and n1 <= 512 and c2 == n1 and not _NO_FFN_ROWS
+                    and (pool_out is not None or next_norm is not None))
+            if rows:
+                # ... and so does the second FFN Linear, on the hidden tile the workgroup still holds, with its consumers:
+                # the block's whole row-wise part is this one launch, and without a backward the hidden tensor is never written
+                s3 = _next_seed() if p > 0 else 0
+                g1 = _empty((M, n1), _BF, x) if save else None
+                x2o = _empty((M, D), _F32, x)
+                hn = stn = wq = bq = qn = None
+                nq = 0
+                if pool_out is None:
+                    hn = _empty((M, D), _BF, x)
+                    stn = _empty((M, 2), _F32, x) if save else None
+                    if next_blk is not None and not _NO_QKV_FUSE:
+                        wq, _, cq, _ = weights.get(next_blk.self_attn.in_proj_weight, need_dgrad)
+                        nq = next_blk.self_attn.in_proj_weight.shape[0]
+                        if cq != 128 or nq % 128 or M * nq >= (1 << 32):
+                            wq, nq = None, 0
+                    if wq is not None:
+                        bq = next_blk.self_attn.in_proj_bias
+                        qn = _empty((M, nq), _BF, x)
+                    nxt = (hn, stn, qn) if wq is not None else (hn, stn)
+                _hip.call("mm_ffn_rows_fwd", o.view(M, D), wf, M, cinp, blk.self_attn.out_proj.bias, x2, x1, float(p), int(s1),
+                          EP(), blk.norm2.weight, blk.norm2.bias, float(blk.norm2.eps), h2, st2, w1, blk.linear1.bias, n1, g1, z1,
+                          ACT[blk._act], float(p), int(s2), w2, blk.linear2.bias, x2o, float(p), int(s3),
+                          None if hn is None else next_norm.weight, None if hn is None else next_norm.bias,
+                          float(next_norm.eps) if hn is not None else 0.0, hn, stn, wq, bq, nq, qn, pool_out,
+                          L if pool_out is not None else 0)
+            else:
+                g1 = _empty((M, n1), _BF, x)
+                _hip.call("mm_linear_fwd_ln_gemm2_act", o.view(M, D), wf, M, cinp, blk.self_attn.out_proj.bias, x2, x1, float(p),
+                          int(s1), EP(), blk.norm2.weight, blk.norm2.bias, float(blk.norm2.eps), h2, st2, w1, blk.linear1.bias,
+                          n1, g1, z1, ACT[blk._act], float(p), int(s2))
             f1 = {"bf16": g1, "pre": z1, "f32": None}
         else:
             _hip.call("mm_linear_fwd_ln", o.view(M, D), wf, M, cinp, blk.self_attn.out_proj.bias, x2, x1, float(p), int(s1),
@@ -720,9 +753,11 @@ def transformer_block_fwd(x: torch.Tensor, blk, training: bool, need_dgrad: bool
         s2 = _next_seed() if p > 0 else 0
         f1 = linear_rows(h2, blk.linear1.weight, blk.linear1.bias, act=blk._act, out_pre=save,
                          drop_p=p, seed=s2, need_dgrad=need_dgrad)
-    s3 = _next_seed() if p > 0 else 0
-    nxt = None
-    if pool_out is not None:
+    if not rows:
+        s3 = _next_seed() if p > 0 else 0
+    if rows:
+        pass                                                    # linear2 and its consumers ran in the launch above
+    elif pool_out is not None:
         wf, _, cinp, _ = weights.get(blk.linear2.weight, need_dgrad)
         x2o = _empty((M, D), _F32, x)
         _hip.call("mm_linear_fwd_meanpool", f1["bf16"], wf, M, cinp, blk.linear2.bias, x1, x2o, float(p), int(s3),
