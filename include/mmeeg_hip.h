@@ -514,6 +514,30 @@ int mm_clip_loss_ws_floats(int B, int Bg, int* floats_host, hipStream_t stream);
 int mm_clip_loss_own_rows_grouped(const float* z_all, const int* gid_all, const float* logit_scale, float* scal4,
                                   float* dz_local, float* ws, int B, int Bg, int N, int row0, hipStream_t stream);
 int mm_clip_loss_grouped_ws_floats(int B, int Bg, int* floats_host, hipStream_t stream);
+/* pairwise sigmoid loss (Zhai et al., "Sigmoid Loss for Language Image Pre-Training") on the same inputs: z_all [Bg][2N]
+ * L2-normalised [ze | zf] rows of the gathered batch, this rank's pairs at rows [row0, row0+B), gid_all int32 [Bg] or
+ * NULL, and two device scalars logit_scale (ln s) and logit_bias (b).  Every pair is its own binary problem:
+ *   C[r][j] = ze_r . zf_j        s = exp(logit_scale)        u[r][j] = s C[r][j] + b
+ *   y[r][j] = +1 if (gid NULL ? r == j : gid_r == gid_j) else -1
+ *   l[r][j] = softplus(-y[r][j] u[r][j])        loss_r = sum_j l[r][j]  (all Bg columns)
+ *   rank loss       = (1/B) sum_{r own} loss_r
+ *   G[r][j]         = -y[r][j] s sigmoid(-y[r][j] u[r][j])        (= d l[r][j] / d C[r][j])
+ *   dze_r           = (1/B) sum_j G[r][j] zf_j        dzf_r = (1/B) sum_j G[j][r] ze_j        (r own; j over all Bg)
+ *   d/d logit_scale = (1/B) sum_{r own} sum_j G[r][j] C[r][j]
+ *   d/d logit_bias  = (1/B) sum_{r own} sum_j -y[r][j] sigmoid(-y[r][j] u[r][j])
+ * dz_local [B][2N] = [dze | dzf] (nullable: scalars only; plain stores) is, as for InfoNCE, d (SUM over ranks of their
+ * rank losses) / d (own rows): column r's terms G[j][r] belong to other ranks' rows and are evaluated here from the
+ * gathered batch, so no reduce-scatter is needed.  scal5 = {rank loss, top1 e->f, top1 f->e, d/d logit_scale,
+ * d/d logit_bias} (plain stores); the top-1 flags are mm_clip_loss_own_rows_grouped's: row r counts when its best positive
+ * reaches the row maximum of C (a tie FOR it), f->e the same over column r.  All fp32; softplus(x) = max(x, 0) +
+ * log1p(exp(-|x|)) with an accurate log1p, sigmoid from the same exp(-|x|).  No float atomics, every sum in a fixed order:
+ * same inputs -> bit-identical outputs.  ws = mm_sigmoid_loss_ws_floats(B, Bg) floats (per-row scalars), no
+ * initialisation.  N % 4 == 0.  Two launches on `stream`; no row reads another row's results.
+ * Extension: the reference has no contrastive trainer. */
+int mm_sigmoid_loss_own_rows(const float* z_all, const int* gid_all, const float* logit_scale, const float* logit_bias,
+                             float* scal5, float* dz_local, float* ws, int B, int Bg, int N, int row0,
+                             hipStream_t stream);
+int mm_sigmoid_loss_ws_floats(int B, int Bg, int* floats_host, hipStream_t stream);
 
 /* ---- gallery-scale retrieval (csrc/retrieval.hip) ---------------------------
  * For each query row q of Q [Nq][D] against gallery G [Ng][D] (fp32, row-major, 16-byte aligned; callers pass

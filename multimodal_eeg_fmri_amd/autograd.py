@@ -882,3 +882,31 @@ class ClipLossFn(torch.autograd.Function):
     def backward(ctx, g_loss, g_a, g_b):
         dz, scal = ctx.saved_tensors
         return dz * g_loss, (scal[3] * g_loss).reshape(()), None, None
+
+
+class SigmoidLossFn(torch.autograd.Function):
+    """`ClipLossFn` for the pairwise sigmoid loss (``mm_sigmoid_loss_own_rows``): the same gather of embeddings and ids,
+    the same own-rows gradient; one more learnable scalar, ``logit_bias``."""
+
+    @staticmethod
+    def forward(ctx, z, logit_scale, logit_bias, group, gid=None):
+        from . import dp
+        z = z.contiguous().float()
+        B, N2 = z.shape
+        rank = dp.rank(group)
+        z_all = dp.gather_embeddings(z, group)
+        need_grad = z.requires_grad or logit_scale.requires_grad or logit_bias.requires_grad
+        scal = _empty((5,), _F32, z)
+        dz = _empty((B, N2), _F32, z) if need_grad else None
+        ls = logit_scale.detach().reshape(1).float().contiguous()
+        lb = logit_bias.detach().reshape(1).float().contiguous()
+        gid_all = None if gid is None else dp.gather_embeddings(gid.view(B, 1), group).view(-1)
+        ops.sigmoid_loss_own_rows(z_all, gid_all, ls, lb, scal, dz, B, rank * B)
+        if need_grad:
+            ctx.save_for_backward(dz, scal)
+        return scal[0].clone(), scal[1].clone(), scal[2].clone()
+
+    @staticmethod
+    def backward(ctx, g_loss, g_a, g_b):
+        dz, scal = ctx.saved_tensors
+        return dz * g_loss, (scal[3] * g_loss).reshape(()), (scal[4] * g_loss).reshape(()), None, None

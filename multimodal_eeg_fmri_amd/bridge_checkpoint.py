@@ -10,7 +10,8 @@ The file is the container of the reference's loops and of `FlexibleTrainer.save_
   layer group, so its slices are mapped back to that order); the frozen half of the bridge has no entry;
 * ``bridge_trainer_state``: the optimizer words (step count, lr, ...), the hyperparameters, the EEG branch kind, the
   model's shapes, the head count of every transformer block, the world size, the bucket layout, the dropout stream,
-  the state of `fit` and - only for a trainer with an augmenter - ``augment``: its parameters and the step index.
+  the state of `fit`, - only for a trainer with an augmenter - ``augment``: its parameters and the step index, and -
+  only for a trainer of the pairwise sigmoid loss - ``loss`` = ``"sigmoid"`` (absent: InfoNCE).
 
 The step itself is untouched: saving and loading are copies, `fit` only calls `train_step` and `embed`.
 
@@ -142,6 +143,8 @@ class TrainerCheckpointMixin:
         bts.update(self._layout())
         if getattr(self, "augment", None) is not None:             # (absent without an augmenter: the container is unchanged)
             bts["augment"] = dict(self.augment.params(), step=int(self._aug_step))
+        if getattr(self, "loss", "infonce") != "infonce":          # (absent for the default loss: the container is unchanged)
+            bts["loss"] = self.loss
         return {"epoch": epoch, "model_state_dict": {k: _cpu(v) for k, v in self.state_dict().items()},
                 "optimizer_state_dict": {"state": state, "param_groups": [group]},
                 "scheduler_state_dict": scheduler.state_dict() if scheduler is not None else None,
@@ -163,6 +166,9 @@ class TrainerCheckpointMixin:
                     raise ValueError(f"load_checkpoint_state: {field} differs: checkpoint {bts.get(field)!r}, "
                                      f"trainer {mine[field]!r}")
         same("eeg_kind", "world")
+        loss, theirs_loss = getattr(self, "loss", "infonce"), bts.get("loss", "infonce")
+        if loss != theirs_loss:                                    # before the shapes: logit_bias exists under one loss only
+            raise ValueError(f"load_checkpoint_state: loss differs: checkpoint {theirs_loss!r}, trainer {loss!r}")
         # a checkpoint written before the head counts were recorded comes from a trainer whose blocks all had 4 heads
         heads = bts.get("heads", [[n, 4] for n, _ in mine["heads"]])
         if heads != mine["heads"]:
@@ -209,7 +215,7 @@ class TrainerCheckpointMixin:
         """continue bit for bit from `checkpoint_state`: parameters, BatchNorm buffers, Adam moments, optimizer words,
         hyperparameters and the dropout stream, all copied in place.  Any captured step is dropped; the next
         graph-mode `train_step` captures again with the checkpoint's seeds and epoch word.  The process-global dropout
-        counter (``ops._seed_state``) is set from the checkpoint.  A checkpoint of another EEG branch, shape, bucket
+        counter (``ops._seed_state``) is set from the checkpoint.  A checkpoint of another EEG branch, loss, shape, bucket
         layout or world size raises ValueError before anything is touched."""
         self._check_compatible(sd)
         bts = sd["bridge_trainer_state"]

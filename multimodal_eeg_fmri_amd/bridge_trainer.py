@@ -45,7 +45,7 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
                  bridge_dim: int = 128, dropout: float = 0.3, lr: float = 1e-4,
                  weight_decay: float = 1e-4, grad_clip: float = 1.0, betas=(0.9, 0.999),
                  eps: float = 1e-8, group=None, device="cuda", mode: str = "graph", eeg_encoder: Optional[nn.Module] = None,
-                 num_heads: int = 4, num_layers: int = 2, augment=None):
+                 num_heads: int = 4, num_layers: int = 2, augment=None, loss: str = "infonce"):
         """``eeg_encoder``: the EEG branch when it is not the default ``EnhancedERPEncoder(eeg_channels, hidden_dim,
         num_layers, num_heads, dropout)`` - an ``EnhancedPowerEncoder`` (enhanced_models_v4.py:196-285) or a
         ``MultiScaleSTFTPowerEncoder`` (BASELINE config #5: raw EEG -> multi-scale STFT power -> a4); it must end in
@@ -53,7 +53,10 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
         (checked at the first step, not here: a trainer built on the CPU to read weights takes any shape).
         ``augment``: an ``EEGTransforms`` (crossmodal_eeg_scr.py) - every `train_step` then augments its EEG batch on the
         device (noise + channel drop, csrc/augment.hip), drawing step index 0, 1, 2, ... from the trainer's own counter and
-        this process's rank; `evaluate`, `embed`, `evaluate_retrieval`, `explain` and `forward` never augment."""
+        this process's rank; `evaluate`, `embed`, `evaluate_retrieval`, `explain` and `forward` never augment.
+        ``loss``: "infonce" (default: the symmetric InfoNCE, mm_clip_loss_own_rows*) or "sigmoid" (the pairwise sigmoid
+        loss, mm_sigmoid_loss_own_rows: no softmax normaliser, so its signal does not depend on the number of in-batch
+        negatives; one more trained scalar, ``head.logit_bias``)."""
         super().__init__()
         if augment is not None:
             from .crossmodal_eeg_scr import EEGTransforms
@@ -74,7 +77,8 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
         else:
             raise TypeError(f"BridgeTrainer: no tape for an EEG encoder of type {type(self.eeg_encoder).__name__}")
         self.fmri_encoder = fMRIVolumeEncoder3D(1, fmri_dim, dropout=dropout)
-        self.head = EEGfMRIContrastiveBridge(hidden_dim, fmri_dim, bridge_dim, dropout)
+        self.head = EEGfMRIContrastiveBridge(hidden_dim, fmri_dim, bridge_dim, dropout, loss=loss)
+        self.loss = loss
         self.to(device)
         self.group = group
         self.two_streams = True
@@ -101,6 +105,8 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
         # (first hand-over) | fMRI encoder (its own, shorter backward).  Each group is one contiguous range of the
         # flat bucket, the fMRI encoder's the tail [fmri_lo, n).
         head_params = [p for p in br.parameters() if p.requires_grad] + [self.head.logit_scale]
+        if loss == "sigmoid":
+            head_params.append(self.head.logit_bias)
         if self._eeg_kind == "erp":
             cl = self.eeg_encoder.conv_layers
             conv1 = list(cl[0].parameters()) + list(cl[1].parameters())
@@ -124,10 +130,10 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
         self._works = []                              # asynchronous all-reduces of the running step (waited for by the optimizer)
         self.capture_mode = None                      # "one graph" | "one graph + captured RCCL collectives" | "3 segments + 2 eager collectives"
         self.bucket.state[2] = lr
-        # {loss, top-1 e->f, top-1 f->e, d loss / d logit_scale} of the last step: owned by this trainer
-        # (plain stores of the loss kernel), so the tensors a step returns are overwritten only by THIS
-        # trainer's next step - keep a value with .item() / .clone()
-        self._scal = torch.zeros(4, device=device)
+        # {loss, top-1 e->f, top-1 f->e, d loss / d logit_scale} (sigmoid: + d loss / d logit_bias) of the last step:
+        # owned by this trainer (plain stores of the loss kernel), so the tensors a step returns are overwritten only
+        # by THIS trainer's next step - keep a value with .item() / .clone()
+        self._scal = torch.zeros(5 if loss == "sigmoid" else 4, device=device)
         ops.weights_changed()
 
     @property
@@ -270,9 +276,14 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
         """symmetric InfoNCE of this rank's rows against the gathered batch, gradient w.r.t. ITS rows only
         (``mm_clip_loss_own_rows``: every rank evaluates all rows of the gathered batch, so no reduce-scatter
         of column gradients is needed).  ``scal`` = the trainer's own 4-float result buffer, ``dz`` (B, 2N): both written with plain stores.
-        ``gid_all``: the gathered int32 group ids -> the grouped loss (``mm_clip_loss_own_rows_grouped``)."""
+        ``gid_all``: the gathered int32 group ids -> the grouped loss (``mm_clip_loss_own_rows_grouped``).
+        ``loss="sigmoid"``: the pairwise sigmoid loss on the same inputs (``mm_sigmoid_loss_own_rows``), ``scal`` 5 floats."""
         ls = self.head.logit_scale.detach().reshape(1)
-        ops.clip_loss_own_rows(z_all, gid_all, ls, scal, dz, dz.shape[0], dp.rank(self.group) * dz.shape[0])
+        B, row0 = dz.shape[0], dp.rank(self.group) * dz.shape[0]
+        if self.loss == "sigmoid":
+            ops.sigmoid_loss_own_rows(z_all, gid_all, ls, self.head.logit_bias.detach().reshape(1), scal, dz, B, row0)
+        else:
+            ops.clip_loss_own_rows(z_all, gid_all, ls, scal, dz, B, row0)
         self._stamp(6)
 
     def _reduce_group(self, ready: str):
@@ -292,6 +303,8 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
         with deferred(bag, dz.device):           # ONE batched reduction after both branches joined
             # d loss / d logit_scale (scal[3]) rides in the same batched reduction launch
             bag.defer(scal.data_ptr() + 12, self.head.logit_scale._mm_grad.view(1), 1, 1, 1, keep=scal)
+            if self.loss == "sigmoid":           # and d loss / d logit_bias (scal[4])
+                bag.defer(scal.data_ptr() + 16, self.head.logit_bias._mm_grad.view(1), 1, 1, 1, keep=scal)
             dfe, dff = contrastive_embed_bwd(bag, sv_h, dz)
             self._stamp(7)
             main = torch.cuda.current_stream()

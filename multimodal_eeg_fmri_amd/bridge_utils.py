@@ -70,13 +70,27 @@ class EEGfMRIContrastiveBridge(nn.Module):
     ``bridge`` carries the reference-compatible parameters (its ``eeg_proj`` and
     ``fmri_proj`` are the trained heads); ``logit_scale`` = ln(1/tau) is the one
     extra learnable scalar (CLIP convention, tau0 = 0.07).
+
+    ``loss``: "infonce" (default; ops.clip_loss) or "sigmoid" (the pairwise sigmoid
+    loss of Zhai et al., ops.sigmoid_loss).  With "sigmoid" ``logit_scale`` starts at
+    ln(``init_scale``) and a second learnable scalar ``logit_bias`` = ``init_bias``
+    exists (the paper's 10 and -10); it is absent otherwise.
     """
 
+    LOSSES = ("infonce", "sigmoid")
+
     def __init__(self, eeg_dim=128, fmri_dim=64, bridge_dim=128, dropout=0.3,
-                 init_tau: float = 0.07):
+                 init_tau: float = 0.07, loss: str = "infonce", init_scale: float = 10.0, init_bias: float = -10.0):
         super().__init__()
+        if loss not in self.LOSSES:
+            raise ValueError(f"EEGfMRIContrastiveBridge: loss must be one of {list(self.LOSSES)}, got {loss!r}")
+        self.loss = loss
         self.bridge = EEGfMRIBridgeFusionNet(eeg_dim, fmri_dim, bridge_dim, dropout=dropout)
-        self.logit_scale = nn.Parameter(torch.tensor(math.log(1.0 / init_tau)))
+        if loss == "sigmoid":
+            self.logit_scale = nn.Parameter(torch.tensor(math.log(init_scale)))
+            self.logit_bias = nn.Parameter(torch.tensor(float(init_bias)))
+        else:
+            self.logit_scale = nn.Parameter(torch.tensor(math.log(1.0 / init_tau)))
 
     def embed(self, eeg_feats, fmri_feats):
         """L2-normalised (ze, zf), each (B, bridge_dim) fp32."""
@@ -86,9 +100,11 @@ class EEGfMRIContrastiveBridge(nn.Module):
         """-> (loss, top1_eeg_to_fmri, top1_fmri_to_eeg).  With a process
         ``group`` the columns are the all-gathered global batch.  ``groups``:
         (B,) integer ids (e.g. subjects); pairs with equal ids are positives of
-        each other (ops.clip_loss)."""
+        each other (ops.clip_loss / ops.sigmoid_loss)."""
         gid = ops.group_ids(groups, eeg_feats.shape[0], eeg_feats.device, "EEGfMRIContrastiveBridge")
         ze, zf = self.embed(eeg_feats, fmri_feats)
+        if self.loss == "sigmoid":
+            return ops.sigmoid_loss(ze, zf, self.logit_scale, self.logit_bias, group, gid)
         return ops.clip_loss(ze, zf, self.logit_scale, group, gid)
 
 

@@ -1,6 +1,7 @@
 // The fused batch-pairwise cosine-similarity / symmetric InfoNCE loss of the contrastive bridge with its gradients, for
-// plain and for subject-grouped positives: one kernel pair, four entry points.  Callers: ops.clip_loss_own_rows* and
-// ops.clip_loss*_ws_floats (bridge_trainer.py's step, autograd.py's tape).
+// plain and for subject-grouped positives: one kernel pair, four entry points; and the pairwise sigmoid (SigLIP) loss on
+// the same inputs and helpers: two kernels, two entry points.  Callers: ops.clip_loss_own_rows*, ops.clip_loss*_ws_floats,
+// ops.sigmoid_loss_own_rows and ops.sigmoid_loss_ws_floats (bridge_trainer.py's step, autograd.py's tape).
 #include "common.h"
 
 namespace {
@@ -91,6 +92,29 @@ __device__ __forceinline__ void clip_max2(float& a, float& c, float* red) {
     a = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
     c = fmaxf(fmaxf(red[4], red[5]), fmaxf(red[6], red[7]));
     __syncthreads();
+}
+
+// one row of dz from the row's dL/dC in LDS: orow[0, N) = dze = sum_j cr[j] zf_j, orow[N, 2N) = dzf = sum_j cc[j] ze_j;
+// every sum in ascending j, plain stores
+__device__ __forceinline__ void clip_dz_row(const float* __restrict__ z_all, const ClipShared& sh, float* __restrict__ orow,
+                                            int Bg, int N) {
+    const int LD = 2 * N;
+    for (int n = threadIdx.x; n < 2 * N; n += 256) {        // first half: dze (columns of zf), second half: dzf
+        const bool first = n < N;
+        const float* g = first ? sh.cr : sh.cc;
+        const float* col = z_all + (first ? N + n : n - N);
+        float acc = 0.f;
+        int j = 0;
+        for (; j + 8 <= Bg; j += 8) {                       // 8 loads in flight, summed in order
+            float v[8];
+#pragma unroll
+            for (int q = 0; q < 8; ++q) v[q] = col[(size_t)(j + q) * LD];
+#pragma unroll
+            for (int q = 0; q < 8; ++q) acc += g[j + q] * v[q];
+        }
+        for (; j < Bg; ++j) acc += g[j] * col[(size_t)j * LD];
+        orow[n] = acc;
+    }
 }
 
 template <bool GROUPED>
@@ -202,23 +226,92 @@ __global__ __launch_bounds__(256) void clip_rows_kernel(const float* __restrict_
         sh.cr[j] = k * ga; sh.cc[j] = k * gc;
     }
     __syncthreads();
-    float* orow = dz + (size_t)i * LD;
-    for (int n = tid; n < 2 * N; n += 256) {                // first half: dze (columns of zf), second half: dzf
-        const bool first = n < N;
-        const float* g = first ? sh.cr : sh.cc;
-        const float* col = z_all + (first ? N + n : n - N);
-        float acc = 0.f;
-        int j = 0;
-        for (; j + 8 <= Bg; j += 8) {                       // 8 loads in flight, summed in order
-            float v[8];
-#pragma unroll
-            for (int q = 0; q < 8; ++q) v[q] = col[(size_t)(j + q) * LD];
-#pragma unroll
-            for (int q = 0; q < 8; ++q) acc += g[j + q] * v[q];
-        }
-        for (; j < Bg; ++j) acc += g[j] * col[(size_t)j * LD];
-        orow[n] = acc;
+    clip_dz_row(z_all, sh, dz + (size_t)i * LD, Bg, N);
+}
+
+// ---------------------------------------------------------------------------
+// pairwise sigmoid loss (Zhai et al., "Sigmoid Loss for Language Image Pre-Training") over the gathered batch: every
+// (EEG r, fMRI j) pair is its own binary problem, so no row or column normaliser and no pass over other rows' results.
+//   u[r][j] = s C[r][j] + b   (s = exp(logit_scale), b = logit_bias)      y[r][j] = +1 for a positive pair, else -1
+//   l[r][j] = softplus(-y u)    loss_r = sum_j l[r][j]    G[r][j] = d l / d C = -y s sigmoid(-y u)
+//   dze_r = 1/B sum_j G[r][j] zf_j    dzf_r = 1/B sum_j G[j][r] ze_j    (column r's terms belong to other ranks' rows and
+//   are evaluated here from the gathered batch: the sum over ranks of their losses, as for InfoNCE)
+// sigmoid_rows_kernel (one workgroup per OWN row gi): row gi and column gi of C, one sweep over j -> G[gi][j], G[j][gi]
+//   in LDS and the row's {loss, top-1 e->f, top-1 f->e, d/d logit_scale, d/d logit_bias} -> ws[5][B]; then its dz row.
+// sigmoid_sum_kernel (one wave): the own rows' scalars summed in a fixed order -> scal[5].  A second launch and not a
+//   last-arriving workgroup: stream order is the only ordering the result then depends on.
+// softplus(x) = max(x, 0) + log1p(exp(-|x|)) and sigmoid(x) from the same exp(-|x|); expf / log1pf, not the fast forms:
+// well-separated pairs have losses of 1e-7 each, which log(1 + e) would quantise to multiples of 2^-24.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ void sigmoid_pair(float u, bool pos, float& l, float& dl_du) {
+    const float x = pos ? -u : u;                             // -y u
+    const float e = expf(-fabsf(x));
+    l = fmaxf(x, 0.f) + log1pf(e);
+    const float sg = (x >= 0.f ? 1.f : e) / (1.f + e);        // sigmoid(x)
+    dl_du = pos ? -sg : sg;                                   // -y sigmoid(-y u)
+}
+
+template <bool GROUPED>
+__global__ __launch_bounds__(256) void sigmoid_rows_kernel(const float* __restrict__ z_all, const float* __restrict__ logit_scale,
+                                                           const float* __restrict__ logit_bias, float* __restrict__ ws,
+                                                           float* __restrict__ dz, int B, int Bg, int N, int row0,
+                                                           const int* __restrict__ gid) {
+    extern __shared__ float sm[];
+    const ClipShared sh = clip_shared(sm, N, Bg);
+    const int i = blockIdx.x, gi = row0 + i, tid = threadIdx.x;
+    const float s = expf(logit_scale[0]), b = logit_bias[0];
+    const float invB = 1.f / (float)B;
+    int gg = 0;
+    if constexpr (GROUPED) gg = gid[gi];
+    float mxr, mxc;
+    clip_cosines(z_all, gi, Bg, N, sh, mxr, mxc);
+    float pmr = -INFINITY, pmc = -INFINITY;                  // maxima over the positive set (the top-1 test, as for InfoNCE)
+    if constexpr (GROUPED) {
+        for (int j = tid; j < Bg; j += 256)
+            if (gid[j] == gg) { pmr = fmaxf(pmr, sh.cr[j]); pmc = fmaxf(pmc, sh.cc[j]); }
+        clip_max2(pmr, pmc, sh.red);
+    } else {
+        pmr = sh.cr[gi]; pmc = sh.cc[gi];
+        __syncthreads();                                     // the sweep below overwrites cr / cc
     }
+    float loss = 0.f, ds = 0.f, db = 0.f, none = 0.f;
+    for (int j = tid; j < Bg; j += 256) {
+        const float a = sh.cr[j], c = sh.cc[j];
+        bool pos;
+        if constexpr (GROUPED) pos = gid[j] == gg; else pos = j == gi;
+        float l, g;
+        sigmoid_pair(s * a + b, pos, l, g);                  // pair (gi, j): the row's loss and scalar gradients
+        loss += l; db += g; ds += s * g * a;
+        if (dz) {
+            sh.cr[j] = invB * s * g;
+            sigmoid_pair(s * c + b, pos, l, g);              // pair (j, gi): row j's term in dzf of gi
+            sh.cc[j] = invB * s * g;
+        }
+    }
+    clip_sum2(loss, ds, sh.red);                             // (its barriers also publish cr / cc to the dz pass)
+    clip_sum2(db, none, sh.red);
+    if (tid == 0) {
+        ws[i] = loss;
+        ws[B + i] = pmr >= mxr ? 1.f : 0.f;                  // the best positive reaches the row maximum (a tie counts FOR it)
+        ws[2 * B + i] = pmc >= mxc ? 1.f : 0.f;
+        ws[3 * B + i] = ds;
+        ws[4 * B + i] = db;
+    }
+    if (dz) clip_dz_row(z_all, sh, dz + (size_t)i * 2 * N, Bg, N);
+}
+
+__global__ __launch_bounds__(64) void sigmoid_sum_kernel(const float* __restrict__ ws, float* __restrict__ scal, int B) {
+    const int tid = threadIdx.x;
+    float acc[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+    for (int r0 = 0; r0 < B; r0 += 64) {                     // 64 rows at a time, chunks in ascending order
+        float v[5];
+#pragma unroll
+        for (int q = 0; q < 5; ++q) v[q] = (r0 + tid < B) ? ws[(size_t)q * B + r0 + tid] : 0.f;
+#pragma unroll
+        for (int q = 0; q < 5; ++q) acc[q] += wave_sum(v[q]);
+    }
+    if (tid < 5)
+        scal[tid] = (tid == 0 ? acc[0] : tid == 1 ? acc[1] : tid == 2 ? acc[2] : tid == 3 ? acc[3] : acc[4]) / (float)B;
 }
 }  // namespace
 
@@ -226,19 +319,27 @@ extern "C" {
 // floats-per-Bg rows of the loss workspace: the only place the count is written (layout: see clip_lse_kernel)
 static int clip_ws_rows(bool grouped) { return grouped ? 8 : 6; }
 
-// the checks and the two launches of both loss entry points; gid = nullptr: the ungrouped loss
-static int clip_loss_launch(const char* who, const float* z_all, const int* gid, const float* logit_scale, float* scal4,
-                            float* dz_local, float* ws, int B, int Bg, int N, int row0, hipStream_t st) {
+// the shape checks of every loss entry point of this file -> the launches' LDS bytes (ClipShared)
+static int clip_check_shape(const char* who, int B, int Bg, int N, int row0, size_t* lds) {
     MM_REQUIRE(B > 0 && Bg >= B && row0 >= 0 && row0 + B <= Bg && N > 0, "%s: B=%d Bg=%d row0=%d", who, B, Bg, row0);
     MM_REQUIRE(N % 4 == 0, "%s: N=%d must be a multiple of 4 (16-byte row loads)", who, N);
-    const size_t lds = (size_t)(2 * N + 2 * Bg + 32) * sizeof(float);
-    MM_REQUIRE(lds <= 64 * 1024, "%s: N/Bg too large for LDS", who);
+    *lds = (size_t)(2 * N + 2 * Bg + 32) * sizeof(float);
+    MM_REQUIRE(*lds <= 64 * 1024, "%s: N/Bg too large for LDS", who);
+    return 0;
+}
+
+// the checks and the two launches of both InfoNCE entry points; gid = nullptr: the ungrouped loss
+static int clip_loss_launch(const char* who, const float* z_all, const int* gid, const float* logit_scale, float* scal4,
+                            float* dz_local, float* ws, int B, int Bg, int N, int row0, hipStream_t st) {
+    size_t lds;
+    int rc = clip_check_shape(who, B, Bg, N, row0, &lds);
+    if (rc) return rc;
     const auto lse = gid ? clip_lse_kernel<true> : clip_lse_kernel<false>;
     const auto rows = gid ? clip_rows_kernel<true> : clip_rows_kernel<false>;
     hipLaunchKernelGGL(lse, dim3(Bg), dim3(256), lds, st, z_all, logit_scale, ws, Bg, N, gid);
     char what[64];
     snprintf(what, sizeof what, "%s(lse)", who);
-    int rc = mm_check_launch(what);
+    rc = mm_check_launch(what);
     if (rc) return rc;
     hipLaunchKernelGGL(rows, dim3(B), dim3(256), lds, st, z_all, logit_scale, ws, scal4, dz_local, B, Bg, N, row0, gid);
     snprintf(what, sizeof what, "%s(rows)", who);
@@ -267,5 +368,25 @@ int mm_clip_loss_own_rows_grouped(const float* z_all, const int* gid_all, const 
                                   float* ws, int B, int Bg, int N, int row0, hipStream_t st) {
     MM_REQUIRE(z_all && gid_all && logit_scale && scal4 && ws, "clip_loss_own_rows_grouped: null");
     return clip_loss_launch("clip_loss_own_rows_grouped", z_all, gid_all, logit_scale, scal4, dz_local, ws, B, Bg, N, row0, st);
+}
+
+int mm_sigmoid_loss_ws_floats(int B, int Bg, int* floats_host, hipStream_t) {
+    MM_REQUIRE(floats_host && B > 0 && Bg >= B, "sigmoid_loss_ws_floats: bad args");
+    *floats_host = 5 * B;                                    // layout: see sigmoid_rows_kernel
+    return 0;
+}
+
+int mm_sigmoid_loss_own_rows(const float* z_all, const int* gid_all, const float* logit_scale, const float* logit_bias,
+                             float* scal5, float* dz_local, float* ws, int B, int Bg, int N, int row0, hipStream_t st) {
+    MM_REQUIRE(z_all && logit_scale && logit_bias && scal5 && ws, "sigmoid_loss_own_rows: null");
+    size_t lds;
+    int rc = clip_check_shape("sigmoid_loss_own_rows", B, Bg, N, row0, &lds);
+    if (rc) return rc;
+    const auto rows = gid_all ? sigmoid_rows_kernel<true> : sigmoid_rows_kernel<false>;
+    hipLaunchKernelGGL(rows, dim3(B), dim3(256), lds, st, z_all, logit_scale, logit_bias, ws, dz_local, B, Bg, N, row0, gid_all);
+    rc = mm_check_launch("sigmoid_loss_own_rows(rows)");
+    if (rc) return rc;
+    hipLaunchKernelGGL(sigmoid_sum_kernel, dim3(1), dim3(64), 0, st, ws, scal5, B);
+    return mm_check_launch("sigmoid_loss_own_rows(sum)");
 }
 }  // extern "C"

@@ -451,6 +451,19 @@ def clip_loss_own_rows(z_all, gid_all, logit_scale1, scal, dz, B: int, row0: int
         _hip.call("mm_clip_loss_own_rows_grouped", z_all, gid_all, logit_scale1, scal, dz, ws, B, Bg, N2 // 2, row0)
 
 
+def sigmoid_loss_ws_floats(B: int, Bg: int) -> int:
+    """floats of the scratch of mm_sigmoid_loss_own_rows for B own rows of a Bg-row gathered batch (plain and grouped alike)"""
+    return _hip.host_int("mm_sigmoid_loss_ws_floats", B, Bg)
+
+
+def sigmoid_loss_own_rows(z_all, gid_all, logit_scale1, logit_bias1, scal, dz, B: int, row0: int):
+    """pairwise sigmoid loss of rows [row0, row0 + B) of the gathered batch z_all (Bg, 2N) -> scal (5,), dz (B, 2N) or None;
+    gid_all (Bg,) int32 group ids: pairs with equal ids are positives, None: pair i only.  Allocates the workspace."""
+    Bg, N2 = z_all.shape
+    ws = _empty((sigmoid_loss_ws_floats(B, Bg),), _F32, z_all)
+    _hip.call("mm_sigmoid_loss_own_rows", z_all, gid_all, logit_scale1, logit_bias1, scal, dz, ws, B, Bg, N2 // 2, row0)
+
+
 def group_ids(groups, n: int, device=None, who: str = "groups") -> Optional[torch.Tensor]:
     """Validate a (n,) vector of group ids (e.g. subject indices; compared for equality only) -> int32 on ``device``, or
     None for None.  A host tensor of any integer dtype is range-checked and converted; a device tensor must already be
@@ -1298,6 +1311,15 @@ def clip_loss(ze, zf, logit_scale, group=None, groups=None):
     gid = group_ids(groups, ze.shape[0], ze.device, "clip_loss")
     from .autograd import ClipLossFn
     return ClipLossFn.apply(_packed_pair(ze, zf), logit_scale, group, gid)
+
+
+def sigmoid_loss(ze, zf, logit_scale, logit_bias, group=None, groups=None):
+    """pairwise sigmoid loss over the (all-gathered) batch (mm_sigmoid_loss_own_rows) -> (loss, top1 e->f, top1 f->e).
+    ``groups`` as in `clip_loss`: pairs with equal ids are positives of each other."""
+    _need_gpu(ze)
+    gid = group_ids(groups, ze.shape[0], ze.device, "sigmoid_loss")
+    from .autograd import SigmoidLossFn
+    return SigmoidLossFn.apply(_packed_pair(ze, zf), logit_scale, logit_bias, group, gid)
 
 
 def _packed_pair(ze: torch.Tensor, zf: torch.Tensor) -> torch.Tensor:

@@ -361,20 +361,52 @@ def retr_case(nq, ng, d, k, vs_torch=False):
     assert ok
 
 
-def groups_case(step_iters=30):
-    """subject-grouped positives vs the ungrouped path: the loss kernel pair (graph-replayed launches) at (B, Bg, N) =
-    (32, 32, 128) and (32, 256, 128), the rank pass at Nq = Ng = 8192 and 65536 (D = 128), and the C2 graph step
-    (B = 32: 8 subjects x 4 epochs) with and without ids, interleaved rounds"""
+def loss_lines():
+    """the loss launches (graph-replayed) at (B, Bg, N) = (32, 32, 128) and (32, 256, 128): the InfoNCE kernel pair and the
+    pairwise sigmoid loss, each plain and grouped, in the same run"""
     for B, Bg, N in ((32, 32, 128), (32, 256, 128)):
         z = torch.nn.functional.normalize(torch.randn(Bg, 2 * N, device="cuda"), dim=1).contiguous()
         gid = (torch.arange(Bg, device="cuda", dtype=torch.int32) // 4).contiguous()
         ls = torch.full((1,), math.log(1 / 0.07), device="cuda")
-        scal, dz = torch.empty(4, device="cuda"), torch.empty(B, 2 * N, device="cuda")
+        scal, dz = torch.empty(5, device="cuda"), torch.empty(B, 2 * N, device="cuda")
         ws_u = torch.empty(ops.clip_loss_ws_floats(B, Bg), device="cuda")
         ws_g = torch.empty(ops.clip_loss_ws_floats(B, Bg, grouped=True), device="cuda")
         tu = graph_time(lambda: _hip.call("mm_clip_loss_own_rows", z, ls, scal, dz, ws_u, B, Bg, N, 0))
         tg = graph_time(lambda: _hip.call("mm_clip_loss_own_rows_grouped", z, gid, ls, scal, dz, ws_g, B, Bg, N, 0))
         print(f"clip loss B={B} Bg={Bg} N={N}: ungrouped {tu:7.2f} us  grouped {tg:7.2f} us  (+{tg - tu:5.2f} us)")
+        lsig, lb = torch.full((1,), math.log(10.0), device="cuda"), torch.full((1,), -10.0, device="cuda")
+        ws_s = torch.empty(ops.sigmoid_loss_ws_floats(B, Bg), device="cuda")
+        su = graph_time(lambda: _hip.call("mm_sigmoid_loss_own_rows", z, None, lsig, lb, scal, dz, ws_s, B, Bg, N, 0))
+        sg = graph_time(lambda: _hip.call("mm_sigmoid_loss_own_rows", z, gid, lsig, lb, scal, dz, ws_s, B, Bg, N, 0))
+        print(f"sigmoid loss B={B} Bg={Bg} N={N}: ungrouped {su:7.2f} us  grouped {sg:7.2f} us  "
+              f"({su - tu:+5.2f} / {sg - tg:+5.2f} us vs clip loss)")
+
+
+def sigmoid_case(step_iters=30):
+    """the pairwise sigmoid loss vs InfoNCE: the loss launches (`loss_lines`) and the C2 graph step (B = 32) with each
+    loss, interleaved rounds"""
+    loss_lines()
+    from multimodal_eeg_fmri_amd.bridge_trainer import BridgeTrainer, synthetic_pairs
+    eeg, fmri = synthetic_pairs(32, 64, 1024, (32, 32, 32))
+    trs = []
+    for loss in ("infonce", "sigmoid"):
+        ops.set_seed_epoch(None)
+        torch.manual_seed(0)
+        tr = BridgeTrainer(eeg_channels=64, dropout=0.3, loss=loss).train()
+        tr.train_step(eeg, fmri)
+        trs.append(tr)
+    times = ([], [])
+    for _ in range(5):
+        for i, tr in enumerate(trs):
+            times[i].append(timeit(lambda: tr.train_step(eeg, fmri), iters=step_iters, rounds=1))
+    ti, ts = statistics.median(times[0]), statistics.median(times[1])
+    print(f"C2 graph step B=32: infonce {ti:7.1f} us  sigmoid {ts:7.1f} us  ({100 * (ts / ti - 1):+.2f} %)")
+
+
+def groups_case(step_iters=30):
+    """subject-grouped positives vs the ungrouped path: the loss launches (`loss_lines`), the rank pass at Nq = Ng = 8192 and
+    65536 (D = 128), and the C2 graph step (B = 32: 8 subjects x 4 epochs) with and without ids, interleaved rounds"""
+    loss_lines()
     for n in (8192, 65536):
         q = torch.nn.functional.normalize(torch.randn(n, 128, device="cuda"), dim=1).contiguous()
         g = torch.nn.functional.normalize(torch.randn(n, 128, device="cuda"), dim=1).contiguous()
@@ -646,6 +678,9 @@ def main():
         return
     if flt == "groups":
         groups_case()
+        return
+    if flt == "sigmoid":
+        sigmoid_case()
         return
     if flt == "retr":
         retr_case(16384, 16384, 128, 10, vs_torch=True)
