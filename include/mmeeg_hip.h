@@ -289,6 +289,21 @@ int mm_linear_dgrad_ln_bwd_gemm2(const void* dy, const void* w, int M, int K, co
                                  const float* gamma, const float* dres, float* dx, void* dx_bf16, float* dgb_repl,
                                  float drop_p, uint32_t seed, const uint32_t* seed_epoch, const void* w2, void* do_bf16,
                                  int dres_rows_per_sample, hipStream_t stream);
+/* The row-wise backward between a TemporalTransformerBlock's output and its attention backward (enhanced_models_v4.py:99-107),
+ * one launch: linear2's data gradient dz_bf16 (M, n1) = (dy2 @ w2d) * act1'(z_bf16) * dropout_mask(drop1_p, seed1) (w2d =
+ * linear2's data-gradient weight image, n1 rows of 128; dy2 (M, 128) bf16 carries linear2's own dropout mask), then, on the dz
+ * rows while they are still in the workgroup, mm_linear_dgrad_ln_bwd_gemm2: linear1's data gradient (w1d = its data-gradient
+ * image, 128 rows of n1), norm2's backward (x1, stat2, gamma2, dres with dres_rows_per_sample -> dx1 fp32, dyo_bf16 masked
+ * with (drop_p, seed), dgb_repl accumulated) and the out-projection's data gradient do_bf16 = dyo_bf16 @ wo_d.
+ * dz_bf16 is written as well: linear1's weight gradient reads it.  M % 32 == 0, n1 % 128 == 0, n1 <= 512 (LDS: two
+ * workgroups per CU), M * n1 < 2^32.  Every output (dz_bf16, dx1, dyo_bf16, the dgb_repl accumulator words, do_bf16) is
+ * bit-identical to mm_conv1d_fwd(dy2, w2d, 1, M, 128, n1, 1, 0, ..., out_bf16 = dz_bf16, drop1_p, seed1, seed_epoch,
+ * gradz = z_bf16, gradz_act = act1) followed by mm_linear_dgrad_ln_bwd_gemm2(dz_bf16, w1d, M, n1, x1, stat2, gamma2, dres,
+ * dx1, dyo_bf16, dgb_repl, drop_p, seed, seed_epoch, wo_d, do_bf16, dres_rows_per_sample). */
+int mm_ffn_rows_bwd(const void* dy2, const void* w2d, int M, int n1, const void* z_bf16, int act1, float drop1_p, uint32_t seed1,
+                    void* dz_bf16, const void* w1d, const float* x1, const float* stat2, const float* gamma2, const float* dres,
+                    int dres_rows_per_sample, float* dx1, void* dyo_bf16, float* dgb_repl, float drop_p, uint32_t seed,
+                    const uint32_t* seed_epoch, const void* wo_d, void* do_bf16, hipStream_t stream);
 /* mm_linear_dgrad_ln_bwd for the FIRST transformer block of EnhancedERPEncoder, whose LayerNorm input is the last conv
  * block's output (enhanced_models_v4.py:143-147: conv_layers[-1] -> pos_encoder -> transformer_layers[0].norm1): the rows dx
  * (fp32) are that block's d(out), so its BatchNorm-backward reduce pass (mm_bn_act_bwd_reduce(y_below, out4_below, NULL, dx,

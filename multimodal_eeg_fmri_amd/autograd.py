@@ -253,6 +253,7 @@ def linear_bwd(bag: GradBag, dy: torch.Tensor, x: torch.Tensor, weight, bias, *,
 _NO_BCAST = bool(os.environ.get("MM_NO_BCAST"))     # A/B knob: the voxel head's gradient as a full (B, V, N) tensor
 _NO_GEMM2 = bool(os.environ.get("MM_NO_GEMM2"))     # A/B knob: the out-projection's data gradient as its own launch
 _NO_BNRED = bool(os.environ.get("MM_NO_BNRED"))     # A/B knob: the BatchNorm-backward reduce as its own launch
+_NO_FFN_ROWS_BWD = bool(os.environ.get("MM_NO_FFN_ROWS_BWD"))   # A/B knob: the FFN-2 data gradient as its own launch
 
 
 def _bn_bwd_args(s: dict, y):
@@ -355,6 +356,20 @@ def _linear_ln_bwd(bag, dy, h, lin, wb, x, stat, ln, dres, dx, dx_bf16, dgb, dro
     _hip.call("mm_layernorm_bwd", dh, None, x, stat, ln.weight, dres, dx, dx_bf16, dgb, M, D, drop_p, seed, ops.EP())
 
 
+def ffn_rows_bwd_fused(blocks) -> bool:
+    """do all these saved transformer blocks take mm_ffn_rows_bwd (width 128, 32-row groups, a 128 x 128 out-projection
+    image, an FFN width that is a multiple of 128 up to 512)?  A trainer balances its two streams by it."""
+    if not blocks or _NO_GEMM2 or _NO_FFN_ROWS_BWD:
+        return False
+    for s in blocks:
+        M, D = s["x1"].shape
+        n1 = s["z"].shape[-1]
+        _, _, ci, co = ops.weights.get(s["blk"].self_attn.out_proj.weight, True)
+        if not (D == 128 and M % 32 == 0 and ci == 128 and co == 128 and n1 % 128 == 0 and n1 <= 512):
+            return False
+    return True
+
+
 def transformer_block_bwd(bag: GradBag, s: dict, dx2: torch.Tensor, dy2=None, emit_for=None, bn_below=None):
     """dx2 fp32 (M, D) -> (dx0 fp32 (M, D), bf16(dx0 * mask) or None).
 
@@ -383,7 +398,6 @@ def transformer_block_bwd(bag: GradBag, s: dict, dx2: torch.Tensor, dy2=None, em
     # FFN second linear:  x2 = x1 + drop(g W2^T + b2);  g = drop(act(z))
     if dy2 is None:
         dy2 = _mask_cast(g_f32=dx2, drop_p=p, seed=s3)
-    dz = linear_bwd(bag, dy2, s["g"], blk.linear2.weight, blk.linear2.bias, below=(s["z"], blk._act, p, s2))
     dx1 = _empty((M, D), _F32, dx2)
     dyo = _empty((M, D), _BF, dx2)                      # bf16(dx1 * mask1): out-proj backward operand
     dgb = _zeros((REPL, 2, D), dx2)
@@ -395,8 +409,25 @@ def transformer_block_bwd(bag: GradBag, s: dict, dx2: torch.Tensor, dy2=None, em
         _, wd_o, cinp_o, coutp_o = ops.weights.get(at.out_proj.weight, True)
         if cinp_o == 128 and coutp_o == 128:
             g2 = (wd_o, holder)
-    _linear_ln_bwd(bag, dz, s["h2"], blk.linear1, None, s["x1"], s["st2"], blk.norm2, dx2, dx1, dyo, dgb,
-                   float(p), int(s1), gemm2=g2, res_rows=res_rows)
+    n1 = s["z"].shape[-1]
+    if g2 is not None and ffn_rows_bwd_fused([s]):
+        # ... and with an FFN width that fits the workgroup's LDS the FFN-2 data gradient heads the same launch: the dz rows
+        # feed the FFN-1 data gradient before they leave the workgroup (mm_ffn_rows_bwd); the three weight gradients as below
+        _, wd2, cinp2, coutp2 = ops.weights.get(blk.linear2.weight, True)
+        _, wd1, cinp1, coutp1 = ops.weights.get(blk.linear1.weight, True)
+        if (cinp2, coutp2, cinp1, coutp1) != (n1, D, D, n1):
+            raise _hip.HipLibraryError(f"transformer_block_bwd: FFN weight images {cinp2} x {coutp2}, {cinp1} x {coutp1} != width {D}, hidden {n1}")
+        linear_bwd(bag, dy2, s["g"], blk.linear2.weight, blk.linear2.bias, need_dx=False)
+        dz = _empty((M, n1), _BF, dx2)
+        do = _empty((M, D), _BF, dx2)
+        _hip.call("mm_ffn_rows_bwd", dy2, wd2, M, n1, s["z"], ACT[blk._act], float(p), int(s2), dz, wd1, s["x1"], s["st2"],
+                  blk.norm2.weight, dx2, int(res_rows), dx1, dyo, dgb, float(p), int(s1), ops.EP(), wd_o, do)
+        linear_bwd(bag, dz, s["h2"], blk.linear1.weight, blk.linear1.bias, need_dx=False)
+        holder.append(do)
+    else:
+        dz = linear_bwd(bag, dy2, s["g"], blk.linear2.weight, blk.linear2.bias, below=(s["z"], blk._act, p, s2))
+        _linear_ln_bwd(bag, dz, s["h2"], blk.linear1, None, s["x1"], s["st2"], blk.norm2, dx2, dx1, dyo, dgb,
+                       float(p), int(s1), gemm2=g2, res_rows=res_rows)
     _ln_param_grads(bag, blk.norm2, dgb, D)
     if holder:
         do = holder[0]

@@ -32,7 +32,8 @@ import torch
 import torch.nn as nn
 
 from . import _hip, dp, ops
-from .autograd import GradBag, contrastive_embed_bwd, deferred, erp_encoder_bwd, power_encoder_bwd, volume_encoder_bwd
+from .autograd import (GradBag, contrastive_embed_bwd, deferred, erp_encoder_bwd, ffn_rows_bwd_fused, power_encoder_bwd,
+                       volume_encoder_bwd)
 from .bridge_checkpoint import TrainerCheckpointMixin
 from .bridge_utils import EEGfMRIContrastiveBridge, retrieval_metrics
 from .enhanced_models_v4 import EnhancedERPEncoder
@@ -330,8 +331,11 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
                 bag.defer_conv_wgrads = False
             # MM_CONV_WGRADS_HANDED: 1 = block 2's only (default: block 3's weight gradient stays on the chain), 2 = blocks 3
             # and 2 (round 2 / early round 3, when the chain was the later stream), 0 = none.  Which stream ends later
-            # decides: 0.773-0.776 / 0.782-0.799 / 0.789-0.793 ms per step for 1 / 2 / 0 (profiles/r03_second_half_ab.txt)
-            handed_convs = int(os.environ.get("MM_CONV_WGRADS_HANDED", "1")) if hand else 0
+            # decides: 0.773-0.776 / 0.782-0.799 / 0.789-0.793 ms per step for 1 / 2 / 0 (profiles/r03_second_half_ab.txt).
+            # With the blocks' row-wise backward in one launch (mm_ffn_rows_bwd) the chain is ~40 us shorter and the side
+            # stream ends last: the default is then 0 (0.735-0.738 against 0.751-0.758 ms for 1, profiles/ffn_rows_bwd_ab.txt)
+            fused_rows = self._eeg_kind == "erp" and ffn_rows_bwd_fused(sv_e.get("blocks"))
+            handed_convs = int(os.environ.get("MM_CONV_WGRADS_HANDED", "0" if fused_rows else "1")) if hand else 0
             bag.defer_conv_wgrads = handed_convs >= 2
 
             def conv3_done():

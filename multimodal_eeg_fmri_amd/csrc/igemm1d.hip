@@ -804,6 +804,133 @@ __global__ __launch_bounds__(256, 2) void ffn_rows_fwd_kernel(FfnRowsArgs fa) {
     }
 }
 
+// a finished 128-column group of ffn_rows_bwd_kernel's dz tile leaves as 16-byte stores, 16 lanes to a 256-byte row segment
+__device__ __forceinline__ void store_dz_group(bf16* dz, const bf16* Gs, int GS, int t0, int n1, int j, int srow, int scol) {
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+        const int row = q * 16 + srow;
+        *reinterpret_cast<uint4*>(dz + (size_t)(t0 + row) * n1 + 128 * j + scol) = *reinterpret_cast<const uint4*>(Gs + row * GS + 128 * j + scol);
+    }
+}
+
+// The backward of those rows, one launch: the second FFN Linear's data gradient (dy2 x W2d, * act'(z) * the hidden
+// dropout's mask -> dz) with the whole 32 x n1 tile KEPT in LDS (and stored: linear1's weight gradient reads it), the first
+// FFN Linear's data gradient on that tile (W1d's fragments from its L2-resident image one 128-chunk ahead, k ascending in
+// 16-steps into one accumulator: the bits of the stand-alone launch's 128-chunks), then norm2's backward and the
+// out-projection's data gradient exactly as conv1d_fwd_kernel<32, 128, 1, 4, 128, ..., 1> runs them behind that GEMM.
+// g = the FFN-2 data gradient's epilogue arguments (gradz, its activation, dropout, out_bf16 = dz), e = the second launch's.
+struct FfnRowsBwdArgs { const bf16* dy2; const bf16* w2d; const bf16* w1d; int M, n1; EpiArgs g; EpiArgs e; };
+// SPEC: the training step's epilogue combination compiled in (GELU', both dropouts, skip gradient, fp32 rows)
+template <bool SPEC>
+__global__ __launch_bounds__(256, 2) void ffn_rows_bwd_kernel(FfnRowsBwdArgs fa) {
+#pragma clang fp contract(off)
+    constexpr int BM = 32, BN = 128, LDC = BN + 4;
+    constexpr unsigned F_LN = SPEC ? (EF_LNBWD | EF_RES | EF_F32 | EF_BF16 | EF_DROP | EF_GEMM2) : EF_ANY;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int tid = threadIdx.x, lane = tid & 63, wn = tid >> 6, lr = lane & 31, lh = lane >> 5;
+    const int t0 = blockIdx.x * BM;
+    const int n1 = fa.n1, GS = n1 + KPAD, ng = n1 / 128;
+    float* Cs = reinterpret_cast<float*>(smem);
+    float* sstat = Cs + BM * LDC;
+    bf16* zs = reinterpret_cast<bf16*>(smem);          // two 32 x A2S staging tiles of z (the C tile is not live yet)
+    bf16* a2 = reinterpret_cast<bf16*>(smem + CT32);   // dy2's rows, later norm2's masked d(input) rows
+    bf16* Gs = a2 + 32 * A2S;                          // [32][n1 + KPAD] dz tile
+    const EpiArgs& g = fa.g;
+    const int act = SPEC ? (int)MM_ACT_GELU : g.gradz_act;
+    const bool drop = SPEC ? true : g.drop_thresh != 0;
+    const uint32_t dseed = drop ? mm_eff_seed(g.drop_seed, g.drop_epoch) : 0u;
+    // 16-byte row segments: thread -> rows srow and srow + 16, columns scol .. scol + 7 of a 128-column group
+    const int srow = tid >> 4, scol = (tid & 15) * 8;
+    bf16x8 zreg[2];
+    {
+        uint4 va[2];
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            va[q] = *reinterpret_cast<const uint4*>(fa.dy2 + (size_t)(t0 + q * 16 + srow) * 128 + scol);
+            zreg[q] = *reinterpret_cast<const bf16x8*>(g.gradz + (size_t)(t0 + q * 16 + srow) * n1 + scol);
+        }
+#pragma unroll
+        for (int q = 0; q < 2; ++q) *reinterpret_cast<uint4*>(a2 + (q * 16 + srow) * A2S + scol) = va[q];
+    }
+    bf16x8 bnx[8];
+    {
+        const bf16* wlane = fa.w2d + (size_t)(32 * wn + lr) * 128 + lh * 8;
+#pragma unroll
+        for (int ks = 0; ks < 8; ++ks) bnx[ks] = *reinterpret_cast<const bf16x8*>(wlane + ks * 16);
+    }
+    __syncthreads();
+    {
+        bf16x8 af[8];
+#pragma unroll
+        for (int ks = 0; ks < 8; ++ks) af[ks] = *reinterpret_cast<const bf16x8*>(a2 + lr * A2S + ks * 16 + lh * 8);
+        const bf16* wlane = fa.w2d + (size_t)(32 * wn + lr) * 128 + lh * 8;
+        for (int j = 0; j < ng; ++j) {
+            bf16x8 bfr[8];
+#pragma unroll
+            for (int ks = 0; ks < 8; ++ks) bfr[ks] = bnx[ks];
+            bf16* zt = zs + (j & 1) * (32 * A2S);      // last read two groups ago: a barrier lies between
+#pragma unroll
+            for (int q = 0; q < 2; ++q) *reinterpret_cast<bf16x8*>(zt + (q * 16 + srow) * A2S + scol) = zreg[q];
+            if (j + 1 < ng) {                          // the next group's weight fragments and z rows fly during this group's MFMAs
+                const bf16* wrow = wlane + (size_t)(j + 1) * 128 * 128;
+#pragma unroll
+                for (int ks = 0; ks < 8; ++ks) bnx[ks] = *reinterpret_cast<const bf16x8*>(wrow + ks * 16);
+#pragma unroll
+                for (int q = 0; q < 2; ++q)
+                    zreg[q] = *reinterpret_cast<const bf16x8*>(g.gradz + (size_t)(t0 + q * 16 + srow) * n1 + 128 * (j + 1) + scol);
+            }
+            f32x16 c2;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) c2[r] = 0.f;
+#pragma unroll
+            for (int ks = 0; ks < 8; ++ks) c2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[ks], bfr[ks], c2, 0, 0, 0);
+            __syncthreads();                           // z's tile is staged; the previous group's columns of the dz tile are complete
+            if (j > 0) store_dz_group(g.out_bf16, Gs, GS, t0, n1, j - 1, srow, scol);
+            // scale 1, shift 0 -> act'(z) -> dropout, the arithmetic of epilogue_rows (FFN-2 data gradient)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int row = (r & 3) + 8 * (r >> 2) + 4 * lh;
+                const int col = 128 * j + 32 * wn + lr;
+                const size_t idx = (size_t)(t0 + row) * n1 + col;
+                float v = __builtin_fmaf(c2[r], 1.f, 0.f);
+                v *= act_grad((float)zt[row * A2S + 32 * wn + lr], act);
+                if (drop) v = __builtin_fmaf(v, dropout_scale(dseed, (uint32_t)idx, g.drop_thresh, g.drop_inv_keep), 0.f);
+                else v += 0.f;
+                Gs[row * GS + col] = (bf16)fmaxf(-INFINITY, v);
+            }
+        }
+    }
+    __syncthreads();                                   // the dz tile is complete; z's staging tiles are dead
+    store_dz_group(g.out_bf16, Gs, GS, t0, n1, ng - 1, srow, scol);
+    f32x16 acc;
+    {
+        const bf16* wlane = fa.w1d + (size_t)(32 * wn + lr) * n1 + lh * 8;
+#pragma unroll
+        for (int ks = 0; ks < 8; ++ks) bnx[ks] = *reinterpret_cast<const bf16x8*>(wlane + ks * 16);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+        for (int c0 = 0; c0 < n1; c0 += 128) {
+            bf16x8 bfr[8];
+#pragma unroll
+            for (int ks = 0; ks < 8; ++ks) bfr[ks] = bnx[ks];
+            if (c0 + 128 < n1)
+#pragma unroll
+                for (int ks = 0; ks < 8; ++ks) bnx[ks] = *reinterpret_cast<const bf16x8*>(wlane + c0 + 128 + ks * 16);
+#pragma unroll
+            for (int ks = 0; ks < 8; ++ks) {
+                const bf16x8 af = *reinterpret_cast<const bf16x8*>(Gs + lr * GS + c0 + ks * 16 + lh * 8);
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, bfr[ks], acc, 0, 0, 0);
+            }
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < 16; ++r) Cs[((r & 3) + 8 * (r >> 2) + 4 * lh) * LDC + wn * 32 + lr] = acc[r];
+    __syncthreads();
+    epilogue_ln_bwd<BM, BN, F_LN>(Cs, fa.e, tid, 0, t0, fa.M, sstat, a2);
+    __syncthreads();                                   // the C tile is dead: it stages the outputs
+    second_gemm<F_LN, false>(a2, fa.e, (size_t)t0, tid, wn, lr, lh, reinterpret_cast<bf16*>(smem), a2 + 32 * A2S);
+}
+
 // second half of a split-K launch: the slices are added in slice order (same bits every run) into the C tile, then the
 // ordinary epilogue runs on it (generic form: every step behind its run-time test, bit-equal to the compiled-in forms)
 template <int BM, int BN>
@@ -1746,7 +1873,7 @@ int mm_ffn_rows_fwd(const void* x, const void* w, int M, int K, const float* bia
 static int linear_dgrad_ln_bwd(const void* dy, const void* w, int M, int K, const float* x, const float* stat,
                                const float* gamma, const float* dres, float* dx, void* dx_bf16, float* dgb_repl,
                                float drop_p, uint32_t seed, const uint32_t* seed_epoch, const BnRed* bn, hipStream_t st,
-                               const void* w2 = nullptr, void* out2 = nullptr, int res_rows = 0) {
+                               const void* w2 = nullptr, void* out2 = nullptr, int res_rows = 0, ConvArgs* args_only = nullptr) {
     MM_REQUIRE(dy && w && x && stat && gamma && (dx || dx_bf16), "linear_dgrad_ln_bwd: null");
     MM_REQUIRE(!w2 || (out2 && dx_bf16), "linear_dgrad_ln_bwd: the second GEMM needs the bf16 rows and an output");
     MM_REQUIRE(M > 0 && M % 32 == 0 && K > 0 && K % 16 == 0, "linear_dgrad_ln_bwd: M=%d (multiple of 32) K=%d (multiple of 16)", M, K);
@@ -1762,6 +1889,7 @@ static int linear_dgrad_ln_bwd(const void* dy, const void* w, int M, int K, cons
     a.e.w2 = (const bf16*)w2; a.e.out2 = (bf16*)out2;
     MM_REQUIRE(res_rows >= 0 && (!res_rows || (dres && M % res_rows == 0 && (size_t)M < (1ull << 32))), "linear_dgrad_ln_bwd: res_rows=%d", res_rows);
     a.e.res_rows = res_rows;
+    if (args_only) { *args_only = a; return 0; }           // mm_ffn_rows_bwd launches it behind the FFN-2 data gradient
     return launch_fwd_32x128(a, st);
 }
 
@@ -1784,6 +1912,42 @@ int mm_linear_dgrad_ln_bwd_gemm2(const void* dy, const void* w, int M, int K, co
     MM_REQUIRE(w2 && do_bf16 && dx_bf16, "linear_dgrad_ln_bwd_gemm2: null");
     return linear_dgrad_ln_bwd(dy, w, M, K, x, stat, gamma, dres, dx, dx_bf16, dgb_repl, drop_p, seed, seed_epoch, nullptr, st,
                                w2, do_bf16, dres_rows_per_sample);
+}
+
+// The FFN-2 data gradient (-> dz) followed, inside the launch, by mm_linear_dgrad_ln_bwd_gemm2 on the dz rows, which never
+// leave the workgroup between the two GEMMs (dz_bf16 is still written: linear1's weight gradient reads it).  See
+// include/mmeeg_hip.h.
+int mm_ffn_rows_bwd(const void* dy2, const void* w2d, int M, int n1, const void* z_bf16, int act1, float drop1_p, uint32_t seed1,
+                    void* dz_bf16, const void* w1d, const float* x1, const float* stat2, const float* gamma2, const float* dres,
+                    int dres_rows_per_sample, float* dx1, void* dyo_bf16, float* dgb_repl, float drop_p, uint32_t seed,
+                    const uint32_t* seed_epoch, const void* wo_d, void* do_bf16, hipStream_t st) {
+    MM_REQUIRE(dy2 && w2d && z_bf16 && dz_bf16 && w1d && x1 && stat2 && gamma2 && dx1 && dyo_bf16 && wo_d && do_bf16, "ffn_rows_bwd: null");
+    MM_REQUIRE(M > 0 && M % 32 == 0, "ffn_rows_bwd: M=%d must be a multiple of 32", M);
+    MM_REQUIRE(n1 > 0 && n1 % 128 == 0 && n1 <= 512, "ffn_rows_bwd: n1=%d must be a multiple of 128 up to 512", n1);
+    MM_REQUIRE(act1 >= MM_ACT_NONE && act1 <= MM_ACT_SIGMOID, "ffn_rows_bwd: act1=%d", act1);
+    MM_REQUIRE(drop1_p >= 0.f && drop1_p < 1.f && drop_p >= 0.f && drop_p < 1.f, "ffn_rows_bwd: drop_p");
+    MM_REQUIRE((size_t)M * n1 < (1ull << 32), "ffn_rows_bwd: 32-bit dropout indices");
+    MM_REQUIRE(dres_rows_per_sample >= 0 && (!dres_rows_per_sample || (dres && M % dres_rows_per_sample == 0)),
+               "ffn_rows_bwd: dres_rows_per_sample=%d must divide M=%d", dres_rows_per_sample, M);
+    ConvArgs c;
+    int rc = conv1d_fwd_args(c, dy2, w2d, 1, M, 128, n1, 1, 0, nullptr, nullptr, 0, nullptr, nullptr, 1, nullptr, nullptr, dz_bf16,
+                             nullptr, drop1_p, seed1, seed_epoch, z_bf16, act1);
+    if (rc) return rc;
+    ConvArgs l;
+    rc = linear_dgrad_ln_bwd(dz_bf16, w1d, M, n1, x1, stat2, gamma2, dres, dx1, dyo_bf16, dgb_repl, drop_p, seed, seed_epoch, nullptr,
+                             st, wo_d, do_bf16, dres_rows_per_sample, &l);
+    if (rc) return rc;
+    FfnRowsBwdArgs fa;
+    fa.dy2 = (const bf16*)dy2; fa.w2d = (const bf16*)w2d; fa.w1d = (const bf16*)w1d; fa.M = M; fa.n1 = n1;
+    fa.g = c.e; fa.e = l.e;
+    const size_t need = CT32 + A2B + (size_t)32 * (n1 + KPAD) * sizeof(bf16);
+    MM_REQUIRE(need <= 64 * 1024, "ffn_rows_bwd: n1=%d needs %zu B of LDS (two workgroups per CU: 64 KiB each)", n1, need);
+    // the combination both replaced launches compile in: GELU' and the hidden dropout; skip gradient, fp32 rows, out_proj's dropout
+    const bool spec = !getenv("MM_EPI_GENERIC") && act1 == MM_ACT_GELU && fa.g.drop_thresh && dres && fa.e.drop_thresh;
+    const dim3 grid(M / 32);
+    if (spec) hipLaunchKernelGGL((ffn_rows_bwd_kernel<true>), grid, dim3(256), need, st, fa);
+    else hipLaunchKernelGGL((ffn_rows_bwd_kernel<false>), grid, dim3(256), need, st, fa);
+    return mm_check_launch("ffn_rows_bwd");
 }
 
 // mm_linear_dgrad_ln_bwd whose rows dx are the fp32 d(out) of a 128-channel, un-pooled conv block (Conv1d -> BatchNorm1d

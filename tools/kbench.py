@@ -664,8 +664,56 @@ def gat_case(B=32, N=64, H=4, C=32, dense=True):
     print(f"{tag} encoder eval forward: whole batch {whole:8.1f} us   one sample per call x {B} {loop:8.1f} us   ({loop / whole:.1f} x)")
 
 
+def ffnbwd_case(M=16384, n1=512, p=0.3):
+    """a transformer block's row-wise backward at the C2 shape: the two launches (FFN-2 data gradient, then FFN-1 data
+    gradient + norm2 backward + out-projection data gradient) against mm_ffn_rows_bwd, and the traffic each form moves"""
+    g = torch.Generator().manual_seed(5)
+
+    def img(cout, cin):                      # data-gradient weight image of a Linear(cin -> cout): cin rows of cout
+        wd = torch.empty(cin, 1, cout, dtype=BF, device="cuda")
+        wf = torch.empty(cout, 1, cin, dtype=BF, device="cuda")
+        w = (torch.randn(cout, cin, 1, generator=g) / math.sqrt(cin)).cuda()
+        _hip.call("mm_prep_conv_weight", w, wf, wd, cout, cin, 1, cin, cout)
+        return wd
+    w2d, w1d, wod = img(128, n1), img(n1, 128), img(128, 128)
+    dy2 = (torch.randn(M, 128, generator=g) * 0.1).cuda().to(BF)
+    z = torch.randn(M, n1, generator=g).cuda().to(BF)
+    x1 = torch.randn(M, 128, generator=g).cuda()
+    stat = torch.stack([x1.mean(1), (x1.var(1, unbiased=False) + 1e-5).rsqrt()], 1).contiguous()
+    gam = (0.5 + torch.rand(128, generator=g)).cuda()
+    dres = (torch.randn(M, 128, generator=g) * 0.1).cuda()
+    dz = torch.empty(M, n1, dtype=BF, device="cuda")
+    dx1 = torch.empty(M, 128, device="cuda")
+    dyo, do = torch.empty(M, 128, dtype=BF, device="cuda"), torch.empty(M, 128, dtype=BF, device="cuda")
+    dgb = torch.zeros(32, 2, 128, device="cuda")
+
+    def first():
+        _hip.call("mm_conv1d_fwd", dy2, w2d, 1, M, 128, n1, 1, 0, None, None, 0, None, None, 1, None, None, dz, None, p, 92, None,
+                  z, ops.ACT["gelu"])
+
+    def second():
+        _hip.call("mm_linear_dgrad_ln_bwd_gemm2", dz, w1d, M, n1, x1, stat, gam, dres, dx1, dyo, dgb, p, 91, None, wod, do, 0)
+
+    def chain():
+        first()
+        second()
+
+    def fused():
+        _hip.call("mm_ffn_rows_bwd", dy2, w2d, M, n1, z, ops.ACT["gelu"], p, 92, dz, w1d, x1, stat, gam, dres, 0, dx1, dyo, dgb,
+                  p, 91, None, wod, do)
+    t1, t2, tc, tf = timeit(first), timeit(second), timeit(chain), timeit(fused)
+    rows = M * 128
+    mb_f = (2 * rows + 2 * 2 * M * n1 + 3 * 4 * rows + 2 * 2 * rows) / 1e6          # dy2, z + dz, x1 + dres + dx1, dyo + do
+    mb_c = mb_f + 2 * M * n1 / 1e6                                                   # + the dz read-back
+    print(f"ffnbwd M={M} n1={n1} p={p}: FFN-2 dgrad {t1:6.1f} us + FFN-1 dgrad/norm2/out-proj {t2:6.1f} us; back to back {tc:6.1f} us "
+          f"({mb_c / tc:5.2f} TB/s of {mb_c:.1f} MB); fused {tf:6.1f} us ({mb_f / tf:5.2f} TB/s of {mb_f:.1f} MB)")
+
+
 def main():
     flt = sys.argv[1] if len(sys.argv) > 1 else ""
+    if flt == "ffnbwd":
+        ffnbwd_case()
+        return
     if flt.startswith("gat"):          # gat[:B,N,H,C]
         dims = [int(d) for d in flt.split(":", 1)[1].split(",")] if ":" in flt and flt.split(":", 1)[1] else []
         gat_case(*dims)
