@@ -37,7 +37,7 @@
 //   16-byte loads where the sample rows allow them): B = 32 samples of 64 x 1024 are 512 workgroups, two per CU - one
 //   workgroup per sample would stream its 256 KB through a single CU.  Workgroup (b, 0) also draws the sample's two
 //   decisions and its channel mask.
-// mm_stage_inputs_aug: stage_inputs_kernel (igemm1d.hip) with the augmentation between the load and the LDS transpose
+// mm_stage_inputs_aug: stage_inputs_kernel (igemm1d_pack.hip) with the augmentation between the load and the LDS transpose
 //   tile.  Every tile workgroup adds its sample's partials in chunk order (<= 64 pairs of doubles, the same bits in
 //   every workgroup) for std_b; the workgroup of the sample's first tile stores the scale and std_b into the plan.  A
 //   thread handles the two elements of a Box-Muller pair: one log, one sqrt, one sincos per two elements.

@@ -152,7 +152,7 @@ inline DropH mm_drop(float p) {
 }
 
 // BatchNorm + activation [+ pool 2] [+ dropout] backward, element level (elementwise.hip's two passes and the reduce pass
-// fused behind a data-gradient GEMM, igemm1d.hip): dz for the (up to) two inputs of one pooled output element.
+// fused behind a data-gradient GEMM, igemm1d.h): dz for the (up to) two inputs of one pooled output element.
 // Args carries act, pool, drop_first, thresh, seed (already mm_eff_seed'ed), inv_keep.  ACT >= 0 / POOL > 0: compiled for that activation /
 // pool size (the per-element switch and the two-way pool logic of the generic form made these passes VALU-bound)
 template <int ACT, int POOL, class Args>

@@ -130,7 +130,7 @@ __global__ void bn_act_fwd_kernel(BnActArgs a) {
         }
         if (a.ln_out) {
             // (host: N == 128, pool == 1, total a multiple of 32: every 32-lane group runs this together on one row;
-            //  arithmetic as epilogue_rows' fused LayerNorm in igemm1d.hip)
+            //  arithmetic as epilogue_rows' fused LayerNorm in igemm1d.h)
             const float mean = half32_sum((o[0] + o[1]) + (o[2] + o[3])) * (1.f / 128.f);
             const float d0 = o[0] - mean, d1 = o[1] - mean, d2 = o[2] - mean, d3 = o[3] - mean;
             const float rstd = rsqrtf(half32_sum((d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3)) * (1.f / 128.f) + a.ln_eps);

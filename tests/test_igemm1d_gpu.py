@@ -1,4 +1,4 @@
-"""GPU: the 1-D implicit-GEMM family of csrc/igemm1d.hip (every nn.Conv1d and nn.Linear on the HIP path) against plain fp64
+"""GPU: the 1-D implicit-GEMM family of csrc/igemm1d*.hip (every nn.Conv1d and nn.Linear on the HIP path) against plain fp64
 references of the same operation, computed on the CPU from the kernels' own operands: the packed bf16 activations and the
 bf16 weight images that mm_prep_conv_weight returns.
 
