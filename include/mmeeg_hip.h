@@ -507,6 +507,54 @@ int mm_proj_heads_bwd(const float* dz, const float* z, const float* nrm, const f
                       float* db_e, float* dg_e, float* dbe_e, float* dx_f, float* dW_f, float* db_f, float* dg_f,
                       float* dbe_f, int B, int N, float drop_p, uint32_t seed_e, uint32_t seed_f,
                       const uint32_t* seed_epoch, hipStream_t stream);
+/* mm_proj_heads_bwd with one more gradient at the heads' outputs: da [2][B][N] = d loss / d (the post-GELU/dropout
+ * activations a_e, a_f) from a second consumer of those rows (mm_bridge_cls_bwd).  It joins the F.normalize-backward
+ * term before the dropout mask and GELU'.  Same kernel, compiled with the extra load; da = 0 gives mm_proj_heads_bwd's
+ * bits. */
+int mm_proj_heads_bwd_da(const float* dz, const float* da, const float* z, const float* nrm, const float* hn,
+                         const float* z1, const float* stat, const float* x_e, const float* W_e, const float* g_e,
+                         int K_e, const float* x_f, const float* W_f, const float* g_f, int K_f, float* dx_e,
+                         float* dW_e, float* db_e, float* dg_e, float* dbe_e, float* dx_f, float* dW_f, float* db_f,
+                         float* dg_f, float* dbe_f, int B, int N, float drop_p, uint32_t seed_e, uint32_t seed_f,
+                         const uint32_t* seed_epoch, hipStream_t stream);
+/* Classification branch of the bridge (bridge_utils.py:22-114: cross attention of the EEG token over [EEG, fMRI],
+ * LearnedFusionModule, Linear -> LayerNorm -> ReLU -> Dropout -> Linear, class-weighted cross-entropy) on the rows
+ * mm_proj_heads_fwd produced: hn [2][B][N] with its drop_p / seed_e / seed_f (the tokens a_e, a_f are recomputed from
+ * them, not evaluated a second time).  fp32, one workgroup per sample, ONE launch.  N = bridge_dim: a multiple of 32 in
+ * [32, 256]; nhead <= 16 dividing it; 2 <= C <= 16.  Weights in PyTorch layout: in_w [3N][N], out_w [N][N], g0_w [N][2N],
+ * g3_w [2][N], fusion_logits [2], temperature [1], c0_w [N/2][N], ln_g / ln_b [N/2], c4_w [C][N/2].  Dropout sites
+ * (own seeds; element index): attention probabilities (b * nhead + h) * 2 + key, gate hidden b * N + n, classifier
+ * hidden b * (N/2) + n.  Outputs (plain stores): logits [B][C], fusion_w [B][2], attn_w [B][2] (head-averaged,
+ * un-dropped), save = mm_bridge_cls_ws_floats(B, N, 0) floats for the backward.  labels int32 [B] (nullable; a label
+ * outside [0, C) gives its row weight 0 and indexes nothing), class_weight [C] (nullable): loss [4] = {ce = sum_b w[y_b]
+ * (lse_b - logit_b[y_b]) / sum_b w[y_b], rows with argmax == y_b, sum_b w[y_b], ce_weight * ce}, summed in row order by
+ * the workgroup that finishes last (ticket: one int32 word, zero before the first launch, left zero).  Without labels
+ * loss and ticket are not touched. */
+int mm_bridge_cls_fwd(const float* hn, float drop_p, uint32_t seed_e, uint32_t seed_f, const float* in_w,
+                      const float* in_b, const float* out_w, const float* out_b, const float* g0_w, const float* g0_b,
+                      const float* g3_w, const float* g3_b, const float* fusion_logits, const float* temperature,
+                      const float* c0_w, const float* c0_b, const float* ln_g, const float* ln_b, const float* c4_w,
+                      const float* c4_b, const int* labels, const float* class_weight, float ce_weight, float* logits,
+                      float* fusion_w, float* attn_w, float* save, float* loss, int* ticket, int B, int N, int nhead,
+                      int C, float ln_eps, float attn_p, uint32_t seed_attn, float gate_p, uint32_t seed_gate,
+                      float cls_p, uint32_t seed_cls, const uint32_t* seed_epoch, hipStream_t stream);
+/* backward of ce_weight * ce, TWO launches, no float atomics: one call per launch with the same arguments, phase 0
+ * (rows) then phase 1 (weights).  Rows (a workgroup per sample): the gradient at every
+ * Linear's output and the per-row pieces of the LayerNorm / fusion_logits / temperature gradients into grad_rows
+ * (mm_bridge_cls_ws_floats(B, N, 1) floats), da [2][B][N] = the gradient of a_e and a_f (plain stores; the extra input
+ * of mm_proj_heads_bwd_da), and loss_total[0] = loss_in[0] + ce_weight * ce when loss_total is given (loss_in null: 0).
+ * Weights: every d_* target (nullable) gets its sum over the rows, in row order, ADDED by the one thread that owns the
+ * element; in_proj's q rows from a_e, its k / v rows from both tokens. */
+int mm_bridge_cls_bwd(const float* save, const float* logits, const float* loss, const int* labels, float ce_weight,
+                      const float* in_w, const float* out_w, const float* g0_w, const float* g3_w,
+                      const float* fusion_logits, const float* temperature, const float* c0_w, const float* ln_g,
+                      const float* ln_b, const float* c4_w, float* grad_rows, float* da, float* d_in_w, float* d_in_b,
+                      float* d_out_w, float* d_out_b, float* d_g0_w, float* d_g0_b, float* d_g3_w, float* d_g3_b,
+                      float* d_fusion_logits, float* d_temperature, float* d_c0_w, float* d_c0_b, float* d_ln_g,
+                      float* d_ln_b, float* d_c4_w, float* d_c4_b, const float* loss_in, float* loss_total, int phase, int B,
+                      int N, int nhead, int C, float attn_p, uint32_t seed_attn, float gate_p, uint32_t seed_gate, float cls_p,
+                      uint32_t seed_cls, const uint32_t* seed_epoch, hipStream_t stream);
+int mm_bridge_cls_ws_floats(int B, int N, int which, int* floats_host, hipStream_t stream);
 /* batch-pairwise cosine-similarity matrix + symmetric InfoNCE, bit-reproducible (no float atomics).
  * Embeddings are packed rows [ze (N) | zf (N)]: z_all [Bg][2N] = the all-gathered global batch, this rank's
  * pairs at rows [row0, row0+B).  C[r][j] = ze_r . zf_j; e->f = row softmax of exp(logit_scale) C, f->e =

@@ -864,6 +864,44 @@ def contrastive_embed_bwd(bag: GradBag, s: dict, dz: torch.Tensor, need=(True, T
     return dxe, dxf
 
 
+def contrastive_embed_bwd_da(bag: GradBag, s: dict, dz: torch.Tensor, da: torch.Tensor, need=(True, True)):
+    """`contrastive_embed_bwd` with ``da`` (2, B, N), a second gradient at the heads' post-dropout activations (the
+    classification branch's, `bridge_cls_bwd`): mm_proj_heads_bwd_da in place of mm_proj_heads_bwd"""
+    B, N = s["B"], s["N"]
+    br = s["bridge"]
+    (le, lne), (lf, lnf) = br.eeg_proj[:2], br.fmri_proj[:2]
+    xe, xf = s["xe"], s["xf"]
+    dxe = _empty(xe.shape, _F32, dz) if need[0] else None
+    dxf = _empty(xf.shape, _F32, dz) if need[1] else None
+    t = bag.target
+    _hip.call("mm_proj_heads_bwd_da", dz.contiguous(), da, s["z"], s["nrm"], s["hn"], s["z1"], s["stat"],
+              xe, le.weight, lne.weight, xe.shape[1], xf, lf.weight, lnf.weight, xf.shape[1],
+              dxe, t(le.weight), t(le.bias), t(lne.weight), t(lne.bias),
+              dxf, t(lf.weight), t(lf.bias), t(lnf.weight), t(lnf.bias),
+              B, N, float(s["p"]), int(s["seeds"][0]), int(s["seeds"][1]), ops.EP())
+    return dxe, dxf
+
+
+def bridge_cls_bwd(bag: GradBag, s: dict, loss_in=None, loss_total=None) -> torch.Tensor:
+    """backward of ``ce_weight * ce`` through the classification branch (``s``: what `ops.bridge_cls_forward_impl`
+    saved, with labels): mm_bridge_cls_bwd's two launches.  Every parameter gradient is ADDED to its `GradBag` target;
+    -> da (2, B, N), the gradient of the two tokens (`contrastive_embed_bwd_da`).  ``loss_total`` (1,): receives
+    ``loss_in[0] + ce_weight * ce`` (plain store of the rows launch)."""
+    if s["labels"] is None:
+        raise ValueError("bridge_cls_bwd: the forward ran without labels")
+    B, N, H, C = s["B"], s["N"], s["H"], s["C"]
+    ps = ops.bridge_cls_params(s["bridge"])
+    (in_w, in_b, out_w, out_b, g0_w, g0_b, g3_w, g3_b, fl, temp, c0_w, c0_b, ln_g, ln_b, c4_w, c4_b) = ps
+    grad_rows = _empty((_hip.host_int("mm_bridge_cls_ws_floats", B, N, 1),), _F32, s["save"])
+    da = _empty((2, B, N), _F32, s["save"])
+    pa, sa_, pg, sg, pc, sc = s["drops"]
+    for phase in (0, 1):                                     # rows, then weights: one launch each
+        _hip.call("mm_bridge_cls_bwd", s["save"], s["logits"], s["loss"], s["labels"], float(s["ce_weight"]),
+                  in_w, out_w, g0_w, g3_w, fl, temp, c0_w, ln_g, ln_b, c4_w, grad_rows, da,
+                  *[bag.target(p) for p in ps], loss_in, loss_total, phase, B, N, H, C, pa, sa_, pg, sg, pc, sc, ops.EP())
+    return da
+
+
 class ContrastiveEmbedFn(torch.autograd.Function):
     @staticmethod
     def run(bridge, eeg, fmri):

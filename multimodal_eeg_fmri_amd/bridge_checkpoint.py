@@ -10,8 +10,9 @@ The file is the container of the reference's loops and of `FlexibleTrainer.save_
   layer group, so its slices are mapped back to that order); the frozen half of the bridge has no entry;
 * ``bridge_trainer_state``: the optimizer words (step count, lr, ...), the hyperparameters, the EEG branch kind, the
   model's shapes, the head count of every transformer block, the world size, the bucket layout, the dropout stream,
-  the state of `fit`, - only for a trainer with an augmenter - ``augment``: its parameters and the step index, and -
-  only for a trainer of the pairwise sigmoid loss - ``loss`` = ``"sigmoid"`` (absent: InfoNCE).
+  the state of `fit`, - only for a trainer with an augmenter - ``augment``: its parameters and the step index, -
+  only for a trainer of the pairwise sigmoid loss - ``loss`` = ``"sigmoid"`` (absent: InfoNCE), and - only for a trainer
+  built with ``classify=True`` - ``classify`` = ``{ce_weight, num_classes, class_weight}``.
 
 The step itself is untouched: saving and loading are copies, `fit` only calls `train_step` and `embed`.
 
@@ -122,6 +123,14 @@ class TrainerCheckpointMixin:
         self._works = []
         self.capture_mode = None
 
+    def checkpoint_classify(self) -> Optional[dict]:
+        """``bridge_trainer_state["classify"]``: None unless the trainer was built with classify=True"""
+        if not getattr(self, "classify", False):
+            return None
+        cw = self._class_weight
+        return {"ce_weight": float(self.ce_weight), "num_classes": int(self.num_classes),
+                "class_weight": None if cw is None else [float(v) for v in cw.detach().cpu()]}
+
     # ------------------------------------------------------------------ state
     def checkpoint_state(self, epoch: Optional[int] = None, metrics: Optional[dict] = None, scheduler=None) -> dict:
         """the checkpoint container (CPU tensors, dicts, lists and Python scalars: loads with ``weights_only=True``)"""
@@ -145,6 +154,8 @@ class TrainerCheckpointMixin:
             bts["augment"] = dict(self.augment.params(), step=int(self._aug_step))
         if getattr(self, "loss", "infonce") != "infonce":          # (absent for the default loss: the container is unchanged)
             bts["loss"] = self.loss
+        if self.checkpoint_classify() is not None:                 # (absent without classify: the container is unchanged)
+            bts["classify"] = self.checkpoint_classify()
         return {"epoch": epoch, "model_state_dict": {k: _cpu(v) for k, v in self.state_dict().items()},
                 "optimizer_state_dict": {"state": state, "param_groups": [group]},
                 "scheduler_state_dict": scheduler.state_dict() if scheduler is not None else None,
@@ -169,6 +180,17 @@ class TrainerCheckpointMixin:
         loss, theirs_loss = getattr(self, "loss", "infonce"), bts.get("loss", "infonce")
         if loss != theirs_loss:                                    # before the shapes: logit_bias exists under one loss only
             raise ValueError(f"load_checkpoint_state: loss differs: checkpoint {theirs_loss!r}, trainer {loss!r}")
+        mine_cls = self.checkpoint_classify()
+        theirs_cls = bts.get("classify")
+        if (mine_cls is None) != (theirs_cls is None):             # before the shapes and the bucket layout, which differ too
+            raise ValueError(f"load_checkpoint_state: classify differs: the checkpoint was written "
+                             f"{'with' if theirs_cls is not None else 'without'} classify=True, this trainer was built "
+                             f"{'with' if mine_cls is not None else 'without'} it")
+        if mine_cls is not None:
+            for field in ("num_classes", "ce_weight", "class_weight"):
+                if theirs_cls.get(field) != mine_cls[field]:
+                    raise ValueError(f"load_checkpoint_state: classify.{field} differs: checkpoint "
+                                     f"{theirs_cls.get(field)!r}, trainer {mine_cls[field]!r}")
         # a checkpoint written before the head counts were recorded comes from a trainer whose blocks all had 4 heads
         heads = bts.get("heads", [[n, 4] for n, _ in mine["heads"]])
         if heads != mine["heads"]:
@@ -307,6 +329,8 @@ class TrainerCheckpointMixin:
         s0 = ops._seed_state["step"]
         ze, zf = self.embed(val[0], val[1], batch_size)
         metrics = retrieval_metrics(ze, zf, groups=val[2] if len(val) > 2 else None)
+        if len(val) > 3 and val[3] is not None:           # class labels: the reference's evaluate_bridge metrics as well
+            metrics["classification"] = self.evaluate_classification(val[0], val[1], val[3], batch_size)
         assert ops._seed_state["step"] == s0, "validation drew dropout seeds"
         return metrics, monitor_value(metrics, monitor)
 
@@ -322,6 +346,8 @@ class TrainerCheckpointMixin:
         grouped and ungrouped batches, captures the step again).
         Schedule: `CosineAnnealingWarmup(warmup_epochs, epochs, min_lr)` from the trainer's current lr, stepped after each
         epoch's training as the reference does (epoch 1 runs at the base rate, epoch e > 1 at ``_lr_at(e - 1)``).
+        A classify trainer takes (eeg, fmri, groups_or_None, labels) batches; ``val = (eeg, fmri, groups_or_None, labels)``
+        adds ``metrics["classification"]`` (`evaluate_classification`), e.g. ``monitor="classification.Accuracy"``.
         ``val = (eeg, fmri[, groups])``: every ``eval_every`` epochs (and after the last) `embed` + `retrieval_metrics`
         (grouped ranks with ``groups``); the
         monitored value (``monitor_value``; ``mode`` "max" or "min") drives `EarlyStopping(patience, min_delta)` and the

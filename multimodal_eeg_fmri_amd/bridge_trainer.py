@@ -32,8 +32,8 @@ import torch
 import torch.nn as nn
 
 from . import _hip, dp, ops
-from .autograd import (GradBag, contrastive_embed_bwd, deferred, erp_encoder_bwd, ffn_rows_bwd_fused, power_encoder_bwd,
-                       volume_encoder_bwd)
+from .autograd import (GradBag, bridge_cls_bwd, contrastive_embed_bwd, contrastive_embed_bwd_da, deferred, erp_encoder_bwd,
+                       ffn_rows_bwd_fused, power_encoder_bwd, volume_encoder_bwd)
 from .bridge_checkpoint import TrainerCheckpointMixin
 from .bridge_utils import EEGfMRIContrastiveBridge, retrieval_metrics
 from .enhanced_models_v4 import EnhancedERPEncoder
@@ -46,7 +46,8 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
                  bridge_dim: int = 128, dropout: float = 0.3, lr: float = 1e-4,
                  weight_decay: float = 1e-4, grad_clip: float = 1.0, betas=(0.9, 0.999),
                  eps: float = 1e-8, group=None, device="cuda", mode: str = "graph", eeg_encoder: Optional[nn.Module] = None,
-                 num_heads: int = 4, num_layers: int = 2, augment=None, loss: str = "infonce"):
+                 num_heads: int = 4, num_layers: int = 2, augment=None, loss: str = "infonce",
+                 classify: bool = False, ce_weight: float = 1.0, class_weight=None, num_classes: int = 2):
         """``eeg_encoder``: the EEG branch when it is not the default ``EnhancedERPEncoder(eeg_channels, hidden_dim,
         num_layers, num_heads, dropout)`` - an ``EnhancedPowerEncoder`` (enhanced_models_v4.py:196-285) or a
         ``MultiScaleSTFTPowerEncoder`` (BASELINE config #5: raw EEG -> multi-scale STFT power -> a4); it must end in
@@ -57,8 +58,27 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
         this process's rank; `evaluate`, `embed`, `evaluate_retrieval`, `explain` and `forward` never augment.
         ``loss``: "infonce" (default: the symmetric InfoNCE, mm_clip_loss_own_rows*) or "sigmoid" (the pairwise sigmoid
         loss, mm_sigmoid_loss_own_rows: no softmax normaliser, so its signal does not depend on the number of in-batch
-        negatives; one more trained scalar, ``head.logit_bias``)."""
+        negatives; one more trained scalar, ``head.logit_bias``).
+        ``classify``: also train the bridge's classification branch (cross attention, fusion, classifier) on class labels
+        with ``ce_weight`` x the (``class_weight``-ed, (num_classes,) floats) cross-entropy: `train_step(..., labels=)`,
+        three more launches per step (mm_bridge_cls_fwd, mm_bridge_cls_bwd).  ``num_classes`` sizes
+        the bridge's classifier on any trainer (`predict`)."""
         super().__init__()
+        self.classify, self.ce_weight, self.num_classes = bool(classify), float(ce_weight), int(num_classes)
+        cw = None
+        if class_weight is not None:
+            if not classify:
+                raise ValueError("BridgeTrainer: class_weight needs classify=True")
+            cw = torch.as_tensor(class_weight, dtype=torch.float32).reshape(-1)
+            if cw.numel() != self.num_classes or bool((cw < 0).any()):
+                raise ValueError(f"BridgeTrainer: class_weight must be {self.num_classes} non-negative floats (got {cw.tolist()})")
+        if classify:
+            if self.ce_weight < 0:
+                raise ValueError(f"BridgeTrainer: ce_weight must be >= 0 (got {ce_weight})")
+            if group is not None and dp.world_size(group) > 1:
+                raise NotImplementedError("BridgeTrainer: classify=True with a process group of world size > 1 is not "
+                                          "supported yet (intended: the mean over ranks of each rank's weighted mean)")
+            ops.bridge_cls_check(bridge_dim, 4, self.num_classes, "BridgeTrainer(classify=True)")   # (the bridge has 4 heads)
         if augment is not None:
             from .crossmodal_eeg_scr import EEGTransforms
             if not isinstance(augment, EEGTransforms):
@@ -78,9 +98,11 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
         else:
             raise TypeError(f"BridgeTrainer: no tape for an EEG encoder of type {type(self.eeg_encoder).__name__}")
         self.fmri_encoder = fMRIVolumeEncoder3D(1, fmri_dim, dropout=dropout)
-        self.head = EEGfMRIContrastiveBridge(hidden_dim, fmri_dim, bridge_dim, dropout, loss=loss)
+        self.head = EEGfMRIContrastiveBridge(hidden_dim, fmri_dim, bridge_dim, dropout, loss=loss, num_classes=num_classes)
         self.loss = loss
         self.to(device)
+        self._class_weight = None if cw is None else cw.to(device)     # (not a buffer: the state dict keeps its keys)
+        self._cls_ticket = None                       # int32 word of mm_bridge_cls_fwd, allocated at the first labelled step
         self.group = group
         self.two_streams = True
         self.mode = mode
@@ -95,17 +117,22 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
         self.lr, self.weight_decay, self.grad_clip = lr, weight_decay, grad_clip
         self.betas, self.eps = betas, eps
         br = self.head.bridge
-        # only what the contrastive path touches is trained (the classifier /
-        # cross-attention half of the bridge stays out of the bucket)
+        # only what the step touches is trained: without ``classify`` the classifier / cross-attention half of the
+        # bridge stays out of the bucket
+        is_proj = lambda name: name.startswith("eeg_proj") or name.startswith("fmri_proj")  # noqa: E731
         for name, p in br.named_parameters():
-            if not (name.startswith("eeg_proj") or name.startswith("fmri_proj")):
+            if not is_proj(name) and not classify:
                 p.requires_grad_(False)
         # bucket order = the order in which gradients are NOT yet final, i.e. the reverse of when each layer group's
         # all-reduce can start (`_seg_backward`): conv block 1 (last kernel of the chain) | conv blocks 2-3 (final once
         # the second hand-over has been flushed) | transformer stack + encoder head + projection heads + logit scale
         # (first hand-over) | fMRI encoder (its own, shorter backward).  Each group is one contiguous range of the
         # flat bucket, the fMRI encoder's the tail [fmri_lo, n).
-        head_params = [p for p in br.parameters() if p.requires_grad] + [self.head.logit_scale]
+        # (classification branch: the parameters whose size is no multiple of 4 floats go last, so that the matrices
+        # before them keep the alignment the projection heads' weights have)
+        cls_params = [p for name, p in br.named_parameters() if p.requires_grad and not is_proj(name)]
+        cls_params.sort(key=lambda p: p.numel() % 4 != 0)
+        head_params = [p for name, p in br.named_parameters() if p.requires_grad and is_proj(name)] + cls_params + [self.head.logit_scale]
         if loss == "sigmoid":
             head_params.append(self.head.logit_bias)
         if self._eeg_kind == "erp":
@@ -134,7 +161,10 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
         # {loss, top-1 e->f, top-1 f->e, d loss / d logit_scale} (sigmoid: + d loss / d logit_bias) of the last step:
         # owned by this trainer (plain stores of the loss kernel), so the tensors a step returns are overwritten only
         # by THIS trainer's next step - keep a value with .item() / .clone()
-        self._scal = torch.zeros(5 if loss == "sigmoid" else 4, device=device)
+        # classify: + {ce, rows classified right, sum of row weights, ce_weight * ce} (mm_bridge_cls_fwd) and the total
+        # loss (mm_bridge_cls_bwd), after the contrastive loss's words
+        self._scal_cls = 5 if loss == "sigmoid" else 4
+        self._scal = torch.zeros(self._scal_cls + (5 if classify else 0), device=device)
         ops.weights_changed()
 
     @property
@@ -163,19 +193,28 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
         many sub-chip kernels of one branch overlap the other's latency.
         ``groups``: (B,) integer ids, pairs with equal ids are positives of each other (ops.clip_loss)."""
         gid = ops.group_ids(groups, eeg.shape[0], eeg.device, "BridgeTrainer")
-        if not self.two_streams:
-            return self.head(self.eeg_encoder(eeg), self.fmri_encoder(fmri), self.group, gid)
-        main = torch.cuda.current_stream()
-        self._side.wait_stream(main)
-        with torch.cuda.stream(self._side):
-            ff = self.fmri_encoder(fmri)
-        fe = self.eeg_encoder(eeg)
-        main.wait_stream(self._side)
-        ff.record_stream(main)
+        fe, ff = self._encode(eeg, fmri)
         return self.head(fe, ff, self.group, gid)
 
     # ------------------------------------------------------------------ step
-    def train_step(self, eeg: torch.Tensor, fmri: torch.Tensor, groups: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+    def _labels(self, labels, B: int, device, who: str):
+        """`ops.class_labels` plus the rule that a classify trainer's step takes labels and no other trainer's does"""
+        if self.classify and labels is None:
+            raise ValueError(f"{who}: this trainer was built with classify=True and needs labels=")
+        if labels is not None and not self.classify:
+            raise ValueError(f"{who}: labels= needs a trainer built with classify=True")
+        return ops.class_labels(labels, B, self.num_classes, device, who)
+
+    def _result(self, scal) -> Dict[str, torch.Tensor]:
+        """the dict a step returns: views of the trainer's result words"""
+        out = {"loss": scal[0], "top1_e2f": scal[1], "top1_f2e": scal[2]}
+        if self.classify:
+            o = self._scal_cls
+            out.update(loss=scal[o + 4], contrastive_loss=scal[0], ce_loss=scal[o], cls_correct=scal[o + 1])
+        return out
+
+    def train_step(self, eeg: torch.Tensor, fmri: torch.Tensor, groups: Optional[torch.Tensor] = None,
+                   labels: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
         """zero_grad -> forward -> backward -> (all-reduce) -> clip + AdamW.
 
         ``mode``: "graph" (default) replays the step from hipGraphs captured on
@@ -183,24 +222,71 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
         collectives otherwise); "manual" runs the same autograd-free tape eagerly;
         "autograd" goes through the public nn.Module / torch.autograd surface.
         ``groups``: (B,) integer ids (e.g. subjects; ``ops.group_ids``): pairs with equal ids are positives of each
-        other (mm_clip_loss_own_rows_grouped).  In graph mode a grouped step is its own capture, as a new shape is."""
+        other (mm_clip_loss_own_rows_grouped).  In graph mode a grouped step is its own capture, as a new shape is.
+        ``labels``: (B,) integer class labels (``ops.class_labels``), required by - and only taken by - a trainer built
+        with ``classify=True``: the step then also trains the classification branch and returns ``contrastive_loss``,
+        ``ce_loss``, ``cls_correct`` and ``loss`` = contrastive_loss + ce_weight * ce_loss."""
         ops.check_volume_shape(fmri.shape)                 # before the first launch of the step (or of its capture)
         gid = ops.group_ids(groups, eeg.shape[0], None if self.mode == "graph" else eeg.device, "train_step")
+        lab = self._labels(labels, eeg.shape[0], None if self.mode == "graph" else eeg.device, "train_step")
+        if lab is not None and self._cls_ticket is None:       # this trainer's own word, allocated before any capture
+            self._cls_ticket = torch.zeros(1, dtype=torch.int32, device=self._scal.device)
         aug_step = None
         if self.augment is not None:                       # one step index per call, whatever the mode
             aug_step, self._aug_step = self._aug_step, self._aug_step + 1
             if self.mode != "graph":
                 eeg = self.augment.batch(eeg, aug_step, dp.rank(self.group))
         if self.mode == "autograd":
-            return self._step_autograd(eeg, fmri, gid)
+            return self._step_autograd(eeg, fmri, gid, lab)
         if self.mode == "manual":
             with torch.no_grad():
-                return self._step_manual(eeg, fmri, gid)
-        return self._step_graph(eeg, fmri, gid, aug_step)
+                return self._step_manual(eeg, fmri, gid, lab)
+        return self._step_graph(eeg, fmri, gid, aug_step, lab)
 
-    def _step_autograd(self, eeg, fmri, gid=None):
+    def _encode(self, eeg, fmri):
+        """both encoders through their nn.Module surface: independent until the heads, so on two HIP streams"""
+        if not self.two_streams:
+            return self.eeg_encoder(eeg), self.fmri_encoder(fmri)
+        main = torch.cuda.current_stream()
+        self._side.wait_stream(main)
+        with torch.cuda.stream(self._side):
+            ff = self.fmri_encoder(fmri)
+        fe = self.eeg_encoder(eeg)
+        main.wait_stream(self._side)
+        ff.record_stream(main)
+        return fe, ff
+
+    def _forward_classify(self, eeg, fmri, gid, lab):
+        """the classify step's forward from the existing differentiable pieces (the independent path the tape is
+        compared with): projection heads, F.normalize, the contrastive loss, `ops.bridge_cls_rows` (bridge_forward's
+        train branch on the projected rows) and the weighted cross-entropy.  Seeds are drawn in the tape's order."""
+        from . import small_autograd as sa
+        br = self.head.bridge
+        fe, ff = self._encode(eeg, fmri)
+        p = br.drop_p if self.training else 0.0
+        ep = sa.proj_head(fe, br.eeg_proj, p)
+        fp = sa.proj_head(ff, br.fmri_proj, p)
+        ze = torch.nn.functional.normalize(ep, dim=1, eps=1e-12)
+        zf = torch.nn.functional.normalize(fp, dim=1, eps=1e-12)
+        logits, fw, aw = ops.bridge_cls_rows(br, ep, fp)
+        if self.loss == "sigmoid":
+            lc, acc_e, acc_f = ops.sigmoid_loss(ze, zf, self.head.logit_scale, self.head.logit_bias, self.group, gid)
+        else:
+            lc, acc_e, acc_f = ops.clip_loss(ze, zf, self.head.logit_scale, self.group, gid)
+        ce = ops.weighted_cross_entropy(logits, lab.long(), self._class_weight)
+        return lc, acc_e, acc_f, ce, logits
+
+    def _step_autograd(self, eeg, fmri, gid=None, lab=None):
         b = self.bucket
         b.zero_grad()
+        if lab is not None:
+            lc, acc_e, acc_f, ce, logits = self._forward_classify(eeg, fmri, gid, lab)
+            loss = lc + self.ce_weight * ce
+            loss.backward()
+            b.absorb_autograd_grads()
+            self._seg_optimizer()
+            return {"loss": loss.detach(), "top1_e2f": acc_e, "top1_f2e": acc_f, "contrastive_loss": lc.detach(),
+                    "ce_loss": ce.detach(), "cls_correct": (logits.detach().argmax(dim=1) == lab).sum().float()}
         loss, acc_e, acc_f = self.forward(eeg, fmri, gid)
         loss.backward()
         b.absorb_autograd_grads()
@@ -216,9 +302,10 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
         if self.stamps is not None:
             _hip.call("mm_debug_stamp", self.stamps, i)
 
-    def _seg_forward(self, eeg, fmri, xb=None):
+    def _seg_forward(self, eeg, fmri, xb=None, lab=None):
         """``xb``: the EEG batch already packed (B, T, Cp) bf16 (the captured step reads its static packed buffer, which
-        the trainer fills outside the graph together with the input copies)"""
+        the trainer fills outside the graph together with the input copies).  ``lab``: int32 device class labels (a
+        classify trainer's step): the classification branch's forward follows the projection heads'."""
         self._stamp(0)
         # one memset of what the step's accumulators actually use (high-water mark of the first
         # step + slack); the gradient bucket is cleared by the previous step's AdamW kernel
@@ -251,8 +338,13 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
             ff, sv_f = fmri_branch()
         main.wait_stream(self._side)
         z, sv_h = ops.contrastive_embed_impl(self.head.bridge, fe, ff, True)
+        sv_c = None
+        if lab is not None:
+            o = self._scal_cls
+            sv_c = ops.bridge_cls_forward_impl(self.head.bridge, sv_h, True, lab, self._class_weight, self.ce_weight,
+                                               loss_out=self._scal[o:o + 4], ticket=self._cls_ticket)[3]
         self._stamp(5)
-        return z, (sv_e, sv_f, sv_h)
+        return z, (sv_e, sv_f, sv_h, sv_c)
 
     @staticmethod
     def _fmri_is_longer(fmri) -> bool:
@@ -298,7 +390,7 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
         """``reduce``: all-reduce every layer group of the gradient bucket as soon as it is final - the fMRI encoder's
         after that branch's backward, the transformer stack's and conv blocks 3-2's after their handed-over sums were
         flushed on the side stream (all three hidden beside the EEG chain), conv block 1's after the chain"""
-        sv_e, sv_f, sv_h = saved
+        sv_e, sv_f, sv_h, sv_c = saved
         self._works = []
         bag = GradBag()
         with deferred(bag, dz.device):           # ONE batched reduction after both branches joined
@@ -306,7 +398,12 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
             bag.defer(scal.data_ptr() + 12, self.head.logit_scale._mm_grad.view(1), 1, 1, 1, keep=scal)
             if self.loss == "sigmoid":           # and d loss / d logit_bias (scal[4])
                 bag.defer(scal.data_ptr() + 16, self.head.logit_bias._mm_grad.view(1), 1, 1, 1, keep=scal)
-            dfe, dff = contrastive_embed_bwd(bag, sv_h, dz)
+            if sv_c is None:
+                dfe, dff = contrastive_embed_bwd(bag, sv_h, dz)
+            else:                                # the classification branch's two launches, then the heads' with its da
+                o = self._scal_cls
+                da = bridge_cls_bwd(bag, sv_c, loss_in=scal[0:1], loss_total=scal[o + 4:o + 5])
+                dfe, dff = contrastive_embed_bwd_da(bag, sv_h, dz, da)
             self._stamp(7)
             main = torch.cuda.current_stream()
             self._side.wait_stream(main)
@@ -403,34 +500,36 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
         ops.arena.end()
         self._stamp(12)
 
-    def _step_manual(self, eeg, fmri, gid=None):
+    def _step_manual(self, eeg, fmri, gid=None, lab=None):
         recording = self._weight_list is None
         if recording:                                 # first step: note every weight image the tape asks for
             ops.weights.start_recording()
         try:
-            return self._step_manual_body(eeg, fmri, gid)
+            return self._step_manual_body(eeg, fmri, gid, lab)
         finally:
             if recording:
                 self._weight_list = ops.weights.stop_recording()
 
-    def _step_manual_body(self, eeg, fmri, gid=None):
+    def _step_manual_body(self, eeg, fmri, gid=None, lab=None):
         gid_all = None if gid is None else dp.gather_embeddings(gid.view(-1, 1), self.group).view(-1)
-        z, saved = self._seg_forward(eeg, fmri)
+        z, saved = self._seg_forward(eeg, fmri, lab=lab)
         z_all = dp.gather_embeddings(z, self.group)
         scal, dz = self._scal, ops._empty(tuple(z.shape), torch.float32, z)
         self._seg_loss(z_all, scal, dz, gid_all)
         early = dp.active(self.group)
         self._seg_backward(saved, dz, scal, reduce=early)
         self._seg_optimizer(reduced=early)
-        return {"loss": scal[0], "top1_e2f": scal[1], "top1_f2e": scal[2]}
+        return self._result(scal)
 
     # ---- hipGraph capture ------------------------------------------------------
-    def _capture(self, eeg, fmri, gid=None):
+    def _capture(self, eeg, fmri, gid=None, lab=None):
         dev = eeg.device
+        if self._cls_ticket is not None:
+            self._cls_ticket.zero_()                      # (a launch that died mid-count would have left it non-zero)
         world = self.world
         c = {"epoch": torch.zeros(1, dtype=torch.int32, device=dev)}
         # the step's static inputs are views of ONE flat buffer `c["in"]` = [EEG operand | fMRI volumes fp32 | group ids
-        # int32 (grouped captures only)], so that a host-fed loop fills them with a single copy (`train_step_packed`).
+        # int32 (grouped captures only) | class labels int32 (labelled captures only)], so that a host-fed loop fills them with a single copy (`train_step_packed`).
         # EEG operand: the first convolution's packed bf16 (B, T, Cp) image (the STFT front-end reads the raw fp32 batch
         # instead and keeps that)
         stft = self._eeg_kind == "stft"
@@ -438,13 +537,19 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
         n_e = eeg.numel() * 4 if stft else Bx * Tx * ops.cpad(Cx) * 2
         n_f = fmri.numel() * 4
         c["grouped"] = gid is not None
-        c["in"] = torch.empty(n_e + n_f + (Bx * 4 if c["grouped"] else 0), dtype=torch.uint8, device=dev)
+        c["labelled"] = lab is not None
+        n_g = Bx * 4 if c["grouped"] else 0
+        c["in"] = torch.empty(n_e + n_f + n_g + (Bx * 4 if c["labelled"] else 0), dtype=torch.uint8, device=dev)
         c["fmri"] = c["in"][n_e:n_e + n_f].view(torch.float32).view(fmri.shape)
         c["fmri"].copy_(fmri)
         c["gid"] = c["gid_all"] = None
         if c["grouped"]:
-            c["gid"] = c["in"][n_e + n_f:].view(torch.int32)
+            c["gid"] = c["in"][n_e + n_f:n_e + n_f + n_g].view(torch.int32)
             c["gid"].copy_(gid)
+        c["lab"] = None
+        if c["labelled"]:
+            c["lab"] = c["in"][n_e + n_f + n_g:].view(torch.int32)
+            c["lab"].copy_(lab)
         if stft:
             c["eeg"], c["xb"] = c["in"][:n_e].view(torch.float32).view(eeg.shape), None
             c["eeg"].copy_(eeg)
@@ -463,7 +568,7 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side), torch.no_grad():
             for _ in range(2):
-                self._step_manual(c["eeg"], c["fmri"], c["gid"])
+                self._step_manual(c["eeg"], c["fmri"], c["gid"], c["lab"])
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
         with torch.no_grad():
@@ -500,7 +605,7 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
             c["gid_all"] = torch.empty(world * B, dtype=torch.int32, device=dev) if c["gid_gather"] else c["gid"]
         if not dist_step:
             def whole():
-                z, saved = self._seg_forward(c["eeg"], c["fmri"], xb=c["xb"])
+                z, saved = self._seg_forward(c["eeg"], c["fmri"], xb=c["xb"], lab=c["lab"])
                 c["z"] = z
                 c["dz"] = ops._empty(tuple(z.shape), torch.float32, z)
                 self._seg_loss(z, c["scal"], c["dz"], c["gid_all"])
@@ -514,7 +619,7 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
         else:
             self.capture_mode = "3 segments + 2 eager collectives"
             def seg1():
-                c["z"], c["saved"] = self._seg_forward(c["eeg"], c["fmri"], xb=c["xb"])
+                c["z"], c["saved"] = self._seg_forward(c["eeg"], c["fmri"], xb=c["xb"], lab=c["lab"])
                 c["dz"] = ops._empty((B, N2), torch.float32, c["z"])
             record(seg1)
             c["z_all"] = torch.empty(world * B, N2, device=dev)
@@ -554,7 +659,7 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
 
         def whole_dp():
             self._gather_group_ids(c)
-            z, saved = self._seg_forward(c["eeg"], c["fmri"], xb=c["xb"])
+            z, saved = self._seg_forward(c["eeg"], c["fmri"], xb=c["xb"], lab=c["lab"])
             c["z"] = z
             c["dz"] = ops._empty((B, N2), torch.float32, z)
             dp.all_gather_into(c["z_all"], z, self.group)
@@ -607,13 +712,13 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
         with torch.cuda.stream(self._side):
             dp.all_gather_into(c["gid_all"].view(-1, 1), c["gid"].view(-1, 1), self.group)
 
-    def _step_graph(self, eeg, fmri, gid=None, aug_step=None):
+    def _step_graph(self, eeg, fmri, gid=None, aug_step=None, lab=None):
         """``aug_step``: the augmentation's step index (trainers with an augmenter).  The capture and its two warm-up steps
         see the batch as it came; what a replay reads is staged below, augmented."""
         if (self._cap is None or self._cap["eeg"].shape != eeg.shape or self._cap["fmri"].shape != fmri.shape
-                or self._cap["grouped"] != (gid is not None)):
+                or self._cap["grouped"] != (gid is not None) or self._cap["labelled"] != (lab is not None)):
             step0, base0 = ops._seed_state["step"], ops._seed_state["base"]
-            self._capture(eeg, fmri, gid)
+            self._capture(eeg, fmri, gid, lab)
             # the dropout seeds of this capture were drawn from here on (checkpoint_state)
             self._cap["seed_step"], self._cap["seed_base"] = step0, base0
             if self._pending_epoch_word is not None:      # resumed: the replays go on from the saved epoch word
@@ -624,6 +729,8 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
             self._stage_inputs(c, eeg if aug_step is None else self.augment.batch(eeg, aug_step, dp.rank(self.group)), fmri)
         if gid is not None and gid.data_ptr() != c["gid"].data_ptr():
             c["gid"].copy_(gid)
+        if lab is not None and lab.data_ptr() != c["lab"].data_ptr():
+            c["lab"].copy_(lab)
         return self._replay()
 
     def _stage_inputs(self, c, eeg, fmri):
@@ -675,7 +782,7 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
             g[1].replay()                                              # loss on the gathered batch + backward
             dp.allreduce_sum_(self.bucket.g, self.group)
             g[2].replay()                                              # clip + AdamW
-        return {"loss": c["scal"][0], "top1_e2f": c["scal"][1], "top1_f2e": c["scal"][2]}
+        return self._result(c["scal"])
 
     # ---- host-fed input path ---------------------------------------------------
     def pack_host_batch(self, eeg: torch.Tensor, fmri: torch.Tensor, out: Optional[torch.Tensor] = None,
@@ -727,6 +834,9 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
         return HostFeeder(self, depth)
 
     def _no_packed_augment(self, who: str):
+        if self.classify:
+            raise ValueError(f"{who}: the packed host-fed path carries no class labels; feed a classify=True trainer "
+                             "through train_step(eeg, fmri, groups, labels)")
         if self.augment is not None:
             raise ValueError(f"{who}: this trainer has an augmenter, and a batch that is already packed to bf16 on the host "
                              "cannot be augmented after the fact (the noise scale needs the fp32 sample); feed "
@@ -767,16 +877,69 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
         return None if self._cap is None else (self._cap["eeg"], self._cap["fmri"])
 
     @torch.no_grad()
-    def evaluate(self, eeg, fmri, groups=None):
-        """eval-mode loss and in-batch top-1 of one batch (``groups``: as in `train_step`)"""
+    def evaluate(self, eeg, fmri, groups=None, labels=None):
+        """eval-mode loss and in-batch top-1 of one batch (``groups``, ``labels``: as in `train_step`; with labels also
+        ``contrastive_loss``, ``ce_loss`` and ``cls_correct``, and ``loss`` is their weighted sum)"""
+        lab = self._labels(labels, eeg.shape[0], eeg.device, "evaluate")
         was = self.training
         self.eval()
         ops.weights_changed()                      # graph replays bypass the python-side version counter
         try:
-            loss, acc_e, acc_f = self.forward(eeg, fmri, groups)
+            if lab is None:
+                loss, acc_e, acc_f = self.forward(eeg, fmri, groups)
+                return {"loss": loss, "top1_e2f": acc_e, "top1_f2e": acc_f}
+            gid = ops.group_ids(groups, eeg.shape[0], eeg.device, "evaluate")
+            br = self.head.bridge
+            fe, ff = self._encode(eeg, fmri)
+            z, sv_h = ops.contrastive_embed_impl(br, fe, ff, False)
+            cls = ops.bridge_cls_forward_impl(br, sv_h, False, lab, self._class_weight, self.ce_weight)[3]["loss"]
+            N = br.bridge_dim
+            if self.loss == "sigmoid":
+                lc, acc_e, acc_f = ops.sigmoid_loss(z[:, :N], z[:, N:], self.head.logit_scale, self.head.logit_bias, self.group, gid)
+            else:
+                lc, acc_e, acc_f = ops.clip_loss(z[:, :N], z[:, N:], self.head.logit_scale, self.group, gid)
+            return {"loss": lc + cls[3], "top1_e2f": acc_e, "top1_f2e": acc_f, "contrastive_loss": lc, "ce_loss": cls[0],
+                    "cls_correct": cls[1]}
         finally:
             self.train(was)
-        return {"loss": loss, "top1_e2f": acc_e, "top1_f2e": acc_f}
+
+    @torch.no_grad()
+    def predict(self, eeg, fmri, batch_size: int = 256) -> Dict[str, torch.Tensor]:
+        """the bridge classifier's eval-mode outputs for paired inputs (host or device, ``batch_size`` pairs at a time):
+        ``logits`` (N, C), ``probs`` = softmax, ``pred`` = argmax (int64), ``fusion_weights`` (N, 2), ``attn_weights``
+        (N, 2; head-averaged) on the trainer's device - the encoders, mm_proj_heads_fwd and mm_bridge_cls_fwd.  Never
+        augments, draws no dropout seed, restores the train / eval state; on a trainer without ``classify`` the branch
+        is the untrained initialisation."""
+        if eeg.shape[0] != fmri.shape[0]:
+            raise ValueError(f"predict: {eeg.shape[0]} EEG epochs but {fmri.shape[0]} fMRI volumes")
+        if batch_size < 1:
+            raise ValueError("predict: batch_size must be >= 1")
+        dev = self._scal.device
+        br = self.head.bridge
+        was = self.training
+        self.eval()
+        ops.weights_changed()                      # graph replays bypass the python-side version counter
+        try:
+            outs = []
+            for x, y in zip(self._chunks(eeg, batch_size, dev), self._chunks(fmri, batch_size, dev)):
+                ops.check_volume_shape(y.shape)
+                fe, ff = self._encode(x, y)
+                _, sv_h = ops.contrastive_embed_impl(br, fe, ff, False)
+                outs.append(ops.bridge_cls_forward_impl(br, sv_h, False)[:3])
+        finally:
+            self.train(was)
+        logits, fw, aw = (torch.cat(t) for t in zip(*outs))
+        return {"logits": logits, "probs": torch.softmax(logits, dim=1), "pred": logits.argmax(dim=1),
+                "fusion_weights": fw, "attn_weights": aw}
+
+    def evaluate_classification(self, eeg, fmri, labels, batch_size: int = 256) -> dict:
+        """`predict`, then the reference's ``evaluate_bridge`` metric dict (`fmri_utils.classification_metrics`: Accuracy,
+        weighted F1 / Precision / Recall, and for two classes the AUC of class 1, 0.5 where undefined)"""
+        from .fmri_utils import classification_metrics
+        lab = ops.class_labels(labels.detach().cpu() if isinstance(labels, torch.Tensor) else labels, eeg.shape[0],
+                               self.num_classes, None, "evaluate_classification")
+        out = self.predict(eeg, fmri, batch_size)
+        return classification_metrics(lab.numpy(), out["pred"].cpu().numpy(), out["probs"].cpu().numpy(), self.num_classes)
 
     @staticmethod
     def _chunks(x: torch.Tensor, batch_size: int, device):

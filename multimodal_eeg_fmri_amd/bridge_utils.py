@@ -74,18 +74,19 @@ class EEGfMRIContrastiveBridge(nn.Module):
     ``loss``: "infonce" (default; ops.clip_loss) or "sigmoid" (the pairwise sigmoid
     loss of Zhai et al., ops.sigmoid_loss).  With "sigmoid" ``logit_scale`` starts at
     ln(``init_scale``) and a second learnable scalar ``logit_bias`` = ``init_bias``
-    exists (the paper's 10 and -10); it is absent otherwise.
+    exists (the paper's 10 and -10); it is absent otherwise.  ``num_classes`` sizes the bridge's classifier.
     """
 
     LOSSES = ("infonce", "sigmoid")
 
     def __init__(self, eeg_dim=128, fmri_dim=64, bridge_dim=128, dropout=0.3,
-                 init_tau: float = 0.07, loss: str = "infonce", init_scale: float = 10.0, init_bias: float = -10.0):
+                 init_tau: float = 0.07, loss: str = "infonce", init_scale: float = 10.0, init_bias: float = -10.0,
+                 num_classes: int = 2):
         super().__init__()
         if loss not in self.LOSSES:
             raise ValueError(f"EEGfMRIContrastiveBridge: loss must be one of {list(self.LOSSES)}, got {loss!r}")
         self.loss = loss
-        self.bridge = EEGfMRIBridgeFusionNet(eeg_dim, fmri_dim, bridge_dim, dropout=dropout)
+        self.bridge = EEGfMRIBridgeFusionNet(eeg_dim, fmri_dim, bridge_dim, num_classes=num_classes, dropout=dropout)
         if loss == "sigmoid":
             self.logit_scale = nn.Parameter(torch.tensor(math.log(init_scale)))
             self.logit_bias = nn.Parameter(torch.tensor(float(init_bias)))

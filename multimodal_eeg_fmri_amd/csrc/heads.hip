@@ -183,6 +183,7 @@ struct HeadsArgs {
     float* z1; float* hn; float* stat;        // [2][B][N], [2][B][N], [2][B][2]   saved for backward
     float* z; float* nrm;                     // [B][2N] packed embeddings, [2][B]
     const float* dz;                          // [B][2N]
+    const float* da;                          // [2][B][N] more gradient at the heads' outputs (proj_heads_bwd_da), or null
     int B, N; float eps; uint32_t thresh; float inv_keep; const uint32_t* epoch;
 };
 constexpr int HEAD_MAXK = 1024, HEAD_MAXN = 256;
@@ -274,8 +275,10 @@ namespace {
 // flops each, the same bits in every block), then block j writes dx of row j and the j-th slice of dW, each element
 // summed over the rows in order; block 0 adds the bias and LayerNorm-parameter gradients (per-wave partials combined
 // in wave order).  NE = ceil(N / 64) elements per lane.
+// DA: a second gradient at the post-dropout activations, `a.da` (the classification branch reads the same rows), joins
+// the F.normalize term before the dropout mask and GELU'.
 constexpr int HB_RC = 32;                                   // rows per LDS chunk (= 2 per wave)
-template <int NE>
+template <int NE, bool DA>
 __global__ __launch_bounds__(1024) void proj_heads_bwd_kernel(HeadsArgs a) {
     __shared__ float d1[HB_RC][HEAD_MAXN];                  // 32 KB; re-used for the LayerNorm partials at the end
     __shared__ float px[1024];                              // dx partials [part][k]
@@ -294,7 +297,7 @@ __global__ __launch_bounds__(1024) void proj_heads_bwd_kernel(HeadsArgs a) {
         const int nb = B - b0 < HB_RC ? B - b0 : HB_RC;
         __syncthreads();                                    // the previous chunk is consumed
         // rows wave and wave + 16 of the chunk: every load of both rows is issued before the first use
-        float dzv[2][NE], zv[2][NE], hnv[2][NE], z1v[2][NE], mean[2], rstd[2], nr[2];
+        float dzv[2][NE], zv[2][NE], hnv[2][NE], z1v[2][NE], dav[2][NE], mean[2], rstd[2], nr[2];
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
             const int r = wave + 16 * q;
@@ -311,6 +314,7 @@ __global__ __launch_bounds__(1024) void proj_heads_bwd_kernel(HeadsArgs a) {
                 zv[q][e] = on ? a.z[oz + n] : 0.f;
                 hnv[q][e] = on ? a.hn[o + n] : 0.f;
                 z1v[q][e] = on ? a.z1[o + n] : 0.f;
+                dav[q][e] = DA && on ? a.da[o + n] : 0.f;
             }
         }
 #pragma unroll
@@ -330,6 +334,7 @@ __global__ __launch_bounds__(1024) void proj_heads_bwd_kernel(HeadsArgs a) {
                 if (n < N) {
                     // F.normalize backward: da = (dz - z (z . dz)) / ||a||
                     float g = (dzv[q][e] - zv[q][e] * dot) / nr[q];
+                    if (DA) g += dav[q][e];
                     if (a.thresh) g *= dropout_scale(seed, (uint32_t)(b * N + n), a.thresh, a.inv_keep);
                     const float dh = g * gelu_erf_grad(hnv[q][e]);
                     xh[e] = (z1v[q][e] - mean[q]) * rstd[q];
@@ -406,12 +411,12 @@ __global__ __launch_bounds__(1024) void proj_heads_bwd_kernel(HeadsArgs a) {
 }  // namespace
 
 extern "C" {
-int mm_proj_heads_bwd(const float* dz, const float* z, const float* nrm, const float* hn, const float* z1,
-                      const float* stat, const float* x_e, const float* W_e, const float* g_e, int K_e,
-                      const float* x_f, const float* W_f, const float* g_f, int K_f, float* dx_e, float* dW_e,
-                      float* db_e, float* dg_e, float* dbe_e, float* dx_f, float* dW_f, float* db_f, float* dg_f,
-                      float* dbe_f, int B, int N, float drop_p, uint32_t seed_e, uint32_t seed_f,
-                      const uint32_t* seed_epoch, hipStream_t st) {
+static int proj_heads_bwd_common(const float* dz, const float* da, const float* z, const float* nrm, const float* hn,
+                                 const float* z1, const float* stat, const float* x_e, const float* W_e, const float* g_e,
+                                 int K_e, const float* x_f, const float* W_f, const float* g_f, int K_f, float* dx_e,
+                                 float* dW_e, float* db_e, float* dg_e, float* dbe_e, float* dx_f, float* dW_f, float* db_f,
+                                 float* dg_f, float* dbe_f, int B, int N, float drop_p, uint32_t seed_e, uint32_t seed_f,
+                                 const uint32_t* seed_epoch, hipStream_t st) {
     MM_REQUIRE(dz && z && nrm && hn && z1 && stat && x_e && W_e && g_e && x_f && W_f && g_f, "proj_heads_bwd: null");
     MM_REQUIRE(B > 0 && N > 0 && N <= HEAD_MAXN && K_e > 0 && K_e <= HEAD_MAXK && K_f > 0 && K_f <= HEAD_MAXK,
                "proj_heads_bwd: B=%d N=%d K=%d/%d", B, N, K_e, K_f);
@@ -421,16 +426,44 @@ int mm_proj_heads_bwd(const float* dz, const float* z, const float* nrm, const f
     a.s[1].x = x_f; a.s[1].W = W_f; a.s[1].gamma = g_f; a.s[1].K = K_f; a.s[1].seed = seed_f;
     a.s[1].dx = dx_f; a.s[1].dW = dW_f; a.s[1].dbias = db_f; a.s[1].dgamma = dg_f; a.s[1].dbeta = dbe_f;
     a.z1 = const_cast<float*>(z1); a.hn = const_cast<float*>(hn); a.stat = const_cast<float*>(stat);
-    a.z = const_cast<float*>(z); a.nrm = const_cast<float*>(nrm); a.dz = dz; a.B = B; a.N = N;
+    a.z = const_cast<float*>(z); a.nrm = const_cast<float*>(nrm); a.dz = dz; a.da = da; a.B = B; a.N = N;
     const DropH d = mm_drop(drop_p);
     a.thresh = d.thresh; a.inv_keep = d.inv_keep; a.epoch = seed_epoch;
+#define MM_HEADS_BWD(NE)                                                                                  \
+    if (da) hipLaunchKernelGGL((proj_heads_bwd_kernel<NE, true>), dim3(B, 2), dim3(1024), 0, st, a);      \
+    else hipLaunchKernelGGL((proj_heads_bwd_kernel<NE, false>), dim3(B, 2), dim3(1024), 0, st, a)
     switch (ceil_div(N, 64)) {
-        case 1: hipLaunchKernelGGL(proj_heads_bwd_kernel<1>, dim3(B, 2), dim3(1024), 0, st, a); break;
-        case 2: hipLaunchKernelGGL(proj_heads_bwd_kernel<2>, dim3(B, 2), dim3(1024), 0, st, a); break;
-        case 3: hipLaunchKernelGGL(proj_heads_bwd_kernel<3>, dim3(B, 2), dim3(1024), 0, st, a); break;
-        default: hipLaunchKernelGGL(proj_heads_bwd_kernel<4>, dim3(B, 2), dim3(1024), 0, st, a); break;
+        case 1: MM_HEADS_BWD(1); break;
+        case 2: MM_HEADS_BWD(2); break;
+        case 3: MM_HEADS_BWD(3); break;
+        default: MM_HEADS_BWD(4); break;
     }
+#undef MM_HEADS_BWD
     return mm_check_launch("proj_heads_bwd");
+}
+
+int mm_proj_heads_bwd(const float* dz, const float* z, const float* nrm, const float* hn, const float* z1,
+                      const float* stat, const float* x_e, const float* W_e, const float* g_e, int K_e,
+                      const float* x_f, const float* W_f, const float* g_f, int K_f, float* dx_e, float* dW_e,
+                      float* db_e, float* dg_e, float* dbe_e, float* dx_f, float* dW_f, float* db_f, float* dg_f,
+                      float* dbe_f, int B, int N, float drop_p, uint32_t seed_e, uint32_t seed_f,
+                      const uint32_t* seed_epoch, hipStream_t st) {
+    return proj_heads_bwd_common(dz, nullptr, z, nrm, hn, z1, stat, x_e, W_e, g_e, K_e, x_f, W_f, g_f, K_f, dx_e, dW_e, db_e,
+                                 dg_e, dbe_e, dx_f, dW_f, db_f, dg_f, dbe_f, B, N, drop_p, seed_e, seed_f, seed_epoch, st);
+}
+
+// mm_proj_heads_bwd with one more gradient at the heads' outputs: da (2, B, N) = d loss / d (the post-GELU/dropout
+// activations a_e, a_f) from a second consumer of those rows (mm_bridge_cls_bwd), added to the F.normalize-backward
+// term before the dropout mask and GELU'.  The same kernel, compiled with the extra load.
+int mm_proj_heads_bwd_da(const float* dz, const float* da, const float* z, const float* nrm, const float* hn,
+                         const float* z1, const float* stat, const float* x_e, const float* W_e, const float* g_e, int K_e,
+                         const float* x_f, const float* W_f, const float* g_f, int K_f, float* dx_e, float* dW_e,
+                         float* db_e, float* dg_e, float* dbe_e, float* dx_f, float* dW_f, float* db_f, float* dg_f,
+                         float* dbe_f, int B, int N, float drop_p, uint32_t seed_e, uint32_t seed_f,
+                         const uint32_t* seed_epoch, hipStream_t st) {
+    MM_REQUIRE(da, "proj_heads_bwd_da: null");
+    return proj_heads_bwd_common(dz, da, z, nrm, hn, z1, stat, x_e, W_e, g_e, K_e, x_f, W_f, g_f, K_f, dx_e, dW_e, db_e,
+                                 dg_e, dbe_e, dx_f, dW_f, db_f, dg_f, dbe_f, B, N, drop_p, seed_e, seed_f, seed_epoch, st);
 }
 }  // extern "C"
 

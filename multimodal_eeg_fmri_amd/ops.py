@@ -1208,6 +1208,101 @@ def proj_embed_one(bridge, x: torch.Tensor, modality: str) -> torch.Tensor:
     return z[:, :N].contiguous()
 
 
+# ------------------------------------------- classification branch of the bridge (fp32, csrc/bridge_cls.hip)
+CLS_MAX_CLASSES = 16
+
+
+def bridge_cls_check(bridge_dim: int, num_heads: int, num_classes: int, who: str = "bridge_cls"):
+    """the shapes mm_bridge_cls_fwd / _bwd serve (the same test as their MM_REQUIRE): ValueError before any launch"""
+    if bridge_dim % 32 != 0 or not 32 <= bridge_dim <= 256:
+        raise ValueError(f"{who}: bridge_dim must be a multiple of 32 in [32, 256] (got {bridge_dim})")
+    if not 1 <= num_heads <= 16 or bridge_dim % num_heads != 0:
+        raise ValueError(f"{who}: num_heads must be <= 16 and divide bridge_dim {bridge_dim} (got {num_heads})")
+    if not 2 <= num_classes <= CLS_MAX_CLASSES:
+        raise ValueError(f"{who}: num_classes must be in [2, {CLS_MAX_CLASSES}] (got {num_classes})")
+
+
+def class_labels(labels, B: int, C: int, device=None, who: str = "labels") -> Optional[torch.Tensor]:
+    """Validate a (B,) vector of class labels -> int32 on ``device``, or None for None.  A host tensor of any integer
+    dtype is checked against [0, C) and converted; a device tensor must already be int32 (checking its values would
+    synchronise a replayed step: the kernel gives a row whose label is outside [0, C) weight 0)."""
+    if labels is None:
+        return None
+    if not isinstance(labels, torch.Tensor):
+        raise ValueError(f"{who}: class labels must be a torch.Tensor (got {type(labels).__name__})")
+    if labels.dim() != 1 or labels.shape[0] != B:
+        raise ValueError(f"{who}: class labels must have shape ({B},) (got {tuple(labels.shape)})")
+    if labels.dtype.is_floating_point or labels.dtype.is_complex or labels.dtype == torch.bool:
+        raise ValueError(f"{who}: class labels must be an integer tensor (got {labels.dtype})")
+    if labels.is_cuda:
+        if labels.dtype != torch.int32:
+            raise ValueError(f"{who}: class labels on the device must be int32 (got {labels.dtype}); host tensors of any "
+                             "integer dtype are converted")
+        if device is not None and labels.device != torch.device(device):
+            raise ValueError(f"{who}: class labels are on {labels.device}, the batch on {device}")
+        return labels.contiguous()
+    if B:
+        l64 = labels.long()
+        if bool((l64 < 0).any()) or bool((l64 >= C).any()):
+            raise ValueError(f"{who}: class labels must lie in [0, {C}) (got {int(l64.min())}..{int(l64.max())})")
+    l32 = labels.to(torch.int32).contiguous()
+    return l32 if device is None else l32.to(device)
+
+
+def bridge_cls_params(bridge):
+    """the parameters of the classification branch in the order of the entry points' arguments"""
+    ca, fu, cl = bridge.cross_attn, bridge.fusion, bridge.classifier
+    return (ca.in_proj_weight, ca.in_proj_bias, ca.out_proj.weight, ca.out_proj.bias, fu.gate_net[0].weight,
+            fu.gate_net[0].bias, fu.gate_net[3].weight, fu.gate_net[3].bias, fu.fusion_logits, fu.temperature,
+            cl[0].weight, cl[0].bias, cl[1].weight, cl[1].bias, cl[4].weight, cl[4].bias)
+
+
+def bridge_cls_forward_impl(bridge, sv_h: dict, training: bool, labels=None, class_weight=None, ce_weight: float = 1.0,
+                            loss_out=None, ticket=None):
+    """the classification branch on the rows of `contrastive_embed_impl` (``sv_h``: what it saved), ONE launch
+    (mm_bridge_cls_fwd) -> (logits (B, C), fusion_w (B, 2), attn_w (B, 2), saved).  ``labels`` int32 (B,) on the device
+    (`class_labels`): ``loss_out`` (4,) = {ce, rows classified right, sum of the row weights, ce_weight * ce} is
+    written (allocated here when None); without labels it is not touched.  ``ticket``: the int32 word in which
+    the launch's workgroups count themselves off (the last one sums the rows' loss terms and leaves it zero) - the
+    caller's own zeroed word, which no launch that may run at the same time shares (a trainer keeps one, allocated outside
+    any capture); None: a fresh zeroed word for this call (one fill; inside a capture it is a node of that graph).
+    Training draws one seed per dropout site whose p > 0: attention probabilities, gate hidden, classifier hidden - the order of `bridge_forward`'s train branch."""
+    hn = sv_h["hn"]
+    B, N = sv_h["B"], sv_h["N"]
+    H = int(bridge.num_heads)
+    ps = bridge_cls_params(bridge)
+    C = ps[14].shape[0]
+    bridge_cls_check(N, H, C)
+    if tuple(ps[4].shape) != (N, 2 * N) or tuple(ps[10].shape) != (N // 2, N):
+        raise ValueError("bridge_cls: the fusion gate / classifier widths are not those of EEGfMRIBridgeFusionNet")
+    if class_weight is not None and (class_weight.dtype != _F32 or tuple(class_weight.shape) != (C,)):
+        raise ValueError(f"bridge_cls: class_weight must be fp32 of shape ({C},)")
+    pa = float(bridge.cross_attn.dropout) if training else 0.0
+    pg = float(bridge.fusion.gate_net[2].p) if training else 0.0
+    pc = float(bridge.drop_p) if training else 0.0
+    sa_, sg, sc = (_next_seed() if p > 0 else 0 for p in (pa, pg, pc))
+    logits = _empty((B, C), _F32, hn)
+    fw = _empty((B, 2), _F32, hn)
+    aw = _empty((B, 2), _F32, hn)
+    save = _empty((_hip.host_int("mm_bridge_cls_ws_floats", B, N, 0),), _F32, hn)
+    if labels is None:
+        ticket = None
+    else:
+        if loss_out is None:
+            loss_out = _empty((4,), _F32, hn)
+        if ticket is None:
+            ticket = torch.zeros(1, dtype=torch.int32, device=hn.device)
+        elif ticket.dtype != torch.int32 or ticket.numel() != 1 or ticket.device != hn.device:
+            raise ValueError("bridge_cls: ticket must be one int32 word on the batch's device")
+    eps = float(bridge.classifier[1].eps)
+    _hip.call("mm_bridge_cls_fwd", hn, float(sv_h["p"]), int(sv_h["seeds"][0]), int(sv_h["seeds"][1]), *ps,
+              labels, class_weight, float(ce_weight), logits, fw, aw, save, loss_out if labels is not None else None,
+              ticket, B, N, H, C, eps, pa, sa_, pg, sg, pc, sc, EP())
+    saved = dict(save=save, logits=logits, loss=loss_out, labels=labels, ticket=ticket, ce_weight=float(ce_weight), B=B, N=N, H=H, C=C,
+                 drops=(pa, sa_, pg, sg, pc, sc), bridge=bridge)
+    return logits, fw, aw, saved
+
+
 def retrieval_ws_floats(nq: int, ng: int, d: int, k: int) -> int:
     """floats of mm_retrieval's scratch (mm_retrieval_ws_floats: the kernel file owns the layout)"""
     return _hip.host_int("mm_retrieval_ws_floats", nq, ng, d, k)
@@ -1403,6 +1498,26 @@ def bridge_forward(m, eeg, fmri):
         _hip.call("mm_act_f32", hn, hr, hn.numel(), ACT["relu"], 0.0, 0, None)
         logits, _ = small_linear(hr, m.classifier[4])
     return logits, fused, fw, attw.view(B, 1, 2)
+
+
+def bridge_cls_rows(m, ep, fp):
+    """the classification half of `bridge_forward`'s differentiable branch on rows that are already projected
+    (ep, fp = the post-dropout outputs of the two projection heads) -> (logits, fusion_w (B, 2), attn_w (B, 2)).
+    These are the lines of `bridge_forward`'s train branch after its two projections (that function stays as it is;
+    test_bridge_cls_rows_is_bridge_forwards_train_branch holds the two to the same bits).
+    The small_autograd composition, one launch per op: the independent path the fused kernels (csrc/bridge_cls.hip)
+    are compared with; dropout follows ``m.training`` and draws its seeds in their order."""
+    from . import small_autograd as sa
+    p = m.drop_p if m.training else 0.0
+    ca = m.cross_attn
+    pe = sa.SmallLinearFn.apply(ep, ca.in_proj_weight, ca.in_proj_bias, "none", 0.0)
+    pf = sa.SmallLinearFn.apply(fp, ca.in_proj_weight, ca.in_proj_bias, "none", 0.0)
+    ctx, attw = sa.Attn1x2Fn.apply(pe, pf, m.num_heads, float(ca.dropout) if m.training else 0.0)
+    att = sa.linear(ctx, ca.out_proj)
+    fused, fw = learned_fusion(m.fusion, [att, fp], m.training, autograd=True)
+    c = m.classifier
+    h = sa.ActFn.apply(sa.LayerNormFn.apply(sa.linear(fused, c[0]), c[1].weight, c[1].bias, c[1].eps), "relu", p)
+    return sa.linear(h, c[4]), fw, attw
 
 
 def _mlp_bn_act(x, lin, bn, act, drop_p, training):

@@ -431,6 +431,77 @@ def groups_case(step_iters=30):
     print(f"C2 graph step B=32: ungrouped {tu:7.1f} us  grouped {tg:7.1f} us  ({100 * (tg / tu - 1):+.2f} %)")
 
 
+def _spread(xs):
+    return f"{statistics.median(xs):7.1f} us  [{min(xs):.1f} .. {max(xs):.1f}]"
+
+
+def cls_case(B=32, N=128, step_iters=30, rounds=5):
+    """the bridge's classification objective.  (a) the section at B = 32, bridge_dim = 128, train mode (dropout 0.3): the
+    fused launches (mm_proj_heads_fwd, mm_bridge_cls_fwd, mm_bridge_cls_bwd x 2, mm_proj_heads_bwd_da; and the three
+    classification launches alone) against the eager composition they stand in for - EEGfMRIBridgeFusionNet's train
+    forward + WeightedCrossEntropy + backward - in the same run, interleaved rounds, median [min .. max].
+    (b) the C2 graph step with classify=True against the default step of the same build."""
+    from multimodal_eeg_fmri_amd import autograd
+    from multimodal_eeg_fmri_amd.bridge_utils import EEGfMRIBridgeFusionNet, WeightedCrossEntropy
+    torch.manual_seed(0)
+    m = EEGfMRIBridgeFusionNet(128, 64, N, 2, 4, dropout=0.3).cuda().train()
+    xe, xf = torch.randn(B, 128, device="cuda"), torch.randn(B, 64, device="cuda")
+    y64 = torch.randint(0, 2, (B,), device="cuda")
+    y32 = y64.to(torch.int32)
+    cw = torch.tensor([0.8, 1.3], device="cuda")
+    ce = WeightedCrossEntropy(cw).cuda()
+    dz = torch.randn(B, 2 * N, device="cuda") * 0.01
+
+    def eager():
+        for q in m.parameters():
+            q.grad = None
+        ce(m(xe, xf), y64).backward()
+
+    bag, keep = autograd.GradBag(), {}
+
+    def fused(heads=True):
+        with torch.no_grad():
+            if heads or "sv_h" not in keep:
+                keep["z"], keep["sv_h"] = ops.contrastive_embed_impl(m, xe, xf, True)
+            sv_c = ops.bridge_cls_forward_impl(m, keep["sv_h"], True, y32, cw, 1.0)[3]
+            da = autograd.bridge_cls_bwd(bag, sv_c)
+            if heads:
+                autograd.contrastive_embed_bwd_da(bag, keep["sv_h"], dz, da)
+
+    cases = [("eager composition (model fwd + CE + bwd)", eager), ("fused section incl. both heads launches", fused),
+             ("fused classification launches alone (3)", lambda: fused(False))]
+    times = [[] for _ in cases]
+    for _ in range(rounds):
+        for i, (_, fn) in enumerate(cases):
+            times[i].append(timeit(fn, iters=step_iters, rounds=1))
+    print(f"classification section B={B} bridge_dim={N} (eager launches from the host, stream time):")
+    for (name, _), t in zip(cases, times):
+        print(f"  {name:44s} {_spread(t)}")
+    g = [[] for _ in cases[1:]]
+    for _ in range(rounds):
+        for i, (_, fn) in enumerate(cases[1:]):
+            g[i].append(graph_time(fn))
+    for (name, _), t in zip(cases[1:], g):
+        print(f"  {name:44s} {_spread(t)}  (graph-replayed)")
+    from multimodal_eeg_fmri_amd.bridge_trainer import BridgeTrainer, synthetic_pairs
+    eeg, fmri = synthetic_pairs(32, 64, 1024, (32, 32, 32))
+    lab = torch.randint(0, 2, (32,), dtype=torch.int32, device="cuda")
+    trs = []
+    for classify in (False, True):
+        ops.set_seed_epoch(None)
+        torch.manual_seed(0)
+        tr = BridgeTrainer(eeg_channels=64, dropout=0.3, classify=classify).train()
+        args = (eeg, fmri, None, lab) if classify else (eeg, fmri)
+        tr.train_step(*args)
+        trs.append((tr, args))
+    times = ([], [])
+    for _ in range(rounds):
+        for i, (tr, args) in enumerate(trs):
+            times[i].append(timeit(lambda: tr.train_step(*args), iters=step_iters, rounds=1))
+    td, tc = statistics.median(times[0]), statistics.median(times[1])
+    print(f"C2 graph step B=32: default {_spread(times[0])}  classify {_spread(times[1])}  ({tc - td:+.1f} us, {100 * (tc / td - 1):+.2f} %)")
+
+
 def aug_case(B=32, C=64, T=1024, vol=(32, 32, 32), step_iters=30):
     """EEG augmentation (csrc/augment.hip) at the C2 shape: mm_stage_inputs alone against the plan + mm_stage_inputs_aug pair
     at p = 0.3 and p = 1 - issued eagerly (what a training loop pays: host issue included) and replayed from a hipGraph
@@ -720,6 +791,9 @@ def main():
         return
     if flt == "xai":
         xai_case()
+        return
+    if flt == "cls":
+        cls_case()
         return
     if flt == "aug":
         aug_case()
