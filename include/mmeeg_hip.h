@@ -555,6 +555,56 @@ int mm_bridge_cls_bwd(const float* save, const float* logits, const float* loss,
                       int N, int nhead, int C, float attn_p, uint32_t seed_attn, float gate_p, uint32_t seed_gate, float cls_p,
                       uint32_t seed_cls, const uint32_t* seed_epoch, hipStream_t stream);
 int mm_bridge_cls_ws_floats(int B, int N, int which, int* floats_host, hipStream_t stream);
+/* Feature half of the tabular fMRI net (fMRI_CODE/fmri_utils.py:23-108: ActivationEncoder, ConnectivityEncoder, the softmax-
+ * weighted concat and the `fusion` block of fMRIFusionNet; what the reference's bridge trains on, _test_bridge.py
+ * extract_fmri_features) in ONE forward and ONE backward launch, no float atomics, every sum in a fixed order.  Tensors are
+ * fp32; the Linear layers' sums over k, the batch statistics and the normalisation are accumulated in fp64 (a small
+ * batch's 1 / deviation multiplies their rounding into every gradient).
+ * x [B][A + C] = [activation | connectivity] (no alignment asked of A, C or any pointer); H = hidden_dim in {32, 64, 128}.
+ * Five Linear -> BatchNorm1d -> ReLU -> Dropout layers, in this order in every argument list, seed list and buffer:
+ * a1 (A -> 2H), a2 (2H -> H), c1 (C -> 2H), c2 (2H -> H), f ([wa * a2 | wc * c2] -> H), (wa, wc) = softmax of the two
+ * scalars.  Per layer: w [out][in], b, BatchNorm g / be, running mean / var, num_batches_tracked (int64, nullable).
+ * train = 1: batch statistics (2 <= B <= 256), running statistics updated with `momentum` (unbiased variance) and the
+ * counters incremented by the one workgroup that owns the feature.  train = 0: frozen BatchNorm (running statistics), any
+ * B >= 1, drop_p must be 0.  Dropout: five seeds in layer order; element index = b * width + f, the flat row-major index
+ * of the layer's (B, width) output.  out [B][H] = the fused feature.  save = 13 B H + 14 H floats for the backward: per
+ * layer the pre-activation (the Linear's output) and (but for f, whose output is `out`) the post-dropout output - a1 x|h
+ * (2 B H each), a2 x|h (B H each), c1, c2 alike, f x - then the layers' means (2H, H, 2H, H, H) and inverse standard
+ * deviations (alike) as the forward used them.
+ * tickets: THREE int32 words owned by the caller, zero before the first launch and left zero: 2 x (2H / 8) workgroups each
+ * own eight features of a first layer; the last arriver of a branch runs its second layer, the last of those two the
+ * fusion layer.  No workgroup waits for another. */
+int mm_fmri_tab_fwd(const float* x, int B, int A, int C, int H,
+                    const float* a1_w, const float* a1_b, const float* a1_g, const float* a1_be, float* a1_rm,
+                    float* a1_rv, int64_t* a1_nbt,
+                    const float* a2_w, const float* a2_b, const float* a2_g, const float* a2_be, float* a2_rm,
+                    float* a2_rv, int64_t* a2_nbt,
+                    const float* c1_w, const float* c1_b, const float* c1_g, const float* c1_be, float* c1_rm,
+                    float* c1_rv, int64_t* c1_nbt,
+                    const float* c2_w, const float* c2_b, const float* c2_g, const float* c2_be, float* c2_rm,
+                    float* c2_rv, int64_t* c2_nbt,
+                    const float* f_w, const float* f_b, const float* f_g, const float* f_be, float* f_rm, float* f_rv,
+                    int64_t* f_nbt,
+                    const float* activation_weight, const float* connectivity_weight, float* out, float* save,
+                    int* tickets, int train, float eps, float momentum, float drop_p, uint32_t seed_a1,
+                    uint32_t seed_a2, uint32_t seed_c1, uint32_t seed_c2, uint32_t seed_f, const uint32_t* seed_epoch,
+                    hipStream_t stream);
+/* its backward from dout [B][H] = d loss / d out (same train / eps / drop_p; the ReLU and dropout masks are read off the
+ * saved outputs).  fp32 but for the BatchNorm backward's sums over the batch, which run in fp64 on batch statistics formed
+ * again from the saved pre-activations (where BatchNorm passes little gradient the result is a small difference of large
+ * terms).  Every d_* destination (nullable) and dx [B][A + C] (nullable) is written with PLAIN stores by its only
+ * writer: ceil(A / 64) + ceil(C / 64) workgroups each own 64 input columns of a first layer (d w1[:, k], dx[:, k]), three
+ * more own the small matrices; each recomputes the B x (H | 2H) chain it needs in its own part of `scratch` =
+ * (ceil(A / 64) + ceil(C / 64) + 3) * 4 B H floats (no initialisation).  No ticket, no workgroup waits for another. */
+int mm_fmri_tab_bwd(const float* dout, const float* x, const float* out, const float* save, int B, int A, int C, int H,
+                    const float* a1_w, const float* a1_g, const float* a2_w, const float* a2_g, const float* c1_w,
+                    const float* c1_g, const float* c2_w, const float* c2_g, const float* f_w, const float* f_g,
+                    const float* activation_weight, const float* connectivity_weight, float* scratch, float* dx,
+                    float* d_a1_w, float* d_a1_b, float* d_a1_g, float* d_a1_be, float* d_a2_w, float* d_a2_b,
+                    float* d_a2_g, float* d_a2_be, float* d_c1_w, float* d_c1_b, float* d_c1_g, float* d_c1_be,
+                    float* d_c2_w, float* d_c2_b, float* d_c2_g, float* d_c2_be, float* d_f_w, float* d_f_b,
+                    float* d_f_g, float* d_f_be, float* d_activation_weight, float* d_connectivity_weight, int train,
+                    float eps, float drop_p, hipStream_t stream);
 /* batch-pairwise cosine-similarity matrix + symmetric InfoNCE, bit-reproducible (no float atomics).
  * Embeddings are packed rows [ze (N) | zf (N)]: z_all [Bg][2N] = the all-gathered global batch, this rank's
  * pairs at rows [row0, row0+B).  C[r][j] = ze_r . zf_j; e->f = row softmax of exp(logit_scale) C, f->e =

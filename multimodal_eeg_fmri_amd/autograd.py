@@ -831,6 +831,48 @@ class VolumeEncoderFn(_ModuleFn):
         return _ModuleFn._finish(ctx, bag, ctx.params, dx)
 
 
+def fmri_tab_bwd(bag: GradBag, sv: dict, dout: torch.Tensor):
+    """backward of ops._tab_forward_impl (train mode, or frozen BatchNorm), ONE launch (mm_fmri_tab_bwd); dout fp32
+    (B, hidden_dim).  Every parameter gradient is written into its `GradBag` target with PLAIN stores (the launch is the
+    target's only writer: one backward of an encoder per step).  Returns d / d x (B, A + C) when the forward was run
+    with need_dx, else None."""
+    m, x = sv["enc"], sv["x"]
+    B, A, C, H = sv["B"], m.activation_dim, m.connectivity_dim, m.hidden_dim
+    layers = m.layers()
+    t = bag.target
+    scratch = _empty((ops.fmri_tab_scratch_floats(B, A, C, H),), _F32, dout)
+    dx = _empty((B, A + C), _F32, dout) if sv.get("need_dx") else None
+    ins = [q for lin, bn in layers for q in (lin.weight, bn.weight)]
+    outs = [t(q) for lin, bn in layers for q in (lin.weight, lin.bias, bn.weight, bn.bias)]
+    _hip.call("mm_fmri_tab_bwd", dout.float().contiguous(), x, sv["out"], sv["save"], B, A, C, H, *ins, m.activation_weight,
+              m.connectivity_weight, scratch, dx, *outs, t(m.activation_weight), t(m.connectivity_weight),
+              int(sv["train"]), sv["eps"], float(sv["p"]))
+    return dx
+
+
+class FmriTabFn(_ModuleFn):
+    """`fMRITabularEncoder` on the autograd tape: train mode, or eval mode with a backward to follow (frozen BatchNorm:
+    running statistics, no dropout, no statistic update) - attribution and fine-tuning on a frozen encoder."""
+
+    @staticmethod
+    def run(m, x):
+        return FmriTabFn.apply(m, x, *_module_params(m))
+
+    @staticmethod
+    def forward(ctx, m, x, *params):
+        ctx.need_dx = bool(x.requires_grad)
+        out, saved = ops._tab_forward_impl(m, x, m.training, True, need_dx=ctx.need_dx)
+        ctx.saved, ctx.params = saved, params
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        bag = GradBag()
+        with deferred(bag, dout.device):
+            dx = fmri_tab_bwd(bag, ctx.saved, dout)
+        return _ModuleFn._finish(ctx, bag, ctx.params, dx)
+
+
 # ------------------------------------------------ projection bridge / loss
 def proj_head_bwd(bag: GradBag, s: dict, da: torch.Tensor, need_dx=True):
     lin, ln = s["seq"][0], s["seq"][1]

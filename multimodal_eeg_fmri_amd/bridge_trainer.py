@@ -33,11 +33,11 @@ import torch.nn as nn
 
 from . import _hip, dp, ops
 from .autograd import (GradBag, bridge_cls_bwd, contrastive_embed_bwd, contrastive_embed_bwd_da, deferred, erp_encoder_bwd,
-                       ffn_rows_bwd_fused, power_encoder_bwd, volume_encoder_bwd)
+                       ffn_rows_bwd_fused, fmri_tab_bwd, power_encoder_bwd, volume_encoder_bwd)
 from .bridge_checkpoint import TrainerCheckpointMixin
 from .bridge_utils import EEGfMRIContrastiveBridge, retrieval_metrics
 from .enhanced_models_v4 import EnhancedERPEncoder
-from .fmri_utils import fMRIVolumeEncoder3D
+from .fmri_utils import fMRITabularEncoder, fMRIVolumeEncoder3D
 from .optim import FlatBucket
 
 
@@ -47,7 +47,8 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
                  weight_decay: float = 1e-4, grad_clip: float = 1.0, betas=(0.9, 0.999),
                  eps: float = 1e-8, group=None, device="cuda", mode: str = "graph", eeg_encoder: Optional[nn.Module] = None,
                  num_heads: int = 4, num_layers: int = 2, augment=None, loss: str = "infonce",
-                 classify: bool = False, ce_weight: float = 1.0, class_weight=None, num_classes: int = 2):
+                 classify: bool = False, ce_weight: float = 1.0, class_weight=None, num_classes: int = 2,
+                 fmri_encoder: Optional[nn.Module] = None):
         """``eeg_encoder``: the EEG branch when it is not the default ``EnhancedERPEncoder(eeg_channels, hidden_dim,
         num_layers, num_heads, dropout)`` - an ``EnhancedPowerEncoder`` (enhanced_models_v4.py:196-285) or a
         ``MultiScaleSTFTPowerEncoder`` (BASELINE config #5: raw EEG -> multi-scale STFT power -> a4); it must end in
@@ -62,8 +63,22 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
         ``classify``: also train the bridge's classification branch (cross attention, fusion, classifier) on class labels
         with ``ce_weight`` x the (``class_weight``-ed, (num_classes,) floats) cross-entropy: `train_step(..., labels=)`,
         three more launches per step (mm_bridge_cls_fwd, mm_bridge_cls_bwd).  ``num_classes`` sizes
-        the bridge's classifier on any trainer (`predict`)."""
+        the bridge's classifier on any trainer (`predict`).
+        ``fmri_encoder``: None (default) = the voxel encoder ``fMRIVolumeEncoder3D(1, fmri_dim)`` on (B, 1, D, H, W)
+        volumes; an ``fMRITabularEncoder`` = the reference's own fMRI input, ROI activation statistics and flattened
+        connectivity as one (B, activation_dim + connectivity_dim) tensor ``[activation | connectivity]`` - the branch is
+        then two launches per step (mm_fmri_tab_fwd, mm_fmri_tab_bwd), train-mode batches of
+        2..256 rows; its ``hidden_dim`` must equal ``fmri_dim``.  Everything else - losses, groups, classify, augment,
+        embed / evaluate / retrieval / predict / explain, checkpoints, `fit`, the packed host-fed path - is the same."""
         super().__init__()
+        if fmri_encoder is not None:
+            if not isinstance(fmri_encoder, fMRITabularEncoder):
+                raise TypeError(f"BridgeTrainer: fmri_encoder must be an fMRITabularEncoder or None (the voxel encoder), got "
+                                f"{type(fmri_encoder).__name__}")
+            if fmri_encoder.hidden_dim != fmri_dim:
+                raise ValueError(f"BridgeTrainer: fmri_dim={fmri_dim} but the fMRITabularEncoder ends in "
+                                 f"{fmri_encoder.hidden_dim} features")
+        self._fmri_kind = "volume" if fmri_encoder is None else "tabular"
         self.classify, self.ce_weight, self.num_classes = bool(classify), float(ce_weight), int(num_classes)
         cw = None
         if class_weight is not None:
@@ -97,7 +112,7 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
             self._eeg_kind = "power"
         else:
             raise TypeError(f"BridgeTrainer: no tape for an EEG encoder of type {type(self.eeg_encoder).__name__}")
-        self.fmri_encoder = fMRIVolumeEncoder3D(1, fmri_dim, dropout=dropout)
+        self.fmri_encoder = fMRIVolumeEncoder3D(1, fmri_dim, dropout=dropout) if fmri_encoder is None else fmri_encoder
         self.head = EEGfMRIContrastiveBridge(hidden_dim, fmri_dim, bridge_dim, dropout, loss=loss, num_classes=num_classes)
         self.loss = loss
         self.to(device)
@@ -205,6 +220,13 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
             raise ValueError(f"{who}: labels= needs a trainer built with classify=True")
         return ops.class_labels(labels, B, self.num_classes, device, who)
 
+    def _check_fmri(self, shape, training: bool, who: str):
+        """the fMRI batch's shape, before the first launch of a step (or of its capture): ``ValueError`` otherwise"""
+        if self._fmri_kind == "volume":
+            ops.check_volume_shape(shape)
+        else:
+            ops.fmri_tab_check(self.fmri_encoder, shape, training, f"{who} (tabular fMRI encoder)")
+
     def _result(self, scal) -> Dict[str, torch.Tensor]:
         """the dict a step returns: views of the trainer's result words"""
         out = {"loss": scal[0], "top1_e2f": scal[1], "top1_f2e": scal[2]}
@@ -226,7 +248,9 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
         ``labels``: (B,) integer class labels (``ops.class_labels``), required by - and only taken by - a trainer built
         with ``classify=True``: the step then also trains the classification branch and returns ``contrastive_loss``,
         ``ce_loss``, ``cls_correct`` and ``loss`` = contrastive_loss + ce_weight * ce_loss."""
-        ops.check_volume_shape(fmri.shape)                 # before the first launch of the step (or of its capture)
+        self._check_fmri(fmri.shape, True, "train_step")   # before the first launch of the step (or of its capture)
+        if self._fmri_kind == "tabular" and fmri.is_cuda:
+            self.fmri_encoder.tickets(fmri.device)         # the forward launch's words exist before any capture
         gid = ops.group_ids(groups, eeg.shape[0], None if self.mode == "graph" else eeg.device, "train_step")
         lab = self._labels(labels, eeg.shape[0], None if self.mode == "graph" else eeg.device, "train_step")
         if lab is not None and self._cls_ticket is None:       # this trainer's own word, allocated before any capture
@@ -327,7 +351,10 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
         def fmri_branch():
             with torch.cuda.stream(self._side):
                 self._stamp(3)
-                out = ops._vol_forward_impl(self.fmri_encoder, fmri, True, True)
+                if self._fmri_kind == "tabular":         # one launch
+                    out = ops._tab_forward_impl(self.fmri_encoder, fmri, True, True)
+                else:
+                    out = ops._vol_forward_impl(self.fmri_encoder, fmri, True, True)
                 self._stamp(4)
             return out
         if self._fmri_longer:
@@ -350,6 +377,8 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
     def _fmri_is_longer(fmri) -> bool:
         """the voxel branch outlasts the EEG chain (config #4: 64 x 64 x 48 = 6 x the voxels of 32^3, 1.4 ms of kernels
         against 1.1 ms): its stream then takes no work from the chain and is issued first.  MM_FMRI_LONGER=0/1 overrides."""
+        if fmri.dim() != 5:                            # the tabular branch is two launches: never the longer one
+            return False
         env = os.environ.get("MM_FMRI_LONGER")
         if env is not None:
             return env == "1"
@@ -443,7 +472,10 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
                     self._stamp(9)
                     bag_f = GradBag()                    # the fMRI branch flushes its own reductions on ITS stream,
                     with deferred(bag_f, dz.device):     # hidden beside the rest of the EEG backward
-                        volume_encoder_bwd(bag_f, sv_f, dff)
+                        if self._fmri_kind == "tabular":     # one launch, plain stores into the bucket's fMRI range
+                            fmri_tab_bwd(bag_f, sv_f, dff)
+                        else:
+                            volume_encoder_bwd(bag_f, sv_f, dff)
                     self._stamp(10)
                     if reduce and hand:
                         self._reduce_group("fmri")
@@ -526,6 +558,8 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
         dev = eeg.device
         if self._cls_ticket is not None:
             self._cls_ticket.zero_()                      # (a launch that died mid-count would have left it non-zero)
+        if self._fmri_kind == "tabular":
+            self.fmri_encoder.tickets(dev).zero_()
         world = self.world
         c = {"epoch": torch.zeros(1, dtype=torch.int32, device=dev)}
         # the step's static inputs are views of ONE flat buffer `c["in"]` = [EEG operand | fMRI volumes fp32 | group ids
@@ -881,6 +915,7 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
         """eval-mode loss and in-batch top-1 of one batch (``groups``, ``labels``: as in `train_step`; with labels also
         ``contrastive_loss``, ``ce_loss`` and ``cls_correct``, and ``loss`` is their weighted sum)"""
         lab = self._labels(labels, eeg.shape[0], eeg.device, "evaluate")
+        self._check_fmri(fmri.shape, False, "evaluate")
         was = self.training
         self.eval()
         ops.weights_changed()                      # graph replays bypass the python-side version counter
@@ -922,7 +957,7 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
         try:
             outs = []
             for x, y in zip(self._chunks(eeg, batch_size, dev), self._chunks(fmri, batch_size, dev)):
-                ops.check_volume_shape(y.shape)
+                self._check_fmri(y.shape, False, "predict")
                 fe, ff = self._encode(x, y)
                 _, sv_h = ops.contrastive_embed_impl(br, fe, ff, False)
                 outs.append(ops.bridge_cls_forward_impl(br, sv_h, False)[:3])
@@ -1002,7 +1037,8 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
         batch mean, batched by ``ops.integrated_gradients``; ``chunk_steps`` overrides its memory rule), "gradient"
         (|d score / d input|) or "gradient_x_input".
         -> {"eeg": (B, C, T), "eeg_channels": (B, C) = the mean over time, "fmri": (B, 1, D, H, W), "scores": (B,)}, fp32
-        on the trainer's device.  The training state is left as it was, bit for bit: parameters, Adam moments, optimizer
+        on the trainer's device; with a tabular fMRI encoder "fmri" is (B, A + C) and "fmri_activation" (B, A) /
+        "fmri_connectivity" (B, C) are views of it.  The training state is left as it was, bit for bit: parameters, Adam moments, optimizer
         words, BatchNorm buffers, the gradient bucket, the dropout seed counter and a captured graph (no seed is drawn in
         eval mode; the gradient bucket, into which the backward kernels add their parameter gradients, is restored).
         Costs and side effects to know: the existing module-level backward functions are reused whole, so every chunk also
@@ -1021,7 +1057,10 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
         steps = int(n_steps) if ig else 1
         attr_e, chan = ops.xai_finish(eeg, bases[0], accs[0], steps, method, channels=True)
         attr_f, _ = ops.xai_finish(fmri, bases[1], accs[1], steps, method)
-        return {"eeg": attr_e, "eeg_channels": chan, "fmri": attr_f, "scores": scores}
+        out = {"eeg": attr_e, "eeg_channels": chan, "fmri": attr_f, "scores": scores}
+        if self._fmri_kind == "tabular":                  # views of the (B, A + C) attribution
+            out["fmri_activation"], out["fmri_connectivity"] = self.fmri_encoder.split(attr_f)
+        return out
 
     def _pair_gradients(self, eeg, fmri, steps: int, baseline: Optional[str], chunk_steps: Optional[int] = None):
         """the signed sums behind `explain`: -> (eeg, fmri on the device, [baseline or None] x 2, [sum over the ``steps``
@@ -1031,7 +1070,7 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
             raise ValueError(f"explain: {eeg.shape[0]} EEG epochs but {fmri.shape[0]} fMRI volumes")
         if steps < 1:
             raise ValueError("explain: n_steps must be >= 1")
-        ops.check_volume_shape(fmri.shape)
+        self._check_fmri(fmri.shape, False, "explain")
         dev = self._scal.device
         eeg = eeg.detach().to(dev).float().contiguous()
         fmri = fmri.detach().to(dev).float().contiguous()
@@ -1171,3 +1210,39 @@ def synthetic_subject_pairs(subjects: int, per_subject: int, eeg_channels: int =
     eeg = (z_ep @ A_e.t()).unsqueeze(-1) * 0.5 + torch.randn(subjects * per_subject, eeg_channels, samples, generator=g)
     fmri = fmri_s[groups]
     return eeg.to(device), fmri.to(device), groups.to(torch.int32).to(device)
+
+
+def _tabular_maps(activation_dim: int, connectivity_dim: int, eeg_channels: int, latent: int):
+    gm = torch.Generator().manual_seed(99)
+    A_e = torch.randn(eeg_channels, latent, generator=gm)
+    A_f = torch.randn(activation_dim + connectivity_dim, latent, generator=gm) / latent ** 0.5
+    return A_e, A_f
+
+
+def synthetic_tabular_pairs(batch: int, eeg_channels: int = 64, samples: int = 1024, activation_dim: int = 100,
+                            connectivity_dim: int = 200, seed: int = 1234, device="cuda", latent: int = 16):
+    """``synthetic_pairs`` with the reference's tabular fMRI input: EEG = A_e z broadcast over time + N(0,1), fMRI =
+    A_f z + N(0,1) as one (batch, activation_dim + connectivity_dim) row ``[activation | connectivity]``."""
+    g = torch.Generator().manual_seed(seed)
+    A_e, A_f = _tabular_maps(activation_dim, connectivity_dim, eeg_channels, latent)
+    z = torch.randn(batch, latent, generator=g)
+    eeg = (z @ A_e.t()).unsqueeze(-1) * 0.5 + torch.randn(batch, eeg_channels, samples, generator=g)
+    fmri = z @ A_f.t() + torch.randn(batch, activation_dim + connectivity_dim, generator=g)
+    return eeg.to(device), fmri.to(device)
+
+
+def synthetic_tabular_subject_pairs(subjects: int, per_subject: int, eeg_channels: int = 64, samples: int = 1024,
+                                    activation_dim: int = 100, connectivity_dim: int = 200, seed: int = 1234, device="cuda",
+                                    latent: int = 16, epoch_noise: float = 0.5):
+    """``synthetic_subject_pairs`` with tabular fMRI rows: one latent and one fMRI row per subject, repeated for each of its
+    EEG epochs; pairs are subject-major.  -> (eeg (S*E, C, T), fmri (S*E, A + C), groups int32 (S*E,))."""
+    if subjects < 1 or per_subject < 1:
+        raise ValueError("synthetic_tabular_subject_pairs: need subjects >= 1 and per_subject >= 1")
+    g = torch.Generator().manual_seed(seed)
+    A_e, A_f = _tabular_maps(activation_dim, connectivity_dim, eeg_channels, latent)
+    z = torch.randn(subjects, latent, generator=g)
+    fmri_s = z @ A_f.t() + torch.randn(subjects, activation_dim + connectivity_dim, generator=g)
+    groups = torch.arange(subjects).repeat_interleave(per_subject)
+    z_ep = z[groups] + epoch_noise * torch.randn(subjects * per_subject, latent, generator=g)
+    eeg = (z_ep @ A_e.t()).unsqueeze(-1) * 0.5 + torch.randn(subjects * per_subject, eeg_channels, samples, generator=g)
+    return eeg.to(device), fmri_s[groups].to(device), groups.to(torch.int32).to(device)

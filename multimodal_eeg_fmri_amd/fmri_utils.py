@@ -3,6 +3,8 @@
 * ``ActivationEncoder`` / ``ConnectivityEncoder`` / ``fMRIFusionNet`` mirror the
   reference's tabular model (``fMRI_CODE/fmri_utils.py:23-108`` ==
   ``fMRI_CODE/run_fmri_v11.py:272-424``): same names, signatures, state_dict.
+* ``fMRITabularEncoder`` is the feature half of ``fMRIFusionNet`` (what the reference's bridge trains on) as one
+  forward and one backward launch: the fMRI branch of ``BridgeTrainer(fmri_encoder=...)``.
 * ``fMRIVolumeEncoder3D`` is the north-star 3-D voxel encoder.  The reference
   has **no** volume code, so this class is an extension defined
   here in the reference's Conv->BN->GELU->Pool idiom and ending in the 64-d
@@ -69,6 +71,77 @@ class fMRIFusionNet(nn.Module):
         with torch.no_grad():
             w = torch.softmax(torch.stack([self.activation_weight, self.connectivity_weight]), dim=0)
         return {"activation": w[0].item(), "connectivity": w[1].item()}
+
+
+class fMRITabularEncoder(nn.Module):
+    """The feature half of ``fMRIFusionNet`` - the two ``_mlp`` encoders, ``activation_weight`` / ``connectivity_weight``
+    and ``fusion`` - as ONE forward and ONE backward launch (csrc/fmri_tab.hip): what the
+    reference's bridge is trained on (``extract_fmri_features`` of _test_bridge.py: the 64-d ``fused`` feature).
+
+    ``forward(x)``: x (B, activation_dim + connectivity_dim) fp32 laid out ``[activation | connectivity]`` (one tensor,
+    so that it travels wherever a trainer's ``fmri`` tensor does; `split` gives the two halves) -> (B, hidden_dim), equal
+    to ``fMRIFusionNet(act, conn, return_features=True)[1]`` at the same state.  ``state_dict`` keys are exactly
+    ``fMRIFusionNet``'s without ``head.*``: ``load_state_dict(net.state_dict(), strict=False)`` reports only those as
+    unexpected, and `from_fusion_net` copies a trained net.
+    Train mode: batch statistics (2 <= B <= 256), running mean / unbiased running var updated with momentum 0.1 and
+    ``num_batches_tracked`` incremented, as ``nn.BatchNorm1d``; B < 2 raises ``ValueError`` as torch does.  Eval mode:
+    running statistics, any B >= 1.  ``hidden_dim`` in {32, 64, 128}; the two input dims >= 1, no alignment asked."""
+    HIDDEN_DIMS = (32, 64, 128)
+    MAX_TRAIN_BATCH = 256
+
+    def __init__(self, activation_dim: int, connectivity_dim: int, hidden_dim: int = 64, dropout: float = 0.3):
+        super().__init__()
+        if hidden_dim not in self.HIDDEN_DIMS:
+            raise ValueError(f"fMRITabularEncoder: hidden_dim must be one of {self.HIDDEN_DIMS}, got {hidden_dim}")
+        if activation_dim < 1 or connectivity_dim < 1:
+            raise ValueError(f"fMRITabularEncoder: activation_dim and connectivity_dim must be >= 1, got {activation_dim}, "
+                             f"{connectivity_dim}")
+        if not 0.0 <= dropout < 1.0:
+            raise ValueError(f"fMRITabularEncoder: dropout must be in [0, 1), got {dropout}")
+        self.activation_dim, self.connectivity_dim, self.hidden_dim = int(activation_dim), int(connectivity_dim), int(hidden_dim)
+        self.activation_encoder = ActivationEncoder(activation_dim, hidden_dim, dropout)
+        self.connectivity_encoder = ConnectivityEncoder(connectivity_dim, hidden_dim, dropout)
+        self.fusion = nn.Sequential(nn.Linear(hidden_dim * 2, hidden_dim), nn.BatchNorm1d(hidden_dim),
+                                    nn.ReLU(), nn.Dropout(dropout))
+        self.activation_weight = nn.Parameter(torch.ones(1) * 0.5)
+        self.connectivity_weight = nn.Parameter(torch.ones(1) * 0.5)
+        self.drop_p = dropout
+        self._tickets = None          # the forward launch's three int32 words (not a buffer: the state dict keeps its keys)
+
+    @classmethod
+    def from_fusion_net(cls, net: "fMRIFusionNet") -> "fMRITabularEncoder":
+        """a copy of a (trained) ``fMRIFusionNet``'s feature half on its device, in its train / eval mode"""
+        lin = net.activation_encoder.encoder[0], net.connectivity_encoder.encoder[0], net.fusion[0]
+        enc = cls(lin[0].in_features, lin[1].in_features, lin[2].out_features, net.drop_p)
+        enc.to(lin[0].weight.device)
+        res = enc.load_state_dict(net.state_dict(), strict=False)
+        assert not res.missing_keys and all(k.startswith("head.") for k in res.unexpected_keys), res
+        return enc.train(net.training)
+
+    @property
+    def in_dim(self) -> int:
+        return self.activation_dim + self.connectivity_dim
+
+    def split(self, x: torch.Tensor):
+        """(B, activation_dim + connectivity_dim) -> (activation, connectivity) views"""
+        return x[..., :self.activation_dim], x[..., self.activation_dim:]
+
+    def layers(self):
+        """[(Linear, BatchNorm1d)] x 5 in the kernels' order: a1, a2, c1, c2, f"""
+        a, c = self.activation_encoder.encoder, self.connectivity_encoder.encoder
+        return [(a[0], a[1]), (a[4], a[5]), (c[0], c[1]), (c[4], c[5]), (self.fusion[0], self.fusion[1])]
+
+    def tickets(self, device) -> torch.Tensor:
+        """the forward launch's ticket words on ``device`` (zero between launches); a trainer asks for them before it
+        captures a step"""
+        if self._tickets is None or self._tickets.device != torch.device(device):
+            self._tickets = torch.zeros(4, dtype=torch.int32, device=device)
+        return self._tickets
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        return ops.fmri_tab_forward(self, x)
+
+    get_fusion_weights = fMRIFusionNet.get_fusion_weights
 
 
 class _fMRISingleBranch(nn.Module):

@@ -1639,6 +1639,64 @@ def fmri_fusion_forward(m, activation, connectivity):
     return out, fused
 
 
+# ------------------------------------------- tabular fMRI encoder (fp32, csrc/fmri_tab.hip: one launch each way)
+def fmri_tab_check(m, shape, training: bool, who: str = "fMRITabularEncoder"):
+    """the input of an `fMRITabularEncoder`, checked before any launch: (B, activation_dim + connectivity_dim); train mode
+    (batch statistics) 2 <= B <= 256 - B = 1 has no variance, as torch says, and one workgroup holds a feature's whole
+    batch - eval mode any B >= 1"""
+    if len(shape) != 2 or shape[1] != m.in_dim:
+        raise ValueError(f"{who}: expected a (B, {m.in_dim}) batch [activation ({m.activation_dim}) | connectivity "
+                         f"({m.connectivity_dim})], got shape {tuple(shape)}")
+    B = shape[0]
+    if training and not 2 <= B <= m.MAX_TRAIN_BATCH:
+        raise ValueError(f"{who}: train mode (batch statistics) takes 2 <= B <= {m.MAX_TRAIN_BATCH} rows, got {B}")
+    if B < 1:
+        raise ValueError(f"{who}: empty batch")
+
+
+def fmri_tab_save_floats(B: int, H: int) -> int:
+    """floats of mm_fmri_tab_fwd's save buffer (include/mmeeg_hip.h)"""
+    return 13 * B * H + 14 * H
+
+
+def fmri_tab_scratch_floats(B: int, A: int, C: int, H: int) -> int:
+    """floats of mm_fmri_tab_bwd's scratch: 4 B H per workgroup"""
+    return ((A + 63) // 64 + (C + 63) // 64 + 3) * 4 * B * H
+
+
+def _tab_forward_impl(m, x: torch.Tensor, training: bool, save=None, need_dx: bool = False):
+    """`fMRITabularEncoder` forward, ONE launch (mm_fmri_tab_fwd).  ``training`` False = frozen BatchNorm (running
+    statistics, no dropout, nothing updated).  What a backward needs is always kept (13 B H + 14 H floats; ``save`` is accepted
+    for symmetry with the other encoders).  Train mode draws five dropout seeds, in layer order.  -> (fused (B, H), saved)"""
+    fmri_tab_check(m, x.shape, training)
+    x = x.float().contiguous()
+    B, A, C, H = x.shape[0], m.activation_dim, m.connectivity_dim, m.hidden_dim
+    p = float(m.drop_p) if training else 0.0
+    seeds = tuple(_next_seed() for _ in range(5)) if p > 0 else (0,) * 5
+    out = _empty((B, H), _F32, x)
+    sv = _empty((fmri_tab_save_floats(B, H),), _F32, x)
+    layers = m.layers()
+    bn0 = layers[0][1]
+    args = []
+    for lin, bn in layers:
+        assert bn.eps == bn0.eps and bn.momentum == bn0.momentum
+        args += [lin.weight, lin.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked]
+    _hip.call("mm_fmri_tab_fwd", x, B, A, C, H, *args, m.activation_weight, m.connectivity_weight, out, sv,
+              m.tickets(x.device), int(training), float(bn0.eps), float(bn0.momentum), p, *seeds, EP())
+    return out, dict(enc=m, x=x, out=out, save=sv, B=B, train=bool(training), p=p, seeds=seeds, need_dx=need_dx,
+                     eps=float(bn0.eps))
+
+
+def fmri_tab_forward(m, x: torch.Tensor) -> torch.Tensor:
+    fmri_tab_check(m, x.shape, m.training)
+    _need_gpu(x)
+    if m.training or attribution_active() or _wants_grad(m, x):    # (eval mode on the tape: frozen BatchNorm, no dropout)
+        from .autograd import FmriTabFn
+        return FmriTabFn.run(m, x)
+    with torch.no_grad():
+        return _tab_forward_impl(m, x, False)[0]
+
+
 def conn_encoder_forward(m, x):
     _need_gpu(x)
     if m.training or attribution_active():                   # (attribution: eval mode on the tape - frozen BatchNorm, no dropout)

@@ -502,6 +502,63 @@ def cls_case(B=32, N=128, step_iters=30, rounds=5):
     print(f"C2 graph step B=32: default {_spread(times[0])}  classify {_spread(times[1])}  ({tc - td:+.1f} us, {100 * (tc / td - 1):+.2f} %)")
 
 
+def tabfmri_case(step_iters=30, rounds=5):
+    """the tabular fMRI encoder.  (a) forward + backward of the feature path at three shapes, train mode (dropout 0.3): the
+    two fused launches (mm_fmri_tab_fwd, mm_fmri_tab_bwd) against the path they stand beside - `fMRIFusionNet`'s train-mode
+    ``return_features`` forward (ops.fmri_fusion_forward, the small_autograd chain) + its autograd backward from the
+    fused feature - in the same run, interleaved rounds, median [min .. max]; eager launches from the host (stream
+    time), then the fused pair graph-replayed.  (b) the C2-shaped graph step (B = 32, 64 ch x 1024) with the tabular
+    branch at (100, 200) against the volume branch at 32^3."""
+    from multimodal_eeg_fmri_amd import autograd
+    from multimodal_eeg_fmri_amd.fmri_utils import fMRIFusionNet, fMRITabularEncoder
+    for B, A, C, H in ((32, 100, 200, 64), (32, 500, 4096, 64), (256, 100, 200, 64)):
+        torch.manual_seed(0)
+        net = fMRIFusionNet(A, C, hidden_dim=H, dropout=0.3).cuda().train()
+        enc = fMRITabularEncoder.from_fusion_net(net).train()
+        x = torch.randn(B, A + C, device="cuda")
+        act, conn = (t.contiguous() for t in enc.split(x))
+        R = torch.randn(B, H, device="cuda")
+        feat = [q for n, q in net.named_parameters() if not n.startswith("head.")]
+
+        def existing():
+            for q in feat:
+                q.grad = None
+            net(act, conn, return_features=True)[1].backward(R)
+
+        bag = autograd.GradBag()
+
+        def fused():
+            with torch.no_grad():
+                _, sv = ops._tab_forward_impl(enc, x, True, True)
+                autograd.fmri_tab_bwd(bag, sv, R)
+
+        cases = [("fMRIFusionNet train fwd (features) + autograd bwd", existing), ("fused pair (2 launches)", fused)]
+        times = [[] for _ in cases]
+        for _ in range(rounds):
+            for i, (_, fn) in enumerate(cases):
+                times[i].append(timeit(fn, iters=step_iters, rounds=1))
+        g = [graph_time(fused) for _ in range(rounds)]
+        print(f"tabular fMRI feature path B={B} A={A} C={C} H={H} (fwd + bwd):")
+        for (name, _), t in zip(cases, times):
+            print(f"  {name:52s} {_spread(t)}")
+        print(f"  {'fused pair, graph-replayed':52s} {_spread(g)}")
+    from multimodal_eeg_fmri_amd.bridge_trainer import BridgeTrainer, synthetic_pairs, synthetic_tabular_pairs
+    trs = []
+    for tab in (False, True):
+        ops.set_seed_epoch(None)
+        torch.manual_seed(0)
+        enc = fMRITabularEncoder(100, 200, 64, dropout=0.3) if tab else None
+        tr = BridgeTrainer(eeg_channels=64, dropout=0.3, fmri_encoder=enc).train()
+        args = synthetic_tabular_pairs(32, 64, 1024, 100, 200) if tab else synthetic_pairs(32, 64, 1024, (32, 32, 32))
+        tr.train_step(*args)
+        trs.append((tr, args))
+    times = ([], [])
+    for _ in range(rounds):
+        for i, (tr, args) in enumerate(trs):
+            times[i].append(timeit(lambda: tr.train_step(*args), iters=step_iters, rounds=1))
+    print(f"C2 graph step B=32: volume branch (32^3) {_spread(times[0])}  tabular branch (100, 200) {_spread(times[1])}")
+
+
 def aug_case(B=32, C=64, T=1024, vol=(32, 32, 32), step_iters=30):
     """EEG augmentation (csrc/augment.hip) at the C2 shape: mm_stage_inputs alone against the plan + mm_stage_inputs_aug pair
     at p = 0.3 and p = 1 - issued eagerly (what a training loop pays: host issue included) and replayed from a hipGraph
@@ -794,6 +851,9 @@ def main():
         return
     if flt == "cls":
         cls_case()
+        return
+    if flt == "tabfmri":
+        tabfmri_case()
         return
     if flt == "aug":
         aug_case()
