@@ -651,6 +651,37 @@ int mm_sigmoid_loss_own_rows(const float* z_all, const int* gid_all, const float
                              float* scal5, float* dz_local, float* ws, int B, int Bg, int N, int row0,
                              hipStream_t stream);
 int mm_sigmoid_loss_ws_floats(int B, int Bg, int* floats_host, hipStream_t stream);
+/* symmetric InfoNCE against the batch AND a cross-batch memory of earlier embeddings (csrc/clip_bank.hip; Wang et al.,
+ * "Cross-Batch Memory for Embedding Learning").  All storage is the caller's device memory, allocated before any capture:
+ *   bank     fp32  [K][2N]  rows [ze | zf], L2-normalised, exactly as z (keys only, constants: no loss, no gradient)
+ *   bank_gid int32 [K]      the rows' group ids (nullable; required when gid is given)
+ *   state    int32 [4]      {head, filled, pushes, 0}; zero them to empty the bank
+ * z [B][2N] the own rows, gid int32 [B] or NULL, logit_scale one device float (ln s).  n = (state.pushes >= warmup) ?
+ * state.filled : 0 is read ON THE DEVICE, so the same launch arguments (and a captured graph) serve every fill level;
+ * valid bank rows are ring slots [0, n) (the ring never wraps before it is full).  For own row r, s = exp(logit_scale):
+ *   e->f keys {zf_j : j < B} u {bank_k.zf : k < n}, query ze_r;   f->e keys {ze_j} u {bank_k.ze}, query zf_r
+ *   P(r): gid NULL: the batch key r only (no bank row is ever a positive); else every batch or bank key whose id = gid_r
+ *   l_dir(r) = LSE_{all keys}(s q.key) - LSE_{P(r)}(s q.key)        loss = (1/B) sum_r (l_e2f(r) + l_f2e(r)) / 2
+ * ("log of the positive mass", as mm_clip_loss_own_rows_grouped; with n = 0 it is that kernel's loss at Bg = B).
+ * dz [B][2N] (nullable, plain stores) = d loss / d z: ze_r's query term over batch and bank keys + its key term from every
+ * batch fMRI query's f->e softmax, zf_r symmetric; bank rows get nothing and are never written.  scal4 = {loss, top1 e->f,
+ * top1 f->e, d loss / d logit_scale} (plain stores); top-1 counts row r when its best positive reaches the maximum over
+ * all keys, bank included (a tie FOR it).  All fp32, no float atomics, every sum in a fixed order (per-key-chunk partials
+ * combined in chunk order): same inputs + same state -> bit-identical outputs.  Rows at or beyond n are never read (their
+ * memory may hold anything, NaN included).  ws = mm_clip_bank_ws_floats(B, K, N) floats (the 2 B (B + K) scores and the
+ * chunk partials), no initialisation.  N % 4 == 0, 1 <= B <= K, warmup >= 0; z, bank, dz, ws 16-byte aligned.  Two
+ * launches on `stream`, both grids sized by the capacity K; no workgroup waits for another.
+ * Extension: the reference has no contrastive trainer. */
+int mm_clip_bank_loss(const float* z, const int* gid, const float* bank, const int* bank_gid, const int* state,
+                      const float* logit_scale, float* scal4, float* dz, float* ws, int B, int K, int N, int warmup,
+                      hipStream_t stream);
+/* the B rows of z (and their ids, when gid is given) into ring slots (head + i) mod K, THEN head = (head + B) mod K,
+ * filled = min(filled + B, K), pushes += 1.  One launch of ONE workgroup: every thread reads the words, the rows are
+ * copied, and thread 0 advances the words behind the workgroup's barrier (plain stores).  Same shape rules. */
+int mm_clip_bank_push(const float* z, const int* gid, float* bank, int* bank_gid, int* state, int B, int K, int N,
+                      hipStream_t stream);
+/* host-only: floats of mm_clip_bank_loss's workspace */
+int mm_clip_bank_ws_floats(int B, int K, int N, int* floats_host, hipStream_t stream);
 
 /* ---- gallery-scale retrieval (csrc/retrieval.hip) ---------------------------
  * For each query row q of Q [Nq][D] against gallery G [Ng][D] (fp32, row-major, 16-byte aligned; callers pass

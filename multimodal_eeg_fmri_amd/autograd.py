@@ -995,6 +995,29 @@ class ClipLossFn(torch.autograd.Function):
         return dz * g_loss, (scal[3] * g_loss).reshape(()), None, None
 
 
+class ClipBankLossFn(torch.autograd.Function):
+    """`ClipLossFn` against the batch and a cross-batch memory (``mm_clip_bank_loss``): ``bank`` (an `ops.ClipBank`) and its
+    state words are constants of the tape - bank rows carry no loss and receive no gradient.  Single process only."""
+
+    @staticmethod
+    def forward(ctx, z, logit_scale, bank, gid=None, warmup=0):
+        z = z.contiguous().float()
+        B, N2 = z.shape
+        need_grad = z.requires_grad or logit_scale.requires_grad
+        scal = _empty((4,), _F32, z)
+        dz = _empty((B, N2), _F32, z) if need_grad else None
+        ls = logit_scale.detach().reshape(1).float().contiguous()
+        ops.clip_bank_loss(z.detach(), gid, bank, ls, scal, dz, warmup)
+        if need_grad:
+            ctx.save_for_backward(dz, scal)
+        return scal[0].clone(), scal[1].clone(), scal[2].clone()
+
+    @staticmethod
+    def backward(ctx, g_loss, g_a, g_b):
+        dz, scal = ctx.saved_tensors
+        return dz * g_loss, (scal[3] * g_loss).reshape(()), None, None, None
+
+
 class SigmoidLossFn(torch.autograd.Function):
     """`ClipLossFn` for the pairwise sigmoid loss (``mm_sigmoid_loss_own_rows``): the same gather of embeddings and ids,
     the same own-rows gradient; one more learnable scalar, ``logit_bias``."""

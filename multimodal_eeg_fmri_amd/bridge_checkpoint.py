@@ -12,7 +12,9 @@ The file is the container of the reference's loops and of `FlexibleTrainer.save_
   model's shapes, the head count of every transformer block, the world size, the bucket layout, the dropout stream,
   the state of `fit`, - only for a trainer with an augmenter - ``augment``: its parameters and the step index, -
   only for a trainer of the pairwise sigmoid loss - ``loss`` = ``"sigmoid"`` (absent: InfoNCE), and - only for a trainer
-  built with ``classify=True`` - ``classify`` = ``{ce_weight, num_classes, class_weight}``.
+  built with ``classify=True`` - ``classify`` = ``{ce_weight, num_classes, class_weight}``, and - only for a trainer with
+  a cross-batch memory (``bank_size > 0``) - ``bank`` = ``{size, warmup, grouped, state, rows, ids}``: the ring's words,
+  rows and group ids (``rows`` / ``ids`` None before the first training step).
 
 The step itself is untouched: saving and loading are copies, `fit` only calls `train_step` and `embed`.
 
@@ -131,6 +133,15 @@ class TrainerCheckpointMixin:
         return {"ce_weight": float(self.ce_weight), "num_classes": int(self.num_classes),
                 "class_weight": None if cw is None else [float(v) for v in cw.detach().cpu()]}
 
+    def checkpoint_bank(self) -> Optional[dict]:
+        """``bridge_trainer_state["bank"]``: None unless the trainer was built with bank_size > 0"""
+        if not getattr(self, "_bank_size", 0):
+            return None
+        bank = self._bank
+        return {"size": int(self._bank_size), "warmup": int(self._bank_warmup), "grouped": self._bank_grouped,
+                "state": [0, 0, 0, 0] if bank is None else [int(v) for v in bank.state.detach().cpu()],
+                "rows": None if bank is None else _cpu(bank.bank), "ids": None if bank is None else _cpu(bank.gid)}
+
     # ------------------------------------------------------------------ state
     def checkpoint_state(self, epoch: Optional[int] = None, metrics: Optional[dict] = None, scheduler=None) -> dict:
         """the checkpoint container (CPU tensors, dicts, lists and Python scalars: loads with ``weights_only=True``)"""
@@ -156,6 +167,8 @@ class TrainerCheckpointMixin:
             bts["loss"] = self.loss
         if self.checkpoint_classify() is not None:                 # (absent without classify: the container is unchanged)
             bts["classify"] = self.checkpoint_classify()
+        if self.checkpoint_bank() is not None:                     # (absent without a bank: the container is unchanged)
+            bts["bank"] = self.checkpoint_bank()
         return {"epoch": epoch, "model_state_dict": {k: _cpu(v) for k, v in self.state_dict().items()},
                 "optimizer_state_dict": {"state": state, "param_groups": [group]},
                 "scheduler_state_dict": scheduler.state_dict() if scheduler is not None else None,
@@ -191,6 +204,19 @@ class TrainerCheckpointMixin:
                 if theirs_cls.get(field) != mine_cls[field]:
                     raise ValueError(f"load_checkpoint_state: classify.{field} differs: checkpoint "
                                      f"{theirs_cls.get(field)!r}, trainer {mine_cls[field]!r}")
+        size, theirs_bank = getattr(self, "_bank_size", 0), bts.get("bank")
+        if (size > 0) != (theirs_bank is not None):
+            raise ValueError(f"load_checkpoint_state: bank differs: the checkpoint was written "
+                             f"{'with' if theirs_bank is not None else 'without'} a cross-batch memory, this trainer was built "
+                             f"{'with' if size > 0 else 'without'} one")
+        if theirs_bank is not None:
+            for field, mine_v in (("size", size), ("warmup", int(self._bank_warmup))):
+                if theirs_bank.get(field) != mine_v:
+                    raise ValueError(f"load_checkpoint_state: bank.{field} differs: checkpoint {theirs_bank.get(field)!r}, "
+                                     f"trainer {mine_v!r}")
+            rows, N2 = theirs_bank.get("rows"), 2 * self.head.bridge.bridge_dim
+            if rows is not None and (tuple(rows.shape) != (size, N2) or tuple(theirs_bank["ids"].shape) != (size,)):
+                raise ValueError(f"load_checkpoint_state: bank.rows differ: checkpoint {tuple(rows.shape)}, trainer {(size, N2)}")
         # a checkpoint written before the head counts were recorded comes from a trainer whose blocks all had 4 heads
         heads = bts.get("heads", [[n, 4] for n, _ in mine["heads"]])
         if heads != mine["heads"]:
@@ -238,7 +264,7 @@ class TrainerCheckpointMixin:
         hyperparameters and the dropout stream, all copied in place.  Any captured step is dropped; the next
         graph-mode `train_step` captures again with the checkpoint's seeds and epoch word.  The process-global dropout
         counter (``ops._seed_state``) is set from the checkpoint.  A checkpoint of another EEG branch, loss, shape, bucket
-        layout or world size raises ValueError before anything is touched."""
+        layout, world size or cross-batch memory (presence, size, warm-up) raises ValueError before anything is touched."""
         self._check_compatible(sd)
         bts = sd["bridge_trainer_state"]
         b = self.bucket
@@ -260,7 +286,25 @@ class TrainerCheckpointMixin:
         self._pending_epoch_word = d["epoch_word"] if d["kind"] == "graph" else None
         if "augment" in bts:
             self._aug_step = int(bts["augment"]["step"])
+        if "bank" in bts:
+            self._load_bank(bts["bank"])
         ops.weights_changed()
+
+    def _load_bank(self, ck: dict):
+        """the ring's words, rows and ids, in place when the storage exists (allocated here otherwise)"""
+        self._bank_grouped = ck["grouped"]
+        self._bank_pushes = int(ck["state"][2])
+        if ck["rows"] is None:                                     # written before the first training step: an empty bank
+            if self._bank is not None:
+                self._bank.reset()
+            return
+        if self._bank is None:
+            self._bank = ops.ClipBank(self._bank_size, self.head.bridge.bridge_dim, True, self._scal.device)
+        bank = self._bank
+        bank.grouped = bool(ck["grouped"])
+        bank.bank.copy_(ck["rows"])
+        bank.gid.copy_(ck["ids"])
+        bank.state.copy_(torch.tensor(ck["state"], dtype=torch.int32))
 
     # ------------------------------------------------------------------ files
     def _barrier(self):

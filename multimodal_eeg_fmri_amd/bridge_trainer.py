@@ -48,7 +48,7 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
                  eps: float = 1e-8, group=None, device="cuda", mode: str = "graph", eeg_encoder: Optional[nn.Module] = None,
                  num_heads: int = 4, num_layers: int = 2, augment=None, loss: str = "infonce",
                  classify: bool = False, ce_weight: float = 1.0, class_weight=None, num_classes: int = 2,
-                 fmri_encoder: Optional[nn.Module] = None):
+                 fmri_encoder: Optional[nn.Module] = None, bank_size: int = 0, bank_warmup: int = 0):
         """``eeg_encoder``: the EEG branch when it is not the default ``EnhancedERPEncoder(eeg_channels, hidden_dim,
         num_layers, num_heads, dropout)`` - an ``EnhancedPowerEncoder`` (enhanced_models_v4.py:196-285) or a
         ``MultiScaleSTFTPowerEncoder`` (BASELINE config #5: raw EEG -> multi-scale STFT power -> a4); it must end in
@@ -69,8 +69,35 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
         connectivity as one (B, activation_dim + connectivity_dim) tensor ``[activation | connectivity]`` - the branch is
         then two launches per step (mm_fmri_tab_fwd, mm_fmri_tab_bwd), train-mode batches of
         2..256 rows; its ``hidden_dim`` must equal ``fmri_dim``.  Everything else - losses, groups, classify, augment,
-        embed / evaluate / retrieval / predict / explain, checkpoints, `fit`, the packed host-fed path - is the same."""
+        embed / evaluate / retrieval / predict / explain, checkpoints, `fit`, the packed host-fed path - is the same.
+        ``bank_size`` = K > 0: a cross-batch memory of the last K pairs' embeddings (Wang et al., "Cross-Batch Memory for
+        Embedding Learning") - every `train_step` scores its rows against the batch AND the valid
+        bank rows (mm_clip_bank_loss in place of mm_clip_loss_own_rows*: more negatives, and with ``groups=`` more
+        positives, at no encoder pass), then pushes its own embeddings (mm_clip_bank_push).  Bank rows are constants: no
+        loss, no gradient.  ``bank_warmup`` = w: the first w steps fill the bank without using it - they launch the in-batch
+        loss (and the push), so they are a default trainer's steps to the bit; in graph mode the step is captured once more
+        when the warm-up ends.  The storage is
+        allocated at the first step, before any capture; the number of valid rows lives on the device, so a captured step
+        is never captured again for it.  Whether the bank carries group ids is fixed by the first training step (a later
+        switch between ``groups=None`` and ``groups=...`` raises ValueError; `reset_bank` lifts that).  InfoNCE only, one
+        process only.  `evaluate`, `embed`, `evaluate_retrieval`, `predict`, `explain` and `forward` never read or write
+        the bank: they keep the in-batch loss.  0 (default): no bank, the step is unchanged."""
         super().__init__()
+        if bank_size < 0 or bank_warmup < 0:
+            raise ValueError(f"BridgeTrainer: bank_size and bank_warmup must be >= 0 (got {bank_size}, {bank_warmup})")
+        if bank_size > 0:
+            if loss == "sigmoid":
+                raise ValueError("BridgeTrainer: bank_size > 0 needs loss='infonce' (the pairwise sigmoid loss is the other "
+                                 "remedy for few in-batch negatives, not a partner of the bank)")
+            if group is not None and dp.world_size(group) > 1:
+                raise NotImplementedError("BridgeTrainer: bank_size > 0 with a process group of world size > 1 is not "
+                                          "supported yet (intended: every rank pushes the gathered rows of all ranks)")
+            ops.clip_bank_check(1, bank_size, bridge_dim, bank_warmup, "BridgeTrainer(bank_size=)")
+        self._bank_size, self._bank_warmup = int(bank_size), int(bank_warmup)
+        self._bank = None                             # ops.ClipBank, allocated at the first training step (before any capture)
+        self._bank_grouped = None                     # fixed by the first training step: do the bank rows carry group ids
+        self._bank_pushes = 0                         # host mirror of the bank's `pushes` word (one push per training step)
+        self._bank_live = bank_warmup == 0            # the running step's loss reads the bank (pushes >= warmup)
         if fmri_encoder is not None:
             if not isinstance(fmri_encoder, fMRITabularEncoder):
                 raise TypeError(f"BridgeTrainer: fmri_encoder must be an fMRITabularEncoder or None (the voxel encoder), got "
@@ -194,6 +221,40 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
         return dist.get_world_size(self.group) if self.group is not None else 1
 
     @property
+    def bank_size(self) -> int:
+        """rows of the cross-batch memory (0: none)"""
+        return self._bank_size
+
+    @property
+    def bank_filled(self) -> int:
+        """valid rows of the bank right now.  Reads a device word: SYNCHRONISES with the stream (not for the step loop)."""
+        return 0 if self._bank is None else int(self._bank.state[1].item())
+
+    def reset_bank(self):
+        """empty the bank (its state words are zeroed on the device; the rows stay and are never read) and let the next
+        training step choose anew whether the bank carries group ids"""
+        if self._bank is not None:
+            self._bank.reset()
+        self._bank_grouped = None
+        self._bank_pushes = 0
+
+    def _bank_prepare(self, B: int, grouped: bool, who: str):
+        """a bank trainer's checks and allocations of a training step, before its first launch (or its capture)"""
+        ops.clip_bank_check(B, self._bank_size, self.head.bridge.bridge_dim, self._bank_warmup, f"{who} (bank_size={self._bank_size})")
+        if self._bank_grouped is not None and self._bank_grouped != grouped:
+            raise ValueError(f"{who}: the bank was filled {'with' if self._bank_grouped else 'without'} group ids and this step "
+                             f"comes {'with' if grouped else 'without'} them: the ids of the bank's rows would be undefined "
+                             "(reset_bank() empties the bank and lifts this)")
+        if self._bank is None:
+            self._bank = ops.ClipBank(self._bank_size, self.head.bridge.bridge_dim, True, self._scal.device)
+        self._bank_grouped = self._bank.grouped = grouped
+        # the device gates on `pushes >= warmup` as well; the host decides which loss the step launches: before that the
+        # in-batch kernels, whose bits a default trainer has (mm_clip_bank_loss at n = 0 agrees with them to rounding only,
+        # and rounding does not stay small behind AdamW's g / (|g| + eps))
+        self._bank_live = self._bank_pushes >= self._bank_warmup
+        self._bank_pushes += 1
+
+    @property
     def augment_step(self) -> int:
         """the step index the next `train_step` augments with (0 after construction; restored by a checkpoint)"""
         return self._aug_step
@@ -253,6 +314,8 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
             self.fmri_encoder.tickets(fmri.device)         # the forward launch's words exist before any capture
         gid = ops.group_ids(groups, eeg.shape[0], None if self.mode == "graph" else eeg.device, "train_step")
         lab = self._labels(labels, eeg.shape[0], None if self.mode == "graph" else eeg.device, "train_step")
+        if self._bank_size:
+            self._bank_prepare(eeg.shape[0], gid is not None, "train_step")
         if lab is not None and self._cls_ticket is None:       # this trainer's own word, allocated before any capture
             self._cls_ticket = torch.zeros(1, dtype=torch.int32, device=self._scal.device)
         aug_step = None
@@ -295,10 +358,23 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
         logits, fw, aw = ops.bridge_cls_rows(br, ep, fp)
         if self.loss == "sigmoid":
             lc, acc_e, acc_f = ops.sigmoid_loss(ze, zf, self.head.logit_scale, self.head.logit_bias, self.group, gid)
+        elif self._bank_size:
+            lc, acc_e, acc_f = self._bank_loss_autograd(ze, zf, gid)
         else:
             lc, acc_e, acc_f = ops.clip_loss(ze, zf, self.head.logit_scale, self.group, gid)
         ce = ops.weighted_cross_entropy(logits, lab.long(), self._class_weight)
         return lc, acc_e, acc_f, ce, logits
+
+    def _bank_loss_autograd(self, ze, zf, gid):
+        """a bank trainer's training loss on the differentiable surface (`ClipBankLossFn`: the bank is a constant of the
+        tape), then the push of the step's own rows - detached: nothing of it is on the tape"""
+        if self._bank_live:
+            out = ops.clip_loss_bank(ze, zf, self.head.logit_scale, self._bank, gid, self._bank_warmup)
+        else:                                          # a warm-up step: the in-batch loss, the bank only fills
+            out = ops.clip_loss(ze, zf, self.head.logit_scale, self.group, gid)
+        with torch.no_grad():
+            ops.clip_bank_push(ops._packed_pair(ze, zf).detach().float().contiguous(), gid, self._bank)
+        return out
 
     def _step_autograd(self, eeg, fmri, gid=None, lab=None):
         b = self.bucket
@@ -311,7 +387,11 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
             self._seg_optimizer()
             return {"loss": loss.detach(), "top1_e2f": acc_e, "top1_f2e": acc_f, "contrastive_loss": lc.detach(),
                     "ce_loss": ce.detach(), "cls_correct": (logits.detach().argmax(dim=1) == lab).sum().float()}
-        loss, acc_e, acc_f = self.forward(eeg, fmri, gid)
+        if self._bank_size:                            # (`forward` keeps the in-batch loss)
+            ze, zf = self.head.embed(*self._encode(eeg, fmri))
+            loss, acc_e, acc_f = self._bank_loss_autograd(ze, zf, gid)
+        else:
+            loss, acc_e, acc_f = self.forward(eeg, fmri, gid)
         loss.backward()
         b.absorb_autograd_grads()
         self._seg_optimizer()
@@ -399,11 +479,19 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
         (``mm_clip_loss_own_rows``: every rank evaluates all rows of the gathered batch, so no reduce-scatter
         of column gradients is needed).  ``scal`` = the trainer's own 4-float result buffer, ``dz`` (B, 2N): both written with plain stores.
         ``gid_all``: the gathered int32 group ids -> the grouped loss (``mm_clip_loss_own_rows_grouped``).
-        ``loss="sigmoid"``: the pairwise sigmoid loss on the same inputs (``mm_sigmoid_loss_own_rows``), ``scal`` 5 floats."""
+        ``loss="sigmoid"``: the pairwise sigmoid loss on the same inputs (``mm_sigmoid_loss_own_rows``), ``scal`` 5 floats.
+        ``bank_size > 0``: the loss against the batch and the valid bank rows (``mm_clip_bank_loss``), then the push of the
+        step's rows (``mm_clip_bank_push``) behind it on the same stream."""
         ls = self.head.logit_scale.detach().reshape(1)
         B, row0 = dz.shape[0], dp.rank(self.group) * dz.shape[0]
         if self.loss == "sigmoid":
             ops.sigmoid_loss_own_rows(z_all, gid_all, ls, self.head.logit_bias.detach().reshape(1), scal, dz, B, row0)
+        elif self._bank_size:
+            if self._bank_live:
+                ops.clip_bank_loss(z_all, gid_all, self._bank, ls, scal, dz, self._bank_warmup)
+            else:                                      # a warm-up step: the in-batch loss, the bank only fills
+                ops.clip_loss_own_rows(z_all, gid_all, ls, scal, dz, B, row0)
+            ops.clip_bank_push(z_all, gid_all, self._bank)
         else:
             ops.clip_loss_own_rows(z_all, gid_all, ls, scal, dz, B, row0)
         self._stamp(6)
@@ -572,6 +660,7 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
         n_f = fmri.numel() * 4
         c["grouped"] = gid is not None
         c["labelled"] = lab is not None
+        c["bank_live"] = self._bank_live              # which loss the recorded step launches (a bank trainer's warm-up)
         n_g = Bx * 4 if c["grouped"] else 0
         c["in"] = torch.empty(n_e + n_f + n_g + (Bx * 4 if c["labelled"] else 0), dtype=torch.uint8, device=dev)
         c["fmri"] = c["in"][n_e:n_e + n_f].view(torch.float32).view(fmri.shape)
@@ -597,6 +686,8 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
         b = self.bucket
         snap = [t.clone() for t in (b.p, b.m, b.v, b.state)]
         bufs = [t for t in self.buffers() if t is not None]
+        if self._bank is not None:                    # the warm-up steps push: the bank is part of the training state
+            bufs += self._bank.tensors()
         snap_bufs = [t.clone() for t in bufs]
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
@@ -750,7 +841,8 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
         """``aug_step``: the augmentation's step index (trainers with an augmenter).  The capture and its two warm-up steps
         see the batch as it came; what a replay reads is staged below, augmented."""
         if (self._cap is None or self._cap["eeg"].shape != eeg.shape or self._cap["fmri"].shape != fmri.shape
-                or self._cap["grouped"] != (gid is not None) or self._cap["labelled"] != (lab is not None)):
+                or self._cap["grouped"] != (gid is not None) or self._cap["labelled"] != (lab is not None)
+                or self._cap["bank_live"] != self._bank_live):
             step0, base0 = ops._seed_state["step"], ops._seed_state["base"]
             self._capture(eeg, fmri, gid, lab)
             # the dropout seeds of this capture were drawn from here on (checkpoint_state)
@@ -857,6 +949,11 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
         if self._cap is None:
             raise RuntimeError("train_step_packed: run one train_step(eeg, fmri) first (it captures the step and fixes the shapes)")
         c = self._cap
+        if self._bank_size:
+            if c["bank_live"] != (self._bank_pushes >= self._bank_warmup):
+                raise RuntimeError("train_step_packed: the bank's warm-up has ended and the captured step is the warm-up's; run "
+                                   "one train_step(eeg, fmri) (it captures the step that reads the bank)")
+            self._bank_pushes += 1
         if flat.dtype != torch.uint8 or flat.numel() != c["in"].numel() or not flat.is_cuda:
             raise ValueError(f"train_step_packed: expected a device uint8 buffer of {c['in'].numel()} bytes")
         c["in"].copy_(flat, non_blocking=True)

@@ -464,6 +464,70 @@ def sigmoid_loss_own_rows(z_all, gid_all, logit_scale1, logit_bias1, scal, dz, B
     _hip.call("mm_sigmoid_loss_own_rows", z_all, gid_all, logit_scale1, logit_bias1, scal, dz, ws, B, Bg, N2 // 2, row0)
 
 
+def clip_bank_check(B: int, K: int, N: int, warmup: int = 0, who: str = "clip_bank"):
+    """the shape rules of mm_clip_bank_loss / mm_clip_bank_push (csrc/clip_bank.hip), before any launch: ``ValueError``"""
+    if K < 1:
+        raise ValueError(f"{who}: the bank needs at least one row (K={K})")
+    if N < 4 or N % 4:
+        raise ValueError(f"{who}: the embedding width must be a positive multiple of 4 (N={N})")
+    if warmup < 0:
+        raise ValueError(f"{who}: warmup must be >= 0 (got {warmup})")
+    if B < 1 or B > K:
+        raise ValueError(f"{who}: a batch of {B} rows does not fit a bank of {K} (need 1 <= B <= K)")
+
+
+class ClipBank:
+    """the cross-batch memory of the InfoNCE loss (mm_clip_bank_loss / mm_clip_bank_push): device storage the caller owns,
+    allocated before any capture.  ``bank`` (K, 2N) fp32 rows [ze | zf]; ``gid`` (K,) int32 ids of the rows (``grouped``
+    banks only, else None); ``state`` (4,) int32 = {head, filled, pushes, 0} - zero it to empty the bank."""
+
+    def __init__(self, K: int, N: int, grouped: bool = False, device="cuda"):
+        clip_bank_check(1, K, N, 0, "ClipBank")
+        self.K, self.N, self.grouped = int(K), int(N), bool(grouped)
+        self.bank = torch.zeros(self.K, 2 * self.N, dtype=_F32, device=device)
+        self.gid = torch.zeros(self.K, dtype=torch.int32, device=device) if grouped else None
+        self.state = torch.zeros(4, dtype=torch.int32, device=device)
+
+    def reset(self):
+        self.state.zero_()
+
+    def tensors(self):
+        return [t for t in (self.bank, self.gid, self.state) if t is not None]
+
+
+def clip_bank_ws_floats(B: int, K: int, N: int) -> int:
+    """floats of the scratch of mm_clip_bank_loss (the 2 B (B + K) scores + the key chunks' partials)"""
+    return _hip.host_int("mm_clip_bank_ws_floats", B, K, N)
+
+
+def _bank_args(z, gid, bank: ClipBank, who: str):
+    B, N2 = z.shape
+    if N2 != 2 * bank.N:
+        raise ValueError(f"{who}: rows of {N2} floats, the bank holds rows of {2 * bank.N}")
+    if (gid is not None) != bank.grouped:
+        raise ValueError(f"{who}: the bank {'carries' if bank.grouped else 'carries no'} group ids, the batch "
+                         f"{'has none' if gid is None else 'has some'}")
+    return B
+
+
+def clip_bank_loss(z, gid, bank: ClipBank, logit_scale1, scal, dz, warmup: int = 0):
+    """symmetric InfoNCE of the B rows of z (B, 2N) against themselves and the valid rows of ``bank`` -> scal (4,), dz
+    (B, 2N) or None; gid (B,) int32 or None (the bank must have been built alike).  The number of valid bank rows is read
+    on the device (``pushes >= warmup ? filled : 0``).  Allocates the workspace; the bank is not written."""
+    B = _bank_args(z, gid, bank, "clip_bank_loss")
+    clip_bank_check(B, bank.K, bank.N, warmup, "clip_bank_loss")
+    ws = _empty((clip_bank_ws_floats(B, bank.K, bank.N),), _F32, z)
+    _hip.call("mm_clip_bank_loss", z, gid, bank.bank, bank.gid, bank.state, logit_scale1, scal, dz, ws, B, bank.K, bank.N,
+              int(warmup))
+
+
+def clip_bank_push(z, gid, bank: ClipBank):
+    """the B rows of z (and their ids) into the ring, then the state words advance (mm_clip_bank_push)"""
+    B = _bank_args(z, gid, bank, "clip_bank_push")
+    clip_bank_check(B, bank.K, bank.N, 0, "clip_bank_push")
+    _hip.call("mm_clip_bank_push", z, gid, bank.bank, bank.gid, bank.state, B, bank.K, bank.N)
+
+
 def group_ids(groups, n: int, device=None, who: str = "groups") -> Optional[torch.Tensor]:
     """Validate a (n,) vector of group ids (e.g. subject indices; compared for equality only) -> int32 on ``device``, or
     None for None.  A host tensor of any integer dtype is range-checked and converted; a device tensor must already be
@@ -1406,6 +1470,15 @@ def clip_loss(ze, zf, logit_scale, group=None, groups=None):
     gid = group_ids(groups, ze.shape[0], ze.device, "clip_loss")
     from .autograd import ClipLossFn
     return ClipLossFn.apply(_packed_pair(ze, zf), logit_scale, group, gid)
+
+
+def clip_loss_bank(ze, zf, logit_scale, bank: ClipBank, groups=None, warmup: int = 0):
+    """`clip_loss` against the batch and the valid rows of ``bank`` (mm_clip_bank_loss; single process only) -> (loss,
+    top1 e->f, top1 f->e).  The bank is a constant of the tape and is NOT pushed to: follow with `clip_bank_push`."""
+    _need_gpu(ze)
+    gid = group_ids(groups, ze.shape[0], ze.device, "clip_loss_bank")
+    from .autograd import ClipBankLossFn
+    return ClipBankLossFn.apply(_packed_pair(ze, zf), logit_scale, bank, gid, warmup)
 
 
 def sigmoid_loss(ze, zf, logit_scale, logit_bias, group=None, groups=None):

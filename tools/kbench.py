@@ -431,6 +431,53 @@ def groups_case(step_iters=30):
     print(f"C2 graph step B=32: ungrouped {tu:7.1f} us  grouped {tg:7.1f} us  ({100 * (tg / tu - 1):+.2f} %)")
 
 
+def bank_case(B=32, N=128, step_iters=30, rounds=5):
+    """the cross-batch negative bank: the loss section's launches, graph-replayed in the same run - the in-batch InfoNCE
+    pair against mm_clip_bank_loss + mm_clip_bank_push on a full bank of K = 1024 and 4096 rows (and the loss's two
+    launches alone) - and the C2 graph step (B = 32) without a bank and with bank_size = 4096 (full), interleaved rounds"""
+    z = torch.nn.functional.normalize(torch.randn(B, 2 * N, device="cuda"), dim=1).contiguous()
+    ls = torch.full((1,), math.log(1 / 0.07), device="cuda")
+    scal, dz = torch.empty(4, device="cuda"), torch.empty(B, 2 * N, device="cuda")
+    ws_u = torch.empty(ops.clip_loss_ws_floats(B, B), device="cuda")
+    cases = [("in-batch clip loss", lambda: _hip.call("mm_clip_loss_own_rows", z, ls, scal, dz, ws_u, B, B, N, 0))]
+    for K in (1024, 4096):
+        bank = ops.ClipBank(K, N, False, "cuda")
+        bank.bank.copy_(torch.nn.functional.normalize(torch.randn(K, 2 * N, device="cuda"), dim=1))
+        bank.state.copy_(torch.tensor([0, K, K // B, 0], dtype=torch.int32))
+        ws = torch.empty(ops.clip_bank_ws_floats(B, K, N), device="cuda")
+
+        def loss(bank=bank, ws=ws, K=K):
+            _hip.call("mm_clip_bank_loss", z, None, bank.bank, None, bank.state, ls, scal, dz, ws, B, K, N, 0)
+
+        def both(bank=bank, loss=loss, K=K):
+            loss()
+            _hip.call("mm_clip_bank_push", z, None, bank.bank, None, bank.state, B, K, N)
+        cases += [(f"bank loss K={K}", loss), (f"bank loss + push K={K}", both)]
+    times = {name: [] for name, _ in cases}
+    for _ in range(rounds):
+        for name, fn in cases:
+            times[name].append(graph_time(fn))
+    for name, _ in cases:
+        print(f"loss section B={B} N={N}: {name:26s} {_spread(times[name])}")
+    from multimodal_eeg_fmri_amd.bridge_trainer import BridgeTrainer, synthetic_pairs
+    eeg, fmri = synthetic_pairs(32, 64, 1024, (32, 32, 32))
+    trs = []
+    for K in (0, 4096):
+        ops.set_seed_epoch(None)
+        torch.manual_seed(0)
+        tr = BridgeTrainer(eeg_channels=64, dropout=0.3, bank_size=K).train()
+        for _ in range(K // 32 + 1):                          # fill the bank: the timed steps see all K rows
+            tr.train_step(eeg, fmri)
+        trs.append(tr)
+    steps = ([], [])
+    for _ in range(rounds):
+        for i, tr in enumerate(trs):
+            steps[i].append(timeit(lambda: tr.train_step(eeg, fmri), iters=step_iters, rounds=1))
+    t0, t1 = statistics.median(steps[0]), statistics.median(steps[1])
+    print(f"C2 graph step B=32: no bank {_spread(steps[0])}   bank_size=4096 (filled {trs[1].bank_filled}) {_spread(steps[1])}   "
+          f"({t1 - t0:+.1f} us, {100 * (t1 / t0 - 1):+.2f} %)")
+
+
 def _spread(xs):
     return f"{statistics.median(xs):7.1f} us  [{min(xs):.1f} .. {max(xs):.1f}]"
 
@@ -851,6 +898,9 @@ def main():
         return
     if flt == "cls":
         cls_case()
+        return
+    if flt == "bank":
+        bank_case()
         return
     if flt == "tabfmri":
         tabfmri_case()
