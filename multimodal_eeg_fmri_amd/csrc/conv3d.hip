@@ -342,7 +342,9 @@ __global__ __launch_bounds__(256) void pool3_bn_act_kernel(Pool3Args a) {
                 for (int j = 0; j < 8; ++j) {
                     const bf16 yv = t[j][c];
                     const float z = (float)yv * sc[c] + sh[c];
-                    if (z > zmax) { zmax = z; jmax = j; ymax = yv; }       // strict: first occurrence wins, as PyTorch
+                    // ReLU maps every z <= 0 to the same 0: such voxels tie, and the first of them wins (as PyTorch)
+                    const float zt = a.act == MM_ACT_RELU ? fmaxf(z, 0.f) : z;
+                    if (zt > zmax) { zmax = zt; jmax = j; ymax = yv; }     // strict: first occurrence wins, as PyTorch
                     if (z < zmin) { zmin = z; jmin = j; ymin = yv; }
                 }
                 // GELU: with zmax >= 0 the largest pre-activation holds the largest activation (conv3d_l1.hip); the second
