@@ -605,6 +605,38 @@ int mm_fmri_tab_bwd(const float* dout, const float* x, const float* out, const f
                     float* d_c2_w, float* d_c2_b, float* d_c2_g, float* d_c2_be, float* d_f_w, float* d_f_b,
                     float* d_f_g, float* d_f_be, float* d_activation_weight, float* d_connectivity_weight, int train,
                     float eps, float drop_p, hipStream_t stream);
+/* The encoders of the fMRI notebook's transformer model (fMRI_CODE/CrossModal_fmri_scr.ipynb, cell "# ENCODER BLOCKS":
+ * ActivationEncoder / ConnectivityEncoder = Linear(in_dim -> H), nn.TransformerEncoder of L post-norm layers (nhead 4,
+ * dim_feedforward 4H, ReLU) on a sequence of length ONE, LayerNorm(H)) for one or two stacks in ONE launch: replaces the
+ * `self.project(x)`, `self.transformer(x)`, `self.norm(x)` calls of that cell's two forward methods.  With one key the
+ * softmax is 1: per layer v = Wv h + bv, sa = Wo (keep_attn * v) + bo, h = LN1(h + drop1(sa)), h = LN2(h + drop2(W2
+ * drop(relu(W1 h + b1)) + b2)), eps 1e-5.  fp32 throughout, sums over k ascending, no atomics, no workgroup waits for
+ * another: grid (ceil(B / 16), stacks), a workgroup keeps 16 rows of one stack in LDS.
+ * x_s [B][in_s] (no alignment asked), out_s [B][H]; H in {32, 64, 128}, 1 <= L <= 8, B >= 1; stack 1's arguments are ignored
+ * when nstacks = 1.  params_host: HOST array of nstacks * (4 + 12 L) device pointers, per stack the module's parameters()
+ * order: project.weight [H][in], project.bias, per layer in_proj_weight [3H][H], in_proj_bias, out_proj.weight, out_proj.bias,
+ * linear1.weight [4H][H], linear1.bias, linear2.weight [H][4H], linear2.bias, norm1.weight, norm1.bias, norm2.weight,
+ * norm2.bias, then norm.weight, norm.bias (copied into the launch's arguments).
+ * Dropout: seeds_host = HOST array of nstacks * 4 L seeds (read only when drop_p > 0), per stack in layer order then site
+ * order: attention (one draw per (row, head): element index b * 4 + head), dropout1 (b * H + f), FFN middle (b * 4H + f),
+ * dropout2 (b * H + f).
+ * save (nullable: eval / no_grad, then only out is written): nstacks * (1 + 9 L) B H floats for the backward, per stack
+ * h0 [B][H], then per layer mv [B][H] = keep_attn * v, y1 (LN1 input), h1 (LN1 output), mid [B][4H] (post ReLU and
+ * dropout), y2 (LN2 input), h2 (LN2 output). */
+int mm_tab_tx_fwd(const float* x0, const float* x1, int nstacks, int B, int in0, int in1, int H, int L,
+                  const void* params_host, float* out0, float* out1, float* save, float drop_p,
+                  const uint32_t* seeds_host, const uint32_t* seed_epoch, hipStream_t stream);
+/* its backward (replaces autograd through the same cell), TWO launches: a row-local pass with the forward's decomposition
+ * that leaves the gradient at every Linear's output and every LayerNorm's dy, dy * xhat in `scratch` = nstacks *
+ * (3 + 11 L) B H floats (no initialisation) and writes dx_s [B][in_s] (nullable: skipped); then a parameter pass in which
+ * one workgroup owns a 64 x 64 tile of one weight gradient, or one layer's column sums, rows ascending.  grads_host: HOST
+ * array of destinations in params_host's layout, each nullable; every destination is written with PLAIN stores by its only
+ * writer, and the query / key rows of in_proj_weight / in_proj_bias (which never reach the output) are written as ZEROS.
+ * LayerNorm has no train / eval distinction: the same call serves eval-mode attribution with drop_p = 0. */
+int mm_tab_tx_bwd(const float* dout0, const float* dout1, const float* x0, const float* x1, int nstacks, int B, int in0,
+                  int in1, int H, int L, const void* params_host, const void* grads_host, const float* save,
+                  float* scratch, float* dx0, float* dx1, float drop_p, const uint32_t* seeds_host,
+                  const uint32_t* seed_epoch, hipStream_t stream);
 /* batch-pairwise cosine-similarity matrix + symmetric InfoNCE, bit-reproducible (no float atomics).
  * Embeddings are packed rows [ze (N) | zf (N)]: z_all [Bg][2N] = the all-gathered global batch, this rank's
  * pairs at rows [row0, row0+B).  C[r][j] = ze_r . zf_j; e->f = row softmax of exp(logit_scale) C, f->e =

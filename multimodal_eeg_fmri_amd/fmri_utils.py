@@ -450,7 +450,8 @@ class fMRIConfig:
                 f"connectivity={self.connectivity_types}, agg={self.agg_method}, val_ratio={self.val_ratio})")
 
 
-def run_experiment(dataset, config, task="classification", device=None, optimizer_factory=None, verbose=True):
+def run_experiment(dataset, config, task="classification", device=None, optimizer_factory=None, verbose=True,
+                   model_classes=None):
     """The protocol of ``run_fmri_v11.py:715-934``: (stratified) K-fold over the subjects; inside every fold the
     training part is split again into train / validation (``val_ratio``, seeded per fold); the three models
     (fusion, activation only, connectivity only) are trained with AdamW + ReduceLROnPlateau(0.5, 5) on the
@@ -458,7 +459,9 @@ def run_experiment(dataset, config, task="classification", device=None, optimize
     once on the held-out test part.  Returns ``(results, fusion_weights_all)`` with the reference's structure:
     ``results[name]`` = list of per-fold metric dicts.  The model calls run on the HIP kernels; the optimizer is
     ``optim.FusedAdamW`` (clip + AdamW in one launch) unless ``optimizer_factory(params, lr, weight_decay)`` says
-    otherwise."""
+    otherwise.  ``model_classes``: {"fusion" / "activation_only" / "connectivity_only": class} taking this module's
+    constructor keywords (``crossmodal_fmri_scr.run_experiment`` passes the notebook's transformer models); default: the
+    three MLP models of this module."""
     import copy
     import numpy as np
     from sklearn.model_selection import KFold, StratifiedKFold, train_test_split
@@ -469,6 +472,8 @@ def run_experiment(dataset, config, task="classification", device=None, optimize
     from .crossmodal_eeg_scr import _PlateauLR
     say = print if verbose else (lambda *a, **k: None)
     device = device or torch.device("cuda")
+    classes = {"fusion": fMRIFusionNet, "activation_only": fMRIActivationOnly, "connectivity_only": fMRIConnectivityOnly}
+    classes.update(model_classes or {})
     if task == "classification":
         labels = np.array([s["class_label"] for s in dataset.samples])
         num_classes = len(np.unique(labels))
@@ -502,14 +507,14 @@ def run_experiment(dataset, config, task="classification", device=None, optimize
             criterion = nn.MSELoss()
         for model_name in ("fusion", "activation_only", "connectivity_only"):
             if model_name == "fusion":
-                model = fMRIFusionNet(activation_dim=activation_dim, connectivity_dim=connectivity_dim, hidden_dim=config.hidden_dim,
-                                      num_classes=num_classes, dropout=config.dropout, task=task)
+                model = classes[model_name](activation_dim=activation_dim, connectivity_dim=connectivity_dim,
+                                            hidden_dim=config.hidden_dim, num_classes=num_classes, dropout=config.dropout, task=task)
             elif model_name == "activation_only":
-                model = fMRIActivationOnly(in_dim=activation_dim, hidden_dim=config.hidden_dim, num_classes=num_classes,
-                                           dropout=config.dropout, task=task)
+                model = classes[model_name](in_dim=activation_dim, hidden_dim=config.hidden_dim, num_classes=num_classes,
+                                            dropout=config.dropout, task=task)
             else:
-                model = fMRIConnectivityOnly(in_dim=connectivity_dim, hidden_dim=config.hidden_dim, num_classes=num_classes,
-                                             dropout=config.dropout, task=task)
+                model = classes[model_name](in_dim=connectivity_dim, hidden_dim=config.hidden_dim, num_classes=num_classes,
+                                            dropout=config.dropout, task=task)
             model = model.to(device)
             if optimizer_factory is not None:
                 optimizer = optimizer_factory(model.parameters(), config.learning_rate, config.weight_decay)

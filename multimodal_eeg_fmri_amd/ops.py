@@ -1770,6 +1770,89 @@ def fmri_tab_forward(m, x: torch.Tensor) -> torch.Tensor:
         return _tab_forward_impl(m, x, False)[0]
 
 
+# ------------------ the fMRI notebook's transformer encoders (fp32, csrc/fmri_tx.hip: one launch forward, two backward)
+TAB_TX_HIDDEN_DIMS = (32, 64, 128)
+TAB_TX_MAX_LAYERS = 8
+TAB_TX_ROW_TILE = 16          # rows a workgroup of mm_tab_tx_fwd owns
+_TX_LAYER_PARAMS = ("self_attn.in_proj_weight", "self_attn.in_proj_bias", "self_attn.out_proj.weight", "self_attn.out_proj.bias",
+                    "linear1.weight", "linear1.bias", "linear2.weight", "linear2.bias", "norm1.weight", "norm1.bias",
+                    "norm2.weight", "norm2.bias")
+
+
+def tab_tx_check(hidden_dim: int, num_layers: int, in_dims=(), dropout: float = 0.0, nhead: int = 4, who: str = "tab_tx"):
+    """what mm_tab_tx_fwd / mm_tab_tx_bwd take, checked before any launch; names the offending argument"""
+    if hidden_dim not in TAB_TX_HIDDEN_DIMS:
+        raise ValueError(f"{who}: hidden_dim must be one of {TAB_TX_HIDDEN_DIMS}, got {hidden_dim}")
+    if not 1 <= int(num_layers) <= TAB_TX_MAX_LAYERS:
+        raise ValueError(f"{who}: num_layers must be in 1..{TAB_TX_MAX_LAYERS}, got {num_layers}")
+    if len(in_dims) > 2:
+        raise ValueError(f"{who}: one or two stacks, got {len(in_dims)}")
+    for d in in_dims:
+        if int(d) < 1:
+            raise ValueError(f"{who}: in_dim must be >= 1, got {d}")
+    if not 0.0 <= float(dropout) < 1.0:
+        raise ValueError(f"{who}: dropout must be in [0, 1), got {dropout}")
+    if nhead != 4:
+        raise ValueError(f"{who}: nhead must be 4 (the notebook's encoder layers), got {nhead}")
+
+
+def tab_tx_save_floats(nstacks: int, B: int, H: int, L: int) -> int:
+    """floats of mm_tab_tx_fwd's save buffer (include/mmeeg_hip.h)"""
+    return nstacks * (1 + 9 * L) * B * H
+
+
+def tab_tx_scratch_floats(nstacks: int, B: int, H: int, L: int) -> int:
+    """floats of mm_tab_tx_bwd's scratch"""
+    return nstacks * (3 + 11 * L) * B * H
+
+
+def tab_tx_params(enc) -> List[torch.Tensor]:
+    """an encoder's 4 + 12 L parameters in the kernels' order (= its parameters() order)"""
+    ps = [enc.project.weight, enc.project.bias]
+    for layer in enc.transformer.layers:
+        named = dict(layer.named_parameters())
+        ps += [named[k] for k in _TX_LAYER_PARAMS]
+    return ps + [enc.norm.weight, enc.norm.bias]
+
+
+def host_table(values, ctype):
+    """a host array the C ABI reads during the call (pointer tables, seed lists): keep the returned object alive until the
+    call has returned"""
+    import ctypes
+    return (ctype * max(len(values), 1))(*values)
+
+
+def tab_tx_forward_impl(encs, xs, training: bool, save: bool):
+    """one or two notebook encoders (``crossmodal_fmri_scr.ActivationEncoder`` / ``ConnectivityEncoder``) on their inputs
+    (B, in_dim), ONE launch (mm_tab_tx_fwd).  Train mode draws 4 L dropout seeds per stack (layer order, then attention,
+    dropout1, FFN middle, dropout2), stack by stack.  ``save`` False: nothing but the outputs is written.
+    -> ([feat (B, H)], saved)"""
+    import ctypes
+    n = len(encs)
+    e0 = encs[0]
+    H, L = e0.hidden_dim, e0.num_layers
+    tab_tx_check(H, L, [e.in_dim for e in encs], e0.drop_p, who="tab_tx_forward")
+    for e, x in zip(encs, xs):
+        if (e.hidden_dim, e.num_layers, e.drop_p) != (H, L, e0.drop_p):
+            raise ValueError("tab_tx_forward: the stacks of one launch share hidden_dim, num_layers and dropout")
+        if x.dim() != 2 or x.shape[1] != e.in_dim or x.shape[0] != xs[0].shape[0] or x.shape[0] < 1:
+            raise ValueError(f"tab_tx_forward: expected a (B, {e.in_dim}) batch with B >= 1 rows in every stack, got shape "
+                             f"{tuple(x.shape)}")
+    _need_gpu(*xs)
+    xs = [x.float().contiguous() for x in xs]
+    B = xs[0].shape[0]
+    p = float(e0.drop_p) if training else 0.0
+    seeds = [_next_seed() for _ in range(n * 4 * L)] if p > 0 else []
+    params = [q for e in encs for q in tab_tx_params(e)]
+    ptab = host_table([_hip._ptr(q) for q in params], ctypes.c_void_p)
+    stab = host_table(seeds, ctypes.c_uint32)
+    outs = [_empty((B, H), _F32, xs[0]) for _ in range(n)]
+    sv = _empty((tab_tx_save_floats(n, B, H, L),), _F32, xs[0]) if save else None
+    _hip.call("mm_tab_tx_fwd", xs[0], xs[1] if n > 1 else None, n, B, encs[0].in_dim, encs[1].in_dim if n > 1 else 0, H, L,
+              ctypes.addressof(ptab), outs[0], outs[1] if n > 1 else None, sv, p, ctypes.addressof(stab) if seeds else None, EP())
+    return outs, dict(encs=list(encs), xs=xs, save=sv, B=B, H=H, L=L, p=p, seeds=seeds, params=params)
+
+
 def conn_encoder_forward(m, x):
     _need_gpu(x)
     if m.training or attribution_active():                   # (attribution: eval mode on the tape - frozen BatchNorm, no dropout)

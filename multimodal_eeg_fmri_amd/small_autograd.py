@@ -573,3 +573,56 @@ def gatv2(conv, x, graph, act="none", training: bool = False, sink=None, ea_csr=
 def proj_head(x, seq, drop_p):
     """Linear -> LayerNorm -> GELU -> Dropout (bridge_utils.py:34-45)"""
     return ActFn.apply(LayerNormFn.apply(linear(x, seq[0]), seq[1].weight, seq[1].bias, seq[1].eps), "gelu", float(drop_p))
+
+
+def tab_tx_bwd(bag: GradBag, sv: dict, douts, need_dx):
+    """backward of ops.tab_tx_forward_impl, TWO launches in one call (mm_tab_tx_bwd: the row-local pass, then the
+    parameter pass); douts fp32 (B, H) per stack (None = no gradient arrives there).  Every parameter gradient is written
+    into its `GradBag` target with PLAIN stores - the query / key rows of every in_proj as zeros - so one backward of an
+    encoder per step.  Returns [d / d x (B, in_dim) or None] per stack."""
+    import ctypes
+    encs, xs, B, H, L = sv["encs"], sv["xs"], sv["B"], sv["H"], sv["L"]
+    n = len(encs)
+    douts = [_zeros((B, H), xs[0]) if g is None else _f(g) for g in douts]
+    gtab = ops.host_table([_hip._ptr(bag.target(q)) for q in sv["params"]], ctypes.c_void_p)
+    ptab = ops.host_table([_hip._ptr(q) for q in sv["params"]], ctypes.c_void_p)
+    stab = ops.host_table(sv["seeds"], ctypes.c_uint32)
+    scratch = _empty((ops.tab_tx_scratch_floats(n, B, H, L),), _F32, xs[0])
+    dxs = [_empty(tuple(x.shape), _F32, x) if want else None for x, want in zip(xs, need_dx)]
+    _hip.call("mm_tab_tx_bwd", douts[0], douts[1] if n > 1 else None, xs[0], xs[1] if n > 1 else None, n, B, encs[0].in_dim,
+              encs[1].in_dim if n > 1 else 0, H, L, ctypes.addressof(ptab), ctypes.addressof(gtab), sv["save"], scratch,
+              dxs[0], dxs[1] if n > 1 else None, float(sv["p"]), ctypes.addressof(stab) if sv["seeds"] else None, ops.EP())
+    return dxs
+
+
+class TabTxFn(torch.autograd.Function):
+    """the fMRI notebook's transformer encoders on the tape, one or two stacks: (encoders, training, x_a[, x_c],
+    parameters...) -> (feat_a[, feat_c]).  Train mode, or eval mode with a backward to follow (LayerNorm has no frozen
+    form: the same kernels with dropout off)."""
+
+    @staticmethod
+    def run(encs, xs, training):
+        return TabTxFn.apply(tuple(encs), bool(training), *xs, *[q for e in encs for q in ops.tab_tx_params(e)])
+
+    @staticmethod
+    def forward(ctx, encs, training, *args):
+        n = len(encs)
+        xs = args[:n]
+        outs, sv = ops.tab_tx_forward_impl(encs, xs, training, True)
+        ctx.saved, ctx.params, ctx.need_dx = sv, args[n:], [bool(x.requires_grad) for x in xs]
+        return tuple(outs)
+
+    @staticmethod
+    def backward(ctx, *douts):
+        bag = GradBag()
+        dxs = tab_tx_bwd(bag, ctx.saved, douts, ctx.need_dx)
+        return (None, None) + tuple(dxs) + tuple(bag.result(q) for q in ctx.params)
+
+
+def tab_tx(encs, xs, training: bool):
+    """[feat] of one or two notebook encoders: on the tape when a backward may follow (autograd on and an input or a
+    parameter asks for a gradient), else - eval, or anything under no_grad - the bare launch, which saves nothing"""
+    if any(ops._wants_grad(e, x) for e, x in zip(encs, xs)):
+        return list(TabTxFn.run(encs, xs, training))
+    with torch.no_grad():
+        return ops.tab_tx_forward_impl(encs, xs, training, False)[0]

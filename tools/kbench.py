@@ -606,6 +606,52 @@ def tabfmri_case(step_iters=30, rounds=5):
     print(f"C2 graph step B=32: volume branch (32^3) {_spread(times[0])}  tabular branch (100, 200) {_spread(times[1])}")
 
 
+def tabtx_case(step_iters=30, rounds=5, H=64, L=2, A=100, C=200, p=0.4):
+    """the fMRI notebook's two transformer encoders (crossmodal_fmri_scr), forward + backward of both stacks, train mode at
+    the notebook's dropout 0.4, at B = 8 (the notebook's batch) and B = 256: the fused path (mm_tab_tx_fwd, one launch,
+    and mm_tab_tx_bwd, two launches) against torch's own eager modules - the encoders' ``project`` / ``nn.TransformerEncoder`` /
+    ``norm`` containers called as the notebook calls them, autograd backward - on the same GPU in the same run:
+    interleaved rounds, median [min .. max] of HIP-event times; then the fused path graph-replayed."""
+    from multimodal_eeg_fmri_amd import autograd
+    from multimodal_eeg_fmri_amd import small_autograd as sa
+    from multimodal_eeg_fmri_amd.crossmodal_fmri_scr import ActivationEncoder, ConnectivityEncoder
+    for B in (8, 256):
+        torch.manual_seed(0)
+        encs = [ActivationEncoder(L, A, H, p).cuda().train(), ConnectivityEncoder(L, C, H, p).cuda().train()]
+        xs = [torch.randn(B, A, device="cuda"), torch.randn(B, C, device="cuda")]
+        Rs = [torch.randn(B, H, device="cuda") for _ in encs]
+        params = [q for e in encs for q in e.parameters()]
+
+        def eager():
+            for q in params:
+                q.grad = None
+            outs = [e.norm(e.transformer(e.project(x).unsqueeze(1)).squeeze(1)) for e, x in zip(encs, xs)]
+            torch.autograd.backward(outs, Rs)
+
+        bag = autograd.GradBag()
+
+        def fused():
+            with torch.no_grad():
+                _, sv = ops.tab_tx_forward_impl(encs, xs, True, True)
+                sa.tab_tx_bwd(bag, sv, Rs, [False, False])
+
+        def fused_fwd():
+            with torch.no_grad():
+                ops.tab_tx_forward_impl(encs, xs, True, True)
+
+        cases = [("torch eager nn.TransformerEncoder fwd + autograd bwd", eager), ("fused (1 + 2 launches)", fused),
+                 ("fused, forward launch alone", fused_fwd)]
+        times = [[] for _ in cases]
+        for _ in range(rounds):
+            for i, (_, fn) in enumerate(cases):
+                times[i].append(timeit(fn, iters=step_iters, rounds=1))
+        g = [graph_time(fused) for _ in range(rounds)]
+        print(f"notebook transformer encoders, two stacks B={B} in=({A}, {C}) H={H} L={L} p={p} (fwd + bwd):")
+        for (name, _), t in zip(cases, times):
+            print(f"  {name:56s} {_spread(t)}")
+        print(f"  {'fused, graph-replayed':56s} {_spread(g)}")
+
+
 def aug_case(B=32, C=64, T=1024, vol=(32, 32, 32), step_iters=30):
     """EEG augmentation (csrc/augment.hip) at the C2 shape: mm_stage_inputs alone against the plan + mm_stage_inputs_aug pair
     at p = 0.3 and p = 1 - issued eagerly (what a training loop pays: host issue included) and replayed from a hipGraph
@@ -904,6 +950,9 @@ def main():
         return
     if flt == "tabfmri":
         tabfmri_case()
+        return
+    if flt == "tabtx":
+        tabtx_case()
         return
     if flt == "aug":
         aug_case()
