@@ -196,11 +196,15 @@ class fMRIVolumeEncoder3D(nn.Module):
     odd slice count - with torch's semantics and no cropping or padding.  Both MaxPool3d(2) floor odd extents; the tail
     (the last plane / row / column no pooling window covers) still counts in the train-mode BatchNorm statistics, gets
     no gradient through the pool, and in training receives BatchNorm's backward term.
+
+    Accepted ``widths``: three channel counts, each 16 or a multiple of 32 up to 1 024 (``ops.check_volume_widths``;
+    anything else raises ``ValueError`` here).  Only w0 = 32 runs the fused first layer; (32, 64, 128) is the tuned set.
     """
 
     def __init__(self, in_channels: int = 1, out_dim: int = 64,
                  widths=(32, 64, 128), dropout: float = 0.3):
         super().__init__()
+        ops.check_volume_widths(widths)
         w0, w1, w2 = widths
         self.conv_layers = nn.Sequential(
             nn.Conv3d(in_channels, w0, kernel_size=3, padding=1), nn.BatchNorm3d(w0),

@@ -1155,6 +1155,34 @@ def check_volume_shape(shape):
                          f"got D, H, W = {tuple(shape[2:])}")
 
 
+VOLUME_WIDTH_MAX = 1024
+
+
+def volume_width_ok(w) -> bool:
+    """a channel width the voxel encoder's kernels take on both sides of a convolution: 16, or a multiple of 32 up to
+    `VOLUME_WIDTH_MAX`.  A layer's output is the next layer's unpadded channels-last input and, in the backward, the
+    data-gradient GEMM's input: mm_conv3d_fwd reads Cin = 16 or a multiple of 32 (one 16-channel or whole 32-channel LDS
+    chunks), `cpad` pads weight images to multiples of 16 only, mm_conv3d_wgrad wants multiples of 8, and the
+    BatchNorm / pool passes and the pooled head stop at 1 024 channels."""
+    try:
+        w = w.__index__()
+    except (AttributeError, TypeError):
+        return False
+    return w == 16 or (w % 32 == 0 and 32 <= w <= VOLUME_WIDTH_MAX)
+
+
+def check_volume_widths(widths):
+    """``fMRIVolumeEncoder3D(widths=(w0, w1, w2))``: refuse what the kernels cannot run with a ValueError, before any
+    launch (a width of 48 used to die on an assert in the backward pass only)."""
+    try:
+        ws = tuple(widths)
+    except TypeError:
+        ws = ()
+    if len(ws) != 3 or not all(volume_width_ok(w) for w in ws):
+        raise ValueError(f"fMRIVolumeEncoder3D: widths must be three channel counts, each 16 or a multiple of 32 up to "
+                         f"{VOLUME_WIDTH_MAX} (16, 32, 64, 96, 128, ...), got {widths!r}")
+
+
 def _vol_forward_impl(m, x: torch.Tensor, training: bool, need_dgrad: bool, save=None, need_dx: bool = False, winners=None):
     """``save`` (default = training): keep what a backward needs; eval + save = frozen BatchNorm.  ``need_dx``: the
     caller wants d / d volume - layer 1 then runs as an ordinary implicit GEMM on the channel-padded volume (the

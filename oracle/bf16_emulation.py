@@ -42,11 +42,16 @@ class _RoundedF:
 
 
 @contextlib.contextmanager
-def bf16_operands(l1_as_gemm: bool = False):
+def bf16_operands(l1_as_gemm: bool = False, widths=(32, 64, 128)):
     """``l1_as_gemm``: the voxel encoder's first layer ran as an ordinary implicit GEMM (a caller asked for d / d volume,
-    ops._vol_forward_impl(need_dx=True)); that form keeps its pooled layer's pre-BatchNorm output in bf16 too."""
+    ops._vol_forward_impl(need_dx=True), or w0 != 32: there is no fused first layer then); that form keeps its pooled
+    layer's pre-BatchNorm output in bf16 too.  ``widths``: the voxel encoder's (w0, w1, w2) - the layers whose output is
+    stored in bf16 are the POOLED ones, w0 -> w1 and (as a GEMM) 1 -> w0, recognised by their (Cout, Cin); the un-pooled
+    last layer keeps fp32 (so its shape must differ from the pooled ones', as it does for the widths the tests use)."""
+    w0, w1, w2 = widths
+    assert (w2, w1) not in ((w1, w0), (w0, 1)), "the last layer's weight shape must tell it from the pooled layers"
     saved = RF.F
-    RF.F = _RoundedF(((64, 32), (32, 1)) if l1_as_gemm else ((64, 32),))
+    RF.F = _RoundedF(((w1, w0), (w0, 1)) if l1_as_gemm else ((w1, w0),))
     try:
         yield
     finally:

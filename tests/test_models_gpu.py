@@ -135,11 +135,11 @@ def test_volume_encoder_eval_vs_oracle(shape):
     assert rel_err(got, want) < 2e-2
 
 
-def _oracle_grads(fn, m, *inputs, gy, emulate):
+def _oracle_grads(fn, m, *inputs, gy, emulate, l1_as_gemm=False, widths=(32, 64, 128)):
     from oracle.bf16_emulation import bf16_operands
     import contextlib
     sd = {k: v.detach().clone().requires_grad_(v.is_floating_point()) for k, v in m.state_dict().items()}
-    with (bf16_operands() if emulate else contextlib.nullcontext()):
+    with (bf16_operands(l1_as_gemm=l1_as_gemm, widths=widths) if emulate else contextlib.nullcontext()):
         out = fn(sd, *inputs, train=True)
         out.backward(gy)
     return out.detach(), {k: v.grad for k, v in sd.items() if v.requires_grad and v.grad is not None}
@@ -249,6 +249,50 @@ def test_volume_encoder_grads_vs_unmodified_fp32_oracle_with_hip_routing(shape, 
         gap = (best - taken) / a.abs().max()
         assert (gap > 0).float().mean().item() <= 2e-2, (act, (gap > 0).float().mean().item())
         assert gap.max().item() <= 2e-2, (act, gap.max().item())
+
+
+# non-default widths: (16, 32, 96) runs the generic first layer (also in training), Cin 16 weight gradients, 32 -> 96 and its
+# data gradient 96 -> 32; (32, 32, 64) runs 32 -> 64 with an fp32 output on the generic kernel and its data gradient 64 -> 32
+# on the streaming kernel, with the weight image in that kernel's lane order
+VOLUME_WIDTHS = [(16, 32, 96), (32, 32, 64)]
+VOLUME_WIDTH_SHAPES = [(16, 16, 16), (13, 18, 11)]
+
+
+@pytest.mark.parametrize("dhw", VOLUME_WIDTH_SHAPES, ids=["x".join(map(str, s)) for s in VOLUME_WIDTH_SHAPES])
+@pytest.mark.parametrize("widths", VOLUME_WIDTHS, ids=["-".join(map(str, w)) for w in VOLUME_WIDTHS])
+def test_volume_encoder_at_other_widths_eval_vs_oracle(widths, dhw):
+    """fMRIVolumeEncoder3D(widths=...) in eval mode, at the bounds of test_volume_encoder_eval_vs_oracle"""
+    m = build(Fm.fMRIVolumeEncoder3D, 41, widths=widths).eval()
+    x = seeded_randn(141, 2, 1, *dhw)
+    with torch.no_grad():
+        want = RF.volume_encoder3d(m.state_dict(), x)
+        got = m.cuda()(x.cuda()).cpu()
+    assert got.shape == want.shape
+    print(f"ERR widths {widths} {dhw} eval: 1 - cos {1 - cos_min(got, want):.3e}, rel {rel_err(got, want):.3e}")
+    assert cos_min(got, want) >= 1 - COS_TOL, cos_min(got, want)
+    assert rel_err(got, want) < 2e-2
+
+
+@pytest.mark.parametrize("dhw", VOLUME_WIDTH_SHAPES, ids=["x".join(map(str, s)) for s in VOLUME_WIDTH_SHAPES])
+@pytest.mark.parametrize("widths", VOLUME_WIDTHS, ids=["-".join(map(str, w)) for w in VOLUME_WIDTHS])
+def test_volume_encoder_at_other_widths_train_grads_vs_oracle(widths, dhw):
+    """train mode, dropout 0: every parameter gradient <= 5e-2 rel-L2 against the oracle run with bf16-rounded GEMM operands
+    (the bound of test_volume_encoder_train_grads_vs_oracle); w0 != 32 takes the generic first layer, which the oracle
+    mirrors with l1_as_gemm; the oracle is told the widths, so that it stores in bf16 what the HIP path stores in bf16 - the
+    pre-BatchNorm output of the pooled layers - whose rounding decides near-tied max-pool windows"""
+    m = build(Fm.fMRIVolumeEncoder3D, 42, widths=widths, dropout=0.0).train()
+    x = seeded_randn(142, 4, 1, *dhw)
+    gy = seeded_randn(143, 4, 64)
+    out, _ = _oracle_grads(RF.volume_encoder3d, m, x, gy=gy, emulate=False)
+    _, g16 = _oracle_grads(RF.volume_encoder3d, m, x, gy=gy, emulate=True, l1_as_gemm=widths[0] != 32, widths=widths)
+    mg = m.cuda()
+    y = mg(x.cuda())
+    y.backward(gy.cuda())
+    w16 = _worst(mg.named_parameters(), g16, zero=bn_cancelled_biases(mg))
+    print(f"ERR widths {widths} {dhw} train: 1 - cos {1 - cos_min(y.detach().cpu(), out):.3e}, worst gradient {w16}")
+    assert all(q.grad is not None and torch.isfinite(q.grad).all() for q in mg.parameters())
+    assert cos_min(y.detach().cpu(), out) >= 1 - COS_TOL
+    assert w16[1] <= 5e-2, ("vs bf16-operand oracle", w16)
 
 
 def test_volume_encoder_train_grads_at_config4_size_vs_oracle():
