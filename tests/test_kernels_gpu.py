@@ -1528,7 +1528,7 @@ def test_sample_zscore_chunked_form_vs_reference_and_the_one_workgroup_form():
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("cin", [20, 304])
+@pytest.mark.parametrize("cin", [20, 304, 400])       # 400: 537 600 weight elements, a second sweep of the 524 288-thread grid
 def test_power_merge_modes(cin):
     """mm_power_merge (EnhancedPowerEncoder's three Conv1d(C -> 64, k = 3 | 5 | 7) + BatchNorm1d(64) branches as ONE k = 7
     layer, enhanced_models_v4.py:210-234): mode 0 == F.pad + torch.cat of the parts; mode 3's bf16 image == mm_prep_conv_weight
@@ -1576,6 +1576,13 @@ def test_power_merge_modes(cin):
         assert torch.equal(gw[i], want_g)
         assert torch.equal(gb[i], 1.0 + dB[64 * i:64 * i + 64] if i != 2 else torch.ones(64, device=dev))
         assert torch.equal(gg[i], 1.0 + dG[64 * i:64 * i + 64]) and torch.equal(gbe[i], 1.0 + dBe[64 * i:64 * i + 64])
+    # mode 2 with the merged weight null: only the vectors are added, the parts' weight gradients keep their bits
+    gw0, gb0, gg0, gbe0 = ([t.clone() for t in trip] for trip in (gw, gb, gg, gbe))
+    ops.power_merge_call(2, (gw, gb, gg, gbe, none3, none3), [None, dB, dG, dBe, None, None], cin=cin, ks=ks)
+    for i in range(3):
+        assert torch.equal(gw[i], gw0[i])
+        assert torch.equal(gb[i], gb0[i] + dB[64 * i:64 * i + 64]) and torch.equal(gg[i], gg0[i] + dG[64 * i:64 * i + 64])
+        assert torch.equal(gbe[i], gbe0[i] + dBe[64 * i:64 * i + 64])
 
 
 @pytest.mark.parametrize("p", [0.0, 0.1, 0.5, 0.99999994])
