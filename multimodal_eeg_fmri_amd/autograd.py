@@ -10,7 +10,7 @@ autograd receives ``None``; otherwise a fresh tensor is returned to autograd.
 from __future__ import annotations
 
 import os
-from typing import Dict, List, Optional
+from typing import Dict, List, NamedTuple, Optional
 
 import torch
 
@@ -222,9 +222,9 @@ def _mask_cast(g_f32=None, g_bf16=None, z=None, act="none", drop_p=0.0, seed=0):
 
 def linear_bwd(bag: GradBag, dy: torch.Tensor, x: torch.Tensor, weight, bias, *, need_dx=True,
                dx_f32=False, below=None):
-    """``below`` = (z, act, drop_p, seed) of the layer that produced ``x``: the data-gradient
+    """dy (M, N) bf16, x (M, Kp) bf16 -> dx (M, Kp); accumulates dW, db.
+    ``below`` = (z, act, drop_p, seed) of the layer that produced ``x``: the data-gradient
     GEMM then returns d(pre-activation z) = (dy W) * act'(z) * dropout_mask directly."""
-    """dy (M, N) bf16, x (M, Kp) bf16 -> dx (M, Kp); accumulates dW, db."""
     M, N = dy.shape
     Kp = x.shape[1]
     K = weight.shape[1]
@@ -317,57 +317,64 @@ def conv_bn_act_bwd(bag: GradBag, s: dict, dout_bf16=None, dout_f32=None, need_d
     return ops.igemm(dy, wd, k, k - 1 - pad, cinp)["bf16"]
 
 
-def _linear_ln_bwd(bag, dy, h, lin, wb, x, stat, ln, dres, dx, dx_bf16, dgb, drop_p, seed, bn_below=None, gemm2=None,
+class BlockBwdPlan(NamedTuple):
+    """which launches a transformer block's backward runs: the forward's ``ops.BlockPlan`` plus this module's knobs"""
+    ffn: str            # FFN + norm2 + out-projection data gradient: "ffn_rows" (mm_ffn_rows_bwd) | "ln_gemm2" (.._ln_bwd_gemm2) |
+    #                     "ln" (mm_linear_dgrad_ln_bwd) | "generic" (data-gradient GEMM, then LayerNorm backward)
+    qkv: str            # QKV projection + norm1: "ln_bn_reduce" (.._ln_bwd_bn_reduce) | "ln" | "generic"
+    head_rows: bool     # the head's gradient is accepted as one fp32 row per sample (read by the "ffn_rows" / "ln_gemm2" launch)
+
+
+def block_bwd_plan(plan: ops.BlockPlan, bn_below: bool = False) -> BlockBwdPlan:
+    """``bn_below``: the block's input is the un-pooled 128-wide output of a conv block whose BatchNorm-backward sums the
+    last launch can form, and nothing asks for a masked bf16 copy of d(input)"""
+    gemm2 = plan.ln_fused and plan.out_proj_128 and not _NO_GEMM2
+    if gemm2:
+        ffn = "ffn_rows" if plan.ffn_rows_width and not _NO_FFN_ROWS_BWD else "ln_gemm2"
+    else:
+        ffn = "ln" if plan.ln_fused else "generic"
+    qkv = "generic" if not plan.ln_fused else "ln_bn_reduce" if bn_below and not _NO_BNRED else "ln"
+    return BlockBwdPlan(ffn, qkv, gemm2)
+
+
+def _linear_ln_bwd(bag, form, dy, h, weight, bias, x, stat, ln, dres, dx, dx_bf16, dgb, drop_p, seed, bn_below=None, w2=None,
                    res_rows=0):
     """backward of ``Linear(LayerNorm(x))``: weight / bias gradients of the Linear (``h`` = LN(x) bf16 is its
-    input), then d x = LN_backward(dy W) + dres.  Width 128 with M % 32 == 0 (the transformer blocks) runs
-    the data-gradient GEMM with the LayerNorm backward as its epilogue; anything else takes two launches."""
-    weight, bias = (lin.weight, lin.bias) if lin is not None else wb
+    input), then d x = LN_backward(dy W) + dres.  ``form`` (BlockBwdPlan.ffn / .qkv): "generic" takes two launches, the
+    others run the data-gradient GEMM with the LayerNorm backward as its epilogue - "ln_bn_reduce" with the BatchNorm-backward
+    sums of the conv block ``bn_below`` (dx is its fp32 d(out)), returned in ``bn_below["sums"]``; "ln_gemm2" with the data
+    gradient of the Linear under this LayerNorm's skip path (``w2`` = the attention out-projection's 128 x 128 image),
+    computed from dx_bf16 before it leaves the workgroup and returned."""
     M, D = x.shape
-    if D == 128 and M % 32 == 0:
-        linear_bwd(bag, dy, h, weight, bias, need_dx=False)
-        _, wd, cinp, coutp = ops.weights.get(weight, True)
-        if coutp != dy.shape[1] or cinp != D:
-            raise _hip.HipLibraryError(f"linear_ln_bwd: dY width {dy.shape[1]} / LN width {D} != weight image {coutp} x {cinp}")
-        if bn_below is not None and dx_bf16 is None and dx is not None and not _NO_BNRED:
-            # dx = the fp32 d(out) of the conv block below the stack: its BatchNorm-backward sums in the same launch
-            sb = bn_below["s"]
-            yb = sb["y"]
-            d2 = sb.get("drop2", (0.0, 0))
-            if yb.shape[2] == 128 and sb["pool"] == 1 and yb.shape[0] * yb.shape[1] == M:
-                sums_b = _zeros((REPL, 2, 128), yb)
-                _hip.call("mm_linear_dgrad_ln_bwd_bn_reduce", dy, wd, M, coutp, x, stat, ln.weight, dres, dx, dgb, ops.EP(),
-                          yb, sb["out4"], sums_b, ACT[sb["act"]], float(sb["drop_p"]), int(sb["seed"]), float(d2[0]), int(d2[1]))
-                bn_below["sums"] = sums_b
-                return
-        if gemm2 is not None and dx_bf16 is not None and not _NO_GEMM2:
-            # ``gemm2`` = (128 x 128 data-gradient image, holder list): the data gradient of the Linear under this
-            # LayerNorm's skip path (the attention out-projection), computed from dx_bf16 before it leaves the workgroup
-            w2, holder = gemm2
-            do = _empty((M, 128), _BF, dy)
-            _hip.call("mm_linear_dgrad_ln_bwd_gemm2", dy, wd, M, coutp, x, stat, ln.weight, dres, dx, dx_bf16, dgb,
-                      drop_p, seed, ops.EP(), w2, do, int(res_rows))
-            holder.append(do)
-            return
-        _hip.call("mm_linear_dgrad_ln_bwd", dy, wd, M, coutp, x, stat, ln.weight, dres, dx, dx_bf16, dgb,
-                  drop_p, seed, ops.EP())
-        return
-    dh = linear_bwd(bag, dy, h, weight, bias)
-    _hip.call("mm_layernorm_bwd", dh, None, x, stat, ln.weight, dres, dx, dx_bf16, dgb, M, D, drop_p, seed, ops.EP())
+    if form == "generic":
+        dh = linear_bwd(bag, dy, h, weight, bias)
+        _hip.call("mm_layernorm_bwd", dh, None, x, stat, ln.weight, dres, dx, dx_bf16, dgb, M, D, drop_p, seed, ops.EP())
+        return None
+    linear_bwd(bag, dy, h, weight, bias, need_dx=False)
+    _, wd, cinp, coutp = ops.weights.get(weight, True)
+    if coutp != dy.shape[1] or cinp != D:
+        raise _hip.HipLibraryError(f"linear_ln_bwd: dY width {dy.shape[1]} / LN width {D} != weight image {coutp} x {cinp}")
+    if form == "ln_bn_reduce":
+        sb = bn_below["s"]
+        yb = sb["y"]
+        d2 = sb.get("drop2", (0.0, 0))
+        bn_below["sums"] = sums_b = _zeros((REPL, 2, 128), yb)
+        _hip.call("mm_linear_dgrad_ln_bwd_bn_reduce", dy, wd, M, coutp, x, stat, ln.weight, dres, dx, dgb, ops.EP(),
+                  yb, sb["out4"], sums_b, ACT[sb["act"]], float(sb["drop_p"]), int(sb["seed"]), float(d2[0]), int(d2[1]))
+        return None
+    if form == "ln_gemm2":
+        do = _empty((M, 128), _BF, dy)
+        _hip.call("mm_linear_dgrad_ln_bwd_gemm2", dy, wd, M, coutp, x, stat, ln.weight, dres, dx, dx_bf16, dgb,
+                  drop_p, seed, ops.EP(), w2, do, int(res_rows))
+        return do
+    _hip.call("mm_linear_dgrad_ln_bwd", dy, wd, M, coutp, x, stat, ln.weight, dres, dx, dx_bf16, dgb,
+              drop_p, seed, ops.EP())
+    return None
 
 
 def ffn_rows_bwd_fused(blocks) -> bool:
-    """do all these saved transformer blocks take mm_ffn_rows_bwd (width 128, 32-row groups, a 128 x 128 out-projection
-    image, an FFN width that is a multiple of 128 up to 512)?  A trainer balances its two streams by it."""
-    if not blocks or _NO_GEMM2 or _NO_FFN_ROWS_BWD:
-        return False
-    for s in blocks:
-        M, D = s["x1"].shape
-        n1 = s["z"].shape[-1]
-        _, _, ci, co = ops.weights.get(s["blk"].self_attn.out_proj.weight, True)
-        if not (D == 128 and M % 32 == 0 and ci == 128 and co == 128 and n1 % 128 == 0 and n1 <= 512):
-            return False
-    return True
+    """do all these saved transformer blocks take mm_ffn_rows_bwd?  A trainer balances its two streams by it."""
+    return bool(blocks) and all(block_bwd_plan(s["plan"]).ffn == "ffn_rows" for s in blocks)
 
 
 def transformer_block_bwd(bag: GradBag, s: dict, dx2: torch.Tensor, dy2=None, emit_for=None, bn_below=None):
@@ -378,23 +385,24 @@ def transformer_block_bwd(bag: GradBag, s: dict, dx2: torch.Tensor, dy2=None, em
     the last LayerNorm-backward then also writes that masked bf16 operand, so no
     stand-alone cast/mask pass runs between GEMMs.
     ``bn_below`` = {"s": saved dict of the conv block whose output is this block's input}: the last launch also forms
-    that block's BatchNorm-backward sums (returned as ``bn_below["sums"]`` when the shapes allow the fusion)."""
+    that block's BatchNorm-backward sums (returned as ``bn_below["sums"]`` when the shapes allow the fusion).
+    Which launches run: ``block_bwd_plan`` of the plan the forward saved."""
     blk = s["blk"]
     p = s["p"]
     s1, s2, s3 = s["seeds"]
     B, L = s["B"], s["L"]
+    M, D = s["x1"].shape
     at = blk.self_attn
+    yb = bn_below["s"]["y"] if bn_below is not None else None
+    form = block_bwd_plan(s["plan"], yb is not None and emit_for is None and yb.shape[2] == 128
+                          and bn_below["s"]["pool"] == 1 and yb.shape[0] * yb.shape[1] == M)
     res_rows = 0
     if isinstance(dx2, tuple):                          # (one fp32 row per sample (B, D), tokens per sample): pooled_head_bwd
         rows, per = dx2
-        M, D = dy2.shape
-        _, _, ci, co = ops.weights.get(at.out_proj.weight, True)
-        if D == 128 and M % 32 == 0 and ci == 128 and co == 128 and not _NO_GEMM2:
+        if form.head_rows:
             dx2, res_rows = rows, per                   # the LayerNorm-backward launch reads the row (res_rows)
         else:                                           # no consumer for the row form: materialise the token gradients
             dx2 = rows.view(-1, 1, D).expand(-1, per, D).reshape(M, D).contiguous()
-    else:
-        M, D = dx2.shape
     # FFN second linear:  x2 = x1 + drop(g W2^T + b2);  g = drop(act(z))
     if dy2 is None:
         dy2 = _mask_cast(g_f32=dx2, drop_p=p, seed=s3)
@@ -403,16 +411,11 @@ def transformer_block_bwd(bag: GradBag, s: dict, dx2: torch.Tensor, dy2=None, em
     dgb = _zeros((REPL, 2, D), dx2)
     # attention output projection:  x1 = x0 + drop(o Wo^T + bo): at width 128 its data gradient is a second GEMM inside the
     # launch above it (FFN-1 data gradient + norm2 backward), fed by the masked rows before they leave the workgroup
-    holder = []
-    g2 = None
-    if D == 128 and M % 32 == 0:
-        _, wd_o, cinp_o, coutp_o = ops.weights.get(at.out_proj.weight, True)
-        if cinp_o == 128 and coutp_o == 128:
-            g2 = (wd_o, holder)
-    n1 = s["z"].shape[-1]
-    if g2 is not None and ffn_rows_bwd_fused([s]):
+    wd_o = ops.weights.get(at.out_proj.weight, True)[1] if form.ffn in ("ffn_rows", "ln_gemm2") else None
+    if form.ffn == "ffn_rows":
         # ... and with an FFN width that fits the workgroup's LDS the FFN-2 data gradient heads the same launch: the dz rows
         # feed the FFN-1 data gradient before they leave the workgroup (mm_ffn_rows_bwd); the three weight gradients as below
+        n1 = s["z"].shape[-1]
         _, wd2, cinp2, coutp2 = ops.weights.get(blk.linear2.weight, True)
         _, wd1, cinp1, coutp1 = ops.weights.get(blk.linear1.weight, True)
         if (cinp2, coutp2, cinp1, coutp1) != (n1, D, D, n1):
@@ -423,17 +426,15 @@ def transformer_block_bwd(bag: GradBag, s: dict, dx2: torch.Tensor, dy2=None, em
         _hip.call("mm_ffn_rows_bwd", dy2, wd2, M, n1, s["z"], ACT[blk._act], float(p), int(s2), dz, wd1, s["x1"], s["st2"],
                   blk.norm2.weight, dx2, int(res_rows), dx1, dyo, dgb, float(p), int(s1), ops.EP(), wd_o, do)
         linear_bwd(bag, dz, s["h2"], blk.linear1.weight, blk.linear1.bias, need_dx=False)
-        holder.append(do)
     else:
         dz = linear_bwd(bag, dy2, s["g"], blk.linear2.weight, blk.linear2.bias, below=(s["z"], blk._act, p, s2))
-        _linear_ln_bwd(bag, dz, s["h2"], blk.linear1, None, s["x1"], s["st2"], blk.norm2, dx2, dx1, dyo, dgb,
-                       float(p), int(s1), gemm2=g2, res_rows=res_rows)
+        do = _linear_ln_bwd(bag, form.ffn, dz, s["h2"], blk.linear1.weight, blk.linear1.bias, s["x1"], s["st2"], blk.norm2,
+                            dx2, dx1, dyo, dgb, float(p), int(s1), w2=wd_o, res_rows=res_rows)
     _ln_param_grads(bag, blk.norm2, dgb, D)
-    if holder:
-        do = holder[0]
-        linear_bwd(bag, dyo, s["o"].view(M, D), at.out_proj.weight, at.out_proj.bias, need_dx=False)
-    else:
+    if do is None:
         do = linear_bwd(bag, dyo, s["o"].view(M, D), at.out_proj.weight, at.out_proj.bias)
+    else:
+        linear_bwd(bag, dyo, s["o"].view(M, D), at.out_proj.weight, at.out_proj.bias, need_dx=False)
     dqkv = _empty((B, L, 3 * D), _BF, dx2)
     delta = _empty((B, blk.nhead, L), _F32, dx2)
     dh = D // blk.nhead
@@ -445,7 +446,7 @@ def transformer_block_bwd(bag: GradBag, s: dict, dx2: torch.Tensor, dy2=None, em
     emit = _empty((M, D), _BF, dx2) if emit_for is not None else None
     ep, es = emit_for if emit_for is not None else (0.0, 0)
     dgb = _zeros((REPL, 2, D), dx2)
-    _linear_ln_bwd(bag, dqkv.view(M, 3 * D), s["h1"], None, (at.in_proj_weight, at.in_proj_bias), s["x"], s["st1"],
+    _linear_ln_bwd(bag, form.qkv, dqkv.view(M, 3 * D), s["h1"], at.in_proj_weight, at.in_proj_bias, s["x"], s["st1"],
                    blk.norm1, dx1, dx0, emit, dgb, float(ep), int(es), bn_below=bn_below)
     _ln_param_grads(bag, blk.norm1, dgb, D)
     return dx0, emit
@@ -455,47 +456,34 @@ def pooled_head_bwd(bag: GradBag, s: dict, dout: torch.Tensor, emit_for=None, ro
     """dout fp32 (B, H) -> d tokens fp32 (B, L, D); with ``emit_for`` = (p, seed) of the consumer also its
     dropout-masked bf16 copy, returned as a pair (fused head only, else None).
     ``rows_only`` (fused head): returns (d pooled SUM fp32 (B, D), 1 / L) instead - every token's gradient is that row
-    times the scale, and a consumer that can take it in this form (mm_bn_act_bwd_*_bcast) saves the (B, L, D) tensor."""
+    times the scale, and a consumer that can take it in this form (mm_bn_act_bwd_*_bcast) saves the (B, L, D) tensor;
+    with ``emit_for`` (the chain's form) ((one fp32 row per sample for the consumer's skip path, L), masked bf16 tokens for
+    its GEMMs)."""
     lin = s["lin"]
-    if s.get("fused") and rows_only and emit_for is None and not _NO_BCAST:
-        B, L, D = s["B"], s["L"], s["D"]
-        N = lin.weight.shape[0]
-        dout = dout.contiguous()
-        dz = _empty((B, N), _BF, dout)
-        dp = _empty((B, 1, D), _F32, dout)
-        _hip.call("mm_pooled_head_bwd", dout, s["z"], lin.weight, dz, dp, None, B, 1, D, N, ACT[s["act"]],
-                  float(s["drop_p"]), int(s["seed"]), 0.0, 0, ops.EP())
-        linear_bwd(bag, dz, s["pooled"], lin.weight, lin.bias, need_dx=False)
-        return dp.view(B, D), 1.0 / L
-    if s.get("fused") and rows_only and emit_for is not None and not _NO_BCAST:
-        # the chain's form: masked bf16 tokens for the consumer's GEMMs + the one fp32 row per sample for its skip path
-        B, L, D = s["B"], s["L"], s["D"]
-        N = lin.weight.shape[0]
-        dout = dout.contiguous()
-        dz = _empty((B, N), _BF, dout)
-        rows = _empty((B, D), _F32, dout)
-        emit = _empty((B, L, D), _BF, dout)
-        _hip.call("mm_pooled_head_bwd_rows", dout, s["z"], lin.weight, dz, rows, emit, B, L, D, N, ACT[s["act"]],
-                  float(s["drop_p"]), int(s["seed"]), float(emit_for[0]), int(emit_for[1]), ops.EP())
-        linear_bwd(bag, dz, s["pooled"], lin.weight, lin.bias, need_dx=False)
-        return (rows, L), emit
+    B, L, D = s["B"], s["L"], s["D"]
     if s.get("fused"):
-        B, L, D = s["B"], s["L"], s["D"]
         N = lin.weight.shape[0]
         dout = dout.contiguous()
+        rows = rows_only and not _NO_BCAST
+        # only the entry point, the gradient buffer and the token count the kernel spreads it over differ
+        if rows and emit_for is not None:
+            entry, shape, Lk = "mm_pooled_head_bwd_rows", (B, D), L
+        else:
+            entry, shape, Lk = "mm_pooled_head_bwd", (B, 1 if rows else L, D), 1 if rows else L
         dz = _empty((B, N), _BF, dout)
-        dx = _empty((B, L, D), _F32, dout)
+        dx = _empty(shape, _F32, dout)
         emit = _empty((B, L, D), _BF, dout) if emit_for is not None else None
         ep, es = emit_for if emit_for is not None else (0.0, 0)
-        _hip.call("mm_pooled_head_bwd", dout, s["z"], lin.weight, dz, dx, emit, B, L, D, N, ACT[s["act"]],
+        _hip.call(entry, dout, s["z"], lin.weight, dz, dx, emit, B, Lk, D, N, ACT[s["act"]],
                   float(s["drop_p"]), int(s["seed"]), float(ep), int(es), ops.EP())
         linear_bwd(bag, dz, s["pooled"], lin.weight, lin.bias, need_dx=False)
+        if rows:
+            return ((dx, L), emit) if emit_for is not None else (dx.view(B, D), 1.0 / L)
         return (dx, emit) if emit_for is not None else dx
     if emit_for is not None:
         return pooled_head_bwd(bag, s, dout), None
     dz = _mask_cast(g_f32=dout.contiguous(), z=s["z"], act=s["act"], drop_p=s["drop_p"], seed=s["seed"])
     dpool = linear_bwd(bag, dz, s["pooled"], lin.weight, lin.bias, dx_f32=True)
-    B, L, D = s["B"], s["L"], s["D"]
     dx = _empty((B, L, D), _F32, dout)
     _hip.call("mm_meanpool_bwd", dpool, dx, B, L, D)
     return dx

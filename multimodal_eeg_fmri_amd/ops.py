@@ -17,7 +17,7 @@ import functools
 import math
 import os
 import weakref
-from typing import Dict, List, Optional
+from typing import Dict, List, NamedTuple, Optional
 
 import torch
 
@@ -739,6 +739,157 @@ def conv_bn_act(xb: torch.Tensor, conv, bn, *, act="gelu", pool=1, training=Fals
     return {"f32": of, "bf16": ob, "pre": None, "prenorm": prenorm}, saved
 
 
+class BlockPlan(NamedTuple):
+    """which launches one transformer block runs, decided from shapes, consumers and the A/B knobs alone (``block_plan``).
+    ``transformer_block_fwd`` dispatches on it and saves it; the backward reads it (``autograd.block_bwd_plan``)."""
+    ln_fused: bool          # width 128, rows in groups of 32: the LayerNorms ride in the epilogue of the GEMM above them
+    front: str              # out-projection .. first FFN Linear: "rows" (mm_ffn_rows_fwd: the tail and its consumers too) |
+    #                         "ln_gemm2_act" (mm_linear_fwd_ln_gemm2_act) | "ln" (mm_linear_fwd_ln + a GEMM) | "generic" (3 launches)
+    tail: str               # second FFN Linear: "rows" (ran in the front's launch) | "meanpool" (mm_linear_fwd_meanpool) |
+    #                         "ln_gemm2" (mm_linear_fwd_ln_gemm2) | "ln" (mm_linear_fwd_ln) | "generic"
+    qkv_fused: bool         # the next block's QKV projection runs on its norm1 rows in this block's last launch
+    out_proj_128: bool      # the out-projection's images are 128 x 128 (the backward can run its data gradient as a second GEMM)
+    ffn_rows_width: bool    # the FFN width is a multiple of 128 up to 512 (the hidden tile fits the workgroup's LDS)
+
+
+def block_plan(D: int, M: int, n1: int, *, pool_out: bool = False, next_norm: bool = False, next_nq: int = 0) -> BlockPlan:
+    """the plan of a ``D``-wide block with FFN width ``n1`` on ``M`` = B * L rows.  ``pool_out`` / ``next_norm``: which consumer
+    the finished rows have; ``next_nq``: the width of the next block's packed QKV projection (0 = no next block).  Pure: the
+    weight images' padded widths are ``cpad`` of the Linear shapes, nothing is built or recorded; the knobs are read here.
+    The QKV projection rides along only with ``M * next_nq < 2**32``, from either launch: the rule in front of
+    mm_linear_fwd_ln_gemm2 once lacked that guard, but the kernel was never safe beyond it (no test reaches that size)."""
+    ln_fused = D == 128 and M % 32 == 0
+    k128 = cpad(D) == 128       # the images that take D-wide rows (out-projection, first FFN Linear, QKV projection) are 128 wide
+    ffn1 = ln_fused and k128 and n1 % 128 == 0 and M * n1 < (1 << 32) and not _NO_FFN1_FUSE
+    rows = ffn1 and n1 <= 512 and cpad(n1) == n1 and not _NO_FFN_ROWS and (pool_out or next_norm)
+    qkv = bool(ln_fused and k128 and next_norm and not pool_out and next_nq > 0 and next_nq % 128 == 0
+               and M * next_nq < (1 << 32) and not _NO_QKV_FUSE)
+    front = "rows" if rows else "ln_gemm2_act" if ffn1 else "ln" if ln_fused else "generic"
+    if rows or pool_out:
+        tail = "rows" if rows else "meanpool"
+    else:
+        tail = ("ln_gemm2" if qkv else "ln") if next_norm and ln_fused else "generic"
+    return BlockPlan(ln_fused, front, tail, qkv, k128, n1 % 128 == 0 and n1 <= 512)
+
+
+def _ln_front_begin(blk, x2, save, need_dgrad):
+    """the three LayerNorm-fused fronts: out-projection and first FFN Linear images, buffers of x1, norm2(x1) and its statistics"""
+    M, D = x2.shape
+    wf, _, cinp, _ = weights.get(blk.self_attn.out_proj.weight, need_dgrad)
+    x1 = _empty((M, D), _F32, x2)
+    h2 = _empty((M, D), _BF, x2)
+    st2 = _empty((M, 2), _F32, x2) if save else None
+    w1 = weights.get(blk.linear1.weight, need_dgrad)[0]
+    return wf, cinp, w1, x1, h2, st2
+
+
+def _next_rows(x2, save, next_blk, qkv_fused, need_dgrad):
+    """the next block's norm1 rows and statistics, with ``qkv_fused`` its QKV image, bias, width and q | k | v buffer too"""
+    M, D = x2.shape
+    hn = _empty((M, D), _BF, x2)
+    stn = _empty((M, 2), _F32, x2) if save else None
+    if not qkv_fused:
+        return hn, stn, None, None, 0, None
+    at = next_blk.self_attn
+    wq, _, cq, _ = weights.get(at.in_proj_weight, need_dgrad)
+    if cq != D:
+        raise _hip.HipLibraryError(f"transformer block: the next block's QKV image is {cq} wide, the rows {D}")
+    nq = at.in_proj_weight.shape[0]
+    return hn, stn, wq, at.in_proj_bias, nq, _empty((M, nq), _BF, x2)
+
+
+def _ffn1_rows(blk, h2, p, s2, save, need_dgrad):
+    """the first FFN Linear as its own GEMM -> (hidden bf16, pre-activation or None)"""
+    f1 = linear_rows(h2, blk.linear1.weight, blk.linear1.bias, act=blk._act, out_pre=save, drop_p=p, seed=s2, need_dgrad=need_dgrad)
+    return f1["bf16"], f1["pre"]
+
+
+def _block_rows(blk, o, x2, p, seeds, save, need_dgrad, plan, L, pool_out, next_norm, next_blk):
+    """front "rows": everything after attention is ONE launch - out-projection, norm2, both FFN Linears on the hidden tile the
+    workgroup still holds, and the consumers of the finished rows (the mean over time, or the next block's norm1 and QKV
+    projection); without a backward the hidden tensor is never written -> (x1, h2, st2, g, z, x2o, next_prenorm)"""
+    M, D = x2.shape
+    s1, s2, s3 = seeds
+    n1 = blk.linear1.weight.shape[0]
+    wf, cinp, w1, x1, h2, st2 = _ln_front_begin(blk, x2, save, need_dgrad)
+    z1 = _empty((M, n1), _BF, x2) if save else None
+    w2 = weights.get(blk.linear2.weight, need_dgrad)[0]
+    g1 = _empty((M, n1), _BF, x2) if save else None
+    x2o = _empty((M, D), _F32, x2)
+    hn = stn = wq = bq = qn = nxt = None
+    nq = 0
+    if pool_out is None:
+        hn, stn, wq, bq, nq, qn = _next_rows(x2, save, next_blk, plan.qkv_fused, need_dgrad)
+        nxt = (hn, stn, qn) if qn is not None else (hn, stn)
+    _hip.call("mm_ffn_rows_fwd", o, wf, M, cinp, blk.self_attn.out_proj.bias, x2, x1, float(p), int(s1),
+              EP(), blk.norm2.weight, blk.norm2.bias, float(blk.norm2.eps), h2, st2, w1, blk.linear1.bias, n1, g1, z1,
+              ACT[blk._act], float(p), int(s2), w2, blk.linear2.bias, x2o, float(p), int(s3),
+              None if hn is None else next_norm.weight, None if hn is None else next_norm.bias,
+              float(next_norm.eps) if hn is not None else 0.0, hn, stn, wq, bq, nq, qn, pool_out,
+              L if pool_out is not None else 0)
+    return x1, h2, st2, g1, z1, x2o, nxt
+
+
+def _front_ln_gemm2_act(blk, o, x2, p, s1, s2, save, need_dgrad):
+    """front "ln_gemm2_act": the first FFN Linear (GELU, Dropout, pre-activation copy) runs on norm2's rows inside the
+    out-projection's launch -> (x1, h2, st2, g, z)"""
+    M = x2.shape[0]
+    n1 = blk.linear1.weight.shape[0]
+    wf, cinp, w1, x1, h2, st2 = _ln_front_begin(blk, x2, save, need_dgrad)
+    z1 = _empty((M, n1), _BF, x2) if save else None
+    weights.get(blk.linear2.weight, need_dgrad)             # (requested with the other two: a cold cache builds all three here)
+    g1 = _empty((M, n1), _BF, x2)
+    _hip.call("mm_linear_fwd_ln_gemm2_act", o, wf, M, cinp, blk.self_attn.out_proj.bias, x2, x1, float(p),
+              int(s1), EP(), blk.norm2.weight, blk.norm2.bias, float(blk.norm2.eps), h2, st2, w1, blk.linear1.bias,
+              n1, g1, z1, ACT[blk._act], float(p), int(s2))
+    return x1, h2, st2, g1, z1
+
+
+def _front_ln(blk, o, x2, p, s1, s2, save, need_dgrad):
+    """front "ln": norm2 in the out-projection's epilogue, the first FFN Linear as its own GEMM -> (x1, h2, st2, g, z)"""
+    wf, cinp, _, x1, h2, st2 = _ln_front_begin(blk, x2, save, need_dgrad)
+    _hip.call("mm_linear_fwd_ln", o, wf, x2.shape[0], cinp, blk.self_attn.out_proj.bias, x2, x1, float(p), int(s1),
+              EP(), blk.norm2.weight, blk.norm2.bias, float(blk.norm2.eps), h2, st2)
+    return (x1, h2, st2) + _ffn1_rows(blk, h2, p, s2, save, need_dgrad)
+
+
+def _front_generic(blk, o, x2, p, s1, s2, save, need_dgrad):
+    """front "generic": out-projection, norm2 and the first FFN Linear as three launches -> (x1, h2, st2, g, z)"""
+    at = blk.self_attn
+    x1 = linear_rows(o, at.out_proj.weight, at.out_proj.bias, residual=x2, out_f32=True, out_bf16=False, drop_p=p, seed=s1,
+                     need_dgrad=need_dgrad)["f32"]
+    h2, st2 = layernorm(x1, blk.norm2, save)
+    return (x1, h2, st2) + _ffn1_rows(blk, h2, p, s2, save, need_dgrad)
+
+
+_BLOCK_FRONTS = {"ln_gemm2_act": _front_ln_gemm2_act, "ln": _front_ln, "generic": _front_generic}
+
+
+def _tail_meanpool(blk, g, x1, p, s3, need_dgrad, L, pool_out):
+    """tail "meanpool": the second FFN Linear also accumulates the mean over time of its output rows -> x2o"""
+    M, D = x1.shape
+    wf, _, cinp, _ = weights.get(blk.linear2.weight, need_dgrad)
+    x2o = _empty((M, D), _F32, x1)
+    _hip.call("mm_linear_fwd_meanpool", g, wf, M, cinp, blk.linear2.bias, x1, x2o, float(p), int(s3), EP(), pool_out, L)
+    return x2o
+
+
+def _tail_ln(blk, g, x1, p, s3, need_dgrad, save, next_norm, next_blk, qkv_fused):
+    """tails "ln" / "ln_gemm2": the next block's norm1 in the second FFN Linear's epilogue, with ``qkv_fused`` followed by that
+    block's QKV projection as a second GEMM of the launch -> (x2o, next_prenorm)"""
+    M, D = x1.shape
+    wf, _, cinp, _ = weights.get(blk.linear2.weight, need_dgrad)
+    x2o = _empty((M, D), _F32, x1)
+    hn, stn, wq, bq, nq, qn = _next_rows(x1, save, next_blk, qkv_fused, need_dgrad)
+    args = (g, wf, M, cinp, blk.linear2.bias, x1, x2o, float(p), int(s3), EP(), next_norm.weight, next_norm.bias,
+            float(next_norm.eps), hn, stn)
+    if qkv_fused:
+        _hip.call("mm_linear_fwd_ln_gemm2", *args, wq, bq, nq, qn)
+        return x2o, (hn, stn, qn)
+    _hip.call("mm_linear_fwd_ln", *args)
+    return x2o, (hn, stn)
+
+
 def transformer_block_fwd(x: torch.Tensor, blk, training: bool, need_dgrad: bool = False,
                           save: Optional[bool] = None, pool_out: Optional[torch.Tensor] = None,
                           prenorm=None, next_norm=None, mask=None, next_blk=None):
@@ -750,124 +901,44 @@ def transformer_block_fwd(x: torch.Tensor, blk, training: bool, need_dgrad: bool
     its input (``prenorm`` = (norm1(x) bf16, stats) handed in by the block below, ``next_norm`` = the next
     block's norm1, whose output is then returned in ``saved['next_prenorm']`` / as third result).  With ``next_blk`` the
     same launch also runs that block's QKV projection on those rows (a second GEMM: the third result then carries the
-    packed q | k | v as its third element).  With a consumer for the finished rows (``pool_out`` or ``next_norm``) and an
-    FFN width that is a multiple of 128 up to 512, everything after attention is ONE launch (``mm_ffn_rows_fwd``)."""
+    packed q | k | v as its third element).  Which launches run is decided once, by ``block_plan``; the plan is kept in
+    ``saved['plan']``.  norm1 / QKV projection and attention first, then the plan's front and tail."""
     B, L, D = x.shape
     M = B * L
     save = training if save is None else save
     p = blk.dropout.p if training else 0.0
+    pa = float(blk.self_attn.dropout) if training else 0.0      # attention-probability dropout
+    plan = block_plan(D, M, blk.linear1.weight.shape[0], pool_out=pool_out is not None, next_norm=next_norm is not None,
+                      next_nq=next_blk.self_attn.in_proj_weight.shape[0] if next_blk is not None else 0)
+    sa = _next_seed() if pa > 0 else 0
+    s1, s2, s3 = (_next_seed(), _next_seed(), _next_seed()) if p > 0 else (0, 0, 0)
     x2 = x.view(M, D)
-    fuse_ln = D == 128 and M % 32 == 0
     h1, st1 = prenorm[:2] if prenorm is not None else layernorm(x2, blk.norm1, save)
     if prenorm is not None and len(prenorm) > 2:            # the block below already projected its fused LayerNorm rows
         qkv = prenorm[2]
     else:
         qkv = linear_rows(h1, blk.self_attn.in_proj_weight, blk.self_attn.in_proj_bias,
                           need_dgrad=need_dgrad)["bf16"]
-    pa = float(blk.self_attn.dropout) if training else 0.0      # attention-probability dropout
-    sa = _next_seed() if pa > 0 else 0
     o, lse = attention(qkv.view(B, L, 3 * D), blk.nhead, save, pa, sa, mask)
-    s1 = _next_seed() if p > 0 else 0
-    f1 = None
-    s2 = None
-    rows = False
+    o2 = o.view(M, D)
     nxt = None
-    if fuse_ln:
-        wf, _, cinp, _ = weights.get(blk.self_attn.out_proj.weight, need_dgrad)
-        x1 = _empty((M, D), _F32, x)
-        h2 = _empty((M, D), _BF, x)
-        st2 = _empty((M, 2), _F32, x) if save else None
-        w1, _, c1, _ = weights.get(blk.linear1.weight, need_dgrad)
-        n1 = blk.linear1.weight.shape[0]
-        if c1 == 128 and n1 % 128 == 0 and M * n1 < (1 << 32) and not _NO_FFN1_FUSE:
-            # the first FFN Linear (GELU, Dropout, pre-activation copy) runs on norm2's rows inside the out-projection's launch
-            s2 = _next_seed() if p > 0 else 0
-            z1 = _empty((M, n1), _BF, x) if save else None
-            w2, _, c2, _ = weights.get(blk.linear2.weight, need_dgrad)
-            rows = (cinp == 128 and n1 <= 512 and c2 == n1 and not _NO_FFN_ROWS
-                    and (pool_out is not None or next_norm is not None))
-            if rows:
-                # ... and so does the second FFN Linear, on the hidden tile the workgroup still holds, with its consumers:
-                # the block's whole row-wise part is this one launch, and without a backward the hidden tensor is never written
-                s3 = _next_seed() if p > 0 else 0
-                g1 = _empty((M, n1), _BF, x) if save else None
-                x2o = _empty((M, D), _F32, x)
-                hn = stn = wq = bq = qn = None
-                nq = 0
-                if pool_out is None:
-                    hn = _empty((M, D), _BF, x)
-                    stn = _empty((M, 2), _F32, x) if save else None
-                    if next_blk is not None and not _NO_QKV_FUSE:
-                        wq, _, cq, _ = weights.get(next_blk.self_attn.in_proj_weight, need_dgrad)
-                        nq = next_blk.self_attn.in_proj_weight.shape[0]
-                        if cq != 128 or nq % 128 or M * nq >= (1 << 32):
-                            wq, nq = None, 0
-                    if wq is not None:
-                        bq = next_blk.self_attn.in_proj_bias
-                        qn = _empty((M, nq), _BF, x)
-                    nxt = (hn, stn, qn) if wq is not None else (hn, stn)
-                _hip.call("mm_ffn_rows_fwd", o.view(M, D), wf, M, cinp, blk.self_attn.out_proj.bias, x2, x1, float(p), int(s1),
-                          EP(), blk.norm2.weight, blk.norm2.bias, float(blk.norm2.eps), h2, st2, w1, blk.linear1.bias, n1, g1, z1,
-                          ACT[blk._act], float(p), int(s2), w2, blk.linear2.bias, x2o, float(p), int(s3),
-                          None if hn is None else next_norm.weight, None if hn is None else next_norm.bias,
-                          float(next_norm.eps) if hn is not None else 0.0, hn, stn, wq, bq, nq, qn, pool_out,
-                          L if pool_out is not None else 0)
-            else:
-                g1 = _empty((M, n1), _BF, x)
-                _hip.call("mm_linear_fwd_ln_gemm2_act", o.view(M, D), wf, M, cinp, blk.self_attn.out_proj.bias, x2, x1, float(p),
-                          int(s1), EP(), blk.norm2.weight, blk.norm2.bias, float(blk.norm2.eps), h2, st2, w1, blk.linear1.bias,
-                          n1, g1, z1, ACT[blk._act], float(p), int(s2))
-            f1 = {"bf16": g1, "pre": z1, "f32": None}
-        else:
-            _hip.call("mm_linear_fwd_ln", o.view(M, D), wf, M, cinp, blk.self_attn.out_proj.bias, x2, x1, float(p), int(s1),
-                      EP(), blk.norm2.weight, blk.norm2.bias, float(blk.norm2.eps), h2, st2)
+    if plan.front == "rows":
+        x1, h2, st2, g, z, x2o, nxt = _block_rows(blk, o2, x2, p, (s1, s2, s3), save, need_dgrad, plan, L, pool_out,
+                                                  next_norm, next_blk)
     else:
-        x1 = linear_rows(o.view(M, D), blk.self_attn.out_proj.weight, blk.self_attn.out_proj.bias,
-                         residual=x2, out_f32=True, out_bf16=False, drop_p=p, seed=s1,
-                         need_dgrad=need_dgrad)["f32"]
-        h2, st2 = layernorm(x1, blk.norm2, save)
-    if f1 is None:
-        s2 = _next_seed() if p > 0 else 0
-        f1 = linear_rows(h2, blk.linear1.weight, blk.linear1.bias, act=blk._act, out_pre=save,
-                         drop_p=p, seed=s2, need_dgrad=need_dgrad)
-    if not rows:
-        s3 = _next_seed() if p > 0 else 0
-    if rows:
-        pass                                                    # linear2 and its consumers ran in the launch above
-    elif pool_out is not None:
-        wf, _, cinp, _ = weights.get(blk.linear2.weight, need_dgrad)
-        x2o = _empty((M, D), _F32, x)
-        _hip.call("mm_linear_fwd_meanpool", f1["bf16"], wf, M, cinp, blk.linear2.bias, x1, x2o, float(p), int(s3),
-                  EP(), pool_out, L)
-    elif next_norm is not None and fuse_ln:
-        wf, _, cinp, _ = weights.get(blk.linear2.weight, need_dgrad)
-        x2o = _empty((M, D), _F32, x)
-        hn = _empty((M, D), _BF, x)
-        stn = _empty((M, 2), _F32, x) if save else None
-        wq = None
-        if next_blk is not None and not _NO_QKV_FUSE:
-            wq, _, cq, _ = weights.get(next_blk.self_attn.in_proj_weight, need_dgrad)
-            if cq != 128 or next_blk.self_attn.in_proj_weight.shape[0] % 128:
-                wq = None
-        if wq is not None:
-            nq = next_blk.self_attn.in_proj_weight.shape[0]
-            qn = _empty((M, nq), _BF, x)
-            _hip.call("mm_linear_fwd_ln_gemm2", f1["bf16"], wf, M, cinp, blk.linear2.bias, x1, x2o, float(p), int(s3), EP(),
-                      next_norm.weight, next_norm.bias, float(next_norm.eps), hn, stn, wq, next_blk.self_attn.in_proj_bias,
-                      nq, qn)
-            nxt = (hn, stn, qn)
+        x1, h2, st2, g, z = _BLOCK_FRONTS[plan.front](blk, o2, x2, p, s1, s2, save, need_dgrad)
+        if plan.tail == "meanpool":
+            x2o = _tail_meanpool(blk, g, x1, p, s3, need_dgrad, L, pool_out)
+        elif plan.tail in ("ln", "ln_gemm2"):
+            x2o, nxt = _tail_ln(blk, g, x1, p, s3, need_dgrad, save, next_norm, next_blk, plan.qkv_fused)
         else:
-            _hip.call("mm_linear_fwd_ln", f1["bf16"], wf, M, cinp, blk.linear2.bias, x1, x2o, float(p), int(s3), EP(),
-                      next_norm.weight, next_norm.bias, float(next_norm.eps), hn, stn)
-            nxt = (hn, stn)
-    else:
-        x2o = linear_rows(f1["bf16"], blk.linear2.weight, blk.linear2.bias, residual=x1, out_f32=True,
-                          out_bf16=False, drop_p=p, seed=s3, need_dgrad=need_dgrad)["f32"]
+            x2o = linear_rows(g, blk.linear2.weight, blk.linear2.bias, residual=x1, out_f32=True,
+                              out_bf16=False, drop_p=p, seed=s3, need_dgrad=need_dgrad)["f32"]
     saved = None
     if save:
         saved = dict(x=x2, h1=h1, st1=st1, qkv=qkv, o=o, lse=lse, x1=x1, h2=h2, st2=st2,
-                     z=f1["pre"], g=f1["bf16"], p=p, seeds=(s1, s2, s3), attn_drop=(pa, sa), B=B, L=L, blk=blk,
-                     mask=mask)
+                     z=z, g=g, p=p, seeds=(s1, s2, s3), attn_drop=(pa, sa), B=B, L=L, blk=blk,
+                     mask=mask, plan=plan)
     if next_norm is not None:
         return x2o.view(B, L, D), saved, nxt
     return x2o.view(B, L, D), saved
