@@ -972,6 +972,36 @@ int mm_gatv2_edge_pack(const float* listed, const int* eid, const int* rowptr, c
 int mm_gatv2_edge_pack_bwd(const float* dcsr, const int* pos, const int* tgt, const int* rowptr, const int* indeg,
                            float* dlisted, int Bo, int N, int El, int E, int D, int fill_mean, hipStream_t stream);
 
+/* ---- projection + pooling over time: the tails of the EEG notebook's single-modality baselines (PWOnlyNet, ERPOnlyNet,
+ * EEG_CODE/CrossModal_EEG_scr.ipynb), csrc/timepool.hip.  x = the (B, L, K) output of the third conv block, w (P, K) /
+ * bias (P) the 1 x 1 convolution; the projected (B, L, P) tensor is never written.  Sizes served: K = 128, P a multiple
+ * of 16 up to 512, 1 <= L <= 64 * 65535, B >= 1, B*L*P < 2^32, bins in 1 .. 8; anything else is MM_ERR_UNSUPPORTED
+ * before a launch.
+ * No floating-point atomics: the same bits on every run.  dw / dbias are nullable and ACCUMULATED into (one owner per
+ * element, batch order), as mm_small_linear_bwd's; dx is nullable and WRITTEN, every row, zeros included.
+ *
+ * max tail:  y[b][t][n] = (sum_k x[b][t][k] w[n][k] + bias[n]) * dropout_scale(mm_eff_seed(seed, epoch), (b L + t) P + n)
+ *            pooled[b][n] = max_t y, arg[b][n] = the SMALLEST t that attains it (a dropped element is an exact 0 and
+ *            competes as such; NaN wins).  x, w bf16 (w = the forward image of mm_prep_conv_weight, taps 1), bf16 MFMA
+ *            with fp32 accumulation.
+ *   bwd:     g[b][n] = dpooled[b][n] * keep-scale at (b, arg[b][n], n);  dx[b][t][:] = sum_{n: arg[b][n] = t} g[b][n] w[n][:]
+ *            (bf16, n ascending);  dw[n][:] += sum_b g[b][n] x[b][arg[b][n]][:];  dbias[n] += sum_b g[b][n].
+ * avg tail:  xbin[b][i][:] = mean of x[b][t][:] over t in [floor(i L / bins), ceil((i + 1) L / bins))  (AdaptiveAvgPool1d:
+ *            the bins overlap when bins does not divide L);  pooled[b][p bins + i] = xbin[b][i][:] . w[p][:] + bias[p]
+ *            = Flatten of AdaptiveAvgPool1d(bins)(projection) - the projection is affine, so pooling first is the same
+ *            function.  fp32 throughout, sums in ascending order.
+ *   bwd:     u[b][i][:] = (sum_p dpooled[b][p bins + i] w[p][:]) / len_i;  dx[b][t][:] = sum_{i holding t} u[b][i][:];
+ *            dw[p][:] += sum_b sum_i dpooled[b][p bins + i] xbin[b][i][:];  dbias[p] += sum_{b,i} dpooled[b][p bins + i]. */
+int mm_timepool_max_fwd(const void* x_bf16, const void* w_bf16, const float* bias, float* pooled, int* arg, int B, int L,
+                        int K, int P, float drop_p, uint32_t seed, const uint32_t* seed_epoch, hipStream_t stream);
+int mm_timepool_max_bwd(const float* dpooled, const int* arg, const void* x_bf16, const void* w_bf16, void* dx_bf16,
+                        float* dw, float* dbias, int B, int L, int K, int P, float drop_p, uint32_t seed,
+                        const uint32_t* seed_epoch, hipStream_t stream);
+int mm_timepool_avg_fwd(const float* x_f32, const float* w, const float* bias, float* xbin, float* pooled, int B, int L,
+                        int K, int P, int bins, hipStream_t stream);
+int mm_timepool_avg_bwd(const float* dpooled, const float* xbin, const float* w, float* dx_f32, float* dw, float* dbias,
+                        int B, int L, int K, int P, int bins, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,6 +1,8 @@
 """Training-side classes of the reference's EEG notebook (``EEG_CODE/CrossModal_EEG_scr.ipynb``) on the
 MI355X HIP path: ``PerFoldNormalizer`` (cell 19), ``FocalLoss`` (cell 20), ``ImprovedTriModalFusionNet`` /
-``ImprovedSmartFusionNet`` (cells 21-22), ``FlexibleTrainer`` (cell 23) and ``collate_trimodal`` (cell 24).
+``ImprovedSmartFusionNet`` (cells 21-22), ``FlexibleTrainer`` (cell 23) and ``collate_trimodal`` (cell 24); the
+single-modality baselines ``ERPOnlyNet`` / ``PWOnlyNet`` with ``ERPEncoder`` / ``PowerEncoder`` / ``BaseEEGModel`` and
+``evaluate_late_fusion``.
 
 SURVEY.md §8 (f).1 / (f).3: same names, constructor arguments, batch conventions and checkpoint
 container (``epoch / model_state_dict / optimizer_state_dict / scheduler_state_dict / metrics``) as
@@ -83,6 +85,124 @@ class ImprovedSmartFusionNet(nn.Module):
 
     def get_weight_history(self):
         return self.fusion_weight_history
+
+
+class BaseEEGModel(nn.Module):
+    """(cell 5) the common forward signature of the notebook's four models"""
+
+    def forward(self, erp: Optional[torch.Tensor] = None, pw: Optional[torch.Tensor] = None,
+                return_feats: bool = False) -> torch.Tensor:
+        raise NotImplementedError
+
+
+class PowerEncoder(nn.Module):
+    """(cell 8) three Conv1d(k=3)-BatchNorm1d-ReLU blocks at 32 / 64 / 128 channels, MaxPool1d(2) after the first two, a
+    1 x 1 projection to ``out_dim`` and dropout: (B, C, T) -> (B, T / 4, out_dim) fp32.  T % 4 == 0 (the kernels pool even
+    lengths; MaxPool1d's floor on an odd length is not served), out_dim a multiple of 16 up to 512."""
+
+    def __init__(self, in_channels: int, out_dim: int = 128, dropout: float = 0.2):
+        super().__init__()
+        self.conv1 = nn.Conv1d(in_channels, 32, kernel_size=3, padding=1)
+        self.bn1 = nn.BatchNorm1d(32)
+        self.conv2 = nn.Conv1d(32, 64, kernel_size=3, padding=1)
+        self.bn2 = nn.BatchNorm1d(64)
+        self.conv3 = nn.Conv1d(64, 128, kernel_size=3, padding=1)
+        self.bn3 = nn.BatchNorm1d(128)
+        self.proj = nn.Conv1d(128, out_dim, kernel_size=1)
+        self.dropout = nn.Dropout(dropout)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        return ops.eeg_step_encoder_forward(self, x, "pw")
+
+
+class PWOnlyNet(BaseEEGModel):
+    """(cell 9) the power-only baseline: PowerEncoder -> max over time -> Linear-BatchNorm1d-GELU-Dropout(0.5)-Linear.
+    The projection, its dropout and the max run as one launch (csrc/timepool.hip); ``return_feats`` is accepted and
+    ignored, as in the notebook."""
+
+    def __init__(self, in_channels: int, pw_out: int = 128, hidden: int = 64, n_classes: int = 2):
+        super().__init__()
+        self.pw_enc = PowerEncoder(in_channels=in_channels, out_dim=pw_out)
+        self.pool = nn.AdaptiveMaxPool1d(1)
+        self.head = nn.Sequential(
+            nn.Flatten(),
+            nn.Linear(pw_out, hidden),
+            nn.BatchNorm1d(hidden),
+            nn.GELU(),
+            nn.Dropout(0.5),
+            nn.Linear(hidden, n_classes)
+        )
+
+    def forward(self, erp: Optional[torch.Tensor] = None, pw: torch.Tensor = None,
+                return_feats: bool = False) -> torch.Tensor:
+        return ops.eeg_baseline_forward(self, pw, "pw")
+
+
+class ERPEncoder(nn.Module):
+    """(cell 12) Conv1d(k=7 / 5 / 3)-BatchNorm1d-ReLU blocks at 32 / 64 / 128 channels, MaxPool1d(2) after the first two and
+    a 1 x 1 projection of every time step: (B, C, T) -> (B, T / 4, out_dim) fp32.  Its ``dropout`` module is never applied
+    (as in the notebook).  T % 4 == 0, out_dim a multiple of 16 up to 512."""
+
+    def __init__(self, in_channels: int = 18, out_dim: int = 128, dropout: float = 0.2):
+        super().__init__()
+        self.out_dim = out_dim
+        self.conv1 = nn.Conv1d(in_channels, 32, kernel_size=7, padding=3)
+        self.bn1 = nn.BatchNorm1d(32)
+        self.conv2 = nn.Conv1d(32, 64, kernel_size=5, padding=2)
+        self.bn2 = nn.BatchNorm1d(64)
+        self.conv3 = nn.Conv1d(64, 128, kernel_size=3, padding=1)
+        self.bn3 = nn.BatchNorm1d(128)
+        self.pool = nn.MaxPool1d(2)
+        self.step_proj = nn.Conv1d(128, out_dim, kernel_size=1)
+        self.dropout = nn.Dropout(dropout)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        return ops.eeg_step_encoder_forward(self, x, "erp")
+
+
+class ERPOnlyNet(BaseEEGModel):
+    """(cell 13) the ERP-only baseline: ERPEncoder -> AdaptiveAvgPool1d(4) -> Flatten -> Linear-BatchNorm1d-GELU-
+    Dropout(0.5)-Linear.  A (B, T, C) batch with T > C is transposed first.  The time bins are averaged before the
+    projection (csrc/timepool.hip: the same function, 4 projected rows per sample)."""
+
+    def __init__(self, in_dim: int, erp_out: int = 128, hidden: int = 64, n_classes: int = 2):
+        super().__init__()
+        self.erp_enc = ERPEncoder(in_channels=in_dim, out_dim=erp_out)
+        self.pool = nn.AdaptiveAvgPool1d(4)
+        self.head = nn.Sequential(
+            nn.Flatten(),
+            nn.Linear(erp_out * 4, hidden),
+            nn.BatchNorm1d(hidden),
+            nn.GELU(),
+            nn.Dropout(0.5),
+            nn.Linear(hidden, n_classes)
+        )
+
+    def forward(self, erp: torch.Tensor, pw: Optional[torch.Tensor] = None,
+                return_feats: bool = False) -> torch.Tensor:
+        if erp is not None and erp.dim() == 3 and erp.shape[1] > erp.shape[2]:
+            erp = erp.permute(0, 2, 1).contiguous()
+        return ops.eeg_baseline_forward(self, erp, "erp")
+
+
+def evaluate_late_fusion(roc_all: Dict) -> Dict:
+    """(cell 34, without its printing) per fold, the mean of the ERP-only and power-only class probabilities decides;
+    ``roc_all[model][fold] = (y_true, probabilities (n, classes), ...)`` -> the means over the folds of the fused
+    accuracy and weighted F1 and of either baseline's own accuracy"""
+    from .fmri_utils import classification_metrics
+    accs, f1s = [], []
+    for erp_fold, pw_fold in zip(roc_all["erponly"], roc_all["pwonly"]):
+        y_true = np.asarray(erp_fold[0])
+        fused = (np.asarray(erp_fold[1]) + np.asarray(pw_fold[1])) / 2.0
+        m = classification_metrics(y_true, np.argmax(fused, axis=1))
+        accs.append(m["Accuracy"])
+        f1s.append(m["F1"])
+
+    def own(folds):
+        return [float(np.mean(np.asarray(f[0]) == np.argmax(np.asarray(f[1]), axis=1))) for f in folds]
+
+    return {"late_fusion_acc": np.mean(accs), "late_fusion_f1": np.mean(f1s),
+            "erp_acc": np.mean(own(roc_all["erponly"])), "pw_acc": np.mean(own(roc_all["pwonly"]))}
 
 
 def _aug_hash(stream: int, idx: np.ndarray) -> np.ndarray:

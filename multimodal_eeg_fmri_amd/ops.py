@@ -2286,6 +2286,113 @@ def lite_encoder_forward(m, x):
     return out
 
 
+# ---- the EEG notebook's single-modality baselines (crossmodal_eeg_scr.py: ERPOnlyNet / PWOnlyNet; csrc/timepool.hip)
+TIMEPOOL_K = 128                 # the width the tail kernels read: the encoders' fixed third conv block
+TIMEPOOL_P_MAX = 512             # projection widths served: the multiples of 16 up to this
+
+
+def timepool_check(P: int, K: int, L: int, who: str = "timepool"):
+    """the sizes mm_timepool_* serve, refused with ValueError before any launch"""
+    if K != TIMEPOOL_K:
+        raise ValueError(f"{who}: the projection reads {K} channels; the time-pool kernels serve {TIMEPOOL_K}")
+    if P < 16 or P > TIMEPOOL_P_MAX or P % 16:
+        raise ValueError(f"{who}: projection width {P} is not served (a multiple of 16 up to {TIMEPOOL_P_MAX})")
+    if L < 1:
+        raise ValueError(f"{who}: {L} time steps reach the projection (at least 1)")
+
+
+def _baseline_parts(m, kind: str):
+    """(encoder, its 1 x 1 projection) of a baseline net or of a stand-alone encoder"""
+    if kind == "erp":
+        enc = getattr(m, "erp_enc", m)
+        return enc, enc.step_proj
+    if kind == "pw":
+        enc = getattr(m, "pw_enc", m)
+        return enc, enc.proj
+    raise ValueError(f"eeg baseline: kind is 'erp' or 'pw' (got {kind!r})")
+
+
+def eeg_baseline_check(m, x, kind: str, head: bool = True):
+    """shape rules of the baselines, before any launch.  The two MaxPool1d(2) run in the BatchNorm apply pass, which
+    pools even lengths only: T % 4 == 0 (the floor MaxPool1d takes on an odd length is not served)."""
+    enc, proj = _baseline_parts(m, kind)
+    who = type(m).__name__
+    if x is None or x.dim() != 3:
+        raise ValueError(f"{who}: expected a (B, C, T) batch, got {None if x is None else tuple(x.shape)}")
+    B, C, T = x.shape
+    if C != enc.conv1.in_channels:
+        raise ValueError(f"{who}: the batch has {C} channels, the encoder takes {enc.conv1.in_channels}")
+    if T < 4 or T % 4:
+        raise ValueError(f"{who}: T = {T} is not served: the two MaxPool1d(2) need T % 4 == 0 (and T >= 4)")
+    if head and m.training and B < 2:
+        raise ValueError(f"{who}: BatchNorm1d of the head needs at least 2 samples in train mode (got {B})")
+    timepool_check(proj.out_channels, enc.conv3.out_channels, T // 4, who)
+
+
+def _baseline_blocks_eval(enc, x, last_f32: bool):
+    """the three Conv-BN-ReLU[-MaxPool2] blocks, BatchNorm folded into the GEMM epilogue: one launch per block"""
+    r, _ = conv_bn_act(pack_nct(x.float()), enc.conv1, enc.bn1, act="relu", pool=2, training=False)
+    r, _ = conv_bn_act(r["bf16"], enc.conv2, enc.bn2, act="relu", pool=2, training=False)
+    r, _ = conv_bn_act(r["bf16"], enc.conv3, enc.bn3, act="relu", training=False, want_f32=last_f32, want_bf16=not last_f32)
+    return r["f32" if last_f32 else "bf16"]
+
+
+def timepool_max(h, proj, drop_p: float = 0.0, seed: int = 0):
+    """(B, L, 128) bf16 -> (max over time of the dropped-out projection (B, P) fp32, arg-max (B, P) int32, weight image)"""
+    B, L, K = h.shape
+    P = proj.out_channels
+    wf = weights.get(proj.weight, False)[0]
+    pooled, arg = _empty((B, P), _F32, h), _empty((B, P), torch.int32, h)
+    _hip.call("mm_timepool_max_fwd", h, wf, proj.bias, pooled, arg, B, L, K, P, float(drop_p), int(seed), EP())
+    return pooled, arg, wf
+
+
+def timepool_avg(h, proj, bins: int):
+    """(B, L, 128) fp32 -> (Flatten(AdaptiveAvgPool1d(bins)(projection)) (B, P * bins), the bin means (B, bins, 128))"""
+    B, L, K = h.shape
+    P = proj.out_channels
+    xbin, pooled = _empty((B, bins, K), _F32, h), _empty((B, P * bins), _F32, h)
+    _hip.call("mm_timepool_avg_fwd", h, proj.weight.detach().reshape(P, K), proj.bias, xbin, pooled, B, L, K, P, bins)
+    return pooled, xbin
+
+
+def eeg_baseline_forward(m, x, kind: str):
+    """ERPOnlyNet (kind "erp") / PWOnlyNet ("pw") -> logits.  Train mode: the tape with batch statistics and dropout;
+    eval with a backward to follow (autograd on and something asks for a gradient, or an attribution): the same tape
+    with frozen BatchNorm and dropout off; otherwise the folded eval launches, detached."""
+    eeg_baseline_check(m, x, kind)
+    _need_gpu(x)
+    enc, proj = _baseline_parts(m, kind)
+    p_head = float(m.head[4].p)
+    if m.training or attribution_active() or _wants_grad(m, x):
+        from . import small_autograd as sa
+        fn = sa.PWOnlyFn if kind == "pw" else sa.ERPOnlyFn
+        pooled = fn.apply(m, x, *list(enc.parameters()))
+        return bn_classifier_forward(m.head[1:], pooled, p_head, m.training)
+    with torch.no_grad():
+        if kind == "pw":
+            pooled = timepool_max(_baseline_blocks_eval(enc, x, False), proj)[0]
+        else:
+            pooled = timepool_avg(_baseline_blocks_eval(enc, x, True), proj, int(m.pool.output_size))[0]
+        return bn_classifier_forward(m.head[1:], pooled, p_head, False)
+
+
+def eeg_step_encoder_forward(enc, x, kind: str):
+    """the notebook's ERPEncoder / PowerEncoder on their own: (B, C, T) -> (B, T / 4, out_dim) fp32, the projection as
+    the taps = 1 GEMM (PowerEncoder: its dropout in the epilogue, train mode only)"""
+    eeg_baseline_check(enc, x, kind, head=False)
+    _need_gpu(x)
+    if enc.training or attribution_active() or _wants_grad(enc, x):
+        from . import small_autograd as sa
+        return sa.StepEncoderFn.apply(enc, kind, x, *list(enc.parameters()))
+    _, proj = _baseline_parts(enc, kind)
+    with torch.no_grad():
+        h = _baseline_blocks_eval(enc, x, False)
+        B, L, K = h.shape
+        r = linear_rows(h.view(B * L, K), proj.weight, proj.bias, out_f32=True, out_bf16=False)
+        return r["f32"].view(B, L, -1)
+
+
 def _power_merged(m, device):
     """the three parallel Conv1d(C->64, k in {3,5,7}) as ONE k=7 conv with 192
     outputs (shorter kernels zero-padded around the centre tap) + folded BN."""

@@ -176,6 +176,115 @@ class LiteConvFn(torch.autograd.Function):
         return (None, dx) + tuple(bag.result(p) for p in ctx.params)
 
 
+def _baseline_blocks(enc, x, last_f32):
+    """the three Conv-BN-ReLU[-MaxPool2] blocks of the EEG notebook's ERPEncoder / PowerEncoder on the tape (train mode:
+    batch statistics; eval: frozen BatchNorm) -> (block 3's output (B, T / 4, 128) fp32 | bf16, the saved dicts)"""
+    kw = dict(act="relu", training=bool(enc.training), drop_p=0.0, save=True)
+    r1, s1 = ops.conv_bn_act(ops.pack_nct(_f(x)), enc.conv1, enc.bn1, pool=2, need_dgrad=bool(x.requires_grad), **kw)
+    r2, s2 = ops.conv_bn_act(r1["bf16"], enc.conv2, enc.bn2, pool=2, need_dgrad=True, **kw)
+    r3, s3 = ops.conv_bn_act(r2["bf16"], enc.conv3, enc.bn3, pool=1, need_dgrad=True, want_f32=last_f32,
+                             want_bf16=not last_f32, **kw)
+    return r3["f32" if last_f32 else "bf16"], (s1, s2, s3)
+
+
+def _baseline_blocks_bwd(bag, saved, xshape, need_dx, dout_bf16=None, dout_f32=None):
+    s1, s2, s3 = saved
+    g = conv_bn_act_bwd(bag, s3, dout_bf16=dout_bf16, dout_f32=dout_f32)
+    g = conv_bn_act_bwd(bag, s2, dout_bf16=g)
+    g = conv_bn_act_bwd(bag, s1, dout_bf16=g, need_dx=need_dx)
+    if not need_dx:
+        return None
+    Bx, C, T = xshape
+    dx = _empty((Bx, C, T), _F32, g)
+    _hip.call("mm_unpack_ntc_f32", g, dx, Bx, C, T, g.shape[2])
+    return dx
+
+
+class PWOnlyFn(torch.autograd.Function):
+    """PWOnlyNet up to its head: PowerEncoder's conv blocks, then proj -> Dropout -> max over time in one launch
+    (``mm_timepool_max_fwd``): (B, C, T) -> (B, P) fp32.  The backward gathers through the saved arg-max."""
+
+    @staticmethod
+    def forward(ctx, m, x, *params):
+        enc = m.pw_enc
+        h, saved = _baseline_blocks(enc, x, False)
+        p = float(enc.dropout.p) if enc.training else 0.0
+        seed = ops._next_seed() if p > 0 else 0
+        pooled, arg, wf = ops.timepool_max(h, enc.proj, p, seed)
+        ctx.saved, ctx.params, ctx.tail = saved, params, (enc.proj, h, wf, arg, p, seed)
+        ctx.dims = (tuple(x.shape), x.requires_grad)
+        return pooled
+
+    @staticmethod
+    def backward(ctx, dout):
+        proj, h, wf, arg, p, seed = ctx.tail
+        xshape, need_dx = ctx.dims
+        B, L, K = h.shape
+        bag = GradBag()
+        dh = _empty((B, L, K), torch.bfloat16, h)
+        _hip.call("mm_timepool_max_bwd", _f(dout), arg, h, wf, dh, bag.target(proj.weight), bag.target(proj.bias),
+                  B, L, K, proj.out_channels, p, seed, ops.EP())
+        dx = _baseline_blocks_bwd(bag, ctx.saved, xshape, need_dx, dout_bf16=dh)
+        return (None, dx) + tuple(bag.result(q) for q in ctx.params)
+
+
+class ERPOnlyFn(torch.autograd.Function):
+    """ERPOnlyNet up to its head: ERPEncoder's conv blocks (block 3 in fp32), then the time bins averaged and projected
+    (``mm_timepool_avg_fwd``): (B, C, T) -> (B, P * bins) fp32 in Flatten order."""
+
+    @staticmethod
+    def forward(ctx, m, x, *params):
+        enc = m.erp_enc
+        bins = int(m.pool.output_size)
+        h, saved = _baseline_blocks(enc, x, True)
+        pooled, xbin = ops.timepool_avg(h, enc.step_proj, bins)
+        ctx.saved, ctx.params, ctx.tail = saved, params, (enc.step_proj, xbin, bins, tuple(h.shape))
+        ctx.dims = (tuple(x.shape), x.requires_grad)
+        return pooled
+
+    @staticmethod
+    def backward(ctx, dout):
+        proj, xbin, bins, (B, L, K) = ctx.tail
+        xshape, need_dx = ctx.dims
+        P = proj.out_channels
+        bag = GradBag()
+        dh = _empty((B, L, K), _F32, xbin)
+        _hip.call("mm_timepool_avg_bwd", _f(dout), xbin, proj.weight.detach().reshape(P, K), dh, bag.target(proj.weight),
+                  bag.target(proj.bias), B, L, K, P, bins)
+        dx = _baseline_blocks_bwd(bag, ctx.saved, xshape, need_dx, dout_f32=dh)
+        return (None, dx) + tuple(bag.result(q) for q in ctx.params)
+
+
+class StepEncoderFn(torch.autograd.Function):
+    """the notebook's ERPEncoder / PowerEncoder on their own: conv blocks, then the 1 x 1 projection of every time step as
+    the taps = 1 GEMM (PowerEncoder: dropout in its epilogue) -> (B, T / 4, out_dim) fp32"""
+
+    @staticmethod
+    def forward(ctx, enc, kind, x, *params):
+        proj = enc.proj if kind == "pw" else enc.step_proj
+        h, saved = _baseline_blocks(enc, x, False)
+        B, L, K = h.shape
+        p = float(enc.dropout.p) if (kind == "pw" and enc.training) else 0.0
+        seed = ops._next_seed() if p > 0 else 0
+        r = ops.linear_rows(h.view(B * L, K), proj.weight, proj.bias, out_f32=True, out_bf16=False, drop_p=p, seed=seed,
+                            need_dgrad=True)
+        ctx.saved, ctx.params, ctx.tail = saved, params, (proj, h, p, seed)
+        ctx.dims = (tuple(x.shape), x.requires_grad)
+        return r["f32"].view(B, L, -1)
+
+    @staticmethod
+    def backward(ctx, dout):
+        from .autograd import _mask_cast, linear_bwd
+        proj, h, p, seed = ctx.tail
+        xshape, need_dx = ctx.dims
+        B, L, K = h.shape
+        bag = GradBag()
+        dy = _mask_cast(g_f32=_f(dout).view(B * L, -1), drop_p=p, seed=seed)
+        dh = linear_bwd(bag, dy, h.view(B * L, K), proj.weight, proj.bias)
+        dx = _baseline_blocks_bwd(bag, ctx.saved, xshape, need_dx, dout_bf16=dh.view(B, L, K))
+        return (None, None, dx) + tuple(bag.result(q) for q in ctx.params)
+
+
 class SmoothedCEFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, target, smoothing):

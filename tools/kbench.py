@@ -652,6 +652,58 @@ def tabtx_case(step_iters=30, rounds=5, H=64, L=2, A=100, C=200, p=0.4):
         print(f"  {'fused, graph-replayed':56s} {_spread(g)}")
 
 
+def timepool_case(B=32, L=256, P=128, p=0.2, step_iters=30, rounds=5):
+    """tails of the EEG baselines (csrc/timepool.hip) at the notebook's widths, T = 1024 (256 steps reach the tail), train
+    mode, forward + backward: the fused pair (max tail: projection, dropout and max over time in one launch, the backward a
+    gather; avg tail: bins averaged first, four rows projected) against torch's eager form of what the notebook computes -
+    Linear over every step, dropout, amax / adaptive_avg_pool1d, autograd backward - in fp32 on the same GPU in the same
+    run: interleaved rounds, median [min .. max] of HIP-event times; then the fused pairs graph-replayed."""
+    import torch.nn.functional as F
+    K = 128
+    torch.manual_seed(0)
+    h32 = torch.randn(B, L, K, device="cuda")
+    hb = h32.to(BF)
+    proj = torch.nn.Conv1d(K, P, 1).cuda()
+    W2 = proj.weight.detach().reshape(P, K)
+    wf = ops.weights.get(proj.weight, False)[0]
+    R, R4 = torch.randn(B, P, device="cuda"), torch.randn(B, 4 * P, device="cuda")
+    pooled, arg = torch.empty(B, P, device="cuda"), torch.empty(B, P, dtype=torch.int32, device="cuda")
+    pooled4, xbin = torch.empty(B, 4 * P, device="cuda"), torch.empty(B, 4, K, device="cuda")
+    dhb, dh32 = torch.empty_like(hb), torch.empty_like(h32)
+    dw, db = torch.zeros(P, K, device="cuda"), torch.zeros(P, device="cuda")
+    hg = h32.clone().requires_grad_(True)
+    Wg, bg = W2.clone().requires_grad_(True), proj.bias.detach().clone().requires_grad_(True)
+
+    def max_fused():
+        _hip.call("mm_timepool_max_fwd", hb, wf, proj.bias, pooled, arg, B, L, K, P, p, 7, None)
+        _hip.call("mm_timepool_max_bwd", R, arg, hb, wf, dhb, dw, db, B, L, K, P, p, 7, None)
+
+    def avg_fused():
+        _hip.call("mm_timepool_avg_fwd", h32, W2, proj.bias, xbin, pooled4, B, L, K, P, 4)
+        _hip.call("mm_timepool_avg_bwd", R4, xbin, W2, dh32, dw, db, B, L, K, P, 4)
+
+    def max_eager():
+        hg.grad = Wg.grad = bg.grad = None
+        F.dropout(F.linear(hg, Wg, bg), p, True).amax(1).backward(R)
+
+    def avg_eager():
+        hg.grad = Wg.grad = bg.grad = None
+        F.adaptive_avg_pool1d(F.linear(hg, Wg, bg).transpose(1, 2), 4).flatten(1).backward(R4)
+
+    cases = [("max tail, torch eager (Linear, dropout, amax; autograd)", max_eager), ("max tail, fused (1 + 2 launches)", max_fused),
+             ("avg tail, torch eager (Linear, adaptive_avg_pool1d; autograd)", avg_eager), ("avg tail, fused (1 + 2 launches)", avg_fused)]
+    times = [[] for _ in cases]
+    for _ in range(rounds):
+        for i, (_, fn) in enumerate(cases):
+            times[i].append(timeit(fn, iters=step_iters, rounds=1))
+    g = [[graph_time(fn) for _ in range(rounds)] for fn in (max_fused, avg_fused)]
+    print(f"baseline tails B={B} L={L} K={K} P={P} p={p} (fwd + bwd; the projected tensor would be {B * L * P * 4 / 1e6:.1f} MB in fp32):")
+    for (name, _), t in zip(cases, times):
+        print(f"  {name:62s} {_spread(t)}")
+    print(f"  {'max tail, fused, graph-replayed':62s} {_spread(g[0])}")
+    print(f"  {'avg tail, fused, graph-replayed':62s} {_spread(g[1])}")
+
+
 def aug_case(B=32, C=64, T=1024, vol=(32, 32, 32), step_iters=30):
     """EEG augmentation (csrc/augment.hip) at the C2 shape: mm_stage_inputs alone against the plan + mm_stage_inputs_aug pair
     at p = 0.3 and p = 1 - issued eagerly (what a training loop pays: host issue included) and replayed from a hipGraph
@@ -956,6 +1008,9 @@ def main():
         return
     if flt == "aug":
         aug_case()
+        return
+    if flt == "timepool":
+        timepool_case()
         return
     if flt == "groups":
         groups_case()
