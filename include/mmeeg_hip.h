@@ -912,6 +912,34 @@ int mm_xai_finish(const float* x, const float* base, int base_rows, const float*
                   int B, int C, int64_t T, int n_steps, int mode, hipStream_t stream);
 int mm_xai_pair_score(const float* z, float* score, float* seed, int B, int N, hipStream_t stream);
 
+/* ---- perturbation attribution (EEG_CODE/CrossModal_EEG_scr.ipynb, InterpretabilityAnalyzer.compute_channel_importance:
+ * one clone, one zeroed channel, one forward and one .item() per channel and batch) ---------------------------------
+ * All the perturbed copies of a batch are rows of one big batch instead.  fp32, contiguous.  A sample is cut into U
+ * units, the things that are knocked out together:
+ *   kind 0  rows     sample (n0, n1) = (C, T)                 unit of an element = c              U = n0
+ *   kind 1  windows  sample (n0, n1) = (C, T), size = w       unit = t / w                        U = ceil(n1 / w)
+ *   kind 2  blocks   sample (n0, n1, n2, n3) = (Cv, D, H, W)  unit = ((d/s) gh + h/s) gw + w/s    U = gd gh gw, g* = ceil(* / s)
+ * (the last window / the edge blocks may be ragged; all Cv channels of a block go together; n2 = n3 = 1 for kinds 0
+ * and 1; a tabular row (F,) is kind 1 with n0 = 1).  The batch must stay below 2^31 elements.
+ * mm_perturb_expand: masks [M][U] int, 1 = keep, 0 = replace.  For j in [0, m):
+ *   out[j * B + b][i] = masks[m0 + j][unit(i)] ? x[b][i] : base[b][i]        (mask-major rows, as mm_xai_interp's steps)
+ * `base` / `base_rows` as for mm_xai_interp: NULL / 0 = zeros, 1 = one sample for all, B = one per sample.  No
+ * arithmetic: every output is a copy of an input's bits or +0.0f.  U must be the unit count of the geometry (checked),
+ * so a mask row is never read past its end.  m <= 65535.
+ * mm_perturb_pair_scores: v[j][b] = z[j * B + b] . z_other[b] over N values, one wave per row in a fixed order: the
+ * matching score of every perturbed row against the OTHER modality's embedding, which is encoded once and not per mask.
+ * mm_perturb_shapley: permutation-sampled Shapley values.  v [P][U - 1][B]: v[q][k - 1] = the score of the coalition of
+ * the first k units of permutation q, k = 1 .. U - 1; pos [P][U] in 1 .. U = the place of unit u in permutation q.  With
+ * v(q, 0) = v_empty and v(q, U) = v_full (both (B,)):
+ *   phi[b][u] = (1 / P) sum_q ( v(q, pos[q][u]) - v(q, pos[q][u] - 1) )
+ * the sum over q in ascending order in fp64, rounded to fp32 once.  U == 1: v may be NULL.  A place outside 1 .. U
+ * yields NaN for that unit. */
+int mm_perturb_expand(const float* x, const float* base, int base_rows, const int* masks, float* out, int B, int kind,
+                      int n0, int n1, int n2, int n3, int size, int U, int m0, int m, hipStream_t stream);
+int mm_perturb_pair_scores(const float* z, const float* z_other, float* v, int B, int m, int N, hipStream_t stream);
+int mm_perturb_shapley(const float* v, const float* v_empty, const float* v_full, const int* pos, float* phi, int B, int U,
+                       int P, hipStream_t stream);
+
 /* ---- GATv2 graph attention over one static graph (EEG_CODE/enhanced_models_v4.py:292-413: the layer of
  * GNNConnectivityEncoder; Brody et al., "How Attentive are Graph Attention Networks?") -------------------------
  * Every sample of the batch shares the graph; a layer is one launch, a workgroup per (sample, head).

@@ -56,7 +56,7 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
         (checked at the first step, not here: a trainer built on the CPU to read weights takes any shape).
         ``augment``: an ``EEGTransforms`` (crossmodal_eeg_scr.py) - every `train_step` then augments its EEG batch on the
         device (noise + channel drop, csrc/augment.hip), drawing step index 0, 1, 2, ... from the trainer's own counter and
-        this process's rank; `evaluate`, `embed`, `evaluate_retrieval`, `explain` and `forward` never augment.
+        this process's rank; `evaluate`, `embed`, `evaluate_retrieval`, `explain`, `perturb` and `forward` never augment.
         ``loss``: "infonce" (default: the symmetric InfoNCE, mm_clip_loss_own_rows*) or "sigmoid" (the pairwise sigmoid
         loss, mm_sigmoid_loss_own_rows: no softmax normaliser, so its signal does not depend on the number of in-batch
         negatives; one more trained scalar, ``head.logit_bias``).
@@ -80,7 +80,7 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
         allocated at the first step, before any capture; the number of valid rows lives on the device, so a captured step
         is never captured again for it.  Whether the bank carries group ids is fixed by the first training step (a later
         switch between ``groups=None`` and ``groups=...`` raises ValueError; `reset_bank` lifts that).  InfoNCE only, one
-        process only.  `evaluate`, `embed`, `evaluate_retrieval`, `predict`, `explain` and `forward` never read or write
+        process only.  `evaluate`, `embed`, `evaluate_retrieval`, `predict`, `explain`, `perturb` and `forward` never read or write
         the bank: they keep the in-batch loss.  0 (default): no bank, the step is unchanged."""
         super().__init__()
         if bank_size < 0 or bank_warmup < 0:
@@ -1210,6 +1210,116 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
             ops._seed_state.update(saved_seed)
             ops.weights_changed()
         return eeg, fmri, bases, accs, scores["at_input"]
+
+    def _perturb_units(self, modality: str, units):
+        """the (kind, size) of `ops.perturb_scores` for `perturb`'s ``eeg_units`` / ``fmri_units``"""
+        if modality == "eeg":
+            if units == "channels":
+                return ("rows", 1)
+            allowed, what = ("windows",), "'channels' or ('windows', w)"
+        elif self._fmri_kind == "volume":
+            if units is None:
+                return ("blocks", 8)
+            allowed, what = ("blocks",), "('blocks', s) for the voxel encoder"
+        else:
+            if units is None:
+                return ("windows", 1)
+            allowed, what = ("windows",), "('windows', w) for a tabular fMRI encoder"
+        if not isinstance(units, (tuple, list)) or len(units) != 2 or units[0] not in allowed:
+            raise ValueError(f"perturb: {modality}_units must be {what}, got {units!r}")
+        return (units[0], units[1])
+
+    def perturb(self, eeg: torch.Tensor, fmri: torch.Tensor, method: str = "occlusion", eeg_units="channels", fmri_units=None,
+                baseline: str = "zero", n_permutations: int = 16, seed: int = 0, permutations=None,
+                chunk_masks: Optional[int] = None) -> Dict[str, torch.Tensor]:
+        """Does the match of pair i survive without this electrode, this time window, this block of the volume:
+        perturbation attribution of the score `explain` attributes - the eval-mode cosine similarity ``ze_i . zf_i`` - from
+        forward scores alone (`ops.perturb_scores`: the masked copies of the batch go through the encoder as a few large
+        batches, csrc/perturb.hip).
+        ``eeg_units``: "channels" or ("windows", w) = w time points of all channels; ``fmri_units``: ("blocks", s) = s^3
+        voxels of a volume (default s = 8), for a tabular encoder ("windows", w) = w features (default 1).  A knocked-out
+        unit is replaced by the ``baseline``: "zero", or "mean" = the batch mean (as in `explain`).
+        ``method``: "occlusion" - drop[b][u] = score_full[b] - score(unit u replaced): U evaluations per modality plus
+        the full one; "shapley" - permutation-sampled Shapley values of the game whose players are the units:
+        ``n_permutations`` = P permutations per modality from ``torch.randperm`` on a CPU generator seeded with ``seed``
+        (EEG drawn first; all samples share them), or ``permutations`` = {"eeg": (P, U) long, "fmri": ...} in place of
+        the draw (a modality not named is drawn); P (U - 1) + 2 evaluations per modality.  Each modality is perturbed
+        with the OTHER intact, and that one is embedded once.
+        -> {"eeg": (B, U_e), "fmri": (B, U_f), "scores": (B,)} fp32 on the trainer's device; Shapley adds
+        "empty_scores": {"eeg": (B,), "fmri": (B,)}, the score with every unit of that modality replaced, so that
+        sum_u phi[b][u] = scores[b] - empty_scores[b] up to rounding (efficiency).
+        A drop is the difference of two bf16-operand scores: differences at the level of the scores' own error are noise
+        (DESIGN.md 5p).  The encoders run the forward `explain` differentiates (eval mode with autograd on), so "scores"
+        are `explain`'s and both methods attribute the same number; that forward keeps what a backward would need, which
+        is dropped after every chunk and counted by the memory rule.  `embed`'s ``no_grad`` forward differs from it by
+        bf16 rounding.  ``chunk_masks``: masks per batch; None = the memory rule of `ops.perturb_scores` (it resets this
+        device's peak-memory statistics).  Changes nothing on the trainer and draws no dropout seed; every module's
+        train / eval flag is put back; a captured graph goes on replaying.  No collectives: any rank may call it on
+        its own data."""
+        if method not in ("occlusion", "shapley"):
+            raise ValueError(f"perturb: method must be 'occlusion' or 'shapley', got {method!r}")
+        if baseline not in ("zero", "mean"):
+            raise ValueError(f"perturb: baseline must be 'zero' or 'mean', got {baseline!r}")
+        if eeg.shape[0] != fmri.shape[0]:
+            raise ValueError(f"perturb: {eeg.shape[0]} EEG epochs but {fmri.shape[0]} fMRI volumes")
+        self._check_fmri(fmri.shape, False, "perturb")
+        units = {"eeg": self._perturb_units("eeg", eeg_units), "fmri": self._perturb_units("fmri", fmri_units)}
+        n_units = {"eeg": ops.perturb_units(units["eeg"][0], eeg.shape[1:], units["eeg"][1]),
+                   "fmri": ops.perturb_units(units["fmri"][0], fmri.shape[1:], units["fmri"][1])}
+        masks, pos = {}, {}
+        if method == "occlusion":
+            for k, U in n_units.items():
+                masks[k] = 1 - torch.eye(U, dtype=torch.int32)
+        else:
+            given = dict(permutations or {})
+            if set(given) - {"eeg", "fmri"}:
+                raise ValueError(f"perturb: permutations has keys {sorted(given)}; 'eeg' and / or 'fmri' are known")
+            if not given.keys() >= {"eeg", "fmri"} and n_permutations < 1:
+                raise ValueError("perturb: n_permutations must be >= 1")
+            gen = torch.Generator().manual_seed(int(seed))
+            for k, U in n_units.items():                                   # EEG first
+                perm = given[k] if k in given else torch.stack([torch.randperm(U, generator=gen) for _ in range(int(n_permutations))])
+                if isinstance(perm, torch.Tensor) and perm.dim() == 2 and perm.shape[1] != U:
+                    raise ValueError(f"perturb: permutations[{k!r}] is {tuple(perm.shape)} but there are {U} units")
+                prefix, pos[k] = ops.shapley_masks(perm)
+                masks[k] = torch.cat([torch.zeros(1, U, dtype=torch.int32), prefix])      # the empty coalition first
+        dev = self._scal.device
+        x = {"eeg": eeg.detach().to(dev).float().contiguous(), "fmri": fmri.detach().to(dev).float().contiguous()}
+        base = {k: (t.mean(dim=0, keepdim=True) if baseline == "mean" else None) for k, t in x.items()}
+        enc = {"eeg": self.eeg_encoder, "fmri": self.fmri_encoder}
+        br = self.head.bridge
+
+        def embed_rows(k, rows):
+            # the forward `explain` differentiates - autograd on, the input asking for a gradient - so that both methods
+            # attribute the same number; the `no_grad` forward of `embed` folds BatchNorm into the convolution kernels and
+            # differs from it by bf16 rounding (DESIGN.md 5p).  No backward follows: the tape is dropped at once.
+            with torch.enable_grad(), ops.attribution_mode():
+                f = enc[k](rows.detach().requires_grad_(True))
+            z = ops.proj_embed_one(br, f, k)
+            ops._release_tape(f)
+            return z
+        modes = [(m, m.training) for m in self.modules()]      # restored module by module (a frozen sub-module stays frozen)
+        self.eval()
+        ops.weights_changed()                                 # graph replays bypass the python-side version counter
+        try:
+            with torch.no_grad():
+                z = {k: embed_rows(k, x[k]) for k in ("eeg", "fmri")}
+                out = {"scores": ops.perturb_pair_scores(z["eeg"], z["fmri"])[0]}
+                empty = {}
+                for k, other in (("eeg", "fmri"), ("fmri", "eeg")):
+                    v = ops.perturb_scores(lambda rows: ops.perturb_pair_scores(embed_rows(k, rows), z[other]),
+                                           x[k], base[k], masks[k], units[k], chunk_masks)
+                    if method == "occlusion":
+                        out[k] = (out["scores"].unsqueeze(0) - v).t().contiguous()
+                    else:
+                        empty[k] = v[0].clone()
+                        out[k] = ops.perturb_shapley(v[1:] if n_units[k] > 1 else None, empty[k], out["scores"], pos[k])
+                if method == "shapley":
+                    out["empty_scores"] = empty
+        finally:
+            for m, mode in modes:
+                m.training = mode
+        return out
 
 
 class HostFeeder:

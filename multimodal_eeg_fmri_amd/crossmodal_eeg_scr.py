@@ -2,7 +2,8 @@
 MI355X HIP path: ``PerFoldNormalizer`` (cell 19), ``FocalLoss`` (cell 20), ``ImprovedTriModalFusionNet`` /
 ``ImprovedSmartFusionNet`` (cells 21-22), ``FlexibleTrainer`` (cell 23) and ``collate_trimodal`` (cell 24); the
 single-modality baselines ``ERPOnlyNet`` / ``PWOnlyNet`` with ``ERPEncoder`` / ``PowerEncoder`` / ``BaseEEGModel`` and
-``evaluate_late_fusion``.
+``evaluate_late_fusion``; ``InterpretabilityAnalyzer`` (channel ablation, channel Shapley values and
+integrated gradients).
 
 SURVEY.md §8 (f).1 / (f).3: same names, constructor arguments, batch conventions and checkpoint
 container (``epoch / model_state_dict / optimizer_state_dict / scheduler_state_dict / metrics``) as
@@ -485,3 +486,134 @@ class FlexibleTrainer:
         self.scheduler.load_state_dict(ck["scheduler_state_dict"])
         self.logger.info("Checkpoint loaded from %s", path)
         return ck["epoch"], ck["metrics"]
+
+
+class InterpretabilityAnalyzer:
+    """The notebook's ``InterpretabilityAnalyzer`` (cell "ADVANCED INTERPRETABILITY") on the batched perturbation engine
+    (`ops.perturb_scores`, csrc/perturb.hip).  The model is called as the notebook calls it,
+    ``model(erp, pw[, conn])``; the score of a sample is ``softmax(logits)[target_class]``, the softmax taken by torch.
+    The notebook runs one clone and one forward per zeroed channel and fetches every mean with ``.item()``; here the
+    zeroed copies of a batch are rows of a few large batches and one tensor per batch goes to the host.
+    ``chunk_masks`` (attribute): masks per forward; None = the engine's memory rule.  ``compute_shap`` (shap's
+    DeepExplainer) is not ported."""
+
+    def __init__(self, model, device, channel_names=None):
+        self.model = model.eval().to(device)
+        self.device = device
+        self.channels = channel_names or [f"Ch{i}" for i in range(18)]
+        self.chunk_masks = None
+
+    def _forward_func(self, *inputs):
+        if len(inputs) == 3:
+            return self.model(inputs[0], inputs[1], inputs[2])
+        return self.model(inputs[0], inputs[1])
+
+    def _to_device(self, erp, pw, conn):
+        put = lambda t: None if t is None else t.detach().to(self.device).float().contiguous()      # noqa: E731
+        return put(erp), put(pw), put(conn)
+
+    def _target(self, target_class, B: int) -> torch.Tensor:
+        """(B,) int64 on the device: one class for every row, or one class per row"""
+        if isinstance(target_class, torch.Tensor):
+            t = target_class.detach().to(self.device).long().reshape(-1)
+            if t.numel() == 1:
+                t = t.expand(B)
+            if t.numel() != B:
+                raise ValueError(f"target_class: {t.numel()} classes for {B} rows")
+            return t.contiguous()
+        return torch.full((B,), int(target_class), dtype=torch.long, device=self.device)
+
+    def _games(self, erp, pw, conn, target, baseline: str, masks_of):
+        """-> (p_full (B,), {"erp": (M_e, B), "pw": (M_p, B)}): the class probability at the inputs and under every mask
+        ``masks_of(C)`` of each modality's channels, the other modality (and conn) intact"""
+        if baseline not in ("zero", "mean"):
+            raise ValueError(f"baseline must be 'zero' or 'mean', got {baseline!r}")
+        self.model.eval()
+        B = erp.shape[0]
+
+        def prob(e, p, c):
+            k = e.shape[0] // B
+            logits = self._forward_func(e, p, c) if c is not None else self._forward_func(e, p)
+            return torch.softmax(logits.float(), dim=1).gather(1, target.repeat(k).unsqueeze(1)).squeeze(1)
+
+        def tiled(t, rows):                                       # the intact inputs, once per mask of the chunk
+            return None if t is None else t.repeat((rows.shape[0] // B,) + (1,) * (t.dim() - 1))
+        with torch.no_grad():
+            full = prob(erp, pw, conn)
+            scores = {}
+            for name, x in (("erp", erp), ("pw", pw)):
+                if x.dim() != 3:
+                    raise ValueError(f"{name}: expected (B, C, T), got {tuple(x.shape)}")
+                base = x.mean(dim=0, keepdim=True) if baseline == "mean" else None
+                if name == "erp":
+                    rows_fn = lambda rows: prob(rows, tiled(pw, rows), tiled(conn, rows))      # noqa: E731
+                else:
+                    rows_fn = lambda rows: prob(tiled(erp, rows), rows, tiled(conn, rows))     # noqa: E731
+                scores[name] = ops.perturb_scores(rows_fn, x, base, masks_of(name, x.shape[1]), ("rows", 1), self.chunk_masks)
+        return full, scores
+
+    def channel_drops(self, erp, pw, conn=None, target_class=1, baseline="zero"):
+        """-> {"erp": (B, C_e), "pw": (B, C_p)} fp32 on the device: per sample, the probability of ``target_class`` (an
+        int, or a tensor of one class per row) at the inputs minus the same with ONE channel replaced by the baseline
+        ("zero", or "mean" = the batch mean) - the notebook's quantity before its mean over the batch."""
+        erp, pw, conn = self._to_device(erp, pw, conn)
+        target = self._target(target_class, erp.shape[0])
+        full, s = self._games(erp, pw, conn, target, baseline, lambda name, C: 1 - torch.eye(C, dtype=torch.int32))
+        return {k: (full.unsqueeze(0) - v).t().contiguous() for k, v in s.items()}
+
+    def compute_channel_importance(self, dataloader):
+        """Measure importance of each channel by zeroing it out -> (importance_erp, importance_pw), numpy arrays of
+        ``len(channel_names)`` values.  Batches of 5 items are (erp, pw, conn, subjects, labels), any other batch is
+        (erp, pw, subjects, labels).  The notebook's arithmetic, kept to the letter: per batch the MEAN over the batch of
+        ``softmax(logits)[:, 1]`` at the input minus the same with one channel zeroed is added up, for every ERP and
+        every PW channel, and at the end the sum of those batch means is divided by the number of SAMPLES, not of
+        batches - so the result scales with 1 / batch size.  That is what the notebook computes.  `channel_drops` has
+        the per-sample drops without that division."""
+        importance_erp = np.zeros(len(self.channels))
+        importance_pw = np.zeros(len(self.channels))
+        n_samples = 0
+        for batch in dataloader:
+            if len(batch) == 5:
+                erp, pw, conn = batch[0], batch[1], batch[2]
+            else:
+                erp, pw, conn = batch[0], batch[1], None
+            if max(erp.shape[1], pw.shape[1]) > len(self.channels):
+                raise ValueError(f"{max(erp.shape[1], pw.shape[1])} channels but {len(self.channels)} channel names")
+            drops = self.channel_drops(erp, pw, conn, target_class=1, baseline="zero")
+            means = torch.cat([drops["erp"].mean(dim=0), drops["pw"].mean(dim=0)]).cpu().numpy()      # one transfer per batch
+            importance_erp[:erp.shape[1]] += means[:erp.shape[1]]
+            importance_pw[:pw.shape[1]] += means[erp.shape[1]:]
+            n_samples += erp.shape[0]
+        return importance_erp / n_samples, importance_pw / n_samples
+
+    def compute_channel_shapley(self, erp, pw, conn=None, target_class=1, n_permutations=16, seed=0, baseline="zero"):
+        """Permutation-sampled Shapley values of the channels -> {"erp": (B, C_e), "pw": (B, C_p)} fp32 on the device.
+        TWO games, not one joint game: the players of the first are the ERP channels with PW (and conn) intact, those of
+        the second the PW channels with ERP intact; a coalition's value is the probability of ``target_class`` with the
+        channels outside it replaced by the baseline.  Per modality sum_c phi[b][c] = p(inputs) - p(all its channels
+        replaced) up to rounding.  ``n_permutations`` permutations per game from ``torch.randperm`` on a CPU generator
+        seeded with ``seed`` (ERP drawn first; all samples share them); P (C - 1) + 2 evaluations per game."""
+        if n_permutations < 1:
+            raise ValueError("n_permutations must be >= 1")
+        erp, pw, conn = self._to_device(erp, pw, conn)
+        target = self._target(target_class, erp.shape[0])
+        gen = torch.Generator().manual_seed(int(seed))
+        pos = {}
+
+        def masks_of(name, C):
+            perm = torch.stack([torch.randperm(C, generator=gen) for _ in range(int(n_permutations))])
+            prefix, pos[name] = ops.shapley_masks(perm)
+            return torch.cat([torch.zeros(1, C, dtype=torch.int32), prefix])             # the empty coalition first
+        full, s = self._games(erp, pw, conn, target, baseline, masks_of)
+        return {k: ops.perturb_shapley(v[1:] if v.shape[0] > 1 else None, v[0].clone(), full, pos[k]) for k, v in s.items()}
+
+    def compute_integrated_gradients(self, erp, pw, conn=None, target_class=1, steps=50):
+        """-> (attr_erp, attr_pw[, attr_conn]) numpy arrays from `eeg_xai_analysis.IntegratedGradients` with ``steps``
+        points and the zero baseline, the model called (erp, pw[, conn]) as everywhere in this class.  These are the
+        ABSOLUTE values |(x - baseline) * mean_s grad| on ``np.linspace(0, 1, steps)``, that module's convention - NOT what
+        the notebook's captum call returns (signed attributions at Gauss-Legendre points); captum is not a dependency
+        (DESIGN.md section 7)."""
+        from .eeg_xai_analysis import IntegratedGradients
+        # that class calls model(pw, erp[, conn]): handing it (erp=pw, pw=erp) makes the call model(erp, pw[, conn])
+        out = IntegratedGradients(self.model, self.device, n_steps=steps).compute(pw, erp, conn, target_class=target_class)
+        return (out["pw"], out["erp"]) + ((out["conn"],) if conn is not None else ())

@@ -2798,3 +2798,185 @@ def integrated_gradients(forward, inputs, baselines, n_steps: int, seed_fn, cons
             plan = plan[:1] + [(s + 1, n) for s, n in ig_chunks(n_steps - 1, ig_chunk_steps(n_steps, step_bytes, budget_bytes))]
         i += 1
     return accs, done
+
+
+# ------------------------------------------------- perturbation attribution (csrc/perturb.hip; EEG_CODE/
+# CrossModal_EEG_scr.ipynb, InterpretabilityAnalyzer.compute_channel_importance)
+PERTURB_KINDS = {"rows": 0, "windows": 1, "blocks": 2}
+
+
+def _perturb_geometry(kind, shape, size, who: str = "perturb"):
+    """-> (kind code, n0, n1, n2, n3, size, U) of mm_perturb_expand for ONE sample of ``shape``: "rows" of a (C, T)
+    sample, "windows" of ``size`` along T of a (C, T) or a tabular (F,) sample, "blocks" of ``size``^3 of a
+    (Cv, D, H, W) volume.  ValueError for anything else."""
+    code = PERTURB_KINDS.get(kind) if isinstance(kind, str) else None
+    if code is None:
+        raise ValueError(f"{who}: kind must be one of {sorted(PERTURB_KINDS)}, got {kind!r}")
+    if isinstance(size, bool) or not isinstance(size, int) or size < 1:
+        raise ValueError(f"{who}: size must be an integer >= 1, got {size!r}")
+    shape = tuple(int(s) for s in shape)
+    if any(s < 1 for s in shape):
+        raise ValueError(f"{who}: empty sample shape {shape}")
+    if code == 2:
+        if len(shape) != 4:
+            raise ValueError(f"{who}: blocks need a (Cv, D, H, W) sample, got {shape}")
+        n0, n1, n2, n3 = shape
+        units = -(-n1 // size) * -(-n2 // size) * -(-n3 // size)
+    else:
+        if code == 1 and len(shape) == 1:
+            shape = (1,) + shape
+        if len(shape) != 2:
+            raise ValueError(f"{who}: {'rows' if code == 0 else 'windows'} need a (C, T) sample"
+                             f"{' or a tabular (F,) one' if code == 1 else ''}, got {shape}")
+        (n0, n1), n2, n3 = shape, 1, 1
+        units = n0 if code == 0 else -(-n1 // size)
+    return code, n0, n1, n2, n3, size, units
+
+
+def perturb_units(kind, shape, size: int = 1) -> int:
+    """U = how many units one sample of ``shape`` has: its rows, ceil(T / size) windows, or ceil(D / size) *
+    ceil(H / size) * ceil(W / size) blocks (the unit table of DESIGN.md 5p); host only"""
+    return _perturb_geometry(kind, shape, size, "perturb_units")[6]
+
+
+def _perturb_masks(masks: torch.Tensor, units: int, who: str) -> torch.Tensor:
+    if masks.dim() != 2 or masks.shape[1] != units or masks.shape[0] < 1:
+        raise ValueError(f"{who}: masks must be (M >= 1, U = {units}), got {tuple(masks.shape)}")
+    return masks
+
+
+def perturb_expand(x: torch.Tensor, base, masks: torch.Tensor, units, m0: int = 0, m: Optional[int] = None) -> torch.Tensor:
+    """(m * B, ...) fp32, mask-major: row j * B + b = sample b with every unit that ``masks[m0 + j]`` marks 0 replaced by
+    the baseline (mm_perturb_expand).  ``units`` = (kind, size); ``masks`` (M, U) int32 on x's device, 1 = keep;
+    ``base``: None (zeros) | (B, ...) | (1, ...) / (...) broadcast, as for `xai_interpolate`."""
+    xc = x.detach().float().contiguous()
+    code, n0, n1, n2, n3, size, U = _perturb_geometry(units[0], xc.shape[1:], units[1], "perturb_expand")
+    _perturb_masks(masks, U, "perturb_expand")
+    m = masks.shape[0] - m0 if m is None else int(m)
+    if m0 < 0 or m < 1 or m0 + m > masks.shape[0]:
+        raise ValueError(f"perturb_expand: masks [{m0}, {m0} + {m}) of {masks.shape[0]}")
+    b, rows = _xai_base(xc, base)
+    _need_gpu(xc, masks)
+    if masks.dtype != torch.int32 or not masks.is_contiguous():
+        raise ValueError("perturb_expand: masks must be a contiguous int32 tensor")
+    B = xc.shape[0]
+    out = _empty((m * B,) + tuple(xc.shape[1:]), _F32, xc)
+    _hip.call("mm_perturb_expand", xc, b, rows, masks, out, B, code, n0, n1, n2, n3, size, U, int(m0), m)
+    return out
+
+
+def perturb_pair_scores(z: torch.Tensor, z_other: torch.Tensor) -> torch.Tensor:
+    """z (m * B, N) embeddings of the perturbed rows, z_other (B, N) the intact other modality -> (m, B) fp32:
+    v[j][b] = z[j * B + b] . z_other[b] (mm_perturb_pair_scores)"""
+    zc, oc = z.detach().float().contiguous(), z_other.detach().float().contiguous()
+    B, N = oc.shape
+    if zc.dim() != 2 or zc.shape[1] != N or zc.shape[0] % B != 0 or zc.shape[0] < B:
+        raise ValueError(f"perturb_pair_scores: rows {tuple(zc.shape)} against {tuple(oc.shape)}")
+    _need_gpu(zc, oc)
+    m = zc.shape[0] // B
+    v = _empty((m, B), _F32, zc)
+    _hip.call("mm_perturb_pair_scores", zc, oc, v, B, m, N)
+    return v
+
+
+def _check_permutations(perm: torch.Tensor, who: str) -> torch.Tensor:
+    """(P >= 1, U >= 1) integer table, every row a permutation of 0 .. U - 1 -> int64 on the host"""
+    if not isinstance(perm, torch.Tensor) or perm.dim() != 2 or perm.shape[0] < 1 or perm.shape[1] < 1 \
+            or perm.dtype.is_floating_point or perm.dtype == torch.bool:
+        raise ValueError(f"{who}: permutations must be a (P, U) integer tensor")
+    p = perm.detach().cpu().long()
+    if not torch.equal(p.sort(dim=1).values, torch.arange(p.shape[1]).expand_as(p)):
+        raise ValueError(f"{who}: every row must be a permutation of 0 .. {p.shape[1] - 1}")
+    return p
+
+
+def shapley_masks(perm: torch.Tensor):
+    """The coalitions a (P, U) table of permutations asks for, host only -> (masks (P * (U - 1), U) int32, pos (P, U)
+    int32): row q * (U - 1) + k - 1 keeps exactly the first k units of permutation q (k = 1 .. U - 1; the empty and the
+    full coalition are shared by all permutations and not repeated), pos[q][u] in 1 .. U = the place of unit u in
+    permutation q (the inverse permutation plus one): what mm_perturb_shapley reads."""
+    p = _check_permutations(perm, "shapley_masks")
+    P, U = p.shape
+    place = torch.argsort(p, dim=1)                                    # unit -> 0-based place
+    k = torch.arange(1, U).view(1, U - 1, 1)
+    masks = (place.view(P, 1, U) < k).to(torch.int32).reshape(P * (U - 1), U)
+    return masks, (place + 1).to(torch.int32)
+
+
+def perturb_shapley(v, v_empty: torch.Tensor, v_full: torch.Tensor, pos: torch.Tensor) -> torch.Tensor:
+    """phi (B, U) fp32 = the mean over the P permutations of every unit's marginal contribution (mm_perturb_shapley).
+    ``v`` (P * (U - 1), B) or (P, U - 1, B) coalition scores in `shapley_masks` order (None when U == 1), ``v_empty`` /
+    ``v_full`` (B,), ``pos`` (P, U) from `shapley_masks`."""
+    if pos.dim() != 2 or pos.dtype.is_floating_point:
+        raise ValueError("perturb_shapley: pos must be a (P, U) integer tensor")
+    P, U = pos.shape
+    B = v_full.numel()
+    if v_empty.numel() != B or (U > 1 and (v is None or v.numel() != P * (U - 1) * B)):
+        raise ValueError(f"perturb_shapley: P={P} U={U} B={B} against v of {None if v is None else tuple(v.shape)}, "
+                         f"v_empty of {tuple(v_empty.shape)}")
+    hp = pos.detach().cpu()
+    if int(hp.min()) < 1 or int(hp.max()) > U:
+        raise ValueError(f"perturb_shapley: places must lie in 1 .. {U}")
+    _need_gpu(v_full, v_empty, v if U > 1 else None)
+    fe, ff = v_empty.detach().float().contiguous(), v_full.detach().float().contiguous()
+    vc = v.detach().float().contiguous() if U > 1 else None
+    pc = pos.detach().to(ff.device, torch.int32).contiguous()
+    phi = _empty((B, U), _F32, ff)
+    _hip.call("mm_perturb_shapley", vc, fe, ff, pc, phi, B, U, P)
+    return phi
+
+
+def perturb_scores(score_rows, x: torch.Tensor, base, masks: torch.Tensor, units, chunk_masks: Optional[int] = None,
+                   budget_bytes: int = XAI_BUDGET_BYTES) -> torch.Tensor:
+    """The batched perturbation engine -> (M, B) fp32: the score of every sample under every mask.  The reference loop
+    (one clone, one forward and one host synchronisation per knocked-out channel) becomes: k masks at a time are expanded
+    into ONE batch of k * B rows (mm_perturb_expand), ``score_rows(rows)`` -> k * B scores (mask-major; any shape with
+    that many elements) runs under ``torch.no_grad()``, and the (k, B) scores land in the result on the device.  In eval
+    mode the rows of a batch are independent (frozen BatchNorm, no dropout), so chunking changes nothing but the kernels'
+    batch size.
+    ``units`` = (kind, size), kind "rows" | "windows" | "blocks" (`perturb_units`); ``masks`` (M, U) integers, 1 = keep,
+    0 = replace by ``base`` (None = zeros | (B, ...) | (1, ...)).
+    The plan and the memory rule are the gradient engine's (`ig_chunks`, `ig_chunk_steps`; one mask = one "step"):
+    ``chunk_masks`` = k given by the caller; None: the first mask runs alone, its peak memory is measured and
+    floor(budget / that) masks form every later chunk.  As in `integrated_gradients`, that measurement calls
+    ``torch.cuda.reset_peak_memory_stats``: the caller's peak-memory statistics of this device start over.
+    Argument errors raise ValueError before any launch."""
+    xc = x.detach().float().contiguous()
+    if not isinstance(units, (tuple, list)) or len(units) != 2:
+        raise ValueError(f"perturb_scores: units must be (kind, size), got {units!r}")
+    U = _perturb_geometry(units[0], xc.shape[1:], units[1], "perturb_scores")[6]
+    if not isinstance(masks, torch.Tensor) or masks.dtype.is_floating_point:
+        raise ValueError("perturb_scores: masks must be an integer tensor")
+    _perturb_masks(masks, U, "perturb_scores")
+    if chunk_masks is not None and int(chunk_masks) < 1:
+        raise ValueError("perturb_scores: chunk_masks must be >= 1")
+    if budget_bytes < 1:
+        raise ValueError("perturb_scores: budget_bytes must be positive")
+    b, _ = _xai_base(xc, base)
+    _need_gpu(xc)
+    dev = xc.device
+    mk = masks.detach().to(dev, torch.int32).contiguous()
+    M, B = mk.shape[0], xc.shape[0]
+    out = _empty((M, B), _F32, xc)
+    probe = chunk_masks is None
+    plan = ig_chunks(M, 1 if probe else int(chunk_masks), first_alone=probe)
+    i = 0
+    while i < len(plan):
+        m0, k = plan[i]
+        if probe and i == 0:
+            torch.cuda.synchronize(dev)
+            before = torch.cuda.memory_allocated(dev)
+            torch.cuda.reset_peak_memory_stats(dev)
+        with torch.no_grad():
+            rows = perturb_expand(xc, b, mk, units, m0, k)
+            s = score_rows(rows)
+            if s.numel() != k * B:
+                raise ValueError(f"perturb_scores: score_rows returned {tuple(s.shape)} for {k * B} rows")
+            out[m0:m0 + k] = s.detach().float().reshape(k, B)
+        del rows, s
+        if probe and i == 0:
+            torch.cuda.synchronize(dev)
+            mask_bytes = max(1, torch.cuda.max_memory_allocated(dev) - before)
+            plan = plan[:1] + [(s0 + 1, n) for s0, n in ig_chunks(M - 1, ig_chunk_steps(M, mask_bytes, budget_bytes))]
+        i += 1
+    return out
