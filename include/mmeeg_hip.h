@@ -389,6 +389,28 @@ int mm_eeg_augment_plan(const float* x, uint32_t* plan, int64_t plan_words, int 
 int mm_stage_inputs_aug(const float* eeg, uint32_t* plan, int64_t plan_words, void* eeg_packed_bf16, float* eeg_out_f32,
                         int B, int C, int T, int Cp, float noise_factor, uint32_t s_gauss_a, uint32_t s_gauss_b,
                         float* fmri_dst, const float* fmri_src, int64_t fmri_n, hipStream_t stream);
+/* fMRI volume augmentation in front of a training step (the reference has no volume code: the transform is defined in
+ * DESIGN.md 5q and csrc/volume_augment.hip): per sample of a (B, 1, D, H, W) fp32 batch, each with its own probability, a
+ * mirror of the W axis, an integer shift (dz, dy, dx) in [-max_shift, max_shift]^3, a scale by 1 + scale_range * (2u - 1),
+ * Gaussian noise of noise_factor * std_b (the unbiased standard deviation of the original sample) and one ed x eh x ew
+ * cuboid set to `fill`; voxels shifted in from outside are `fill` too.  The draws are h(stream, sample) of csrc/augment.hip
+ * on 14 stream words of purposes 5..18 (ops.volume_augment_streams); no state on the device.  Two launches:
+ *   mm_volume_augment_plan  fills `plan` (32-bit words, 8-byte aligned): per sample 16 words - [0] flags (bit 0 flip,
+ *     1 shift, 2 scale, 3 noise, 4 erase), [1..3] dz, dy, dx (int32), [4] scale factor fp32 (1 when off), [5..7] erase
+ *     corner z, y, x, [8..10] erase extents (0 when off), [11] noise scale fp32, [12] std_b fp32, [13..15] 0 - then, from
+ *     word 16 * B, fp64 {sum, sum of squares} per chunk of each sample: double[B][nchunk][2], nchunk = ceil(V / chunk),
+ *     V = D * H * W, chunk = 4096 doubled until nchunk <= 64.  So plan_words >= 16 * B + 4 * B * nchunk.
+ *   mm_volume_augment  reads x and the plan, writes out (B, 1, D, H, W) and the plan's words [11] and [12].
+ * Refused before any launch: V < 2, V >= 2^31, B * ceil(V / 2) >= 2^32, max_shift outside [0, min(D, H, W)), a probability
+ * outside [0, 1], scale_range outside [0, 1), an extent outside [1, its axis], a noise_factor or fill that is not finite,
+ * out overlapping x (the shift is a gather), the plan overlapping either. */
+int mm_volume_augment_plan(const float* x, uint32_t* plan, int64_t plan_words, int B, int D, int H, int W, float p_flip,
+                           float p_shift, int max_shift, float p_scale, float scale_range, float p_noise, float p_erase,
+                           int ed, int eh, int ew, uint32_t s_flip, uint32_t s_shift, uint32_t s_dz, uint32_t s_dy,
+                           uint32_t s_dx, uint32_t s_scale, uint32_t s_scale_u, uint32_t s_noise, uint32_t s_erase,
+                           uint32_t s_ez, uint32_t s_ey, uint32_t s_ex, hipStream_t stream);
+int mm_volume_augment(const float* x, uint32_t* plan, int64_t plan_words, float* out, int B, int D, int H, int W,
+                      float noise_factor, float fill, uint32_t s_gauss_a, uint32_t s_gauss_b, hipStream_t stream);
 /* out = bf16( g * dropout_mask * act'(z) ) */
 int mm_act_bwd(const float* g_f32, const void* g_bf16, const void* z, void* out, int64_t n, int act,
                float drop_p, uint32_t seed, const uint32_t* seed_epoch, hipStream_t stream);

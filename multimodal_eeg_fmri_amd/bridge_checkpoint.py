@@ -10,7 +10,8 @@ The file is the container of the reference's loops and of `FlexibleTrainer.save_
   layer group, so its slices are mapped back to that order); the frozen half of the bridge has no entry;
 * ``bridge_trainer_state``: the optimizer words (step count, lr, ...), the hyperparameters, the EEG branch kind, the
   model's shapes, the head count of every transformer block, the world size, the bucket layout, the dropout stream,
-  the state of `fit`, - only for a trainer with an augmenter - ``augment``: its parameters and the step index, -
+  the state of `fit`, - only for a trainer with an augmenter - ``augment``: its parameters and the step index
+  (``fmri_augment``: the same for a volume augmenter), -
   only for a trainer of the pairwise sigmoid loss - ``loss`` = ``"sigmoid"`` (absent: InfoNCE), and - only for a trainer
   built with ``classify=True`` - ``classify`` = ``{ce_weight, num_classes, class_weight}``, and - only for a trainer with
   a cross-batch memory (``bank_size > 0``) - ``bank`` = ``{size, warmup, grouped, state, rows, ids}``: the ring's words,
@@ -163,6 +164,8 @@ class TrainerCheckpointMixin:
         bts.update(self._layout())
         if getattr(self, "augment", None) is not None:             # (absent without an augmenter: the container is unchanged)
             bts["augment"] = dict(self.augment.params(), step=int(self._aug_step))
+        if getattr(self, "fmri_augment", None) is not None:        # (absent without a volume augmenter: the container is unchanged)
+            bts["fmri_augment"] = dict(self.fmri_augment.params(), step=int(self._fmri_aug_step))
         if getattr(self, "loss", "infonce") != "infonce":          # (absent for the default loss: the container is unchanged)
             bts["loss"] = self.loss
         if self.checkpoint_classify() is not None:                 # (absent without classify: the container is unchanged)
@@ -237,6 +240,15 @@ class TrainerCheckpointMixin:
             mine_aug = aug.params()
             if {k: theirs_aug.get(k) for k in mine_aug} != mine_aug:
                 raise ValueError(f"load_checkpoint_state: augment differs: checkpoint {theirs_aug!r}, trainer {mine_aug!r}")
+        vaug, theirs_vaug = getattr(self, "fmri_augment", None), bts.get("fmri_augment")
+        if (vaug is None) != (theirs_vaug is None):
+            raise ValueError(f"load_checkpoint_state: fmri_augment differs: the checkpoint was written "
+                             f"{'with' if theirs_vaug is not None else 'without'} a volume augmenter, this trainer has "
+                             f"{'none' if vaug is None else 'one'}")
+        if vaug is not None:
+            mine_vaug = vaug.params()
+            if {k: theirs_vaug.get(k) for k in mine_vaug} != mine_vaug:
+                raise ValueError(f"load_checkpoint_state: fmri_augment differs: checkpoint {theirs_vaug!r}, trainer {mine_vaug!r}")
         msd = sd["model_state_dict"]
         for k, shp in mine["shapes"].items():
             if k not in msd or list(msd[k].shape) != shp:
@@ -286,6 +298,8 @@ class TrainerCheckpointMixin:
         self._pending_epoch_word = d["epoch_word"] if d["kind"] == "graph" else None
         if "augment" in bts:
             self._aug_step = int(bts["augment"]["step"])
+        if "fmri_augment" in bts:
+            self._fmri_aug_step = int(bts["fmri_augment"]["step"])
         if "bank" in bts:
             self._load_bank(bts["bank"])
         ops.weights_changed()

@@ -48,7 +48,7 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
                  eps: float = 1e-8, group=None, device="cuda", mode: str = "graph", eeg_encoder: Optional[nn.Module] = None,
                  num_heads: int = 4, num_layers: int = 2, augment=None, loss: str = "infonce",
                  classify: bool = False, ce_weight: float = 1.0, class_weight=None, num_classes: int = 2,
-                 fmri_encoder: Optional[nn.Module] = None, bank_size: int = 0, bank_warmup: int = 0):
+                 fmri_encoder: Optional[nn.Module] = None, bank_size: int = 0, bank_warmup: int = 0, fmri_augment=None):
         """``eeg_encoder``: the EEG branch when it is not the default ``EnhancedERPEncoder(eeg_channels, hidden_dim,
         num_layers, num_heads, dropout)`` - an ``EnhancedPowerEncoder`` (enhanced_models_v4.py:196-285) or a
         ``MultiScaleSTFTPowerEncoder`` (BASELINE config #5: raw EEG -> multi-scale STFT power -> a4); it must end in
@@ -81,7 +81,12 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
         is never captured again for it.  Whether the bank carries group ids is fixed by the first training step (a later
         switch between ``groups=None`` and ``groups=...`` raises ValueError; `reset_bank` lifts that).  InfoNCE only, one
         process only.  `evaluate`, `embed`, `evaluate_retrieval`, `predict`, `explain`, `perturb` and `forward` never read or write
-        the bank: they keep the in-batch loss.  0 (default): no bank, the step is unchanged."""
+        the bank: they keep the in-batch loss.  0 (default): no bank, the step is unchanged.
+        ``fmri_augment``: a ``VolumeTransforms`` (fmri_utils.py; voxel encoder only) - every `train_step` then augments its
+        fMRI batch on the device (flip, shift, scale, noise, erase; csrc/volume_augment.hip), drawing
+        step index 0, 1, 2, ... from a counter of its own (`fmri_augment_step`) and this process's rank; in graph mode the
+        two launches write the captured step's static fMRI buffer.  The entry points that never augment the EEG never
+        augment the volumes either.  None (default): the step issues the launches it always did."""
         super().__init__()
         if bank_size < 0 or bank_warmup < 0:
             raise ValueError(f"BridgeTrainer: bank_size and bank_warmup must be >= 0 (got {bank_size}, {bank_warmup})")
@@ -127,6 +132,15 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
                 raise TypeError(f"BridgeTrainer: augment must be an EEGTransforms (got {type(augment).__name__})")
         self.augment = augment
         self._aug_step = 0                            # step index the next train_step's augmentation draws with
+        if fmri_augment is not None:
+            from .fmri_utils import VolumeTransforms
+            if not isinstance(fmri_augment, VolumeTransforms):
+                raise TypeError(f"BridgeTrainer: fmri_augment must be a VolumeTransforms (got {type(fmri_augment).__name__})")
+            if fmri_encoder is not None:
+                raise ValueError("BridgeTrainer: fmri_augment augments (B, 1, D, H, W) volumes; the fMRITabularEncoder's "
+                                 "input is a feature table (build the trainer without fmri_augment=, or with the voxel encoder)")
+        self.fmri_augment = fmri_augment
+        self._fmri_aug_step = 0                       # step index the next train_step's volume augmentation draws with
         self.eeg_encoder = (EnhancedERPEncoder(eeg_channels, hidden_dim, num_layers, num_heads, dropout)
                             if eeg_encoder is None else eeg_encoder)
         from .crossmodal_v4_enhancements import MultiScaleSTFTPowerEncoder
@@ -259,6 +273,11 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
         """the step index the next `train_step` augments with (0 after construction; restored by a checkpoint)"""
         return self._aug_step
 
+    @property
+    def fmri_augment_step(self) -> int:
+        """the step index the next `train_step` augments its fMRI batch with (0 after construction; restored by a checkpoint)"""
+        return self._fmri_aug_step
+
     def set_lr(self, lr: float):
         self.lr = lr
         self.bucket.state[2] = lr
@@ -323,12 +342,18 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
             aug_step, self._aug_step = self._aug_step, self._aug_step + 1
             if self.mode != "graph":
                 eeg = self.augment.batch(eeg, aug_step, dp.rank(self.group))
+        fmri_aug_step = None
+        if self.fmri_augment is not None:                  # a counter of its own: one step index per call, whatever the mode
+            self.fmri_augment.check(fmri.shape, "train_step (fmri_augment)")
+            fmri_aug_step, self._fmri_aug_step = self._fmri_aug_step, self._fmri_aug_step + 1
+            if self.mode != "graph":
+                fmri = self.fmri_augment.batch(fmri, fmri_aug_step, dp.rank(self.group))
         if self.mode == "autograd":
             return self._step_autograd(eeg, fmri, gid, lab)
         if self.mode == "manual":
             with torch.no_grad():
                 return self._step_manual(eeg, fmri, gid, lab)
-        return self._step_graph(eeg, fmri, gid, aug_step, lab)
+        return self._step_graph(eeg, fmri, gid, aug_step, lab, fmri_aug_step)
 
     def _encode(self, eeg, fmri):
         """both encoders through their nn.Module surface: independent until the heads, so on two HIP streams"""
@@ -837,9 +862,9 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
         with torch.cuda.stream(self._side):
             dp.all_gather_into(c["gid_all"].view(-1, 1), c["gid"].view(-1, 1), self.group)
 
-    def _step_graph(self, eeg, fmri, gid=None, aug_step=None, lab=None):
-        """``aug_step``: the augmentation's step index (trainers with an augmenter).  The capture and its two warm-up steps
-        see the batch as it came; what a replay reads is staged below, augmented."""
+    def _step_graph(self, eeg, fmri, gid=None, aug_step=None, lab=None, fmri_aug_step=None):
+        """``aug_step`` / ``fmri_aug_step``: the step index of the EEG / volume augmentation (trainers with that augmenter).
+        The capture and its two warm-up steps see the batch as it came; what a replay reads is staged below, augmented."""
         if (self._cap is None or self._cap["eeg"].shape != eeg.shape or self._cap["fmri"].shape != fmri.shape
                 or self._cap["grouped"] != (gid is not None) or self._cap["labelled"] != (lab is not None)
                 or self._cap["bank_live"] != self._bank_live):
@@ -851,7 +876,12 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
                 self._cap["epoch"].fill_(self._pending_epoch_word)
                 self._pending_epoch_word = None
         c = self._cap
-        if aug_step is None or not self._stage_augmented(c, eeg, fmri, aug_step):
+        if fmri_aug_step is not None:
+            # the augmented volumes go straight into the static buffer; the EEG batch is then staged without the fMRI copy
+            self._stage_fmri_augmented(c, fmri, fmri_aug_step)
+            if aug_step is None or not self._stage_augmented(c, eeg, c["fmri"], aug_step):
+                self._stage_eeg(c, eeg if aug_step is None else self.augment.batch(eeg, aug_step, dp.rank(self.group)))
+        elif aug_step is None or not self._stage_augmented(c, eeg, fmri, aug_step):
             self._stage_inputs(c, eeg if aug_step is None else self.augment.batch(eeg, aug_step, dp.rank(self.group)), fmri)
         if gid is not None and gid.data_ptr() != c["gid"].data_ptr():
             c["gid"].copy_(gid)
@@ -877,6 +907,34 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
             if c["xb"] is not None:
                 Bx, Cx, Tx = c["eeg"].shape
                 _hip.call("mm_pack_nct_bf16", c["eeg"], c["xb"], Bx, Cx, Tx, c["xb"].shape[2])
+
+    def _stage_eeg(self, c, eeg):
+        """the EEG batch alone into the captured step's static input (the fMRI buffer has been written already): ONE launch
+        - the pack into the first convolution's operand, or a plain copy for the STFT front end, which reads the fp32 batch"""
+        if c["xb"] is None:
+            if eeg.data_ptr() != c["eeg"].data_ptr():
+                c["eeg"].copy_(eeg)
+            return
+        if not (eeg.dtype == torch.float32 and eeg.is_cuda and eeg.is_contiguous()):
+            c["eeg"].copy_(eeg)
+            eeg = c["eeg"]
+        Bx, Cx, Tx = eeg.shape
+        _hip.call("mm_pack_nct_bf16", eeg, c["xb"], Bx, Cx, Tx, c["xb"].shape[2])
+
+    def _stage_fmri_augmented(self, c, fmri, step):
+        """the augmented fMRI batch into the captured step's static buffer: the two launches of csrc/volume_augment.hip write
+        `c["fmri"]` directly.  The shift is a gather, so a batch that IS the static buffer (an in-place loader) - or is not a
+        contiguous fp32 device tensor - is augmented into a scratch tensor first and copied (the scratch tensor and the plan
+        are kept with the capture: no allocation per step)."""
+        kw = dict(step=step, rank=dp.rank(self.group), plan=c.get("fmri_aug_plan"), **self.fmri_augment.kernel_args(fmri.shape))
+        src = fmri.detach().to(c["fmri"].device, torch.float32).contiguous()     # (the tensor itself when it already is all that)
+        if not ops._overlap(src, c["fmri"]):
+            c["fmri_aug_plan"] = ops.volume_augment_into(src, c["fmri"], **kw)
+            return
+        if c.get("fmri_scratch") is None:
+            c["fmri_scratch"] = torch.empty(c["fmri"].shape, dtype=torch.float32, device=c["fmri"].device)
+        c["fmri_aug_plan"] = ops.volume_augment_into(src, c["fmri_scratch"], **kw)
+        c["fmri"].copy_(c["fmri_scratch"])
 
     def _stage_augmented(self, c, eeg, fmri, aug_step) -> bool:
         """the augmented batch straight into the packed operand (and the fMRI batch into its buffer): TWO launches - the
@@ -972,6 +1030,10 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
             raise ValueError(f"{who}: this trainer has an augmenter, and a batch that is already packed to bf16 on the host "
                              "cannot be augmented after the fact (the noise scale needs the fp32 sample); feed "
                              "train_step(eeg, fmri) from device tensors, or build the trainer without augment=")
+        if self.fmri_augment is not None:
+            raise ValueError(f"{who}: this trainer has a volume augmenter, and the packed path copies the host's bytes straight "
+                             "into the static inputs the volume augmentation writes (one copy, no launch that could augment); "
+                             "feed train_step(eeg, fmri) from device tensors, or build the trainer without fmri_augment=")
 
     def time_collectives(self, batch: int, iters: int = 50) -> Dict[str, float]:
         """microseconds per call of every collective one step issues, each alone at its message size (HIP events on the

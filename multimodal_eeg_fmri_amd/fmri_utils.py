@@ -14,7 +14,10 @@
 from __future__ import annotations
 
 import logging
+import math
+import numbers
 
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -219,6 +222,146 @@ class fMRIVolumeEncoder3D(nn.Module):
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         return ops.volume_encoder_forward(self, x)
+
+
+class VolumeTransforms:
+    """Augmenter of (B, 1, D, H, W) fMRI volumes, the voxel encoder's counterpart of ``EEGTransforms`` (the reference has no
+    volume code; the transform is defined in DESIGN.md 5q).  Per sample, in this order and each with its own probability:
+    mirror of the W axis (``p_flip``), integer translation by up to ``max_shift`` voxels per axis (``p_shift``; voxels from
+    outside the volume are ``fill``), intensity scale by ``1 + scale_range * (2u - 1)`` (``p_scale``), Gaussian noise of
+    ``noise_factor`` x the original sample's standard deviation (``p_noise``), one cuboid of ``max(1, int(erase_fraction *
+    extent))`` voxels per axis set to ``fill`` (``p_erase``).  A probability of 0 or 1 is a valid setting.
+
+    The random stream is csrc/augment.hip's on purposes of its own (``ops.volume_augment_streams``), a pure function of
+    (seed, step, rank, sample, voxel): ``batch`` on a device tensor runs the two HIP launches of ``ops.volume_augment``, on a
+    CPU tensor the same stream in numpy - the same decisions, shifts and boxes, arithmetic equal to fp32 rounding.
+    `BridgeTrainer(fmri_augment=)` augments each training step's fMRI batch on the device; ``__call__`` is the per-sample
+    dataset form (``transform=``)."""
+
+    def __init__(self, p_flip: float = 0.5, p_shift: float = 0.5, max_shift: int = 2, p_scale: float = 0.3,
+                 scale_range: float = 0.1, p_noise: float = 0.3, noise_factor: float = 0.05, p_erase: float = 0.3,
+                 erase_fraction: float = 0.25, fill: float = 0.0, seed: int = 0):
+        real = lambda v: isinstance(v, numbers.Real) and not isinstance(v, bool)  # noqa: E731
+        for name, v in (("p_flip", p_flip), ("p_shift", p_shift), ("p_scale", p_scale), ("p_noise", p_noise), ("p_erase", p_erase)):
+            if not (real(v) and 0.0 <= v <= 1.0):
+                raise ValueError(f"VolumeTransforms: {name} must lie in [0, 1] (got {v!r})")
+        if not (isinstance(max_shift, numbers.Integral) and not isinstance(max_shift, bool) and max_shift >= 0):
+            raise ValueError(f"VolumeTransforms: max_shift must be an integer >= 0 (got {max_shift!r})")
+        if not (real(scale_range) and 0.0 <= scale_range < 1.0):
+            raise ValueError(f"VolumeTransforms: scale_range must lie in [0, 1) (got {scale_range!r})")
+        if not (real(erase_fraction) and 0.0 < erase_fraction <= 1.0):
+            raise ValueError(f"VolumeTransforms: erase_fraction must lie in (0, 1] (got {erase_fraction!r})")
+        for name, v in (("noise_factor", noise_factor), ("fill", fill)):
+            if not (real(v) and math.isfinite(v)):
+                raise ValueError(f"VolumeTransforms: {name} must be a finite number (got {v!r})")
+        self.p_flip, self.p_shift, self.p_scale, self.p_noise, self.p_erase = p_flip, p_shift, p_scale, p_noise, p_erase
+        self.max_shift, self.scale_range, self.noise_factor = int(max_shift), scale_range, noise_factor
+        self.erase_fraction, self.fill, self.seed = erase_fraction, fill, int(seed)
+        self.calls = 0
+
+    def erase_extents(self, dims) -> tuple:
+        """the erased cuboid's (ed, eh, ew) for a (D, H, W) volume"""
+        return tuple(max(1, int(self.erase_fraction * int(n))) for n in dims)
+
+    def params(self) -> dict:
+        """what two augmenters must share to draw the same stream (the trainer's checkpoint carries it)"""
+        return {"seed": self.seed, "p_flip": float(self.p_flip), "p_shift": float(self.p_shift), "max_shift": self.max_shift,
+                "p_scale": float(self.p_scale), "scale_range": float(self.scale_range), "p_noise": float(self.p_noise),
+                "noise_factor": float(self.noise_factor), "p_erase": float(self.p_erase),
+                "erase_fraction": float(self.erase_fraction), "fill": float(self.fill)}
+
+    def kernel_args(self, shape) -> dict:
+        """the keywords of ``ops.volume_augment`` for a batch of ``shape`` (its last three extents size the erased cuboid)"""
+        kw = self.params()
+        del kw["erase_fraction"]
+        kw["erase"] = self.erase_extents(tuple(shape)[-3:])
+        return kw
+
+    def check(self, shape, who: str = "VolumeTransforms") -> dict:
+        """``ops.volume_augment_check`` of a batch of ``shape`` under this augmenter's settings (``ValueError`` before
+        anything runs) -> `kernel_args(shape)`"""
+        kw = self.kernel_args(shape)
+        ops.volume_augment_check(shape, who=who, **{k: v for k, v in kw.items() if k != "seed"})
+        return kw
+
+    def batch(self, x: torch.Tensor, step: int, rank: int = 0) -> torch.Tensor:
+        """the augmented copy of a (B, 1, D, H, W) batch at step index ``step`` on rank ``rank``"""
+        if x.dim() != 5:
+            raise ValueError(f"VolumeTransforms.batch: expected a (B, 1, D, H, W) batch, got shape {tuple(x.shape)}")
+        kw = self.check(x.shape)
+        if x.is_cuda:
+            return ops.volume_augment(x, step=step, rank=rank, **kw).to(x.dtype)
+        return self._batch_cpu(x, step, rank, kw)
+
+    def draws(self, B: int, dims, step: int, rank: int = 0) -> dict:
+        """the per-sample draws of a step, on the host (numpy; what mm_volume_augment_plan writes into its headers):
+        {"flags": {flip, shift, scale, noise, erase: bool (B,)}, "shift": int (B, 3) = (dz, dy, dx), "factor": fp32 (B,),
+        "erase_box": int (B, 6) = (ez, ey, ex, ed, eh, ew; zeros when off)}"""
+        from .crossmodal_eeg_scr import _aug_hash, _aug_thresh
+        s = dict(zip(ops.VOL_AUG_PURPOSES, ops.volume_augment_streams(self.seed, step, rank)))
+        b = np.arange(B, dtype=np.uint64)
+        draw = lambda name: _aug_hash(s[name], b)  # noqa: E731
+        uniform = lambda name, n: ((draw(name) * np.uint64(n)) >> np.uint64(32)).astype(np.int64)  # noqa: E731
+        flags = {k: draw(k + "_decision") < np.uint64(_aug_thresh(getattr(self, "p_" + k))) for k in ops.VOL_AUG_FLAGS}
+        m = self.max_shift
+        shift = np.stack([uniform("shift_" + ax, 2 * m + 1) - m for ax in "zyx"], axis=1) * flags["shift"][:, None]
+        u = draw("scale_u").astype(np.float64) * 2.0 ** -31 - 1.0
+        factor = np.where(flags["scale"], 1.0 + float(np.float32(self.scale_range)) * u, 1.0).astype(np.float32)
+        ext = self.erase_extents(dims)
+        corner = [uniform("erase_" + ax, int(n) - e + 1) for ax, n, e in zip("zyx", dims, ext)]
+        box = np.stack(corner + [np.full(B, e, dtype=np.int64) for e in ext], axis=1) * flags["erase"][:, None]
+        return {"flags": flags, "shift": shift, "factor": factor, "erase_box": box}
+
+    def _batch_cpu(self, x: torch.Tensor, step: int, rank: int, kw: dict) -> torch.Tensor:
+        from .crossmodal_eeg_scr import _aug_hash
+        B, _, D, H, W = x.shape
+        V, half = D * H * W, (D * H * W + 1) // 2
+        a = x.detach().to(torch.float32).contiguous().numpy()
+        d = self.draws(B, (D, H, W), step, rank)
+        s = dict(zip(ops.VOL_AUG_PURPOSES, ops.volume_augment_streams(self.seed, step, rank)))
+        fill = np.float32(self.fill)
+        out = np.empty_like(a)
+        for b in range(B):
+            src = a[b, 0, :, :, ::-1] if d["flags"]["flip"][b] else a[b, 0]
+            vol = np.full((D, H, W), fill, dtype=np.float32)
+            inside = np.zeros((D, H, W), dtype=bool)
+            dst, frm = [], []
+            for n, sh in zip((D, H, W), d["shift"][b]):           # out[i] = src[i - sh] where 0 <= i - sh < n
+                dst.append(slice(max(int(sh), 0), n + min(int(sh), 0)))
+                frm.append(slice(max(-int(sh), 0), n + min(-int(sh), 0)))
+            vol[tuple(dst)] = src[tuple(frm)]
+            inside[tuple(dst)] = True
+            if d["flags"]["scale"][b]:
+                vol = np.where(inside, vol * d["factor"][b], vol)
+            if d["flags"]["noise"][b]:
+                std = np.float32(a[b].astype(np.float64).std(ddof=1))
+                ns = np.float32(self.noise_factor) * std
+                if ns != 0:
+                    idx = np.uint64(b * half) + np.arange(half, dtype=np.uint64)
+                    u1 = (_aug_hash(s["gauss_a"], idx).astype(np.float64) + 1.0) * 2.0 ** -32
+                    u2 = _aug_hash(s["gauss_b"], idx).astype(np.float64) * 2.0 ** -32
+                    r = np.sqrt(-2.0 * np.log(u1))
+                    z = np.stack([r * np.cos(2.0 * np.pi * u2), r * np.sin(2.0 * np.pi * u2)], axis=-1).reshape(-1)[:V]
+                    vol = np.where(inside, vol + z.astype(np.float32).reshape(D, H, W) * ns, vol)
+            if d["flags"]["erase"][b]:
+                ez, ey, ex, ed, eh, ew = (int(v) for v in d["erase_box"][b])
+                vol[ez:ez + ed, ey:ey + eh, ex:ex + ew] = fill
+            out[b, 0] = vol
+        return torch.from_numpy(np.ascontiguousarray(out)).to(x.dtype)
+
+    def __call__(self, x: torch.Tensor) -> torch.Tensor:
+        """the per-sample dataset form: one (1, D, H, W) or (D, H, W) volume -> a new tensor; the call counter is the step
+        index"""
+        if x.dim() not in (3, 4) or (x.dim() == 4 and x.shape[0] != 1):
+            raise ValueError(f"VolumeTransforms: expected a (1, D, H, W) or (D, H, W) volume, got shape {tuple(x.shape)}")
+        step, self.calls = self.calls, self.calls + 1
+        return self.batch(x.reshape(1, 1, *x.shape[-3:]), step).reshape(x.shape)
+
+    def state_dict(self) -> dict:
+        return {"seed": self.seed, "calls": self.calls}
+
+    def load_state_dict(self, sd: dict) -> None:
+        self.seed, self.calls = int(sd["seed"]), int(sd["calls"])
 
 
 # ---------------------------------------------------------------------------

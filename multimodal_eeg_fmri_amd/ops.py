@@ -392,6 +392,124 @@ def eeg_augment(x: torch.Tensor, *, p_noise: float, p_drop: float, noise_factor:
     return (res, eeg_augment_read_plan(plan, B, C, T)) if return_plan else res
 
 
+# ---- fMRI volume augmentation (csrc/volume_augment.hip): the same h(stream, idx) and stream(seed, step, rank,
+# purpose) as the EEG augmenter, on purposes of its own - the two are independent at equal seed and step.
+VOL_AUG_PURPOSES = ("flip_decision", "shift_decision", "shift_z", "shift_y", "shift_x", "scale_decision", "scale_u",
+                    "noise_decision", "gauss_a", "gauss_b", "erase_decision", "erase_z", "erase_y", "erase_x")
+VOL_AUG_FLAGS = ("flip", "shift", "scale", "noise", "erase")            # bit k of a plan's flag word
+_VOL_HDR = 16
+
+
+def _stream_word(seed: int, step: int, rank: int, purpose: int) -> int:
+    z = (int(seed) * 0x9E3779B97F4A7C15 + int(step) * 0xBF58476D1CE4E5B9 + int(rank) * 0x94D049BB133111EB
+         + (purpose + 1) * 0xD6E8FEB86659FD93) & _M64
+    z ^= z >> 30
+    z = z * 0xBF58476D1CE4E5B9 & _M64
+    z ^= z >> 27
+    z = z * 0x94D049BB133111EB & _M64
+    z ^= z >> 31
+    return (z ^ (z >> 32)) & 0xFFFFFFFF
+
+
+def volume_augment_streams(seed: int, step: int, rank: int = 0) -> tuple:
+    """the fourteen 32-bit stream words of one volume-augmentation step, in `VOL_AUG_PURPOSES` order: purposes 5, 6, ...,
+    18 of csrc/augment.hip's stream(seed, step, rank, purpose) (`augment_streams` holds 0..4)"""
+    return tuple(_stream_word(seed, step, rank, len(AUG_PURPOSES) + k) for k in range(len(VOL_AUG_PURPOSES)))
+
+
+def volume_augment_check(shape, *, p_flip: float, p_shift: float, max_shift: int, p_scale: float, scale_range: float,
+                         p_noise: float, noise_factor: float, p_erase: float, erase, fill: float,
+                         who: str = "volume_augment"):
+    """what both the kernels and the CPU path refuse, before anything runs.  ``shape``: (B, 1, D, H, W); ``erase``: the
+    erased cuboid's extents (ed, eh, ew)"""
+    if len(shape) != 5:
+        raise ValueError(f"{who}: expected a (B, 1, D, H, W) batch, got shape {tuple(shape)}")
+    B, C, D, H, W = (int(v) for v in shape)
+    if C != 1:
+        raise ValueError(f"{who}: volumes have one channel (got C = {C})")
+    V = D * H * W
+    if min(B, D, H, W) < 1 or V < 2:
+        raise ValueError(f"{who}: a sample needs D * H * W >= 2 voxels for its standard deviation (got {D} x {H} x {W})")
+    if V >= 1 << 31:
+        raise ValueError(f"{who}: D * H * W must stay below 2^31 (the voxel index)")
+    if B * ((V + 1) // 2) >= 1 << 32:
+        raise ValueError(f"{who}: B * ceil(D * H * W / 2) must stay below 2^32 (the random stream's index)")
+    for name, p in (("p_flip", p_flip), ("p_shift", p_shift), ("p_scale", p_scale), ("p_noise", p_noise), ("p_erase", p_erase)):
+        if not 0.0 <= p <= 1.0:                                    # (a NaN fails too)
+            raise ValueError(f"{who}: {name} must lie in [0, 1] (got {p!r})")
+    if int(max_shift) != max_shift or not 0 <= max_shift < min(D, H, W):
+        raise ValueError(f"{who}: max_shift must be an integer in [0, min(D, H, W)) = [0, {min(D, H, W)}) (got {max_shift!r})")
+    if not 0.0 <= scale_range < 1.0:
+        raise ValueError(f"{who}: scale_range must lie in [0, 1) (got {scale_range!r})")
+    if not math.isfinite(noise_factor) or not math.isfinite(fill):
+        raise ValueError(f"{who}: noise_factor and fill must be finite (got {noise_factor!r}, {fill!r})")
+    if len(erase) != 3 or any(int(e) != e or not 1 <= e <= n for e, n in zip(erase, (D, H, W))):
+        raise ValueError(f"{who}: the erased cuboid's extents must lie in [1, {D}] x [1, {H}] x [1, {W}] (got {tuple(erase)!r})")
+
+
+def volume_augment_plan_layout(B: int, D: int, H: int, W: int):
+    """(words, words per sample, chunks per sample) of mm_volume_augment_plan's buffer (include/mmeeg_hip.h)"""
+    V, chunk = D * H * W, 4096
+    while (V + chunk - 1) // chunk > 64:
+        chunk *= 2
+    nchunk = (V + chunk - 1) // chunk
+    return B * _VOL_HDR + 4 * B * nchunk, _VOL_HDR, nchunk
+
+
+def _overlap(a: torch.Tensor, b: torch.Tensor) -> bool:
+    a0, b0 = a.data_ptr(), b.data_ptr()
+    return a0 < b0 + b.numel() * b.element_size() and b0 < a0 + a.numel() * a.element_size()
+
+
+def volume_augment_into(x: torch.Tensor, out: torch.Tensor, *, p_flip: float, p_shift: float, max_shift: int, p_scale: float,
+                        scale_range: float, p_noise: float, noise_factor: float, p_erase: float, erase, fill: float, seed: int,
+                        step: int, rank: int = 0, plan: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """the two launches: the plan of batch ``x`` (B, 1, D, H, W) fp32, then the augmented batch into ``out`` (same shape,
+    fp32, contiguous, NOT overlapping ``x``: the shift is a gather).  ``plan``: a buffer of `volume_augment_plan_layout`
+    words to reuse (a training loop keeps one per batch shape).  -> the plan buffer (int32 words)."""
+    kw = dict(p_flip=p_flip, p_shift=p_shift, max_shift=max_shift, p_scale=p_scale, scale_range=scale_range, p_noise=p_noise,
+              noise_factor=noise_factor, p_erase=p_erase, erase=erase, fill=fill)
+    volume_augment_check(x.shape, **kw)
+    if x.dtype != _F32 or out.dtype != _F32 or tuple(out.shape) != tuple(x.shape):
+        raise ValueError(f"volume_augment_into: fp32 batches of one shape (got {x.dtype} {tuple(x.shape)} -> {out.dtype} {tuple(out.shape)})")
+    if _overlap(x, out):
+        raise ValueError("volume_augment_into: source and destination overlap (the shift is a gather: augment into another buffer)")
+    _need_gpu(x, out)
+    B, _, D, H, W = x.shape
+    words, _, _ = volume_augment_plan_layout(B, D, H, W)
+    if plan is None:
+        plan = torch.empty(words, dtype=torch.int32, device=x.device)
+    s = dict(zip(VOL_AUG_PURPOSES, volume_augment_streams(seed, step, rank)))
+    _hip.call("mm_volume_augment_plan", x, plan, words, B, D, H, W, p_flip, p_shift, int(max_shift), p_scale, scale_range, p_noise,
+              p_erase, int(erase[0]), int(erase[1]), int(erase[2]), s["flip_decision"], s["shift_decision"], s["shift_z"],
+              s["shift_y"], s["shift_x"], s["scale_decision"], s["scale_u"], s["noise_decision"], s["erase_decision"],
+              s["erase_z"], s["erase_y"], s["erase_x"])
+    _hip.call("mm_volume_augment", x, plan, words, out, B, D, H, W, noise_factor, fill, s["gauss_a"], s["gauss_b"])
+    return plan
+
+
+def volume_augment_read_plan(plan: torch.Tensor, B: int, D: int, H: int, W: int) -> dict:
+    """a plan both launches have written -> {"flags": {flip, shift, scale, noise, erase: bool (B,)}, "shift": int32 (B, 3)
+    = (dz, dy, dx), "factor": fp32 (B,), "erase_box": int32 (B, 6) = (ez, ey, ex, ed, eh, ew; zeros when off), "std":
+    fp32 (B,), "noise_scale": fp32 (B,)}"""
+    hdr = plan[:B * _VOL_HDR].view(B, _VOL_HDR)
+    return {"flags": {name: (hdr[:, 0] >> k) & 1 != 0 for k, name in enumerate(VOL_AUG_FLAGS)},
+            "shift": hdr[:, 1:4].contiguous(), "factor": hdr[:, 4].contiguous().view(_F32),
+            "erase_box": hdr[:, 5:11].contiguous(), "std": hdr[:, 12].contiguous().view(_F32),
+            "noise_scale": hdr[:, 11].contiguous().view(_F32)}
+
+
+def volume_augment(x: torch.Tensor, *, step: int, rank: int = 0, return_plan: bool = False, **kw):
+    """VolumeTransforms on a device batch (B, 1, D, H, W): flip, shift, scale, noise and erase per sample (the keywords of
+    `volume_augment_into`); the draws are a function of (seed, step, rank) alone.  -> the augmented fp32 batch (a new
+    tensor); with ``return_plan`` also `volume_augment_read_plan`'s dict."""
+    _need_gpu(x)
+    x = x.contiguous().float()
+    out = torch.empty_like(x)
+    plan = volume_augment_into(x, out, step=step, rank=rank, **kw)
+    return (out, volume_augment_read_plan(plan, x.shape[0], *x.shape[2:])) if return_plan else out
+
+
 def igemm(x: torch.Tensor, wf: torch.Tensor, taps: int, pad: int, cout: int, *,
           scale=None, shift=None, act="none", residual=None, pe=None, pool=1, stats=None,
           out_f32=False, out_bf16=True, out_pre=False, drop_p=0.0, seed=0, gradz=None, gradz_act="none"):

@@ -750,6 +750,78 @@ def aug_case(B=32, C=64, T=1024, vol=(32, 32, 32), step_iters=30):
         print(f"C2 graph step B={B}: {name:16s} {us:7.1f} us  (min {min(t):6.1f}, max {max(t):6.1f})  {100 * (us / base - 1):+.2f} %")
 
 
+def volaug_case(B=32, C=64, T=1024, vol=(32, 32, 32), odd=(91, 109, 91), step_iters=30):
+    """fMRI volume augmentation (csrc/volume_augment.hip) at the C2 shape: mm_stage_inputs alone against the staging sequences
+    of a trainer with a volume augmenter - the kernel pair + mm_pack_nct_bf16, and the kernel pair + the EEG augmenter's pair
+    without its fMRI copy - issued eagerly and replayed from a hipGraph, HIP events, interleaved rounds; the kernel pair alone
+    on a batch of odd MNI volumes; then the C2 graph step with and without `fmri_augment`"""
+    from multimodal_eeg_fmri_amd.bridge_trainer import BridgeTrainer, synthetic_pairs
+    from multimodal_eeg_fmri_amd.crossmodal_eeg_scr import EEGTransforms
+    from multimodal_eeg_fmri_amd.fmri_utils import VolumeTransforms
+    eeg, fmri = synthetic_pairs(B, C, T, vol)
+    cp = ops.cpad(C)
+    xb, fdst = torch.empty(B, T, cp, dtype=BF, device="cuda"), torch.empty_like(fmri)
+    step = [0]
+    eplan = torch.empty(ops.eeg_augment_plan_layout(B, C, T)[0], dtype=torch.int32, device="cuda")
+    vplan = torch.empty(ops.volume_augment_plan_layout(B, *vol)[0], dtype=torch.int32, device="cuda")
+    default, every = VolumeTransforms(seed=1), VolumeTransforms(1.0, 1.0, 2, 1.0, 0.1, 1.0, 0.05, 1.0, seed=1)
+
+    def pair(aug, src=fmri, dst=fdst, plan=vplan):
+        step[0] += 1
+        ops.volume_augment_into(src, dst, step=step[0], plan=plan, **aug.kernel_args(src.shape))
+
+    def vol_then_pack(aug):
+        pair(aug)
+        _hip.call("mm_pack_nct_bf16", eeg, xb, B, C, T, cp)
+
+    def vol_then_eeg(aug, p):
+        pair(aug)
+        ops.eeg_augment_into(eeg, xb, None, p_noise=p, p_drop=p, noise_factor=0.05, n_drop=max(1, int(0.1 * C)), seed=1,
+                             step=step[0], plan=eplan)
+    nf, ne = fmri.numel() * 4, eeg.numel() * 4
+    cases = [("mm_stage_inputs", lambda: _hip.call("mm_stage_inputs", eeg, xb, None, B, C, T, cp, fdst, fmri, fmri.numel()), ne + xb.numel() * 2 + 2 * nf),
+             ("volume pair alone, defaults", lambda: pair(default), 3 * nf),
+             ("volume pair alone, every p = 1", lambda: pair(every), 3 * nf),
+             ("volume pair (defaults) + mm_pack_nct_bf16", lambda: vol_then_pack(default), ne + xb.numel() * 2 + 3 * nf),
+             ("volume pair (p = 1) + mm_pack_nct_bf16", lambda: vol_then_pack(every), ne + xb.numel() * 2 + 3 * nf),
+             ("volume pair (defaults) + EEG pair p = 0.3", lambda: vol_then_eeg(default, 0.3), 2 * ne + xb.numel() * 2 + 3 * nf)]
+    times, gtimes = [[] for _ in cases], [[] for _ in cases]
+    for _ in range(5):
+        for i, (_, fn, _) in enumerate(cases):
+            times[i].append(timeit(fn, iters=200, rounds=1))
+            gtimes[i].append(graph_time(fn, n=50))
+    for (name, _, nbytes), t, gt in zip(cases, times, gtimes):
+        us, gus = statistics.median(t), statistics.median(gt)
+        print(f"{name:44s} eager {us:6.2f} us (min {min(t):5.2f}, max {max(t):5.2f})  in a graph {gus:6.2f} us (min {min(gt):5.2f}, "
+              f"max {max(gt):5.2f})  {nbytes / 1e6:5.1f} MB  {nbytes / gus / 1e6:5.2f} TB/s")
+    # the odd MNI volume: the kernel pair alone (scalar loads in the plan, rows that start at any address)
+    g = torch.Generator().manual_seed(3)
+    big = torch.randn(4, 1, *odd, generator=g).cuda()
+    bdst, bplan = torch.empty_like(big), torch.empty(ops.volume_augment_plan_layout(4, *odd)[0], dtype=torch.int32, device="cuda")
+    for name, aug in (("defaults", default), ("every p = 1", every)):
+        t = [timeit(lambda: pair(aug, big, bdst, bplan), iters=100, rounds=1) for _ in range(5)]
+        gt = [graph_time(lambda: pair(aug, big, bdst, bplan), n=50) for _ in range(5)]
+        nbytes = 3 * big.numel() * 4
+        print(f"volume pair alone, B = 4 of {odd[0]}x{odd[1]}x{odd[2]}, {name:12s} eager {statistics.median(t):6.2f} us (min {min(t):5.2f}, max "
+              f"{max(t):5.2f})  in a graph {statistics.median(gt):6.2f} us (min {min(gt):5.2f}, max {max(gt):5.2f})  {nbytes / 1e6:5.1f} MB  "
+              f"{nbytes / statistics.median(gt) / 1e6:5.2f} TB/s")
+    trs, names = [], ("no augmenter", "fmri_augment defaults", "fmri_augment p = 1", "fmri_augment defaults + augment p = 0.3")
+    for vaug, eaug in ((None, None), (default, None), (every, None), (default, EEGTransforms(p=0.3, seed=1))):
+        ops.set_seed_epoch(None)
+        torch.manual_seed(0)
+        tr = BridgeTrainer(eeg_channels=C, dropout=0.3, augment=eaug, fmri_augment=vaug).train()
+        tr.train_step(eeg, fmri)
+        trs.append(tr)
+    times = [[] for _ in trs]
+    for _ in range(5):
+        for i, tr in enumerate(trs):
+            times[i].append(timeit(lambda: tr.train_step(eeg, fmri), iters=step_iters, rounds=1))
+    base = statistics.median(times[0])
+    for name, t in zip(names, times):
+        us = statistics.median(t)
+        print(f"C2 graph step B={B}: {name:40s} {us:7.1f} us  (min {min(t):6.1f}, max {max(t):6.1f})  {100 * (us / base - 1):+.2f} %")
+
+
 def xai_case(B=32, C=64, T=1024, vol=(32, 32, 32), n_steps=50, rounds=5):
     """attribution (csrc/xai.hip, BridgeTrainer.explain) at the C2 shape.  (1) the three streaming kernels alone: GB/s of
     the bytes each must move, beside the ~6.3 TB/s a float4 copy reaches on this part.  (2) integrated gradients of the
@@ -1008,6 +1080,9 @@ def main():
         return
     if flt == "aug":
         aug_case()
+        return
+    if flt == "volaug":
+        volaug_case()
         return
     if flt == "timepool":
         timepool_case()
