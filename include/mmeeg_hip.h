@@ -336,7 +336,8 @@ int mm_pooled_head_bwd_rows(const float* dout, const void* z_pre_bf16, const flo
 /* ---- multi-head self-attention, head_dim 32 (nn.MultiheadAttention,
  * enhanced_models_v4.py:71-73, 99).  qkv [B][L][3E] bf16 -> out [B][L][E] bf16,
  * lse [B][H][L] fp32.  drop_p = attention-probability dropout (train mode).  The
- * head-averaged weights the reference computes and discards (:99) are not produced.
+ * head-averaged weights the reference computes and discards (:99) are not produced here: mm_attn_weights /
+ * mm_attn_received (below) form them from the qkv and lse a saving forward keeps.
  * attn_mask (nullable): the `mask` of TemporalTransformerBlock.forward(x, mask)
  * (enhanced_models_v4.py:88-98 -> self_attn(..., attn_mask=mask)) as an ADDITIVE fp32 (L, L)
  * matrix shared by every batch element and head (a boolean mask = 0 / -inf), or - attn_mask_per_head != 0 -
@@ -359,6 +360,28 @@ int mm_attn_bwd_hd(const void* qkv, const void* out, const void* dout, const flo
                    float* delta_ws, int B, int L, int H, int head_dim, float scale, float drop_p,
                    uint32_t seed, const uint32_t* seed_epoch, const float* attn_mask, int attn_mask_per_head,
                    hipStream_t stream);
+/* Read-out of the attention probabilities (eval mode: no dropout) from what a forward with lse keeps (csrc/attention_readout.hip).
+ * Operands as mm_attn_fwd / mm_attn_fwd_hd: qkv [B][L][3E] bf16, lse [B][H][L] fp32 (natural log), the additive mask in
+ * both forms; head_dim a multiple of 8 in [16, 64], anything else is refused (MM_ERR_ARG, the entry's name and
+ * "head_dim" in mm_last_error()) before a launch.
+ *     P[b][h][i][j] = exp(scale * q_i . k_j + mask[i][j] - lse[b][h][i])
+ * mm_attn_weights: per_head == 0: w fp32 (B, L, L) = the mean of P over the heads, summed in the order h = 0 .. H-1
+ * (nn.MultiheadAttention(need_weights=True, average_attn_weights=True): the second value of the reference's self.attn
+ * call, enhanced_models_v4.py:99); per_head == 1: w (B, H, L, L).  Every element is written once.
+ * A fully masked row (lse = -inf) is NaN in that row of w, as in PyTorch. */
+int mm_attn_weights(const void* qkv, const float* lse, float* w, int B, int L, int H, int head_dim, float scale,
+                    const float* attn_mask, int attn_mask_per_head, int per_head, hipStream_t stream);
+/* out[b][j] = self_weight * r[b][j] + (1 - self_weight) * sum_i r[b][i] * (1/H) sum_h P[b][h][i][j], fp32 (B, L), without
+ * storing a score matrix.  r = row_w (B, L), or 1 / L everywhere when row_w is NULL.  self_weight = 0, row_w NULL: the
+ * attention every time step receives; self_weight = 0.5: one step of attention rollout (Abnar & Zuidema 2020) taken as a
+ * row-vector product r <- r (0.5 A + 0.5 I).  self_weight outside [0, 1] is refused.  ws: mm_attn_received_ws_floats(B, L, H)
+ * floats of scratch (one slot per batch element, head and key, summed in head order by a second launch), no
+ * initialisation.  No floating-point atomics: the same inputs give the same bits.  A fully masked query row is NaN in
+ * EVERY column of its batch element (every key sums over that query).  Two launches on `stream`. */
+int mm_attn_received(const void* qkv, const float* lse, const float* row_w, float self_weight, float* out, float* ws,
+                     int B, int L, int H, int head_dim, float scale, const float* attn_mask, int attn_mask_per_head,
+                     hipStream_t stream);
+int mm_attn_received_ws_floats(int B, int L, int H, int* floats_host, hipStream_t stream);
 
 /* ---- small reductions / elementwise --------------------------------------- */
 int mm_colsum(const void* a_bf16, const float* a_f32, float* out, int M, int N, hipStream_t stream);

@@ -1169,6 +1169,24 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
         return ze, zf
 
     @torch.no_grad()
+    def temporal_attention(self, eeg: torch.Tensor, method: str = "rollout", layer: Optional[int] = None,
+                           batch_size: int = 256) -> Dict[str, torch.Tensor]:
+        """Which time steps the EEG encoder's transformer stack attends to (``ops.encoder_attention``): ``method``
+        "rollout" (attention rollout over all layers to the mean-pooled feature) or "received" (the attention every step
+        receives in layer ``layer``, default the last).  Host or device input, ``batch_size`` epochs at a time like
+        ``embed``.  -> {"tokens": (N, L)} and, where the token-to-sample map is fixed (ERP: pooled pairs, power: identity;
+        not the overlapping STFT frames), "time": (N, T); fp32 on the trainer's device.  Forward kernels only, in their
+        eval form (frozen BatchNorm, no dropout, no seed drawn) whatever the train / eval flags are: parameters,
+        BatchNorm buffers, the dropout seed counter, the gradient bucket and a captured graph stay as they were.  An
+        EEG encoder without transformer layers raises ValueError."""
+        if batch_size < 1:
+            raise ValueError("temporal_attention: batch_size must be >= 1")
+        ops.weights_changed()                      # graph replays bypass the python-side version counter
+        parts = [ops.encoder_temporal_attention(self.eeg_encoder, x, method, layer)
+                 for x in self._chunks(eeg, batch_size, self._scal.device)]
+        return {k: torch.cat([p[k] for p in parts]) for k in parts[0]}
+
+    @torch.no_grad()
     def evaluate_retrieval(self, eeg, fmri, batch_size: int = 256, ks=(1, 5, 10), k: int = 0, groups=None):
         """held-out gallery retrieval: ``embed`` both modalities, then ``retrieval_metrics`` (pair i is the positive of
         query i, both directions; with ``groups`` (N,) every pair of the query's group, the best-placed one ranked).

@@ -21,6 +21,7 @@ from . import ops
 from .enhanced_models_v4 import (  # noqa: F401  (reference keeps copies here)
     EnhancedERPEncoder, EnhancedPowerEncoder, LearnedFusionModule,
     PositionalEncoding, TemporalTransformerBlock)
+from .enhanced_models_v4 import _TemporalAttentionReadout
 
 
 # ----------------------------------------------------------------- utilities
@@ -268,7 +269,7 @@ class BalancedTriModalDataset(torch.utils.data.Dataset):
 
 
 # ----------------------------------------------------------------- encoders
-class MultiScaleSTFTPowerEncoder(nn.Module):
+class MultiScaleSTFTPowerEncoder(_TemporalAttentionReadout, nn.Module):
     """BASELINE config #5 front-end (north-star extension a-X3; the reference loads
     MATLAB spectra instead, eeg_data_utils.py:86-119): raw EEG (B, C, T) -> Hann STFT
     power at several window sizes -> (B, C * sum(F), frames) -> [per-sample z-score] -> EnhancedPowerEncoder.

@@ -273,6 +273,40 @@ def attention_connectivity_importance(encoder, x: torch.Tensor, edge_index: torc
     return {pair: v / total for pair, v in raw.items()}
 
 
+def temporal_attention_importance(model, erp: Optional[torch.Tensor] = None, pw: Optional[torch.Tensor] = None,
+                                  method: str = "rollout", top_k: int = 10) -> Dict[str, Dict[str, object]]:
+    """which time steps the EEG transformer encoders attend to: {"erp": {...}, "pw": {...}} for the modalities given.
+    ``model`` is a fusion net with ``erp_encoder`` / ``pw_encoder`` (EnhancedTriModalFusionNet, the V4 nets) or a bare
+    encoder (its input goes in ``erp`` for an EnhancedERPEncoder, in ``pw`` otherwise).  Per modality: "tokens" (B, L)
+    from ``encoder.temporal_attention(x, method)`` ("rollout" / "received") and "time" (B, T) where the encoder
+    defines it, as numpy, and "top_steps": the ``top_k`` steps of the batch-mean importance ("time" when there is one,
+    else "tokens") as [(index, value), ...], largest first.  Eval-mode semantics; the train / eval flags are not
+    touched.  A model without a transformer encoder (the Lite nets, the notebook baselines) raises ValueError."""
+    pairs = []
+    if hasattr(model, "erp_encoder") or hasattr(model, "pw_encoder"):
+        if erp is not None:
+            pairs.append(("erp", getattr(model, "erp_encoder", None), erp))
+        if pw is not None:
+            pairs.append(("pw", getattr(model, "pw_encoder", None), pw))
+    else:
+        kind = ops._attention_encoder(model)[0]             # ValueError for anything that is not a transformer encoder
+        name = "erp" if kind == "erp" else "pw"
+        pairs.append((name, model, erp if name == "erp" else pw))
+    if not pairs or any(x is None for _, _, x in pairs):
+        raise ValueError("temporal_attention_importance: give erp= and / or pw= inputs for the model's encoders")
+    out: Dict[str, Dict[str, object]] = {}
+    for name, enc, x in pairs:
+        if enc is None:
+            raise ValueError(f"temporal_attention_importance: {type(model).__name__} has no {name}_encoder")
+        res = ops.encoder_temporal_attention(enc, x, method)
+        entry: Dict[str, object] = {k: v.detach().float().cpu().numpy() for k, v in res.items()}
+        steps = entry.get("time", entry["tokens"]).mean(axis=0)
+        order = np.argsort(-steps, kind="stable")[:max(int(top_k), 0)]
+        entry["top_steps"] = [(int(i), float(steps[i])) for i in order]
+        out[name] = entry
+    return out
+
+
 class EEGExplainer:
     """several attribution methods + channel-level summaries behind one object (reference :498-693)"""
 

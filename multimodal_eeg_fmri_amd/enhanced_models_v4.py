@@ -76,6 +76,27 @@ class TemporalTransformerBlock(nn.Module):
         # (True = not allowed) or additive float; the encoders themselves never pass one (reference :169-193)
         return ops.transformer_block(x, self, self.training, mask)
 
+    def attention_weights(self, x: torch.Tensor, mask: Optional[torch.Tensor] = None,
+                          average_attn_weights: bool = True) -> torch.Tensor:
+        """the second value of the reference's ``self.attn(x, x, x, attn_mask=mask)`` on ``norm1(x)`` (:99, which it
+        discards): eval-mode attention probabilities, fp32 (B, L, L) averaged over the heads or (B, heads, L, L)"""
+        return ops.block_attention_weights(self, x, mask, average_attn_weights)
+
+
+class _TemporalAttentionReadout:
+    """what the three EEG transformer encoders share: the attention of their transformer stack over time"""
+
+    def attention_maps(self, x: torch.Tensor) -> List[torch.Tensor]:
+        """one head-averaged (B, L, L) attention matrix per transformer layer, eval-mode semantics (frozen BatchNorm, no
+        dropout) whatever the module's train / eval flags are; they are left as they were"""
+        return ops.encoder_attention(self, x, "maps")
+
+    def temporal_attention(self, x: torch.Tensor, method: str = "rollout", layer: Optional[int] = None) -> Dict[str, torch.Tensor]:
+        """per-time-step importance from the attention maps, without storing them: ``method`` "rollout" (all layers) or
+        "received" (layer ``layer``, default last).  {"tokens": (B, L)} and, where the token-to-sample map is fixed,
+        "time": (B, T), which sums to what "tokens" sums to."""
+        return ops.encoder_temporal_attention(self, x, method, layer)
+
 
 def _transformer_stack(hidden_dim, layers, heads, dropout):
     return nn.ModuleList([
@@ -89,7 +110,7 @@ def _pool_proj(hidden_dim, dropout):
                          nn.Linear(hidden_dim, hidden_dim), nn.GELU(), _drop(dropout))
 
 
-class EnhancedERPEncoder(nn.Module):
+class EnhancedERPEncoder(_TemporalAttentionReadout, nn.Module):
     """(B, C, T) fp32 -> (B, hidden_dim): 3x [Conv1d-BN-GELU] (+MaxPool2 after
     the second) -> PE -> N transformer blocks -> mean over time -> Linear-GELU."""
 
@@ -114,7 +135,7 @@ class EnhancedERPEncoder(nn.Module):
         return ops.erp_encoder_forward(self, x)
 
 
-class EnhancedPowerEncoder(nn.Module):
+class EnhancedPowerEncoder(_TemporalAttentionReadout, nn.Module):
     """Multi-scale k=3/5/7 Conv1d front-end -> 1x1 fusion conv -> same tail."""
 
     def __init__(self, in_channels: int, hidden_dim: int = 128,

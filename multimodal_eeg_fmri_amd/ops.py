@@ -791,6 +791,160 @@ def additive_attn_mask(mask, L: int, like: torch.Tensor):
     return mask.to(device=like.device, dtype=_F32).contiguous()
 
 
+# ------------------------------------------------------- attention read-out
+def _attn_readout_args(qkv: torch.Tensor, lse: torch.Tensor, nhead: int, mask, who: str):
+    """what ``attention_weights`` / ``attention_received`` check alike, before a launch: the packed bf16 (B, L, 3E)
+    projections, the fp32 (B, nhead, L) log-sum-exp, the head-dim rule of ``attn_entry`` and the two mask forms"""
+    if qkv.dim() != 3 or qkv.dtype != _BF or qkv.shape[2] % 3 or min(qkv.shape) < 1:
+        raise ValueError(f"{who}: qkv must be a non-empty bf16 (B, L, 3 E) tensor, got {qkv.dtype} {tuple(qkv.shape)}")
+    B, L, E3 = qkv.shape
+    attn_entry(E3 // 3, nhead, "fwd")
+    if lse.dtype != _F32 or tuple(lse.shape) != (B, nhead, L):
+        raise ValueError(f"{who}: lse must be fp32 (B, heads, L) = ({B}, {nhead}, {L}), got {lse.dtype} {tuple(lse.shape)}")
+    mask = additive_attn_mask(mask, L, qkv)
+    per = attn_mask_per_head(mask, B, nhead, L)
+    return B, L, E3 // 3 // nhead, mask, per
+
+
+def attention_weights(qkv: torch.Tensor, lse: torch.Tensor, nhead: int, mask=None, per_head: bool = False) -> torch.Tensor:
+    """the eval-mode attention probabilities of a forward that kept ``qkv`` and ``lse`` (``transformer_block_fwd``'s
+    ``saved['qkv']`` / ``saved['lse']``): fp32 (B, L, L), the mean over the heads - what nn.MultiheadAttention returns
+    with ``need_weights=True`` - or (B, nhead, L, L) with ``per_head``.  One launch of mm_attn_weights."""
+    B, L, dh, mask, per = _attn_readout_args(qkv, lse, nhead, mask, "attention_weights")
+    _need_gpu(qkv, lse)
+    w = _empty((B, nhead, L, L) if per_head else (B, L, L), _F32, qkv)
+    _hip.call("mm_attn_weights", qkv.contiguous(), lse.contiguous(), w, B, L, nhead, dh, 1.0 / math.sqrt(dh), mask, per,
+              1 if per_head else 0)
+    return w
+
+
+def attention_received(qkv: torch.Tensor, lse: torch.Tensor, nhead: int, row_w: Optional[torch.Tensor] = None,
+                       self_weight: float = 0.0, mask=None) -> torch.Tensor:
+    """fp32 (B, L): ``self_weight * r + (1 - self_weight) * r @ A`` with A the head-averaged attention matrix of
+    ``attention_weights`` - never stored - and r = ``row_w`` (B, L), or 1 / L everywhere.  The defaults give the attention
+    every time step receives; ``self_weight = 0.5`` is one step of attention rollout (mm_attn_received)."""
+    B, L, dh, mask, per = _attn_readout_args(qkv, lse, nhead, mask, "attention_received")
+    if not 0.0 <= float(self_weight) <= 1.0:
+        raise ValueError(f"attention_received: self_weight must lie in [0, 1], got {self_weight}")
+    if row_w is not None:
+        if tuple(row_w.shape) != (B, L):
+            raise ValueError(f"attention_received: row_w must be (B, L) = ({B}, {L}), got {tuple(row_w.shape)}")
+        row_w = row_w.to(_F32).contiguous()
+    _need_gpu(qkv, lse, row_w)
+    out = _empty((B, L), _F32, qkv)
+    ws = _empty((max(_hip.host_int("mm_attn_received_ws_floats", B, L, nhead), 1),), _F32, qkv)
+    _hip.call("mm_attn_received", qkv.contiguous(), lse.contiguous(), row_w, float(self_weight), out, ws, B, L, nhead, dh,
+              1.0 / math.sqrt(dh), mask, per)
+    return out
+
+
+ATTN_READOUT_METHODS = ("received", "rollout", "maps")
+
+
+def _attention_encoder(encoder):
+    """(kind, the module that owns ``transformer_layers``) of an encoder ``encoder_attention`` serves"""
+    from .crossmodal_v4_enhancements import MultiScaleSTFTPowerEncoder
+    from .enhanced_models_v4 import EnhancedERPEncoder, EnhancedPowerEncoder
+    if isinstance(encoder, EnhancedERPEncoder):
+        return "erp", encoder
+    if isinstance(encoder, EnhancedPowerEncoder):
+        return "power", encoder
+    if isinstance(encoder, MultiScaleSTFTPowerEncoder):
+        return "stft", encoder.encoder
+    raise ValueError(f"encoder_attention: {type(encoder).__name__} is not an EEG transformer encoder (EnhancedERPEncoder, "
+                     "EnhancedPowerEncoder, MultiScaleSTFTPowerEncoder): it has no temporal attention to read out")
+
+
+def encoder_tokens(encoder, T: int) -> int:
+    """tokens the transformer stack of ``encoder`` sees for a ``T``-sample input: the ERP encoder pools by 2, the power
+    encoder keeps every step, the STFT front end makes T // hop + 1 frames"""
+    kind, _ = _attention_encoder(encoder)
+    return T // 2 if kind == "erp" else T if kind == "power" else T // encoder.hop + 1
+
+
+def spread_pooled_tokens(tokens: torch.Tensor, T: int) -> torch.Tensor:
+    """(B, L) token weights of the ERP encoder -> (B, T) sample weights: token i came out of MaxPool1d(2) over samples
+    2i, 2i + 1 (the convolutions keep the length), which share its weight equally; an odd last sample fed no token and
+    gets 0.  The sum over time is the sum over tokens."""
+    B, L = tokens.shape
+    if L != T // 2:
+        raise ValueError(f"spread_pooled_tokens: {L} tokens do not come from {T} samples (expected {T // 2})")
+    time = tokens.new_zeros((B, T))
+    time[:, :2 * L] = (0.5 * tokens).repeat_interleave(2, dim=1)
+    return time
+
+
+def encoder_attention(encoder, x: torch.Tensor, method: str, layer: Optional[int] = None, mask=None):
+    """What the transformer stack of an EEG encoder attends to over time.  ONE eval-mode forward (frozen BatchNorm, no
+    dropout, no seed drawn: the module's own train / eval flags are not consulted and not touched) keeps every block's
+    ``qkv`` and ``lse``; the read-out kernels do the rest.
+      "maps":     the list of per-layer head-averaged (B, L, L) matrices;
+      "received": (B, L), the mean over the queries of layer ``layer``'s matrix (default: the last layer);
+      "rollout":  (B, L), attention rollout (Abnar & Zuidema 2020) to the mean-pooled feature: r_N = 1 / L,
+                  r_{l-1} = r_l (0.5 A_l + 0.5 I) - a chain of N vector steps, no L x L product is formed."""
+    if method not in ATTN_READOUT_METHODS:
+        raise ValueError(f"encoder_attention: unknown method {method!r} (one of {', '.join(ATTN_READOUT_METHODS)})")
+    kind, inner = _attention_encoder(encoder)
+    n = len(inner.transformer_layers)
+    if n == 0:
+        raise ValueError(f"encoder_attention: this {type(encoder).__name__} has no transformer layers")
+    if layer is not None and method != "received":
+        raise ValueError(f"encoder_attention: layer applies to method 'received' only, not to {method!r}")
+    li = n - 1 if layer is None else int(layer)
+    if not 0 <= li < n:
+        raise ValueError(f"encoder_attention: layer {layer} out of range for {n} transformer layers")
+    if x.dim() != 3:
+        raise ValueError(f"encoder_attention: expected (batch, channels, time), got {tuple(x.shape)}")
+    _need_gpu(x)
+    nhead = inner.transformer_layers[0].nhead
+    with torch.no_grad():
+        mask = additive_attn_mask(mask, encoder_tokens(encoder, x.shape[2]), x)
+        if kind == "erp":
+            saved = _erp_forward_impl(inner, x.float(), False, True, save=True, mask=mask)[1]
+        else:
+            xb = pack_nct(x.float()) if kind == "power" else stft_front_end(x, encoder.n_ffts, encoder.hop, encoder.normalize)
+            saved = _power_forward_impl(inner, xb, False, True, save=True, mask=mask)[1]
+        recs = [(s["qkv"].view(s["B"], s["L"], -1), s["lse"]) for s in saved["blocks"]]
+        if method == "maps":
+            return [attention_weights(q, l, nhead, mask) for q, l in recs]
+        if method == "received":
+            return attention_received(*recs[li], nhead, mask=mask)
+        r = None
+        for q, l in reversed(recs):
+            r = attention_received(q, l, nhead, row_w=r, self_weight=0.5, mask=mask)
+        return r
+
+
+def encoder_temporal_attention(encoder, x: torch.Tensor, method: str = "rollout", layer: Optional[int] = None) -> dict:
+    """``encoder_attention`` as the encoders' ``temporal_attention`` returns it: {"tokens": (B, L)} plus "time": (B, T)
+    where the token-to-sample map is fixed - the ERP encoder's pooled pairs, the power encoder's identity; STFT frames
+    overlap, so there is none."""
+    if method == "maps":
+        raise ValueError("temporal_attention: method 'maps' has no per-step form; call attention_maps")
+    tokens = encoder_attention(encoder, x, method, layer)
+    out = {"tokens": tokens}
+    kind, _ = _attention_encoder(encoder)
+    if kind == "erp":
+        out["time"] = spread_pooled_tokens(tokens, x.shape[2])
+    elif kind == "power":
+        out["time"] = tokens
+    return out
+
+
+def block_attention_weights(blk, x: torch.Tensor, mask=None, average_attn_weights: bool = True) -> torch.Tensor:
+    """TemporalTransformerBlock.attention_weights: norm1, in-projection, attention forward with lse, mm_attn_weights"""
+    if x.dim() != 3:
+        raise ValueError(f"attention_weights: expected (batch, seq, d_model), got {tuple(x.shape)}")
+    _need_gpu(x)
+    B, L, D = x.shape
+    with torch.no_grad():
+        mask = additive_attn_mask(mask, L, x)
+        h1, _ = layernorm(x.float().contiguous().view(B * L, D), blk.norm1, False)
+        qkv = linear_rows(h1, blk.self_attn.in_proj_weight, blk.self_attn.in_proj_bias)["bf16"].view(B, L, 3 * D)
+        _, lse = attention(qkv, blk.nhead, True, mask=mask)
+        return attention_weights(qkv, lse, blk.nhead, mask, per_head=not average_attn_weights)
+
+
 # ------------------------------------------------------------------- stages
 def conv_bn_act(xb: torch.Tensor, conv, bn, *, act="gelu", pool=1, training=False, drop_p=0.0,
                 drop_first=True, pe=None, pe_drop_p=0.0, want_f32=False, want_bf16=True, need_dgrad=False,
@@ -1102,10 +1256,11 @@ def pe_table(pos_encoder, L: int) -> torch.Tensor:
 
 
 # ------------------------------------------------------------ EEG encoders
-def _encoder_tail_impl(m, h, training: bool, need_dgrad: bool, save: bool, prenorm=None, stages=None):
+def _encoder_tail_impl(m, h, training: bool, need_dgrad: bool, save: bool, prenorm=None, stages=None, mask=None):
     """shared tail of both EEG encoders: transformer stack -> mean pool -> Linear -> GELU.
     ``prenorm``: (norm1(h) bf16, stats) of the FIRST block when the producer of ``h`` already formed it.
-    ``stages`` (dict, inspection only): receives a copy of the residual stream after every block (``block<i>``)."""
+    ``stages`` (dict, inspection only): receives a copy of the residual stream after every block (``block<i>``).
+    ``mask`` (additive fp32, ``additive_attn_mask``): every block's attn_mask; the encoders' own forward passes none."""
     blocks = []
     B, L, D = h.shape
     nblk = len(m.transformer_layers)
@@ -1115,9 +1270,9 @@ def _encoder_tail_impl(m, h, training: bool, need_dgrad: bool, save: bool, preno
     for i, blk in enumerate(layers):
         if i < nblk - 1:                                 # the next block's norm1 rides in this block's last GEMM
             h, s, prenorm = transformer_block_fwd(h, blk, training, need_dgrad, save=save, prenorm=prenorm,
-                                                  next_norm=layers[i + 1].norm1, next_blk=layers[i + 1])
+                                                  next_norm=layers[i + 1].norm1, next_blk=layers[i + 1], mask=mask)
         else:
-            h, s = transformer_block_fwd(h, blk, training, need_dgrad, save=save, pool_out=pooled, prenorm=prenorm)
+            h, s = transformer_block_fwd(h, blk, training, need_dgrad, save=save, pool_out=pooled, prenorm=prenorm, mask=mask)
         blocks.append(s)
         if stages is not None:
             stages[f"block{i}"] = h.clone()
@@ -1126,7 +1281,7 @@ def _encoder_tail_impl(m, h, training: bool, need_dgrad: bool, save: bool, preno
     return out, blocks, s, h
 
 
-def _erp_forward_impl(m, x: torch.Tensor, training: bool, need_dgrad: bool, save=None, xb=None, stages=None):
+def _erp_forward_impl(m, x: torch.Tensor, training: bool, need_dgrad: bool, save=None, xb=None, stages=None, mask=None):
     """EnhancedERPEncoder forward; returns (features fp32 (B, H), saved list).
     ``save`` (default = training): keep what a backward needs (eval + save = frozen BatchNorm).
     ``xb``: ``pack_nct(x)`` when the caller already holds it (a trainer stages its inputs packed).
@@ -1162,7 +1317,8 @@ def _erp_forward_impl(m, x: torch.Tensor, training: bool, need_dgrad: bool, save
             o4 = bn_fold_eval(cl[10], cl[9].bias)
             stages["conv3"] = igemm(saved_in[1], wf3, cl[9].kernel_size[0], cl[9].padding[0], cl[9].out_channels,
                                     scale=o4[0], shift=o4[1], act="gelu", out_f32=True, out_bf16=False)["f32"]
-    out, blocks, s, h = _encoder_tail_impl(m, r["f32"], training, need_dgrad, save, prenorm=r.get("prenorm"), stages=stages)
+    out, blocks, s, h = _encoder_tail_impl(m, r["f32"], training, need_dgrad, save, prenorm=r.get("prenorm"), stages=stages,
+                                           mask=mask)
     return out, dict(convs=saved, blocks=blocks, head=s, x_shape=tuple(x.shape), tokens=h)
 
 
@@ -2631,7 +2787,7 @@ def _power_merged_train(m, need_dgrad: bool = True):
     return conv, bn, seqs
 
 
-def _power_forward_impl(m, xb: torch.Tensor, training: bool, need_dgrad: bool, save=None):
+def _power_forward_impl(m, xb: torch.Tensor, training: bool, need_dgrad: bool, save=None, mask=None):
     """EnhancedPowerEncoder on packed (B, T, Cp) bf16 input, train / frozen-BN forms."""
     save = training if save is None else save
     conv, bn, seqs = _power_merged_train(m, need_dgrad)
@@ -2647,7 +2803,7 @@ def _power_forward_impl(m, xb: torch.Tensor, training: bool, need_dgrad: bool, s
     r, s1 = conv_bn_act(r["bf16"], m.fusion[0], m.fusion[1], training=training, drop_p=p,
                         pe=pe_table(m.pos_encoder, T), pe_drop_p=(m.pos_encoder.dropout.p if training else 0.0),
                         want_f32=True, want_bf16=False, need_dgrad=True, save=save)
-    out, blocks, sh, h = _encoder_tail_impl(m, r["f32"], training, True, save)
+    out, blocks, sh, h = _encoder_tail_impl(m, r["f32"], training, True, save, mask=mask)
     return out, dict(convs=[s0, s1], blocks=blocks, head=sh, merged=(conv, bn, seqs), tokens=h)
 
 

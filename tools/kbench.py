@@ -174,6 +174,33 @@ def attn_case(B=32, L=512, H=4, p=0.1, head_dim=32):
           f"bwd (dq + dkv) {b:6.1f} us")
 
 
+def attnmap_case(B=32, L=512, H=4, head_dim=32):
+    """the attention read-out (csrc/attention_readout.hip) next to the forward it reads from: head-mean weights, received,
+    and the route it replaces - per-head weights materialised, then reduced by torch"""
+    E = H * head_dim
+    fwd = ops.attn_entry(E, H, "fwd")
+    qkv = (torch.randn(B, L, 3 * E, device="cuda") * 0.5).to(BF)
+    out = torch.empty(B, L, E, dtype=BF, device="cuda")
+    lse = torch.empty(B, H, L, device="cuda")
+    sc = 1 / math.sqrt(head_dim)
+    _hip.call(fwd, qkv, out, lse, B, L, H, head_dim, sc, 0.0, 0, None, None, 0)
+    w = torch.empty(B, L, L, device="cuda")
+    wh = torch.empty(B, H, L, L, device="cuda")
+    rec = torch.empty(B, L, device="cuda")
+    ws = torch.empty(_hip.host_int("mm_attn_received_ws_floats", B, L, H), device="cuda")
+    f = timeit(lambda: _hip.call(fwd, qkv, out, lse, B, L, H, head_dim, sc, 0.0, 0, None, None, 0))
+    tw = timeit(lambda: _hip.call("mm_attn_weights", qkv, lse, w, B, L, H, head_dim, sc, None, 0, 0))
+    tr = timeit(lambda: _hip.call("mm_attn_received", qkv, lse, None, 0.0, rec, ws, B, L, H, head_dim, sc, None, 0))
+
+    def materialise():
+        _hip.call("mm_attn_weights", qkv, lse, wh, B, L, H, head_dim, sc, None, 0, 1)
+        return wh.mean(dim=(1, 2))
+    tm = timeit(materialise)
+    print(f"attnmap B={B} L={L} H={H} dh={head_dim}: fwd (p=0) {f:7.1f} us | weights (head mean) {tw:7.1f} us, writes "
+          f"{w.numel() * 4 / 1e6:.1f} MB | received {tr:7.1f} us, writes {(ws.numel() + rec.numel()) * 4 / 1e6:.2f} MB | "
+          f"per-head weights + torch mean {tm:7.1f} us, writes {wh.numel() * 4 / 1e6:.1f} MB")
+
+
 def floor_case():
     x = torch.zeros(64, device="cuda")
     y = torch.zeros(64, device="cuda")
@@ -1058,6 +1085,10 @@ def main():
     flt = sys.argv[1] if len(sys.argv) > 1 else ""
     if flt == "ffnbwd":
         ffnbwd_case()
+        return
+    if flt == "attnmap":
+        attnmap_case(L=512)
+        attnmap_case(L=1024)
         return
     if flt.startswith("gat"):          # gat[:B,N,H,C]
         dims = [int(d) for d in flt.split(":", 1)[1].split(",")] if ":" in flt and flt.split(":", 1)[1] else []
