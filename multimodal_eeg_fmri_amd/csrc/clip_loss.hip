@@ -154,12 +154,14 @@ __global__ __launch_bounds__(256) void clip_lse_kernel(const float* __restrict__
         clip_sum2(qee, qef, sh.red);
     }
     if (tid == 0) {
+        // the row's loss = LSE - LSE_P as s (max - max_P) + (log sum - log sum_P), ungrouped s (max - diag) + log sum: never
+        // the difference of two numbers near s, whose rounding (4e-6 at s = 100) is the size of a trained model's loss
         if constexpr (GROUPED) {
-            const float lse_r = s * mxr + __logf(se), lse_c = s * mxc + __logf(sf);
-            const float lsp_r = s * pmr + __logf(qe), lsp_c = s * pmc + __logf(qf);
-            ws[r] = lse_r;
-            ws[Bg + r] = lse_c;
-            ws[2 * Bg + r] = 0.5f * ((lse_r - lsp_r) + (lse_c - lsp_c));
+            const float lg_r = __logf(se), lg_c = __logf(sf), lq_r = __logf(qe), lq_c = __logf(qf);
+            const float lsp_r = s * pmr + lq_r, lsp_c = s * pmc + lq_c;
+            ws[r] = s * mxr + lg_r;
+            ws[Bg + r] = s * mxc + lg_c;
+            ws[2 * Bg + r] = 0.5f * ((s * (mxr - pmr) + (lg_r - lq_r)) + (s * (mxc - pmc) + (lg_c - lq_c)));
             ws[3 * Bg + r] = pmr >= mxr ? 1.f : 0.f;         // the best positive reaches the row maximum (a tie counts FOR it)
             ws[4 * Bg + r] = pmc >= mxc ? 1.f : 0.f;
             ws[5 * Bg + r] = s * 0.5f * ((ee / se - qee / qe) + (ef / sf - qef / qf));
@@ -167,10 +169,10 @@ __global__ __launch_bounds__(256) void clip_lse_kernel(const float* __restrict__
             ws[7 * Bg + r] = lsp_c;
         } else {
             const float diag = sh.cr[r];
-            const float lse_r = s * mxr + __logf(se), lse_c = s * mxc + __logf(sf);
-            ws[r] = lse_r;
-            ws[Bg + r] = lse_c;
-            ws[2 * Bg + r] = 0.5f * ((lse_r - s * diag) + (lse_c - s * sh.cc[r]));
+            const float lg_r = __logf(se), lg_c = __logf(sf);
+            ws[r] = s * mxr + lg_r;
+            ws[Bg + r] = s * mxc + lg_c;
+            ws[2 * Bg + r] = 0.5f * ((s * (mxr - diag) + lg_r) + (s * (mxc - sh.cc[r]) + lg_c));
             // top-1: a tie with the row maximum counts FOR the pair (diag >= max).  mm_retrieval's rank counts a tie
             // AGAINST the query (csrc/retrieval.hip), so a collapsed encoder ranks Ng there but scores top-1 = 1 here.
             ws[3 * Bg + r] = diag >= mxr ? 1.f : 0.f;
@@ -200,7 +202,8 @@ __global__ __launch_bounds__(256) void clip_rows_kernel(const float* __restrict_
 #pragma unroll
             for (int q = 0; q < 4; ++q) acc[q] += wave_sum(v[q]);
         }
-        if (tid < 4) scal[tid] = (tid == 0 ? acc[0] : tid == 1 ? acc[1] : tid == 2 ? acc[2] : acc[3]) * invB;
+        // divided, not scaled by a rounded 1/B: the top-1 fractions are count / B rounded once, whatever B is
+        if (tid < 4) scal[tid] = (tid == 0 ? acc[0] : tid == 1 ? acc[1] : tid == 2 ? acc[2] : acc[3]) / (float)B;
     }
     if (!dz) return;
     float mxr, mxc;
