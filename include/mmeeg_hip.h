@@ -924,12 +924,27 @@ int mm_meanpool_bf16(const void* x, float* out, int R, int S, int N, hipStream_t
  * partial sums written by mm_sumsq and added in a fixed order by mm_adamw_clip (no float
  * atomics: ranks holding the same all-reduced gradient stay bit-identical).
  * zero_grad != 0: g is cleared after use (the next step's zero_grad()); seed_epoch (nullable): the
- * device dropout-epoch word is incremented for the next step. */
+ * device dropout-epoch word is incremented for the next step.
+ * state[5]: the weight-average decay d of the last step, written by mm_adamw_clip_ema only; mm_adamw_clip never writes
+ * state[5..8).
+ *
+ * mm_adamw_clip_ema: the same update (the same kernel template: p, g, m, v and state[0..5) get mm_adamw_clip's bits)
+ * plus an exponential moving average of the weights in `ema` (n floats, device, not NULL), in the same launch:
+ *     ema[i] = fma(1 - d, p_new[i] - ema[i], ema[i])
+ * with 1 - d formed in fp32, the difference rounded to fp32, then one fused multiply-add - so ema[i] keeps its bits
+ * wherever it already equals p_new[i].  d comes from the step count on the device (the launch can live in a hipGraph):
+ * with t = state[0] + 1, the count after this step, d = ema_warmup ? min(ema_decay, (1 + t) / (10 + t)) : ema_decay.
+ * ema_decay must lie in [0, 1); a NULL ema or a decay outside the range is an argument error, nothing is launched.
+ * No float atomics: ranks that hold the same parameters keep bit-identical averages without a collective. */
 #define MM_OPT_STATE_FLOATS 1032
 int mm_sumsq(const float* g, float* state, int64_t n, hipStream_t stream);
 int mm_adamw_clip(float* p, float* g, float* m, float* v, float* state, int64_t n, float beta1,
                   float beta2, float eps, float weight_decay, float max_norm, float grad_scale,
                   int zero_grad, uint32_t* seed_epoch, hipStream_t stream);
+int mm_adamw_clip_ema(float* p, float* g, float* m, float* v, float* state, int64_t n, float beta1,
+                      float beta2, float eps, float weight_decay, float max_norm, float grad_scale,
+                      int zero_grad, uint32_t* seed_epoch, float* ema, float ema_decay, int ema_warmup,
+                      hipStream_t stream);
 
 /* ---- attribution (EEG_CODE/eeg_xai_analysis.py:88-236: GradientSaliency, IntegratedGradients) ---------------
  * The reference walks its n_steps interpolation points one forward/backward at a time with a numpy round trip

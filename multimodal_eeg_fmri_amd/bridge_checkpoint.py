@@ -15,7 +15,9 @@ The file is the container of the reference's loops and of `FlexibleTrainer.save_
   only for a trainer of the pairwise sigmoid loss - ``loss`` = ``"sigmoid"`` (absent: InfoNCE), and - only for a trainer
   built with ``classify=True`` - ``classify`` = ``{ce_weight, num_classes, class_weight}``, and - only for a trainer with
   a cross-batch memory (``bank_size > 0``) - ``bank`` = ``{size, warmup, grouped, state, rows, ids}``: the ring's words,
-  rows and group ids (``rows`` / ``ids`` None before the first training step).
+  rows and group ids (``rows`` / ``ids`` None before the first training step), and - only for a trainer that keeps
+  averaged weights (``ema_decay > 0``) - ``ema`` = ``{decay, warmup, shadow}``: ``shadow`` is the flat fp32 average of
+  the bucket (``bucket_n`` elements, bucket order).  ``model_state_dict`` always holds the live weights.
 
 The step itself is untouched: saving and loading are copies, `fit` only calls `train_step` and `embed`.
 
@@ -25,6 +27,7 @@ a bare state dict (_test_bridge.py:499-504).
 """
 from __future__ import annotations
 
+import contextlib
 import math
 import os
 import tempfile
@@ -143,9 +146,19 @@ class TrainerCheckpointMixin:
                 "state": [0, 0, 0, 0] if bank is None else [int(v) for v in bank.state.detach().cpu()],
                 "rows": None if bank is None else _cpu(bank.bank), "ids": None if bank is None else _cpu(bank.gid)}
 
+    def checkpoint_ema(self) -> Optional[dict]:
+        """``bridge_trainer_state["ema"]``: None unless the trainer was built with ema_decay > 0"""
+        ema = getattr(self.bucket, "ema", None)
+        if ema is None:
+            return None
+        return {"decay": float(self.ema_decay), "warmup": bool(self.ema_warmup), "shadow": _cpu(ema)}
+
     # ------------------------------------------------------------------ state
     def checkpoint_state(self, epoch: Optional[int] = None, metrics: Optional[dict] = None, scheduler=None) -> dict:
         """the checkpoint container (CPU tensors, dicts, lists and Python scalars: loads with ``weights_only=True``)"""
+        if getattr(self, "_ema_active", False):        # model_state_dict always holds the live weights
+            raise RuntimeError("checkpoint_state inside ema_weights(): the parameters hold the averaged weights; leave "
+                               "the context first")
         b = self.bucket
         words = _cpu(b.state)
         step = float(words[0])
@@ -172,6 +185,8 @@ class TrainerCheckpointMixin:
             bts["classify"] = self.checkpoint_classify()
         if self.checkpoint_bank() is not None:                     # (absent without a bank: the container is unchanged)
             bts["bank"] = self.checkpoint_bank()
+        if self.checkpoint_ema() is not None:                      # (absent without averaged weights: the container is unchanged)
+            bts["ema"] = self.checkpoint_ema()
         return {"epoch": epoch, "model_state_dict": {k: _cpu(v) for k, v in self.state_dict().items()},
                 "optimizer_state_dict": {"state": state, "param_groups": [group]},
                 "scheduler_state_dict": scheduler.state_dict() if scheduler is not None else None,
@@ -220,6 +235,20 @@ class TrainerCheckpointMixin:
             rows, N2 = theirs_bank.get("rows"), 2 * self.head.bridge.bridge_dim
             if rows is not None and (tuple(rows.shape) != (size, N2) or tuple(theirs_bank["ids"].shape) != (size,)):
                 raise ValueError(f"load_checkpoint_state: bank.rows differ: checkpoint {tuple(rows.shape)}, trainer {(size, N2)}")
+        mine_ema, theirs_ema = getattr(self.bucket, "ema", None), bts.get("ema")
+        if (mine_ema is None) != (theirs_ema is None):
+            raise ValueError(f"load_checkpoint_state: ema differs: the checkpoint was written "
+                             f"{'with' if theirs_ema is not None else 'without'} averaged weights, this trainer was built "
+                             f"{'with' if mine_ema is not None else 'without'} ema_decay")
+        if theirs_ema is not None:
+            for field, mine_v in (("decay", float(self.ema_decay)), ("warmup", bool(self.ema_warmup))):
+                if theirs_ema.get(field) != mine_v:
+                    raise ValueError(f"load_checkpoint_state: ema.{field} differs: checkpoint {theirs_ema.get(field)!r}, "
+                                     f"trainer {mine_v!r}")
+            shadow = theirs_ema.get("shadow")
+            if shadow is None or tuple(shadow.shape) != (int(self.bucket.n),) or shadow.dtype != torch.float32:
+                raise ValueError(f"load_checkpoint_state: ema.shadow differs: the trainer's bucket has {int(self.bucket.n)} "
+                                 "fp32 elements")
         # a checkpoint written before the head counts were recorded comes from a trainer whose blocks all had 4 heads
         heads = bts.get("heads", [[n, 4] for n, _ in mine["heads"]])
         if heads != mine["heads"]:
@@ -276,7 +305,10 @@ class TrainerCheckpointMixin:
         hyperparameters and the dropout stream, all copied in place.  Any captured step is dropped; the next
         graph-mode `train_step` captures again with the checkpoint's seeds and epoch word.  The process-global dropout
         counter (``ops._seed_state``) is set from the checkpoint.  A checkpoint of another EEG branch, loss, shape, bucket
-        layout, world size or cross-batch memory (presence, size, warm-up) raises ValueError before anything is touched."""
+        layout, world size, cross-batch memory (presence, size, warm-up) or averaged weights (presence, decay, warm-up)
+        raises ValueError before anything is touched.  The average (``ema.shadow``) is copied into ``bucket.ema`` in place."""
+        if getattr(self, "_ema_active", False):
+            raise RuntimeError("load_checkpoint_state inside ema_weights(): leave the context first")
         self._check_compatible(sd)
         bts = sd["bridge_trainer_state"]
         b = self.bucket
@@ -302,6 +334,8 @@ class TrainerCheckpointMixin:
             self._fmri_aug_step = int(bts["fmri_augment"]["step"])
         if "bank" in bts:
             self._load_bank(bts["bank"])
+        if "ema" in bts:
+            b.ema.copy_(bts["ema"]["shadow"])
         ops.weights_changed()
 
     def _load_bank(self, ck: dict):
@@ -349,16 +383,22 @@ class TrainerCheckpointMixin:
     def load_checkpoint(self, path: str, scheduler=None):
         """-> (epoch, metrics).  A `save_checkpoint` file restores everything (`load_checkpoint_state`); a
         reference-style container without ``bridge_trainer_state`` or a bare state dict restores the model only.
-        ``scheduler``: receives ``scheduler_state_dict`` when the file has one."""
+        ``scheduler``: receives ``scheduler_state_dict`` when the file has one.  A model-only file carries no average:
+        a trainer that keeps one starts it anew from the loaded weights (`sync_ema`)."""
         ck = torch.load(path, map_location="cpu", weights_only=True)
+        averaging = getattr(self.bucket, "ema", None) is not None
         if "model_state_dict" not in ck:                       # a bare state dict (_test_bridge.py:499-504)
             self.load_state_dict(ck)
+            if averaging:
+                self.sync_ema()
             ops.weights_changed()
             return None, None
         if "bridge_trainer_state" in ck:
             self.load_checkpoint_state(ck)
         else:
             self.load_state_dict(ck["model_state_dict"])
+            if averaging:
+                self.sync_ema()
             ops.weights_changed()
         if scheduler is not None and ck.get("scheduler_state_dict") is not None:
             scheduler.load_state_dict(ck["scheduler_state_dict"])
@@ -366,36 +406,44 @@ class TrainerCheckpointMixin:
 
     # ------------------------------------------------------------------ epoch loop
     def _best_copy(self):
-        return self.bucket.p.clone(), [t.clone() for t in self.buffers()]
+        """(live parameters, buffers, averaged parameters or None): the average travels with the weights it belongs to"""
+        ema = getattr(self.bucket, "ema", None)
+        return self.bucket.p.clone(), [t.clone() for t in self.buffers()], None if ema is None else ema.clone()
 
-    def _best_copy_from(self, msd: dict):
+    def _best_copy_from(self, ck: dict):
+        """`_best_copy` from a ``best.pt`` container"""
+        msd = ck["model_state_dict"]
         names = {id(p): n for n, p in self.named_parameters()}
         dev = self.bucket.p.device
         p = torch.cat([msd[names[id(q)]].reshape(-1) for q in self.bucket.params]).to(dev)
-        return p, [msd[n].to(dev) for n, _ in self.named_buffers()]
+        ema = ck.get("bridge_trainer_state", {}).get("ema")
+        return p, [msd[n].to(dev) for n, _ in self.named_buffers()], None if ema is None else ema["shadow"].to(dev)
 
     @torch.no_grad()
     def _restore_best(self, best):
-        p, bufs = best
+        p, bufs, ema = best
         self.bucket.p.copy_(p)
         for t, s in zip(self.buffers(), bufs):
             t.copy_(s)
+        if ema is not None:
+            self.bucket.ema.copy_(ema)
         ops.weights_changed()
 
-    def _validate(self, val, monitor, batch_size):
+    def _validate(self, val, monitor, batch_size, use_ema: bool = False):
         from .bridge_utils import retrieval_metrics
         s0 = ops._seed_state["step"]
-        ze, zf = self.embed(val[0], val[1], batch_size)
-        metrics = retrieval_metrics(ze, zf, groups=val[2] if len(val) > 2 else None)
-        if len(val) > 3 and val[3] is not None:           # class labels: the reference's evaluate_bridge metrics as well
-            metrics["classification"] = self.evaluate_classification(val[0], val[1], val[3], batch_size)
+        with (self.ema_weights() if use_ema else contextlib.nullcontext()):
+            ze, zf = self.embed(val[0], val[1], batch_size)
+            metrics = retrieval_metrics(ze, zf, groups=val[2] if len(val) > 2 else None)
+            if len(val) > 3 and val[3] is not None:       # class labels: the reference's evaluate_bridge metrics as well
+                metrics["classification"] = self.evaluate_classification(val[0], val[1], val[3], batch_size)
         assert ops._seed_state["step"] == s0, "validation drew dropout seeds"
         return metrics, monitor_value(metrics, monitor)
 
     def fit(self, train, epochs: int, *, val=None, warmup_epochs: int = 3, min_lr: float = 1e-6,
             monitor: Union[str, Callable[[dict], float]] = "mean_R@1", mode: str = "max", patience: int = 15,
             min_delta: float = 1e-3, eval_every: int = 1, checkpoint_dir: Optional[str] = None, resume: bool = False,
-            val_batch_size: int = 256):
+            val_batch_size: int = 256, validate_with: Optional[str] = None):
         """The reference's epoch loop (run_training_lite.py:465-520) on the contrastive step -> per-epoch history.
 
         ``train``: an iterable of (eeg, fmri) or (eeg, fmri, groups) batches re-iterated every epoch, or ``epoch ->
@@ -413,6 +461,10 @@ class TrainerCheckpointMixin:
         when ``checkpoint_dir`` is set); the best model is restored in place at the end (the optimizer state is not,
         as in the reference).  ``last.pt`` is written after every epoch; ``resume=True`` continues from it at the
         epoch boundary (the same ``train``, ``val`` and arguments must be given).
+        ``validate_with``: "ema" - validation, early stopping and the best-epoch decision use the averaged weights
+        (`ema_weights()`; the default on a trainer built with ``ema_decay > 0``, ValueError on one without) - or "live"
+        (the default otherwise).  The best state kept, written and restored is the live weights AND their average;
+        ``model_state_dict`` of ``best.pt`` / ``last.pt`` is always the live weights (`ema_state_dict()` exports the average).
         Data parallel: rank 0 validates and broadcasts the metrics, the monitored value and its decisions; every rank
         acts on them.  Pass the same ``val`` on every rank (only rank 0 reads it)."""
         from .crossmodal_v4_enhancements import CosineAnnealingWarmup, EarlyStopping
@@ -424,6 +476,14 @@ class TrainerCheckpointMixin:
             raise ValueError("fit: mode is 'max' or 'min'")
         if resume and checkpoint_dir is None:
             raise ValueError("fit: resume=True needs checkpoint_dir")
+        averaging = getattr(self.bucket, "ema", None) is not None
+        if validate_with is None:
+            validate_with = "ema" if averaging else "live"
+        if validate_with not in ("ema", "live"):
+            raise ValueError(f"fit: validate_with is 'ema' or 'live' (got {validate_with!r})")
+        if validate_with == "ema" and not averaging:
+            raise ValueError("fit: validate_with='ema' needs a trainer built with ema_decay > 0")
+        use_ema = validate_with == "ema"
         if checkpoint_dir is not None and dp.rank(self.group) == 0:
             os.makedirs(checkpoint_dir, exist_ok=True)
         last = os.path.join(checkpoint_dir, "last.pt") if checkpoint_dir else None
@@ -443,7 +503,7 @@ class TrainerCheckpointMixin:
             history, best_score, best_epoch, stopped = list(fs["history"]), fs["best_score"], fs["best_epoch"], fs["stopped"]
             start = ck["epoch"] + 1
             if best_epoch is not None:
-                best = self._best_copy_from(torch.load(best_path, map_location="cpu", weights_only=True)["model_state_dict"])
+                best = self._best_copy_from(torch.load(best_path, map_location="cpu", weights_only=True))
         dev = self.bucket.p.device
         try:
             for epoch in range(start, epochs + 1):
@@ -459,7 +519,7 @@ class TrainerCheckpointMixin:
                 entry = {"epoch": epoch, "lr": lr, "steps": n, "train_loss": total.item() / max(n, 1),
                          "val": None, "monitor": None, "improved": False, "stop": False}
                 if val is not None and (epoch % eval_every == 0 or epoch == epochs):
-                    entry.update(self._decide(val, monitor, mode, val_batch_size, stopper, best_score))
+                    entry.update(self._decide(val, monitor, mode, val_batch_size, stopper, best_score, use_ema))
                     if entry["improved"]:
                         best_score, best_epoch = entry["monitor"], epoch
                         best = self._best_copy()
@@ -478,11 +538,12 @@ class TrainerCheckpointMixin:
             self._restore_best(best)
         return history
 
-    def _decide(self, val, monitor, mode, batch_size, stopper, best_score) -> dict:
-        """rank 0 validates; every rank takes rank 0's metrics, monitored value, improvement and stop"""
+    def _decide(self, val, monitor, mode, batch_size, stopper, best_score, use_ema: bool = False) -> dict:
+        """rank 0 validates (``use_ema``: with the averaged weights); every rank takes rank 0's metrics, monitored value,
+        improvement and stop"""
         metrics = score = None
         if dp.rank(self.group) == 0:
-            metrics, score = self._validate(val, monitor, batch_size)
+            metrics, score = self._validate(val, monitor, batch_size, use_ema)
         if dp.world_size(self.group) > 1:
             import torch.distributed as dist
             ctrl = dp._control_group(self.group)

@@ -25,6 +25,7 @@ this keeps that step structure.
 """
 from __future__ import annotations
 
+import contextlib
 import os
 from typing import Dict, Optional
 
@@ -38,7 +39,7 @@ from .bridge_checkpoint import TrainerCheckpointMixin
 from .bridge_utils import EEGfMRIContrastiveBridge, retrieval_metrics
 from .enhanced_models_v4 import EnhancedERPEncoder
 from .fmri_utils import fMRITabularEncoder, fMRIVolumeEncoder3D
-from .optim import FlatBucket
+from .optim import FlatBucket, check_ema_decay
 
 
 class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
@@ -48,7 +49,8 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
                  eps: float = 1e-8, group=None, device="cuda", mode: str = "graph", eeg_encoder: Optional[nn.Module] = None,
                  num_heads: int = 4, num_layers: int = 2, augment=None, loss: str = "infonce",
                  classify: bool = False, ce_weight: float = 1.0, class_weight=None, num_classes: int = 2,
-                 fmri_encoder: Optional[nn.Module] = None, bank_size: int = 0, bank_warmup: int = 0, fmri_augment=None):
+                 fmri_encoder: Optional[nn.Module] = None, bank_size: int = 0, bank_warmup: int = 0, fmri_augment=None,
+                 ema_decay: float = 0.0, ema_warmup: bool = True):
         """``eeg_encoder``: the EEG branch when it is not the default ``EnhancedERPEncoder(eeg_channels, hidden_dim,
         num_layers, num_heads, dropout)`` - an ``EnhancedPowerEncoder`` (enhanced_models_v4.py:196-285) or a
         ``MultiScaleSTFTPowerEncoder`` (BASELINE config #5: raw EEG -> multi-scale STFT power -> a4); it must end in
@@ -86,8 +88,19 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
         fMRI batch on the device (flip, shift, scale, noise, erase; csrc/volume_augment.hip), drawing
         step index 0, 1, 2, ... from a counter of its own (`fmri_augment_step`) and this process's rank; in graph mode the
         two launches write the captured step's static fMRI buffer.  The entry points that never augment the EEG never
-        augment the volumes either.  None (default): the step issues the launches it always did."""
+        augment the volumes either.  None (default): the step issues the launches it always did.
+        ``ema_decay`` = d in (0, 1): an exponential moving average of every trained parameter (``bucket.ema``, one more
+        flat fp32 buffer), kept by the update kernel itself - the step launches mm_adamw_clip_ema in place of
+        mm_adamw_clip: no new launch, no graph node, no collective (every rank computes the same bits), in all three
+        modes.  After step t the decay is ``min(d, (1 + t) / (10 + t))`` with ``ema_warmup`` (default), d without
+        (DESIGN.md section 5s).  `ema_weights()` evaluates with the average, `fit` validates with it, checkpoints carry it,
+        `ema_state_dict()` exports it.  Only parameters are averaged: BatchNorm running statistics and the other buffers
+        are running averages already, so the averaged weights run with the LIVE buffers.  0 (default): no average; the
+        trainer takes exactly the code path, launches and checkpoint container it has without the keyword."""
         super().__init__()
+        check_ema_decay(ema_decay, "BridgeTrainer")
+        self.ema_decay, self.ema_warmup = float(ema_decay), bool(ema_warmup)
+        self._ema_active = False                      # inside `ema_weights()`: the parameters hold the averaged weights
         if bank_size < 0 or bank_warmup < 0:
             raise ValueError(f"BridgeTrainer: bank_size and bank_warmup must be >= 0 (got {bank_size}, {bank_warmup})")
         if bank_size > 0:
@@ -202,8 +215,8 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
         else:
             layout = [("eeg encoder + heads", "main", list(self.eeg_encoder.parameters()) + head_params)]
         layout.append(("fmri encoder", "fmri", list(self.fmri_encoder.parameters())))
-        self.bucket = FlatBucket([p for _, _, ps in layout for p in ps])
-        self.groups = []                              # (name, ready point, lo, hi) over the flat bucket, in bucket order
+        self.bucket = FlatBucket([p for _, _, ps in layout for p in ps], ema=self.ema_decay > 0)
+        self.groups = []                            # (name, ready point, lo, hi) over the flat bucket, in bucket order
         off = 0
         for name, ready, ps in layout:
             k = sum(p.numel() for p in ps if p.requires_grad)
@@ -282,6 +295,50 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
         self.lr = lr
         self.bucket.state[2] = lr
 
+    # ------------------------------------------------------------------ averaged weights
+    def _need_ema(self, who: str):
+        if self.bucket.ema is None:
+            raise RuntimeError(f"{who}: this trainer was built without ema_decay, there are no averaged weights")
+
+    def _no_step_on_average(self, who: str):
+        if self._ema_active:
+            raise RuntimeError(f"{who} inside ema_weights(): the parameters hold the averaged weights; leave the context first")
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Inside, every trained parameter holds its exponential moving average: `evaluate`, `embed`,
+        `evaluate_retrieval`, `predict`, `evaluate_classification`, `explain`, `perturb`, `temporal_attention` and
+        `forward` see the averaged weights.  The contents of ``bucket.p`` and ``bucket.ema`` are exchanged in place (two
+        bucket-sized copies each way, exact), so parameter views and a captured graph's pointers stay valid, and the
+        prepared weight images are invalidated on both edges; on exit the live weights have their old bits and training
+        goes on as if nothing had happened.  BatchNorm running statistics and the other buffers are not averaged (they
+        are running averages already): the averaged weights run with the live buffers.  `train_step` /
+        `train_step_packed` inside raise RuntimeError before any launch.  Not re-entrant."""
+        self._need_ema("ema_weights")
+        if self._ema_active:
+            raise RuntimeError("ema_weights: already inside ema_weights()")
+        with self.bucket.swapped():
+            self._ema_active = True
+            try:
+                yield self
+            finally:
+                self._ema_active = False
+
+    @torch.no_grad()
+    def sync_ema(self):
+        """set the average to the live weights (after weights were loaded by other means than a trainer checkpoint)"""
+        self._need_ema("sync_ema")
+        self._no_step_on_average("sync_ema")
+        self.bucket.ema.copy_(self.bucket.p)
+
+    def ema_state_dict(self) -> dict:
+        """the model ``state_dict()`` with the averaged weights, as CPU copies: the trained parameters are the average,
+        the frozen parameters and the buffers (BatchNorm statistics: live, not averaged) are what ``state_dict()`` holds.
+        For export into the reference's modules."""
+        self._need_ema("ema_state_dict")
+        with self.ema_weights():
+            return {k: v.detach().to("cpu", copy=True) for k, v in self.state_dict().items()}
+
     def forward(self, eeg: torch.Tensor, fmri: torch.Tensor, groups: Optional[torch.Tensor] = None):
         """the two encoders are independent until the heads: they run on two HIP
         streams (autograd replays each backward on its forward stream), so the
@@ -328,6 +385,7 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
         ``labels``: (B,) integer class labels (``ops.class_labels``), required by - and only taken by - a trainer built
         with ``classify=True``: the step then also trains the classification branch and returns ``contrastive_loss``,
         ``ce_loss``, ``cls_correct`` and ``loss`` = contrastive_loss + ce_weight * ce_loss."""
+        self._no_step_on_average("train_step")
         self._check_fmri(fmri.shape, True, "train_step")   # before the first launch of the step (or of its capture)
         if self._fmri_kind == "tabular" and fmri.is_cuda:
             self.fmri_encoder.tickets(fmri.device)         # the forward launch's words exist before any capture
@@ -637,8 +695,13 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
     def _seg_adamw(self):
         b = self.bucket
         _hip.call("mm_sumsq", b.g, b.state, b.n)
-        _hip.call("mm_adamw_clip", b.p, b.g, b.m, b.v, b.state, b.n, self.betas[0], self.betas[1],
-                  self.eps, self.weight_decay, self.grad_clip, 1.0 / self.world, 1, ops.EP())
+        if b.ema is None:
+            _hip.call("mm_adamw_clip", b.p, b.g, b.m, b.v, b.state, b.n, self.betas[0], self.betas[1],
+                      self.eps, self.weight_decay, self.grad_clip, 1.0 / self.world, 1, ops.EP())
+        else:                                         # the same update + the weight average, in the same launch
+            _hip.call("mm_adamw_clip_ema", b.p, b.g, b.m, b.v, b.state, b.n, self.betas[0], self.betas[1],
+                      self.eps, self.weight_decay, self.grad_clip, 1.0 / self.world, 1, ops.EP(),
+                      b.ema, self.ema_decay, int(self.ema_warmup))
         ops.weights_changed()
         if self._arena_need is None:
             self._arena_need = (ops.arena.high * 5 // 4 + 4095) // 4096 * 4096
@@ -711,6 +774,8 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
         b = self.bucket
         snap = [t.clone() for t in (b.p, b.m, b.v, b.state)]
         bufs = [t for t in self.buffers() if t is not None]
+        if b.ema is not None:                         # the warm-up steps average: the shadow is part of the training state
+            bufs.append(b.ema)
         if self._bank is not None:                    # the warm-up steps push: the bank is part of the training state
             bufs += self._bank.tensors()
         snap_bufs = [t.clone() for t in bufs]
@@ -1004,6 +1069,7 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
         """one graph-replayed step on a batch that is already in the packed layout of `pack_host_batch` and on the device
         (a staging buffer an H2D copy filled): ONE device-to-device copy into the static inputs, then the replay"""
         self._no_packed_augment("train_step_packed")
+        self._no_step_on_average("train_step_packed")
         if self._cap is None:
             raise RuntimeError("train_step_packed: run one train_step(eeg, fmri) first (it captures the step and fixes the shapes)")
         c = self._cap

@@ -505,6 +505,56 @@ def bank_case(B=32, N=128, step_iters=30, rounds=5):
           f"({t1 - t0:+.1f} us, {100 * (t1 / t0 - 1):+.2f} %)")
 
 
+def ema_case(step_iters=30, rounds=5):
+    """averaged weights in the update kernel, at the default C2 trainer's bucket size, graph-replayed launches in the same
+    run, interleaved rounds: mm_adamw_clip, mm_adamw_clip_ema (the same update + the average: 10 streams over the bucket
+    against 8) and mm_adamw_clip followed by a separate torch ``lerp_`` of the same buffers (the two-launch form); then the
+    C2 graph step (B = 32) without and with ema_decay"""
+    from multimodal_eeg_fmri_amd.bridge_trainer import BridgeTrainer, synthetic_pairs
+    trs = []
+    for d in (0.0, 0.999):
+        ops.set_seed_epoch(None)
+        torch.manual_seed(0)
+        trs.append(BridgeTrainer(eeg_channels=64, dropout=0.3, ema_decay=d).train())
+    n = trs[0].bucket.n
+    p, g, m, ema = (torch.randn(n, device="cuda") * s for s in (1.0, 0.1, 0.01, 1.0))
+    v = torch.rand(n, device="cuda") * 1e-3
+    state = torch.zeros(8 + 1024, device="cuda")
+    state[2] = 1e-4
+    _hip.call("mm_sumsq", g, state, n)
+    args = (p, g, m, v, state, n, 0.9, 0.999, 1e-8, 1e-4, 1.0, 1.0, 0, None)
+
+    def plain():
+        _hip.call("mm_adamw_clip", *args)
+
+    def fused():
+        _hip.call("mm_adamw_clip_ema", *args, ema, 0.999, 1)
+
+    def two():
+        _hip.call("mm_adamw_clip", *args)
+        ema.lerp_(p, 1e-3)
+    cases = [("mm_adamw_clip", plain), ("mm_adamw_clip_ema", fused), ("mm_adamw_clip + torch lerp_", two)]
+    times = {name: [] for name, _ in cases}
+    for _ in range(rounds):
+        for name, fn in cases:
+            times[name].append(graph_time(fn))
+    for name, _ in cases:
+        print(f"update n={n} ({4 * n / 1e6:.2f} MB per stream): {name:28s} {_spread(times[name])}")
+    t0, t1, t2 = (statistics.median(times[name]) for name, _ in cases)
+    print(f"fused / plain {t1 / t0:.3f}x (traffic: 10 / 8 streams = 1.25x)   fused / two-launch {t1 / t2:.3f}x")
+    eeg, fmri = synthetic_pairs(32, 64, 1024, (32, 32, 32))
+    for tr in trs:
+        for _ in range(3):
+            tr.train_step(eeg, fmri)
+    steps = ([], [])
+    for _ in range(rounds):
+        for i, tr in enumerate(trs):
+            steps[i].append(timeit(lambda: tr.train_step(eeg, fmri), iters=step_iters, rounds=1))
+    s0, s1 = statistics.median(steps[0]), statistics.median(steps[1])
+    print(f"C2 graph step B=32: no average {_spread(steps[0])}   ema_decay=0.999 {_spread(steps[1])}   "
+          f"({s1 - s0:+.1f} us, {100 * (s1 / s0 - 1):+.2f} %)")
+
+
 def _spread(xs):
     return f"{statistics.median(xs):7.1f} us  [{min(xs):.1f} .. {max(xs):.1f}]"
 
@@ -1102,6 +1152,9 @@ def main():
         return
     if flt == "bank":
         bank_case()
+        return
+    if flt == "ema":
+        ema_case()
         return
     if flt == "tabfmri":
         tabfmri_case()
