@@ -1,7 +1,7 @@
 """GPU: the attention read-out kernels (csrc/attention_readout.hip: mm_attn_weights, mm_attn_received,
 mm_attn_received_ws_floats) against an fp64 softmax on the kernels' bf16 operands, as `_ref` of
-test_attention_head_dims_gpu.py.  Inputs are randn qkv (scores O(1)); lse comes from the matching mm_attn_fwd (head dim 32)
-or mm_attn_fwd_hd call.
+test_attention_head_dims_gpu.py.  Inputs are randn qkv, scores of order 1 nat (scores of tens of nats and near one-hot rows:
+test_attention_sharp_scores_gpu.py); lse comes from the matching mm_attn_fwd (head dim 32) or mm_attn_fwd_hd call.
 
 Tolerances.  The project holds lse to 1e-3 (test_kernels_gpu / test_attention_head_dims_gpu); P = exp(s - lse) inherits
 that as a relative error, doubled for the score's own fp32 rounding and the hardware exp: weights rtol 2e-3, atol 1e-6,

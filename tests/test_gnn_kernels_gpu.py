@@ -21,6 +21,10 @@ about twice the worst case measured on the MI355X over the 20 runs:
     out 1.6e-7 (bound 3.5e-7)   alpha 1.8e-7 (3.5e-7)   dxl 2.7e-7 (5.5e-7)   dxr 3.3e-7 (7e-7)
     datt 5.4e-7 (1.1e-6: the sum over all B N deg edges of a head, 12 288 terms in case 4)   dbias 1.8e-7 (4e-7)
 
+Those scores are a few nats.  test_gatv2_subtracts_the_maximum_at_large_scores runs cases 2 and 4 with `att` scaled until the
+edge scores span +-60 nats, each quantity bounded by 16 x the error of the same formula in fp32 torch on the CPU (measured:
+at most 0.08 of that bound).
+
 Exact: an (sample, node, head) whose incoming edges are all dropped leaves the bias alone; two backward runs give the
 same bits; a second backward onto the same d att / d bias buffers doubles them (they are accumulated into)."""
 import functools
@@ -97,27 +101,27 @@ def _case(case):
     return t
 
 
-def _oracle(t, n, h, c, keep, gelu):
-    """fp64 forward + autograd gradients; keep (B, H, E')"""
+def _oracle(t, n, h, c, keep, gelu, dtype=D64):
+    """fp64 forward + autograd gradients; keep (B, H, E').  dtype = torch.float32: the same formula in plain fp32"""
     src, dst = t["src"], t["dst"]
-    xlr = t["xlr"].double()
+    xlr = t["xlr"].to(dtype)
     xl = xlr[..., :h * c].reshape(B, n, h, c).clone().requires_grad_(True)
     xr = xlr[..., h * c:].reshape(B, n, h, c).clone().requires_grad_(True)
-    att = t["att"].double().clone().requires_grad_(True)
-    bias = t["bias"].double().clone().requires_grad_(True)
+    att = t["att"].to(dtype).clone().requires_grad_(True)
+    bias = t["bias"].to(dtype).clone().requires_grad_(True)
     score = (F.leaky_relu(xl[:, src] + xr[:, dst], SLOPE) * att).sum(-1)           # (B, E', H)
     alpha = torch.zeros_like(score)
     for i in range(n):                                                             # softmax over the edges into i
         sel = (dst == i).nonzero().flatten()
         alpha = alpha.index_copy(1, sel, torch.softmax(score[:, sel], dim=1))
-    a = alpha * keep.double().permute(0, 2, 1)
-    out = torch.zeros(B, n, h, c, dtype=D64).index_add(1, dst, a.unsqueeze(-1) * xl[:, src]) + bias.view(h, c)
+    a = alpha * keep.to(dtype).permute(0, 2, 1)
+    out = torch.zeros(B, n, h, c, dtype=dtype).index_add(1, dst, a.unsqueeze(-1) * xl[:, src]) + bias.view(h, c)
     out = out.reshape(B, n, h * c)
     pre = out
     if gelu:
         out = 0.5 * out * (1.0 + torch.erf(out / math.sqrt(2.0)))
-    (out * t["dout"].double()).sum().backward()
-    return dict(out=out.detach(), pre=pre.detach(), alpha=alpha.detach(),
+    (out * t["dout"].to(dtype)).sum().backward()
+    return dict(out=out.detach(), pre=pre.detach(), alpha=alpha.detach(), score=score.detach(),
                 dxl=xl.grad.reshape(B, n, h * c), dxr=xr.grad.reshape(B, n, h * c), datt=att.grad, dbias=bias.grad)
 
 
@@ -198,6 +202,32 @@ def test_gatv2_fwd_bwd_match_fp64(case, p, gelu):
         if case == 1:                                            # degree 1, edge dropped: nothing flows back either
             for k in ("dxl", "dxr"):
                 assert torch.count_nonzero(bwd[k].cpu().view(B, n, h, c)[alone]) == 0
+
+
+@pytest.mark.parametrize("case,p,gelu", [(2, 0.25, True), (4, 0.0, False)])
+def test_gatv2_subtracts_the_maximum_at_large_scores(case, p, gelu):
+    """`att` scaled until the edge scores span +-60 nats (every case above: a few nats, where exp needs no maximum
+    subtracted).  The absolute bounds above assume scores of order 1; here each quantity is held to 16 x e32, e32 = the
+    rel-L2 error of the same formula in plain fp32 torch on the CPU on the same inputs (test_norm_passes_gpu.py)."""
+    n, h, c = SHAPES[case]
+    t = dict(_case(case))
+    E = len(t["src"])
+    keep = keep_scale(SEED, B * h * E, p).view(B, h, E)
+    t["att"] = t["att"] * (60.0 / _oracle(t, n, h, c, keep, gelu)["score"].abs().max().item())
+    want = _oracle(t, n, h, c, keep, gelu)
+    assert 59.0 < want["score"].abs().max().item() < 61.0
+    assert want["score"].min().item() < -30.0 and want["score"].max().item() > 30.0
+    cpu32 = _oracle(t, n, h, c, keep, gelu, torch.float32)
+    _, fwd, (bwd,), _ = _run_kernels(t, n, h, c, p, gelu)
+    got = {"out": fwd["out"], "alpha": fwd["alpha"].permute(0, 2, 1), **{k: bwd[k] for k in ("dxl", "dxr", "datt", "dbias")}}
+    bad = {}
+    for k, v in got.items():
+        err, bound = _rel(v.reshape(want[k].shape), want[k]), 16 * _rel(cpu32[k], want[k])
+        print(f"ERR gatv2 large scores case {case} p {p} gelu {int(gelu)} {k} {err:.3e} (bound {bound:.3e})")
+        assert torch.isfinite(v).all(), k
+        if not err <= bound:
+            bad[k] = (err, bound)
+    assert not bad, bad
 
 
 @pytest.mark.parametrize("case,p,gelu", [(2, 0.25, True), (4, 0.0, False), (5, 0.25, True)])

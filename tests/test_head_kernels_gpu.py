@@ -528,6 +528,51 @@ def test_attn_1xk_matches_fp64(K, p):
     err.done()
 
 
+def test_attn_1xk_and_1x2_subtract_the_maximum_at_large_scores():
+    """projections x 8: scores q k / sqrt(dh) of std 64 nats (every case above: order 1, where exp needs no maximum subtracted).
+    The absolute bounds above assume scores of order 1; here each quantity is held to 16 x e32, e32 = the rel-L2 error of
+    the same formula in plain fp32 torch on the CPU on the same inputs (test_norm_passes_gpu.py)."""
+    hip = _hip()
+    B, E, nhead, p = 300, 128, 8, 0.25
+    dh = E // nhead
+    g = _g(4242)
+    ps4 = [8.0 * torch.randn(B, 3 * E, generator=g) for _ in range(4)]
+    dctx = torch.randn(B, E, generator=g)
+    rows = []
+
+    def refs(ps, keep):
+        res = []
+        for dt in (D64, torch.float32):
+            leaves = [t.clone().to(dt).requires_grad_(True) for t in ps]
+            ctx, attw = _mha_1xk_ref(leaves, E, nhead, keep.to(dt))
+            (ctx * dctx.to(dt)).sum().backward()
+            res.append([ctx.detach(), attw.detach()] + [t.grad for t in leaves])
+        return res
+
+    for K, ps, seed in ((4, ps4, 81), (2, ps4[:2], 515)):
+        keep = keep_scale(seed, B * nhead * K, p).view(B, nhead, K)
+        want, cpu32 = refs(ps, keep)
+        q = ps[0][:, :E].view(B, nhead, 1, dh).double()
+        k = torch.stack([t[:, E:2 * E].view(B, nhead, dh) for t in ps], dim=2).double()
+        assert ((q * k).sum(-1) / math.sqrt(dh)).abs().max().item() > 100.0
+        ctx = torch.full((B, E), float("nan"), device="cuda")
+        attw = torch.full((B, K), float("nan"), device="cuda")
+        dps = [torch.full((B, 3 * E), float("nan"), device="cuda") for _ in range(K)]
+        if K == 4:
+            pc = [_cu(t) for t in ps]
+            hip.call("mm_attn_1xk", *pc, K, None, ctx, attw, None, None, None, None, B, E, nhead, p, seed, None, 0)
+            hip.call("mm_attn_1xk", *pc, K, _cu(dctx), None, None, *dps, B, E, nhead, p, seed, None, 1)
+        else:
+            hip.call("mm_attn_1x2_train", _cu(ps[0]), _cu(ps[1]), None, ctx, attw, None, None, B, E, nhead, p, seed, None, 0)
+            hip.call("mm_attn_1x2_train", _cu(ps[0]), _cu(ps[1]), _cu(dctx), None, None, *dps, B, E, nhead, p, seed, None, 1)
+        names = [f"K{K} ctx", f"K{K} attw"] + [f"K{K} dp{j}" for j in range(K)]
+        for name, a, w, c32 in zip(names, [ctx, attw] + dps, want, cpu32):
+            rows.append((name, _rel(a, w), 16 * _rel(c32, w), bool(torch.isfinite(a).all())))
+            print(f"ERR attn_1xk/1x2 large scores {name} {rows[-1][1]:.3e} (bound {rows[-1][2]:.3e})")
+    bad = [r for r in rows if not (r[3] and r[1] <= r[2])]
+    assert not bad, bad
+
+
 # ------------------------------------------------------------------------------------------------------------- losses
 def _targets(B, C, g):
     return torch.randint(0, C, (B,), generator=g, dtype=torch.int64)
