@@ -935,8 +935,21 @@ int mm_meanpool_bf16(const void* x, float* out, int R, int S, int N, hipStream_t
  * wherever it already equals p_new[i].  d comes from the step count on the device (the launch can live in a hipGraph):
  * with t = state[0] + 1, the count after this step, d = ema_warmup ? min(ema_decay, (1 + t) / (10 + t)) : ema_decay.
  * ema_decay must lie in [0, 1); a NULL ema or a decay outside the range is an argument error, nothing is launched.
- * No float atomics: ranks that hold the same parameters keep bit-identical averages without a collective. */
+ * No float atomics: ranks that hold the same parameters keep bit-identical averages without a collective.
+ *
+ * mm_adamw_clip_groups / mm_adamw_clip_groups_ema: the same step with parameter groups.  The bucket is cut into n_seg
+ * (1 .. MM_OPT_MAX_SEGMENTS) contiguous segments by a table in DEVICE memory, read at launch (so a launch captured in a
+ * hipGraph serves any later change of the table's values): seg_end (int64, strictly increasing, seg_end[n_seg-1] == n;
+ * segment s = [seg_end[s-1], seg_end[s])), seg_lr_mult and seg_wd (fp32, n_seg values each; what lies behind them in
+ * the arrays is never read).  The caller builds and validates the contents; an element past the last end takes the
+ * last segment, and no element or table content forms an address outside the table.  An element of segment s is
+ * updated with lr_s = fl32(state[2] * seg_lr_mult[s]) and weight decay seg_wd[s]: its p, m, v, g (and ema) bits are
+ * those mm_adamw_clip (mm_adamw_clip_ema) writes on the whole bucket when called with state[2] = lr_s and
+ * weight_decay = seg_wd[s]; state[0..5) and state[5] get the plain entry points' bits.  The step count, the norm (over
+ * the WHOLE bucket: clip_grad_norm_ over all groups), the clip coefficient, zero_grad and the average are unchanged.
+ * A multiplier of 0 leaves p bit-unchanged while m and v move (torch's lr = 0 group).  Two launches, as the plain step. */
 #define MM_OPT_STATE_FLOATS 1032
+#define MM_OPT_MAX_SEGMENTS 1024
 int mm_sumsq(const float* g, float* state, int64_t n, hipStream_t stream);
 int mm_adamw_clip(float* p, float* g, float* m, float* v, float* state, int64_t n, float beta1,
                   float beta2, float eps, float weight_decay, float max_norm, float grad_scale,
@@ -945,6 +958,15 @@ int mm_adamw_clip_ema(float* p, float* g, float* m, float* v, float* state, int6
                       float beta2, float eps, float weight_decay, float max_norm, float grad_scale,
                       int zero_grad, uint32_t* seed_epoch, float* ema, float ema_decay, int ema_warmup,
                       hipStream_t stream);
+int mm_adamw_clip_groups(float* p, float* g, float* m, float* v, float* state, int64_t n, float beta1,
+                         float beta2, float eps, float max_norm, float grad_scale, int zero_grad,
+                         uint32_t* seed_epoch, const int64_t* seg_end, const float* seg_lr_mult,
+                         const float* seg_wd, int n_seg, hipStream_t stream);
+int mm_adamw_clip_groups_ema(float* p, float* g, float* m, float* v, float* state, int64_t n, float beta1,
+                             float beta2, float eps, float max_norm, float grad_scale, int zero_grad,
+                             uint32_t* seed_epoch, const int64_t* seg_end, const float* seg_lr_mult,
+                             const float* seg_wd, int n_seg, float* ema, float ema_decay, int ema_warmup,
+                             hipStream_t stream);
 
 /* ---- attribution (EEG_CODE/eeg_xai_analysis.py:88-236: GradientSaliency, IntegratedGradients) ---------------
  * The reference walks its n_steps interpolation points one forward/backward at a time with a numpy round trip

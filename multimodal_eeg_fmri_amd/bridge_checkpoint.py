@@ -17,7 +17,10 @@ The file is the container of the reference's loops and of `FlexibleTrainer.save_
   a cross-batch memory (``bank_size > 0``) - ``bank`` = ``{size, warmup, grouped, state, rows, ids}``: the ring's words,
   rows and group ids (``rows`` / ``ids`` None before the first training step), and - only for a trainer that keeps
   averaged weights (``ema_decay > 0``) - ``ema`` = ``{decay, warmup, shadow}``: ``shadow`` is the flat fp32 average of
-  the bucket (``bucket_n`` elements, bucket order).  ``model_state_dict`` always holds the live weights.
+  the bucket (``bucket_n`` elements, bucket order), and - only for a trainer with parameter groups (a learning-rate
+  multiplier other than 1, ``no_decay=True`` or a frozen encoder) - ``param_groups`` = ``{components, multipliers,
+  no_decay, freeze, seg_end, seg_wd}``: the multipliers by component and the update kernel's segment table.
+  ``model_state_dict`` always holds the live weights.
 
 The step itself is untouched: saving and loading are copies, `fit` only calls `train_step` and `embed`.
 
@@ -153,6 +156,20 @@ class TrainerCheckpointMixin:
             return None
         return {"decay": float(self.ema_decay), "warmup": bool(self.ema_warmup), "shadow": _cpu(ema)}
 
+    def checkpoint_param_groups(self) -> Optional[dict]:
+        """``bridge_trainer_state["param_groups"]``: None while every learning-rate multiplier is 1, ``no_decay`` is off and
+        nothing is frozen"""
+        scales = getattr(self, "_lr_scale", None)
+        if scales is None:
+            return None
+        frozen, no_decay = list(getattr(self, "_frozen", ())), bool(getattr(self, "no_decay", False))
+        if all(v == 1.0 for v in scales.values()) and not no_decay and not frozen:
+            return None
+        t = self._table
+        return {"components": list(self.COMPONENTS), "multipliers": [float(scales[c]) for c in self.COMPONENTS],
+                "no_decay": no_decay, "freeze": frozen, "seg_end": [int(e) for e in t.ends],
+                "seg_wd": [float(w) for w in t.wds]}
+
     # ------------------------------------------------------------------ state
     def checkpoint_state(self, epoch: Optional[int] = None, metrics: Optional[dict] = None, scheduler=None) -> dict:
         """the checkpoint container (CPU tensors, dicts, lists and Python scalars: loads with ``weights_only=True``)"""
@@ -187,6 +204,8 @@ class TrainerCheckpointMixin:
             bts["bank"] = self.checkpoint_bank()
         if self.checkpoint_ema() is not None:                      # (absent without averaged weights: the container is unchanged)
             bts["ema"] = self.checkpoint_ema()
+        if self.checkpoint_param_groups() is not None:             # (absent at the defaults: the container is unchanged)
+            bts["param_groups"] = self.checkpoint_param_groups()
         return {"epoch": epoch, "model_state_dict": {k: _cpu(v) for k, v in self.state_dict().items()},
                 "optimizer_state_dict": {"state": state, "param_groups": [group]},
                 "scheduler_state_dict": scheduler.state_dict() if scheduler is not None else None,
@@ -249,6 +268,19 @@ class TrainerCheckpointMixin:
             if shadow is None or tuple(shadow.shape) != (int(self.bucket.n),) or shadow.dtype != torch.float32:
                 raise ValueError(f"load_checkpoint_state: ema.shadow differs: the trainer's bucket has {int(self.bucket.n)} "
                                  "fp32 elements")
+        # parameter groups: before the bucket layout, which a frozen encoder changes too
+        theirs_pg = bts.get("param_groups") or {}
+        for field, mine_v in (("no_decay", bool(getattr(self, "no_decay", False))), ("freeze", list(getattr(self, "_frozen", ())))):
+            theirs_v = theirs_pg.get(field, type(mine_v)())
+            if theirs_v != mine_v:
+                raise ValueError(f"load_checkpoint_state: {field} differs: checkpoint {theirs_v!r}, trainer {mine_v!r}")
+        if theirs_pg:
+            if list(theirs_pg.get("components", ())) != list(self.COMPONENTS) or len(theirs_pg.get("multipliers", ())) != len(self.COMPONENTS):
+                raise ValueError(f"load_checkpoint_state: param_groups.components differ: checkpoint "
+                                 f"{theirs_pg.get('components')!r}, trainer {list(self.COMPONENTS)!r}")
+            if list(theirs_pg.get("seg_end", ())) != list(self._table.ends) or len(theirs_pg.get("seg_wd", ())) != self._table.n_seg:
+                raise ValueError(f"load_checkpoint_state: param_groups.seg_end differs: checkpoint {theirs_pg.get('seg_end')!r}, "
+                                 f"trainer {self._table.ends!r}")
         # a checkpoint written before the head counts were recorded comes from a trainer whose blocks all had 4 heads
         heads = bts.get("heads", [[n, 4] for n, _ in mine["heads"]])
         if heads != mine["heads"]:
@@ -305,8 +337,8 @@ class TrainerCheckpointMixin:
         hyperparameters and the dropout stream, all copied in place.  Any captured step is dropped; the next
         graph-mode `train_step` captures again with the checkpoint's seeds and epoch word.  The process-global dropout
         counter (``ops._seed_state``) is set from the checkpoint.  A checkpoint of another EEG branch, loss, shape, bucket
-        layout, world size, cross-batch memory (presence, size, warm-up) or averaged weights (presence, decay, warm-up)
-        raises ValueError before anything is touched.  The average (``ema.shadow``) is copied into ``bucket.ema`` in place."""
+        layout, world size, cross-batch memory (presence, size, warm-up), averaged weights (presence, decay, warm-up),
+        ``no_decay`` or ``freeze`` raises ValueError before anything is touched; the learning-rate multipliers are restored.  The average (``ema.shadow``) is copied into ``bucket.ema`` in place."""
         if getattr(self, "_ema_active", False):
             raise RuntimeError("load_checkpoint_state inside ema_weights(): leave the context first")
         self._check_compatible(sd)
@@ -324,6 +356,13 @@ class TrainerCheckpointMixin:
         self.betas, self.eps = (h["betas"][0], h["betas"][1]), h["eps"]
         self.weight_decay, self.grad_clip = h["weight_decay"], h["grad_clip"]
         self.lr = float(bts["lr"])
+        if getattr(self, "_table", None) is not None:              # the multipliers and decays, restored like the lr word
+            pg = bts.get("param_groups")
+            mult = dict(zip(pg["components"], pg["multipliers"])) if pg else {c: 1.0 for c in self.COMPONENTS}
+            self._lr_scale.update({c: float(v) for c, v in mult.items()})
+            self._table.write(mults=[self._lr_scale[c] for c in self._seg_component],
+                              wds=pg["seg_wd"] if pg else self._table_lists()[2])
+            self._grouped = self._grouped or not self._table.uniform   # (the capture was dropped above)
         d = bts["dropout"]
         ops._seed_state["base"] = int(d["base"])
         ops._seed_state["step"] = int(d["step"])

@@ -32,7 +32,7 @@ from typing import Dict, Optional
 import torch
 import torch.nn as nn
 
-from . import _hip, dp, ops
+from . import _hip, dp, ops, optim
 from .autograd import (GradBag, bridge_cls_bwd, contrastive_embed_bwd, contrastive_embed_bwd_da, deferred, erp_encoder_bwd,
                        ffn_rows_bwd_fused, fmri_tab_bwd, power_encoder_bwd, volume_encoder_bwd)
 from .bridge_checkpoint import TrainerCheckpointMixin
@@ -50,7 +50,7 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
                  num_heads: int = 4, num_layers: int = 2, augment=None, loss: str = "infonce",
                  classify: bool = False, ce_weight: float = 1.0, class_weight=None, num_classes: int = 2,
                  fmri_encoder: Optional[nn.Module] = None, bank_size: int = 0, bank_warmup: int = 0, fmri_augment=None,
-                 ema_decay: float = 0.0, ema_warmup: bool = True):
+                 ema_decay: float = 0.0, ema_warmup: bool = True, lr_scale=None, no_decay: bool = False, freeze=()):
         """``eeg_encoder``: the EEG branch when it is not the default ``EnhancedERPEncoder(eeg_channels, hidden_dim,
         num_layers, num_heads, dropout)`` - an ``EnhancedPowerEncoder`` (enhanced_models_v4.py:196-285) or a
         ``MultiScaleSTFTPowerEncoder`` (BASELINE config #5: raw EEG -> multi-scale STFT power -> a4); it must end in
@@ -96,8 +96,29 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
         (DESIGN.md section 5s).  `ema_weights()` evaluates with the average, `fit` validates with it, checkpoints carry it,
         `ema_state_dict()` exports it.  Only parameters are averaged: BatchNorm running statistics and the other buffers
         are running averages already, so the averaged weights run with the LIVE buffers.  0 (default): no average; the
-        trainer takes exactly the code path, launches and checkpoint container it has without the keyword."""
+        trainer takes exactly the code path, launches and checkpoint container it has without the keyword.
+        Parameter groups - the reference's transfer recipe, pretrained encoders frozen and then
+        fine-tuned below the heads' rate.  The components are ``"eeg_encoder"``, ``"fmri_encoder"`` and ``"head"`` (the
+        bridge's trained parameters, ``logit_scale`` and ``logit_bias``); an unknown name raises ValueError.
+        ``lr_scale`` = ``{"eeg_encoder": 0.1, ...}``: a multiplier of the learning rate per component (finite, >= 0;
+        missing components: 1).  `set_lr` / `fit`'s schedule move the base rate only, the ratios stay; `set_lr_scale`
+        rewrites a multiplier between steps (device memory the captured step reads: no new capture), `lr_scales` reads
+        them.  0 holds a component still while its Adam moments and BatchNorm statistics keep moving (torch's
+        ``lr=0`` group) - the held-then-released stage.
+        ``no_decay=True``: every trained parameter with ``ndim <= 1`` - biases, LayerNorm / BatchNorm gains and biases,
+        ``logit_scale``, ``logit_bias``, fusion logits and temperatures - gets weight decay 0.
+        Both go into the update kernel as a segment table over the flat bucket (mm_adamw_clip_groups[_ema] in place of
+        mm_adamw_clip[_ema]: no new launch; the clipped norm stays the whole bucket's); the table is the same on every
+        rank, so both work at any world size.  A table of multiplier 1 and one decay launches the plain kernel.
+        ``freeze`` = ``("fmri_encoder",)`` and / or ``"eeg_encoder"``: the reference's ``requires_grad_(False)`` +
+        ``eval()`` of a pretrained encoder.  The component's parameters leave the bucket, its forward runs in eval form
+        inside the step (frozen BatchNorm, no dropout seed drawn, nothing updated), and its backward is not issued in
+        any mode.  Fixed at construction; ``"head"`` cannot be frozen (ValueError); one process only
+        (NotImplementedError at world size > 1)."""
         super().__init__()
+        self._frozen = self._check_freeze(freeze, group)
+        self._lr_scale = self._check_lr_scale(lr_scale)
+        self.no_decay = bool(no_decay)
         check_ema_decay(ema_decay, "BridgeTrainer")
         self.ema_decay, self.ema_warmup = float(ema_decay), bool(ema_warmup)
         self._ema_active = False                      # inside `ema_weights()`: the parameters hold the averaged weights
@@ -204,7 +225,12 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
         head_params = [p for name, p in br.named_parameters() if p.requires_grad and is_proj(name)] + cls_params + [self.head.logit_scale]
         if loss == "sigmoid":
             head_params.append(self.head.logit_bias)
-        if self._eeg_kind == "erp":
+        # a frozen encoder (the reference's requires_grad_(False) + eval()): out of the bucket, eval form for good
+        for name in self._frozen:
+            getattr(self, name).requires_grad_(False).eval()
+        if "eeg_encoder" in self._frozen:             # no EEG backward, no hand-over: the heads' gradients are final on the chain
+            layout = [("heads", "main", head_params)]
+        elif self._eeg_kind == "erp":
             cl = self.eeg_encoder.conv_layers
             conv1 = list(cl[0].parameters()) + list(cl[1].parameters())
             conv23 = [p for i in (4, 5, 9, 10) for p in cl[i].parameters()]
@@ -224,6 +250,17 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
             off += k
         assert off == self.bucket.n
         self.fmri_lo = self.groups[-1][2]
+        # parameter groups: which component every bucket parameter belongs to, and the segment table of the update kernel
+        # (device arrays, allocated here - before any capture - and rewritten in place by `set_lr_scale`)
+        comp = {id(p): "head" for p in head_params}
+        comp.update({id(p): "eeg_encoder" for p in self.eeg_encoder.parameters()})
+        comp.update({id(p): "fmri_encoder" for p in self.fmri_encoder.parameters()})
+        self._param_component = [comp[id(p)] for p in self.bucket.params]
+        self._seg_component = self._segment_components()
+        self._table = optim.SegmentTable(*self._table_lists(), device=self.bucket.p.device)
+        # which update kernel the step launches: the plain one while the table is uniform (multiplier 1, one decay).  Fixed
+        # here for the captured step; `set_lr_scale` away from a uniform table switches it once (and drops the capture)
+        self._grouped = not self._table.uniform
         self._works = []                              # asynchronous all-reduces of the running step (waited for by the optimizer)
         self.capture_mode = None                      # "one graph" | "one graph + captured RCCL collectives" | "3 segments + 2 eager collectives"
         self.bucket.state[2] = lr
@@ -294,6 +331,71 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
     def set_lr(self, lr: float):
         self.lr = lr
         self.bucket.state[2] = lr
+
+    # ------------------------------------------------------------------ parameter groups
+    COMPONENTS = ("eeg_encoder", "fmri_encoder", "head")
+
+    @classmethod
+    def _check_component(cls, name, who: str) -> str:
+        if name not in cls.COMPONENTS:
+            raise ValueError(f"BridgeTrainer: {who} names the component {name!r}; the components are {cls.COMPONENTS}")
+        return name
+
+    @classmethod
+    def _check_freeze(cls, freeze, group) -> tuple:
+        names = (freeze,) if isinstance(freeze, str) else tuple(freeze)
+        for name in names:
+            if cls._check_component(name, "freeze") == "head":
+                raise ValueError("BridgeTrainer: freeze=('head',) would leave nothing the contrastive loss trains; freeze the "
+                                 "encoders, hold the head with lr_scale={'head': 0.0}")
+        if names and group is not None and dp.world_size(group) > 1:
+            raise NotImplementedError("BridgeTrainer: freeze= with a process group of world size > 1 is not supported yet "
+                                      "(intended: the gradient groups of the remaining parameters, reduced as now)")
+        return tuple(n for n in cls.COMPONENTS if n in names)
+
+    @classmethod
+    def _check_lr_scale(cls, lr_scale) -> dict:
+        scales = {name: 1.0 for name in cls.COMPONENTS}
+        for name, value in (lr_scale or {}).items():
+            scales[cls._check_component(name, "lr_scale")] = optim.check_lr_scale(value, f"BridgeTrainer(lr_scale[{name!r}])")
+        return scales
+
+    def _table_entries(self):
+        """(numel, multiplier, weight decay, component) of every bucket parameter, in bucket order"""
+        wd = float(self.weight_decay)
+        return [(p.numel(), self._lr_scale[c], 0.0 if self.no_decay and p.ndim <= 1 else wd, c)
+                for p, c in zip(self.bucket.params, self._param_component)]
+
+    def _table_lists(self):
+        return optim.segment_table(self._table_entries(), "BridgeTrainer")
+
+    def _segment_components(self) -> list:
+        """the component of every segment of the table (segments never span two components: `segment_table`'s tag)"""
+        return optim.segment_table(self._table_entries(), "BridgeTrainer", tags=True)[3]
+
+    @property
+    def lr_scales(self) -> dict:
+        """``{component: multiplier of the learning rate}`` (a frozen component's is kept but unused)"""
+        return dict(self._lr_scale)
+
+    def set_lr_scale(self, name: str, value: float):
+        """rewrite one component's learning-rate multiplier: a copy into the segment table on the device, outside the
+        captured step, the way `set_lr` writes the rate itself - the next step uses it, nothing is captured again.
+        (Only a trainer whose table was uniform - it launches the plain kernel - switches to the per-segment kernel at the
+        first multiplier that differs, once: its captured step is dropped and the next graph step captures anew.)"""
+        self._check_component(name, "set_lr_scale")
+        self._lr_scale[name] = optim.check_lr_scale(value, f"set_lr_scale({name!r})")
+        self._table.write(mults=[self._lr_scale[c] for c in self._seg_component])
+        if not self._grouped and not self._table.uniform:
+            self._grouped = True
+            self._drop_capture()
+
+    def train(self, mode: bool = True):
+        """a frozen encoder stays in eval form"""
+        super().train(mode)
+        for name in getattr(self, "_frozen", ()):
+            getattr(self, name).eval()
+        return self
 
     # ------------------------------------------------------------------ averaged weights
     def _need_ema(self, who: str):
@@ -386,7 +488,7 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
         with ``classify=True``: the step then also trains the classification branch and returns ``contrastive_loss``,
         ``ce_loss``, ``cls_correct`` and ``loss`` = contrastive_loss + ce_weight * ce_loss."""
         self._no_step_on_average("train_step")
-        self._check_fmri(fmri.shape, True, "train_step")   # before the first launch of the step (or of its capture)
+        self._check_fmri(fmri.shape, "fmri_encoder" not in self._frozen, "train_step")   # before the first launch of the step (or of its capture)
         if self._fmri_kind == "tabular" and fmri.is_cuda:
             self.fmri_encoder.tickets(fmri.device)         # the forward launch's words exist before any capture
         gid = ops.group_ids(groups, eeg.shape[0], None if self.mode == "graph" else eeg.device, "train_step")
@@ -514,10 +616,11 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
         def fmri_branch():
             with torch.cuda.stream(self._side):
                 self._stamp(3)
+                live = "fmri_encoder" not in self._frozen     # frozen: the eval form, nothing saved, no seed drawn
                 if self._fmri_kind == "tabular":         # one launch
-                    out = ops._tab_forward_impl(self.fmri_encoder, fmri, True, True)
+                    out = ops._tab_forward_impl(self.fmri_encoder, fmri, live, live)
                 else:
-                    out = ops._vol_forward_impl(self.fmri_encoder, fmri, True, True)
+                    out = ops._vol_forward_impl(self.fmri_encoder, fmri, live, live)
                 self._stamp(4)
             return out
         if self._fmri_longer:
@@ -549,13 +652,14 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
 
     def _eeg_forward(self, eeg, xb):
         enc = self.eeg_encoder
+        live = "eeg_encoder" not in self._frozen          # frozen: the eval form, nothing saved, no seed drawn
         if self._eeg_kind == "erp":
-            return ops._erp_forward_impl(enc, eeg, True, True, xb=xb)
+            return ops._erp_forward_impl(enc, eeg, live, live, xb=xb)
         if self._eeg_kind == "power":
-            return ops._power_forward_impl(enc, xb if xb is not None else ops.pack_nct(eeg), True, False)
+            return ops._power_forward_impl(enc, xb if xb is not None else ops.pack_nct(eeg), live, False)
         # config #5: the parameter-free multi-scale STFT power front-end (z-scored per sample), then a4
         spec = ops.stft_front_end(eeg, enc.n_ffts, enc.hop, enc.normalize)
-        return ops._power_forward_impl(enc.encoder, spec, True, False)
+        return ops._power_forward_impl(enc.encoder, spec, live, False)
 
     def _seg_loss(self, z_all, scal, dz, gid_all=None):
         """symmetric InfoNCE of this rank's rows against the gathered batch, gradient w.r.t. ITS rows only
@@ -611,7 +715,8 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
             # reads) do not wait for the end of the chain: they are handed to the side stream, which
             # is idle once the fMRI branch is done - unless that branch is the longer one (`_fmri_is_longer`): then
             # nothing is handed over, the chain flushes its own sums, and the fMRI backward is issued first
-            hand = not getattr(self, "_fmri_longer", False)
+            eeg_live, fmri_live = "eeg_encoder" not in self._frozen, "fmri_encoder" not in self._frozen
+            hand = not getattr(self, "_fmri_longer", False) and eeg_live   # (a frozen EEG encoder hands nothing over)
             handed = []
 
             def split():
@@ -631,7 +736,7 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
             # decides: 0.773-0.776 / 0.782-0.799 / 0.789-0.793 ms per step for 1 / 2 / 0 (profiles/r03_second_half_ab.txt).
             # With the blocks' row-wise backward in one launch (mm_ffn_rows_bwd) the chain is ~40 us shorter and the side
             # stream ends last: the default is then 0 (0.735-0.738 against 0.751-0.758 ms for 1, profiles/ffn_rows_bwd_ab.txt)
-            fused_rows = self._eeg_kind == "erp" and ffn_rows_bwd_fused(sv_e.get("blocks"))
+            fused_rows = self._eeg_kind == "erp" and eeg_live and ffn_rows_bwd_fused(sv_e.get("blocks"))
             handed_convs = int(os.environ.get("MM_CONV_WGRADS_HANDED", "0" if fused_rows else "1")) if hand else 0
             bag.defer_conv_wgrads = handed_convs >= 2
 
@@ -643,7 +748,9 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
                     self._stamp(9)
                     bag_f = GradBag()                    # the fMRI branch flushes its own reductions on ITS stream,
                     with deferred(bag_f, dz.device):     # hidden beside the rest of the EEG backward
-                        if self._fmri_kind == "tabular":     # one launch, plain stores into the bucket's fMRI range
+                        if not fmri_live:                    # frozen: no backward launch of this encoder
+                            pass
+                        elif self._fmri_kind == "tabular":   # one launch, plain stores into the bucket's fMRI range
                             fmri_tab_bwd(bag_f, sv_f, dff)
                         else:
                             volume_encoder_bwd(bag_f, sv_f, dff)
@@ -660,7 +767,9 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
             if not hand:
                 bag_f = fmri_branch()
             finish = None
-            if self._eeg_kind == "erp":
+            if not eeg_live:                     # frozen: no backward launch of this encoder
+                pass
+            elif self._eeg_kind == "erp":
                 erp_encoder_bwd(bag, sv_e, dfe, after_blocks=split, after_conv2=split_convs, after_conv3=conv3_done)   # longer chain first (see _seg_forward)
             else:
                 _, finish = power_encoder_bwd(bag, sv_e, dfe)
@@ -695,7 +804,10 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
     def _seg_adamw(self):
         b = self.bucket
         _hip.call("mm_sumsq", b.g, b.state, b.n)
-        if b.ema is None:
+        if self._grouped:                             # parameter groups: the segment table in place of the scalar decay
+            optim.adamw_clip_groups(b, self._table, self.betas, self.eps, self.grad_clip, 1.0 / self.world, 1, ops.EP(),
+                                    self.ema_decay, self.ema_warmup)
+        elif b.ema is None:
             _hip.call("mm_adamw_clip", b.p, b.g, b.m, b.v, b.state, b.n, self.betas[0], self.betas[1],
                       self.eps, self.weight_decay, self.grad_clip, 1.0 / self.world, 1, ops.EP())
         else:                                         # the same update + the weight average, in the same launch

@@ -1,6 +1,7 @@
 // The optimizer step: sum of squared gradients, then fused AdamW with the global-norm clip, on one flat fp32 bucket.
 // Callers: optim.FusedAdamW and bridge_trainer.py's captured step (mm_sumsq, then mm_adamw_clip or, with an exponential
-// moving average of the weights, mm_adamw_clip_ema).
+// moving average of the weights, mm_adamw_clip_ema; with parameter groups - per-segment learning-rate multipliers and weight
+// decays - mm_adamw_clip_groups / mm_adamw_clip_groups_ema).
 #include "common.h"
 
 namespace {
@@ -106,12 +107,89 @@ __global__ void adamw_finish_kernel(float* __restrict__ state, float max_norm, f
     state[1] = ss;
 }
 
+// Parameter groups (mm_adamw_clip_groups[_ema]): the bucket is cut into n_seg <= MM_OPT_MAX_SEGMENTS contiguous segments,
+// segment s = [seg_end[s-1], seg_end[s]) with its own learning rate lr_s = fl32(state[2] * seg_lr_mult[s]) and weight decay
+// seg_wd[s].  The table is DEVICE memory read at launch, so a captured launch serves any later change of its values.
+// Contract: an element of segment s gets the bits adamw_kernel<EMA> writes for it when called with the scalars lr = lr_s,
+// wd = seg_wd[s] (step count, norm, clip, zero_grad and the average are the bucket's, as there).  adamw_kernel's
+// expressions are contracted by the compiler; the forms it takes there are WRITTEN OUT here (__fmaf_rn / __fmul_rn), so
+// that this kernel's bits do not depend on what the optimizer makes of a differently shaped loop:
+//     clip    max_norm / fma(sqrt(sumsq), grad_scale, 1e-6)
+//     decay   fma(-wd, lr, 1)                      step_size  lr / bc1
+//     m       fma(1 - b1, g, b1 * m)               v          fma(g, (1 - b2) * g, b2 * v)
+//     p       fma(decay, p, -(step_size * m / fma(rsqrt(bc2), sqrt(v), eps)))
+// (tests/test_adamw_groups_kernels_gpu.py holds the two kernels to each other bit for bit.)
+// Every workgroup stages {end, decay, step_size} of all segments in LDS once (16 bytes a segment, 16 KB at the cap) and
+// finds an element's segment by binary search over the ends: the first s with i < end[s], else the last one - the search
+// runs over [0, n_seg) only, so no element and no table content can form an address outside the table.
+constexpr int OPT_MAX_SEGMENTS = 1024;            // MM_OPT_MAX_SEGMENTS
+
+template <bool EMA>
+__global__ void adamw_groups_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
+                                    float* __restrict__ v, const float* __restrict__ state, size_t n, float beta1,
+                                    float beta2, float eps, float max_norm, float grad_scale, int zero_grad,
+                                    const long long* __restrict__ seg_end, const float* __restrict__ seg_lr_mult,
+                                    const float* __restrict__ seg_wd, int n_seg, float* __restrict__ ema,
+                                    float ema_decay, int ema_warmup) {
+    __shared__ long long s_end[OPT_MAX_SEGMENTS];
+    __shared__ float s_decay[OPT_MAX_SEGMENTS], s_step[OPT_MAX_SEGMENTS];
+    const float step = state[0] + 1.f;
+    const float lr = state[2];
+    const float gn = __fmaf_rn(sqrtf(sumsq_total(state)), grad_scale, 1e-6f);
+    const float clip = (max_norm > 0.f) ? fminf(1.f, max_norm / gn) : 1.f;
+    const float gs = __fmul_rn(grad_scale, clip);
+    const float bc1 = 1.f - powf(beta1, step), bc2 = 1.f - powf(beta2, step);
+    const float inv_sqrt_bc2 = rsqrtf(bc2);
+    const float omb1 = 1.f - beta1, omb2 = 1.f - beta2;
+    const float one_minus_d = EMA ? 1.f - ema_decay_at(step, ema_decay, ema_warmup) : 0.f;
+    for (int s = threadIdx.x; s < n_seg; s += blockDim.x) {
+        const float lr_s = __fmul_rn(lr, seg_lr_mult[s]);
+        s_end[s] = seg_end[s];
+        s_decay[s] = __fmaf_rn(-seg_wd[s], lr_s, 1.f);
+        s_step[s] = lr_s / bc1;
+    }
+    __syncthreads();
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        int lo = 0, hi = n_seg - 1;
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if ((long long)i < s_end[mid]) hi = mid; else lo = mid + 1;
+        }
+        const float decay = s_decay[lo], step_size = s_step[lo];
+        const float gi = __fmul_rn(g[i], gs);
+        const float mi = __fmaf_rn(omb1, gi, __fmul_rn(beta1, m[i]));
+        const float vi = __fmaf_rn(gi, __fmul_rn(omb2, gi), __fmul_rn(beta2, v[i]));
+        const float q = __fmul_rn(step_size, mi) / __fmaf_rn(inv_sqrt_bc2, sqrtf(vi), eps);
+        const float pi = __fmaf_rn(decay, p[i], -q);
+        p[i] = pi; m[i] = mi; v[i] = vi;
+        if (zero_grad) g[i] = 0.f;
+        if (EMA) {
+            const float e = ema[i];
+            ema[i] = __fmaf_rn(one_minus_d, __fsub_rn(pi, e), e);
+        }
+    }
+}
+
 template <bool EMA>
 int adamw_launch(float* p, float* g, float* m, float* v, float* state, int64_t n, float beta1, float beta2, float eps,
                  float weight_decay, float max_norm, float grad_scale, int zero_grad, uint32_t* seed_epoch, float* ema,
                  float ema_decay, int ema_warmup, hipStream_t st, const char* what) {
     hipLaunchKernelGGL(adamw_kernel<EMA>, dim3(grid_for((size_t)n, 2048)), dim3(256), 0, st, p, g, m, v, state, (size_t)n,
                        beta1, beta2, eps, weight_decay, max_norm, grad_scale, zero_grad, ema, ema_decay, ema_warmup);
+    hipLaunchKernelGGL(adamw_finish_kernel<EMA>, dim3(1), dim3(256), 0, st, state, max_norm, grad_scale, seed_epoch,
+                       ema_decay, ema_warmup);
+    return mm_check_launch(what);
+}
+
+// the same two launches with the per-segment update kernel: adamw_finish_kernel is the plain step's
+template <bool EMA>
+int adamw_groups_launch(float* p, float* g, float* m, float* v, float* state, int64_t n, float beta1, float beta2,
+                        float eps, float max_norm, float grad_scale, int zero_grad, uint32_t* seed_epoch,
+                        const int64_t* seg_end, const float* seg_lr_mult, const float* seg_wd, int n_seg, float* ema,
+                        float ema_decay, int ema_warmup, hipStream_t st, const char* what) {
+    hipLaunchKernelGGL(adamw_groups_kernel<EMA>, dim3(grid_for((size_t)n, 2048)), dim3(256), 0, st, p, g, m, v, state,
+                       (size_t)n, beta1, beta2, eps, max_norm, grad_scale, zero_grad, (const long long*)seg_end,
+                       seg_lr_mult, seg_wd, n_seg, ema, ema_decay, ema_warmup);
     hipLaunchKernelGGL(adamw_finish_kernel<EMA>, dim3(1), dim3(256), 0, st, state, max_norm, grad_scale, seed_epoch,
                        ema_decay, ema_warmup);
     return mm_check_launch(what);
@@ -135,5 +213,33 @@ int mm_adamw_clip_ema(float* p, float* g, float* m, float* v, float* state, int6
     MM_REQUIRE(ema_decay >= 0.f && ema_decay < 1.f, "adamw_clip_ema: ema_decay %g outside [0, 1)", (double)ema_decay);
     return adamw_launch<true>(p, g, m, v, state, n, beta1, beta2, eps, weight_decay, max_norm, grad_scale, zero_grad,
                               seed_epoch, ema, ema_decay, ema_warmup, st, "adamw_clip_ema");
+}
+
+// (the table's CONTENTS are device memory: the host that builds it validates them - optim.segment_table)
+#define MM_REQUIRE_SEGMENTS(who)                                                                                      \
+    MM_REQUIRE(seg_end && seg_lr_mult && seg_wd, who ": a segment table array is null");                              \
+    MM_REQUIRE(n_seg >= 1 && n_seg <= OPT_MAX_SEGMENTS, who ": n_seg %d outside [1, %d]", n_seg, OPT_MAX_SEGMENTS)
+
+int mm_adamw_clip_groups(float* p, float* g, float* m, float* v, float* state, int64_t n, float beta1, float beta2,
+                         float eps, float max_norm, float grad_scale, int zero_grad, uint32_t* seed_epoch,
+                         const int64_t* seg_end, const float* seg_lr_mult, const float* seg_wd, int n_seg,
+                         hipStream_t st) {
+    MM_REQUIRE(p && g && m && v && state && n > 0, "adamw_clip_groups: null");
+    MM_REQUIRE_SEGMENTS("adamw_clip_groups");
+    return adamw_groups_launch<false>(p, g, m, v, state, n, beta1, beta2, eps, max_norm, grad_scale, zero_grad, seed_epoch,
+                                      seg_end, seg_lr_mult, seg_wd, n_seg, nullptr, 0.f, 0, st, "adamw_clip_groups");
+}
+
+int mm_adamw_clip_groups_ema(float* p, float* g, float* m, float* v, float* state, int64_t n, float beta1, float beta2,
+                             float eps, float max_norm, float grad_scale, int zero_grad, uint32_t* seed_epoch,
+                             const int64_t* seg_end, const float* seg_lr_mult, const float* seg_wd, int n_seg,
+                             float* ema, float ema_decay, int ema_warmup, hipStream_t st) {
+    MM_REQUIRE(p && g && m && v && state && n > 0, "adamw_clip_groups_ema: null");
+    MM_REQUIRE_SEGMENTS("adamw_clip_groups_ema");
+    MM_REQUIRE(ema, "adamw_clip_groups_ema: ema is null (mm_adamw_clip_groups is the update without a weight average)");
+    MM_REQUIRE(ema_decay >= 0.f && ema_decay < 1.f, "adamw_clip_groups_ema: ema_decay %g outside [0, 1)", (double)ema_decay);
+    return adamw_groups_launch<true>(p, g, m, v, state, n, beta1, beta2, eps, max_norm, grad_scale, zero_grad, seed_epoch,
+                                     seg_end, seg_lr_mult, seg_wd, n_seg, ema, ema_decay, ema_warmup, st,
+                                     "adamw_clip_groups_ema");
 }
 }  // extern "C"

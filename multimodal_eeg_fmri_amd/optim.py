@@ -1,5 +1,7 @@
 """Flat parameter bucket + fused clip/AdamW (``mm_sumsq`` + ``mm_adamw_clip``, or ``mm_adamw_clip_ema`` when an
-exponential moving average of the weights is kept: same launch, one more read and one more write stream).
+exponential moving average of the weights is kept: same launch, one more read and one more write stream; with parameter
+groups - learning-rate multipliers and weight decays per segment of the bucket, `segment_table` - ``mm_adamw_clip_groups``
+/ ``mm_adamw_clip_groups_ema``).
 
 Replaces the reference's ``clip_grad_norm_(max_norm=1.0)`` + ``torch.optim.AdamW.step()``
 pair (run_training_lite.py:487-488, _test_bridge.py:784-786) with two kernel
@@ -7,6 +9,7 @@ launches over one contiguous fp32 buffer."""
 from __future__ import annotations
 
 import contextlib
+import math
 
 import torch
 
@@ -17,6 +20,93 @@ def check_ema_decay(ema_decay, who: str):
     """``ema_decay`` is 0 (no average) or a decay in (0, 1): ValueError otherwise"""
     if not 0.0 <= float(ema_decay) < 1.0:
         raise ValueError(f"{who}: ema_decay must be in [0, 1) (got {ema_decay}); 0 = no averaged weights")
+
+
+MAX_SEGMENTS = 1024                               # MM_OPT_MAX_SEGMENTS
+
+
+def check_lr_scale(value, who: str) -> float:
+    """a learning-rate multiplier is a finite number >= 0 (0 holds the weights still while the moments move):
+    ValueError otherwise"""
+    try:
+        x = float(value)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: lr_scale must be a number (got {value!r})") from None
+    if not math.isfinite(x) or x < 0.0:
+        raise ValueError(f"{who}: lr_scale must be finite and >= 0 (got {value})")
+    return x
+
+
+def segment_table(entries, who: str = "segment_table", tags: bool = False):
+    """The host side of the segment table of ``mm_adamw_clip_groups``.  ``entries``: ``(numel, lr_scale, weight_decay)``
+    or ``(numel, lr_scale, weight_decay, tag)`` per parameter, in bucket order.  Neighbours with equal
+    ``(lr_scale, weight_decay, tag)`` merge into one segment (a tag keeps two ranges apart whose values are equal now
+    but are changed separately later); entries of no elements vanish.  Returns ``(seg_end, seg_lr_mult, seg_wd)``:
+    lists of equal length 1 .. ``MAX_SEGMENTS``, the ends strictly increasing and the last one the bucket's size
+    (``tags=True``: and the list of the segments' tags).
+    ValueError: a multiplier that is negative, NaN or infinite, a weight decay that is, a negative size, no element at
+    all, or more than ``MAX_SEGMENTS`` segments."""
+    ends, mults, wds, seg_tags = [], [], [], []
+    off = 0
+    for e in entries:
+        k, scale, wd = int(e[0]), check_lr_scale(e[1], who), float(e[2])
+        tag = e[3] if len(e) > 3 else None
+        if k < 0:
+            raise ValueError(f"{who}: a parameter of {k} elements")
+        if not math.isfinite(wd) or wd < 0.0:
+            raise ValueError(f"{who}: weight_decay must be finite and >= 0 (got {e[2]})")
+        if k == 0:
+            continue
+        off += k
+        if ends and (mults[-1], wds[-1], seg_tags[-1]) == (scale, wd, tag):
+            ends[-1] = off
+        else:
+            ends.append(off); mults.append(scale); wds.append(wd); seg_tags.append(tag)
+    if not ends:
+        raise ValueError(f"{who}: no elements")
+    if len(ends) > MAX_SEGMENTS:
+        raise ValueError(f"{who}: {len(ends)} segments, the update kernel takes at most {MAX_SEGMENTS} (order the parameters "
+                         "so that equal (lr_scale, weight_decay) are neighbours)")
+    return (ends, mults, wds, seg_tags) if tags else (ends, mults, wds)
+
+
+class SegmentTable:
+    """``segment_table``'s lists as the device arrays ``mm_adamw_clip_groups`` reads: ``end`` int64, ``mult`` and ``wd``
+    fp32, ``n_seg`` values each.  The arrays are written in place (`write`), so a captured launch that holds their
+    pointers serves later values; the number of segments of a table is fixed."""
+
+    def __init__(self, ends, mults, wds, device):
+        self.n_seg = len(ends)
+        self.ends, self.mults, self.wds = list(ends), list(mults), list(wds)
+        self.end = torch.tensor(self.ends, dtype=torch.int64, device=device)
+        self.mult = torch.tensor(self.mults, dtype=torch.float32, device=device)
+        self.wd = torch.tensor(self.wds, dtype=torch.float32, device=device)
+
+    @property
+    def uniform(self) -> bool:
+        """multiplier 1 everywhere and one weight decay: the step of the plain kernel"""
+        return all(m == 1.0 for m in self.mults) and len(set(self.wds)) == 1
+
+    def write(self, mults=None, wds=None):
+        """new multipliers and / or decays for the same segments, copied into the device arrays"""
+        for new, host, devt in ((mults, self.mults, self.mult), (wds, self.wds, self.wd)):
+            if new is None:
+                continue
+            if len(new) != self.n_seg:
+                raise ValueError(f"SegmentTable.write: {len(new)} values for {self.n_seg} segments")
+            host[:] = [float(x) for x in new]
+            devt.copy_(torch.tensor(host, dtype=torch.float32))
+
+
+def adamw_clip_groups(b, table, betas, eps, max_norm, grad_scale, zero_grad, seed_epoch, ema_decay=0.0, ema_warmup=True):
+    """the update launch of a step with parameter groups on FlatBucket ``b`` (after ``mm_sumsq``): SegmentTable
+    ``table`` in place of the scalar weight decay; with ``b.ema`` the weight average rides along, as in the plain step"""
+    args = (b.p, b.g, b.m, b.v, b.state, b.n, betas[0], betas[1], eps, float(max_norm), float(grad_scale),
+            int(zero_grad), seed_epoch, table.end, table.mult, table.wd, table.n_seg)
+    if b.ema is None:
+        _hip.call("mm_adamw_clip_groups", *args)
+    else:
+        _hip.call("mm_adamw_clip_groups_ema", *args, b.ema, float(ema_decay), int(ema_warmup))
 
 
 class FlatBucket:
@@ -80,35 +170,84 @@ class FusedAdamW:
     ``ema_decay`` in (0, 1): ``step()`` also keeps an exponential moving average of the weights (``bucket.ema``), in the
     update kernel itself: ``ema += (1 - d) * (p - ema)`` after every step, ``d = min(ema_decay, (1 + t) / (10 + t))`` at
     step count t with ``ema_warmup`` (the usual warm-up of the decay, so that the first steps are not averaged with the
-    initialisation for long), ``d = ema_decay`` without.  0 (default): no average, the launches are unchanged."""
+    initialisation for long), ``d = ema_decay`` without.  0 (default): no average, the launches are unchanged.
+    ``params``: parameters, or torch-style groups ``[{"params": a}, {"params": b, "lr_scale": 0.1, "weight_decay": 0.0}]``.
+    ``param_groups[i]["lr"]`` is the BASE learning rate, one value shared by all groups (``step()`` raises ValueError when
+    they disagree; a scheduler that sets every group to the same value keeps the ratios); ``lr_scale`` (default 1, finite,
+    >= 0) multiplies it for the group, ``weight_decay`` defaults to the constructor's.  The bucket is laid out in group
+    order, neighbours with equal ``(lr_scale, weight_decay)`` share one segment of the table (`segment_table`); one
+    segment of multiplier 1 - a plain parameter list - launches ``mm_adamw_clip[_ema]`` as ever, anything else
+    ``mm_adamw_clip_groups[_ema]``.  The norm that is clipped is over all groups."""
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01,
                  max_grad_norm: float = 0.0, ema_decay: float = 0.0, ema_warmup: bool = True):
         check_ema_decay(ema_decay, "FusedAdamW")
         self.ema_decay, self.ema_warmup = float(ema_decay), bool(ema_warmup)
         self._averaged = False
-        self._all = list(params)                  # torch's state_dict numbers EVERY param of the group
+        params = list(params)
+        groups = params if params and isinstance(params[0], dict) else [{"params": params}]
+        self._group_all = []                      # every param of each group: torch's state_dict numbers them ALL
+        self.param_groups = []
+        for gr in groups:
+            unknown = set(gr) - {"params", "lr", "lr_scale", "weight_decay"}
+            if unknown:
+                raise ValueError(f"FusedAdamW: a parameter group has the keys {sorted(unknown)}; betas and eps are shared, "
+                                 "a group sets lr_scale and weight_decay")
+            ps = list(gr["params"])
+            self._group_all.append(ps)
+            self.param_groups.append({"lr": gr.get("lr", lr), "params": [p for p in ps if p.requires_grad],
+                                      "lr_scale": check_lr_scale(gr.get("lr_scale", 1.0), "FusedAdamW"),
+                                      "weight_decay": gr.get("weight_decay", weight_decay)})
+        self._all = [p for ps in self._group_all for p in ps]
+        if len({id(p) for p in self._all}) != len(self._all):
+            raise ValueError("FusedAdamW: some parameters appear in more than one parameter group")
         self.bucket = FlatBucket(self._all, ema=self.ema_decay > 0)
-        self.param_groups = [{"lr": lr, "params": self.bucket.params}]
-        self.betas, self.eps, self.weight_decay, self.max_grad_norm = betas, eps, weight_decay, max_grad_norm
+        self.betas, self.eps, self.max_grad_norm = betas, eps, max_grad_norm
+        self._table = None                        # SegmentTable of the last step that needed one
+        self._host_table()                        # (more than MAX_SEGMENTS segments: ValueError here, not at step 1)
         ops.weights_changed()
+
+    @property
+    def weight_decay(self):
+        """the weight decay of group 0 - of every parameter when ``params`` was a plain list"""
+        return self.param_groups[0]["weight_decay"]
+
+    @weight_decay.setter
+    def weight_decay(self, value):
+        self.param_groups[0]["weight_decay"] = value
 
     def zero_grad(self, set_to_none: bool = True):
         self.bucket.zero_grad()
 
+    def _host_table(self):
+        return segment_table([(p.numel(), gr["lr_scale"], gr["weight_decay"]) for gr in self.param_groups
+                              for p in gr["params"]], "FusedAdamW")
+
     def step(self):
         b = self.bucket
         b.absorb_autograd_grads()
-        b.state[2] = float(self.param_groups[0]["lr"])
+        lrs = {float(gr["lr"]) for gr in self.param_groups}
+        if len(lrs) != 1:
+            raise ValueError(f"FusedAdamW.step: the groups' 'lr' is the shared base learning rate, they hold {sorted(lrs)}; "
+                             "give a group its own rate with 'lr_scale'")
+        b.state[2] = lrs.pop()
         if self._averaged:
             raise RuntimeError("FusedAdamW.step inside averaged(): the parameters hold the averaged weights")
+        ends, mults, wds = self._host_table()     # (read every step: the groups' values may be changed between steps)
         _hip.call("mm_sumsq", b.g, b.state, b.n)
-        if b.ema is None:
+        if not (len(ends) == 1 and mults[0] == 1.0):
+            t = self._table
+            if t is None or t.ends != ends:
+                t = self._table = SegmentTable(ends, mults, wds, b.p.device)
+            elif (t.mults, t.wds) != (mults, wds):
+                t.write(mults, wds)
+            adamw_clip_groups(b, t, self.betas, self.eps, self.max_grad_norm, 1.0, 0, None, self.ema_decay, self.ema_warmup)
+        elif b.ema is None:
             _hip.call("mm_adamw_clip", b.p, b.g, b.m, b.v, b.state, b.n, self.betas[0], self.betas[1],
-                      self.eps, self.weight_decay, float(self.max_grad_norm), 1.0, 0, None)
+                      self.eps, wds[0], float(self.max_grad_norm), 1.0, 0, None)
         else:
             _hip.call("mm_adamw_clip_ema", b.p, b.g, b.m, b.v, b.state, b.n, self.betas[0], self.betas[1],
-                      self.eps, self.weight_decay, float(self.max_grad_norm), 1.0, 0, None,
+                      self.eps, wds[0], float(self.max_grad_norm), 1.0, 0, None,
                       b.ema, self.ema_decay, int(self.ema_warmup))
         ops.weights_changed()
 
@@ -153,22 +292,34 @@ class FusedAdamW:
         step = float(b.state[0].item())
         state = {i: {"step": torch.tensor(step), "exp_avg": b.m[sl].view(p.shape).clone(),
                      "exp_avg_sq": b.v[sl].view(p.shape).clone()} for i, p, sl in self._slices()}
-        group = {"lr": self.param_groups[0]["lr"], "betas": tuple(self.betas), "eps": self.eps,
-                 "weight_decay": self.weight_decay, "amsgrad": False, "maximize": False, "foreach": None,
-                 "capturable": False, "differentiable": False, "fused": None, "decoupled_weight_decay": True,
-                 "params": list(range(len(self._all)))}
-        sd = {"state": state, "param_groups": [group]}
+        groups, first = [], 0
+        for gr, ps in zip(self.param_groups, self._group_all):
+            groups.append({"lr": gr["lr"], "betas": tuple(self.betas), "eps": self.eps,
+                           "weight_decay": gr["weight_decay"], "amsgrad": False, "maximize": False, "foreach": None,
+                           "capturable": False, "differentiable": False, "fused": None, "decoupled_weight_decay": True,
+                           "params": list(range(first, first + len(ps)))})
+            if len(self.param_groups) > 1 or gr["lr_scale"] != 1.0:    # (a plain parameter list keeps its container)
+                groups[-1]["lr_scale"] = gr["lr_scale"]
+            first += len(ps)
+        sd = {"state": state, "param_groups": groups}
         if b.ema is not None:                     # one extra top-level key, only when averaging is on
             sd["ema"] = {"decay": self.ema_decay, "warmup": self.ema_warmup, "shadow": b.ema.clone()}
         return sd
 
     def load_state_dict(self, sd):
-        group = sd["param_groups"][0]
-        if len(group["params"]) != len(self._all):
+        groups = sd["param_groups"]
+        if len(groups) != len(self.param_groups):
+            raise ValueError("loaded state dict has a different number of parameter groups")
+        if any(len(g["params"]) != len(ps) for g, ps in zip(groups, self._group_all)):
             raise ValueError("loaded state dict contains a parameter group that doesn't match the size of "
                              "optimizer's group")
-        if group.get("amsgrad"):
+        if any(g.get("amsgrad") for g in groups):
             raise ValueError("FusedAdamW has no amsgrad state")
+        if any((tuple(g["betas"]), g["eps"]) != (tuple(groups[0]["betas"]), groups[0]["eps"]) for g in groups):
+            raise ValueError("FusedAdamW shares betas and eps between its parameter groups; the loaded groups' differ")
+        scales = [check_lr_scale(g.get("lr_scale", mine["lr_scale"]), "FusedAdamW.load_state_dict")
+                  for g, mine in zip(groups, self.param_groups)]
+        group = groups[0]
         b = self.bucket
         ema = sd.get("ema")
         # (a torch.optim.AdamW state dict has no "ema": the average is then left as it is - `sync_ema` after loading the
@@ -177,8 +328,9 @@ class FusedAdamW:
             raise ValueError("FusedAdamW: the state dict carries averaged weights, this optimizer was built without ema_decay")
         if ema is not None and tuple(ema["shadow"].shape) != (b.n,):
             raise ValueError(f"FusedAdamW: ema.shadow has {tuple(ema['shadow'].shape)} elements, the bucket {b.n}")
-        self.param_groups[0]["lr"] = group["lr"]
-        self.betas, self.eps, self.weight_decay = tuple(group["betas"]), group["eps"], group["weight_decay"]
+        for mine, g, scale in zip(self.param_groups, groups, scales):
+            mine["lr"], mine["weight_decay"], mine["lr_scale"] = g["lr"], g["weight_decay"], scale
+        self.betas, self.eps = tuple(group["betas"]), group["eps"]
         steps = set()
         b.m.zero_(); b.v.zero_()
         for i, p, sl in self._slices():

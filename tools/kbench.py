@@ -555,6 +555,61 @@ def ema_case(step_iters=30, rounds=5):
           f"({s1 - s0:+.1f} us, {100 * (s1 / s0 - 1):+.2f} %)")
 
 
+def groups_case(step_iters=30, rounds=5):
+    """parameter groups in the update kernel, at the default C2 trainer's bucket size, graph-replayed launches in the same
+    run, interleaved rounds: mm_adamw_clip against mm_adamw_clip_groups with 1, 8 and ~200 segments (the same 8 streams over
+    the bucket; the difference is the staging of the table in LDS and the per-element search); then the C2 graph step
+    (B = 32) of the default trainer, with no_decay=True (the trainer's own table), and with the fMRI encoder / both encoders
+    frozen"""
+    from multimodal_eeg_fmri_amd.bridge_trainer import BridgeTrainer, synthetic_pairs
+    setups = [("default", {}), ("no_decay", {"no_decay": True}), ("freeze fmri", {"freeze": ("fmri_encoder",)}),
+              ("freeze both", {"freeze": ("eeg_encoder", "fmri_encoder")})]
+    trs = []
+    for _, kw in setups:
+        ops.set_seed_epoch(None)
+        torch.manual_seed(0)
+        trs.append(BridgeTrainer(eeg_channels=64, dropout=0.3, **kw).train())
+    n = trs[0].bucket.n
+    p, g, m = (torch.randn(n, device="cuda") * s for s in (1.0, 0.1, 0.01))
+    v = torch.rand(n, device="cuda") * 1e-3
+    state = torch.zeros(8 + 1024, device="cuda")
+    state[2] = 1e-4
+    _hip.call("mm_sumsq", g, state, n)
+    head = (p, g, m, v, state, n, 0.9, 0.999, 1e-8)
+    cases = [("mm_adamw_clip", lambda: _hip.call("mm_adamw_clip", *head, 1e-4, 1.0, 1.0, 0, None))]
+    for n_seg in dict.fromkeys((1, 8, 200, trs[1]._table.n_seg)):
+        if n_seg == trs[1]._table.n_seg:
+            ends = list(trs[1]._table.ends)
+        else:
+            ends = [n * (s + 1) // n_seg for s in range(n_seg)]
+        end = torch.tensor(ends, dtype=torch.int64, device="cuda")
+        mult = torch.tensor([(1.0, 0.1)[s % 2] for s in range(n_seg)], device="cuda")
+        wd = torch.tensor([(1e-4, 0.0)[s % 2] for s in range(n_seg)], device="cuda")
+        cases.append((f"mm_adamw_clip_groups {n_seg} segments",
+                      lambda end=end, mult=mult, wd=wd, n_seg=n_seg: _hip.call("mm_adamw_clip_groups", *head, 1.0, 1.0, 0, None,
+                                                                              end, mult, wd, n_seg)))
+    times = {name: [] for name, _ in cases}
+    for _ in range(rounds):
+        for name, fn in cases:
+            times[name].append(graph_time(fn))
+    t0 = statistics.median(times["mm_adamw_clip"])
+    for name, _ in cases:
+        print(f"update n={n} ({4 * n / 1e6:.2f} MB per stream): {name:36s} {_spread(times[name])}  "
+              f"({statistics.median(times[name]) / t0:.3f}x)")
+    eeg, fmri = synthetic_pairs(32, 64, 1024, (32, 32, 32))
+    for tr in trs:
+        for _ in range(3):
+            tr.train_step(eeg, fmri)
+    steps = [[] for _ in trs]
+    for _ in range(rounds):
+        for i, tr in enumerate(trs):
+            steps[i].append(timeit(lambda: tr.train_step(eeg, fmri), iters=step_iters, rounds=1))
+    s0 = statistics.median(steps[0])
+    for (name, _), tr, xs in zip(setups, trs, steps):
+        print(f"C2 graph step B=32: {name:12s} bucket {tr.bucket.n:8d}  segments {tr._table.n_seg:4d}  {_spread(xs)}  "
+              f"({statistics.median(xs) - s0:+.1f} us)")
+
+
 def _spread(xs):
     return f"{statistics.median(xs):7.1f} us  [{min(xs):.1f} .. {max(xs):.1f}]"
 
@@ -1155,6 +1210,9 @@ def main():
         return
     if flt == "ema":
         ema_case()
+        return
+    if flt == "groups":
+        groups_case()
         return
     if flt == "tabfmri":
         tabfmri_case()
