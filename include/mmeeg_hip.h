@@ -928,7 +928,10 @@ int mm_meanpool_bf16(const void* x, float* out, int R, int S, int N, hipStream_t
  * state[5]: the weight-average decay d of the last step, written by mm_adamw_clip_ema only; mm_adamw_clip never writes
  * state[5..8).
  *
- * mm_adamw_clip_ema: the same update (the same kernel template: p, g, m, v and state[0..5) get mm_adamw_clip's bits)
+ * The four mm_adamw_clip* entry points are instances of ONE update kernel body (and one finish kernel for state[0..5)),
+ * so what they share they share bit for bit.
+ *
+ * mm_adamw_clip_ema: the same update (p, g, m, v and state[0..5) get mm_adamw_clip's bits)
  * plus an exponential moving average of the weights in `ema` (n floats, device, not NULL), in the same launch:
  *     ema[i] = fma(1 - d, p_new[i] - ema[i], ema[i])
  * with 1 - d formed in fp32, the difference rounded to fp32, then one fused multiply-add - so ema[i] keeps its bits
@@ -945,7 +948,8 @@ int mm_meanpool_bf16(const void* x, float* out, int R, int S, int N, hipStream_t
  * last segment, and no element or table content forms an address outside the table.  An element of segment s is
  * updated with lr_s = fl32(state[2] * seg_lr_mult[s]) and weight decay seg_wd[s]: its p, m, v, g (and ema) bits are
  * those mm_adamw_clip (mm_adamw_clip_ema) writes on the whole bucket when called with state[2] = lr_s and
- * weight_decay = seg_wd[s]; state[0..5) and state[5] get the plain entry points' bits.  The step count, the norm (over
+ * weight_decay = seg_wd[s] - it is the same body, the two scalars looked up per element - and state[0..5) and state[5]
+ * are written by the same finish kernel.  The step count, the norm (over
  * the WHOLE bucket: clip_grad_norm_ over all groups), the clip coefficient, zero_grad and the average are unchanged.
  * A multiplier of 0 leaves p bit-unchanged while m and v move (torch's lr = 0 group).  Two launches, as the plain step. */
 #define MM_OPT_STATE_FLOATS 1032

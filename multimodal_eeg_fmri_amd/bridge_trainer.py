@@ -802,18 +802,9 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
         self._seg_adamw()
 
     def _seg_adamw(self):
-        b = self.bucket
-        _hip.call("mm_sumsq", b.g, b.state, b.n)
-        if self._grouped:                             # parameter groups: the segment table in place of the scalar decay
-            optim.adamw_clip_groups(b, self._table, self.betas, self.eps, self.grad_clip, 1.0 / self.world, 1, ops.EP(),
-                                    self.ema_decay, self.ema_warmup)
-        elif b.ema is None:
-            _hip.call("mm_adamw_clip", b.p, b.g, b.m, b.v, b.state, b.n, self.betas[0], self.betas[1],
-                      self.eps, self.weight_decay, self.grad_clip, 1.0 / self.world, 1, ops.EP())
-        else:                                         # the same update + the weight average, in the same launch
-            _hip.call("mm_adamw_clip_ema", b.p, b.g, b.m, b.v, b.state, b.n, self.betas[0], self.betas[1],
-                      self.eps, self.weight_decay, self.grad_clip, 1.0 / self.world, 1, ops.EP(),
-                      b.ema, self.ema_decay, int(self.ema_warmup))
+        # parameter groups: the segment table in place of the scalar decay; with bucket.ema the weight average rides along
+        optim.adamw_update(self.bucket, self.betas, self.eps, self.grad_clip, 1.0 / self.world, 1, ops.EP(),
+                           self._table if self._grouped else self.weight_decay, self.ema_decay, self.ema_warmup)
         ops.weights_changed()
         if self._arena_need is None:
             self._arena_need = (ops.arena.high * 5 // 4 + 4095) // 4096 * 4096

@@ -1,7 +1,8 @@
 // The optimizer step: sum of squared gradients, then fused AdamW with the global-norm clip, on one flat fp32 bucket.
-// Callers: optim.FusedAdamW and bridge_trainer.py's captured step (mm_sumsq, then mm_adamw_clip or, with an exponential
-// moving average of the weights, mm_adamw_clip_ema; with parameter groups - per-segment learning-rate multipliers and weight
-// decays - mm_adamw_clip_groups / mm_adamw_clip_groups_ema).
+// Caller: optim.adamw_update, for optim.FusedAdamW and bridge_trainer.py's captured step (mm_sumsq, then one of the four
+// entry points of ONE update kernel template: mm_adamw_clip; with an exponential moving average of the weights,
+// mm_adamw_clip_ema; with parameter groups - per-segment learning-rate multipliers and weight decays - mm_adamw_clip_groups /
+// mm_adamw_clip_groups_ema).
 #include "common.h"
 
 namespace {
@@ -58,32 +59,76 @@ __device__ inline float ema_decay_at(float t, float ema_decay, int ema_warmup) {
     return ema_warmup ? fminf(ema_decay, (1.f + t) / (10.f + t)) : ema_decay;
 }
 
-// (The bookkeeping below - step counter, last norm / clip coefficient, the dropout epoch word of the next step - stays a
-// one-workgroup launch of its own.  Folding it into the update kernel's LAST-ARRIVING workgroup was tried: 2 048 arrivals on
-// one counter serialise at the L2 and the update went from 10 to 30 us, profiles/r04_step_kernel_summary.txt history.)
-// EMA = false is mm_adamw_clip: `ema` is never read or written, and the compiled loop is the one it always was.
-// EMA = true (mm_adamw_clip_ema): after element i's update, ema[i] += (1 - d) * (p_new[i] - ema[i]) with 1 - d formed in
-// fp32, the difference rounded, then ONE fused multiply-add: where ema[i] == p_new[i] the difference is exactly 0 and
-// ema[i] keeps its bits.  One more read stream and one more write stream over the bucket, no new launch.
-template <bool EMA>
+// The update, written ONCE and instantiated four ways (mm_adamw_clip, _ema, _groups, _groups_ema), so every entry point's
+// bits are one body's.  The forms are WRITTEN OUT (__fmaf_rn / __fmul_rn: what the compiler contracts the plain expressions
+// into), so that the bits do not depend on what the optimizer makes of a differently shaped loop:
+//     clip    max_norm / fma(sqrt(sumsq), grad_scale, 1e-6)
+//     decay   fma(-wd, lr, 1)                      step_size  lr / bc1
+//     m       fma(1 - b1, g, b1 * m)               v          fma(g, (1 - b2) * g, b2 * v)
+//     p       fma(decay, p, -(step_size * m / fma(rsqrt(bc2), sqrt(v), eps)))
+// EMA = false: `ema` is never read or written.  EMA = true: after element i's update, ema[i] += (1 - d) * (p_new[i] - ema[i])
+// with 1 - d formed in fp32, the difference rounded, then ONE fused multiply-add: where ema[i] == p_new[i] the difference is
+// exactly 0 and ema[i] keeps its bits.  One more read stream and one more write stream over the bucket, no new launch.
+// GROUPS = false: decay and step_size are two scalars, from state[2] and `wd`; the table arguments are never read, and the
+// table's LDS arrays are not allocated.
+// GROUPS = true (parameter groups): the bucket is cut into n_seg <= MM_OPT_MAX_SEGMENTS contiguous segments, segment
+// s = [seg_end[s-1], seg_end[s]) with its own learning rate lr_s = fl32(state[2] * seg_lr_mult[s]) and weight decay seg_wd[s]
+// (`wd` is not read).  The table is DEVICE memory read at launch, so a captured launch serves any later change of its
+// values.  Every workgroup stages {end, decay, step_size} of all segments in LDS once (16 bytes a segment, 16 KB at the cap)
+// and finds an element's segment by binary search over the ends: the first s with i < end[s], else the last one - the search
+// runs over [0, n_seg) only, so no element and no table content can form an address outside the table.
+// (The bookkeeping - step counter, last norm / clip coefficient, the dropout epoch word of the next step - stays a
+// one-workgroup launch of its own, adamw_finish_kernel.  Folding it into the update kernel's LAST-ARRIVING workgroup was
+// tried: 2 048 arrivals on one counter serialise at the L2 and the update went from 10 to 30 us,
+// profiles/r04_step_kernel_summary.txt history.)
+constexpr int OPT_MAX_SEGMENTS = 1024;            // MM_OPT_MAX_SEGMENTS
+
+template <bool EMA, bool GROUPS>
 __global__ void adamw_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
                              float* __restrict__ v, const float* __restrict__ state, size_t n, float beta1,
                              float beta2, float eps, float wd, float max_norm, float grad_scale, int zero_grad,
-                             float* __restrict__ ema, float ema_decay, int ema_warmup) {
+                             const long long* __restrict__ seg_end, const float* __restrict__ seg_lr_mult,
+                             const float* __restrict__ seg_wd, int n_seg, float* __restrict__ ema, float ema_decay,
+                             int ema_warmup) {
+    constexpr int LDS_SEGMENTS = GROUPS ? OPT_MAX_SEGMENTS : 1;              // (GROUPS = false: unused, and so not allocated)
+    __shared__ long long s_end[LDS_SEGMENTS];
+    __shared__ float s_decay[LDS_SEGMENTS], s_step[LDS_SEGMENTS];
     const float step = state[0] + 1.f;
     const float lr = state[2];
-    const float gn = sqrtf(sumsq_total(state)) * grad_scale;
-    const float clip = (max_norm > 0.f) ? fminf(1.f, max_norm / (gn + 1e-6f)) : 1.f;
-    const float gs = grad_scale * clip;
+    const float gn = __fmaf_rn(sqrtf(sumsq_total(state)), grad_scale, 1e-6f);
+    const float clip = (max_norm > 0.f) ? fminf(1.f, max_norm / gn) : 1.f;
+    const float gs = __fmul_rn(grad_scale, clip);
     const float bc1 = 1.f - powf(beta1, step), bc2 = 1.f - powf(beta2, step);
-    const float step_size = lr / bc1, inv_sqrt_bc2 = rsqrtf(bc2);
+    const float inv_sqrt_bc2 = rsqrtf(bc2);
+    const float omb1 = 1.f - beta1, omb2 = 1.f - beta2;
     const float one_minus_d = EMA ? 1.f - ema_decay_at(step, ema_decay, ema_warmup) : 0.f;
+    float decay = 0.f, step_size = 0.f;            // GROUPS: looked up per element
+    if (GROUPS) {
+        for (int s = threadIdx.x; s < n_seg; s += blockDim.x) {
+            const float lr_s = __fmul_rn(lr, seg_lr_mult[s]);
+            s_end[s] = seg_end[s];
+            s_decay[s] = __fmaf_rn(-seg_wd[s], lr_s, 1.f);
+            s_step[s] = lr_s / bc1;
+        }
+        __syncthreads();
+    } else {
+        decay = __fmaf_rn(-wd, lr, 1.f);
+        step_size = lr / bc1;
+    }
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        const float gi = g[i] * gs;
-        float pi = p[i] * (1.f - lr * wd);
-        const float mi = beta1 * m[i] + (1.f - beta1) * gi;
-        const float vi = beta2 * v[i] + (1.f - beta2) * gi * gi;
-        pi -= step_size * mi / (sqrtf(vi) * inv_sqrt_bc2 + eps);
+        if (GROUPS) {
+            int lo = 0, hi = n_seg - 1;
+            while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                if ((long long)i < s_end[mid]) hi = mid; else lo = mid + 1;
+            }
+            decay = s_decay[lo]; step_size = s_step[lo];
+        }
+        const float gi = __fmul_rn(g[i], gs);
+        const float mi = __fmaf_rn(omb1, gi, __fmul_rn(beta1, m[i]));
+        const float vi = __fmaf_rn(gi, __fmul_rn(omb2, gi), __fmul_rn(beta2, v[i]));
+        const float q = __fmul_rn(step_size, mi) / __fmaf_rn(inv_sqrt_bc2, sqrtf(vi), eps);
+        const float pi = __fmaf_rn(decay, p[i], -q);
         p[i] = pi; m[i] = mi; v[i] = vi;
         if (zero_grad) g[i] = 0.f;                 // the next step's zero_grad(), for free
         if (EMA) {
@@ -107,92 +152,28 @@ __global__ void adamw_finish_kernel(float* __restrict__ state, float max_norm, f
     state[1] = ss;
 }
 
-// Parameter groups (mm_adamw_clip_groups[_ema]): the bucket is cut into n_seg <= MM_OPT_MAX_SEGMENTS contiguous segments,
-// segment s = [seg_end[s-1], seg_end[s]) with its own learning rate lr_s = fl32(state[2] * seg_lr_mult[s]) and weight decay
-// seg_wd[s].  The table is DEVICE memory read at launch, so a captured launch serves any later change of its values.
-// Contract: an element of segment s gets the bits adamw_kernel<EMA> writes for it when called with the scalars lr = lr_s,
-// wd = seg_wd[s] (step count, norm, clip, zero_grad and the average are the bucket's, as there).  adamw_kernel's
-// expressions are contracted by the compiler; the forms it takes there are WRITTEN OUT here (__fmaf_rn / __fmul_rn), so
-// that this kernel's bits do not depend on what the optimizer makes of a differently shaped loop:
-//     clip    max_norm / fma(sqrt(sumsq), grad_scale, 1e-6)
-//     decay   fma(-wd, lr, 1)                      step_size  lr / bc1
-//     m       fma(1 - b1, g, b1 * m)               v          fma(g, (1 - b2) * g, b2 * v)
-//     p       fma(decay, p, -(step_size * m / fma(rsqrt(bc2), sqrt(v), eps)))
-// (tests/test_adamw_groups_kernels_gpu.py holds the two kernels to each other bit for bit.)
-// Every workgroup stages {end, decay, step_size} of all segments in LDS once (16 bytes a segment, 16 KB at the cap) and
-// finds an element's segment by binary search over the ends: the first s with i < end[s], else the last one - the search
-// runs over [0, n_seg) only, so no element and no table content can form an address outside the table.
-constexpr int OPT_MAX_SEGMENTS = 1024;            // MM_OPT_MAX_SEGMENTS
-
-template <bool EMA>
-__global__ void adamw_groups_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
-                                    float* __restrict__ v, const float* __restrict__ state, size_t n, float beta1,
-                                    float beta2, float eps, float max_norm, float grad_scale, int zero_grad,
-                                    const long long* __restrict__ seg_end, const float* __restrict__ seg_lr_mult,
-                                    const float* __restrict__ seg_wd, int n_seg, float* __restrict__ ema,
-                                    float ema_decay, int ema_warmup) {
-    __shared__ long long s_end[OPT_MAX_SEGMENTS];
-    __shared__ float s_decay[OPT_MAX_SEGMENTS], s_step[OPT_MAX_SEGMENTS];
-    const float step = state[0] + 1.f;
-    const float lr = state[2];
-    const float gn = __fmaf_rn(sqrtf(sumsq_total(state)), grad_scale, 1e-6f);
-    const float clip = (max_norm > 0.f) ? fminf(1.f, max_norm / gn) : 1.f;
-    const float gs = __fmul_rn(grad_scale, clip);
-    const float bc1 = 1.f - powf(beta1, step), bc2 = 1.f - powf(beta2, step);
-    const float inv_sqrt_bc2 = rsqrtf(bc2);
-    const float omb1 = 1.f - beta1, omb2 = 1.f - beta2;
-    const float one_minus_d = EMA ? 1.f - ema_decay_at(step, ema_decay, ema_warmup) : 0.f;
-    for (int s = threadIdx.x; s < n_seg; s += blockDim.x) {
-        const float lr_s = __fmul_rn(lr, seg_lr_mult[s]);
-        s_end[s] = seg_end[s];
-        s_decay[s] = __fmaf_rn(-seg_wd[s], lr_s, 1.f);
-        s_step[s] = lr_s / bc1;
+// The argument checks (nothing is launched when one fails; `who` names the entry point), then the update and the finish
+// kernel.  The table's CONTENTS are device memory: the host that builds it validates them - optim.segment_table.
+template <bool EMA, bool GROUPS>
+int adamw_launch(const char* who, float* p, float* g, float* m, float* v, float* state, int64_t n, float beta1, float beta2,
+                 float eps, float weight_decay, float max_norm, float grad_scale, int zero_grad, uint32_t* seed_epoch,
+                 const int64_t* seg_end, const float* seg_lr_mult, const float* seg_wd, int n_seg, float* ema,
+                 float ema_decay, int ema_warmup, hipStream_t st) {
+    MM_REQUIRE(p && g && m && v && state && n > 0, "%s: null", who);
+    if (GROUPS) {
+        MM_REQUIRE(seg_end && seg_lr_mult && seg_wd, "%s: a segment table array is null", who);
+        MM_REQUIRE(n_seg >= 1 && n_seg <= OPT_MAX_SEGMENTS, "%s: n_seg %d outside [1, %d]", who, n_seg, OPT_MAX_SEGMENTS);
     }
-    __syncthreads();
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        int lo = 0, hi = n_seg - 1;
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if ((long long)i < s_end[mid]) hi = mid; else lo = mid + 1;
-        }
-        const float decay = s_decay[lo], step_size = s_step[lo];
-        const float gi = __fmul_rn(g[i], gs);
-        const float mi = __fmaf_rn(omb1, gi, __fmul_rn(beta1, m[i]));
-        const float vi = __fmaf_rn(gi, __fmul_rn(omb2, gi), __fmul_rn(beta2, v[i]));
-        const float q = __fmul_rn(step_size, mi) / __fmaf_rn(inv_sqrt_bc2, sqrtf(vi), eps);
-        const float pi = __fmaf_rn(decay, p[i], -q);
-        p[i] = pi; m[i] = mi; v[i] = vi;
-        if (zero_grad) g[i] = 0.f;
-        if (EMA) {
-            const float e = ema[i];
-            ema[i] = __fmaf_rn(one_minus_d, __fsub_rn(pi, e), e);
-        }
+    if (EMA) {
+        MM_REQUIRE(ema, "%s: ema is null (the entry point without _ema is the update without a weight average)", who);
+        MM_REQUIRE(ema_decay >= 0.f && ema_decay < 1.f, "%s: ema_decay %g outside [0, 1)", who, (double)ema_decay);
     }
-}
-
-template <bool EMA>
-int adamw_launch(float* p, float* g, float* m, float* v, float* state, int64_t n, float beta1, float beta2, float eps,
-                 float weight_decay, float max_norm, float grad_scale, int zero_grad, uint32_t* seed_epoch, float* ema,
-                 float ema_decay, int ema_warmup, hipStream_t st, const char* what) {
-    hipLaunchKernelGGL(adamw_kernel<EMA>, dim3(grid_for((size_t)n, 2048)), dim3(256), 0, st, p, g, m, v, state, (size_t)n,
-                       beta1, beta2, eps, weight_decay, max_norm, grad_scale, zero_grad, ema, ema_decay, ema_warmup);
+    hipLaunchKernelGGL((adamw_kernel<EMA, GROUPS>), dim3(grid_for((size_t)n, 2048)), dim3(256), 0, st, p, g, m, v, state,
+                       (size_t)n, beta1, beta2, eps, weight_decay, max_norm, grad_scale, zero_grad,
+                       (const long long*)seg_end, seg_lr_mult, seg_wd, n_seg, ema, ema_decay, ema_warmup);
     hipLaunchKernelGGL(adamw_finish_kernel<EMA>, dim3(1), dim3(256), 0, st, state, max_norm, grad_scale, seed_epoch,
                        ema_decay, ema_warmup);
-    return mm_check_launch(what);
-}
-
-// the same two launches with the per-segment update kernel: adamw_finish_kernel is the plain step's
-template <bool EMA>
-int adamw_groups_launch(float* p, float* g, float* m, float* v, float* state, int64_t n, float beta1, float beta2,
-                        float eps, float max_norm, float grad_scale, int zero_grad, uint32_t* seed_epoch,
-                        const int64_t* seg_end, const float* seg_lr_mult, const float* seg_wd, int n_seg, float* ema,
-                        float ema_decay, int ema_warmup, hipStream_t st, const char* what) {
-    hipLaunchKernelGGL(adamw_groups_kernel<EMA>, dim3(grid_for((size_t)n, 2048)), dim3(256), 0, st, p, g, m, v, state,
-                       (size_t)n, beta1, beta2, eps, max_norm, grad_scale, zero_grad, (const long long*)seg_end,
-                       seg_lr_mult, seg_wd, n_seg, ema, ema_decay, ema_warmup);
-    hipLaunchKernelGGL(adamw_finish_kernel<EMA>, dim3(1), dim3(256), 0, st, state, max_norm, grad_scale, seed_epoch,
-                       ema_decay, ema_warmup);
-    return mm_check_launch(what);
+    return mm_check_launch(who);
 }
 }  // namespace
 
@@ -200,46 +181,33 @@ extern "C" {
 int mm_adamw_clip(float* p, float* g, float* m, float* v, float* state, int64_t n, float beta1, float beta2,
                   float eps, float weight_decay, float max_norm, float grad_scale, int zero_grad, uint32_t* seed_epoch,
                   hipStream_t st) {
-    MM_REQUIRE(p && g && m && v && state && n > 0, "adamw_clip: null");
-    return adamw_launch<false>(p, g, m, v, state, n, beta1, beta2, eps, weight_decay, max_norm, grad_scale, zero_grad,
-                               seed_epoch, nullptr, 0.f, 0, st, "adamw_clip");
+    return adamw_launch<false, false>("adamw_clip", p, g, m, v, state, n, beta1, beta2, eps, weight_decay, max_norm,
+                                      grad_scale, zero_grad, seed_epoch, nullptr, nullptr, nullptr, 0, nullptr, 0.f, 0, st);
 }
 
 int mm_adamw_clip_ema(float* p, float* g, float* m, float* v, float* state, int64_t n, float beta1, float beta2,
                       float eps, float weight_decay, float max_norm, float grad_scale, int zero_grad, uint32_t* seed_epoch,
                       float* ema, float ema_decay, int ema_warmup, hipStream_t st) {
-    MM_REQUIRE(p && g && m && v && state && n > 0, "adamw_clip_ema: null");
-    MM_REQUIRE(ema, "adamw_clip_ema: ema is null (mm_adamw_clip is the update without a weight average)");
-    MM_REQUIRE(ema_decay >= 0.f && ema_decay < 1.f, "adamw_clip_ema: ema_decay %g outside [0, 1)", (double)ema_decay);
-    return adamw_launch<true>(p, g, m, v, state, n, beta1, beta2, eps, weight_decay, max_norm, grad_scale, zero_grad,
-                              seed_epoch, ema, ema_decay, ema_warmup, st, "adamw_clip_ema");
+    return adamw_launch<true, false>("adamw_clip_ema", p, g, m, v, state, n, beta1, beta2, eps, weight_decay, max_norm,
+                                     grad_scale, zero_grad, seed_epoch, nullptr, nullptr, nullptr, 0, ema, ema_decay,
+                                     ema_warmup, st);
 }
-
-// (the table's CONTENTS are device memory: the host that builds it validates them - optim.segment_table)
-#define MM_REQUIRE_SEGMENTS(who)                                                                                      \
-    MM_REQUIRE(seg_end && seg_lr_mult && seg_wd, who ": a segment table array is null");                              \
-    MM_REQUIRE(n_seg >= 1 && n_seg <= OPT_MAX_SEGMENTS, who ": n_seg %d outside [1, %d]", n_seg, OPT_MAX_SEGMENTS)
 
 int mm_adamw_clip_groups(float* p, float* g, float* m, float* v, float* state, int64_t n, float beta1, float beta2,
                          float eps, float max_norm, float grad_scale, int zero_grad, uint32_t* seed_epoch,
                          const int64_t* seg_end, const float* seg_lr_mult, const float* seg_wd, int n_seg,
                          hipStream_t st) {
-    MM_REQUIRE(p && g && m && v && state && n > 0, "adamw_clip_groups: null");
-    MM_REQUIRE_SEGMENTS("adamw_clip_groups");
-    return adamw_groups_launch<false>(p, g, m, v, state, n, beta1, beta2, eps, max_norm, grad_scale, zero_grad, seed_epoch,
-                                      seg_end, seg_lr_mult, seg_wd, n_seg, nullptr, 0.f, 0, st, "adamw_clip_groups");
+    return adamw_launch<false, true>("adamw_clip_groups", p, g, m, v, state, n, beta1, beta2, eps, 0.f, max_norm,
+                                     grad_scale, zero_grad, seed_epoch, seg_end, seg_lr_mult, seg_wd, n_seg, nullptr, 0.f,
+                                     0, st);
 }
 
 int mm_adamw_clip_groups_ema(float* p, float* g, float* m, float* v, float* state, int64_t n, float beta1, float beta2,
                              float eps, float max_norm, float grad_scale, int zero_grad, uint32_t* seed_epoch,
                              const int64_t* seg_end, const float* seg_lr_mult, const float* seg_wd, int n_seg,
                              float* ema, float ema_decay, int ema_warmup, hipStream_t st) {
-    MM_REQUIRE(p && g && m && v && state && n > 0, "adamw_clip_groups_ema: null");
-    MM_REQUIRE_SEGMENTS("adamw_clip_groups_ema");
-    MM_REQUIRE(ema, "adamw_clip_groups_ema: ema is null (mm_adamw_clip_groups is the update without a weight average)");
-    MM_REQUIRE(ema_decay >= 0.f && ema_decay < 1.f, "adamw_clip_groups_ema: ema_decay %g outside [0, 1)", (double)ema_decay);
-    return adamw_groups_launch<true>(p, g, m, v, state, n, beta1, beta2, eps, max_norm, grad_scale, zero_grad, seed_epoch,
-                                     seg_end, seg_lr_mult, seg_wd, n_seg, ema, ema_decay, ema_warmup, st,
-                                     "adamw_clip_groups_ema");
+    return adamw_launch<true, true>("adamw_clip_groups_ema", p, g, m, v, state, n, beta1, beta2, eps, 0.f, max_norm,
+                                    grad_scale, zero_grad, seed_epoch, seg_end, seg_lr_mult, seg_wd, n_seg, ema, ema_decay,
+                                    ema_warmup, st);
 }
 }  // extern "C"

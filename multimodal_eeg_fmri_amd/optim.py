@@ -1,7 +1,8 @@
-"""Flat parameter bucket + fused clip/AdamW (``mm_sumsq`` + ``mm_adamw_clip``, or ``mm_adamw_clip_ema`` when an
-exponential moving average of the weights is kept: same launch, one more read and one more write stream; with parameter
-groups - learning-rate multipliers and weight decays per segment of the bucket, `segment_table` - ``mm_adamw_clip_groups``
-/ ``mm_adamw_clip_groups_ema``).
+"""Flat parameter bucket + fused clip/AdamW.  `adamw_update` is the one host call of a step, for `FusedAdamW` and the
+bridge trainer alike: ``mm_sumsq`` + ``mm_adamw_clip``, or ``mm_adamw_clip_ema`` when an exponential moving average of the
+weights is kept (same launch, one more read and one more write stream); with parameter groups - learning-rate multipliers
+and weight decays per segment of the bucket, `segment_table` - ``mm_adamw_clip_groups`` / ``mm_adamw_clip_groups_ema``.
+The four entry points are instances of one kernel body.
 
 Replaces the reference's ``clip_grad_norm_(max_norm=1.0)`` + ``torch.optim.AdamW.step()``
 pair (run_training_lite.py:487-488, _test_bridge.py:784-786) with two kernel
@@ -98,15 +99,18 @@ class SegmentTable:
             devt.copy_(torch.tensor(host, dtype=torch.float32))
 
 
-def adamw_clip_groups(b, table, betas, eps, max_norm, grad_scale, zero_grad, seed_epoch, ema_decay=0.0, ema_warmup=True):
-    """the update launch of a step with parameter groups on FlatBucket ``b`` (after ``mm_sumsq``): SegmentTable
-    ``table`` in place of the scalar weight decay; with ``b.ema`` the weight average rides along, as in the plain step"""
-    args = (b.p, b.g, b.m, b.v, b.state, b.n, betas[0], betas[1], eps, float(max_norm), float(grad_scale),
-            int(zero_grad), seed_epoch, table.end, table.mult, table.wd, table.n_seg)
-    if b.ema is None:
-        _hip.call("mm_adamw_clip_groups", *args)
-    else:
-        _hip.call("mm_adamw_clip_groups_ema", *args, b.ema, float(ema_decay), int(ema_warmup))
+def adamw_update(b, betas, eps, max_norm, grad_scale, zero_grad, seed_epoch, decay, ema_decay=0.0, ema_warmup=True):
+    """The two launches of a step on FlatBucket ``b``: ``mm_sumsq``, then the one matching entry point of the update
+    kernel.  ``decay``: a scalar weight decay (``mm_adamw_clip``) or a SegmentTable in its place (``mm_adamw_clip_groups``);
+    ``_ema`` - the weight average rides along in the same launch - exactly when ``b.ema`` exists."""
+    _hip.call("mm_sumsq", b.g, b.state, b.n)
+    grouped, averaged = isinstance(decay, SegmentTable), b.ema is not None
+    args = [b.p, b.g, b.m, b.v, b.state, b.n, betas[0], betas[1], eps]
+    args += [] if grouped else [float(decay)]
+    args += [float(max_norm), float(grad_scale), int(zero_grad), seed_epoch]
+    args += [decay.end, decay.mult, decay.wd, decay.n_seg] if grouped else []
+    args += [b.ema, float(ema_decay), int(ema_warmup)] if averaged else []
+    _hip.call("mm_adamw_clip" + "_groups" * grouped + "_ema" * averaged, *args)
 
 
 class FlatBucket:
@@ -234,21 +238,14 @@ class FusedAdamW:
         if self._averaged:
             raise RuntimeError("FusedAdamW.step inside averaged(): the parameters hold the averaged weights")
         ends, mults, wds = self._host_table()     # (read every step: the groups' values may be changed between steps)
-        _hip.call("mm_sumsq", b.g, b.state, b.n)
+        decay = wds[0]                            # one segment of multiplier 1: the plain kernel
         if not (len(ends) == 1 and mults[0] == 1.0):
-            t = self._table
-            if t is None or t.ends != ends:
-                t = self._table = SegmentTable(ends, mults, wds, b.p.device)
-            elif (t.mults, t.wds) != (mults, wds):
-                t.write(mults, wds)
-            adamw_clip_groups(b, t, self.betas, self.eps, self.max_grad_norm, 1.0, 0, None, self.ema_decay, self.ema_warmup)
-        elif b.ema is None:
-            _hip.call("mm_adamw_clip", b.p, b.g, b.m, b.v, b.state, b.n, self.betas[0], self.betas[1],
-                      self.eps, wds[0], float(self.max_grad_norm), 1.0, 0, None)
-        else:
-            _hip.call("mm_adamw_clip_ema", b.p, b.g, b.m, b.v, b.state, b.n, self.betas[0], self.betas[1],
-                      self.eps, wds[0], float(self.max_grad_norm), 1.0, 0, None,
-                      b.ema, self.ema_decay, int(self.ema_warmup))
+            decay = self._table
+            if decay is None or decay.ends != ends:
+                decay = self._table = SegmentTable(ends, mults, wds, b.p.device)
+            elif (decay.mults, decay.wds) != (mults, wds):
+                decay.write(mults, wds)
+        adamw_update(b, self.betas, self.eps, self.max_grad_norm, 1.0, 0, None, decay, self.ema_decay, self.ema_warmup)
         ops.weights_changed()
 
     # -- averaged weights

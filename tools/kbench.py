@@ -555,7 +555,7 @@ def ema_case(step_iters=30, rounds=5):
           f"({s1 - s0:+.1f} us, {100 * (s1 / s0 - 1):+.2f} %)")
 
 
-def groups_case(step_iters=30, rounds=5):
+def param_groups_case(step_iters=30, rounds=5):
     """parameter groups in the update kernel, at the default C2 trainer's bucket size, graph-replayed launches in the same
     run, interleaved rounds: mm_adamw_clip against mm_adamw_clip_groups with 1, 8 and ~200 segments (the same 8 streams over
     the bucket; the difference is the staging of the table in LDS and the per-element search); then the C2 graph step
@@ -1211,8 +1211,8 @@ def main():
     if flt == "ema":
         ema_case()
         return
-    if flt == "groups":
-        groups_case()
+    if flt == "pgroups":
+        param_groups_case()
         return
     if flt == "tabfmri":
         tabfmri_case()
