@@ -412,6 +412,28 @@ int mm_eeg_augment_plan(const float* x, uint32_t* plan, int64_t plan_words, int 
 int mm_stage_inputs_aug(const float* eeg, uint32_t* plan, int64_t plan_words, void* eeg_packed_bf16, float* eeg_out_f32,
                         int B, int C, int T, int Cp, float noise_factor, uint32_t s_gauss_a, uint32_t s_gauss_b,
                         float* fmri_dst, const float* fmri_src, int64_t fmri_n, hipStream_t stream);
+/* mm_stage_inputs_aug with the temporal EEG transforms (the reference has none): per sample an integer time
+ * shift s_b in [-max_shift, max_shift] (out[t] = x[t - s_b], +0 where there is no source - and no noise there), a gain
+ * g_b = (invert ? -1 : 1) * (1 + scale_range * (2u - 1)) and one window of mask_len samples set to +0 on every channel.
+ * The seven per-sample draws h(stream_k, b) (decision / amount of the shift, decision / u of the scale, the inversion,
+ * decision / start of the mask: purposes 19..25 of csrc/augment.hip's stream) are recomputed by every tile workgroup, so
+ * the time transforms need no plan launch:
+ *   plan == NULL   time transforms alone, ONE launch (plan_words, noise_factor, s_gauss_* are not read)
+ *   plan != NULL   a plan mm_eeg_augment_plan has written for the same batch: its noise (indexed by the OUTPUT position,
+ *                  scaled by the original sample's std_b) goes onto the gathered value before the gain, its dropped
+ *                  channels are +0.
+ * time_plan (nullable): 8 int32 words per sample - [0] flags (bit 0 shift, 1 scale, 2 invert, 3 mask), [1] s_b, [2] g_b
+ * (fp32 bits; 1.0f when neither scale nor invert is on), [3] mask start, [4] mask length (0 when off), [5..7] 0.
+ * With every time probability 0 the outputs are mm_stage_inputs_aug's (plan) / mm_stage_inputs' (no plan) bit for bit.
+ * Refused before any launch: a probability outside [0, 1], max_shift outside [0, T), scale_range outside [0, 1), mask_len
+ * outside [1, T], the batch and eeg_out_f32 overlapping (the shift is a gather), and - with a plan - what
+ * mm_stage_inputs_aug refuses. */
+int mm_stage_inputs_taug(const float* eeg, uint32_t* plan, int64_t plan_words, void* eeg_packed_bf16, float* eeg_out_f32,
+                         int B, int C, int T, int Cp, float noise_factor, uint32_t s_gauss_a, uint32_t s_gauss_b,
+                         float p_shift, int max_shift, float p_scale, float scale_range, float p_invert, float p_mask,
+                         int mask_len, uint32_t s_shift, uint32_t s_shift_amt, uint32_t s_scale, uint32_t s_scale_u,
+                         uint32_t s_invert, uint32_t s_mask, uint32_t s_mask_start, int32_t* time_plan, float* fmri_dst,
+                         const float* fmri_src, int64_t fmri_n, hipStream_t stream);
 /* fMRI volume augmentation in front of a training step (the reference has no volume code: the transform is defined in
  * DESIGN.md 5q and csrc/volume_augment.hip): per sample of a (B, 1, D, H, W) fp32 batch, each with its own probability, a
  * mirror of the W axis, an integer shift (dz, dy, dx) in [-max_shift, max_shift]^3, a scale by 1 + scale_range * (2u - 1),

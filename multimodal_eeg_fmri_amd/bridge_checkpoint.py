@@ -11,7 +11,8 @@ The file is the container of the reference's loops and of `FlexibleTrainer.save_
 * ``bridge_trainer_state``: the optimizer words (step count, lr, ...), the hyperparameters, the EEG branch kind, the
   model's shapes, the head count of every transformer block, the world size, the bucket layout, the dropout stream,
   the state of `fit`, - only for a trainer with an augmenter - ``augment``: its parameters and the step index
-  (``fmri_augment``: the same for a volume augmenter), -
+  (``fmri_augment``: the same for a volume augmenter; ``eeg_time_augment``: for a temporal EEG augmenter, whose step index
+  is ``augment``'s), -
   only for a trainer of the pairwise sigmoid loss - ``loss`` = ``"sigmoid"`` (absent: InfoNCE), and - only for a trainer
   built with ``classify=True`` - ``classify`` = ``{ce_weight, num_classes, class_weight}``, and - only for a trainer with
   a cross-batch memory (``bank_size > 0``) - ``bank`` = ``{size, warmup, grouped, state, rows, ids}``: the ring's words,
@@ -194,6 +195,8 @@ class TrainerCheckpointMixin:
         bts.update(self._layout())
         if getattr(self, "augment", None) is not None:             # (absent without an augmenter: the container is unchanged)
             bts["augment"] = dict(self.augment.params(), step=int(self._aug_step))
+        if getattr(self, "eeg_time_augment", None) is not None:    # (absent without a temporal augmenter; the step index is `augment`'s)
+            bts["eeg_time_augment"] = dict(self.eeg_time_augment.params(), step=int(self._aug_step))
         if getattr(self, "fmri_augment", None) is not None:        # (absent without a volume augmenter: the container is unchanged)
             bts["fmri_augment"] = dict(self.fmri_augment.params(), step=int(self._fmri_aug_step))
         if getattr(self, "loss", "infonce") != "infonce":          # (absent for the default loss: the container is unchanged)
@@ -301,6 +304,18 @@ class TrainerCheckpointMixin:
             mine_aug = aug.params()
             if {k: theirs_aug.get(k) for k in mine_aug} != mine_aug:
                 raise ValueError(f"load_checkpoint_state: augment differs: checkpoint {theirs_aug!r}, trainer {mine_aug!r}")
+        taug, theirs_taug = getattr(self, "eeg_time_augment", None), bts.get("eeg_time_augment")
+        if (taug is None) != (theirs_taug is None):
+            raise ValueError(f"load_checkpoint_state: eeg_time_augment differs: the checkpoint was written "
+                             f"{'with' if theirs_taug is not None else 'without'} a temporal augmenter, this trainer has "
+                             f"{'none' if taug is None else 'one'}")
+        if taug is not None:
+            mine_taug = taug.params()
+            if {k: theirs_taug.get(k) for k in mine_taug} != mine_taug:
+                raise ValueError(f"load_checkpoint_state: eeg_time_augment differs: checkpoint {theirs_taug!r}, trainer {mine_taug!r}")
+        if aug is not None and taug is not None and int(theirs_aug["step"]) != int(theirs_taug["step"]):
+            raise ValueError(f"load_checkpoint_state: eeg_time_augment differs: the two EEG augmenters share one step index, the "
+                             f"checkpoint holds {theirs_aug['step']!r} and {theirs_taug['step']!r}")
         vaug, theirs_vaug = getattr(self, "fmri_augment", None), bts.get("fmri_augment")
         if (vaug is None) != (theirs_vaug is None):
             raise ValueError(f"load_checkpoint_state: fmri_augment differs: the checkpoint was written "
@@ -369,6 +384,8 @@ class TrainerCheckpointMixin:
         self._pending_epoch_word = d["epoch_word"] if d["kind"] == "graph" else None
         if "augment" in bts:
             self._aug_step = int(bts["augment"]["step"])
+        if "eeg_time_augment" in bts:                              # (one counter for both EEG augmenters: checked equal above)
+            self._aug_step = int(bts["eeg_time_augment"]["step"])
         if "fmri_augment" in bts:
             self._fmri_aug_step = int(bts["fmri_augment"]["step"])
         if "bank" in bts:

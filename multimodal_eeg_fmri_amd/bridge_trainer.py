@@ -50,7 +50,8 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
                  num_heads: int = 4, num_layers: int = 2, augment=None, loss: str = "infonce",
                  classify: bool = False, ce_weight: float = 1.0, class_weight=None, num_classes: int = 2,
                  fmri_encoder: Optional[nn.Module] = None, bank_size: int = 0, bank_warmup: int = 0, fmri_augment=None,
-                 ema_decay: float = 0.0, ema_warmup: bool = True, lr_scale=None, no_decay: bool = False, freeze=()):
+                 ema_decay: float = 0.0, ema_warmup: bool = True, lr_scale=None, no_decay: bool = False, freeze=(),
+                 eeg_time_augment=None):
         """``eeg_encoder``: the EEG branch when it is not the default ``EnhancedERPEncoder(eeg_channels, hidden_dim,
         num_layers, num_heads, dropout)`` - an ``EnhancedPowerEncoder`` (enhanced_models_v4.py:196-285) or a
         ``MultiScaleSTFTPowerEncoder`` (BASELINE config #5: raw EEG -> multi-scale STFT power -> a4); it must end in
@@ -114,7 +115,12 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
         ``eval()`` of a pretrained encoder.  The component's parameters leave the bucket, its forward runs in eval form
         inside the step (frozen BatchNorm, no dropout seed drawn, nothing updated), and its backward is not issued in
         any mode.  Fixed at construction; ``"head"`` cannot be frozen (ValueError); one process only
-        (NotImplementedError at world size > 1)."""
+        (NotImplementedError at world size > 1).
+        ``eeg_time_augment``: an ``EEGTimeTransforms`` (crossmodal_eeg_scr.py) - every `train_step` then shifts, scales,
+        inverts and masks its EEG batch along the time axis on the device (mm_stage_inputs_taug).
+        Alone it replaces the step's one staging launch by one launch; together with ``augment=`` the two share the
+        staging launch (after the plan launch) and therefore the step index (`augment_step`).  The entry points that never
+        augment never shift either.  None (default): the step issues the launches it always did."""
         super().__init__()
         self._frozen = self._check_freeze(freeze, group)
         self._lr_scale = self._check_lr_scale(lr_scale)
@@ -165,7 +171,12 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
             if not isinstance(augment, EEGTransforms):
                 raise TypeError(f"BridgeTrainer: augment must be an EEGTransforms (got {type(augment).__name__})")
         self.augment = augment
-        self._aug_step = 0                            # step index the next train_step's augmentation draws with
+        if eeg_time_augment is not None:
+            from .crossmodal_eeg_scr import EEGTimeTransforms
+            if not isinstance(eeg_time_augment, EEGTimeTransforms):
+                raise TypeError(f"BridgeTrainer: eeg_time_augment must be an EEGTimeTransforms (got {type(eeg_time_augment).__name__})")
+        self.eeg_time_augment = eeg_time_augment
+        self._aug_step = 0                            # step index the next train_step's EEG augmentation draws with (both augmenters)
         if fmri_augment is not None:
             from .fmri_utils import VolumeTransforms
             if not isinstance(fmri_augment, VolumeTransforms):
@@ -498,10 +509,12 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
         if lab is not None and self._cls_ticket is None:       # this trainer's own word, allocated before any capture
             self._cls_ticket = torch.zeros(1, dtype=torch.int32, device=self._scal.device)
         aug_step = None
-        if self.augment is not None:                       # one step index per call, whatever the mode
+        if self.augment is not None or self.eeg_time_augment is not None:    # one step index per call, whatever the mode
+            if self.eeg_time_augment is not None:
+                self.eeg_time_augment.check(eeg.shape, self.augment, "train_step (eeg_time_augment)")
             aug_step, self._aug_step = self._aug_step, self._aug_step + 1
             if self.mode != "graph":
-                eeg = self.augment.batch(eeg, aug_step, dp.rank(self.group))
+                eeg = self._augment_eeg(eeg, aug_step)
         fmri_aug_step = None
         if self.fmri_augment is not None:                  # a counter of its own: one step index per call, whatever the mode
             self.fmri_augment.check(fmri.shape, "train_step (fmri_augment)")
@@ -1030,6 +1043,12 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
         with torch.cuda.stream(self._side):
             dp.all_gather_into(c["gid_all"].view(-1, 1), c["gid"].view(-1, 1), self.group)
 
+    def _augment_eeg(self, eeg, aug_step):
+        """the augmented copy of an EEG batch at step index ``aug_step``: both EEG augmenters in one pass when both exist"""
+        if self.eeg_time_augment is not None:
+            return self.eeg_time_augment.batch(eeg, aug_step, dp.rank(self.group), base=self.augment)
+        return self.augment.batch(eeg, aug_step, dp.rank(self.group))
+
     def _step_graph(self, eeg, fmri, gid=None, aug_step=None, lab=None, fmri_aug_step=None):
         """``aug_step`` / ``fmri_aug_step``: the step index of the EEG / volume augmentation (trainers with that augmenter).
         The capture and its two warm-up steps see the batch as it came; what a replay reads is staged below, augmented."""
@@ -1048,9 +1067,9 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
             # the augmented volumes go straight into the static buffer; the EEG batch is then staged without the fMRI copy
             self._stage_fmri_augmented(c, fmri, fmri_aug_step)
             if aug_step is None or not self._stage_augmented(c, eeg, c["fmri"], aug_step):
-                self._stage_eeg(c, eeg if aug_step is None else self.augment.batch(eeg, aug_step, dp.rank(self.group)))
+                self._stage_eeg(c, eeg if aug_step is None else self._augment_f32(c, eeg, aug_step))
         elif aug_step is None or not self._stage_augmented(c, eeg, fmri, aug_step):
-            self._stage_inputs(c, eeg if aug_step is None else self.augment.batch(eeg, aug_step, dp.rank(self.group)), fmri)
+            self._stage_inputs(c, eeg if aug_step is None else self._augment_f32(c, eeg, aug_step), fmri)
         if gid is not None and gid.data_ptr() != c["gid"].data_ptr():
             c["gid"].copy_(gid)
         if lab is not None and lab.data_ptr() != c["lab"].data_ptr():
@@ -1114,12 +1133,34 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
         cf = fmri.data_ptr() != c["fmri"].data_ptr()
         fuse = (cf and fmri.dtype == torch.float32 and fmri.is_cuda and fmri.is_contiguous() and fmri.numel() % 4 == 0
                 and fmri.data_ptr() % 16 == 0)
-        c["aug_plan"] = ops.eeg_augment_into(eeg, c["xb"], None, step=aug_step, rank=dp.rank(self.group),
-                                             fmri_dst=c["fmri"] if fuse else None, fmri_src=fmri if fuse else None,
-                                             plan=c.get("aug_plan"), **self.augment.kernel_args(eeg.shape[1]))
+        kw = dict(step=aug_step, rank=dp.rank(self.group), fmri_dst=c["fmri"] if fuse else None, fmri_src=fmri if fuse else None,
+                  plan=c.get("aug_plan"))
+        if self.eeg_time_augment is not None:             # ONE launch without `augment=`: the time draws need no plan
+            c["aug_plan"] = ops.eeg_time_augment_into(eeg, c["xb"], None, time_args=self.eeg_time_augment.kernel_args(eeg.shape[2]),
+                                                      base_args=self.augment.kernel_args(eeg.shape[1]) if self.augment is not None else None,
+                                                      **kw)
+        else:
+            c["aug_plan"] = ops.eeg_augment_into(eeg, c["xb"], None, **kw, **self.augment.kernel_args(eeg.shape[1]))
         if cf and not fuse:
             c["fmri"].copy_(fmri)
         return True
+
+    def _augment_f32(self, c, eeg, aug_step):
+        """the augmented fp32 batch of a step that cannot write the packed operand directly.  The time transforms gather, so
+        they never run in place: a contiguous fp32 device batch - the static `c["eeg"]` of an in-place loader included - is
+        augmented into a scratch tensor kept with the capture (no allocation per step); anything else goes through `batch`"""
+        if self.eeg_time_augment is None or eeg.dtype != torch.float32 or not eeg.is_cuda or not eeg.is_contiguous():
+            return self._augment_eeg(eeg, aug_step)
+        dst = c["eeg"]
+        if ops._overlap(eeg, dst):
+            if c.get("eeg_scratch") is None:
+                c["eeg_scratch"] = torch.empty(c["eeg"].shape, dtype=torch.float32, device=c["eeg"].device)
+            dst = c["eeg_scratch"]
+        c["aug_plan"] = ops.eeg_time_augment_into(eeg, None, dst, step=aug_step, rank=dp.rank(self.group),
+                                                  time_args=self.eeg_time_augment.kernel_args(eeg.shape[2]),
+                                                  base_args=self.augment.kernel_args(eeg.shape[1]) if self.augment is not None else None,
+                                                  plan=c.get("aug_plan"))
+        return dst
 
     def _replay(self):
         c = self._cap
@@ -1199,6 +1240,10 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
             raise ValueError(f"{who}: this trainer has an augmenter, and a batch that is already packed to bf16 on the host "
                              "cannot be augmented after the fact (the noise scale needs the fp32 sample); feed "
                              "train_step(eeg, fmri) from device tensors, or build the trainer without augment=")
+        if self.eeg_time_augment is not None:
+            raise ValueError(f"{who}: this trainer has a temporal EEG augmenter, and a batch that is already packed to bf16 on "
+                             "the host cannot be augmented after the fact (the shift gathers from the fp32 sample); feed "
+                             "train_step(eeg, fmri) from device tensors, or build the trainer without eeg_time_augment=")
         if self.fmri_augment is not None:
             raise ValueError(f"{who}: this trainer has a volume augmenter, and the packed path copies the host's bytes straight "
                              "into the static inputs the volume augmentation writes (one copy, no launch that could augment); "

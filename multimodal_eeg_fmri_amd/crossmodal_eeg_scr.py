@@ -272,16 +272,17 @@ class EEGTransforms:
             return ops.eeg_augment(x, step=step, rank=rank, **self.kernel_args(x.shape[1]))
         return self._batch_cpu(x, step, rank)
 
-    def _batch_cpu(self, x: torch.Tensor, step: int, rank: int) -> torch.Tensor:
-        B, C, T = x.shape
+    def _fields_cpu(self, a: np.ndarray, step: int, rank: int):
+        """the draws of a step for the fp32 batch ``a`` (B, C, T), in numpy -> (noise scale fp32 (B,): noise_factor * std_b,
+        0 where the noise is off; z fp64 (B, C, T): the unit Gaussian field, None when no sample takes noise; dropped bool
+        (B, C))"""
+        B, C, T = a.shape
         n_drop = self.n_drop(C)
-        ops.eeg_augment_check(B, C, T, n_drop, "EEGTransforms")
-        a = x.detach().to(torch.float32).contiguous().numpy()
         s = ops.augment_streams(self.seed, step, rank)
         b = np.arange(B, dtype=np.uint64)
         noise_on = _aug_hash(s[0], b) < np.uint64(_aug_thresh(self.p_noise))
         drop_on = _aug_hash(s[1], b) < np.uint64(_aug_thresh(self.p_drop))
-        out = a.copy()
+        scale, z = np.zeros(B, dtype=np.float32), None
         if noise_on.any():
             std = a.astype(np.float64).std(axis=(1, 2), ddof=1).astype(np.float32)
             scale = np.where(noise_on, np.float32(self.noise_factor) * std, np.float32(0)).astype(np.float32)
@@ -291,14 +292,25 @@ class EEGTransforms:
             u2 = _aug_hash(s[4], idx).astype(np.float64) * 2.0 ** -32
             r = np.sqrt(-2.0 * np.log(u1))
             z = np.stack([r * np.cos(2.0 * np.pi * u2), r * np.sin(2.0 * np.pi * u2)], axis=-1).reshape(B, C, 2 * half)[:, :, :T]
-            noisy = (a.astype(np.float64) + z * scale.astype(np.float64)[:, None, None]).astype(np.float32)
-            out = np.where((scale != 0)[:, None, None], noisy, a)
+        dropped = np.zeros((B, C), dtype=bool)
         if drop_on.any():
             keys = _aug_hash(s[2], np.arange(B * C, dtype=np.uint64)).reshape(B, C)
             order = np.argsort(keys, axis=1, kind="stable")          # ties by channel index
             ranks = np.empty_like(order)
             np.put_along_axis(ranks, order, np.broadcast_to(np.arange(C), (B, C)), axis=1)
-            out[drop_on[:, None] & (ranks < n_drop)] = 0.0
+            dropped = drop_on[:, None] & (ranks < n_drop)
+        return scale, z, dropped
+
+    def _batch_cpu(self, x: torch.Tensor, step: int, rank: int) -> torch.Tensor:
+        B, C, T = x.shape
+        ops.eeg_augment_check(B, C, T, self.n_drop(C), "EEGTransforms")
+        a = x.detach().to(torch.float32).contiguous().numpy()
+        scale, z, dropped = self._fields_cpu(a, step, rank)
+        out = a.copy()
+        if z is not None:
+            noisy = (a.astype(np.float64) + z * scale.astype(np.float64)[:, None, None]).astype(np.float32)
+            out = np.where((scale != 0)[:, None, None], noisy, a)
+        out[dropped] = 0.0
         return torch.from_numpy(np.ascontiguousarray(out)).to(x.dtype)
 
     def __call__(self, x: torch.Tensor) -> torch.Tensor:
@@ -308,6 +320,124 @@ class EEGTransforms:
             raise ValueError(f"EEGTransforms: expected a (channels, ...) sample, got shape {tuple(x.shape)}")
         step, self.calls = self.calls, self.calls + 1
         return self.batch(x.reshape(1, x.shape[0], -1), step).reshape(x.shape)
+
+    def state_dict(self) -> dict:
+        return {"seed": self.seed, "calls": self.calls}
+
+    def load_state_dict(self, sd: dict) -> None:
+        self.seed, self.calls = int(sd["seed"]), int(sd["calls"])
+
+
+class EEGTimeTransforms:
+    """Temporal augmenter of (B, C, T) EEG batches (this package's own; the reference has none - DESIGN.md 5u).  Per sample,
+    each with its own probability: an integer time shift ``s`` in ``[-max_shift, max_shift]`` (``out[t] = x[t - s]``,
+    zeros where there is no source), an amplitude scale by ``1 + scale_range * (2u - 1)``, a polarity inversion, and one
+    window of ``max(1, int(mask_fraction * T))`` samples zeroed on every channel.  A probability of 0 or 1 is valid.
+
+    The random stream is csrc/augment.hip's on purposes of its own (``ops.eeg_time_augment_streams``), a pure function of
+    (seed, step, rank, sample).  ``batch`` on a device tensor is ONE HIP launch (mm_stage_inputs_taug), on a CPU tensor the
+    same stream in numpy - the same decisions, shifts, gains and windows.  With ``base=`` an ``EEGTransforms`` its noise
+    and channel drop ride in the same launch: the noise is indexed by the output position and scaled by the original
+    sample's standard deviation, and an element without a source takes none.  `BridgeTrainer(eeg_time_augment=)`
+    augments each training step's EEG batch on the device; ``__call__`` is the per-sample dataset form."""
+
+    def __init__(self, p_shift: float = 0.5, max_shift: int = 16, p_scale: float = 0.3, scale_range: float = 0.1,
+                 p_invert: float = 0.0, p_mask: float = 0.3, mask_fraction: float = 0.1, seed: int = 0):
+        real = lambda v: isinstance(v, numbers.Real) and not isinstance(v, bool)  # noqa: E731
+        for name, v in (("p_shift", p_shift), ("p_scale", p_scale), ("p_invert", p_invert), ("p_mask", p_mask)):
+            if not (real(v) and 0.0 <= v <= 1.0):
+                raise ValueError(f"EEGTimeTransforms: {name} must lie in [0, 1] (got {v!r})")
+        if not (isinstance(max_shift, numbers.Integral) and not isinstance(max_shift, bool) and max_shift >= 0):
+            raise ValueError(f"EEGTimeTransforms: max_shift must be an integer >= 0 (got {max_shift!r})")
+        if not (real(scale_range) and 0.0 <= scale_range < 1.0):
+            raise ValueError(f"EEGTimeTransforms: scale_range must lie in [0, 1) (got {scale_range!r})")
+        if not (real(mask_fraction) and 0.0 < mask_fraction <= 1.0):
+            raise ValueError(f"EEGTimeTransforms: mask_fraction must lie in (0, 1] (got {mask_fraction!r})")
+        self.p_shift, self.p_scale, self.p_invert, self.p_mask = p_shift, p_scale, p_invert, p_mask
+        self.max_shift, self.scale_range, self.mask_fraction, self.seed = int(max_shift), scale_range, mask_fraction, int(seed)
+        self.calls = 0
+
+    def mask_len(self, T: int) -> int:
+        return max(1, int(self.mask_fraction * T))
+
+    def params(self) -> dict:
+        """what two augmenters must share to draw the same stream (the trainer's checkpoint carries it)"""
+        return {"seed": self.seed, "p_shift": float(self.p_shift), "max_shift": self.max_shift, "p_scale": float(self.p_scale),
+                "scale_range": float(self.scale_range), "p_invert": float(self.p_invert), "p_mask": float(self.p_mask),
+                "mask_fraction": float(self.mask_fraction)}
+
+    def kernel_args(self, T: int) -> dict:
+        """``time_args`` of ``ops.eeg_time_augment`` for epochs of ``T`` samples (which size the masked window)"""
+        kw = self.params()
+        del kw["mask_fraction"]
+        kw["mask_len"] = self.mask_len(T)
+        return kw
+
+    def check(self, shape, base: Optional[EEGTransforms] = None, who: str = "EEGTimeTransforms") -> dict:
+        """``ops.eeg_time_augment_check`` of a (B, C, T) batch under this augmenter's settings, with ``base`` riding along
+        (``ValueError`` before anything runs) -> `kernel_args(T)`"""
+        B, C, T = (int(v) for v in shape)
+        kw = self.kernel_args(T)
+        ops.eeg_time_augment_check(B, C, T, n_drop=None if base is None else base.n_drop(C), who=who,
+                                   **{k: v for k, v in kw.items() if k != "seed"})
+        return kw
+
+    def batch(self, x: torch.Tensor, step: int, rank: int = 0, base: Optional[EEGTransforms] = None) -> torch.Tensor:
+        """the augmented copy of a (B, C, T) batch at step index ``step`` on rank ``rank``; ``base``: an ``EEGTransforms``
+        whose noise and channel drop (drawn at the same step index) go into the same pass"""
+        if x.dim() != 3:
+            raise ValueError(f"EEGTimeTransforms.batch: expected a (B, C, T) batch, got shape {tuple(x.shape)}")
+        if base is not None and not isinstance(base, EEGTransforms):
+            raise TypeError(f"EEGTimeTransforms.batch: base must be an EEGTransforms (got {type(base).__name__})")
+        kw = self.check(x.shape, base)
+        if x.is_cuda:
+            return ops.eeg_time_augment(x, time_args=kw, base_args=None if base is None else base.kernel_args(x.shape[1]),
+                                        step=step, rank=rank).to(x.dtype)
+        return self._batch_cpu(x, step, rank, base)
+
+    def draws(self, B: int, T: int, step: int, rank: int = 0) -> dict:
+        """the per-sample draws of a step, on the host (numpy; what mm_stage_inputs_taug writes into its time plan):
+        {"flags": {shift, scale, invert, mask: bool (B,)}, "shift": int (B,), "gain": fp32 (B,), "mask_start": int (B,),
+        "mask_len": int (B,) (0 when off)}"""
+        s = dict(zip(ops.EEG_TIME_AUG_PURPOSES, ops.eeg_time_augment_streams(self.seed, step, rank)))
+        b = np.arange(B, dtype=np.uint64)
+        draw = lambda name: _aug_hash(s[name], b)  # noqa: E731
+        uniform = lambda name, n: ((draw(name) * np.uint64(n)) >> np.uint64(32)).astype(np.int64)  # noqa: E731
+        flags = {k: draw(k + "_decision") < np.uint64(_aug_thresh(getattr(self, "p_" + k))) for k in ops.EEG_TIME_AUG_FLAGS}
+        shift = (uniform("shift_amount", 2 * self.max_shift + 1) - self.max_shift) * flags["shift"]
+        u = draw("scale_u").astype(np.float64) * 2.0 ** -31 - 1.0
+        factor = np.where(flags["scale"], 1.0 + float(np.float32(self.scale_range)) * u, 1.0).astype(np.float32)
+        gain = np.where(flags["invert"], -factor, factor).astype(np.float32)
+        L = self.mask_len(T)
+        return {"flags": flags, "shift": shift, "gain": gain, "mask_start": uniform("mask_start", T - L + 1) * flags["mask"],
+                "mask_len": L * flags["mask"].astype(np.int64)}
+
+    def _batch_cpu(self, x: torch.Tensor, step: int, rank: int, base: Optional[EEGTransforms]) -> torch.Tensor:
+        B, C, T = x.shape
+        a = x.detach().to(torch.float32).contiguous().numpy()
+        d = self.draws(B, T, step, rank)
+        scale, z, dropped = (np.zeros(B, dtype=np.float32), None, np.zeros((B, C), dtype=bool)) if base is None \
+            else base._fields_cpu(a, step, rank)
+        out = np.zeros_like(a)
+        for b in range(B):
+            sh = int(d["shift"][b])
+            dst, frm = slice(max(sh, 0), T + min(sh, 0)), slice(max(-sh, 0), T + min(-sh, 0))   # out[t] = x[t - sh]
+            v = a[b, :, frm]
+            if scale[b] != 0:                                     # the noise field sits at the OUTPUT positions
+                v = (v.astype(np.float64) + z[b, :, dst] * float(scale[b])).astype(np.float32)
+            if d["flags"]["scale"][b] or d["flags"]["invert"][b]:
+                v = v * d["gain"][b]                              # (one fp32 product)
+            out[b, :, dst] = v
+            out[b, dropped[b], :] = 0.0
+            out[b, :, int(d["mask_start"][b]):int(d["mask_start"][b]) + int(d["mask_len"][b])] = 0.0
+        return torch.from_numpy(np.ascontiguousarray(out)).to(x.dtype)
+
+    def __call__(self, x: torch.Tensor) -> torch.Tensor:
+        """the per-sample dataset form: one (C, T) epoch -> a new tensor; the call counter is the step index"""
+        if x.dim() != 2:
+            raise ValueError(f"EEGTimeTransforms: expected a (C, T) sample, got shape {tuple(x.shape)}")
+        step, self.calls = self.calls, self.calls + 1
+        return self.batch(x.reshape(1, *x.shape), step).reshape(x.shape)
 
     def state_dict(self) -> dict:
         return {"seed": self.seed, "calls": self.calls}

@@ -150,15 +150,50 @@ __global__ void __launch_bounds__(256) eeg_augment_plan_kernel(PlanArgs a) {
     }
 }
 
+// the time transforms of mm_stage_inputs_taug: thresholds and stream words of the seven per-sample draws
+struct TimeAugArgs {
+    uint64_t t_shift, t_scale, t_invert, t_mask;
+    uint32_t s_shift, s_shift_amt, s_scale, s_scale_u, s_invert, s_mask, s_mask_start;
+    int max_shift, mask_len;
+    float scale_range;
+    int32_t* time_plan;
+};
+
 struct StageAugArgs {
     const float* x; uint32_t* plan; bf16* y; float* out;
     int B, C, T, Cp, tcw, stride, nchunk, npack;
     float noise_factor;
     uint32_t s_ga, s_gb;
     float4* d1; const float4* s1; size_t n1;
+    TimeAugArgs tm;                                                // (read by the <true> instance only)
 };
 
+enum { TF_SHIFT = 1, TF_SCALE = 2, TF_INVERT = 4, TF_MASK = 8 };
+
+__device__ __forceinline__ uint32_t aug_uniform(uint32_t h, uint32_t n) { return (uint32_t)(((uint64_t)h * n) >> 32); }
+
+// fp32( 1 + (double)scale_range * (h * 2^-31 - 1) ): fp64 operations in this order, each rounded on its own (no FMA)
+__device__ __forceinline__ float aug_scale_factor(float scale_range, uint32_t h) {
+#pragma clang fp contract(off)
+    return (float)(1.0 + (double)scale_range * ((double)h * 4.656612873077392578125e-10 - 1.0));
+}
+
+// the noise of the Box-Muller pair idx onto the two elements of a thread: ONE expression for both instances of the kernel
+// below, so that they round alike
+__device__ __forceinline__ void aug_add_noise(float& v0, float& v1, bool two, uint32_t s_ga, uint32_t s_gb, uint32_t idx, float scale) {
+    const float u1 = ((float)aug_hash(s_ga, idx) + 1.0f) * 2.3283064365386963e-10f;   // 2^-32
+    const float w2 = (float)aug_hash(s_gb, idx) * 4.6566128730773926e-10f;            // 2 u2
+    const float r = sqrtf(-2.0f * logf(u1));
+    float sn, cs;
+    sincospif(w2, &sn, &cs);
+    v0 = v0 + (r * cs) * scale;
+    if (two) v1 = v1 + (r * sn) * scale;
+}
+
 // Workgroups [0, npack) are 32 x 32 (channel x time) tiles, the rest copy the fMRI batch (as stage_inputs_kernel).
+// TIME: the time transforms as well (mm_stage_inputs_taug) - every tile workgroup draws its sample's shift, gain and mask
+// window itself (seven hashes), so they need no plan; the EEG plan may then be absent (no noise, no channel drop).
+template <bool TIME>
 __global__ void __launch_bounds__(256) stage_inputs_aug_kernel(StageAugArgs a) {
     __shared__ float tile[32][33];
     if ((int)blockIdx.x >= a.npack) {
@@ -169,19 +204,51 @@ __global__ void __launch_bounds__(256) stage_inputs_aug_kernel(StageAugArgs a) {
     const int tt = (a.T + 31) / 32;
     const int b = blockIdx.x / (tt * a.tcw), rem = blockIdx.x % (tt * a.tcw);
     const int t0 = (rem % tt) * 32, c0 = (rem / tt) * 32;
-    uint32_t* hdr = a.plan + (size_t)b * a.stride;
-    // std_b from the chunk partials, in chunk order
-    const double* part = reinterpret_cast<const double*>(a.plan + (size_t)a.B * a.stride) + (size_t)b * a.nchunk * 2;
-    double s1 = 0.0, s2 = 0.0;
-    for (int k = 0; k < a.nchunk; ++k) { s1 += part[2 * k]; s2 += part[2 * k + 1]; }
-    const double n = (double)a.C * (double)a.T;
-    double var = (s2 - s1 * (s1 / n)) / (n - 1.0);
-    var = var < 0.0 ? 0.0 : var;                                   // (a NaN stays a NaN)
-    const float std_b = (float)sqrt(var);
-    const float scale = hdr[2] ? a.noise_factor * std_b : 0.f;
-    if (rem == 0 && threadIdx.x == 0) { hdr[0] = __float_as_uint(scale); hdr[1] = __float_as_uint(std_b); }
-    const bool drop_on = hdr[3] != 0;
+    const bool planned = !TIME || a.plan != nullptr;
+    uint32_t* hdr = planned ? a.plan + (size_t)b * a.stride : nullptr;
+    float scale = 0.f;
+    bool drop_on = false;
+    if (planned) {
+        // std_b from the chunk partials, in chunk order
+        const double* part = reinterpret_cast<const double*>(a.plan + (size_t)a.B * a.stride) + (size_t)b * a.nchunk * 2;
+        double s1 = 0.0, s2 = 0.0;
+        for (int k = 0; k < a.nchunk; ++k) { s1 += part[2 * k]; s2 += part[2 * k + 1]; }
+        const double n = (double)a.C * (double)a.T;
+        double var = (s2 - s1 * (s1 / n)) / (n - 1.0);
+        var = var < 0.0 ? 0.0 : var;                               // (a NaN stays a NaN)
+        const float std_b = (float)sqrt(var);
+        scale = hdr[2] ? a.noise_factor * std_b : 0.f;
+        if (rem == 0 && threadIdx.x == 0) { hdr[0] = __float_as_uint(scale); hdr[1] = __float_as_uint(std_b); }
+        drop_on = hdr[3] != 0;
+    }
     const uint32_t half_t = (uint32_t)((a.T + 1) / 2);
+    // the sample's time draws: shift sh (out[t] = x[t - sh]), gain, mask window [m0, m0 + mlen)
+    int sh = 0, m0 = 0, mlen = 0;
+    uint32_t flags = 0;
+    float gain = 1.0f;
+    if constexpr (TIME) {
+        const TimeAugArgs& tm = a.tm;
+        const uint32_t ub = (uint32_t)b;
+        if ((uint64_t)aug_hash(tm.s_shift, ub) < tm.t_shift) {
+            flags |= TF_SHIFT;
+            sh = (int)aug_uniform(aug_hash(tm.s_shift_amt, ub), 2u * (uint32_t)tm.max_shift + 1u) - tm.max_shift;
+        }
+        if ((uint64_t)aug_hash(tm.s_scale, ub) < tm.t_scale) {
+            flags |= TF_SCALE;
+            gain = aug_scale_factor(tm.scale_range, aug_hash(tm.s_scale_u, ub));
+        }
+        if ((uint64_t)aug_hash(tm.s_invert, ub) < tm.t_invert) { flags |= TF_INVERT; gain = -gain; }
+        if ((uint64_t)aug_hash(tm.s_mask, ub) < tm.t_mask) {
+            flags |= TF_MASK;
+            m0 = (int)aug_uniform(aug_hash(tm.s_mask_start, ub), (uint32_t)(a.T - tm.mask_len + 1));
+            mlen = tm.mask_len;
+        }
+        if (tm.time_plan && rem == 0 && threadIdx.x < 8) {
+            const int w = threadIdx.x;
+            tm.time_plan[(size_t)b * 8 + w] = w == 0 ? (int)flags : w == 1 ? sh : w == 2 ? (int)__float_as_uint(gain) : w == 3 ? m0 : w == 4 ? mlen : 0;
+        }
+    }
+    const bool gain_on = (flags & (TF_SCALE | TF_INVERT)) != 0;
 
     const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;         // a thread: elements (t, t + 1) of one row, t even
     for (int i = ty; i < 32; i += 16) {
@@ -191,17 +258,24 @@ __global__ void __launch_bounds__(256) stage_inputs_aug_kernel(StageAugArgs a) {
             const uint32_t row = (uint32_t)b * (uint32_t)a.C + (uint32_t)c;
             const size_t o = (size_t)row * a.T + t;
             const bool two = t + 1 < a.T;
-            v0 = a.x[o];
-            if (two) v1 = a.x[o + 1];
-            if (scale != 0.f) {
-                const uint32_t idx = row * half_t + (uint32_t)(t >> 1);
-                const float u1 = ((float)aug_hash(a.s_ga, idx) + 1.0f) * 2.3283064365386963e-10f;   // 2^-32
-                const float w2 = (float)aug_hash(a.s_gb, idx) * 4.6566128730773926e-10f;            // 2 u2
-                const float r = sqrtf(-2.0f * logf(u1));
-                float sn, cs;
-                sincospif(w2, &sn, &cs);
-                v0 = v0 + (r * cs) * scale;
-                if (two) v1 = v1 + (r * sn) * scale;
+            // (TIME) does the element have a source x[t - sh] inside the row - if not it is +0, and takes no noise
+            bool in0 = true, in1 = two;
+            if constexpr (TIME) {
+                const int ts = t - sh;
+                in0 = ts >= 0 && ts < a.T;
+                in1 = two && ts + 1 >= 0 && ts + 1 < a.T;
+                const float* xr = a.x + (size_t)row * a.T;
+                if (in0) v0 = xr[ts];
+                if (in1) v1 = xr[ts + 1];
+            } else {
+                v0 = a.x[o];
+                if (two) v1 = a.x[o + 1];
+            }
+            if (scale != 0.f) aug_add_noise(v0, v1, two, a.s_ga, a.s_gb, row * half_t + (uint32_t)(t >> 1), scale);
+            if constexpr (TIME) {
+                if (gain_on) { v0 = v0 * gain; v1 = v1 * gain; }
+                if (!in0 || (t >= m0 && t < m0 + mlen)) v0 = 0.f;
+                if (!in1 || (t + 1 >= m0 && t + 1 < m0 + mlen)) v1 = 0.f;
             }
             if (drop_on && ((hdr[AUG_HDR + (c >> 5)] >> (c & 31)) & 1u)) v0 = v1 = 0.f;
             if (a.out) {
@@ -226,6 +300,48 @@ int aug_check_shape(const char* who, int B, int C, int T) {
     MM_REQUIRE((int64_t)C * T >= 2, "%s: a sample needs C * T >= 2 values for its standard deviation", who);
     MM_REQUIRE((int64_t)B * C * ((T + 1) / 2) < (1ll << 32), "%s: B * C * ceil(T / 2) must be below 2^32 (the stream's index)", who);
     return MM_OK;
+}
+
+// the launch of both staging entry points; tm: the time transforms of mm_stage_inputs_taug (the plan may then be null)
+int stage_aug_launch(const char* who, const TimeAugArgs* tm, const float* eeg, uint32_t* plan, int64_t plan_words, void* eeg_packed_bf16,
+                     float* eeg_out_f32, int B, int C, int T, int Cp, float noise_factor, uint32_t s_gauss_a, uint32_t s_gauss_b,
+                     float* fmri_dst, const float* fmri_src, int64_t fmri_n, hipStream_t st) {
+    if (plan || !tm) {
+        if (int rc = aug_check_shape(who, B, C, T)) return rc;
+    } else {
+        MM_REQUIRE(B > 0 && C > 0 && T > 0, "%s: bad shape", who);
+        MM_REQUIRE((int64_t)B * C < (1ll << 32), "%s: B * C must be below 2^32 (the kernel's row index)", who);
+    }
+    MM_REQUIRE(eeg && (plan || tm) && ((uintptr_t)plan & 7) == 0 && (eeg_packed_bf16 || eeg_out_f32) && eeg_out_f32 != eeg,
+               "%s: bad EEG args (a batch, a plan and at least one output, not in place)", who);
+    MM_REQUIRE(Cp >= C && Cp % 16 == 0, "%s: bad EEG args (Cp)", who);
+    MM_REQUIRE(noise_factor >= 0.f, "%s: noise_factor must not be negative", who);
+    AugShape s = {0, 0, 0, 0};
+    if (plan) {
+        s = aug_shape(B, C, T);
+        MM_REQUIRE(plan_words >= s.words, "%s: the plan needs %lld words", who, (long long)s.words);
+    }
+    const bool copy = fmri_dst || fmri_src || fmri_n;
+    if (copy)
+        MM_REQUIRE(fmri_dst && fmri_src && fmri_n > 0 && fmri_n % 4 == 0 && (((uintptr_t)fmri_dst | (uintptr_t)fmri_src) & 15) == 0,
+                   "%s: fMRI copy needs 16-byte alignment and a multiple of 4 floats", who);
+    StageAugArgs a = {};
+    a.tcw = ceil_div(eeg_packed_bf16 ? Cp : C, 32);
+    const int64_t npack = (int64_t)B * ceil_div(T, 32) * a.tcw;
+    const long n4 = copy ? fmri_n / 4 : 0;
+    const int ncopy = (int)((n4 + 1023) / 1024 < 1024 ? (n4 + 1023) / 1024 : 1024);
+    MM_REQUIRE(npack + ncopy < (1ll << 31), "%s: too many workgroups", who);
+    a.x = eeg; a.plan = plan; a.y = (bf16*)eeg_packed_bf16; a.out = eeg_out_f32;
+    a.B = B; a.C = C; a.T = T; a.Cp = Cp; a.stride = s.stride; a.nchunk = s.nchunk; a.npack = (int)npack;
+    a.noise_factor = noise_factor; a.s_ga = s_gauss_a; a.s_gb = s_gauss_b;
+    a.d1 = reinterpret_cast<float4*>(fmri_dst); a.s1 = reinterpret_cast<const float4*>(fmri_src); a.n1 = (size_t)n4;
+    if (tm) {
+        a.tm = *tm;
+        hipLaunchKernelGGL(stage_inputs_aug_kernel<true>, dim3((unsigned)(npack + ncopy)), dim3(256), 0, st, a);
+    } else {
+        hipLaunchKernelGGL(stage_inputs_aug_kernel<false>, dim3((unsigned)(npack + ncopy)), dim3(256), 0, st, a);
+    }
+    return mm_check_launch(who);
 }
 
 }  // namespace
@@ -254,29 +370,33 @@ int mm_eeg_augment_plan(const float* x, uint32_t* plan, int64_t plan_words, int 
 int mm_stage_inputs_aug(const float* eeg, uint32_t* plan, int64_t plan_words, void* eeg_packed_bf16, float* eeg_out_f32, int B,
                         int C, int T, int Cp, float noise_factor, uint32_t s_gauss_a, uint32_t s_gauss_b, float* fmri_dst,
                         const float* fmri_src, int64_t fmri_n, hipStream_t st) {
-    if (int rc = aug_check_shape("stage_inputs_aug", B, C, T)) return rc;
-    MM_REQUIRE(eeg && plan && ((uintptr_t)plan & 7) == 0 && (eeg_packed_bf16 || eeg_out_f32) && eeg_out_f32 != eeg,
-               "stage_inputs_aug: bad EEG args (a batch, a plan and at least one output, not in place)");
-    MM_REQUIRE(Cp >= C && Cp % 16 == 0, "stage_inputs_aug: bad EEG args (Cp)");
-    MM_REQUIRE(noise_factor >= 0.f, "stage_inputs_aug: noise_factor must not be negative");
-    const AugShape s = aug_shape(B, C, T);
-    MM_REQUIRE(plan_words >= s.words, "stage_inputs_aug: the plan needs %lld words", (long long)s.words);
-    const bool copy = fmri_dst || fmri_src || fmri_n;
-    if (copy)
-        MM_REQUIRE(fmri_dst && fmri_src && fmri_n > 0 && fmri_n % 4 == 0 && (((uintptr_t)fmri_dst | (uintptr_t)fmri_src) & 15) == 0,
-                   "stage_inputs_aug: fMRI copy needs 16-byte alignment and a multiple of 4 floats");
-    StageAugArgs a;
-    a.tcw = ceil_div(eeg_packed_bf16 ? Cp : C, 32);
-    const int64_t npack = (int64_t)B * ceil_div(T, 32) * a.tcw;
-    const long n4 = copy ? fmri_n / 4 : 0;
-    const int ncopy = (int)((n4 + 1023) / 1024 < 1024 ? (n4 + 1023) / 1024 : 1024);
-    MM_REQUIRE(npack + ncopy < (1ll << 31), "stage_inputs_aug: too many workgroups");
-    a.x = eeg; a.plan = plan; a.y = (bf16*)eeg_packed_bf16; a.out = eeg_out_f32;
-    a.B = B; a.C = C; a.T = T; a.Cp = Cp; a.stride = s.stride; a.nchunk = s.nchunk; a.npack = (int)npack;
-    a.noise_factor = noise_factor; a.s_ga = s_gauss_a; a.s_gb = s_gauss_b;
-    a.d1 = reinterpret_cast<float4*>(fmri_dst); a.s1 = reinterpret_cast<const float4*>(fmri_src); a.n1 = (size_t)n4;
-    hipLaunchKernelGGL(stage_inputs_aug_kernel, dim3((unsigned)(npack + ncopy)), dim3(256), 0, st, a);
-    return mm_check_launch("stage_inputs_aug");
+    return stage_aug_launch("stage_inputs_aug", nullptr, eeg, plan, plan_words, eeg_packed_bf16, eeg_out_f32, B, C, T, Cp, noise_factor,
+                            s_gauss_a, s_gauss_b, fmri_dst, fmri_src, fmri_n, st);
+}
+
+int mm_stage_inputs_taug(const float* eeg, uint32_t* plan, int64_t plan_words, void* eeg_packed_bf16, float* eeg_out_f32, int B,
+                         int C, int T, int Cp, float noise_factor, uint32_t s_gauss_a, uint32_t s_gauss_b, float p_shift,
+                         int max_shift, float p_scale, float scale_range, float p_invert, float p_mask, int mask_len,
+                         uint32_t s_shift, uint32_t s_shift_amt, uint32_t s_scale, uint32_t s_scale_u, uint32_t s_invert,
+                         uint32_t s_mask, uint32_t s_mask_start, int32_t* time_plan, float* fmri_dst, const float* fmri_src,
+                         int64_t fmri_n, hipStream_t st) {
+    MM_REQUIRE(B > 0 && C > 0 && T > 0, "stage_inputs_taug: bad shape");
+    MM_REQUIRE(p_shift >= 0.f && p_shift <= 1.f && p_scale >= 0.f && p_scale <= 1.f && p_invert >= 0.f && p_invert <= 1.f &&
+               p_mask >= 0.f && p_mask <= 1.f, "stage_inputs_taug: probabilities lie in [0, 1]");
+    MM_REQUIRE(max_shift >= 0 && max_shift < T, "stage_inputs_taug: max_shift must lie in [0, T)");
+    MM_REQUIRE(scale_range >= 0.f && scale_range < 1.f, "stage_inputs_taug: scale_range must lie in [0, 1)");
+    MM_REQUIRE(mask_len >= 1 && mask_len <= T, "stage_inputs_taug: the mask length must lie in [1, T]");
+    if (eeg && eeg_out_f32) {                        // the shift is a gather: it cannot run in place, or into a part of its source
+        const uintptr_t x0 = (uintptr_t)eeg, o0 = (uintptr_t)eeg_out_f32, n = (uintptr_t)B * C * T * sizeof(float);
+        MM_REQUIRE(x0 + n <= o0 || o0 + n <= x0, "stage_inputs_taug: the batch and the fp32 output overlap (the shift is a gather)");
+    }
+    TimeAugArgs tm;
+    tm.t_shift = aug_thresh(p_shift); tm.t_scale = aug_thresh(p_scale); tm.t_invert = aug_thresh(p_invert); tm.t_mask = aug_thresh(p_mask);
+    tm.s_shift = s_shift; tm.s_shift_amt = s_shift_amt; tm.s_scale = s_scale; tm.s_scale_u = s_scale_u; tm.s_invert = s_invert;
+    tm.s_mask = s_mask; tm.s_mask_start = s_mask_start;
+    tm.max_shift = max_shift; tm.mask_len = mask_len; tm.scale_range = scale_range; tm.time_plan = time_plan;
+    return stage_aug_launch("stage_inputs_taug", &tm, eeg, plan, plan_words, eeg_packed_bf16, eeg_out_f32, B, C, T, Cp, noise_factor,
+                            s_gauss_a, s_gauss_b, fmri_dst, fmri_src, fmri_n, st);
 }
 
 }  // extern "C"

@@ -510,6 +510,110 @@ def volume_augment(x: torch.Tensor, *, step: int, rank: int = 0, return_plan: bo
     return (out, volume_augment_read_plan(plan, x.shape[0], *x.shape[2:])) if return_plan else out
 
 
+# ---- temporal EEG augmentation (csrc/augment.hip's mm_stage_inputs_taug): the same h(stream, idx) and
+# stream(seed, step, rank, purpose) on purposes 19..25 - independent of the two augmenters above at equal seed and step.
+EEG_TIME_AUG_PURPOSES = ("shift_decision", "shift_amount", "scale_decision", "scale_u", "invert_decision", "mask_decision",
+                         "mask_start")
+EEG_TIME_AUG_FLAGS = ("shift", "scale", "invert", "mask")              # bit k of a time plan's flag word
+_TIME_HDR = 8
+
+
+def eeg_time_augment_streams(seed: int, step: int, rank: int = 0) -> tuple:
+    """the seven 32-bit stream words of one temporal-augmentation step, in `EEG_TIME_AUG_PURPOSES` order: purposes 19..25"""
+    first = len(AUG_PURPOSES) + len(VOL_AUG_PURPOSES)
+    return tuple(_stream_word(seed, step, rank, first + k) for k in range(len(EEG_TIME_AUG_PURPOSES)))
+
+
+def eeg_time_augment_check(B: int, C: int, T: int, *, p_shift: float, max_shift: int, p_scale: float, scale_range: float,
+                           p_invert: float, p_mask: float, mask_len: int, n_drop: Optional[int] = None,
+                           who: str = "eeg_time_augment"):
+    """what both the kernel and the CPU path refuse, before anything runs.  ``mask_len``: the masked window's samples;
+    ``n_drop``: that of an `EEGTransforms` riding along (its shape limits then hold too), None without one"""
+    if min(B, C, T) < 1:
+        raise ValueError(f"{who}: expected a non-empty (B, C, T) batch (got {B} x {C} x {T})")
+    if B * C >= 1 << 32:
+        raise ValueError(f"{who}: B * C must stay below 2^32 (the kernel's row index)")
+    for name, p in (("p_shift", p_shift), ("p_scale", p_scale), ("p_invert", p_invert), ("p_mask", p_mask)):
+        if not 0.0 <= p <= 1.0:                                    # (a NaN fails too)
+            raise ValueError(f"{who}: {name} must lie in [0, 1] (got {p!r})")
+    if int(max_shift) != max_shift or not 0 <= max_shift < T:
+        raise ValueError(f"{who}: max_shift must be an integer in [0, T) = [0, {T}) (got {max_shift!r})")
+    if not 0.0 <= scale_range < 1.0:
+        raise ValueError(f"{who}: scale_range must lie in [0, 1) (got {scale_range!r})")
+    if int(mask_len) != mask_len or not 1 <= mask_len <= T:
+        raise ValueError(f"{who}: the masked window must lie in [1, T] = [1, {T}] samples (got {mask_len!r})")
+    if n_drop is not None:
+        eeg_augment_check(B, C, T, n_drop, who)
+
+
+def eeg_time_augment_into(x: torch.Tensor, xb: Optional[torch.Tensor], out: Optional[torch.Tensor], *, time_args: dict,
+                          base_args: Optional[dict] = None, step: int, rank: int = 0,
+                          fmri_dst: Optional[torch.Tensor] = None, fmri_src: Optional[torch.Tensor] = None,
+                          plan: Optional[torch.Tensor] = None, time_plan: Optional[torch.Tensor] = None):
+    """batch ``x`` (B, C, T) fp32 through the time transforms into the packed bf16 operand ``xb`` (B, T, cpad(C)) and / or
+    the fp32 ``out`` (B, C, T; NOT overlapping ``x``: the shift is a gather), with the fMRI copy of mm_stage_inputs when
+    given.  ``time_args``: `EEGTimeTransforms.kernel_args(T)`.  ``base_args`` None: ONE launch.  ``base_args`` =
+    `EEGTransforms.kernel_args(C)`: its noise and channel drop in the same launch, after mm_eeg_augment_plan (two launches);
+    ``plan`` is then a buffer of `eeg_augment_plan_layout` words to reuse.  ``time_plan``: (B, 8) int32 for the per-sample
+    draws (`eeg_time_augment_read_plan`), or None.  -> the EEG plan buffer (None without ``base_args``)."""
+    B, C, T = x.shape
+    t = dict(time_args)
+    seed = t.pop("seed")
+    eeg_time_augment_check(B, C, T, n_drop=None if base_args is None else base_args["n_drop"], **t)
+    if x.dtype != _F32 or (out is not None and (out.dtype != _F32 or tuple(out.shape) != (B, C, T))):
+        raise ValueError("eeg_time_augment_into: fp32 batches of one shape")
+    if out is not None and _overlap(x, out):
+        raise ValueError("eeg_time_augment_into: source and destination overlap (the shift is a gather: augment into another buffer)")
+    _need_gpu(x)
+    words, s, noise_factor = 0, (0, 0, 0, 0, 0), 0.0
+    if base_args is not None:
+        words, _, _ = eeg_augment_plan_layout(B, C, T)
+        if plan is None:
+            plan = torch.empty(words, dtype=torch.int32, device=x.device)
+        s = augment_streams(base_args["seed"], step, rank)
+        noise_factor = base_args["noise_factor"]
+        _hip.call("mm_eeg_augment_plan", x, plan, words, B, C, T, base_args["p_noise"], base_args["p_drop"], base_args["n_drop"],
+                  s[0], s[1], s[2])
+    else:
+        plan = None
+    ts = eeg_time_augment_streams(seed, step, rank)
+    _hip.call("mm_stage_inputs_taug", x, plan, words, xb, out, B, C, T, cpad(C), noise_factor, s[3], s[4],
+              t["p_shift"], int(t["max_shift"]), t["p_scale"], t["scale_range"], t["p_invert"], t["p_mask"], int(t["mask_len"]),
+              *ts, time_plan, fmri_dst, fmri_src, 0 if fmri_src is None else fmri_src.numel())
+    return plan
+
+
+def eeg_time_augment_read_plan(time_plan: torch.Tensor) -> dict:
+    """a (B, 8) int32 time plan mm_stage_inputs_taug has written -> {"flags": {shift, scale, invert, mask: bool (B,)},
+    "shift": int32 (B,), "gain": fp32 (B,), "mask_start": int32 (B,), "mask_len": int32 (B,) (0 when off)}"""
+    hdr = time_plan.view(-1, _TIME_HDR)
+    return {"flags": {name: (hdr[:, 0] >> k) & 1 != 0 for k, name in enumerate(EEG_TIME_AUG_FLAGS)},
+            "shift": hdr[:, 1].contiguous(), "gain": hdr[:, 2].contiguous().view(_F32), "mask_start": hdr[:, 3].contiguous(),
+            "mask_len": hdr[:, 4].contiguous()}
+
+
+def eeg_time_augment(x: torch.Tensor, *, time_args: dict, base_args: Optional[dict] = None, step: int, rank: int = 0,
+                     packed: bool = False, return_plan: bool = False):
+    """EEGTimeTransforms (with ``base_args`` also an EEGTransforms) on a device batch (B, C, T); the draws are a function
+    of (seed, step, rank) alone.  -> the augmented fp32 batch (a new tensor); with ``packed`` also its channels-last bf16
+    image (B, T, cpad(C)); with ``return_plan`` also `eeg_time_augment_read_plan`'s dict (plus "base": `eeg_augment_read_plan`'s
+    tuple when ``base_args`` is given)."""
+    _need_gpu(x)
+    x = x.contiguous().float()
+    B, C, T = x.shape
+    out = _empty((B, C, T), _F32, x)
+    xb = _empty((B, T, cpad(C)), _BF, x) if packed else None
+    tp = torch.empty(B, _TIME_HDR, dtype=torch.int32, device=x.device) if return_plan else None
+    plan = eeg_time_augment_into(x, xb, out, time_args=time_args, base_args=base_args, step=step, rank=rank, time_plan=tp)
+    res = (out, xb) if packed else out
+    if not return_plan:
+        return res
+    info = eeg_time_augment_read_plan(tp)
+    if plan is not None:
+        info["base"] = eeg_augment_read_plan(plan, B, C, T)
+    return res, info
+
+
 def igemm(x: torch.Tensor, wf: torch.Tensor, taps: int, pad: int, cout: int, *,
           scale=None, shift=None, act="none", residual=None, pe=None, pool=1, stats=None,
           out_f32=False, out_bf16=True, out_pre=False, drop_p=0.0, seed=0, gradz=None, gradz_act="none"):

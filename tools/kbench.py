@@ -882,6 +882,66 @@ def aug_case(B=32, C=64, T=1024, vol=(32, 32, 32), step_iters=30):
         print(f"C2 graph step B={B}: {name:16s} {us:7.1f} us  (min {min(t):6.1f}, max {max(t):6.1f})  {100 * (us / base - 1):+.2f} %")
 
 
+def taug_case(B=32, C=64, T=1024, vol=(32, 32, 32), step_iters=30):
+    """temporal EEG augmentation (csrc/augment.hip's mm_stage_inputs_taug) at the C2 shape, in one run: the
+    parent's mm_stage_inputs and plan + mm_stage_inputs_aug pair against the time-only launch and plan + mm_stage_inputs_taug -
+    issued eagerly and replayed from a hipGraph, HIP events, interleaved rounds - then the C2 graph step with and without the
+    augmenter"""
+    from multimodal_eeg_fmri_amd.bridge_trainer import BridgeTrainer, synthetic_pairs
+    from multimodal_eeg_fmri_amd.crossmodal_eeg_scr import EEGTimeTransforms, EEGTransforms
+    eeg, fmri = synthetic_pairs(B, C, T, vol)
+    cp = ops.cpad(C)
+    xb, fdst = torch.empty(B, T, cp, dtype=BF, device="cuda"), torch.empty_like(fmri)
+    step = [0]
+    plan = torch.empty(ops.eeg_augment_plan_layout(B, C, T)[0], dtype=torch.int32, device="cuda")
+    default, every = EEGTimeTransforms(seed=1), EEGTimeTransforms(p_shift=1.0, p_scale=1.0, p_invert=1.0, p_mask=1.0, seed=1)
+    base = EEGTransforms(p=0.3, seed=1)
+
+    def aug():
+        step[0] += 1
+        ops.eeg_augment_into(eeg, xb, None, step=step[0], fmri_dst=fdst, fmri_src=fmri, plan=plan, **base.kernel_args(C))
+
+    def taug(time_aug, with_base):
+        step[0] += 1
+        ops.eeg_time_augment_into(eeg, xb, None, time_args=time_aug.kernel_args(T), base_args=base.kernel_args(C) if with_base else None,
+                                  step=step[0], fmri_dst=fdst, fmri_src=fmri, plan=plan)
+    cases = [("mm_stage_inputs", lambda: _hip.call("mm_stage_inputs", eeg, xb, None, B, C, T, cp, fdst, fmri, fmri.numel()), 1),
+             ("plan + mm_stage_inputs_aug p = 0.3", aug, 2),
+             ("mm_stage_inputs_taug defaults", lambda: taug(default, False), 1),
+             ("mm_stage_inputs_taug every p = 1", lambda: taug(every, False), 1),
+             ("plan + mm_stage_inputs_taug p = 0.3", lambda: taug(default, True), 2)]
+    times, gtimes = [[] for _ in cases], [[] for _ in cases]
+    for _ in range(5):
+        for i, (_, fn, _) in enumerate(cases):
+            times[i].append(timeit(fn, iters=200, rounds=1))
+            gtimes[i].append(graph_time(fn, n=50))
+    for (name, _, reads), t, gt in zip(cases, times, gtimes):
+        us, gus = statistics.median(t), statistics.median(gt)
+        nbytes = reads * eeg.numel() * 4 + xb.numel() * 2 + 2 * fmri.numel() * 4
+        print(f"{name:38s} eager {us:6.2f} us (min {min(t):5.2f}, max {max(t):5.2f})  in a graph {gus:6.2f} us (min {min(gt):5.2f}, "
+              f"max {max(gt):5.2f})  {nbytes / 1e6:5.1f} MB  {nbytes / gus / 1e6:5.2f} TB/s")
+    # After the graph captures above, the FOURTH trainer built in this process replays its step ~210 us slower whatever its
+    # configuration (measured with an augmenter-free trainer, `augment=` alone and both augmenters in that place; the
+    # trainers before and after it are not affected, nor is a fourth trainer in a process without those captures - DESIGN.md
+    # 5u; the cause was not looked for).  So the fourth place holds a second augmenter-free trainer, which shows the effect.
+    trs, names = [], ("no augmenter", "eeg_time_augment defaults", "eeg_time_augment p = 1", "no augmenter, 4th trainer",
+                      "augment p = 0.3", "defaults + augment p = 0.3")
+    for time_aug, eaug in ((None, None), (default, None), (every, None), (None, None), (None, base), (default, base)):
+        ops.set_seed_epoch(None)
+        torch.manual_seed(0)
+        tr = BridgeTrainer(eeg_channels=C, dropout=0.3, augment=eaug, eeg_time_augment=time_aug).train()
+        tr.train_step(eeg, fmri)
+        trs.append(tr)
+    times = [[] for _ in trs]
+    for _ in range(5):
+        for i, tr in enumerate(trs):
+            times[i].append(timeit(lambda: tr.train_step(eeg, fmri), iters=step_iters, rounds=1))
+    ref = statistics.median(times[0])
+    for name, t in zip(names, times):
+        us = statistics.median(t)
+        print(f"C2 graph step B={B}: {name:28s} {us:7.1f} us  (min {min(t):6.1f}, max {max(t):6.1f})  {100 * (us / ref - 1):+.2f} %")
+
+
 def volaug_case(B=32, C=64, T=1024, vol=(32, 32, 32), odd=(91, 109, 91), step_iters=30):
     """fMRI volume augmentation (csrc/volume_augment.hip) at the C2 shape: mm_stage_inputs alone against the staging sequences
     of a trainer with a volume augmenter - the kernel pair + mm_pack_nct_bf16, and the kernel pair + the EEG augmenter's pair
@@ -1222,6 +1282,9 @@ def main():
         return
     if flt == "aug":
         aug_case()
+        return
+    if flt == "taug":
+        taug_case()
         return
     if flt == "volaug":
         volaug_case()
