@@ -40,6 +40,7 @@ from typing import Callable, Optional, Union
 import torch
 
 from . import dp, ops
+from .bridge_staging import AUGMENTERS
 from .enhanced_models_v4 import TemporalTransformerBlock
 
 FORMAT = 1
@@ -193,12 +194,9 @@ class TrainerCheckpointMixin:
                          "weight_decay": float(self.weight_decay), "grad_clip": float(self.grad_clip)},
                "dropout": self._dropout_stream_state(), "fit": getattr(self, "_fit_state", None)}
         bts.update(self._layout())
-        if getattr(self, "augment", None) is not None:             # (absent without an augmenter: the container is unchanged)
-            bts["augment"] = dict(self.augment.params(), step=int(self._aug_step))
-        if getattr(self, "eeg_time_augment", None) is not None:    # (absent without a temporal augmenter; the step index is `augment`'s)
-            bts["eeg_time_augment"] = dict(self.eeg_time_augment.params(), step=int(self._aug_step))
-        if getattr(self, "fmri_augment", None) is not None:        # (absent without a volume augmenter: the container is unchanged)
-            bts["fmri_augment"] = dict(self.fmri_augment.params(), step=int(self._fmri_aug_step))
+        for a in AUGMENTERS:                                       # (absent without that augmenter: the container is unchanged)
+            if getattr(self, a.attr, None) is not None:
+                bts[a.attr] = dict(getattr(self, a.attr).params(), step=int(getattr(self, a.counter)))
         if getattr(self, "loss", "infonce") != "infonce":          # (absent for the default loss: the container is unchanged)
             bts["loss"] = self.loss
         if self.checkpoint_classify() is not None:                 # (absent without classify: the container is unchanged)
@@ -295,36 +293,22 @@ class TrainerCheckpointMixin:
         if set(theirs) != set(mine["shapes"]):
             raise ValueError(f"load_checkpoint_state: shapes differ: extra keys {sorted(set(theirs) - set(mine['shapes']))}")
         same("bucket_n", "groups")
-        aug, theirs_aug = getattr(self, "augment", None), bts.get("augment")
-        if (aug is None) != (theirs_aug is None):
-            raise ValueError(f"load_checkpoint_state: augment differs: the checkpoint was written "
-                             f"{'with' if theirs_aug is not None else 'without'} an augmenter, this trainer has "
-                             f"{'none' if aug is None else 'one'}")
-        if aug is not None:
+        steps = {}                                                 # augmenters that share a counter hold one step index
+        for a in AUGMENTERS:
+            aug, theirs = getattr(self, a.attr, None), bts.get(a.attr)
+            if (aug is None) != (theirs is None):
+                raise ValueError(f"load_checkpoint_state: {a.attr} differs: the checkpoint was written "
+                                 f"{'with' if theirs is not None else 'without'} {a.ckpt_noun}, this trainer has "
+                                 f"{'none' if aug is None else 'one'}")
+            if aug is None:
+                continue
             mine_aug = aug.params()
-            if {k: theirs_aug.get(k) for k in mine_aug} != mine_aug:
-                raise ValueError(f"load_checkpoint_state: augment differs: checkpoint {theirs_aug!r}, trainer {mine_aug!r}")
-        taug, theirs_taug = getattr(self, "eeg_time_augment", None), bts.get("eeg_time_augment")
-        if (taug is None) != (theirs_taug is None):
-            raise ValueError(f"load_checkpoint_state: eeg_time_augment differs: the checkpoint was written "
-                             f"{'with' if theirs_taug is not None else 'without'} a temporal augmenter, this trainer has "
-                             f"{'none' if taug is None else 'one'}")
-        if taug is not None:
-            mine_taug = taug.params()
-            if {k: theirs_taug.get(k) for k in mine_taug} != mine_taug:
-                raise ValueError(f"load_checkpoint_state: eeg_time_augment differs: checkpoint {theirs_taug!r}, trainer {mine_taug!r}")
-        if aug is not None and taug is not None and int(theirs_aug["step"]) != int(theirs_taug["step"]):
-            raise ValueError(f"load_checkpoint_state: eeg_time_augment differs: the two EEG augmenters share one step index, the "
-                             f"checkpoint holds {theirs_aug['step']!r} and {theirs_taug['step']!r}")
-        vaug, theirs_vaug = getattr(self, "fmri_augment", None), bts.get("fmri_augment")
-        if (vaug is None) != (theirs_vaug is None):
-            raise ValueError(f"load_checkpoint_state: fmri_augment differs: the checkpoint was written "
-                             f"{'with' if theirs_vaug is not None else 'without'} a volume augmenter, this trainer has "
-                             f"{'none' if vaug is None else 'one'}")
-        if vaug is not None:
-            mine_vaug = vaug.params()
-            if {k: theirs_vaug.get(k) for k in mine_vaug} != mine_vaug:
-                raise ValueError(f"load_checkpoint_state: fmri_augment differs: checkpoint {theirs_vaug!r}, trainer {mine_vaug!r}")
+            if {k: theirs.get(k) for k in mine_aug} != mine_aug:
+                raise ValueError(f"load_checkpoint_state: {a.attr} differs: checkpoint {theirs!r}, trainer {mine_aug!r}")
+            first = steps.setdefault(a.counter, theirs["step"])
+            if int(first) != int(theirs["step"]):
+                raise ValueError(f"load_checkpoint_state: {a.attr} differs: the two EEG augmenters share one step index, the "
+                                 f"checkpoint holds {first!r} and {theirs['step']!r}")
         msd = sd["model_state_dict"]
         for k, shp in mine["shapes"].items():
             if k not in msd or list(msd[k].shape) != shp:
@@ -382,12 +366,9 @@ class TrainerCheckpointMixin:
         ops._seed_state["base"] = int(d["base"])
         ops._seed_state["step"] = int(d["step"])
         self._pending_epoch_word = d["epoch_word"] if d["kind"] == "graph" else None
-        if "augment" in bts:
-            self._aug_step = int(bts["augment"]["step"])
-        if "eeg_time_augment" in bts:                              # (one counter for both EEG augmenters: checked equal above)
-            self._aug_step = int(bts["eeg_time_augment"]["step"])
-        if "fmri_augment" in bts:
-            self._fmri_aug_step = int(bts["fmri_augment"]["step"])
+        for a in AUGMENTERS:
+            if a.attr in bts:
+                setattr(self, a.counter, int(bts[a.attr]["step"]))
         if "bank" in bts:
             self._load_bank(bts["bank"])
         if "ema" in bts:

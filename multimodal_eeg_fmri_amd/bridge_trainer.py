@@ -36,13 +36,14 @@ from . import _hip, dp, ops, optim
 from .autograd import (GradBag, bridge_cls_bwd, contrastive_embed_bwd, contrastive_embed_bwd_da, deferred, erp_encoder_bwd,
                        ffn_rows_bwd_fused, fmri_tab_bwd, power_encoder_bwd, volume_encoder_bwd)
 from .bridge_checkpoint import TrainerCheckpointMixin
+from .bridge_staging import TrainerStagingMixin
 from .bridge_utils import EEGfMRIContrastiveBridge, retrieval_metrics
 from .enhanced_models_v4 import EnhancedERPEncoder
 from .fmri_utils import fMRITabularEncoder, fMRIVolumeEncoder3D
 from .optim import FlatBucket, check_ema_decay
 
 
-class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
+class BridgeTrainer(TrainerCheckpointMixin, TrainerStagingMixin, nn.Module):
     def __init__(self, eeg_channels: int = 64, hidden_dim: int = 128, fmri_dim: int = 64,
                  bridge_dim: int = 128, dropout: float = 0.3, lr: float = 1e-4,
                  weight_decay: float = 1e-4, grad_clip: float = 1.0, betas=(0.9, 0.999),
@@ -508,19 +509,16 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
             self._bank_prepare(eeg.shape[0], gid is not None, "train_step")
         if lab is not None and self._cls_ticket is None:       # this trainer's own word, allocated before any capture
             self._cls_ticket = torch.zeros(1, dtype=torch.int32, device=self._scal.device)
-        aug_step = None
-        if self.augment is not None or self.eeg_time_augment is not None:    # one step index per call, whatever the mode
-            if self.eeg_time_augment is not None:
-                self.eeg_time_augment.check(eeg.shape, self.augment, "train_step (eeg_time_augment)")
-            aug_step, self._aug_step = self._aug_step, self._aug_step + 1
-            if self.mode != "graph":
-                eeg = self._augment_eeg(eeg, aug_step)
-        fmri_aug_step = None
-        if self.fmri_augment is not None:                  # a counter of its own: one step index per call, whatever the mode
+        if self.eeg_time_augment is not None:
+            self.eeg_time_augment.check(eeg.shape, self.augment, "train_step (eeg_time_augment)")
+        aug_step = self._take_step("_aug_step")
+        if aug_step is not None and self.mode != "graph":
+            eeg = self._augmented_eeg(eeg, aug_step)
+        if self.fmri_augment is not None:
             self.fmri_augment.check(fmri.shape, "train_step (fmri_augment)")
-            fmri_aug_step, self._fmri_aug_step = self._fmri_aug_step, self._fmri_aug_step + 1
-            if self.mode != "graph":
-                fmri = self.fmri_augment.batch(fmri, fmri_aug_step, dp.rank(self.group))
+        fmri_aug_step = self._take_step("_fmri_aug_step")
+        if fmri_aug_step is not None and self.mode != "graph":
+            fmri = self.fmri_augment.batch(fmri, fmri_aug_step, dp.rank(self.group))
         if self.mode == "autograd":
             return self._step_autograd(eeg, fmri, gid, lab)
         if self.mode == "manual":
@@ -1043,12 +1041,6 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
         with torch.cuda.stream(self._side):
             dp.all_gather_into(c["gid_all"].view(-1, 1), c["gid"].view(-1, 1), self.group)
 
-    def _augment_eeg(self, eeg, aug_step):
-        """the augmented copy of an EEG batch at step index ``aug_step``: both EEG augmenters in one pass when both exist"""
-        if self.eeg_time_augment is not None:
-            return self.eeg_time_augment.batch(eeg, aug_step, dp.rank(self.group), base=self.augment)
-        return self.augment.batch(eeg, aug_step, dp.rank(self.group))
-
     def _step_graph(self, eeg, fmri, gid=None, aug_step=None, lab=None, fmri_aug_step=None):
         """``aug_step`` / ``fmri_aug_step``: the step index of the EEG / volume augmentation (trainers with that augmenter).
         The capture and its two warm-up steps see the batch as it came; what a replay reads is staged below, augmented."""
@@ -1063,104 +1055,12 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
                 self._cap["epoch"].fill_(self._pending_epoch_word)
                 self._pending_epoch_word = None
         c = self._cap
-        if fmri_aug_step is not None:
-            # the augmented volumes go straight into the static buffer; the EEG batch is then staged without the fMRI copy
-            self._stage_fmri_augmented(c, fmri, fmri_aug_step)
-            if aug_step is None or not self._stage_augmented(c, eeg, c["fmri"], aug_step):
-                self._stage_eeg(c, eeg if aug_step is None else self._augment_f32(c, eeg, aug_step))
-        elif aug_step is None or not self._stage_augmented(c, eeg, fmri, aug_step):
-            self._stage_inputs(c, eeg if aug_step is None else self._augment_f32(c, eeg, aug_step), fmri)
+        self._stage(c, eeg, fmri, aug_step, fmri_aug_step)
         if gid is not None and gid.data_ptr() != c["gid"].data_ptr():
             c["gid"].copy_(gid)
         if lab is not None and lab.data_ptr() != c["lab"].data_ptr():
             c["lab"].copy_(lab)
         return self._replay()
-
-    def _stage_inputs(self, c, eeg, fmri):
-        """a batch into the captured step's static inputs"""
-        ce, cf = eeg.data_ptr() != c["eeg"].data_ptr(), fmri.data_ptr() != c["fmri"].data_ptr()
-        if (c["xb"] is not None and ce and cf and eeg.dtype == torch.float32 and fmri.dtype == torch.float32 and eeg.is_cuda and fmri.is_cuda
-                and eeg.is_contiguous() and fmri.is_contiguous() and eeg.numel() % 4 == 0 and fmri.numel() % 4 == 0
-                and (eeg.data_ptr() | fmri.data_ptr()) % 16 == 0):
-            # ONE launch: EEG batch packed into the first convolution's bf16 operand, fMRI batch copied
-            Bx, Cx, Tx = eeg.shape
-            # (no fp32 copy of the EEG batch: the captured step reads the packed operand only - c["eeg"] gives it its shape)
-            _hip.call("mm_stage_inputs", eeg, c["xb"], None, Bx, Cx, Tx, c["xb"].shape[2], c["fmri"], fmri, fmri.numel())
-        else:                                               # each input on its own: a loader may fill only one in place
-            if ce:
-                c["eeg"].copy_(eeg)
-            if cf:
-                c["fmri"].copy_(fmri)
-            if c["xb"] is not None:
-                Bx, Cx, Tx = c["eeg"].shape
-                _hip.call("mm_pack_nct_bf16", c["eeg"], c["xb"], Bx, Cx, Tx, c["xb"].shape[2])
-
-    def _stage_eeg(self, c, eeg):
-        """the EEG batch alone into the captured step's static input (the fMRI buffer has been written already): ONE launch
-        - the pack into the first convolution's operand, or a plain copy for the STFT front end, which reads the fp32 batch"""
-        if c["xb"] is None:
-            if eeg.data_ptr() != c["eeg"].data_ptr():
-                c["eeg"].copy_(eeg)
-            return
-        if not (eeg.dtype == torch.float32 and eeg.is_cuda and eeg.is_contiguous()):
-            c["eeg"].copy_(eeg)
-            eeg = c["eeg"]
-        Bx, Cx, Tx = eeg.shape
-        _hip.call("mm_pack_nct_bf16", eeg, c["xb"], Bx, Cx, Tx, c["xb"].shape[2])
-
-    def _stage_fmri_augmented(self, c, fmri, step):
-        """the augmented fMRI batch into the captured step's static buffer: the two launches of csrc/volume_augment.hip write
-        `c["fmri"]` directly.  The shift is a gather, so a batch that IS the static buffer (an in-place loader) - or is not a
-        contiguous fp32 device tensor - is augmented into a scratch tensor first and copied (the scratch tensor and the plan
-        are kept with the capture: no allocation per step)."""
-        kw = dict(step=step, rank=dp.rank(self.group), plan=c.get("fmri_aug_plan"), **self.fmri_augment.kernel_args(fmri.shape))
-        src = fmri.detach().to(c["fmri"].device, torch.float32).contiguous()     # (the tensor itself when it already is all that)
-        if not ops._overlap(src, c["fmri"]):
-            c["fmri_aug_plan"] = ops.volume_augment_into(src, c["fmri"], **kw)
-            return
-        if c.get("fmri_scratch") is None:
-            c["fmri_scratch"] = torch.empty(c["fmri"].shape, dtype=torch.float32, device=c["fmri"].device)
-        c["fmri_aug_plan"] = ops.volume_augment_into(src, c["fmri_scratch"], **kw)
-        c["fmri"].copy_(c["fmri_scratch"])
-
-    def _stage_augmented(self, c, eeg, fmri, aug_step) -> bool:
-        """the augmented batch straight into the packed operand (and the fMRI batch into its buffer): TWO launches - the
-        plan, then the staging launch with the augmentation between its load and its transpose tile.  False when the step
-        reads the fp32 batch instead (the STFT front-end) or the batch is not a contiguous fp32 device tensor: the caller
-        then augments into a fp32 batch and stages that."""
-        if c["xb"] is None or eeg.dtype != torch.float32 or not eeg.is_cuda or not eeg.is_contiguous():
-            return False
-        cf = fmri.data_ptr() != c["fmri"].data_ptr()
-        fuse = (cf and fmri.dtype == torch.float32 and fmri.is_cuda and fmri.is_contiguous() and fmri.numel() % 4 == 0
-                and fmri.data_ptr() % 16 == 0)
-        kw = dict(step=aug_step, rank=dp.rank(self.group), fmri_dst=c["fmri"] if fuse else None, fmri_src=fmri if fuse else None,
-                  plan=c.get("aug_plan"))
-        if self.eeg_time_augment is not None:             # ONE launch without `augment=`: the time draws need no plan
-            c["aug_plan"] = ops.eeg_time_augment_into(eeg, c["xb"], None, time_args=self.eeg_time_augment.kernel_args(eeg.shape[2]),
-                                                      base_args=self.augment.kernel_args(eeg.shape[1]) if self.augment is not None else None,
-                                                      **kw)
-        else:
-            c["aug_plan"] = ops.eeg_augment_into(eeg, c["xb"], None, **kw, **self.augment.kernel_args(eeg.shape[1]))
-        if cf and not fuse:
-            c["fmri"].copy_(fmri)
-        return True
-
-    def _augment_f32(self, c, eeg, aug_step):
-        """the augmented fp32 batch of a step that cannot write the packed operand directly.  The time transforms gather, so
-        they never run in place: a contiguous fp32 device batch - the static `c["eeg"]` of an in-place loader included - is
-        augmented into a scratch tensor kept with the capture (no allocation per step); anything else goes through `batch`"""
-        if self.eeg_time_augment is None or eeg.dtype != torch.float32 or not eeg.is_cuda or not eeg.is_contiguous():
-            return self._augment_eeg(eeg, aug_step)
-        dst = c["eeg"]
-        if ops._overlap(eeg, dst):
-            if c.get("eeg_scratch") is None:
-                c["eeg_scratch"] = torch.empty(c["eeg"].shape, dtype=torch.float32, device=c["eeg"].device)
-            dst = c["eeg_scratch"]
-        c["aug_plan"] = ops.eeg_time_augment_into(eeg, None, dst, step=aug_step, rank=dp.rank(self.group),
-                                                  time_args=self.eeg_time_augment.kernel_args(eeg.shape[2]),
-                                                  base_args=self.augment.kernel_args(eeg.shape[1]) if self.augment is not None else None,
-                                                  plan=c.get("aug_plan"))
-        return dst
 
     def _replay(self):
         c = self._cap
@@ -1231,23 +1131,6 @@ class BridgeTrainer(TrainerCheckpointMixin, nn.Module):
         """the loop that feeds `train_step_packed` from pinned host buffers (see `HostFeeder`)"""
         self._no_packed_augment("host_feeder")
         return HostFeeder(self, depth)
-
-    def _no_packed_augment(self, who: str):
-        if self.classify:
-            raise ValueError(f"{who}: the packed host-fed path carries no class labels; feed a classify=True trainer "
-                             "through train_step(eeg, fmri, groups, labels)")
-        if self.augment is not None:
-            raise ValueError(f"{who}: this trainer has an augmenter, and a batch that is already packed to bf16 on the host "
-                             "cannot be augmented after the fact (the noise scale needs the fp32 sample); feed "
-                             "train_step(eeg, fmri) from device tensors, or build the trainer without augment=")
-        if self.eeg_time_augment is not None:
-            raise ValueError(f"{who}: this trainer has a temporal EEG augmenter, and a batch that is already packed to bf16 on "
-                             "the host cannot be augmented after the fact (the shift gathers from the fp32 sample); feed "
-                             "train_step(eeg, fmri) from device tensors, or build the trainer without eeg_time_augment=")
-        if self.fmri_augment is not None:
-            raise ValueError(f"{who}: this trainer has a volume augmenter, and the packed path copies the host's bytes straight "
-                             "into the static inputs the volume augmentation writes (one copy, no launch that could augment); "
-                             "feed train_step(eeg, fmri) from device tensors, or build the trainer without fmri_augment=")
 
     def time_collectives(self, batch: int, iters: int = 50) -> Dict[str, float]:
         """microseconds per call of every collective one step issues, each alone at its message size (HIP events on the

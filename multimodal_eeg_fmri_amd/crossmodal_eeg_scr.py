@@ -20,7 +20,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import ops
+from . import augment_stream as AS, ops
 from .bridge_utils import ImprovedTriModalFusionNet, WeightedCrossEntropy
 from .crossmodal_v4_enhancements import EnhancedSmartFusionNetV4, get_fusion_weights_from_model
 from .optim import FusedAdamW
@@ -206,32 +206,13 @@ def evaluate_late_fusion(roc_all: Dict) -> Dict:
             "erp_acc": np.mean(own(roc_all["erponly"])), "pw_acc": np.mean(own(roc_all["pwonly"]))}
 
 
-def _aug_hash(stream: int, idx: np.ndarray) -> np.ndarray:
-    """h(stream, idx) of csrc/augment.hip on a uint64 array of 32-bit indices -> uint64 array of 32-bit values"""
-    m = np.uint64(0xFFFFFFFF)
-    x = (idx.astype(np.uint64) * np.uint64(0x9E3779B1) + np.uint64(stream)) & m
-    x ^= x >> np.uint64(16)
-    x = (x * np.uint64(0x7FEB352D)) & m
-    x ^= x >> np.uint64(15)
-    x = (x + np.uint64(((stream << 16) | (stream >> 16)) & 0xFFFFFFFF)) & m
-    x = (x * np.uint64(0x846CA68B)) & m
-    x ^= x >> np.uint64(16)
-    return x
-
-
-def _aug_thresh(p: float) -> int:
-    """decision threshold of a probability, formed through double from its fp32 value (as the kernels' host code does)"""
-    p = float(np.float32(p))
-    return 0 if p <= 0.0 else 1 << 32 if p >= 1.0 else int(p * 4294967296.0)
-
-
-class EEGTransforms:
+class EEGTransforms(AS.StepCounter):
     """The notebook's augmenter (cell 18; handed to the training datasets as ``transform=``): with probability ``p``
     Gaussian noise of ``noise_factor * x.std()``, then with probability ``p`` ``max(1, int(0.1 * C))`` random channels
     zeroed.  Same positional signature; ``p_noise`` / ``p_drop`` (default ``p``) and ``drop_fraction`` split what the
     notebook ties together.
 
-    The random stream is this package's own (csrc/augment.hip), a pure function of (seed, step, rank, sample,
+    The random stream is this package's own (augment_stream.py), a pure function of (seed, step, rank, sample,
     element): ``batch`` on a device tensor runs the two HIP launches of ``ops.eeg_augment``, on a CPU tensor the same
     stream in numpy - the same decisions and dropped channels, the noise equal to fp32 rounding.  `BridgeTrainer(augment=)`
     augments each training step's EEG batch on the device; ``__call__`` is the per-sample dataset form."""
@@ -250,7 +231,6 @@ class EEGTransforms:
             raise ValueError(f"EEGTransforms: noise_factor must be a finite number >= 0 (got {noise_factor!r})")
         if not (isinstance(drop_fraction, numbers.Real) and 0.0 < drop_fraction <= 1.0):
             raise ValueError(f"EEGTransforms: drop_fraction must lie in (0, 1] (got {drop_fraction!r})")
-        self.calls = 0
 
     def n_drop(self, channels: int) -> int:
         return max(1, int(self.drop_fraction * channels))
@@ -278,23 +258,18 @@ class EEGTransforms:
         (B, C))"""
         B, C, T = a.shape
         n_drop = self.n_drop(C)
-        s = ops.augment_streams(self.seed, step, rank)
-        b = np.arange(B, dtype=np.uint64)
-        noise_on = _aug_hash(s[0], b) < np.uint64(_aug_thresh(self.p_noise))
-        drop_on = _aug_hash(s[1], b) < np.uint64(_aug_thresh(self.p_drop))
+        s = dict(zip(ops.AUG_PURPOSES, ops.augment_streams(self.seed, step, rank)))
+        h = AS.sample_draws("eeg", self.seed, step, rank, B)
+        noise_on, drop_on = AS.decide(h["noise_decision"], self.p_noise), AS.decide(h["drop_decision"], self.p_drop)
         scale, z = np.zeros(B, dtype=np.float32), None
         if noise_on.any():
             std = a.astype(np.float64).std(axis=(1, 2), ddof=1).astype(np.float32)
             scale = np.where(noise_on, np.float32(self.noise_factor) * std, np.float32(0)).astype(np.float32)
             half = (T + 1) // 2
-            idx = np.arange(B * C * half, dtype=np.uint64)
-            u1 = (_aug_hash(s[3], idx).astype(np.float64) + 1.0) * 2.0 ** -32
-            u2 = _aug_hash(s[4], idx).astype(np.float64) * 2.0 ** -32
-            r = np.sqrt(-2.0 * np.log(u1))
-            z = np.stack([r * np.cos(2.0 * np.pi * u2), r * np.sin(2.0 * np.pi * u2)], axis=-1).reshape(B, C, 2 * half)[:, :, :T]
+            z = AS.gauss_field(s["gauss_a"], s["gauss_b"], 0, B * C * half).reshape(B, C, 2 * half)[:, :, :T]
         dropped = np.zeros((B, C), dtype=bool)
         if drop_on.any():
-            keys = _aug_hash(s[2], np.arange(B * C, dtype=np.uint64)).reshape(B, C)
+            keys = AS.aug_hash(s["channel_keys"], np.arange(B * C, dtype=np.uint64)).reshape(B, C)
             order = np.argsort(keys, axis=1, kind="stable")          # ties by channel index
             ranks = np.empty_like(order)
             np.put_along_axis(ranks, order, np.broadcast_to(np.arange(C), (B, C)), axis=1)
@@ -318,23 +293,16 @@ class EEGTransforms:
         notebook: a flat feature vector drops single values); the call counter is the step index"""
         if x.dim() < 1:
             raise ValueError(f"EEGTransforms: expected a (channels, ...) sample, got shape {tuple(x.shape)}")
-        step, self.calls = self.calls, self.calls + 1
-        return self.batch(x.reshape(1, x.shape[0], -1), step).reshape(x.shape)
-
-    def state_dict(self) -> dict:
-        return {"seed": self.seed, "calls": self.calls}
-
-    def load_state_dict(self, sd: dict) -> None:
-        self.seed, self.calls = int(sd["seed"]), int(sd["calls"])
+        return self.batch(x.reshape(1, x.shape[0], -1), self.next_step()).reshape(x.shape)
 
 
-class EEGTimeTransforms:
+class EEGTimeTransforms(AS.StepCounter):
     """Temporal augmenter of (B, C, T) EEG batches (this package's own; the reference has none - DESIGN.md 5u).  Per sample,
     each with its own probability: an integer time shift ``s`` in ``[-max_shift, max_shift]`` (``out[t] = x[t - s]``,
     zeros where there is no source), an amplitude scale by ``1 + scale_range * (2u - 1)``, a polarity inversion, and one
     window of ``max(1, int(mask_fraction * T))`` samples zeroed on every channel.  A probability of 0 or 1 is valid.
 
-    The random stream is csrc/augment.hip's on purposes of its own (``ops.eeg_time_augment_streams``), a pure function of
+    The random stream is augment_stream.py's on purposes of its own (``ops.eeg_time_augment_streams``), a pure function of
     (seed, step, rank, sample).  ``batch`` on a device tensor is ONE HIP launch (mm_stage_inputs_taug), on a CPU tensor the
     same stream in numpy - the same decisions, shifts, gains and windows.  With ``base=`` an ``EEGTransforms`` its noise
     and channel drop ride in the same launch: the noise is indexed by the output position and scaled by the original
@@ -355,7 +323,6 @@ class EEGTimeTransforms:
             raise ValueError(f"EEGTimeTransforms: mask_fraction must lie in (0, 1] (got {mask_fraction!r})")
         self.p_shift, self.p_scale, self.p_invert, self.p_mask = p_shift, p_scale, p_invert, p_mask
         self.max_shift, self.scale_range, self.mask_fraction, self.seed = int(max_shift), scale_range, mask_fraction, int(seed)
-        self.calls = 0
 
     def mask_len(self, T: int) -> int:
         return max(1, int(self.mask_fraction * T))
@@ -399,17 +366,13 @@ class EEGTimeTransforms:
         """the per-sample draws of a step, on the host (numpy; what mm_stage_inputs_taug writes into its time plan):
         {"flags": {shift, scale, invert, mask: bool (B,)}, "shift": int (B,), "gain": fp32 (B,), "mask_start": int (B,),
         "mask_len": int (B,) (0 when off)}"""
-        s = dict(zip(ops.EEG_TIME_AUG_PURPOSES, ops.eeg_time_augment_streams(self.seed, step, rank)))
-        b = np.arange(B, dtype=np.uint64)
-        draw = lambda name: _aug_hash(s[name], b)  # noqa: E731
-        uniform = lambda name, n: ((draw(name) * np.uint64(n)) >> np.uint64(32)).astype(np.int64)  # noqa: E731
-        flags = {k: draw(k + "_decision") < np.uint64(_aug_thresh(getattr(self, "p_" + k))) for k in ops.EEG_TIME_AUG_FLAGS}
-        shift = (uniform("shift_amount", 2 * self.max_shift + 1) - self.max_shift) * flags["shift"]
-        u = draw("scale_u").astype(np.float64) * 2.0 ** -31 - 1.0
-        factor = np.where(flags["scale"], 1.0 + float(np.float32(self.scale_range)) * u, 1.0).astype(np.float32)
+        h = AS.sample_draws("eeg_time", self.seed, step, rank, B)
+        flags = {k: AS.decide(h[k + "_decision"], getattr(self, "p_" + k)) for k in ops.EEG_TIME_AUG_FLAGS}
+        shift = (AS.uniform(h["shift_amount"], 2 * self.max_shift + 1) - self.max_shift) * flags["shift"]
+        factor = np.where(flags["scale"], AS.scale_factor(self.scale_range, h["scale_u"]), np.float32(1.0))
         gain = np.where(flags["invert"], -factor, factor).astype(np.float32)
         L = self.mask_len(T)
-        return {"flags": flags, "shift": shift, "gain": gain, "mask_start": uniform("mask_start", T - L + 1) * flags["mask"],
+        return {"flags": flags, "shift": shift, "gain": gain, "mask_start": AS.uniform(h["mask_start"], T - L + 1) * flags["mask"],
                 "mask_len": L * flags["mask"].astype(np.int64)}
 
     def _batch_cpu(self, x: torch.Tensor, step: int, rank: int, base: Optional[EEGTransforms]) -> torch.Tensor:
@@ -436,14 +399,7 @@ class EEGTimeTransforms:
         """the per-sample dataset form: one (C, T) epoch -> a new tensor; the call counter is the step index"""
         if x.dim() != 2:
             raise ValueError(f"EEGTimeTransforms: expected a (C, T) sample, got shape {tuple(x.shape)}")
-        step, self.calls = self.calls, self.calls + 1
-        return self.batch(x.reshape(1, *x.shape), step).reshape(x.shape)
-
-    def state_dict(self) -> dict:
-        return {"seed": self.seed, "calls": self.calls}
-
-    def load_state_dict(self, sd: dict) -> None:
-        self.seed, self.calls = int(sd["seed"]), int(sd["calls"])
+        return self.batch(x.reshape(1, *x.shape), self.next_step()).reshape(x.shape)
 
 
 def _channels_first(x):

@@ -3,25 +3,11 @@
 // Fused into the launch that stages a training step's inputs (mm_stage_inputs): the augmented batch never exists as a
 // separate pass over the packed operand.
 //
-// ---- the random stream (tests/test_augment_*.py carry an fp64 replica of exactly this) ----------------
-// Counter based, stateless on the device, independent of the dropout stream (mm_hash / ops._seed_state).
-//
-//   h(stream, idx):   x  = idx * 0x9E3779B1 + stream            (all arithmetic mod 2^32)
-//                     x ^= x >> 16;  x *= 0x7FEB352D
-//                     x ^= x >> 15;  x += rotl(stream, 16);  x *= 0x846CA68B
-//                     x ^= x >> 16
-//   (the two multiply-xorshift rounds of the "lowbias32" integer mixer; the stream word enters twice, so that two
-//   streams are not index-shifted copies of each other)
-//
-//   stream(seed, step, rank, purpose), formed on the host in 64-bit arithmetic (mod 2^64):
-//                     z  = seed * 0x9E3779B97F4A7C15 + step * 0xBF58476D1CE4E5B9 + rank * 0x94D049BB133111EB
-//                          + (purpose + 1) * 0xD6E8FEB86659FD93
-//                     z ^= z >> 30;  z *= 0xBF58476D1CE4E5B9;  z ^= z >> 27;  z *= 0x94D049BB133111EB;  z ^= z >> 31
-//                     stream = (z ^ (z >> 32)) mod 2^32
-//   purpose: 0 noise decision, 1 drop decision, 2 channel keys, 3 gauss a, 4 gauss b
+// ---- the random stream: h(stream, idx), stream(seed, step, rank, purpose), thresh(p) and the uniform draw are
+// aug_stream.h's (tests/test_augment_*.py carry an fp64 replica).  This file's purposes: 0 noise decision,
+// 1 drop decision, 2 channel keys, 3 gauss a, 4 gauss b; mm_stage_inputs_taug's time draws use 19..25.
 //
 //   sample b:         noise on  iff  h(stream0, b) < thresh(p_noise),   drop on  iff  h(stream1, b) < thresh(p_drop)
-//                     thresh(p) = (uint64)((double)p * 2^32) for the fp32 value p (p = 1: 2^32, always on)
 //   channel c:        key_c = h(stream2, b * C + c); dropped iff drop is on and fewer than n_drop channels c' have
 //                     (key_c', c') < (key_c, c) lexicographically (= the first n_drop of a random permutation)
 //   elements (t, t+1), t even, of row (b, c) share the Box-Muller pair idx = (b * C + c) * ceil(T / 2) + t / 2:
@@ -45,6 +31,7 @@
 // plan (32-bit words; include/mmeeg_hip.h): per sample S = 4 + ceil(C / 32) words, rounded up to even -
 //   [0] noise scale (fp32; 0 = off), [1] std_b (fp32), [2] noise on, [3] drop on, [4...] channel mask (bit c % 32 of
 //   word c / 32) - then, from word B * S, the partials double[B][nchunk][2].
+#include "aug_stream.h"
 #include "common.h"
 #include "mmeeg_hip.h"
 
@@ -52,34 +39,18 @@ namespace {
 
 constexpr int AUG_HDR = 4;
 
-__device__ __forceinline__ uint32_t aug_hash(uint32_t stream, uint32_t idx) {
-    uint32_t x = idx * 0x9E3779B1u + stream;
-    x ^= x >> 16;
-    x *= 0x7FEB352Du;
-    x ^= x >> 15;
-    x += (stream << 16) | (stream >> 16);
-    x *= 0x846CA68Bu;
-    x ^= x >> 16;
-    return x;
-}
-
 struct AugShape { int stride, chunk, nchunk; int64_t words; };
 // the layout of the plan for (B, C, T): ops.eeg_augment_plan_words computes the same
 inline AugShape aug_shape(int B, int C, int T) {
     AugShape s;
     const int64_t ct = (int64_t)C * T;
     s.stride = (AUG_HDR + (C + 31) / 32 + 1) & ~1;
-    int64_t chunk = 4096;
-    while ((ct + chunk - 1) / chunk > 64) chunk *= 2;
-    s.chunk = (int)chunk;
-    s.nchunk = (int)((ct + chunk - 1) / chunk);
+    const AugChunks k = aug_chunks(ct);
+    s.chunk = k.chunk;
+    s.nchunk = k.nchunk;
     s.words = (int64_t)B * s.stride + 4 * (int64_t)B * s.nchunk;
     return s;
 }
-inline uint64_t aug_thresh(float p) {
-    return p <= 0.f ? 0ull : p >= 1.f ? (1ull << 32) : (uint64_t)((double)p * 4294967296.0);
-}
-
 struct PlanArgs {
     const float* x; uint32_t* plan;
     int B, C, T, stride, chunk, nchunk, n_drop, vec;
@@ -169,14 +140,6 @@ struct StageAugArgs {
 };
 
 enum { TF_SHIFT = 1, TF_SCALE = 2, TF_INVERT = 4, TF_MASK = 8 };
-
-__device__ __forceinline__ uint32_t aug_uniform(uint32_t h, uint32_t n) { return (uint32_t)(((uint64_t)h * n) >> 32); }
-
-// fp32( 1 + (double)scale_range * (h * 2^-31 - 1) ): fp64 operations in this order, each rounded on its own (no FMA)
-__device__ __forceinline__ float aug_scale_factor(float scale_range, uint32_t h) {
-#pragma clang fp contract(off)
-    return (float)(1.0 + (double)scale_range * ((double)h * 4.656612873077392578125e-10 - 1.0));
-}
 
 // the noise of the Box-Muller pair idx onto the two elements of a thread: ONE expression for both instances of the kernel
 // below, so that they round alike

@@ -3,16 +3,14 @@
 // axis, an integer translation, an intensity scale, Gaussian noise of noise_factor * std(sample), and one cuboid erased.
 // It sits beside the EEG augmenter (augment.hip) and follows it: counter-based draws, no state on the device, two launches.
 //
-// ---- the random stream (tests/test_volume_augment_*.py carry an fp64 replica of exactly this) ---------
-//   h(stream, idx) and stream(seed, step, rank, purpose) are augment.hip's, unchanged.  New purposes, one per decision and
-//   per drawn quantity (the EEG augmenter owns 0..4, so the two are independent at equal seed and step):
+// ---- the random stream: h(stream, idx), stream(seed, step, rank, purpose), thresh(p), the uniform draw and the scale
+// factor are aug_stream.h's (tests/test_volume_augment_*.py carry an fp64 replica).  This file's
+// purposes, one per decision and per drawn quantity:
 //     5 flip decision   6 shift decision   7 dz   8 dy   9 dx   10 scale decision   11 scale u   12 noise decision
 //     13 gauss a   14 gauss b   15 erase decision   16 erase z   17 erase y   18 erase x
 //   every draw of sample b is h(stream_k, b) (the noise: of the pair index below):
-//     decision on  iff  h < thresh(p), thresh(p) = (uint64)((double)p * 2^32) of the fp32 value p (p = 1: 2^32, always)
-//     uniform integer in [0, n):  (h * n) >> 32 in 64-bit arithmetic
 //     dz, dy, dx = uniform[0, 2 * max_shift + 1) - max_shift           (0, 0, 0 when the shift is off)
-//     factor = fp32( 1 + (double)scale_range * (h * 2^-31 - 1) )       (fp64 in this order, rounded once; 1.0f when off)
+//     factor = aug_scale_factor(scale_range, h)                        (1.0f when off)
 //     erase corner (ez, ey, ex) = uniform[0, D - ed + 1), [0, H - eh + 1), [0, W - ew + 1);  the extents ed, eh, ew
 //     = max(1, int(erase_fraction * D)), ... are formed on the host
 //   output voxel (z, y, x) of sample b, v = (z * H + y) * W + x, V = D * H * W:
@@ -45,6 +43,7 @@
 //   [13..15] 0 - then, from word 16 * B, the partials double[B][nchunk][2].  Words 11 and 12 are mm_volume_augment's.
 #include <cmath>
 
+#include "aug_stream.h"
 #include "common.h"
 #include "mmeeg_hip.h"
 
@@ -57,31 +56,15 @@ constexpr int VOL_HDR = 16;
 constexpr int VOL_PAIRS = 2048;                    // Box-Muller pairs per workgroup of mm_volume_augment (8 per thread)
 enum : uint32_t { VF_FLIP = 1, VF_SHIFT = 2, VF_SCALE = 4, VF_NOISE = 8, VF_ERASE = 16 };
 
-__device__ __forceinline__ uint32_t vol_hash(uint32_t stream, uint32_t idx) {      // augment.hip's h(stream, idx)
-    uint32_t x = idx * 0x9E3779B1u + stream;
-    x ^= x >> 16;
-    x *= 0x7FEB352Du;
-    x ^= x >> 15;
-    x += (stream << 16) | (stream >> 16);
-    x *= 0x846CA68Bu;
-    x ^= x >> 16;
-    return x;
-}
-__device__ __forceinline__ uint32_t vol_uniform(uint32_t h, uint32_t n) { return (uint32_t)(((uint64_t)h * n) >> 32); }
-
 struct VolShape { int chunk, nchunk; int64_t words; };
 // the layout of the plan for (B, V): ops.volume_augment_plan_layout computes the same
 inline VolShape vol_shape(int B, int64_t V) {
     VolShape s;
-    int64_t chunk = 4096;
-    while ((V + chunk - 1) / chunk > 64) chunk *= 2;
-    s.chunk = (int)chunk;
-    s.nchunk = (int)((V + chunk - 1) / chunk);
+    const AugChunks k = aug_chunks(V);
+    s.chunk = k.chunk;
+    s.nchunk = k.nchunk;
     s.words = (int64_t)B * VOL_HDR + 4 * (int64_t)B * s.nchunk;
     return s;
-}
-inline uint64_t vol_thresh(float p) {
-    return p <= 0.f ? 0ull : p >= 1.f ? (1ull << 32) : (uint64_t)((double)p * 4294967296.0);
 }
 inline bool prob_ok(float p) { return p >= 0.f && p <= 1.f; }
 
@@ -134,23 +117,23 @@ __global__ void __launch_bounds__(256) volume_augment_plan_kernel(VolPlanArgs a)
     uint32_t* hdr = a.plan + (size_t)b * VOL_HDR;
     const uint32_t ub = (uint32_t)b;
     uint32_t flags = 0;
-    if ((uint64_t)vol_hash(a.s_flip, ub) < a.t_flip) flags |= VF_FLIP;
-    if ((uint64_t)vol_hash(a.s_shift, ub) < a.t_shift) flags |= VF_SHIFT;
-    if ((uint64_t)vol_hash(a.s_scale, ub) < a.t_scale) flags |= VF_SCALE;
-    if ((uint64_t)vol_hash(a.s_noise, ub) < a.t_noise) flags |= VF_NOISE;
-    if ((uint64_t)vol_hash(a.s_erase, ub) < a.t_erase) flags |= VF_ERASE;
+    if ((uint64_t)aug_hash(a.s_flip, ub) < a.t_flip) flags |= VF_FLIP;
+    if ((uint64_t)aug_hash(a.s_shift, ub) < a.t_shift) flags |= VF_SHIFT;
+    if ((uint64_t)aug_hash(a.s_scale, ub) < a.t_scale) flags |= VF_SCALE;
+    if ((uint64_t)aug_hash(a.s_noise, ub) < a.t_noise) flags |= VF_NOISE;
+    if ((uint64_t)aug_hash(a.s_erase, ub) < a.t_erase) flags |= VF_ERASE;
     const bool sh = flags & VF_SHIFT, er = flags & VF_ERASE;
     const uint32_t span = 2u * (uint32_t)a.max_shift + 1u;
     hdr[0] = flags;
-    hdr[1] = (uint32_t)(sh ? (int)vol_uniform(vol_hash(a.s_dz, ub), span) - a.max_shift : 0);
-    hdr[2] = (uint32_t)(sh ? (int)vol_uniform(vol_hash(a.s_dy, ub), span) - a.max_shift : 0);
-    hdr[3] = (uint32_t)(sh ? (int)vol_uniform(vol_hash(a.s_dx, ub), span) - a.max_shift : 0);
+    hdr[1] = (uint32_t)(sh ? (int)aug_uniform(aug_hash(a.s_dz, ub), span) - a.max_shift : 0);
+    hdr[2] = (uint32_t)(sh ? (int)aug_uniform(aug_hash(a.s_dy, ub), span) - a.max_shift : 0);
+    hdr[3] = (uint32_t)(sh ? (int)aug_uniform(aug_hash(a.s_dx, ub), span) - a.max_shift : 0);
     float factor = 1.0f;
-    if (flags & VF_SCALE) factor = (float)(1.0 + (double)a.scale_range * ((double)vol_hash(a.s_scale_u, ub) * 4.656612873077392578125e-10 - 1.0));
+    if (flags & VF_SCALE) factor = aug_scale_factor(a.scale_range, aug_hash(a.s_scale_u, ub));
     hdr[4] = __float_as_uint(factor);
-    hdr[5] = er ? vol_uniform(vol_hash(a.s_ez, ub), (uint32_t)(a.D - a.ed + 1)) : 0u;
-    hdr[6] = er ? vol_uniform(vol_hash(a.s_ey, ub), (uint32_t)(a.H - a.eh + 1)) : 0u;
-    hdr[7] = er ? vol_uniform(vol_hash(a.s_ex, ub), (uint32_t)(a.W - a.ew + 1)) : 0u;
+    hdr[5] = er ? aug_uniform(aug_hash(a.s_ez, ub), (uint32_t)(a.D - a.ed + 1)) : 0u;
+    hdr[6] = er ? aug_uniform(aug_hash(a.s_ey, ub), (uint32_t)(a.H - a.eh + 1)) : 0u;
+    hdr[7] = er ? aug_uniform(aug_hash(a.s_ex, ub), (uint32_t)(a.W - a.ew + 1)) : 0u;
     hdr[8] = er ? (uint32_t)a.ed : 0u;
     hdr[9] = er ? (uint32_t)a.eh : 0u;
     hdr[10] = er ? (uint32_t)a.ew : 0u;
@@ -220,8 +203,8 @@ __global__ void __launch_bounds__(256) volume_augment_kernel(VolAugArgs a) {
         float z0 = 0.f, z1 = 0.f;
         if (p.ns != 0.f) {
             const uint32_t idx = (uint32_t)b * a.half + pi;
-            const float u1 = ((float)vol_hash(a.s_ga, idx) + 1.0f) * 2.3283064365386963e-10f;   // 2^-32
-            const float w2 = (float)vol_hash(a.s_gb, idx) * 4.6566128730773926e-10f;            // 2 u2
+            const float u1 = ((float)aug_hash(a.s_ga, idx) + 1.0f) * 2.3283064365386963e-10f;   // 2^-32
+            const float w2 = (float)aug_hash(a.s_gb, idx) * 4.6566128730773926e-10f;            // 2 u2
             const float r = sqrtf(-2.0f * logf(u1));
             float sn, cs;
             sincospif(w2, &sn, &cs);
@@ -268,8 +251,8 @@ int mm_volume_augment_plan(const float* x, uint32_t* plan, int64_t plan_words, i
     VolPlanArgs a;
     a.x = x; a.plan = plan; a.B = B; a.D = D; a.H = H; a.W = W; a.V = (uint32_t)V; a.chunk = s.chunk; a.nchunk = s.nchunk;
     a.max_shift = max_shift; a.ed = ed; a.eh = eh; a.ew = ew; a.scale_range = scale_range;
-    a.t_flip = vol_thresh(p_flip); a.t_shift = vol_thresh(p_shift); a.t_scale = vol_thresh(p_scale);
-    a.t_noise = vol_thresh(p_noise); a.t_erase = vol_thresh(p_erase);
+    a.t_flip = aug_thresh(p_flip); a.t_shift = aug_thresh(p_shift); a.t_scale = aug_thresh(p_scale);
+    a.t_noise = aug_thresh(p_noise); a.t_erase = aug_thresh(p_erase);
     a.s_flip = s_flip; a.s_shift = s_shift; a.s_dz = s_dz; a.s_dy = s_dy; a.s_dx = s_dx; a.s_scale = s_scale;
     a.s_scale_u = s_scale_u; a.s_noise = s_noise; a.s_erase = s_erase; a.s_ez = s_ez; a.s_ey = s_ey; a.s_ex = s_ex;
     hipLaunchKernelGGL(volume_augment_plan_kernel, dim3(B * s.nchunk), dim3(256), 0, st, a);

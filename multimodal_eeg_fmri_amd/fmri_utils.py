@@ -21,7 +21,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import ops
+from . import augment_stream as AS, ops
 
 logger = logging.getLogger(__name__)
 
@@ -224,7 +224,7 @@ class fMRIVolumeEncoder3D(nn.Module):
         return ops.volume_encoder_forward(self, x)
 
 
-class VolumeTransforms:
+class VolumeTransforms(AS.StepCounter):
     """Augmenter of (B, 1, D, H, W) fMRI volumes, the voxel encoder's counterpart of ``EEGTransforms`` (the reference has no
     volume code; the transform is defined in DESIGN.md 5q).  Per sample, in this order and each with its own probability:
     mirror of the W axis (``p_flip``), integer translation by up to ``max_shift`` voxels per axis (``p_shift``; voxels from
@@ -232,7 +232,7 @@ class VolumeTransforms:
     ``noise_factor`` x the original sample's standard deviation (``p_noise``), one cuboid of ``max(1, int(erase_fraction *
     extent))`` voxels per axis set to ``fill`` (``p_erase``).  A probability of 0 or 1 is a valid setting.
 
-    The random stream is csrc/augment.hip's on purposes of its own (``ops.volume_augment_streams``), a pure function of
+    The random stream is augment_stream.py's on purposes of its own (``ops.volume_augment_streams``), a pure function of
     (seed, step, rank, sample, voxel): ``batch`` on a device tensor runs the two HIP launches of ``ops.volume_augment``, on a
     CPU tensor the same stream in numpy - the same decisions, shifts and boxes, arithmetic equal to fp32 rounding.
     `BridgeTrainer(fmri_augment=)` augments each training step's fMRI batch on the device; ``__call__`` is the per-sample
@@ -257,7 +257,6 @@ class VolumeTransforms:
         self.p_flip, self.p_shift, self.p_scale, self.p_noise, self.p_erase = p_flip, p_shift, p_scale, p_noise, p_erase
         self.max_shift, self.scale_range, self.noise_factor = int(max_shift), scale_range, noise_factor
         self.erase_fraction, self.fill, self.seed = erase_fraction, fill, int(seed)
-        self.calls = 0
 
     def erase_extents(self, dims) -> tuple:
         """the erased cuboid's (ed, eh, ew) for a (D, H, W) volume"""
@@ -297,23 +296,17 @@ class VolumeTransforms:
         """the per-sample draws of a step, on the host (numpy; what mm_volume_augment_plan writes into its headers):
         {"flags": {flip, shift, scale, noise, erase: bool (B,)}, "shift": int (B, 3) = (dz, dy, dx), "factor": fp32 (B,),
         "erase_box": int (B, 6) = (ez, ey, ex, ed, eh, ew; zeros when off)}"""
-        from .crossmodal_eeg_scr import _aug_hash, _aug_thresh
-        s = dict(zip(ops.VOL_AUG_PURPOSES, ops.volume_augment_streams(self.seed, step, rank)))
-        b = np.arange(B, dtype=np.uint64)
-        draw = lambda name: _aug_hash(s[name], b)  # noqa: E731
-        uniform = lambda name, n: ((draw(name) * np.uint64(n)) >> np.uint64(32)).astype(np.int64)  # noqa: E731
-        flags = {k: draw(k + "_decision") < np.uint64(_aug_thresh(getattr(self, "p_" + k))) for k in ops.VOL_AUG_FLAGS}
+        h = AS.sample_draws("volume", self.seed, step, rank, B)
+        flags = {k: AS.decide(h[k + "_decision"], getattr(self, "p_" + k)) for k in ops.VOL_AUG_FLAGS}
         m = self.max_shift
-        shift = np.stack([uniform("shift_" + ax, 2 * m + 1) - m for ax in "zyx"], axis=1) * flags["shift"][:, None]
-        u = draw("scale_u").astype(np.float64) * 2.0 ** -31 - 1.0
-        factor = np.where(flags["scale"], 1.0 + float(np.float32(self.scale_range)) * u, 1.0).astype(np.float32)
+        shift = np.stack([AS.uniform(h["shift_" + ax], 2 * m + 1) - m for ax in "zyx"], axis=1) * flags["shift"][:, None]
+        factor = np.where(flags["scale"], AS.scale_factor(self.scale_range, h["scale_u"]), np.float32(1.0))
         ext = self.erase_extents(dims)
-        corner = [uniform("erase_" + ax, int(n) - e + 1) for ax, n, e in zip("zyx", dims, ext)]
+        corner = [AS.uniform(h["erase_" + ax], int(n) - e + 1) for ax, n, e in zip("zyx", dims, ext)]
         box = np.stack(corner + [np.full(B, e, dtype=np.int64) for e in ext], axis=1) * flags["erase"][:, None]
         return {"flags": flags, "shift": shift, "factor": factor, "erase_box": box}
 
     def _batch_cpu(self, x: torch.Tensor, step: int, rank: int, kw: dict) -> torch.Tensor:
-        from .crossmodal_eeg_scr import _aug_hash
         B, _, D, H, W = x.shape
         V, half = D * H * W, (D * H * W + 1) // 2
         a = x.detach().to(torch.float32).contiguous().numpy()
@@ -337,11 +330,7 @@ class VolumeTransforms:
                 std = np.float32(a[b].astype(np.float64).std(ddof=1))
                 ns = np.float32(self.noise_factor) * std
                 if ns != 0:
-                    idx = np.uint64(b * half) + np.arange(half, dtype=np.uint64)
-                    u1 = (_aug_hash(s["gauss_a"], idx).astype(np.float64) + 1.0) * 2.0 ** -32
-                    u2 = _aug_hash(s["gauss_b"], idx).astype(np.float64) * 2.0 ** -32
-                    r = np.sqrt(-2.0 * np.log(u1))
-                    z = np.stack([r * np.cos(2.0 * np.pi * u2), r * np.sin(2.0 * np.pi * u2)], axis=-1).reshape(-1)[:V]
+                    z = AS.gauss_field(s["gauss_a"], s["gauss_b"], b * half, half)[:V]
                     vol = np.where(inside, vol + z.astype(np.float32).reshape(D, H, W) * ns, vol)
             if d["flags"]["erase"][b]:
                 ez, ey, ex, ed, eh, ew = (int(v) for v in d["erase_box"][b])
@@ -354,14 +343,7 @@ class VolumeTransforms:
         index"""
         if x.dim() not in (3, 4) or (x.dim() == 4 and x.shape[0] != 1):
             raise ValueError(f"VolumeTransforms: expected a (1, D, H, W) or (D, H, W) volume, got shape {tuple(x.shape)}")
-        step, self.calls = self.calls, self.calls + 1
-        return self.batch(x.reshape(1, 1, *x.shape[-3:]), step).reshape(x.shape)
-
-    def state_dict(self) -> dict:
-        return {"seed": self.seed, "calls": self.calls}
-
-    def load_state_dict(self, sd: dict) -> None:
-        self.seed, self.calls = int(sd["seed"]), int(sd["calls"])
+        return self.batch(x.reshape(1, 1, *x.shape[-3:]), self.next_step()).reshape(x.shape)
 
 
 # ---------------------------------------------------------------------------

@@ -21,7 +21,7 @@ from typing import Dict, List, NamedTuple, Optional
 
 import torch
 
-from . import _hip
+from . import _hip, augment_stream
 
 ACT = {"none": 0, "gelu": 1, "relu": 2, "tanh": 3, "sigmoid": 4}
 _BF = torch.bfloat16
@@ -306,23 +306,20 @@ def pack_nct(x: torch.Tensor) -> torch.Tensor:
 
 # ---- EEG augmentation (csrc/augment.hip; the reference's EEGTransforms).  The stream is counter based and has nothing
 # to do with the dropout stream above: no state here, none on the device.
-AUG_PURPOSES = ("noise_decision", "drop_decision", "channel_keys", "gauss_a", "gauss_b")
-_M64 = (1 << 64) - 1
+AUG_PURPOSES = augment_stream.PURPOSES["eeg"]
 
 
 def augment_streams(seed: int, step: int, rank: int = 0) -> tuple:
-    """the five 32-bit stream words of one augmentation step, in `AUG_PURPOSES` order (csrc/augment.hip's header)"""
-    out = []
-    for purpose in range(len(AUG_PURPOSES)):
-        z = (int(seed) * 0x9E3779B97F4A7C15 + int(step) * 0xBF58476D1CE4E5B9 + int(rank) * 0x94D049BB133111EB
-             + (purpose + 1) * 0xD6E8FEB86659FD93) & _M64
-        z ^= z >> 30
-        z = z * 0xBF58476D1CE4E5B9 & _M64
-        z ^= z >> 27
-        z = z * 0x94D049BB133111EB & _M64
-        z ^= z >> 31
-        out.append((z ^ (z >> 32)) & 0xFFFFFFFF)
-    return tuple(out)
+    """the five 32-bit stream words of one augmentation step, in `AUG_PURPOSES` order: purposes 0..4 of augment_stream.py"""
+    return augment_stream.streams("eeg", seed, step, rank)
+
+
+def _aug_chunks(n: int) -> int:
+    """chunks a sample of ``n`` values is summed in: 4096 values each, doubled until there are at most 64 (csrc/aug_stream.h)"""
+    chunk = 4096
+    while (n + chunk - 1) // chunk > 64:
+        chunk *= 2
+    return (n + chunk - 1) // chunk
 
 
 def eeg_augment_check(B: int, C: int, T: int, n_drop: int, who: str = "eeg_augment"):
@@ -338,32 +335,8 @@ def eeg_augment_check(B: int, C: int, T: int, n_drop: int, who: str = "eeg_augme
 def eeg_augment_plan_layout(B: int, C: int, T: int):
     """(words, words per sample, chunks per sample) of mm_eeg_augment_plan's buffer (include/mmeeg_hip.h)"""
     stride = (4 + (C + 31) // 32 + 1) & ~1
-    chunk = 4096
-    while (C * T + chunk - 1) // chunk > 64:
-        chunk *= 2
-    nchunk = (C * T + chunk - 1) // chunk
+    nchunk = _aug_chunks(C * T)
     return B * stride + 4 * B * nchunk, stride, nchunk
-
-
-def eeg_augment_into(x: torch.Tensor, xb: Optional[torch.Tensor], out: Optional[torch.Tensor], *, p_noise: float, p_drop: float,
-                     noise_factor: float, n_drop: int, seed: int, step: int, rank: int = 0,
-                     fmri_dst: Optional[torch.Tensor] = None, fmri_src: Optional[torch.Tensor] = None,
-                     plan: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """the two launches: the plan of batch ``x`` (B, C, T) fp32, then the augmented batch into the packed bf16 operand
-    ``xb`` (B, T, cpad(C)) and / or the fp32 ``out`` (B, C, T), with the fMRI copy of mm_stage_inputs when given.
-    ``plan``: a buffer of `eeg_augment_plan_layout` words to reuse (a training loop keeps one per batch shape).
-    -> the plan buffer (int32 words)."""
-    _need_gpu(x)
-    B, C, T = x.shape
-    eeg_augment_check(B, C, T, n_drop)
-    words, _, _ = eeg_augment_plan_layout(B, C, T)
-    if plan is None:
-        plan = torch.empty(words, dtype=torch.int32, device=x.device)
-    s = augment_streams(seed, step, rank)
-    _hip.call("mm_eeg_augment_plan", x, plan, words, B, C, T, p_noise, p_drop, n_drop, s[0], s[1], s[2])
-    _hip.call("mm_stage_inputs_aug", x, plan, words, xb, out, B, C, T, cpad(C), noise_factor, s[3], s[4],
-              fmri_dst, fmri_src, 0 if fmri_src is None else fmri_src.numel())
-    return plan
 
 
 def eeg_augment_read_plan(plan: torch.Tensor, B: int, C: int, T: int):
@@ -375,46 +348,15 @@ def eeg_augment_read_plan(plan: torch.Tensor, B: int, C: int, T: int):
     return hdr[:, 2] != 0, bits.reshape(B, nw * 32)[:, :C] != 0, hdr[:, 1].contiguous().view(_F32)
 
 
-def eeg_augment(x: torch.Tensor, *, p_noise: float, p_drop: float, noise_factor: float, n_drop: int, seed: int, step: int,
-                rank: int = 0, packed: bool = False, return_plan: bool = False):
-    """EEGTransforms on a device batch (B, C, T): per sample, with probability ``p_noise``, Gaussian noise of
-    ``noise_factor`` x the sample's standard deviation, then with probability ``p_drop`` ``n_drop`` channels zeroed; the
-    draws are a function of (seed, step, rank) alone.  -> the augmented fp32 batch; with ``packed`` also its channels-last
-    bf16 image (B, T, cpad(C)), the first convolution's operand; with ``return_plan`` also (noise_on, drop_mask, std)."""
-    _need_gpu(x)
-    x = x.contiguous().float()
-    B, C, T = x.shape
-    out = _empty((B, C, T), _F32, x)
-    xb = _empty((B, T, cpad(C)), _BF, x) if packed else None
-    plan = eeg_augment_into(x, xb, out, p_noise=p_noise, p_drop=p_drop, noise_factor=noise_factor, n_drop=n_drop, seed=seed,
-                            step=step, rank=rank)
-    res = (out, xb) if packed else out
-    return (res, eeg_augment_read_plan(plan, B, C, T)) if return_plan else res
-
-
-# ---- fMRI volume augmentation (csrc/volume_augment.hip, DESIGN.md 5q): the same h(stream, idx) and stream(seed, step, rank,
-# purpose) as the EEG augmenter, on purposes of its own - the two are independent at equal seed and step.
-VOL_AUG_PURPOSES = ("flip_decision", "shift_decision", "shift_z", "shift_y", "shift_x", "scale_decision", "scale_u",
-                    "noise_decision", "gauss_a", "gauss_b", "erase_decision", "erase_z", "erase_y", "erase_x")
+# ---- fMRI volume augmentation (csrc/volume_augment.hip), on purposes of its own of the same stream
+VOL_AUG_PURPOSES = augment_stream.PURPOSES["volume"]
 VOL_AUG_FLAGS = ("flip", "shift", "scale", "noise", "erase")            # bit k of a plan's flag word
 _VOL_HDR = 16
 
 
-def _stream_word(seed: int, step: int, rank: int, purpose: int) -> int:
-    z = (int(seed) * 0x9E3779B97F4A7C15 + int(step) * 0xBF58476D1CE4E5B9 + int(rank) * 0x94D049BB133111EB
-         + (purpose + 1) * 0xD6E8FEB86659FD93) & _M64
-    z ^= z >> 30
-    z = z * 0xBF58476D1CE4E5B9 & _M64
-    z ^= z >> 27
-    z = z * 0x94D049BB133111EB & _M64
-    z ^= z >> 31
-    return (z ^ (z >> 32)) & 0xFFFFFFFF
-
-
 def volume_augment_streams(seed: int, step: int, rank: int = 0) -> tuple:
-    """the fourteen 32-bit stream words of one volume-augmentation step, in `VOL_AUG_PURPOSES` order: purposes 5, 6, ...,
-    18 of csrc/augment.hip's stream(seed, step, rank, purpose) (`augment_streams` holds 0..4)"""
-    return tuple(_stream_word(seed, step, rank, len(AUG_PURPOSES) + k) for k in range(len(VOL_AUG_PURPOSES)))
+    """the fourteen 32-bit stream words of one volume-augmentation step, in `VOL_AUG_PURPOSES` order: purposes 5..18"""
+    return augment_stream.streams("volume", seed, step, rank)
 
 
 def volume_augment_check(shape, *, p_flip: float, p_shift: float, max_shift: int, p_scale: float, scale_range: float,
@@ -449,10 +391,7 @@ def volume_augment_check(shape, *, p_flip: float, p_shift: float, max_shift: int
 
 def volume_augment_plan_layout(B: int, D: int, H: int, W: int):
     """(words, words per sample, chunks per sample) of mm_volume_augment_plan's buffer (include/mmeeg_hip.h)"""
-    V, chunk = D * H * W, 4096
-    while (V + chunk - 1) // chunk > 64:
-        chunk *= 2
-    nchunk = (V + chunk - 1) // chunk
+    nchunk = _aug_chunks(D * H * W)
     return B * _VOL_HDR + 4 * B * nchunk, _VOL_HDR, nchunk
 
 
@@ -510,18 +449,15 @@ def volume_augment(x: torch.Tensor, *, step: int, rank: int = 0, return_plan: bo
     return (out, volume_augment_read_plan(plan, x.shape[0], *x.shape[2:])) if return_plan else out
 
 
-# ---- temporal EEG augmentation (csrc/augment.hip's mm_stage_inputs_taug): the same h(stream, idx) and
-# stream(seed, step, rank, purpose) on purposes 19..25 - independent of the two augmenters above at equal seed and step.
-EEG_TIME_AUG_PURPOSES = ("shift_decision", "shift_amount", "scale_decision", "scale_u", "invert_decision", "mask_decision",
-                         "mask_start")
+# ---- temporal EEG augmentation (csrc/augment.hip's mm_stage_inputs_taug), on purposes of its own of the same stream
+EEG_TIME_AUG_PURPOSES = augment_stream.PURPOSES["eeg_time"]
 EEG_TIME_AUG_FLAGS = ("shift", "scale", "invert", "mask")              # bit k of a time plan's flag word
 _TIME_HDR = 8
 
 
 def eeg_time_augment_streams(seed: int, step: int, rank: int = 0) -> tuple:
     """the seven 32-bit stream words of one temporal-augmentation step, in `EEG_TIME_AUG_PURPOSES` order: purposes 19..25"""
-    first = len(AUG_PURPOSES) + len(VOL_AUG_PURPOSES)
-    return tuple(_stream_word(seed, step, rank, first + k) for k in range(len(EEG_TIME_AUG_PURPOSES)))
+    return augment_stream.streams("eeg_time", seed, step, rank)
 
 
 def eeg_time_augment_check(B: int, C: int, T: int, *, p_shift: float, max_shift: int, p_scale: float, scale_range: float,
@@ -546,43 +482,6 @@ def eeg_time_augment_check(B: int, C: int, T: int, *, p_shift: float, max_shift:
         eeg_augment_check(B, C, T, n_drop, who)
 
 
-def eeg_time_augment_into(x: torch.Tensor, xb: Optional[torch.Tensor], out: Optional[torch.Tensor], *, time_args: dict,
-                          base_args: Optional[dict] = None, step: int, rank: int = 0,
-                          fmri_dst: Optional[torch.Tensor] = None, fmri_src: Optional[torch.Tensor] = None,
-                          plan: Optional[torch.Tensor] = None, time_plan: Optional[torch.Tensor] = None):
-    """batch ``x`` (B, C, T) fp32 through the time transforms into the packed bf16 operand ``xb`` (B, T, cpad(C)) and / or
-    the fp32 ``out`` (B, C, T; NOT overlapping ``x``: the shift is a gather), with the fMRI copy of mm_stage_inputs when
-    given.  ``time_args``: `EEGTimeTransforms.kernel_args(T)`.  ``base_args`` None: ONE launch.  ``base_args`` =
-    `EEGTransforms.kernel_args(C)`: its noise and channel drop in the same launch, after mm_eeg_augment_plan (two launches);
-    ``plan`` is then a buffer of `eeg_augment_plan_layout` words to reuse.  ``time_plan``: (B, 8) int32 for the per-sample
-    draws (`eeg_time_augment_read_plan`), or None.  -> the EEG plan buffer (None without ``base_args``)."""
-    B, C, T = x.shape
-    t = dict(time_args)
-    seed = t.pop("seed")
-    eeg_time_augment_check(B, C, T, n_drop=None if base_args is None else base_args["n_drop"], **t)
-    if x.dtype != _F32 or (out is not None and (out.dtype != _F32 or tuple(out.shape) != (B, C, T))):
-        raise ValueError("eeg_time_augment_into: fp32 batches of one shape")
-    if out is not None and _overlap(x, out):
-        raise ValueError("eeg_time_augment_into: source and destination overlap (the shift is a gather: augment into another buffer)")
-    _need_gpu(x)
-    words, s, noise_factor = 0, (0, 0, 0, 0, 0), 0.0
-    if base_args is not None:
-        words, _, _ = eeg_augment_plan_layout(B, C, T)
-        if plan is None:
-            plan = torch.empty(words, dtype=torch.int32, device=x.device)
-        s = augment_streams(base_args["seed"], step, rank)
-        noise_factor = base_args["noise_factor"]
-        _hip.call("mm_eeg_augment_plan", x, plan, words, B, C, T, base_args["p_noise"], base_args["p_drop"], base_args["n_drop"],
-                  s[0], s[1], s[2])
-    else:
-        plan = None
-    ts = eeg_time_augment_streams(seed, step, rank)
-    _hip.call("mm_stage_inputs_taug", x, plan, words, xb, out, B, C, T, cpad(C), noise_factor, s[3], s[4],
-              t["p_shift"], int(t["max_shift"]), t["p_scale"], t["scale_range"], t["p_invert"], t["p_mask"], int(t["mask_len"]),
-              *ts, time_plan, fmri_dst, fmri_src, 0 if fmri_src is None else fmri_src.numel())
-    return plan
-
-
 def eeg_time_augment_read_plan(time_plan: torch.Tensor) -> dict:
     """a (B, 8) int32 time plan mm_stage_inputs_taug has written -> {"flags": {shift, scale, invert, mask: bool (B,)},
     "shift": int32 (B,), "gain": fp32 (B,), "mask_start": int32 (B,), "mask_len": int32 (B,) (0 when off)}"""
@@ -592,26 +491,100 @@ def eeg_time_augment_read_plan(time_plan: torch.Tensor) -> dict:
             "mask_len": hdr[:, 4].contiguous()}
 
 
-def eeg_time_augment(x: torch.Tensor, *, time_args: dict, base_args: Optional[dict] = None, step: int, rank: int = 0,
-                     packed: bool = False, return_plan: bool = False):
-    """EEGTimeTransforms (with ``base_args`` also an EEGTransforms) on a device batch (B, C, T); the draws are a function
-    of (seed, step, rank) alone.  -> the augmented fp32 batch (a new tensor); with ``packed`` also its channels-last bf16
-    image (B, T, cpad(C)); with ``return_plan`` also `eeg_time_augment_read_plan`'s dict (plus "base": `eeg_augment_read_plan`'s
-    tuple when ``base_args`` is given)."""
+# ---- the ONE host call of both EEG augmenters: `eeg_augment*` and `eeg_time_augment*` below are its public spellings
+def eeg_augmenters_into(x: torch.Tensor, xb: Optional[torch.Tensor], out: Optional[torch.Tensor], *, base_args: Optional[dict] = None,
+                        time_args: Optional[dict] = None, step: int, rank: int = 0, fmri_dst: Optional[torch.Tensor] = None,
+                        fmri_src: Optional[torch.Tensor] = None, plan: Optional[torch.Tensor] = None,
+                        time_plan: Optional[torch.Tensor] = None):
+    """batch ``x`` (B, C, T) fp32 through an `EEGTransforms` (``base_args`` = its `kernel_args(C)`), an `EEGTimeTransforms`
+    (``time_args`` = its `kernel_args(T)`) or both, into the packed bf16 operand ``xb`` (B, T, cpad(C)) and / or the fp32
+    ``out`` (B, C, T), with the fMRI copy of mm_stage_inputs when given.  The launches: base only - mm_eeg_augment_plan, then
+    mm_stage_inputs_aug; time only - mm_stage_inputs_taug alone (its draws need no plan); both - the plan, then
+    mm_stage_inputs_taug with the noise and the channel drop in the same launch.  With ``time_args`` ``out`` must not overlap
+    ``x``: the shift is a gather.  ``plan``: a buffer of `eeg_augment_plan_layout` words to reuse (a training loop keeps one
+    per batch shape); ``time_plan``: (B, 8) int32 for the per-sample time draws (`eeg_time_augment_read_plan`), or None.
+    -> the EEG plan buffer (int32 words; None without ``base_args``)."""
+    if base_args is None and time_args is None:
+        raise ValueError("eeg_augmenters_into: neither base_args nor time_args")
+    n_drop = None if base_args is None else base_args["n_drop"]
+    if time_args is None:
+        _need_gpu(x)
+        B, C, T = x.shape
+        eeg_augment_check(B, C, T, n_drop)
+    else:
+        B, C, T = x.shape
+        t = {k: v for k, v in time_args.items() if k != "seed"}
+        eeg_time_augment_check(B, C, T, n_drop=n_drop, **t)
+        if x.dtype != _F32 or (out is not None and (out.dtype != _F32 or tuple(out.shape) != (B, C, T))):
+            raise ValueError("eeg_time_augment_into: fp32 batches of one shape")
+        if out is not None and _overlap(x, out):
+            raise ValueError("eeg_time_augment_into: source and destination overlap (the shift is a gather: augment into another buffer)")
+        _need_gpu(x)
+    words, s, noise_factor = 0, (0, 0, 0, 0, 0), 0.0
+    if base_args is None:
+        plan = None
+    else:
+        words, _, _ = eeg_augment_plan_layout(B, C, T)
+        if plan is None:
+            plan = torch.empty(words, dtype=torch.int32, device=x.device)
+        s = augment_streams(base_args["seed"], step, rank)
+        noise_factor = base_args["noise_factor"]
+        _hip.call("mm_eeg_augment_plan", x, plan, words, B, C, T, base_args["p_noise"], base_args["p_drop"], n_drop, s[0], s[1], s[2])
+    stage = (x, plan, words, xb, out, B, C, T, cpad(C), noise_factor, s[3], s[4])
+    fmri = (fmri_dst, fmri_src, 0 if fmri_src is None else fmri_src.numel())
+    if time_args is None:
+        _hip.call("mm_stage_inputs_aug", *stage, *fmri)
+    else:
+        _hip.call("mm_stage_inputs_taug", *stage, t["p_shift"], int(t["max_shift"]), t["p_scale"], t["scale_range"], t["p_invert"],
+                  t["p_mask"], int(t["mask_len"]), *eeg_time_augment_streams(time_args["seed"], step, rank), time_plan, *fmri)
+    return plan
+
+
+def eeg_augmenters(x: torch.Tensor, *, base_args: Optional[dict] = None, time_args: Optional[dict] = None, step: int,
+                   rank: int = 0, packed: bool = False, return_plan: bool = False):
+    """`eeg_augmenters_into` on a device batch (B, C, T); the draws are a function of (seed, step, rank) alone.  -> the
+    augmented fp32 batch (a new tensor); with ``packed`` also its channels-last bf16 image (B, T, cpad(C)), the first
+    convolution's operand; with ``return_plan`` also what the launches drew: `eeg_augment_read_plan`'s tuple without
+    ``time_args``, else `eeg_time_augment_read_plan`'s dict (plus "base": that tuple when ``base_args`` is given)."""
     _need_gpu(x)
     x = x.contiguous().float()
     B, C, T = x.shape
     out = _empty((B, C, T), _F32, x)
     xb = _empty((B, T, cpad(C)), _BF, x) if packed else None
-    tp = torch.empty(B, _TIME_HDR, dtype=torch.int32, device=x.device) if return_plan else None
-    plan = eeg_time_augment_into(x, xb, out, time_args=time_args, base_args=base_args, step=step, rank=rank, time_plan=tp)
+    tp = torch.empty(B, _TIME_HDR, dtype=torch.int32, device=x.device) if return_plan and time_args is not None else None
+    plan = eeg_augmenters_into(x, xb, out, base_args=base_args, time_args=time_args, step=step, rank=rank, time_plan=tp)
     res = (out, xb) if packed else out
     if not return_plan:
         return res
+    base = None if plan is None else eeg_augment_read_plan(plan, B, C, T)
+    if tp is None:
+        return res, base
     info = eeg_time_augment_read_plan(tp)
-    if plan is not None:
-        info["base"] = eeg_augment_read_plan(plan, B, C, T)
+    if base is not None:
+        info["base"] = base
     return res, info
+
+
+def eeg_augment_into(x: torch.Tensor, xb: Optional[torch.Tensor], out: Optional[torch.Tensor], *, p_noise: float, p_drop: float,
+                     noise_factor: float, n_drop: int, seed: int, step: int, rank: int = 0,
+                     fmri_dst: Optional[torch.Tensor] = None, fmri_src: Optional[torch.Tensor] = None,
+                     plan: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`eeg_augmenters_into` with an `EEGTransforms` alone, its `kernel_args(C)` as keywords: the two launches"""
+    return eeg_augmenters_into(x, xb, out, base_args=dict(p_noise=p_noise, p_drop=p_drop, noise_factor=noise_factor, n_drop=n_drop, seed=seed),
+                               step=step, rank=rank, fmri_dst=fmri_dst, fmri_src=fmri_src, plan=plan)
+
+
+def eeg_augment(x: torch.Tensor, *, p_noise: float, p_drop: float, noise_factor: float, n_drop: int, seed: int, step: int,
+                rank: int = 0, packed: bool = False, return_plan: bool = False):
+    """EEGTransforms on a device batch (B, C, T): per sample, with probability ``p_noise``, Gaussian noise of
+    ``noise_factor`` x the sample's standard deviation, then with probability ``p_drop`` ``n_drop`` channels zeroed
+    (`eeg_augmenters`; with ``return_plan`` also (noise_on, drop_mask, std))"""
+    return eeg_augmenters(x, base_args=dict(p_noise=p_noise, p_drop=p_drop, noise_factor=noise_factor, n_drop=n_drop, seed=seed),
+                          step=step, rank=rank, packed=packed, return_plan=return_plan)
+
+
+# (the time spellings take the same keywords: `time_args`, optionally `base_args`)
+eeg_time_augment_into, eeg_time_augment = eeg_augmenters_into, eeg_augmenters
 
 
 def igemm(x: torch.Tensor, wf: torch.Tensor, taps: int, pad: int, cout: int, *,
