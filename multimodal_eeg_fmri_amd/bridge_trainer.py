@@ -33,13 +33,13 @@ import torch
 import torch.nn as nn
 
 from . import _hip, dp, ops, optim
-from .autograd import (GradBag, bridge_cls_bwd, contrastive_embed_bwd, contrastive_embed_bwd_da, deferred, erp_encoder_bwd,
-                       ffn_rows_bwd_fused, fmri_tab_bwd, power_encoder_bwd, volume_encoder_bwd)
+from .autograd import GradBag, bridge_cls_bwd, contrastive_embed_bwd, contrastive_embed_bwd_da, deferred, ffn_rows_bwd_fused
+from .bridge_branches import input_layout, select_eeg, select_fmri, step_schedule
 from .bridge_checkpoint import TrainerCheckpointMixin
 from .bridge_staging import TrainerStagingMixin
 from .bridge_utils import EEGfMRIContrastiveBridge, retrieval_metrics
 from .enhanced_models_v4 import EnhancedERPEncoder
-from .fmri_utils import fMRITabularEncoder, fMRIVolumeEncoder3D
+from .fmri_utils import fMRIVolumeEncoder3D
 from .optim import FlatBucket, check_ema_decay
 
 
@@ -144,14 +144,8 @@ class BridgeTrainer(TrainerCheckpointMixin, TrainerStagingMixin, nn.Module):
         self._bank_grouped = None                     # fixed by the first training step: do the bank rows carry group ids
         self._bank_pushes = 0                         # host mirror of the bank's `pushes` word (one push per training step)
         self._bank_live = bank_warmup == 0            # the running step's loss reads the bank (pushes >= warmup)
-        if fmri_encoder is not None:
-            if not isinstance(fmri_encoder, fMRITabularEncoder):
-                raise TypeError(f"BridgeTrainer: fmri_encoder must be an fMRITabularEncoder or None (the voxel encoder), got "
-                                f"{type(fmri_encoder).__name__}")
-            if fmri_encoder.hidden_dim != fmri_dim:
-                raise ValueError(f"BridgeTrainer: fmri_dim={fmri_dim} but the fMRITabularEncoder ends in "
-                                 f"{fmri_encoder.hidden_dim} features")
-        self._fmri_kind = "volume" if fmri_encoder is None else "tabular"
+        self._fmri = select_fmri(fmri_encoder, fmri_dim)      # the fMRI branch's entry of `bridge_branches.FMRI_BRANCHES`
+        self._fmri_kind = self._fmri.kind
         self.classify, self.ce_weight, self.num_classes = bool(classify), float(ce_weight), int(num_classes)
         cw = None
         if class_weight is not None:
@@ -182,23 +176,15 @@ class BridgeTrainer(TrainerCheckpointMixin, TrainerStagingMixin, nn.Module):
             from .fmri_utils import VolumeTransforms
             if not isinstance(fmri_augment, VolumeTransforms):
                 raise TypeError(f"BridgeTrainer: fmri_augment must be a VolumeTransforms (got {type(fmri_augment).__name__})")
-            if fmri_encoder is not None:
+            if not self._fmri.augmentable:
                 raise ValueError("BridgeTrainer: fmri_augment augments (B, 1, D, H, W) volumes; the fMRITabularEncoder's "
                                  "input is a feature table (build the trainer without fmri_augment=, or with the voxel encoder)")
         self.fmri_augment = fmri_augment
         self._fmri_aug_step = 0                       # step index the next train_step's volume augmentation draws with
         self.eeg_encoder = (EnhancedERPEncoder(eeg_channels, hidden_dim, num_layers, num_heads, dropout)
                             if eeg_encoder is None else eeg_encoder)
-        from .crossmodal_v4_enhancements import MultiScaleSTFTPowerEncoder
-        from .enhanced_models_v4 import EnhancedPowerEncoder
-        if isinstance(self.eeg_encoder, EnhancedERPEncoder):
-            self._eeg_kind = "erp"
-        elif isinstance(self.eeg_encoder, MultiScaleSTFTPowerEncoder):
-            self._eeg_kind = "stft"
-        elif isinstance(self.eeg_encoder, EnhancedPowerEncoder):
-            self._eeg_kind = "power"
-        else:
-            raise TypeError(f"BridgeTrainer: no tape for an EEG encoder of type {type(self.eeg_encoder).__name__}")
+        self._eeg = select_eeg(self.eeg_encoder)              # the EEG branch's entry of `bridge_branches.EEG_BRANCHES`
+        self._eeg_kind = self._eeg.kind               # (the checkpoint's "eeg_kind")
         self.fmri_encoder = fMRIVolumeEncoder3D(1, fmri_dim, dropout=dropout) if fmri_encoder is None else fmri_encoder
         self.head = EEGfMRIContrastiveBridge(hidden_dim, fmri_dim, bridge_dim, dropout, loss=loss, num_classes=num_classes)
         self.loss = loss
@@ -216,6 +202,8 @@ class BridgeTrainer(TrainerCheckpointMixin, TrainerStagingMixin, nn.Module):
         self.stamps = None                            # int64[16] device buffer when phase stamps are wanted
         self.force_segments = False                   # rehearsal: run the N > 1 segmented step even at world 1
         self._side_stream = None                      # created on first use (the host logic also constructs on CPU)
+        self.schedule = None                          # the `StepSchedule` of the last issued (or captured) step: for inspection only
+        self._bags = []                               # the last steps' gradient bags (they keep descriptor tables alive)
         self.lr, self.weight_decay, self.grad_clip = lr, weight_decay, grad_clip
         self.betas, self.eps = betas, eps
         br = self.head.bridge
@@ -226,7 +214,7 @@ class BridgeTrainer(TrainerCheckpointMixin, TrainerStagingMixin, nn.Module):
             if not is_proj(name) and not classify:
                 p.requires_grad_(False)
         # bucket order = the order in which gradients are NOT yet final, i.e. the reverse of when each layer group's
-        # all-reduce can start (`_seg_backward`): conv block 1 (last kernel of the chain) | conv blocks 2-3 (final once
+        # all-reduce can start (`step_schedule`): conv block 1 (last kernel of the chain) | conv blocks 2-3 (final once
         # the second hand-over has been flushed) | transformer stack + encoder head + projection heads + logit scale
         # (first hand-over) | fMRI encoder (its own, shorter backward).  Each group is one contiguous range of the
         # flat bucket, the fMRI encoder's the tail [fmri_lo, n).
@@ -242,16 +230,8 @@ class BridgeTrainer(TrainerCheckpointMixin, TrainerStagingMixin, nn.Module):
             getattr(self, name).requires_grad_(False).eval()
         if "eeg_encoder" in self._frozen:             # no EEG backward, no hand-over: the heads' gradients are final on the chain
             layout = [("heads", "main", head_params)]
-        elif self._eeg_kind == "erp":
-            cl = self.eeg_encoder.conv_layers
-            conv1 = list(cl[0].parameters()) + list(cl[1].parameters())
-            conv23 = [p for i in (4, 5, 9, 10) for p in cl[i].parameters()]
-            seen = {id(p) for p in conv1 + conv23}
-            rest = [p for p in self.eeg_encoder.parameters() if id(p) not in seen]
-            layout = [("eeg conv block 1", "main", conv1), ("eeg conv blocks 2-3", "handed1", conv23),
-                      ("eeg transformer stack + heads", "handed0", rest + head_params)]
         else:
-            layout = [("eeg encoder + heads", "main", list(self.eeg_encoder.parameters()) + head_params)]
+            layout = self._eeg.layout(self.eeg_encoder, head_params)
         layout.append(("fmri encoder", "fmri", list(self.fmri_encoder.parameters())))
         self.bucket = FlatBucket([p for _, _, ps in layout for p in ps], ema=self.ema_decay > 0)
         self.groups = []                            # (name, ready point, lo, hi) over the flat bucket, in bucket order
@@ -473,10 +453,7 @@ class BridgeTrainer(TrainerCheckpointMixin, TrainerStagingMixin, nn.Module):
 
     def _check_fmri(self, shape, training: bool, who: str):
         """the fMRI batch's shape, before the first launch of a step (or of its capture): ``ValueError`` otherwise"""
-        if self._fmri_kind == "volume":
-            ops.check_volume_shape(shape)
-        else:
-            ops.fmri_tab_check(self.fmri_encoder, shape, training, f"{who} (tabular fMRI encoder)")
+        self._fmri.check(self.fmri_encoder, shape, training, who)
 
     def _result(self, scal) -> Dict[str, torch.Tensor]:
         """the dict a step returns: views of the trainer's result words"""
@@ -501,8 +478,8 @@ class BridgeTrainer(TrainerCheckpointMixin, TrainerStagingMixin, nn.Module):
         ``ce_loss``, ``cls_correct`` and ``loss`` = contrastive_loss + ce_weight * ce_loss."""
         self._no_step_on_average("train_step")
         self._check_fmri(fmri.shape, "fmri_encoder" not in self._frozen, "train_step")   # before the first launch of the step (or of its capture)
-        if self._fmri_kind == "tabular" and fmri.is_cuda:
-            self.fmri_encoder.tickets(fmri.device)         # the forward launch's words exist before any capture
+        if self._fmri.capture_words is not None and fmri.is_cuda:
+            self._fmri.capture_words(self.fmri_encoder, fmri.device)   # the forward launch's words exist before any capture
         gid = ops.group_ids(groups, eeg.shape[0], None if self.mode == "graph" else eeg.device, "train_step")
         lab = self._labels(labels, eeg.shape[0], None if self.mode == "graph" else eeg.device, "train_step")
         if self._bank_size:
@@ -552,18 +529,19 @@ class BridgeTrainer(TrainerCheckpointMixin, TrainerStagingMixin, nn.Module):
         ze = torch.nn.functional.normalize(ep, dim=1, eps=1e-12)
         zf = torch.nn.functional.normalize(fp, dim=1, eps=1e-12)
         logits, fw, aw = ops.bridge_cls_rows(br, ep, fp)
-        if self.loss == "sigmoid":
-            lc, acc_e, acc_f = ops.sigmoid_loss(ze, zf, self.head.logit_scale, self.head.logit_bias, self.group, gid)
-        elif self._bank_size:
-            lc, acc_e, acc_f = self._bank_loss_autograd(ze, zf, gid)
-        else:
-            lc, acc_e, acc_f = ops.clip_loss(ze, zf, self.head.logit_scale, self.group, gid)
+        lc, acc_e, acc_f = self._loss_autograd(ze, zf, gid, True)
         ce = ops.weighted_cross_entropy(logits, lab.long(), self._class_weight)
         return lc, acc_e, acc_f, ce, logits
 
-    def _bank_loss_autograd(self, ze, zf, gid):
-        """a bank trainer's training loss on the differentiable surface (`ClipBankLossFn`: the bank is a constant of the
-        tape), then the push of the step's own rows - detached: nothing of it is on the tape"""
+    def _loss_autograd(self, ze, zf, gid, training: bool):
+        """-> (loss, acc_e, acc_f): the trainer's contrastive loss on the differentiable surface, `_seg_loss`'s choice.
+        A bank trainer's training step (``training``; everything else keeps the in-batch loss) scores against the bank
+        (`ClipBankLossFn`: the bank is a constant of the tape), then pushes its own rows - detached: nothing of it is on
+        the tape"""
+        if self.loss == "sigmoid":
+            return ops.sigmoid_loss(ze, zf, self.head.logit_scale, self.head.logit_bias, self.group, gid)
+        if not (training and self._bank_size):
+            return ops.clip_loss(ze, zf, self.head.logit_scale, self.group, gid)
         if self._bank_live:
             out = ops.clip_loss_bank(ze, zf, self.head.logit_scale, self._bank, gid, self._bank_warmup)
         else:                                          # a warm-up step: the in-batch loss, the bank only fills
@@ -575,23 +553,18 @@ class BridgeTrainer(TrainerCheckpointMixin, TrainerStagingMixin, nn.Module):
     def _step_autograd(self, eeg, fmri, gid=None, lab=None):
         b = self.bucket
         b.zero_grad()
+        out = {}
         if lab is not None:
             lc, acc_e, acc_f, ce, logits = self._forward_classify(eeg, fmri, gid, lab)
             loss = lc + self.ce_weight * ce
-            loss.backward()
-            b.absorb_autograd_grads()
-            self._seg_optimizer()
-            return {"loss": loss.detach(), "top1_e2f": acc_e, "top1_f2e": acc_f, "contrastive_loss": lc.detach(),
-                    "ce_loss": ce.detach(), "cls_correct": (logits.detach().argmax(dim=1) == lab).sum().float()}
-        if self._bank_size:                            # (`forward` keeps the in-batch loss)
-            ze, zf = self.head.embed(*self._encode(eeg, fmri))
-            loss, acc_e, acc_f = self._bank_loss_autograd(ze, zf, gid)
+            out = {"contrastive_loss": lc.detach(), "ce_loss": ce.detach(),
+                   "cls_correct": (logits.detach().argmax(dim=1) == lab).sum().float()}
         else:
-            loss, acc_e, acc_f = self.forward(eeg, fmri, gid)
+            loss, acc_e, acc_f = self._loss_autograd(*self.head.embed(*self._encode(eeg, fmri)), gid, True)
         loss.backward()
         b.absorb_autograd_grads()
         self._seg_optimizer()
-        return {"loss": loss.detach(), "top1_e2f": acc_e, "top1_f2e": acc_f}
+        return {"loss": loss.detach(), "top1_e2f": acc_e, "top1_f2e": acc_f, **out}
 
     # ---- the segments of the autograd-free tape ------------------------------
     STAMP_NAMES = ("step start", "weights prepared", "EEG fwd done", "fMRI fwd start", "fMRI fwd done",
@@ -621,24 +594,22 @@ class BridgeTrainer(TrainerCheckpointMixin, TrainerStagingMixin, nn.Module):
         # The longer branch is issued FIRST: a hipGraph replay writes its kernel packets in capture order at
         # ~4.6 us per node, and the branch captured second cannot start before the host has written every packet
         # of the first (profiles/README.md).  That is the EEG chain at 32^3 voxels, the fMRI branch at config #4's
-        # 64 x 64 x 48 (`_fmri_is_longer`).
-        self._fmri_longer = self._fmri_is_longer(fmri)
+        # 64 x 64 x 48 (`step_schedule`; which row-wise backward the saved blocks take bears on the backward only).
+        def schedule(fused_rows):
+            return step_schedule(self._eeg_kind, self._fmri_kind, self._frozen, tuple(fmri.shape[1:]), fused_rows, os.environ)
+        sched = schedule(False)
 
         def fmri_branch():
             with torch.cuda.stream(self._side):
-                self._stamp(3)
-                live = "fmri_encoder" not in self._frozen     # frozen: the eval form, nothing saved, no seed drawn
-                if self._fmri_kind == "tabular":         # one launch
-                    out = ops._tab_forward_impl(self.fmri_encoder, fmri, live, live)
-                else:
-                    out = ops._vol_forward_impl(self.fmri_encoder, fmri, live, live)
+                self._stamp(3)                           # (frozen: the eval form, nothing saved, no seed drawn)
+                out = self._fmri.forward(self.fmri_encoder, fmri, sched.fmri_live)
                 self._stamp(4)
             return out
-        if self._fmri_longer:
+        if sched.fmri_first:
             ff, sv_f = fmri_branch()
-        fe, sv_e = self._eeg_forward(eeg, xb)
+        fe, sv_e = self._eeg.forward(self.eeg_encoder, eeg, xb, sched.eeg_live)
         self._stamp(2)
-        if not self._fmri_longer:
+        if not sched.fmri_first:
             ff, sv_f = fmri_branch()
         main.wait_stream(self._side)
         z, sv_h = ops.contrastive_embed_impl(self.head.bridge, fe, ff, True)
@@ -648,29 +619,10 @@ class BridgeTrainer(TrainerCheckpointMixin, TrainerStagingMixin, nn.Module):
             sv_c = ops.bridge_cls_forward_impl(self.head.bridge, sv_h, True, lab, self._class_weight, self.ce_weight,
                                                loss_out=self._scal[o:o + 4], ticket=self._cls_ticket)[3]
         self._stamp(5)
-        return z, (sv_e, sv_f, sv_h, sv_c)
-
-    @staticmethod
-    def _fmri_is_longer(fmri) -> bool:
-        """the voxel branch outlasts the EEG chain (config #4: 64 x 64 x 48 = 6 x the voxels of 32^3, 1.4 ms of kernels
-        against 1.1 ms): its stream then takes no work from the chain and is issued first.  MM_FMRI_LONGER=0/1 overrides."""
-        if fmri.dim() != 5:                            # the tabular branch is two launches: never the longer one
-            return False
-        env = os.environ.get("MM_FMRI_LONGER")
-        if env is not None:
-            return env == "1"
-        return fmri[0].numel() >= 4 * 32 ** 3
-
-    def _eeg_forward(self, eeg, xb):
-        enc = self.eeg_encoder
-        live = "eeg_encoder" not in self._frozen          # frozen: the eval form, nothing saved, no seed drawn
-        if self._eeg_kind == "erp":
-            return ops._erp_forward_impl(enc, eeg, live, live, xb=xb)
-        if self._eeg_kind == "power":
-            return ops._power_forward_impl(enc, xb if xb is not None else ops.pack_nct(eeg), live, False)
-        # config #5: the parameter-free multi-scale STFT power front-end (z-scored per sample), then a4
-        spec = ops.stft_front_end(eeg, enc.n_ffts, enc.hop, enc.normalize)
-        return ops._power_forward_impl(enc.encoder, spec, live, False)
+        # the backward's schedule travels with what the forward saved (across a graph-segment boundary too): the same
+        # pure function, asked again now that the saved blocks say which row-wise backward they take
+        self.schedule = sched = schedule(sched.eeg_live and ffn_rows_bwd_fused(sv_e.get("blocks")))
+        return z, (sv_e, sv_f, sv_h, sv_c, sched)
 
     def _seg_loss(self, z_all, scal, dz, gid_all=None):
         """symmetric InfoNCE of this rank's rows against the gathered batch, gradient w.r.t. ITS rows only
@@ -705,8 +657,13 @@ class BridgeTrainer(TrainerCheckpointMixin, TrainerStagingMixin, nn.Module):
         """``reduce``: all-reduce every layer group of the gradient bucket as soon as it is final - the fMRI encoder's
         after that branch's backward, the transformer stack's and conv blocks 3-2's after their handed-over sums were
         flushed on the side stream (all three hidden beside the EEG chain), conv block 1's after the chain"""
-        sv_e, sv_f, sv_h, sv_c = saved
+        sv_e, sv_f, sv_h, sv_c, sched = saved
         self._works = []
+        pending = list(sched.reduce_order) if reduce else []
+
+        def reduce_ready(ready):                 # the schedule's next collective, once ``ready``'s gradients are final
+            if pending and pending[0][0] == ready:
+                self._reduce_group(pending.pop(0)[0])
         bag = GradBag()
         with deferred(bag, dz.device):           # ONE batched reduction after both branches joined
             # d loss / d logit_scale (scal[3]) rides in the same batched reduction launch
@@ -722,16 +679,10 @@ class BridgeTrainer(TrainerCheckpointMixin, TrainerStagingMixin, nn.Module):
             self._stamp(7)
             main = torch.cuda.current_stream()
             self._side.wait_stream(main)
-            # the transformer stack's weight-gradient slot sums and parameter reductions (~50 MB of
-            # reads) do not wait for the end of the chain: they are handed to the side stream, which
-            # is idle once the fMRI branch is done - unless that branch is the longer one (`_fmri_is_longer`): then
-            # nothing is handed over, the chain flushes its own sums, and the fMRI backward is issued first
-            eeg_live, fmri_live = "eeg_encoder" not in self._frozen, "fmri_encoder" not in self._frozen
-            hand = not getattr(self, "_fmri_longer", False) and eeg_live   # (a frozen EEG encoder hands nothing over)
-            handed = []
+            handed = []                          # (`step_schedule`: why, and when, the chain hands its sums to the side stream)
 
             def split():
-                if not hand:
+                if not sched.hand:
                     return
                 ev = torch.cuda.Event()
                 handed.append((bag.hand_over(), ev))
@@ -742,65 +693,43 @@ class BridgeTrainer(TrainerCheckpointMixin, TrainerStagingMixin, nn.Module):
             def split_convs():
                 split()
                 bag.defer_conv_wgrads = False
-            # MM_CONV_WGRADS_HANDED: 1 = block 2's only (default: block 3's weight gradient stays on the chain), 2 = blocks 3
-            # and 2 (round 2 / early round 3, when the chain was the later stream), 0 = none.  Which stream ends later
-            # decides: 0.773-0.776 / 0.782-0.799 / 0.789-0.793 ms per step for 1 / 2 / 0 (profiles/r03_second_half_ab.txt).
-            # With the blocks' row-wise backward in one launch (mm_ffn_rows_bwd) the chain is ~40 us shorter and the side
-            # stream ends last: the default is then 0 (0.735-0.738 against 0.751-0.758 ms for 1, profiles/ffn_rows_bwd_ab.txt)
-            fused_rows = self._eeg_kind == "erp" and eeg_live and ffn_rows_bwd_fused(sv_e.get("blocks"))
-            handed_convs = int(os.environ.get("MM_CONV_WGRADS_HANDED", "0" if fused_rows else "1")) if hand else 0
-            bag.defer_conv_wgrads = handed_convs >= 2
+            bag.defer_conv_wgrads = sched.handed_convs >= 2
 
             def conv3_done():
-                bag.defer_conv_wgrads = handed_convs >= 1
+                bag.defer_conv_wgrads = sched.handed_convs >= 1
 
             def fmri_branch():
                 with torch.cuda.stream(self._side):
                     self._stamp(9)
                     bag_f = GradBag()                    # the fMRI branch flushes its own reductions on ITS stream,
                     with deferred(bag_f, dz.device):     # hidden beside the rest of the EEG backward
-                        if not fmri_live:                    # frozen: no backward launch of this encoder
-                            pass
-                        elif self._fmri_kind == "tabular":   # one launch, plain stores into the bucket's fMRI range
-                            fmri_tab_bwd(bag_f, sv_f, dff)
-                        else:
-                            volume_encoder_bwd(bag_f, sv_f, dff)
+                        if sched.fmri_live:              # (frozen: no backward launch of this encoder)
+                            self._fmri.backward(bag_f, sv_f, dff)
                     self._stamp(10)
-                    if reduce and hand:
-                        self._reduce_group("fmri")
+                    reduce_ready("fmri")
                     for i, (hb, ev) in enumerate(handed):
                         self._side.wait_event(ev)
                         hb.flush(dz.device)
-                        if reduce:
-                            self._reduce_group(f"handed{i}")
+                        reduce_ready(f"handed{i}")
                     self._stamp(13)
                 return bag_f
-            if not hand:
+            if not sched.hand:
                 bag_f = fmri_branch()
             finish = None
-            if not eeg_live:                     # frozen: no backward launch of this encoder
-                pass
-            elif self._eeg_kind == "erp":
-                erp_encoder_bwd(bag, sv_e, dfe, after_blocks=split, after_conv2=split_convs, after_conv3=conv3_done)   # longer chain first (see _seg_forward)
-            else:
-                _, finish = power_encoder_bwd(bag, sv_e, dfe)
+            if sched.eeg_live:                   # (frozen: no backward launch of this encoder); longer chain first (see _seg_forward)
+                finish = self._eeg.backward(bag, sv_e, dfe, after_blocks=split, after_conv2=split_convs, after_conv3=conv3_done)
             bag.flush(dz.device)
             if finish is not None:
-                finish()                         # the merged 192-channel conv / BatchNorm gradients back into the six real parameters
+                finish()
             self._stamp(8)
-            if hand:
+            if sched.hand:
                 bag_f = fmri_branch()
-            if reduce:
-                if not hand:                     # the chain's groups are final first; the fMRI encoder's goes out last
-                    self._reduce_group("handed0")
-                    self._reduce_group("handed1")
-                self._reduce_group("main")       # issued last on the host: the collectives run in issue order
-                if not hand:
-                    with torch.cuda.stream(self._side):
-                        self._reduce_group("fmri")
+            for ready, stream in pending:        # what only the chain's end makes final (the collectives run in host issue order)
+                with torch.cuda.stream(self._side) if stream == "side" else contextlib.nullcontext():
+                    self._reduce_group(ready)
             main.wait_stream(self._side)
         self._stamp(11)
-        self._bags = getattr(self, "_bags", [])[-12:] + [bag, bag_f] + [hb for hb, _ in handed]   # keep descriptor tables alive
+        self._bags = self._bags[-12:] + [bag, bag_f] + [hb for hb, _ in handed]   # keep descriptor tables alive
 
     def _seg_optimizer(self, reduced: bool = False):
         """``reduced``: the backward issued the per-group all-reduces (wait for them); else ONE all-reduce of the whole bucket"""
@@ -848,23 +777,18 @@ class BridgeTrainer(TrainerCheckpointMixin, TrainerStagingMixin, nn.Module):
         dev = eeg.device
         if self._cls_ticket is not None:
             self._cls_ticket.zero_()                      # (a launch that died mid-count would have left it non-zero)
-        if self._fmri_kind == "tabular":
-            self.fmri_encoder.tickets(dev).zero_()
+        if self._fmri.capture_words is not None:
+            self._fmri.capture_words(self.fmri_encoder, dev).zero_()
         world = self.world
         c = {"epoch": torch.zeros(1, dtype=torch.int32, device=dev)}
-        # the step's static inputs are views of ONE flat buffer `c["in"]` = [EEG operand | fMRI volumes fp32 | group ids
-        # int32 (grouped captures only) | class labels int32 (labelled captures only)], so that a host-fed loop fills them with a single copy (`train_step_packed`).
-        # EEG operand: the first convolution's packed bf16 (B, T, Cp) image (the STFT front-end reads the raw fp32 batch
-        # instead and keeps that)
-        stft = self._eeg_kind == "stft"
+        # the step's static inputs are views of ONE flat buffer `c["in"]` (`bridge_branches.input_layout`), so that a
+        # host-fed loop fills them with a single copy (`train_step_packed`)
         Bx, Cx, Tx = eeg.shape
-        n_e = eeg.numel() * 4 if stft else Bx * Tx * ops.cpad(Cx) * 2
-        n_f = fmri.numel() * 4
         c["grouped"] = gid is not None
         c["labelled"] = lab is not None
         c["bank_live"] = self._bank_live              # which loss the recorded step launches (a bank trainer's warm-up)
-        n_g = Bx * 4 if c["grouped"] else 0
-        c["in"] = torch.empty(n_e + n_f + n_g + (Bx * 4 if c["labelled"] else 0), dtype=torch.uint8, device=dev)
+        n_e, n_f, n_g, n_l = input_layout(self._eeg, eeg.shape, fmri.numel(), c["grouped"], c["labelled"])
+        c["in"] = torch.empty(n_e + n_f + n_g + n_l, dtype=torch.uint8, device=dev)
         c["fmri"] = c["in"][n_e:n_e + n_f].view(torch.float32).view(fmri.shape)
         c["fmri"].copy_(fmri)
         c["gid"] = c["gid_all"] = None
@@ -875,7 +799,7 @@ class BridgeTrainer(TrainerCheckpointMixin, TrainerStagingMixin, nn.Module):
         if c["labelled"]:
             c["lab"] = c["in"][n_e + n_f + n_g:].view(torch.int32)
             c["lab"].copy_(lab)
-        if stft:
+        if self._eeg.raw_input:
             c["eeg"], c["xb"] = c["in"][:n_e].view(torch.float32).view(eeg.shape), None
             c["eeg"].copy_(eeg)
         else:
@@ -926,7 +850,6 @@ class BridgeTrainer(TrainerCheckpointMixin, TrainerStagingMixin, nn.Module):
         B = eeg.shape[0]
         N2 = 2 * self.head.bridge.bridge_dim
         c["scal"] = self._scal
-        import os
         dist_step = not (world == 1 and not (self.force_segments and self.group is not None))
         # a grouped step gathers its ids when it issues collectives (world > 1, or MM_DP_FORCE); else they are the local ones
         c["gid_gather"] = c["grouped"] and dist_step and dp.active(self.group)
@@ -1090,23 +1013,21 @@ class BridgeTrainer(TrainerCheckpointMixin, TrainerStagingMixin, nn.Module):
         self._no_packed_augment("pack_host_batch")
         gid = ops.group_ids(groups.detach().cpu() if groups is not None else None, eeg.shape[0], None, "pack_host_batch")
         eeg, fmri = eeg.detach().cpu().float(), fmri.detach().cpu().float().contiguous()
-        if self._eeg_kind == "stft":
+        if self._eeg.raw_input:
             e_bytes = eeg.contiguous().view(-1).view(torch.uint8)
         else:
             B, C, T = eeg.shape
-            cp = ops.cpad(C)
-            xb = torch.zeros(B, T, cp, dtype=torch.bfloat16)
+            xb = torch.zeros(B, T, ops.cpad(C), dtype=torch.bfloat16)
             xb[:, :, :C] = eeg.permute(0, 2, 1)
             e_bytes = xb.view(-1).view(torch.uint8)
-        f_bytes = fmri.view(-1).view(torch.uint8)
-        g_bytes = gid.view(torch.uint8) if gid is not None else torch.empty(0, dtype=torch.uint8)
-        n_e, n_f = e_bytes.numel(), f_bytes.numel()
-        n = n_e + n_f + g_bytes.numel()
+        n_e, n_f, n_g, _ = input_layout(self._eeg, eeg.shape, fmri.numel(), gid is not None)
+        n = n_e + n_f + n_g
         if out is None:
             out = torch.empty(n, dtype=torch.uint8).pin_memory()
         out[:n_e].copy_(e_bytes)
-        out[n_e:n_e + n_f].copy_(f_bytes)
-        out[n_e + n_f:n].copy_(g_bytes)
+        out[n_e:n_e + n_f].copy_(fmri.view(-1).view(torch.uint8))
+        if gid is not None:
+            out[n_e + n_f:n].copy_(gid.view(torch.uint8))
         return out
 
     def train_step_packed(self, flat: torch.Tensor) -> Dict[str, torch.Tensor]:
@@ -1166,16 +1087,26 @@ class BridgeTrainer(TrainerCheckpointMixin, TrainerStagingMixin, nn.Module):
         a loader that writes the next batch straight into them saves the two device copies per step"""
         return None if self._cap is None else (self._cap["eeg"], self._cap["fmri"])
 
+    @contextlib.contextmanager
+    def _eval_scope(self):
+        """the eval form of every module inside; on exit each module's own train / eval flag is what it was (a frozen
+        or hand-set sub-module stays as it is)"""
+        modes = [(m, m.training) for m in self.modules()]
+        self.eval()
+        ops.weights_changed()                      # graph replays bypass the python-side version counter
+        try:
+            yield
+        finally:
+            for m, mode in modes:
+                m.training = mode
+
     @torch.no_grad()
     def evaluate(self, eeg, fmri, groups=None, labels=None):
         """eval-mode loss and in-batch top-1 of one batch (``groups``, ``labels``: as in `train_step`; with labels also
         ``contrastive_loss``, ``ce_loss`` and ``cls_correct``, and ``loss`` is their weighted sum)"""
         lab = self._labels(labels, eeg.shape[0], eeg.device, "evaluate")
         self._check_fmri(fmri.shape, False, "evaluate")
-        was = self.training
-        self.eval()
-        ops.weights_changed()                      # graph replays bypass the python-side version counter
-        try:
+        with self._eval_scope():
             if lab is None:
                 loss, acc_e, acc_f = self.forward(eeg, fmri, groups)
                 return {"loss": loss, "top1_e2f": acc_e, "top1_f2e": acc_f}
@@ -1185,14 +1116,9 @@ class BridgeTrainer(TrainerCheckpointMixin, TrainerStagingMixin, nn.Module):
             z, sv_h = ops.contrastive_embed_impl(br, fe, ff, False)
             cls = ops.bridge_cls_forward_impl(br, sv_h, False, lab, self._class_weight, self.ce_weight)[3]["loss"]
             N = br.bridge_dim
-            if self.loss == "sigmoid":
-                lc, acc_e, acc_f = ops.sigmoid_loss(z[:, :N], z[:, N:], self.head.logit_scale, self.head.logit_bias, self.group, gid)
-            else:
-                lc, acc_e, acc_f = ops.clip_loss(z[:, :N], z[:, N:], self.head.logit_scale, self.group, gid)
+            lc, acc_e, acc_f = self._loss_autograd(z[:, :N], z[:, N:], gid, False)
             return {"loss": lc + cls[3], "top1_e2f": acc_e, "top1_f2e": acc_f, "contrastive_loss": lc, "ce_loss": cls[0],
                     "cls_correct": cls[1]}
-        finally:
-            self.train(was)
 
     @torch.no_grad()
     def predict(self, eeg, fmri, batch_size: int = 256) -> Dict[str, torch.Tensor]:
@@ -1207,18 +1133,13 @@ class BridgeTrainer(TrainerCheckpointMixin, TrainerStagingMixin, nn.Module):
             raise ValueError("predict: batch_size must be >= 1")
         dev = self._scal.device
         br = self.head.bridge
-        was = self.training
-        self.eval()
-        ops.weights_changed()                      # graph replays bypass the python-side version counter
-        try:
+        with self._eval_scope():
             outs = []
             for x, y in zip(self._chunks(eeg, batch_size, dev), self._chunks(fmri, batch_size, dev)):
                 self._check_fmri(y.shape, False, "predict")
                 fe, ff = self._encode(x, y)
                 _, sv_h = ops.contrastive_embed_impl(br, fe, ff, False)
                 outs.append(ops.bridge_cls_forward_impl(br, sv_h, False)[:3])
-        finally:
-            self.train(was)
         logits, fw, aw = (torch.cat(t) for t in zip(*outs))
         return {"logits": logits, "probs": torch.softmax(logits, dim=1), "pred": logits.argmax(dim=1),
                 "fusion_weights": fw, "attn_weights": aw}
@@ -1250,10 +1171,7 @@ class BridgeTrainer(TrainerCheckpointMixin, TrainerStagingMixin, nn.Module):
             raise ValueError("embed: batch_size must be >= 1")
         dev = self._scal.device
         br = self.head.bridge
-        was = self.training
-        self.eval()
-        ops.weights_changed()                      # graph replays bypass the python-side version counter
-        try:
+        with self._eval_scope():
             ze = zf = None
             if eeg is not None:
                 ze = torch.cat([ops.proj_embed_one(br, self.eeg_encoder(x), "eeg")
@@ -1261,8 +1179,6 @@ class BridgeTrainer(TrainerCheckpointMixin, TrainerStagingMixin, nn.Module):
             if fmri is not None:
                 zf = torch.cat([ops.proj_embed_one(br, self.fmri_encoder(x), "fmri")
                                 for x in self._chunks(fmri, batch_size, dev)])
-        finally:
-            self.train(was)
         return ze, zf
 
     @torch.no_grad()
@@ -1332,8 +1248,8 @@ class BridgeTrainer(TrainerCheckpointMixin, TrainerStagingMixin, nn.Module):
         attr_e, chan = ops.xai_finish(eeg, bases[0], accs[0], steps, method, channels=True)
         attr_f, _ = ops.xai_finish(fmri, bases[1], accs[1], steps, method)
         out = {"eeg": attr_e, "eeg_channels": chan, "fmri": attr_f, "scores": scores}
-        if self._fmri_kind == "tabular":                  # views of the (B, A + C) attribution
-            out["fmri_activation"], out["fmri_connectivity"] = self.fmri_encoder.split(attr_f)
+        if self._fmri.explain_views is not None:
+            out.update(self._fmri.explain_views(self.fmri_encoder, attr_f))
         return out
 
     def _pair_gradients(self, eeg, fmri, steps: int, baseline: Optional[str], chunk_steps: Optional[int] = None):
@@ -1366,23 +1282,19 @@ class BridgeTrainer(TrainerCheckpointMixin, TrainerStagingMixin, nn.Module):
             if s0 + k == steps:                               # the last step is the input itself (alpha = 1)
                 scores["at_input"] = score[-B:].clone()
             return g
-        modes = [(m, m.training) for m in self.modules()]      # restored module by module (a frozen sub-module stays frozen)
         saved_seed = dict(ops._seed_state)
         g0 = self.bucket.g.clone()                            # the backward kernels add parameter gradients into the bucket
-        self.eval()
-        ops.weights_changed()                                 # graph replays bypass the python-side version counter
         try:
-            accs, _ = ops.integrated_gradients(forward, [eeg, fmri], path, steps, seed,
-                                               chunk_steps=1 if baseline is None else chunk_steps)
-            if baseline is not None and steps == 1:           # a single step is the BASELINE (alpha = 0), not the input:
-                with torch.enable_grad(), ops.attribution_mode():      # the scores at the inputs, through the same kernels
-                    z = forward(eeg.clone().requires_grad_(True), fmri.clone().requires_grad_(True))
-                scores["at_input"] = ops.xai_pair_score(z, want_seed=False)[0]
-                ops._release_tape(z)
-                del z
+            with self._eval_scope():
+                accs, _ = ops.integrated_gradients(forward, [eeg, fmri], path, steps, seed,
+                                                   chunk_steps=1 if baseline is None else chunk_steps)
+                if baseline is not None and steps == 1:           # a single step is the BASELINE (alpha = 0), not the input:
+                    with torch.enable_grad(), ops.attribution_mode():      # the scores at the inputs, through the same kernels
+                        z = forward(eeg.clone().requires_grad_(True), fmri.clone().requires_grad_(True))
+                    scores["at_input"] = ops.xai_pair_score(z, want_seed=False)[0]
+                    ops._release_tape(z)
+                    del z
         finally:
-            for m, mode in modes:
-                m.training = mode
             self.bucket.g.copy_(g0)
             ops._seed_state.update(saved_seed)
             ops.weights_changed()
@@ -1394,14 +1306,10 @@ class BridgeTrainer(TrainerCheckpointMixin, TrainerStagingMixin, nn.Module):
             if units == "channels":
                 return ("rows", 1)
             allowed, what = ("windows",), "'channels' or ('windows', w)"
-        elif self._fmri_kind == "volume":
-            if units is None:
-                return ("blocks", 8)
-            allowed, what = ("blocks",), "('blocks', s) for the voxel encoder"
         else:
             if units is None:
-                return ("windows", 1)
-            allowed, what = ("windows",), "('windows', w) for a tabular fMRI encoder"
+                return self._fmri.perturb_default
+            allowed, what = self._fmri.perturb_kinds, self._fmri.perturb_what
         if not isinstance(units, (tuple, list)) or len(units) != 2 or units[0] not in allowed:
             raise ValueError(f"perturb: {modality}_units must be {what}, got {units!r}")
         return (units[0], units[1])
@@ -1475,27 +1383,20 @@ class BridgeTrainer(TrainerCheckpointMixin, TrainerStagingMixin, nn.Module):
             z = ops.proj_embed_one(br, f, k)
             ops._release_tape(f)
             return z
-        modes = [(m, m.training) for m in self.modules()]      # restored module by module (a frozen sub-module stays frozen)
-        self.eval()
-        ops.weights_changed()                                 # graph replays bypass the python-side version counter
-        try:
-            with torch.no_grad():
-                z = {k: embed_rows(k, x[k]) for k in ("eeg", "fmri")}
-                out = {"scores": ops.perturb_pair_scores(z["eeg"], z["fmri"])[0]}
-                empty = {}
-                for k, other in (("eeg", "fmri"), ("fmri", "eeg")):
-                    v = ops.perturb_scores(lambda rows: ops.perturb_pair_scores(embed_rows(k, rows), z[other]),
-                                           x[k], base[k], masks[k], units[k], chunk_masks)
-                    if method == "occlusion":
-                        out[k] = (out["scores"].unsqueeze(0) - v).t().contiguous()
-                    else:
-                        empty[k] = v[0].clone()
-                        out[k] = ops.perturb_shapley(v[1:] if n_units[k] > 1 else None, empty[k], out["scores"], pos[k])
-                if method == "shapley":
-                    out["empty_scores"] = empty
-        finally:
-            for m, mode in modes:
-                m.training = mode
+        with self._eval_scope(), torch.no_grad():
+            z = {k: embed_rows(k, x[k]) for k in ("eeg", "fmri")}
+            out = {"scores": ops.perturb_pair_scores(z["eeg"], z["fmri"])[0]}
+            empty = {}
+            for k, other in (("eeg", "fmri"), ("fmri", "eeg")):
+                v = ops.perturb_scores(lambda rows: ops.perturb_pair_scores(embed_rows(k, rows), z[other]),
+                                       x[k], base[k], masks[k], units[k], chunk_masks)
+                if method == "occlusion":
+                    out[k] = (out["scores"].unsqueeze(0) - v).t().contiguous()
+                else:
+                    empty[k] = v[0].clone()
+                    out[k] = ops.perturb_shapley(v[1:] if n_units[k] > 1 else None, empty[k], out["scores"], pos[k])
+            if method == "shapley":
+                out["empty_scores"] = empty
         return out
 
 

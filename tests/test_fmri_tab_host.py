@@ -7,6 +7,7 @@ import pytest
 import torch
 
 from multimodal_eeg_fmri_amd import _hip, ops
+from multimodal_eeg_fmri_amd.bridge_branches import step_schedule
 from multimodal_eeg_fmri_amd.bridge_trainer import (BridgeTrainer, synthetic_tabular_pairs,
                                                     synthetic_tabular_subject_pairs)
 from multimodal_eeg_fmri_amd.fmri_utils import fMRIFusionNet, fMRITabularEncoder
@@ -169,7 +170,8 @@ def test_cpu_trainer_bucket_layout(kw):
     keys = set(tab.state_dict())
     assert {k for k in keys if k.startswith("fmri_encoder.")} == {"fmri_encoder." + k for k in enc.state_dict()}
     assert {k for k in keys if not k.startswith("fmri_encoder.")} == {k for k in vol.state_dict() if not k.startswith("fmri_encoder.")}
-    assert not tab._fmri_is_longer(torch.zeros(4, 87)) and not vol._fmri_is_longer(torch.zeros(2, 1, 16, 16, 16))
+    assert not step_schedule("erp", "tabular", (), (87,), True, {}).fmri_first
+    assert not step_schedule("erp", "volume", (), (1, 16, 16, 16), True, {}).fmri_first
 
 
 def test_synthetic_tabular_helpers():

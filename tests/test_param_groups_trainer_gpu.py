@@ -8,7 +8,7 @@ gradients between the eager tape and the autograd surface, is the one the traine
 import pytest
 import torch
 
-from multimodal_eeg_fmri_amd import _hip, bridge_trainer, ops
+from multimodal_eeg_fmri_amd import _hip, bridge_branches, ops
 from multimodal_eeg_fmri_amd.bridge_trainer import BridgeTrainer, synthetic_pairs
 from multimodal_eeg_fmri_amd.fmri_utils import fMRITabularEncoder
 
@@ -223,7 +223,7 @@ def _launches(tr, batch, monkeypatch):
     monkeypatch.setattr(_hip, "call", call)
     for c, fns in BACKWARDS.items():
         for fn in fns:
-            monkeypatch.setattr(bridge_trainer, fn, wrap(c, getattr(bridge_trainer, fn)))
+            monkeypatch.setattr(bridge_branches, fn, wrap(c, getattr(bridge_branches, fn)))
     try:
         tr.train_step(*batch)
         torch.cuda.synchronize()

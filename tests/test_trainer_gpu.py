@@ -500,9 +500,10 @@ def test_fused_launches_train_exactly_as_their_separate_forms(monkeypatch):
 
 def test_config4_volume_step_takes_the_fmri_first_schedule_and_matches_the_other(monkeypatch):
     """config #4's 64 x 64 x 48 volumes make the voxel branch the longer stream: the trainer picks the fMRI-first
-    schedule by itself (`_fmri_is_longer`), and four graph steps end bit-identical to the EEG-first / hand-over schedule
+    schedule by itself (`step_schedule`), and four graph steps end bit-identical to the EEG-first / hand-over schedule
     forced by MM_FMRI_LONGER=0 (what config #2 runs, which the oracle tests pin).  Dropout off: the masks' seeds are
     drawn in issue order, so the two schedules would draw different (equally valid) masks."""
+    from multimodal_eeg_fmri_amd.bridge_branches import step_schedule
     from multimodal_eeg_fmri_amd.bridge_trainer import BridgeTrainer, synthetic_pairs
     from multimodal_eeg_fmri_amd import ops
     batches = [synthetic_pairs(4, 16, 256, (64, 64, 48), seed=500 + i) for i in range(2)]
@@ -519,13 +520,43 @@ def test_config4_volume_step_takes_the_fmri_first_schedule_and_matches_the_other
         params = tr.bucket.p.detach().clone()
         ops.set_seed_epoch(None)
         monkeypatch.undo()
-        return torch.stack(losses), params, tr._fmri_longer
+        return torch.stack(losses), params, tr.schedule.fmri_first
     la, pa, longer = run(None)
     assert longer and torch.isfinite(la).all()
     lb, pb, longer_b = run("0")
     assert not longer_b
     assert torch.equal(la, lb) and torch.equal(pa, pb)
-    assert not BridgeTrainer._fmri_is_longer(torch.empty(2, 1, 32, 32, 32))
+    assert not step_schedule("erp", "volume", (), (1, 32, 32, 32), True, {}).fmri_first
+
+
+def test_manual_step_issues_its_phase_stamps_in_schedule_order(monkeypatch):
+    """the host issue order of one manual-mode step's phase stamps (`BridgeTrainer.STAMP_NAMES`) under the three
+    schedules: EEG first with the hand-over (the fMRI backward, 9 10 13, follows the chain's 8), fMRI first (its forward
+    3 4 before the EEG's 2, its backward before the chain), and a frozen EEG encoder (EEG first, nothing handed over)"""
+    from multimodal_eeg_fmri_amd.bridge_trainer import BridgeTrainer, synthetic_pairs
+    from multimodal_eeg_fmri_amd import _hip, ops
+    batch = synthetic_pairs(4, 16, 256, (16, 16, 16), seed=900)
+    real = _hip.call
+
+    def stamps(env=None, **kw):
+        if env is not None:
+            monkeypatch.setenv("MM_FMRI_LONGER", env)
+        ops.set_seed_epoch(None)
+        torch.manual_seed(0)
+        tr = BridgeTrainer(eeg_channels=16, dropout=0.0, lr=1e-3, mode="manual", **kw).train()
+        tr.train_step(*batch)                               # the first step records the weight list
+        tr.stamps = torch.zeros(16, dtype=torch.int64, device="cuda")
+        order = []
+        monkeypatch.setattr(_hip, "call", lambda name, *a: (order.append(a[1]) if name == "mm_debug_stamp" else None, real(name, *a))[1])
+        try:
+            tr.train_step(*batch)
+            torch.cuda.synchronize()
+        finally:
+            monkeypatch.undo()
+        return order
+    assert stamps() == [0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 13, 11, 12]
+    assert stamps(env="1") == [0, 1, 3, 4, 2, 5, 6, 7, 9, 10, 13, 8, 11, 12]
+    assert stamps(freeze=("eeg_encoder",)) == [0, 1, 2, 3, 4, 5, 6, 7, 9, 10, 13, 8, 11, 12]
 
 
 def test_packed_host_batch_step_is_bit_identical_to_the_device_side_pack():
