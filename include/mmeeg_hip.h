@@ -781,6 +781,29 @@ int mm_clip_bank_push(const float* z, const int* gid, float* bank, int* bank_gid
                       hipStream_t stream);
 /* host-only: floats of mm_clip_bank_loss's workspace */
 int mm_clip_bank_ws_floats(int B, int K, int N, int* floats_host, hipStream_t stream);
+/* mm_clip_bank_loss with the batch's keys taken from a SECOND set of rows (a momentum key encoder's embeddings of the same
+ * pairs; He et al., "Momentum Contrast"): q [B][2N] = [qe | qf] the online rows (queries only; gradients flow into them),
+ * k [B][2N] = [ke | kf] the key rows of the same pairs (constants); bank, bank_gid, state, gid, logit_scale, warmup, n as
+ * above.  Key index t < B is k's row t, else bank slot t - B:
+ *   e->f: query qe_r over keys kf_t;   f->e: query qf_r over keys ke_t;   P(r) = {t : gid_t = gid_r} (gid NULL: {r})
+ *   l_dir(r) = LSE_t(s x[r][t]) - LSE_{t in P(r)}(s x[r][t])        loss = (1/B) sum_r (l_e2f(r) + l_f2e(r)) / 2
+ *   dqe_r = sum_t G_e2f[r][t] kf_t,  dqf_r = sum_t G_f2e[r][t] ke_t,  G = 0.5 s / B (softmax - [t in P] softmax over P)
+ * There is no key term: neither k nor the bank receives anything or is written.  dq [B][2N] nullable (plain stores);
+ * scal4 = {loss, top1 e->f, top1 f->e, d loss / d logit_scale}, top-1 as in mm_clip_bank_loss.  q and k may be the same
+ * rows (the loss is then mm_clip_bank_loss's, to rounding).  All fp32, no float atomics, every sum in a fixed order: same
+ * inputs + same state -> bit-identical outputs.  Rows at or beyond n are never read.  ws = mm_clip_key_ws_floats(B, K, N)
+ * floats (scores, chunk partials, the folded normalisers, the key tiles' dq sums and tickets), no initialisation.  N % 4 == 0, 1 <= B <= K, warmup >= 0; q, k,
+ * bank, dq, ws 16-byte aligned.  Three launches on `stream` (scores + chunk partials; the fold of the partials, once per
+ * query and direction; dq, one workgroup per tile of 8 queries x 32 columns x 512 keys, a key row read once per query
+ * tile - dq NULL: one workgroup for the scalars), grids sized by the capacity K.  No workgroup waits for another: with more
+ * than one key tile each workgroup stores its sums and takes an integer ticket (zeroed by the second launch), and the last
+ * arriver adds the tiles' sums in tile order.
+ * Extension: the reference has no contrastive trainer. */
+int mm_clip_key_loss(const float* q, const float* k, const int* gid, const float* bank, const int* bank_gid,
+                     const int* state, const float* logit_scale, float* scal4, float* dq, float* ws, int B, int K, int N,
+                     int warmup, hipStream_t stream);
+/* host-only: floats of mm_clip_key_loss's workspace */
+int mm_clip_key_ws_floats(int B, int K, int N, int* floats_host, hipStream_t stream);
 
 /* ---- gallery-scale retrieval (csrc/retrieval.hip) ---------------------------
  * For each query row q of Q [Nq][D] against gallery G [Ng][D] (fp32, row-major, 16-byte aligned; callers pass

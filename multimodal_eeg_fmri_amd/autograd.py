@@ -1006,6 +1006,30 @@ class ClipBankLossFn(torch.autograd.Function):
         return dz * g_loss, (scal[3] * g_loss).reshape(()), None, None, None
 
 
+class ClipKeyLossFn(torch.autograd.Function):
+    """`ClipBankLossFn` with a momentum key encoder (``mm_clip_key_loss``): the online rows ``q`` are queries only, the key
+    rows ``k`` of the same pairs are constants of the tape like the bank - ``k`` carries no gradient."""
+
+    @staticmethod
+    def forward(ctx, q, k, logit_scale, bank, gid=None, warmup=0):
+        q = q.contiguous().float()
+        k = k.detach().contiguous().float()
+        B, N2 = q.shape
+        need_grad = q.requires_grad or logit_scale.requires_grad
+        scal = _empty((4,), _F32, q)
+        dq = _empty((B, N2), _F32, q) if need_grad else None
+        ls = logit_scale.detach().reshape(1).float().contiguous()
+        ops.clip_key_loss(q.detach(), k, gid, bank, ls, scal, dq, warmup)
+        if need_grad:
+            ctx.save_for_backward(dq, scal)
+        return scal[0].clone(), scal[1].clone(), scal[2].clone()
+
+    @staticmethod
+    def backward(ctx, g_loss, g_a, g_b):
+        dq, scal = ctx.saved_tensors
+        return dq * g_loss, None, (scal[3] * g_loss).reshape(()), None, None, None
+
+
 class SigmoidLossFn(torch.autograd.Function):
     """`ClipLossFn` for the pairwise sigmoid loss (``mm_sigmoid_loss_own_rows``): the same gather of embeddings and ids,
     the same own-rows gradient; one more learnable scalar, ``logit_bias``."""

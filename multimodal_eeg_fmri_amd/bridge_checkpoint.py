@@ -16,7 +16,8 @@ The file is the container of the reference's loops and of `FlexibleTrainer.save_
   only for a trainer of the pairwise sigmoid loss - ``loss`` = ``"sigmoid"`` (absent: InfoNCE), and - only for a trainer
   built with ``classify=True`` - ``classify`` = ``{ce_weight, num_classes, class_weight}``, and - only for a trainer with
   a cross-batch memory (``bank_size > 0``) - ``bank`` = ``{size, warmup, grouped, state, rows, ids}``: the ring's words,
-  rows and group ids (``rows`` / ``ids`` None before the first training step), and - only for a trainer that keeps
+  rows and group ids (``rows`` / ``ids`` None before the first training step; with ``key_encoder=True`` one more field,
+  ``key_encoder`` = True: the rows are the key encoder's), and - only for a trainer that keeps
   averaged weights (``ema_decay > 0``) - ``ema`` = ``{decay, warmup, shadow}``: ``shadow`` is the flat fp32 average of
   the bucket (``bucket_n`` elements, bucket order), and - only for a trainer with parameter groups (a learning-rate
   multiplier other than 1, ``no_decay=True`` or a frozen encoder) - ``param_groups`` = ``{components, multipliers,
@@ -147,9 +148,12 @@ class TrainerCheckpointMixin:
         if not getattr(self, "_bank_size", 0):
             return None
         bank = self._bank
-        return {"size": int(self._bank_size), "warmup": int(self._bank_warmup), "grouped": self._bank_grouped,
-                "state": [0, 0, 0, 0] if bank is None else [int(v) for v in bank.state.detach().cpu()],
-                "rows": None if bank is None else _cpu(bank.bank), "ids": None if bank is None else _cpu(bank.gid)}
+        out = {"size": int(self._bank_size), "warmup": int(self._bank_warmup), "grouped": self._bank_grouped,
+               "state": [0, 0, 0, 0] if bank is None else [int(v) for v in bank.state.detach().cpu()],
+               "rows": None if bank is None else _cpu(bank.bank), "ids": None if bank is None else _cpu(bank.gid)}
+        if getattr(self, "_key_encoder", False):                   # (absent without a key encoder: the container is unchanged)
+            out["key_encoder"] = True
+        return out
 
     def checkpoint_ema(self) -> Optional[dict]:
         """``bridge_trainer_state["ema"]``: None unless the trainer was built with ema_decay > 0"""
@@ -252,6 +256,11 @@ class TrainerCheckpointMixin:
                 if theirs_bank.get(field) != mine_v:
                     raise ValueError(f"load_checkpoint_state: bank.{field} differs: checkpoint {theirs_bank.get(field)!r}, "
                                      f"trainer {mine_v!r}")
+            mine_key = bool(getattr(self, "_key_encoder", False))
+            if bool(theirs_bank.get("key_encoder", False)) != mine_key:
+                raise ValueError(f"load_checkpoint_state: bank.key_encoder differs: the checkpoint's bank holds the rows of "
+                                 f"{'a key encoder' if not mine_key else 'the online encoders'}, this trainer was built "
+                                 f"{'with' if mine_key else 'without'} key_encoder=True")
             rows, N2 = theirs_bank.get("rows"), 2 * self.head.bridge.bridge_dim
             if rows is not None and (tuple(rows.shape) != (size, N2) or tuple(theirs_bank["ids"].shape) != (size,)):
                 raise ValueError(f"load_checkpoint_state: bank.rows differ: checkpoint {tuple(rows.shape)}, trainer {(size, N2)}")

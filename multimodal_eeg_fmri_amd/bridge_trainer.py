@@ -52,7 +52,7 @@ class BridgeTrainer(TrainerCheckpointMixin, TrainerStagingMixin, nn.Module):
                  classify: bool = False, ce_weight: float = 1.0, class_weight=None, num_classes: int = 2,
                  fmri_encoder: Optional[nn.Module] = None, bank_size: int = 0, bank_warmup: int = 0, fmri_augment=None,
                  ema_decay: float = 0.0, ema_warmup: bool = True, lr_scale=None, no_decay: bool = False, freeze=(),
-                 eeg_time_augment=None):
+                 eeg_time_augment=None, key_encoder: bool = False):
         """``eeg_encoder``: the EEG branch when it is not the default ``EnhancedERPEncoder(eeg_channels, hidden_dim,
         num_layers, num_heads, dropout)`` - an ``EnhancedPowerEncoder`` (enhanced_models_v4.py:196-285) or a
         ``MultiScaleSTFTPowerEncoder`` (BASELINE config #5: raw EEG -> multi-scale STFT power -> a4); it must end in
@@ -121,7 +121,18 @@ class BridgeTrainer(TrainerCheckpointMixin, TrainerStagingMixin, nn.Module):
         inverts and masks its EEG batch along the time axis on the device (mm_stage_inputs_taug).
         Alone it replaces the step's one staging launch by one launch; together with ``augment=`` the two share the
         staging launch (after the plan launch) and therefore the step index (`augment_step`).  The entry points that never
-        augment never shift either.  None (default): the step issues the launches it always did."""
+        augment never shift either.  None (default): the step issues the launches it always did.
+        ``key_encoder=True``: a momentum key encoder for the bank (He et al., "Momentum Contrast").
+        Needs ``bank_size > 0``, ``ema_decay > 0``, ``loss="infonce"`` and one process (ValueError otherwise).  Every
+        `train_step` then embeds its (staged, augmented) batch a second time with the AVERAGED weights - unregistered twins
+        of the trained encoders and of the two projection heads whose parameters are views into ``bucket.ema`` and whose
+        buffers are the online modules' own, run in the eval form (nothing saved, no seed drawn, no running statistic
+        written; a frozen encoder has no twin: its online features are the key features).  These rows are the keys of the
+        batch and what the bank receives (mm_clip_key_loss in place of mm_clip_bank_loss, then mm_clip_bank_push of the
+        keys); gradients flow through the online rows - the queries - only.  Each encoder's key pass is issued in front
+        of its online pass on that branch's stream: it reads the BatchNorm running statistics as they stood before this
+        step's update, and step t's keys come from the average after step t - 1.  During ``bank_warmup`` the same kernel
+        runs with no valid bank row (decided on the device): the step is captured once.  False (default): unchanged."""
         super().__init__()
         self._frozen = self._check_freeze(freeze, group)
         self._lr_scale = self._check_lr_scale(lr_scale)
@@ -129,6 +140,19 @@ class BridgeTrainer(TrainerCheckpointMixin, TrainerStagingMixin, nn.Module):
         check_ema_decay(ema_decay, "BridgeTrainer")
         self.ema_decay, self.ema_warmup = float(ema_decay), bool(ema_warmup)
         self._ema_active = False                      # inside `ema_weights()`: the parameters hold the averaged weights
+        if key_encoder:                               # each missing partner by name, before any allocation
+            if not bank_size > 0:
+                raise ValueError("BridgeTrainer: key_encoder=True needs bank_size > 0 (the key encoder fills the cross-batch "
+                                 "bank; without one there is nothing for its rows to be keys of)")
+            if not ema_decay > 0:
+                raise ValueError("BridgeTrainer: key_encoder=True needs ema_decay > 0 (the key encoder runs on the averaged "
+                                 "weights, bucket.ema)")
+            if loss != "infonce":
+                raise ValueError(f"BridgeTrainer: key_encoder=True needs loss='infonce' (got {loss!r}: the pairwise sigmoid "
+                                 "loss has no bank for a key encoder to fill)")
+            if group is not None and dp.world_size(group) > 1:
+                raise ValueError("BridgeTrainer: key_encoder=True needs a world size of 1 (the bank it fills is one "
+                                 f"process's; got a process group of {dp.world_size(group)})")
         if bank_size < 0 or bank_warmup < 0:
             raise ValueError(f"BridgeTrainer: bank_size and bank_warmup must be >= 0 (got {bank_size}, {bank_warmup})")
         if bank_size > 0:
@@ -139,11 +163,16 @@ class BridgeTrainer(TrainerCheckpointMixin, TrainerStagingMixin, nn.Module):
                 raise NotImplementedError("BridgeTrainer: bank_size > 0 with a process group of world size > 1 is not "
                                           "supported yet (intended: every rank pushes the gathered rows of all ranks)")
             ops.clip_bank_check(1, bank_size, bridge_dim, bank_warmup, "BridgeTrainer(bank_size=)")
+        self._key_encoder = bool(key_encoder)
+        self._key = None                              # the key encoder's unregistered twins (`_build_key_modules`)
+        self._key_rows = None                         # the running step's key embeddings (B, 2N): `_seg_forward` -> `_seg_loss`
         self._bank_size, self._bank_warmup = int(bank_size), int(bank_warmup)
         self._bank = None                             # ops.ClipBank, allocated at the first training step (before any capture)
         self._bank_grouped = None                     # fixed by the first training step: do the bank rows carry group ids
         self._bank_pushes = 0                         # host mirror of the bank's `pushes` word (one push per training step)
-        self._bank_live = bank_warmup == 0            # the running step's loss reads the bank (pushes >= warmup)
+        # the running step launches a loss that reads the bank: pushes >= warmup - a key trainer always (mm_clip_key_loss
+        # gates on the device alone; there are no in-batch bits to keep, the keys are not the queries)
+        self._bank_live = bank_warmup == 0 or self._key_encoder
         self._fmri = select_fmri(fmri_encoder, fmri_dim)      # the fMRI branch's entry of `bridge_branches.FMRI_BRANCHES`
         self._fmri_kind = self._fmri.kind
         self.classify, self.ce_weight, self.num_classes = bool(classify), float(ce_weight), int(num_classes)
@@ -263,6 +292,8 @@ class BridgeTrainer(TrainerCheckpointMixin, TrainerStagingMixin, nn.Module):
         # loss (mm_bridge_cls_bwd), after the contrastive loss's words
         self._scal_cls = 5 if loss == "sigmoid" else 4
         self._scal = torch.zeros(self._scal_cls + (5 if classify else 0), device=device)
+        if self._key_encoder:
+            self._build_key_modules()
         ops.weights_changed()
 
     @property
@@ -307,8 +338,46 @@ class BridgeTrainer(TrainerCheckpointMixin, TrainerStagingMixin, nn.Module):
         # the device gates on `pushes >= warmup` as well; the host decides which loss the step launches: before that the
         # in-batch kernels, whose bits a default trainer has (mm_clip_bank_loss at n = 0 agrees with them to rounding only,
         # and rounding does not stay small behind AdamW's g / (|g| + eps))
-        self._bank_live = self._bank_pushes >= self._bank_warmup
+        self._bank_live = self._key_encoder or self._bank_pushes >= self._bank_warmup
         self._bank_pushes += 1
+
+    # ------------------------------------------------------------------ momentum key encoder
+    def _build_key_modules(self):
+        """structural twins of the trained encoders and of the two projection heads: every parameter a view into
+        ``bucket.ema`` at the online parameter's offset (a parameter outside the bucket: the online storage itself), every
+        buffer the online module's own tensor (BatchNorm running statistics, positional tables: read-only in the eval
+        form).  Kept in a plain dict - NOT registered: absent from parameters(), state_dict(), the bucket, the gradient
+        groups and checkpoints.  A frozen encoder has no twin."""
+        import copy
+        import types
+        b = self.bucket
+        where, off = {}, 0
+        for p in b.params:
+            where[id(p)] = off
+            off += p.numel()
+
+        def twin(online: nn.Module) -> nn.Module:
+            t = copy.deepcopy(online).eval()
+            for mo, mt in zip(online.modules(), t.modules()):
+                for name, p in mo._parameters.items():
+                    if p is None:
+                        continue
+                    tp = mt._parameters[name]
+                    tp.requires_grad_(False)
+                    o = where.get(id(p))
+                    tp.data = p.data if o is None else b.ema[o:o + p.numel()].view(p.shape)
+                for name, buf in mo._buffers.items():
+                    mt._buffers[name] = buf
+            return t
+        br = self.head.bridge
+        key = {name: twin(getattr(self, name)) for name in ("eeg_encoder", "fmri_encoder") if name not in self._frozen}
+        key["bridge"] = types.SimpleNamespace(eeg_proj=twin(br.eeg_proj), fmri_proj=twin(br.fmri_proj),
+                                              bridge_dim=br.bridge_dim, drop_p=br.drop_p)
+        self._key = key
+
+    def _key_embed(self, kfe, kff):
+        """the twin heads on the two encoders' key features -> the key rows (B, 2N) = [ke | kf]; eval form"""
+        return ops.contrastive_embed_impl(self._key["bridge"], kfe, kff, False)[0]
 
     @property
     def augment_step(self) -> int:
@@ -480,6 +549,8 @@ class BridgeTrainer(TrainerCheckpointMixin, TrainerStagingMixin, nn.Module):
         self._check_fmri(fmri.shape, "fmri_encoder" not in self._frozen, "train_step")   # before the first launch of the step (or of its capture)
         if self._fmri.capture_words is not None and fmri.is_cuda:
             self._fmri.capture_words(self.fmri_encoder, fmri.device)   # the forward launch's words exist before any capture
+            if self._key is not None and "fmri_encoder" in self._key:
+                self._fmri.capture_words(self._key["fmri_encoder"], fmri.device)
         gid = ops.group_ids(groups, eeg.shape[0], None if self.mode == "graph" else eeg.device, "train_step")
         lab = self._labels(labels, eeg.shape[0], None if self.mode == "graph" else eeg.device, "train_step")
         if self._bank_size:
@@ -516,32 +587,51 @@ class BridgeTrainer(TrainerCheckpointMixin, TrainerStagingMixin, nn.Module):
         ff.record_stream(main)
         return fe, ff
 
+    def _encode_with_keys(self, eeg, fmri):
+        """`_encode`, and for a key trainer the key rows of the same batch (else None).  Each twin's eval pass runs BEFORE
+        the online forward (it reads the running statistics this step's forward updates); a frozen encoder's online
+        features are its key features.  Nothing of the key pass is on the tape."""
+        if not self._key_encoder:
+            return self._encode(eeg, fmri), None
+        with torch.no_grad():
+            kfe = self._eeg.forward(self._key["eeg_encoder"], eeg, None, False)[0] if "eeg_encoder" in self._key else None
+            kff = self._fmri.forward(self._key["fmri_encoder"], fmri, False)[0] if "fmri_encoder" in self._key else None
+        fe, ff = self._encode(eeg, fmri)
+        with torch.no_grad():
+            keys = self._key_embed(fe.detach() if kfe is None else kfe, ff.detach() if kff is None else kff)
+        return (fe, ff), keys
+
     def _forward_classify(self, eeg, fmri, gid, lab):
         """the classify step's forward from the existing differentiable pieces (the independent path the tape is
         compared with): projection heads, F.normalize, the contrastive loss, `ops.bridge_cls_rows` (bridge_forward's
         train branch on the projected rows) and the weighted cross-entropy.  Seeds are drawn in the tape's order."""
         from . import small_autograd as sa
         br = self.head.bridge
-        fe, ff = self._encode(eeg, fmri)
+        (fe, ff), keys = self._encode_with_keys(eeg, fmri)
         p = br.drop_p if self.training else 0.0
         ep = sa.proj_head(fe, br.eeg_proj, p)
         fp = sa.proj_head(ff, br.fmri_proj, p)
         ze = torch.nn.functional.normalize(ep, dim=1, eps=1e-12)
         zf = torch.nn.functional.normalize(fp, dim=1, eps=1e-12)
         logits, fw, aw = ops.bridge_cls_rows(br, ep, fp)
-        lc, acc_e, acc_f = self._loss_autograd(ze, zf, gid, True)
+        lc, acc_e, acc_f = self._loss_autograd(ze, zf, gid, True, keys)
         ce = ops.weighted_cross_entropy(logits, lab.long(), self._class_weight)
         return lc, acc_e, acc_f, ce, logits
 
-    def _loss_autograd(self, ze, zf, gid, training: bool):
+    def _loss_autograd(self, ze, zf, gid, training: bool, keys=None):
         """-> (loss, acc_e, acc_f): the trainer's contrastive loss on the differentiable surface, `_seg_loss`'s choice.
         A bank trainer's training step (``training``; everything else keeps the in-batch loss) scores against the bank
         (`ClipBankLossFn`: the bank is a constant of the tape), then pushes its own rows - detached: nothing of it is on
-        the tape"""
+        the tape.  ``keys``: a key trainer's key rows (`_encode_with_keys`) - the batch's keys and what is pushed"""
         if self.loss == "sigmoid":
             return ops.sigmoid_loss(ze, zf, self.head.logit_scale, self.head.logit_bias, self.group, gid)
         if not (training and self._bank_size):
             return ops.clip_loss(ze, zf, self.head.logit_scale, self.group, gid)
+        if keys is not None:
+            out = ops.clip_loss_key(ze, zf, keys, self.head.logit_scale, self._bank, gid, self._bank_warmup)
+            with torch.no_grad():
+                ops.clip_bank_push(keys, gid, self._bank)
+            return out
         if self._bank_live:
             out = ops.clip_loss_bank(ze, zf, self.head.logit_scale, self._bank, gid, self._bank_warmup)
         else:                                          # a warm-up step: the in-batch loss, the bank only fills
@@ -560,7 +650,8 @@ class BridgeTrainer(TrainerCheckpointMixin, TrainerStagingMixin, nn.Module):
             out = {"contrastive_loss": lc.detach(), "ce_loss": ce.detach(),
                    "cls_correct": (logits.detach().argmax(dim=1) == lab).sum().float()}
         else:
-            loss, acc_e, acc_f = self._loss_autograd(*self.head.embed(*self._encode(eeg, fmri)), gid, True)
+            feats, keys = self._encode_with_keys(eeg, fmri)
+            loss, acc_e, acc_f = self._loss_autograd(*self.head.embed(*feats), gid, True, keys)
         loss.backward()
         b.absorb_autograd_grads()
         self._seg_optimizer()
@@ -569,7 +660,8 @@ class BridgeTrainer(TrainerCheckpointMixin, TrainerStagingMixin, nn.Module):
     # ---- the segments of the autograd-free tape ------------------------------
     STAMP_NAMES = ("step start", "weights prepared", "EEG fwd done", "fMRI fwd start", "fMRI fwd done",
                    "heads fwd done", "loss done", "heads bwd done", "EEG bwd done", "fMRI bwd start",
-                   "fMRI bwd done", "grad reductions done", "AdamW done", "side stream done")
+                   "fMRI bwd done", "grad reductions done", "AdamW done", "side stream done",
+                   "EEG key pass done", "fMRI key pass done")     # (the last two: key_encoder=True only)
 
     def _stamp(self, i):
         if self.stamps is not None:
@@ -598,21 +690,34 @@ class BridgeTrainer(TrainerCheckpointMixin, TrainerStagingMixin, nn.Module):
         def schedule(fused_rows):
             return step_schedule(self._eeg_kind, self._fmri_kind, self._frozen, tuple(fmri.shape[1:]), fused_rows, os.environ)
         sched = schedule(False)
+        # key_encoder: each trained encoder's twin runs its eval form IN FRONT of the online pass, on that branch's own
+        # stream - stream order alone makes it read the BatchNorm running statistics as they stood before this step's
+        # update.  A frozen encoder has no twin: its online pass is the eval form, its features are the key features.
+        key = self._key or {}
+        kf = {}
 
         def fmri_branch():
             with torch.cuda.stream(self._side):
                 self._stamp(3)                           # (frozen: the eval form, nothing saved, no seed drawn)
+                if "fmri_encoder" in key:
+                    kf["fmri"] = self._fmri.forward(key["fmri_encoder"], fmri, False)[0]
+                    self._stamp(15)
                 out = self._fmri.forward(self.fmri_encoder, fmri, sched.fmri_live)
                 self._stamp(4)
             return out
         if sched.fmri_first:
             ff, sv_f = fmri_branch()
+        if "eeg_encoder" in key:
+            kf["eeg"] = self._eeg.forward(key["eeg_encoder"], eeg, xb, False)[0]
+            self._stamp(14)
         fe, sv_e = self._eeg.forward(self.eeg_encoder, eeg, xb, sched.eeg_live)
         self._stamp(2)
         if not sched.fmri_first:
             ff, sv_f = fmri_branch()
         main.wait_stream(self._side)
         z, sv_h = ops.contrastive_embed_impl(self.head.bridge, fe, ff, True)
+        if self._key_encoder:
+            self._key_rows = self._key_embed(kf.get("eeg", fe), kf.get("fmri", ff))
         sv_c = None
         if lab is not None:
             o = self._scal_cls
@@ -636,6 +741,9 @@ class BridgeTrainer(TrainerCheckpointMixin, TrainerStagingMixin, nn.Module):
         B, row0 = dz.shape[0], dp.rank(self.group) * dz.shape[0]
         if self.loss == "sigmoid":
             ops.sigmoid_loss_own_rows(z_all, gid_all, ls, self.head.logit_bias.detach().reshape(1), scal, dz, B, row0)
+        elif self._key_encoder:                        # the keys of the batch and the rows pushed are the key encoder's
+            ops.clip_key_loss(z_all, self._key_rows, gid_all, self._bank, ls, scal, dz, self._bank_warmup)
+            ops.clip_bank_push(self._key_rows, gid_all, self._bank)
         elif self._bank_size:
             if self._bank_live:
                 ops.clip_bank_loss(z_all, gid_all, self._bank, ls, scal, dz, self._bank_warmup)
@@ -1039,7 +1147,7 @@ class BridgeTrainer(TrainerCheckpointMixin, TrainerStagingMixin, nn.Module):
             raise RuntimeError("train_step_packed: run one train_step(eeg, fmri) first (it captures the step and fixes the shapes)")
         c = self._cap
         if self._bank_size:
-            if c["bank_live"] != (self._bank_pushes >= self._bank_warmup):
+            if c["bank_live"] != (self._key_encoder or self._bank_pushes >= self._bank_warmup):
                 raise RuntimeError("train_step_packed: the bank's warm-up has ended and the captured step is the warm-up's; run "
                                    "one train_step(eeg, fmri) (it captures the step that reads the bank)")
             self._bank_pushes += 1

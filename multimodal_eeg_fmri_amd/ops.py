@@ -716,6 +716,28 @@ def clip_bank_loss(z, gid, bank: ClipBank, logit_scale1, scal, dz, warmup: int =
               int(warmup))
 
 
+def clip_key_ws_floats(B: int, K: int, N: int) -> int:
+    """floats of the scratch of mm_clip_key_loss (scores, the key chunks' partials, the folded normalisers and - with more
+    than one key tile - the tiles' dq sums and their tickets)"""
+    return _hip.host_int("mm_clip_key_ws_floats", B, K, N)
+
+
+def clip_key_loss(q, k, gid, bank: ClipBank, logit_scale1, scal, dq, warmup: int = 0):
+    """`clip_bank_loss` with the batch's keys taken from ``k`` (B, 2N), a momentum key encoder's rows of the same pairs:
+    the online rows ``q`` (B, 2N) are queries only, ``k`` and the bank are constants -> scal (4,), dq (B, 2N) or None = the
+    gradient w.r.t. ``q`` (there is no key term).  Allocates the workspace; neither ``k`` nor the bank is written
+    (mm_clip_key_loss)."""
+    B = _bank_args(q, gid, bank, "clip_key_loss")
+    if tuple(k.shape) != tuple(q.shape):
+        raise ValueError(f"clip_key_loss: {tuple(q.shape)} query rows but key rows of {tuple(k.shape)} (one key row per pair)")
+    if q.dtype != _F32 or k.dtype != _F32:
+        raise ValueError(f"clip_key_loss: q and k must be float32 (got {q.dtype}, {k.dtype})")
+    clip_bank_check(B, bank.K, bank.N, warmup, "clip_key_loss")
+    ws = _empty((clip_key_ws_floats(B, bank.K, bank.N),), _F32, q)
+    _hip.call("mm_clip_key_loss", q, k, gid, bank.bank, bank.gid, bank.state, logit_scale1, scal, dq, ws, B, bank.K, bank.N,
+              int(warmup))
+
+
 def clip_bank_push(z, gid, bank: ClipBank):
     """the B rows of z (and their ids) into the ring, then the state words advance (mm_clip_bank_push)"""
     B = _bank_args(z, gid, bank, "clip_bank_push")
@@ -1929,6 +1951,16 @@ def clip_loss_bank(ze, zf, logit_scale, bank: ClipBank, groups=None, warmup: int
     gid = group_ids(groups, ze.shape[0], ze.device, "clip_loss_bank")
     from .autograd import ClipBankLossFn
     return ClipBankLossFn.apply(_packed_pair(ze, zf), logit_scale, bank, gid, warmup)
+
+
+def clip_loss_key(ze, zf, keys, logit_scale, bank: ClipBank, groups=None, warmup: int = 0):
+    """`clip_loss_bank` with a momentum key encoder (mm_clip_key_loss): ``keys`` (B, 2N) = [ke | kf], the key encoder's
+    rows of the same pairs, are the batch's keys and constants of the tape like the bank - the gradient reaches ``ze``,
+    ``zf`` and ``logit_scale`` only.  NOT pushed to the bank: follow with `clip_bank_push` of ``keys``."""
+    _need_gpu(ze)
+    gid = group_ids(groups, ze.shape[0], ze.device, "clip_loss_key")
+    from .autograd import ClipKeyLossFn
+    return ClipKeyLossFn.apply(_packed_pair(ze, zf), keys, logit_scale, bank, gid, warmup)
 
 
 def sigmoid_loss(ze, zf, logit_scale, logit_bias, group=None, groups=None):

@@ -505,6 +505,85 @@ def bank_case(B=32, N=128, step_iters=30, rounds=5):
           f"({t1 - t0:+.1f} us, {100 * (t1 / t0 - 1):+.2f} %)")
 
 
+def key_case(B=32, N=128, step_iters=30, rounds=5, stamps=True):
+    """the momentum key encoder: mm_clip_key_loss (+ push) against mm_clip_bank_loss (+ push) on a full bank of K = 1024 and
+    4096 rows - eager launches between HIP events and graph-replayed launches, interleaved rounds in the same run - then the
+    C2 graph step (B = 32, bank_size = 4096 full, ema_decay = 0.999) without and with key_encoder=True, the eval forward of
+    both encoders alone (what the key pass adds to each stream), and both steps' phase stamps"""
+    q = torch.nn.functional.normalize(torch.randn(B, 2, N, device="cuda"), dim=2).reshape(B, 2 * N).contiguous()
+    k = torch.nn.functional.normalize(q.view(B, 2, N) + 0.3 * torch.randn(B, 2, N, device="cuda"), dim=2).reshape(B, 2 * N).contiguous()
+    ls = torch.full((1,), math.log(1 / 0.07), device="cuda")
+    scal, dz = torch.empty(4, device="cuda"), torch.empty(B, 2 * N, device="cuda")
+    cases = []
+    for K in (1024, 4096):
+        bank = ops.ClipBank(K, N, False, "cuda")
+        bank.bank.copy_(torch.nn.functional.normalize(torch.randn(K, 2, N, device="cuda"), dim=2).reshape(K, 2 * N))
+        bank.state.copy_(torch.tensor([0, K, K // B, 0], dtype=torch.int32))
+        ws_b = torch.empty(ops.clip_bank_ws_floats(B, K, N), device="cuda")
+        ws_k = torch.empty(ops.clip_key_ws_floats(B, K, N), device="cuda")
+
+        def bank_loss(bank=bank, ws=ws_b, K=K):
+            _hip.call("mm_clip_bank_loss", q, None, bank.bank, None, bank.state, ls, scal, dz, ws, B, K, N, 0)
+
+        def key_loss(bank=bank, ws=ws_k, K=K):
+            _hip.call("mm_clip_key_loss", q, k, None, bank.bank, None, bank.state, ls, scal, dz, ws, B, K, N, 0)
+
+        def push(bank=bank, K=K):
+            _hip.call("mm_clip_bank_push", k, None, bank.bank, None, bank.state, B, K, N)
+        cases += [(f"bank loss K={K}", bank_loss), (f"key loss K={K}", key_loss),
+                  (f"bank loss + push K={K}", lambda a=bank_loss, b=push: (a(), b())),
+                  (f"key loss + push K={K}", lambda a=key_loss, b=push: (a(), b()))]
+    eager, replayed = {name: [] for name, _ in cases}, {name: [] for name, _ in cases}
+    for _ in range(rounds):
+        for name, fn in cases:
+            eager[name].append(timeit(fn, iters=20, rounds=1))
+            replayed[name].append(graph_time(fn))
+    for name, _ in cases:
+        print(f"loss section B={B} N={N}: {name:26s} eager {_spread(eager[name])}   graph {_spread(replayed[name])}")
+    from multimodal_eeg_fmri_amd.bridge_trainer import BridgeTrainer, synthetic_pairs
+    eeg, fmri = synthetic_pairs(32, 64, 1024, (32, 32, 32))
+    trs = []
+    for key in (False, True):
+        ops.set_seed_epoch(None)
+        torch.manual_seed(0)
+        tr = BridgeTrainer(eeg_channels=64, dropout=0.3, bank_size=4096, ema_decay=0.999, key_encoder=key).train()
+        for _ in range(4096 // 32 + 1):                       # fill the bank: the timed steps see all K rows
+            tr.train_step(eeg, fmri)
+        trs.append(tr)
+    steps = ([], [])
+    for _ in range(rounds):
+        for i, tr in enumerate(trs):
+            steps[i].append(timeit(lambda: tr.train_step(eeg, fmri), iters=step_iters, rounds=1))
+    t0, t1 = statistics.median(steps[0]), statistics.median(steps[1])
+    print(f"C2 graph step B=32 bank_size=4096 ema_decay=0.999: no key encoder {_spread(steps[0])}   key_encoder=True {_spread(steps[1])}   "
+          f"({t1 - t0:+.1f} us, {100 * (t1 / t0 - 1):+.2f} %)")
+    tr = trs[1]
+    xb = ops.pack_nct(eeg)
+    with torch.no_grad():
+        fwd = {"EEG eval forward": lambda: tr._eeg.forward(tr._key["eeg_encoder"], eeg, xb, False),
+               "fMRI eval forward": lambda: tr._fmri.forward(tr._key["fmri_encoder"], fmri, False),
+               "twin heads": lambda: tr._key_embed(torch.zeros(32, 128, device="cuda"), torch.zeros(32, 64, device="cuda"))}
+        for name, fn in fwd.items():
+            print(f"key pass alone, graph-replayed: {name:18s} {_spread([graph_time(fn, n=5) for _ in range(rounds)])}")
+    if stamps:
+        for name, key in (("no key encoder", False), ("key_encoder=True", True)):
+            ops.set_seed_epoch(None)
+            torch.manual_seed(0)
+            tr = BridgeTrainer(eeg_channels=64, dropout=0.3, bank_size=4096, ema_decay=0.999, key_encoder=key).train()
+            tr.stamps = torch.zeros(16, dtype=torch.int64, device="cuda")
+            acc = torch.zeros(16, dtype=torch.float64)
+            for _ in range(5):
+                tr.train_step(eeg, fmri)
+            for _ in range(20):
+                tr.train_step(eeg, fmri)
+                torch.cuda.synchronize()
+                s = tr.stamps.cpu().double()
+                acc += (s - s[0]) / 100.0
+            order = sorted((i for i in range(len(tr.STAMP_NAMES)) if key or i < 14), key=lambda i: acc[i].item())
+            print(f"stamps, {name} (us after step start, graph step): " +
+                  "; ".join(f"{tr.STAMP_NAMES[i]} {acc[i].item() / 20:.1f}" for i in order))
+
+
 def ema_case(step_iters=30, rounds=5):
     """averaged weights in the update kernel, at the default C2 trainer's bucket size, graph-replayed launches in the same
     run, interleaved rounds: mm_adamw_clip, mm_adamw_clip_ema (the same update + the average: 10 streams over the bucket
@@ -1267,6 +1346,9 @@ def main():
         return
     if flt == "bank":
         bank_case()
+        return
+    if flt == "key":
+        key_case()
         return
     if flt == "ema":
         ema_case()
