@@ -139,7 +139,9 @@ int mm_scatter_many(const void* desc_host, int ndesc, hipStream_t stream);
  * HOST array of {const void* src; float* dst; int64 K, nrep, rep_stride} (40 bytes each), copied into the
  * kernel arguments (capturable in a hipGraph).  nrep = 16: src = a gradient accumulator workspace (8-byte
  * aligned; element e of it is at byte offset 8 e; rep_stride in 64-bit elements), dst[k] += its sum in fp32;
- * nrep = 1: src = compact fp32 vector, dst[k] += src[k]. */
+ * nrep = 1: src = compact fp32 vector, dst[k] += src[k];
+ * nrep = -R: src = R fp32 rows rep_stride floats apart (per-sample partial rows, each written by one workgroup),
+ * dst[k] += ((src[k] + src[rep_stride + k]) + ...) in ascending row order. */
 int mm_reduce_many(const void* desc_host, int ndesc, hipStream_t stream);
 /* mm_scatter_many(scatter_desc_host, nscatter) and mm_reduce_many(reduce_desc_host, nreduce) in ONE launch (per 48
  * descriptors of each kind): the two are independent, and a graph node costs ~5 us on the stream that flushes */
@@ -672,6 +674,24 @@ int mm_fmri_tab_bwd(const float* dout, const float* x, const float* out, const f
                     float* d_c2_w, float* d_c2_b, float* d_c2_g, float* d_c2_be, float* d_f_w, float* d_f_b,
                     float* d_f_g, float* d_f_be, float* d_activation_weight, float* d_connectivity_weight, int train,
                     float eps, float drop_p, hipStream_t stream);
+/* Lag attention pooling over the frame features of an fMRI sequence (no reference counterpart: the reference pairs an
+ * epoch with one fMRI row).  x [B][F][N] fp32, q [N] and c [F] the two trained vectors:
+ *   s[b][f] = (x[b][f] . q) / sqrt(N) + c[f],  attw[b] = softmax_f(s[b]) (max-subtracted),  out[b] = sum_f attw[b][f] x[b][f]
+ * and from dout [B][N], with da[b][f] = dout[b] . x[b][f] and ds[b][f] = attw[b][f] (da[b][f] - sum_g attw[b][g] da[b][g]):
+ *   dx[b][f] = attw[b][f] dout[b] + ds[b][f] q / sqrt(N),   dparts[b] = ( sum_f ds[b][f] x[b][f] / sqrt(N) | ds[b][.] )
+ * dparts [B][N + F] are the per-sample rows (dq_b | dc_b); dq and dc are their sums in ascending b (mm_reduce_many /
+ * mm_flush_many, nrep = -B).  ONE launch each, one wave per sample.  All fp32 with the accurate expf; every element of
+ * out, attw [B][F], dx [B][F][N] and dparts is written with a plain store (nothing needs zeroing); no sample reads another
+ * sample's data or results; the same inputs give the same bits.  The exponent is formed from differences to the row's
+ * largest score, so a common offset of c of any size drops out exactly; ds is evaluated as attw[f] sum_g attw[g] (da[f] -
+ * da[g]) (equal, since the weights sum to 1), which keeps its relative accuracy when the softmax is nearly one-hot.
+ * 1 <= F <= 64, N % 4 == 0, 4 <= N <= 1024, B >= 1; x, out, dout and dx 16-byte aligned (q and c: parameters, any float
+ * offset of a flat bucket).
+ * F == 1: attw is exactly 1.0f, out is x and dx is dout bit for bit, dparts is exactly zero. */
+int mm_lagpool_fwd(const float* x, const float* q, const float* c, float* out, float* attw, int B, int F, int N,
+                   hipStream_t stream);
+int mm_lagpool_bwd(const float* dout, const float* x, const float* attw, const float* q, float* dx, float* dparts, int B,
+                   int F, int N, hipStream_t stream);
 /* The encoders of the fMRI notebook's transformer model (fMRI_CODE/CrossModal_fmri_scr.ipynb, cell "# ENCODER BLOCKS":
  * ActivationEncoder / ConnectivityEncoder = Linear(in_dim -> H), nn.TransformerEncoder of L post-norm layers (nhead 4,
  * dim_feedforward 4H, ReLU) on a sequence of length ONE, LayerNorm(H)) for one or two stacks in ONE launch: replaces the

@@ -819,6 +819,72 @@ class VolumeEncoderFn(_ModuleFn):
         return _ModuleFn._finish(ctx, bag, ctx.params, dx)
 
 
+def _lag_param_grads(bag: GradBag, query, lag_bias, dparts: torch.Tensor, B: int, F: int, N: int):
+    """dparts (B, N + F) = mm_lagpool_bwd's per-sample rows (dq_b | dc_b): their sums in ascending b go into the two
+    parameter gradients with the bag's batched reduction (descriptors of B fp32 rows: no launch of their own)"""
+    for p, K, off in ((query, N, 0), (lag_bias, F, N)):
+        dst = bag.target(p)
+        if dst is not None:
+            bag.defer(dparts.data_ptr() + 4 * off, dst, K, -B, N + F, keep=dparts)
+
+
+class LagPoolFn(torch.autograd.Function):
+    """`ops.lag_pool_fwd` on the tape: (x (B, F, N), query, lag_bias) -> (out, weights); the weights are a read-out"""
+
+    @staticmethod
+    def forward(ctx, x, query, lag_bias):
+        out, attw = ops.lag_pool_fwd(x, query, lag_bias)
+        ctx.saved = (x.detach().float().contiguous(), attw, query, lag_bias)
+        ctx.mark_non_differentiable(attw)
+        return out, attw
+
+    @staticmethod
+    def backward(ctx, dout, _dweights):
+        x, attw, query, lag_bias = ctx.saved
+        B, F, N = x.shape
+        dx, dparts = ops.lag_pool_bwd(dout.contiguous(), x, attw, query)
+        bag = GradBag()
+        with deferred(bag, dout.device):
+            _lag_param_grads(bag, query, lag_bias, dparts, B, F, N)
+        return dx if ctx.needs_input_grad[0] else None, bag.result(query), bag.result(lag_bias)
+
+
+def sequence_encoder_bwd(bag: GradBag, sv: dict, dout: torch.Tensor):
+    """backward of ops._seq_forward_impl; dout fp32 (B, out_dim): the pool's backward (mm_lagpool_bwd, one launch; its
+    parameter rows ride in the bag's reduction), then `volume_encoder_bwd` on the B * F volumes with the pool's dx as its
+    dout.  Returns d / d frames (B, F, D, H, W) when the forward was run with need_dx, else None."""
+    B, F = sv["B"], sv["F"]
+    N = dout.shape[1]
+    dx, dparts = ops.lag_pool_bwd(dout.contiguous(), sv["feats"].view(B, F, N), sv["weights"], sv["pool"].query)
+    _lag_param_grads(bag, sv["pool"].query, sv["pool"].lag_bias, dparts, B, F, N)
+    dvol = volume_encoder_bwd(bag, sv["vol"], dx.view(B * F, N))
+    return None if dvol is None else dvol.view(B, F, *dvol.shape[2:])
+
+
+class SequenceEncoderFn(_ModuleFn):
+    """`fMRISequenceEncoder3D` on the tape -> (features, lag weights): train mode, or eval mode with a backward to follow
+    (frozen BatchNorm, no dropout, no statistic update), as `VolumeEncoderFn`"""
+
+    @staticmethod
+    def run(m, x):
+        return SequenceEncoderFn.apply(m, x, *_module_params(m))
+
+    @staticmethod
+    def forward(ctx, m, x, *params):
+        ctx.need_dx = bool(x.requires_grad)
+        out, saved = ops._seq_forward_impl(m, x, m.training, save=True, need_dx=ctx.need_dx)
+        ctx.saved, ctx.params = saved, params
+        ctx.mark_non_differentiable(saved["weights"])
+        return out, saved["weights"]
+
+    @staticmethod
+    def backward(ctx, dout, _dweights):
+        bag = GradBag()
+        with deferred(bag, dout.device):
+            dx = sequence_encoder_bwd(bag, ctx.saved, dout)
+        return _ModuleFn._finish(ctx, bag, ctx.params, dx)
+
+
 def fmri_tab_bwd(bag: GradBag, sv: dict, dout: torch.Tensor):
     """backward of ops._tab_forward_impl (train mode, or frozen BatchNorm), ONE launch (mm_fmri_tab_bwd); dout fp32
     (B, hidden_dim).  Every parameter gradient is written into its `GradBag` target with PLAIN stores (the launch is the

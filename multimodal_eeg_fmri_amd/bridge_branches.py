@@ -1,5 +1,6 @@
 """What `BridgeTrainer` asks of its two encoder branches - `EEG_BRANCHES` (erp | power | stft) and `FMRI_BRANCHES` (volume |
-tabular), plain tables in the style of `bridge_staging.AUGMENTERS` holding exactly what the trainer asks today - and
+tabular: one fMRI item per pair) with `FMRI_SEQUENCE_BRANCH` beside them (sequence: F frames per pair; `fmri_branch` looks a
+kind up in both), plain tables in the style of `bridge_staging.AUGMENTERS` holding exactly what the trainer asks today - and
 `step_schedule`, which decides a step's issue order once, as a pure function (the step's `ops.block_plan`).  The entries reach
 the forward / backward functions through `ops`' attributes and this module's globals, looked up at call time: a test that
 patches ``bridge_branches.erp_encoder_bwd`` sees the step's call."""
@@ -7,10 +8,10 @@ import math
 from typing import Callable, Mapping, NamedTuple, Optional, Tuple
 
 from . import ops
-from .autograd import erp_encoder_bwd, fmri_tab_bwd, power_encoder_bwd, volume_encoder_bwd
+from .autograd import erp_encoder_bwd, fmri_tab_bwd, power_encoder_bwd, sequence_encoder_bwd, volume_encoder_bwd
 from .crossmodal_v4_enhancements import MultiScaleSTFTPowerEncoder
 from .enhanced_models_v4 import EnhancedERPEncoder, EnhancedPowerEncoder
-from .fmri_utils import fMRITabularEncoder
+from .fmri_utils import fMRISequenceEncoder3D, fMRITabularEncoder
 
 
 class EEGBranch(NamedTuple):
@@ -77,8 +78,11 @@ class FMRIBranch(NamedTuple):
     perturb_default: Tuple[str, int]    # `perturb`'s fmri_units=None
     perturb_kinds: Tuple[str, ...]      # the unit kinds `perturb` takes ...
     perturb_what: str                   # ... and how its refusal words them
-    explain_views: Optional[Callable]   # (encoder, attribution) -> further entries of `explain`'s result
-    augmentable: bool                   # fmri_augment= (a VolumeTransforms) is allowed
+    explain_views: Optional[Callable]   # (encoder, attribution, fMRI batch) -> further entries of `explain`'s result
+    augmentable: bool                   # fmri_augment= (a VolumeTransforms) is allowed ...
+    not_augmentable_why: str = ""       # ... and why not
+    perturb_shape: Optional[Callable] = None   # (unit kind, sample shape) -> the sample shape `perturb` cuts its units from (None: as it is)
+    checkpoint_tag: Optional[Callable] = None  # (encoder) -> what a checkpoint records of the branch beside its kind (None: nothing)
 
 
 FMRI_BRANCHES = {b.kind: b for b in (
@@ -92,16 +96,40 @@ FMRI_BRANCHES = {b.kind: b for b in (
                lambda enc, fmri, live: ops._tab_forward_impl(enc, fmri, live, live),
                lambda bag, saved, dff: fmri_tab_bwd(bag, saved, dff),
                False, ("windows", 1), ("windows",), "('windows', w) for a tabular fMRI encoder",
-               lambda enc, attr: dict(zip(("fmri_activation", "fmri_connectivity"), enc.split(attr))),   # views of the (B, A + C) attribution
-               False))}
+               lambda enc, attr, fmri: dict(zip(("fmri_activation", "fmri_connectivity"), enc.split(attr))),   # views of the (B, A + C) attribution
+               False, "the fMRITabularEncoder's input is a feature table (build the trainer without fmri_augment=, or with the "
+               "voxel encoder)"))}
+
+# F frames per pair: the volume branch's launches on the B * F volumes plus the lag pool's one launch each way (DESIGN.md
+# section 5x).  ("rows", 1): one unit = one frame, the sample viewed as (F, D * H * W); ("blocks", s): the volume branch's
+# kind with Cv = F, all frames of a block go together
+FMRI_SEQUENCE_BRANCH = FMRIBranch(
+    "sequence", lambda enc, shape, training, who: ops.check_sequence_shape(enc, shape, f"{who} (fMRI sequence encoder)"), None,
+    lambda enc, fmri, live: ops._seq_forward_impl(enc, fmri, live),
+    lambda bag, saved, dff: sequence_encoder_bwd(bag, saved, dff),
+    True, ("rows", 1), ("rows", "blocks"), "('rows', 1) = one frame or ('blocks', s) for an fMRI sequence encoder",
+    lambda enc, attr, fmri: {"fmri_frames": attr.flatten(2).sum(dim=2), "lag_weights": enc.lag_weights(fmri)},
+    False, "a flip or shift must be the same for all frames of a sample, and VolumeTransforms draws per volume (build the "
+    "trainer without fmri_augment=)",
+    lambda kind, shape: (shape[0], math.prod(shape[1:])) if kind == "rows" else tuple(shape),
+    lambda enc: {"frames": int(enc.frames)})
+
+
+def fmri_branch(kind: str) -> FMRIBranch:
+    return FMRI_SEQUENCE_BRANCH if kind == FMRI_SEQUENCE_BRANCH.kind else FMRI_BRANCHES[kind]
 
 
 def select_fmri(encoder, fmri_dim: int) -> FMRIBranch:
     """``encoder``: the constructor's ``fmri_encoder`` (None = the voxel encoder, which the trainer builds)"""
     if encoder is None:
         return FMRI_BRANCHES["volume"]
+    if isinstance(encoder, fMRISequenceEncoder3D):
+        if encoder.out_dim != fmri_dim:
+            raise ValueError(f"BridgeTrainer: fmri_dim={fmri_dim} but the fMRISequenceEncoder3D ends in {encoder.out_dim} features")
+        return FMRI_SEQUENCE_BRANCH
     if not isinstance(encoder, fMRITabularEncoder):
-        raise TypeError(f"BridgeTrainer: fmri_encoder must be an fMRITabularEncoder or None (the voxel encoder), got {type(encoder).__name__}")
+        raise TypeError(f"BridgeTrainer: fmri_encoder must be an fMRITabularEncoder or None (the voxel encoder), got "
+                        f"{type(encoder).__name__} (frame sequences take an fMRISequenceEncoder3D)")
     if encoder.hidden_dim != fmri_dim:
         raise ValueError(f"BridgeTrainer: fmri_dim={fmri_dim} but the fMRITabularEncoder ends in {encoder.hidden_dim} features")
     return FMRI_BRANCHES["tabular"]
@@ -133,7 +161,7 @@ def step_schedule(eeg_kind: str, fmri_kind: str, frozen, fmri_shape, fused_rows:
     first.  MM_FMRI_LONGER=0/1 overrides - not for a branch that cannot be the longer one (the tabular branch's two launches)."""
     eeg_live, fmri_live = "eeg_encoder" not in frozen, "fmri_encoder" not in frozen
     fmri_first = False
-    if FMRI_BRANCHES[fmri_kind].can_be_longer:
+    if fmri_branch(fmri_kind).can_be_longer:
         forced = env.get("MM_FMRI_LONGER")
         fmri_first = forced == "1" if forced is not None else math.prod(fmri_shape) >= 4 * 32 ** 3
     # the transformer stack's weight-gradient slot sums and parameter reductions (~50 MB of reads) do not wait for the

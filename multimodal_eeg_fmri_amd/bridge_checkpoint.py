@@ -155,6 +155,14 @@ class TrainerCheckpointMixin:
             out["key_encoder"] = True
         return out
 
+    def checkpoint_fmri_branch(self) -> Optional[dict]:
+        """``bridge_trainer_state["fmri_branch"]``: None unless the fMRI branch records more than the shapes say (a sequence
+        encoder: its kind and frame count)"""
+        branch = getattr(self, "_fmri", None)
+        if branch is None or branch.checkpoint_tag is None:
+            return None
+        return {"kind": branch.kind, **branch.checkpoint_tag(self.fmri_encoder)}
+
     def checkpoint_ema(self) -> Optional[dict]:
         """``bridge_trainer_state["ema"]``: None unless the trainer was built with ema_decay > 0"""
         ema = getattr(self.bucket, "ema", None)
@@ -209,6 +217,8 @@ class TrainerCheckpointMixin:
             bts["bank"] = self.checkpoint_bank()
         if self.checkpoint_ema() is not None:                      # (absent without averaged weights: the container is unchanged)
             bts["ema"] = self.checkpoint_ema()
+        if self.checkpoint_fmri_branch() is not None:              # (absent for the volume and tabular branches: the container is unchanged)
+            bts["fmri_branch"] = self.checkpoint_fmri_branch()
         if self.checkpoint_param_groups() is not None:             # (absent at the defaults: the container is unchanged)
             bts["param_groups"] = self.checkpoint_param_groups()
         return {"epoch": epoch, "model_state_dict": {k: _cpu(v) for k, v in self.state_dict().items()},
@@ -232,6 +242,12 @@ class TrainerCheckpointMixin:
                     raise ValueError(f"load_checkpoint_state: {field} differs: checkpoint {bts.get(field)!r}, "
                                      f"trainer {mine[field]!r}")
         same("eeg_kind", "world")
+        mine_fb, theirs_fb = self.checkpoint_fmri_branch(), bts.get("fmri_branch")
+        if mine_fb != theirs_fb:                                   # before the shapes: lag_pool.* exists in one branch only
+            words = lambda fb: "one fMRI item per pair (volume or tabular)" if fb is None else \
+                ", ".join(f"{k}={v!r}" for k, v in fb.items())     # noqa: E731
+            raise ValueError(f"load_checkpoint_state: fmri_branch differs: checkpoint [{words(theirs_fb)}], trainer "
+                             f"[{words(mine_fb)}]")
         loss, theirs_loss = getattr(self, "loss", "infonce"), bts.get("loss", "infonce")
         if loss != theirs_loss:                                    # before the shapes: logit_bias exists under one loss only
             raise ValueError(f"load_checkpoint_state: loss differs: checkpoint {theirs_loss!r}, trainer {loss!r}")

@@ -74,6 +74,11 @@ class BridgeTrainer(TrainerCheckpointMixin, TrainerStagingMixin, nn.Module):
         then two launches per step (mm_fmri_tab_fwd, mm_fmri_tab_bwd), train-mode batches of
         2..256 rows; its ``hidden_dim`` must equal ``fmri_dim``.  Everything else - losses, groups, classify, augment,
         embed / evaluate / retrieval / predict / explain, checkpoints, `fit`, the packed host-fed path - is the same.
+        An ``fMRISequenceEncoder3D(frames=F, out_dim=fmri_dim)`` = F fMRI frames per EEG epoch, (B, F, D, H, W): every
+        frame through one shared voxel encoder (the B * F volumes are one batch, BatchNorm statistics over all of them),
+        then a learned attention pool over the frames (mm_lagpool_fwd, mm_lagpool_bwd) - the voxel
+        branch's launches plus one each way; `explain` adds ``fmri_frames`` and ``lag_weights``, `perturb` knocks out
+        frames (``("rows", 1)``, default) or blocks of all frames; no ``fmri_augment``.
         ``bank_size`` = K > 0: a cross-batch memory of the last K pairs' embeddings (Wang et al., "Cross-Batch Memory for
         Embedding Learning") - every `train_step` scores its rows against the batch AND the valid
         bank rows (mm_clip_bank_loss in place of mm_clip_loss_own_rows*: more negatives, and with ``groups=`` more
@@ -206,8 +211,7 @@ class BridgeTrainer(TrainerCheckpointMixin, TrainerStagingMixin, nn.Module):
             if not isinstance(fmri_augment, VolumeTransforms):
                 raise TypeError(f"BridgeTrainer: fmri_augment must be a VolumeTransforms (got {type(fmri_augment).__name__})")
             if not self._fmri.augmentable:
-                raise ValueError("BridgeTrainer: fmri_augment augments (B, 1, D, H, W) volumes; the fMRITabularEncoder's "
-                                 "input is a feature table (build the trainer without fmri_augment=, or with the voxel encoder)")
+                raise ValueError(f"BridgeTrainer: fmri_augment augments (B, 1, D, H, W) volumes; {self._fmri.not_augmentable_why}")
         self.fmri_augment = fmri_augment
         self._fmri_aug_step = 0                       # step index the next train_step's volume augmentation draws with
         self.eeg_encoder = (EnhancedERPEncoder(eeg_channels, hidden_dim, num_layers, num_heads, dropout)
@@ -1336,7 +1340,9 @@ class BridgeTrainer(TrainerCheckpointMixin, TrainerStagingMixin, nn.Module):
         (|d score / d input|) or "gradient_x_input".
         -> {"eeg": (B, C, T), "eeg_channels": (B, C) = the mean over time, "fmri": (B, 1, D, H, W), "scores": (B,)}, fp32
         on the trainer's device; with a tabular fMRI encoder "fmri" is (B, A + C) and "fmri_activation" (B, A) /
-        "fmri_connectivity" (B, C) are views of it.  The training state is left as it was, bit for bit: parameters, Adam moments, optimizer
+        "fmri_connectivity" (B, C) are views of it; with a sequence encoder "fmri" is (B, F, D, H, W), "fmri_frames" (B, F)
+        its sum over each frame's voxels and "lag_weights" (B, F) the encoder's `lag_weights` of the batch.
+        The training state is left as it was, bit for bit: parameters, Adam moments, optimizer
         words, BatchNorm buffers, the gradient bucket, the dropout seed counter and a captured graph (no seed is drawn in
         eval mode; the gradient bucket, into which the backward kernels add their parameter gradients, is restored).
         Costs and side effects to know: the existing module-level backward functions are reused whole, so every chunk also
@@ -1357,7 +1363,7 @@ class BridgeTrainer(TrainerCheckpointMixin, TrainerStagingMixin, nn.Module):
         attr_f, _ = ops.xai_finish(fmri, bases[1], accs[1], steps, method)
         out = {"eeg": attr_e, "eeg_channels": chan, "fmri": attr_f, "scores": scores}
         if self._fmri.explain_views is not None:
-            out.update(self._fmri.explain_views(self.fmri_encoder, attr_f))
+            out.update(self._fmri.explain_views(self.fmri_encoder, attr_f, fmri))
         return out
 
     def _pair_gradients(self, eeg, fmri, steps: int, baseline: Optional[str], chunk_steps: Optional[int] = None):
@@ -1430,7 +1436,8 @@ class BridgeTrainer(TrainerCheckpointMixin, TrainerStagingMixin, nn.Module):
         forward scores alone (`ops.perturb_scores`: the masked copies of the batch go through the encoder as a few large
         batches, csrc/perturb.hip).
         ``eeg_units``: "channels" or ("windows", w) = w time points of all channels; ``fmri_units``: ("blocks", s) = s^3
-        voxels of a volume (default s = 8), for a tabular encoder ("windows", w) = w features (default 1).  A knocked-out
+        voxels of a volume (default s = 8), for a tabular encoder ("windows", w) = w features (default 1), for a sequence
+        encoder ("rows", 1) = one frame (default) or ("blocks", s) = s^3 voxels of all frames.  A knocked-out
         unit is replaced by the ``baseline``: "zero", or "mean" = the batch mean (as in `explain`).
         ``method``: "occlusion" - drop[b][u] = score_full[b] - score(unit u replaced): U evaluations per modality plus
         the full one; "shapley" - permutation-sampled Shapley values of the game whose players are the units:
@@ -1457,8 +1464,11 @@ class BridgeTrainer(TrainerCheckpointMixin, TrainerStagingMixin, nn.Module):
             raise ValueError(f"perturb: {eeg.shape[0]} EEG epochs but {fmri.shape[0]} fMRI volumes")
         self._check_fmri(fmri.shape, False, "perturb")
         units = {"eeg": self._perturb_units("eeg", eeg_units), "fmri": self._perturb_units("fmri", fmri_units)}
-        n_units = {"eeg": ops.perturb_units(units["eeg"][0], eeg.shape[1:], units["eeg"][1]),
-                   "fmri": ops.perturb_units(units["fmri"][0], fmri.shape[1:], units["fmri"][1])}
+        # the sample shape each modality's units are cut from (a frame sequence's frames are the rows of (F, D * H * W))
+        cut = {"eeg": tuple(eeg.shape[1:]), "fmri": tuple(fmri.shape[1:])}
+        if self._fmri.perturb_shape is not None:
+            cut["fmri"] = self._fmri.perturb_shape(units["fmri"][0], cut["fmri"])
+        n_units = {k: ops.perturb_units(units[k][0], cut[k], units[k][1]) for k in ("eeg", "fmri")}
         masks, pos = {}, {}
         if method == "occlusion":
             for k, U in n_units.items():
@@ -1477,7 +1487,9 @@ class BridgeTrainer(TrainerCheckpointMixin, TrainerStagingMixin, nn.Module):
                 prefix, pos[k] = ops.shapley_masks(perm)
                 masks[k] = torch.cat([torch.zeros(1, U, dtype=torch.int32), prefix])      # the empty coalition first
         dev = self._scal.device
+        shape = {"eeg": tuple(eeg.shape[1:]), "fmri": tuple(fmri.shape[1:])}
         x = {"eeg": eeg.detach().to(dev).float().contiguous(), "fmri": fmri.detach().to(dev).float().contiguous()}
+        x = {k: t.view(t.shape[0], *cut[k]) for k, t in x.items()}
         base = {k: (t.mean(dim=0, keepdim=True) if baseline == "mean" else None) for k, t in x.items()}
         enc = {"eeg": self.eeg_encoder, "fmri": self.fmri_encoder}
         br = self.head.bridge
@@ -1487,7 +1499,7 @@ class BridgeTrainer(TrainerCheckpointMixin, TrainerStagingMixin, nn.Module):
             # attribute the same number; the `no_grad` forward of `embed` folds BatchNorm into the convolution kernels and
             # differs from it by bf16 rounding.  No backward follows: the tape is dropped at once.
             with torch.enable_grad(), ops.attribution_mode():
-                f = enc[k](rows.detach().requires_grad_(True))
+                f = enc[k](rows.detach().view(-1, *shape[k]).requires_grad_(True))
             z = ops.proj_embed_one(br, f, k)
             ops._release_tape(f)
             return z
@@ -1603,6 +1615,24 @@ def synthetic_subject_pairs(subjects: int, per_subject: int, eeg_channels: int =
     eeg = (z_ep @ A_e.t()).unsqueeze(-1) * 0.5 + torch.randn(subjects * per_subject, eeg_channels, samples, generator=g)
     fmri = fmri_s[groups]
     return eeg.to(device), fmri.to(device), groups.to(torch.int32).to(device)
+
+
+def synthetic_sequence_pairs(batch: int, frames: int, peak: int, eeg_channels: int = 64, samples: int = 1024, vol=(32, 32, 32),
+                             seed: int = 1234, device="cuda", latent: int = 16):
+    """``synthetic_pairs`` whose fMRI is a sequence of ``frames`` volumes (batch, frames, *vol) with a planted lag: only
+    frame ``peak`` carries the shared latent (A_f z + N(0, 1)), every other frame is N(0, 1) noise - what a lag pool must
+    find.  The EEG, the maps and the latents are `synthetic_pairs`' for the same seed."""
+    if frames < 1 or not 0 <= peak < frames:
+        raise ValueError(f"synthetic_sequence_pairs: need frames >= 1 and 0 <= peak < frames (got {frames}, {peak})")
+    g = torch.Generator().manual_seed(seed)
+    gm = torch.Generator().manual_seed(99)
+    A_e = torch.randn(eeg_channels, latent, generator=gm)
+    A_f = torch.randn(vol[0] * vol[1] * vol[2], latent, generator=gm) / latent ** 0.5
+    z = torch.randn(batch, latent, generator=g)
+    eeg = (z @ A_e.t()).unsqueeze(-1) * 0.5 + torch.randn(batch, eeg_channels, samples, generator=g)
+    fmri = torch.randn(batch, frames, *vol, generator=g)
+    fmri[:, peak] += (z @ A_f.t()).view(batch, *vol)
+    return eeg.to(device), fmri.to(device)
 
 
 def _tabular_maps(activation_dim: int, connectivity_dim: int, eeg_channels: int, latent: int):

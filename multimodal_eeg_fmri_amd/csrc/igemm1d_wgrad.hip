@@ -505,10 +505,12 @@ int mm_conv1d_wgrad_many(const void* desc_host, int n, hipStream_t st) {
 
 // many independent reductions into parameter gradients in one launch: desc[i] = {src, dst, K, nrep, stride};
 // nrep = MM_ACC_REPL: src is a fixed-point accumulator workspace (stride in 64-bit elements);
-// nrep = 1: src is a compact fp32 vector (plain dst[k] += src[k])
+// nrep = 1: src is a compact fp32 vector (plain dst[k] += src[k]);
+// nrep = -R: src is R fp32 rows `stride` floats apart (per-sample partial rows, one writer each): dst[k] += their sum in
+// ascending row order
 struct ReduceDesc { const void* src; float* dst; long K, nrep, stride; };
 static bool reduce_desc_ok(const ReduceDesc& d) {
-    return d.src && d.dst && d.K > 0 && d.stride >= d.K && (d.nrep == 1 || (d.nrep == MM_ACC_REPL && ((uintptr_t)d.src & 7) == 0));
+    return d.src && d.dst && d.K > 0 && d.stride >= d.K && (d.nrep == 1 || d.nrep < 0 || (d.nrep == MM_ACC_REPL && ((uintptr_t)d.src & 7) == 0));
 }
 constexpr int RM_MAX = 64;
 struct ReduceTable { ReduceDesc d[RM_MAX]; };      // passed BY VALUE (kernel argument): no memcpy node,
@@ -517,6 +519,15 @@ __device__ __forceinline__ void reduce_body(const ReduceDesc& d, int blk, int nb
     if (d.nrep == 1) {
         const float* src = reinterpret_cast<const float*>(d.src);
         for (long k = (long)blk * 256 + threadIdx.x; k < d.K; k += (long)nblk * 256) d.dst[k] += src[k];
+        return;
+    }
+    if (d.nrep < 0) {
+        const float* src = reinterpret_cast<const float*>(d.src);
+        for (long k = (long)blk * 256 + threadIdx.x; k < d.K; k += (long)nblk * 256) {
+            float s = src[k];
+            for (long r = 1; r < -d.nrep; ++r) s += src[r * d.stride + k];
+            d.dst[k] += s;
+        }
         return;
     }
     acc_reduce_rows(reinterpret_cast<const mm_acc_t*>(d.src), d.dst, d.K, d.stride, (long)blk * 16, (long)nblk * 16);

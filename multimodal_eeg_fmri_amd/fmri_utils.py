@@ -224,6 +224,83 @@ class fMRIVolumeEncoder3D(nn.Module):
         return ops.volume_encoder_forward(self, x)
 
 
+class LagAttentionPool(nn.Module):
+    """Learned pooling over the ``frames`` feature rows of a sample, x (B, F, N) -> (B, N):
+    ``s = (x . query) / sqrt(N) + lag_bias``, ``w = softmax_f(s)``, ``out = sum_f w_f x_f`` (csrc/lagpool.hip, DESIGN.md
+    section 5x).  ``query`` (N,) scores a frame by its content, ``lag_bias`` (F,) by its place in the sequence - the lag
+    after the EEG epoch.  Both start at zero: the pool then is the plain mean over the frames, and ``query`` has a
+    non-zero gradient from the first step.  1 <= frames <= 64; dim a multiple of 4 in 4..1024.
+    ``forward(x, return_weights=False)``; CPU tensors run the torch composition of the same formulas (host tests and
+    analysis code), device tensors the kernels."""
+
+    def __init__(self, frames: int, dim: int):
+        super().__init__()
+        ops.lag_pool_check(frames, dim, "LagAttentionPool")
+        self.frames, self.dim = int(frames), int(dim)
+        self.query = nn.Parameter(torch.zeros(self.dim))
+        self.lag_bias = nn.Parameter(torch.zeros(self.frames))
+
+    def forward(self, x: torch.Tensor, return_weights: bool = False):
+        if x.dim() != 3 or tuple(x.shape[1:]) != (self.frames, self.dim):
+            raise ValueError(f"LagAttentionPool: expected (B, {self.frames}, {self.dim}) frame features, got shape {tuple(x.shape)}")
+        if x.is_cuda:
+            out, w = ops.lag_pool(x, self.query, self.lag_bias)
+        else:
+            s = (x * self.query).sum(dim=-1) / math.sqrt(self.dim) + self.lag_bias
+            w = torch.softmax(s, dim=1)
+            out = (w.unsqueeze(-1) * x).sum(dim=1)
+        return (out, w) if return_weights else out
+
+
+class fMRISequenceEncoder3D(nn.Module):
+    """(B, F, D, H, W) fp32 sequence of ``frames`` = F fMRI volumes -> (B, out_dim): the frames that follow an EEG epoch
+    (the BOLD response is spread over the next few TRs), each encoded by ONE shared ``frame_encoder`` - an
+    ``fMRIVolumeEncoder3D(1, out_dim, widths, dropout)`` - and pooled by ``lag_pool``, a ``LagAttentionPool``: the model
+    uses the neighbouring frames and says which lag carried the match (`lag_weights`).
+
+    The batch is run as B * F single-channel volumes, so the train-mode BatchNorm statistics are those of all B * F
+    volumes (`ops._seq_forward_impl`).  The same frame count for every sample; D, H, W >= 4 as for the volume encoder.
+    ``state_dict`` keys: ``frame_encoder.<the volume encoder's keys>``, ``lag_pool.query``, ``lag_pool.lag_bias``;
+    `from_volume_encoder` is the transfer route from a trained single-volume encoder.  With ``frames=1`` the pool is the
+    identity and features and gradients are the volume encoder's bit for bit."""
+
+    def __init__(self, frames: int, out_dim: int = 64, widths=(32, 64, 128), dropout: float = 0.3):
+        super().__init__()
+        ops.lag_pool_check(frames, out_dim, "fMRISequenceEncoder3D")
+        self.frames, self.out_dim = int(frames), int(out_dim)
+        self.frame_encoder = fMRIVolumeEncoder3D(1, out_dim, widths, dropout)
+        self.lag_pool = LagAttentionPool(frames, out_dim)
+        self.drop_p = dropout
+
+    @classmethod
+    def from_volume_encoder(cls, enc: "fMRIVolumeEncoder3D", frames: int) -> "fMRISequenceEncoder3D":
+        """a sequence encoder whose ``frame_encoder`` is a copy of a (trained) single-channel volume encoder, on its
+        device and in its train / eval mode; the pool starts as the mean over the frames"""
+        cl, lin = enc.conv_layers, enc.output_proj[2]
+        if cl[0].in_channels != 1:
+            raise ValueError(f"fMRISequenceEncoder3D.from_volume_encoder: the volume encoder must take 1 input channel, "
+                             f"got {cl[0].in_channels}")
+        seq = cls(frames, lin.out_features, (cl[0].out_channels, cl[5].out_channels, cl[10].out_channels), enc.drop_p)
+        seq.to(lin.weight.device)
+        seq.frame_encoder.load_state_dict(enc.state_dict())
+        return seq.train(enc.training)
+
+    def forward(self, x: torch.Tensor, return_weights: bool = False):
+        return ops.sequence_encoder_forward(self, x, return_weights)
+
+    @torch.no_grad()
+    def lag_weights(self, x: torch.Tensor) -> torch.Tensor:
+        """(B, F): how much each frame of each sample contributes to its feature - the eval-mode, no-grad read-out; the
+        train / eval flags are left as they were"""
+        modes = [(m, m.training) for m in self.modules()]
+        self.eval()
+        try:
+            return self.forward(x, return_weights=True)[1]
+        finally:
+            for m, mode in modes:
+                m.training = mode
+
+
 class VolumeTransforms(AS.StepCounter):
     """Augmenter of (B, 1, D, H, W) fMRI volumes, the voxel encoder's counterpart of ``EEGTransforms`` (the reference has no
     volume code; the transform is defined in DESIGN.md 5q).  Per sample, in this order and each with its own probability:

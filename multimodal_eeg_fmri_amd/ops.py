@@ -1667,6 +1667,121 @@ def volume_encoder_forward(m, x: torch.Tensor) -> torch.Tensor:
         return _vol_forward_impl(m, x.float(), False, False)[0]
 
 
+# ------------------------- lag attention pooling over fMRI frame sequences (fp32, csrc/lagpool.hip: one launch each way)
+LAG_MAX_FRAMES = 64
+LAG_MAX_DIM = 1024
+
+
+def lag_pool_check(frames, dim, who: str = "lag_pool"):
+    """what mm_lagpool_fwd / mm_lagpool_bwd take, checked before any launch: 1 <= F <= 64 frames of N features, N a
+    multiple of 4 in 4..1024"""
+    if not 1 <= int(frames) <= LAG_MAX_FRAMES:
+        raise ValueError(f"{who}: frames must be in 1..{LAG_MAX_FRAMES}, got {frames}")
+    if int(dim) % 4 != 0 or not 4 <= int(dim) <= LAG_MAX_DIM:
+        raise ValueError(f"{who}: the feature width must be a multiple of 4 in 4..{LAG_MAX_DIM}, got {dim}")
+
+
+def _lag_pool_args(x, q, c, who: str):
+    if x.dim() != 3:
+        raise ValueError(f"{who}: expected (B, F, N) frame features, got shape {tuple(x.shape)}")
+    B, F, N = x.shape
+    lag_pool_check(F, N, who)
+    if B < 1:
+        raise ValueError(f"{who}: empty batch")
+    if q.numel() != N or (c is not None and c.numel() != F):
+        raise ValueError(f"{who}: query must have N = {N} elements and lag_bias F = {F}, got {q.numel()}"
+                         f"{'' if c is None else f' and {c.numel()}'}")
+    return B, F, N
+
+
+def _chunked(t: torch.Tensor) -> torch.Tensor:
+    """fp32, contiguous and 16-byte aligned, as the lag pool's kernels read activations (a copy only when it is not)"""
+    t = t.detach().float().contiguous()
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+def lag_pool_fwd(x: torch.Tensor, query: torch.Tensor, lag_bias: torch.Tensor):
+    """x (B, F, N) fp32 frame features -> (out (B, N), weights (B, F)): weights = softmax over the frames of
+    (x . query) / sqrt(N) + lag_bias, out = the weighted sum of the frames (mm_lagpool_fwd, one launch)"""
+    B, F, N = _lag_pool_args(x, query, lag_bias, "lag_pool_fwd")
+    _need_gpu(x, query, lag_bias)
+    xc = _chunked(x)
+    out, attw = _empty((B, N), _F32, xc), _empty((B, F), _F32, xc)
+    _hip.call("mm_lagpool_fwd", xc, query.detach().float().contiguous(), lag_bias.detach().float().contiguous(), out, attw, B, F, N)
+    return out, attw
+
+
+def lag_pool_bwd(dout: torch.Tensor, x: torch.Tensor, weights: torch.Tensor, query: torch.Tensor):
+    """-> (dx (B, F, N), dparts (B, N + F)): the gradient of `lag_pool_fwd` w.r.t. the frames and the per-sample rows
+    (d query | d lag_bias), whose sums in ascending b are the two parameter gradients (mm_lagpool_bwd, one launch)"""
+    B, F, N = _lag_pool_args(x, query, None, "lag_pool_bwd")
+    if tuple(dout.shape) != (B, N) or tuple(weights.shape) != (B, F):
+        raise ValueError(f"lag_pool_bwd: dout must be {(B, N)} and weights {(B, F)}, got {tuple(dout.shape)} and {tuple(weights.shape)}")
+    _need_gpu(dout, x, weights, query)
+    xc = _chunked(x)
+    dx, dparts = _empty((B, F, N), _F32, xc), _empty((B, N + F), _F32, xc)
+    _hip.call("mm_lagpool_bwd", _chunked(dout), xc, weights.detach().float().contiguous(),
+              query.detach().float().contiguous(), dx, dparts, B, F, N)
+    return dx, dparts
+
+
+def lag_pool(x: torch.Tensor, query: torch.Tensor, lag_bias: torch.Tensor):
+    """`lag_pool_fwd` on the autograd tape (`autograd.LagPoolFn`) -> (out (B, N), weights (B, F)); the weights are a
+    read-out and carry no gradient"""
+    _lag_pool_args(x, query, lag_bias, "lag_pool")
+    _need_gpu(x, query, lag_bias)
+    if torch.is_grad_enabled() and (x.requires_grad or query.requires_grad or lag_bias.requires_grad):
+        from .autograd import LagPoolFn
+        return LagPoolFn.apply(x, query, lag_bias)
+    with torch.no_grad():
+        return lag_pool_fwd(x, query, lag_bias)
+
+
+def check_sequence_shape(m, shape, who: str = "fMRISequenceEncoder3D"):
+    """(B, F, D, H, W) with F = the encoder's frame count and every spatial extent >= 4 (`check_volume_shape`)"""
+    if len(shape) != 5:
+        raise ValueError(f"{who}: expected a (B, F, D, H, W) batch of fMRI frame sequences, got shape {tuple(shape)}")
+    if shape[1] != m.frames:
+        raise ValueError(f"{who}: the encoder pools F = {m.frames} frames, the batch has {shape[1]} (shape {tuple(shape)})")
+    if min(shape[2:]) < 4:
+        raise ValueError(f"{who}: every spatial extent must be >= 4 (two MaxPool3d(2) layers), got D, H, W = {tuple(shape[2:])}")
+    if shape[0] < 1:
+        raise ValueError(f"{who}: empty batch")
+
+
+def _seq_forward_impl(m, x: torch.Tensor, live: bool, save=None, need_dx: bool = False):
+    """`fMRISequenceEncoder3D` forward: the (B, F, D, H, W) batch is viewed as B * F single-channel volumes
+    (B * F, 1, D, H, W), run through `_vol_forward_impl` on ``m.frame_encoder`` and pooled over the frames
+    (mm_lagpool_fwd).  BY DEFINITION the train-mode BatchNorm statistics are those of all B * F volumes - every frame of
+    every sample counts alike, and the running statistics are updated once per step with them.
+    ``live`` False = the frozen form (eval kernels, no dropout seed drawn, nothing saved unless ``save``); ``save`` (default
+    = live) keeps what `autograd.sequence_encoder_bwd` needs; ``need_dx``: the caller wants d / d frames.
+    -> (features (B, out_dim), saved); saved["weights"] (B, F) are the lag weights of this pass."""
+    save = live if save is None else save
+    check_sequence_shape(m, x.shape)
+    B, F, D, H, W = x.shape
+    vols = x.float().contiguous().view(B * F, 1, D, H, W)
+    feats, sv = _vol_forward_impl(m.frame_encoder, vols, live, save, save=save, need_dx=need_dx)
+    pool = m.lag_pool
+    out, attw = lag_pool_fwd(feats.view(B, F, -1), pool.query, pool.lag_bias)
+    if not save:
+        return out, dict(weights=attw)
+    return out, dict(vol=sv, feats=feats, weights=attw, pool=pool, B=B, F=F, need_dx=need_dx)
+
+
+def sequence_encoder_forward(m, x: torch.Tensor, return_weights: bool = False):
+    check_sequence_shape(m, x.shape)
+    _need_gpu(x)
+    if m.training or _wants_grad(m, x):
+        from .autograd import SequenceEncoderFn
+        out, attw = SequenceEncoderFn.run(m, x)
+    else:
+        with torch.no_grad():
+            out, sv = _seq_forward_impl(m, x, False)
+            attw = sv["weights"]
+    return (out, attw) if return_weights else out
+
+
 # ------------------------------------------------- projection bridge (fp32)
 def small_linear(x: torch.Tensor, lin, *, act="none", drop_p=0.0, seed=0, want_pre=False, bn=None,
                  weight=None, bias=None):

@@ -584,6 +584,90 @@ def key_case(B=32, N=128, step_iters=30, rounds=5, stamps=True):
                   "; ".join(f"{tr.STAMP_NAMES[i]} {acc[i].item() / 20:.1f}" for i in order))
 
 
+def lagpool_case(B=32, F=8, N=64, step_iters=30, rounds=5, stamps=True):
+    """the lag attention pool.  (a) mm_lagpool_fwd / mm_lagpool_bwd at B = 32, F = 8, N = 64 against the same operation as a
+    chain of torch ops (matmul, softmax, bmm; the backward is their autograd) - eager launches between HIP events and the
+    kernels graph-replayed, interleaved rounds in the same run, median [min .. max].  (b) the C2 graph step (B = 32,
+    64 ch x 1024, 32^3 voxels) of the default trainer against `fMRISequenceEncoder3D(frames=1)`: the difference is the
+    pool's two graph nodes.  (c) the step at F = 4 (128 volumes of 32^3 per step: `step_schedule` issues the fMRI branch
+    first) and the phase stamps of both streams at F = 1 and F = 4."""
+    torch.manual_seed(0)
+    x = torch.randn(B, F, N, device="cuda")
+    q, c, dout = torch.randn(N, device="cuda"), torch.randn(F, device="cuda"), torch.randn(B, N, device="cuda")
+    out, attw = torch.empty(B, N, device="cuda"), torch.empty(B, F, device="cuda")
+    dx, dparts = torch.empty(B, F, N, device="cuda"), torch.empty(B, N + F, device="cuda")
+    r = 1.0 / math.sqrt(N)
+    xt, qt, ct = (t.clone().requires_grad_(True) for t in (x, q, c))
+
+    def torch_fwd():
+        a = torch.softmax(torch.matmul(xt, qt) * r + ct, dim=1)
+        return torch.bmm(a.unsqueeze(1), xt).squeeze(1)
+
+    def torch_fwd_bwd():
+        xt.grad = qt.grad = ct.grad = None
+        torch_fwd().backward(dout)
+
+    def k_fwd():
+        _hip.call("mm_lagpool_fwd", x, q, c, out, attw, B, F, N)
+
+    def k_bwd():
+        _hip.call("mm_lagpool_bwd", dout, x, attw, q, dx, dparts, B, F, N)
+    k_fwd()
+    # (x, q and c ask for no gradient: this forward keeps no tape)
+    plain_fwd = lambda: torch.bmm(torch.softmax(torch.matmul(x, q) * r + c, dim=1).unsqueeze(1), x)   # noqa: E731
+    cases = [("torch chain, forward (no tape)", plain_fwd), ("torch chain, forward + autograd backward", torch_fwd_bwd),
+             ("mm_lagpool_fwd", k_fwd), ("mm_lagpool_bwd", k_bwd)]
+    eager = {name: [] for name, _ in cases}
+    replayed = {"mm_lagpool_fwd": [], "mm_lagpool_bwd": []}
+    for _ in range(rounds):
+        for name, fn in cases:
+            eager[name].append(timeit(fn, iters=20, rounds=1))
+        replayed["mm_lagpool_fwd"].append(graph_time(k_fwd))
+        replayed["mm_lagpool_bwd"].append(graph_time(k_bwd))
+    for name, _ in cases:
+        tail = f"   graph {_spread(replayed[name])}" if name in replayed else ""
+        print(f"lag pool B={B} F={F} N={N}: {name:42s} eager {_spread(eager[name])}{tail}")
+    tf, tfb = statistics.median(eager[cases[0][0]]), statistics.median(eager[cases[1][0]])
+    print(f"lag pool B={B} F={F} N={N}: torch chain backward alone (fwd + bwd minus the forward without a tape): {tfb - tf:.1f} us")
+    from multimodal_eeg_fmri_amd.bridge_trainer import BridgeTrainer, synthetic_pairs
+    from multimodal_eeg_fmri_amd.fmri_utils import fMRISequenceEncoder3D
+    eeg, fmri = synthetic_pairs(32, 64, 1024, (32, 32, 32))
+    seq4 = torch.randn(32, 4, 32, 32, 32, device="cuda")
+
+    def trainer(frames):
+        ops.set_seed_epoch(None)
+        torch.manual_seed(0)
+        enc = None if frames is None else fMRISequenceEncoder3D(frames, 64, dropout=0.3)
+        return BridgeTrainer(eeg_channels=64, dropout=0.3, fmri_encoder=enc).train()
+    trs = [("default trainer", trainer(None), fmri), ("sequence encoder, frames=1", trainer(1), fmri),
+           ("sequence encoder, frames=4", trainer(4), seq4)]
+    for _, tr, f in trs:
+        tr.train_step(eeg, f)
+    steps = [[] for _ in trs]
+    for _ in range(rounds):
+        for i, (_, tr, f) in enumerate(trs):
+            steps[i].append(timeit(lambda: tr.train_step(eeg, f), iters=step_iters, rounds=1))
+    t0, t1 = statistics.median(steps[0]), statistics.median(steps[1])
+    for (name, tr, _), t in zip(trs, steps):
+        print(f"C2 graph step B=32: {name:28s} {_spread(t)}   fmri_first={tr.schedule.fmri_first}")
+    print(f"C2 graph step B=32: frames=1 against the default trainer {t1 - t0:+.1f} us ({100 * (t1 / t0 - 1):+.2f} %)")
+    if stamps:
+        for name, frames, f in (("frames=1", 1, fmri), ("frames=4", 4, seq4)):
+            tr = trainer(frames)
+            tr.stamps = torch.zeros(16, dtype=torch.int64, device="cuda")
+            acc = torch.zeros(16, dtype=torch.float64)
+            for _ in range(5):
+                tr.train_step(eeg, f)
+            for _ in range(20):
+                tr.train_step(eeg, f)
+                torch.cuda.synchronize()
+                s = tr.stamps.cpu().double()
+                acc += (s - s[0]) / 100.0
+            order = sorted(range(14), key=lambda i: acc[i].item())
+            print(f"stamps, sequence encoder {name}, fmri_first={tr.schedule.fmri_first} (us after step start, graph step): " +
+                  "; ".join(f"{tr.STAMP_NAMES[i]} {acc[i].item() / 20:.1f}" for i in order))
+
+
 def ema_case(step_iters=30, rounds=5):
     """averaged weights in the update kernel, at the default C2 trainer's bucket size, graph-replayed launches in the same
     run, interleaved rounds: mm_adamw_clip, mm_adamw_clip_ema (the same update + the average: 10 streams over the bucket
@@ -1352,6 +1436,9 @@ def main():
         return
     if flt == "ema":
         ema_case()
+        return
+    if flt == "lagpool":
+        lagpool_case()
         return
     if flt == "pgroups":
         param_groups_case()
