@@ -907,12 +907,17 @@ int mm_learned_fusion_bwd(const float* f0, const float* f1, const float* f2, con
 int mm_softmax2_concat_bwd(const float* dout, const float* a, const float* c, const float* pa,
                            const float* pc, float* da, float* dc, float* dpa, float* dpc, int B, int Ha,
                            int Hc, hipStream_t stream);
-/* nn.CrossEntropyLoss(weight=class_weight) (_test_bridge.py:858; run_fmri_v11.py): loss_out[0] += loss */
+/* nn.CrossEntropyLoss(weight=class_weight) (_test_bridge.py:858; run_fmri_v11.py): loss_out[0] += loss; dlogits [B][C]
+ * nullable.  Labels: the 64-bit label is compared with [0, C) before anything is indexed with it; a row whose label is
+ * outside (-100, C, 2^32 + 1, ...) is dropped like torch's ignore_index: it adds nothing to the loss sum or the weight
+ * sum and its gradient row is 0 (every row dropped: 0 / 0, as torch) */
 int mm_weighted_ce(const float* logits, const void* target_i64, const float* class_weight, float* loss_out,
                    float* dlogits, int B, int C, hipStream_t stream);
 /* FocalLoss (CrossModal_EEG_scr.ipynb cell 20; FlexibleTrainer(use_focal_loss=True), cell 23):
  * fl_b = alpha (1 - exp(-ce_b))^gamma ce_b.  loss_out[0] += scale * sum_b fl_b (zeroed by the caller),
- * per_sample[b] = fl_b (nullable), dlogits = d fl_b / d logits without the reduction's factor (nullable) */
+ * per_sample[b] = fl_b (nullable), dlogits = d fl_b / d logits without the reduction's factor (nullable).
+ * Labels as mm_weighted_ce: a row whose label is outside [0, C) is dropped - per_sample[b] = 0, a zero gradient row,
+ * nothing added to the sum; `scale` stays the caller's */
 int mm_focal_loss(const float* logits, const void* target_i64, float* loss_out, float* per_sample,
                   float* dlogits, int B, int C, float alpha, float gamma, float scale, hipStream_t stream);
 /* HybridFusionModule gate + mix + conn boost (crossmodal_v4_enhancements.py:787-797) */
@@ -921,7 +926,8 @@ int mm_gate2_mix(const float* g, const float* erp, const float* pw, const float*
 int mm_gate2_mix_bwd(const float* dcomb, const float* g, const float* erp, const float* pw, float* derp,
                      float* dpw, float* dconn, float* dg, int B, int H, float boost, hipStream_t stream);
 /* LabelSmoothingCrossEntropy (crossmodal_v4_enhancements.py:665-677): loss_out[0] += loss (zeroed by
- * the caller), dlogits = d loss / d logits; target is int64 class indices */
+ * the caller), dlogits = d loss / d logits (nullable); target is int64 class indices.  Labels as mm_weighted_ce: a row
+ * whose label is outside [0, C) is dropped - it adds nothing, its gradient row is 0, the divisor stays B */
 int mm_smoothed_ce(const float* logits, const void* target_i64, float* loss_out, float* dlogits, int B,
                    int C, float smoothing, hipStream_t stream);
 /* Multi-scale STFT power front-end (extension a-X3; semantics = torch.stft(center=True,

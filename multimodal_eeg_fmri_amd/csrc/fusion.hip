@@ -62,7 +62,7 @@ __global__ void softmax2_concat_bwd_kernel(const float* __restrict__ dout, const
 extern "C" {
 int mm_softmax2_concat_bwd(const float* dout, const float* a, const float* c, const float* pa, const float* pc,
                            float* da, float* dc, float* dpa, float* dpc, int B, int Ha, int Hc, hipStream_t st) {
-    MM_REQUIRE(dout && a && c && pa && pc && da && dc && dpa && dpc && B > 0, "softmax2_concat_bwd: null");
+    MM_REQUIRE(dout && a && c && pa && pc && da && dc && dpa && dpc && B > 0 && Ha > 0 && Hc > 0, "softmax2_concat_bwd: null");
     hipLaunchKernelGGL(softmax2_concat_bwd_kernel, dim3(1), dim3(1024), 0, st, dout, a, c, pa, pc, da, dc, dpa, dpc, B, Ha, Hc);
     return mm_check_launch("softmax2_concat_bwd");
 }
@@ -175,8 +175,8 @@ extern "C" {
 int mm_learned_fusion_bwd(const float* f0, const float* f1, const float* f2, const float* dyn, const float* logits,
                           const float* temperature, const float* dfused, float* df0, float* df1, float* df2,
                           float* ddyn, float* dlogits, float* dtemp, int B, int H, int M, hipStream_t st) {
-    MM_REQUIRE(f0 && f1 && dyn && logits && temperature && dfused && df0 && df1 && ddyn && dlogits && dtemp,
-               "learned_fusion_bwd: null");
+    MM_REQUIRE(f0 && f1 && dyn && logits && temperature && dfused && df0 && df1 && ddyn && dlogits && dtemp &&
+               B > 0 && H > 0, "learned_fusion_bwd: null");
     MM_REQUIRE(M >= 2 && M <= 3 && (M == 2 || (f2 && df2)), "learned_fusion_bwd: M=%d", M);
     hipLaunchKernelGGL(learned_fusion_bwd_kernel, dim3(1), dim3(1024), 0, st, f0, f1, f2, dyn, logits,
                        temperature, dfused, df0, df1, df2, ddyn, dlogits, dtemp, B, H, M);
@@ -381,7 +381,7 @@ __global__ void gate2_mix_kernel(const float* __restrict__ g, const float* __res
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < B * 2 * H; i += gridDim.x * blockDim.x) {
         const int b = i / (2 * H), j = i % (2 * H);
         const float g0 = g[2 * b], g1 = g[2 * b + 1], m = fmaxf(g0, g1);
-        const float e0 = __expf(g0 - m), e1 = __expf(g1 - m);
+        const float e0 = expf(g0 - m), e1 = expf(g1 - m);    // expf: __expf is off by |x| 2^-24 relative, a far gate logit's weight
         const float w0 = e0 / (e0 + e1), w1 = e1 / (e0 + e1);
         comb[i] = j < H ? w0 * erp[(size_t)b * H + j] + w1 * pw[(size_t)b * H + j] : conn[(size_t)b * H + (j - H)] * boost;
         if (j == 0 && gate) { gate[2 * b] = w0; gate[2 * b + 1] = w1; }
@@ -408,7 +408,7 @@ __global__ void gate2_mix_bwd_kernel(const float* __restrict__ dcomb, const floa
     const int lane = threadIdx.x & 63;
     if (b >= B) return;
     const float g0 = g[2 * b], g1 = g[2 * b + 1], m = fmaxf(g0, g1);
-    const float e0 = __expf(g0 - m), e1 = __expf(g1 - m);
+    const float e0 = expf(g0 - m), e1 = expf(g1 - m);        // the forward's expression: the same weights
     const float w0 = e0 / (e0 + e1), w1 = e1 / (e0 + e1);
     float a0 = 0.f, a1 = 0.f;
     for (int h = lane; h < H; h += 64) {

@@ -1,10 +1,15 @@
 // The three classification losses with their logit gradients, one workgroup each (B is a batch size): class-weighted
 // cross entropy, focal loss, label-smoothed cross entropy.  Callers: small_autograd.py (weighted_ce, focal_loss,
 // smoothed_ce).
+// Labels: every kernel compares the 64-bit label with [0, C) before anything is indexed with it (label_ok); a row whose
+// label is outside (-100, C, 2^32 + 1) is dropped: nothing read through the label, no loss term, a zero gradient row.
 #include "common.h"
 
 namespace {
-// nn.CrossEntropyLoss(weight=w): loss = sum_b w[t_b] nll_b / sum_b w[t_b]   (single block, B small)
+__device__ __forceinline__ bool label_ok(long long t, int C) { return t >= 0 && t < (long long)C; }
+
+// nn.CrossEntropyLoss(weight=w): loss = sum_b w[t_b] nll_b / sum_b w[t_b]   (single block, B small); both sums run over
+// the rows with a label in [0, C) only (ignore_index for every label outside)
 __global__ void weighted_ce_kernel(const float* __restrict__ logits, const long long* __restrict__ target,
                                    const float* __restrict__ cw, float* __restrict__ out, float* __restrict__ dlogits,
                                    int B, int C) {
@@ -17,7 +22,8 @@ __global__ void weighted_ce_kernel(const float* __restrict__ logits, const long 
             for (int c = 0; c < C; ++c) m = fmaxf(m, z[c]);
             float se = 0.f;
             for (int c = 0; c < C; ++c) se += __expf(z[c] - m);
-            const int t = (int)target[b];
+            const long long t = target[b];
+            if (!label_ok(t, C)) continue;                   // dropped row: weight 0 in both sums (ignore_index)
             const float w = cw ? cw[t] : 1.f;
             ws += w; ls += w * (m + __logf(se) - z[t]);
         }
@@ -28,12 +34,13 @@ __global__ void weighted_ce_kernel(const float* __restrict__ logits, const long 
     if (!dlogits) return;
     for (int i = threadIdx.x; i < B * C; i += blockDim.x) {
         const int b = i / C, c = i % C;
+        const long long t = target[b];
+        if (!label_ok(t, C)) { dlogits[i] = 0.f; continue; }
         const float* z = logits + (size_t)b * C;
         float m = -INFINITY;
         for (int k = 0; k < C; ++k) m = fmaxf(m, z[k]);
         float se = 0.f;
         for (int k = 0; k < C; ++k) se += __expf(z[k] - m);
-        const int t = (int)target[b];
         const float w = cw ? cw[t] : 1.f;
         dlogits[i] = w * (__expf(z[c] - m) / se - (c == t ? 1.f : 0.f)) / wsum_s;
     }
@@ -60,12 +67,18 @@ __global__ void focal_loss_kernel(const float* __restrict__ logits, const long l
     __shared__ float red[256];
     float acc = 0.f;
     for (int b = threadIdx.x; b < B; b += blockDim.x) {
+        const long long t = target[b];
+        if (!label_ok(t, C)) {                               // dropped row: fl_b = 0, zero gradient row
+            if (per_sample) per_sample[b] = 0.f;
+            if (dlogits)
+                for (int c = 0; c < C; ++c) dlogits[(size_t)b * C + c] = 0.f;
+            continue;
+        }
         const float* z = logits + (size_t)b * C;
         float m = -INFINITY;
         for (int c = 0; c < C; ++c) m = fmaxf(m, z[c]);
         float se = 0.f;
         for (int c = 0; c < C; ++c) se += __expf(z[c] - m);
-        const int t = (int)target[b];
         const float ce = m + __logf(se) - z[t];
         const float pt = __expf(-ce), q = fmaxf(1.f - pt, 0.f);
         const float qg = (gamma == 0.f) ? 1.f : powf(q, gamma);
@@ -109,18 +122,23 @@ __global__ void smoothed_ce_kernel(const float* __restrict__ logits, const long 
     __shared__ float red[256];
     float acc = 0.f;
     for (int b = threadIdx.x; b < B; b += blockDim.x) {
+        const long long t = target[b];
+        if (!label_ok(t, C)) {                               // dropped row: no term (the divisor stays B), zero gradient row
+            if (dlogits)
+                for (int c = 0; c < C; ++c) dlogits[(size_t)b * C + c] = 0.f;
+            continue;
+        }
         const float* z = logits + (size_t)b * C;
         float m = -INFINITY;
         for (int c = 0; c < C; ++c) m = fmaxf(m, z[c]);
         float se = 0.f, sz = 0.f;
         for (int c = 0; c < C; ++c) { se += __expf(z[c] - m); sz += z[c]; }
         const float lse = m + __logf(se);
-        const int t = (int)target[b];
         const float nll = lse - z[t], smooth = lse - sz / (float)C;
         acc += ((1.f - smoothing) * nll + smoothing * smooth) / (float)B;
         if (dlogits)
             for (int c = 0; c < C; ++c) {
-                const float p = __expf(z[c] - lse);
+                const float p = __expf(z[c] - m) / se;       // not exp(z - lse): lse is rounded at the size of |m|
                 dlogits[(size_t)b * C + c] = (p - (c == t ? 1.f - smoothing : 0.f) - smoothing / (float)C) / (float)B;
             }
     }

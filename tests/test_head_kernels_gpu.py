@@ -6,8 +6,9 @@ kernels next to them) against plain fp64 references of the same operation, compu
     forward's T = 4 / 2 / 1 lane groups, K % 4 != 0 (the scalar loop) and K = 1024 (HEAD_MAXK);
   - the STFT power front end (mm_stft_power) at every accepted nfft: the radix-2 FFT kernel (8 .. 256) and the direct DFT
     (512, 1024) with and without the frame-block split, into a channel window of a wider row;
-  - the small fused tails of the V4 / Lite / fMRI models, the losses, and the elementwise / layout kernels, at sizes past
-    every thread and grid stride.
+  - the small fused tails of the V4 / Lite / fMRI models and the losses at one large order-1 shape each (their ragged
+    shapes, grid-stride second trips, absent optional arguments, saturated inputs and out-of-range labels are in
+    tests/test_fusion_loss_edges_gpu.py), and the elementwise / layout kernels at sizes past every thread and grid stride.
 
 Dropout masks come from the host replica (oracle/dropout_replica.py: keep_scale); rates are exact binary fractions, so
 the kernels' fp32 threshold and the replica's fp64 one are the same integer.  Each figure is a rel-L2 error
