@@ -746,6 +746,25 @@ int mm_clip_loss_ws_floats(int B, int Bg, int* floats_host, hipStream_t stream);
 int mm_clip_loss_own_rows_grouped(const float* z_all, const int* gid_all, const float* logit_scale, float* scal4,
                                   float* dz_local, float* ws, int B, int Bg, int N, int row0, hipStream_t stream);
 int mm_clip_loss_grouped_ws_floats(int B, int Bg, int* floats_host, hipStream_t stream);
+/* the grouped loss with IGNORED keys: the ids are positions on a timeline and temporal neighbours are neither positives
+ * nor negatives.  gid_all int32 [Bg] as above, radius >= 0.  For query r and key j, d = |gid_j - gid_r| computed so that it
+ * cannot wrap (ids -2^31 and 2^31 - 1 are 2^32 - 1 apart):
+ *   d == 0: positive, P(r) (always holds r)      0 < d <= radius: ignored      d > radius: negative
+ *   A(r) = {j : d == 0 or d > radius}, the admitted keys; the relation is symmetric and serves rows and columns alike
+ *   l_row(r) = LSE_{j in A(r)}(s C[r][j]) - LSE_{j in P(r)}(s C[r][j]), l_col(r) the same over column r, loss_r = (l_row + l_col) / 2
+ *   dL/dC[r][j] = 0.5/B * s * ([j in A(r)] (P_row + P_col)[r][j] - [d == 0] (Q_row + Q_col)[r][j])
+ * with P_row[r][j] = exp(s C[r][j] - LSE_A(row r)), P_col[r][j] = exp(s C[r][j] - LSE_A(column j)) and Q the same over the
+ * positive sets.  An ignored key is in no normaliser and no positive set, its pair's coefficient is exactly 0.f (stored, not
+ * computed: whatever finite values the key holds), and d loss / d logit_scale sums over A and P in the same way.  top-1 counts
+ * row r when max_{j in P(r)} C[r][j] >= max_{j in A(r)} C[r][j] (a tie FOR it).  A row without an admitted negative has
+ * A = P: loss, d / d logit_scale and gradient exactly 0 (stored, as for an ignored pair).  radius = 0 is mm_clip_loss_own_rows_grouped's loss.  scal4, dz_local, the own
+ * rows (B, Bg, row0) and the rules (no float atomics, fixed-order sums, same inputs -> bit-identical outputs) as above.
+ * ws = mm_clip_loss_masked_ws_floats(B, Bg) floats, no initialisation.  N % 4 == 0.  Two launches on `stream`.
+ * Extension: the reference has no contrastive trainer. */
+int mm_clip_loss_own_rows_masked(const float* z_all, const int* gid_all, const float* logit_scale, float* scal4,
+                                 float* dz_local, float* ws, int B, int Bg, int N, int row0, int radius,
+                                 hipStream_t stream);
+int mm_clip_loss_masked_ws_floats(int B, int Bg, int* floats_host, hipStream_t stream);
 /* pairwise sigmoid loss (Zhai et al., "Sigmoid Loss for Language Image Pre-Training") on the same inputs: z_all [Bg][2N]
  * L2-normalised [ze | zf] rows of the gathered batch, this rank's pairs at rows [row0, row0+B), gid_all int32 [Bg] or
  * NULL, and two device scalars logit_scale (ln s) and logit_bias (b).  Every pair is its own binary problem:
@@ -770,6 +789,16 @@ int mm_sigmoid_loss_own_rows(const float* z_all, const int* gid_all, const float
                              float* scal5, float* dz_local, float* ws, int B, int Bg, int N, int row0,
                              hipStream_t stream);
 int mm_sigmoid_loss_ws_floats(int B, int Bg, int* floats_host, hipStream_t stream);
+/* the same with IGNORED pairs (relations, gid_all (required) and radius >= 0 as mm_clip_loss_own_rows_masked): an ignored
+ * pair (0 < |gid_j - gid_r| <= radius, the difference computed so that it cannot wrap) contributes l[r][j] = 0 and
+ * G[r][j] = exactly 0.f to every sum above, in both directions; y = +1 where the ids are equal, -1 beyond the radius.  The
+ * 1/B normalisation is unchanged; the top-1 flags are mm_clip_loss_own_rows_masked's (the maximum runs over the admitted
+ * keys).  radius = 0 is mm_sigmoid_loss_own_rows with ids.  ws = mm_sigmoid_loss_masked_ws_floats(B, Bg) floats, no
+ * initialisation.  N % 4 == 0.  Two launches on `stream`; same inputs -> bit-identical outputs. */
+int mm_sigmoid_loss_own_rows_masked(const float* z_all, const int* gid_all, const float* logit_scale,
+                                    const float* logit_bias, float* scal5, float* dz_local, float* ws, int B, int Bg,
+                                    int N, int row0, int radius, hipStream_t stream);
+int mm_sigmoid_loss_masked_ws_floats(int B, int Bg, int* floats_host, hipStream_t stream);
 /* symmetric InfoNCE against the batch AND a cross-batch memory of earlier embeddings (csrc/clip_bank.hip; Wang et al.,
  * "Cross-Batch Memory for Embedding Learning").  All storage is the caller's device memory, allocated before any capture:
  *   bank     fp32  [K][2N]  rows [ze | zf], L2-normalised, exactly as z (keys only, constants: no loss, no gradient)

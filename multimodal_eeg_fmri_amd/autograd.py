@@ -1026,8 +1026,9 @@ class ClipLossFn(torch.autograd.Function):
     gathered gradients would deliver - and the usual gradient all-reduce of data parallelism completes it."""
 
     @staticmethod
-    def forward(ctx, z, logit_scale, group, gid=None):
-        """``gid``: (B,) int32 device group ids (ops.group_ids) -> the grouped loss; gathered like the embeddings"""
+    def forward(ctx, z, logit_scale, group, gid=None, radius=0):
+        """``gid``: (B,) int32 device group ids (ops.group_ids) -> the grouped loss; gathered like the embeddings.
+        ``radius`` > 0: ids within it are ignored keys (``mm_clip_loss_own_rows_masked``)"""
         from . import dp
         z = z.contiguous().float()
         B, N2 = z.shape
@@ -1038,7 +1039,7 @@ class ClipLossFn(torch.autograd.Function):
         dz = _empty((B, N2), _F32, z) if need_grad else None
         ls = logit_scale.detach().reshape(1).float().contiguous()
         gid_all = None if gid is None else dp.gather_embeddings(gid.view(B, 1), group).view(-1)
-        ops.clip_loss_own_rows(z_all, gid_all, ls, scal, dz, B, rank * B)
+        ops.clip_loss_own_rows(z_all, gid_all, ls, scal, dz, B, rank * B, radius)
         if need_grad:
             ctx.save_for_backward(dz, scal)
         return scal[0].clone(), scal[1].clone(), scal[2].clone()
@@ -1046,7 +1047,7 @@ class ClipLossFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_loss, g_a, g_b):
         dz, scal = ctx.saved_tensors
-        return dz * g_loss, (scal[3] * g_loss).reshape(()), None, None
+        return dz * g_loss, (scal[3] * g_loss).reshape(()), None, None, None
 
 
 class ClipBankLossFn(torch.autograd.Function):
@@ -1101,7 +1102,7 @@ class SigmoidLossFn(torch.autograd.Function):
     the same own-rows gradient; one more learnable scalar, ``logit_bias``."""
 
     @staticmethod
-    def forward(ctx, z, logit_scale, logit_bias, group, gid=None):
+    def forward(ctx, z, logit_scale, logit_bias, group, gid=None, radius=0):
         from . import dp
         z = z.contiguous().float()
         B, N2 = z.shape
@@ -1113,7 +1114,7 @@ class SigmoidLossFn(torch.autograd.Function):
         ls = logit_scale.detach().reshape(1).float().contiguous()
         lb = logit_bias.detach().reshape(1).float().contiguous()
         gid_all = None if gid is None else dp.gather_embeddings(gid.view(B, 1), group).view(-1)
-        ops.sigmoid_loss_own_rows(z_all, gid_all, ls, lb, scal, dz, B, rank * B)
+        ops.sigmoid_loss_own_rows(z_all, gid_all, ls, lb, scal, dz, B, rank * B, radius)
         if need_grad:
             ctx.save_for_backward(dz, scal)
         return scal[0].clone(), scal[1].clone(), scal[2].clone()
@@ -1121,4 +1122,4 @@ class SigmoidLossFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_loss, g_a, g_b):
         dz, scal = ctx.saved_tensors
-        return dz * g_loss, (scal[3] * g_loss).reshape(()), (scal[4] * g_loss).reshape(()), None, None
+        return dz * g_loss, (scal[3] * g_loss).reshape(()), (scal[4] * g_loss).reshape(()), None, None, None

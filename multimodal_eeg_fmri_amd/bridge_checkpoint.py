@@ -14,6 +14,7 @@ The file is the container of the reference's loops and of `FlexibleTrainer.save_
   (``fmri_augment``: the same for a volume augmenter; ``eeg_time_augment``: for a temporal EEG augmenter, whose step index
   is ``augment``'s), -
   only for a trainer of the pairwise sigmoid loss - ``loss`` = ``"sigmoid"`` (absent: InfoNCE), and - only for a trainer
+  built with ``neighbour_radius > 0`` - ``neighbour_radius`` (absent: 0, no ignored neighbours), and - only for a trainer
   built with ``classify=True`` - ``classify`` = ``{ce_weight, num_classes, class_weight}``, and - only for a trainer with
   a cross-batch memory (``bank_size > 0``) - ``bank`` = ``{size, warmup, grouped, state, rows, ids}``: the ring's words,
   rows and group ids (``rows`` / ``ids`` None before the first training step; with ``key_encoder=True`` one more field,
@@ -211,6 +212,8 @@ class TrainerCheckpointMixin:
                 bts[a.attr] = dict(getattr(self, a.attr).params(), step=int(getattr(self, a.counter)))
         if getattr(self, "loss", "infonce") != "infonce":          # (absent for the default loss: the container is unchanged)
             bts["loss"] = self.loss
+        if getattr(self, "neighbour_radius", 0):                   # (absent at radius 0: the container is unchanged)
+            bts["neighbour_radius"] = int(self.neighbour_radius)
         if self.checkpoint_classify() is not None:                 # (absent without classify: the container is unchanged)
             bts["classify"] = self.checkpoint_classify()
         if self.checkpoint_bank() is not None:                     # (absent without a bank: the container is unchanged)
@@ -251,6 +254,9 @@ class TrainerCheckpointMixin:
         loss, theirs_loss = getattr(self, "loss", "infonce"), bts.get("loss", "infonce")
         if loss != theirs_loss:                                    # before the shapes: logit_bias exists under one loss only
             raise ValueError(f"load_checkpoint_state: loss differs: checkpoint {theirs_loss!r}, trainer {loss!r}")
+        radius, theirs_radius = int(getattr(self, "neighbour_radius", 0)), int(bts.get("neighbour_radius", 0))
+        if radius != theirs_radius:                                # the same weights under another loss: not a resume
+            raise ValueError(f"load_checkpoint_state: neighbour_radius differs: checkpoint {theirs_radius}, trainer {radius}")
         mine_cls = self.checkpoint_classify()
         theirs_cls = bts.get("classify")
         if (mine_cls is None) != (theirs_cls is None):             # before the shapes and the bucket layout, which differ too

@@ -52,7 +52,7 @@ class BridgeTrainer(TrainerCheckpointMixin, TrainerStagingMixin, nn.Module):
                  classify: bool = False, ce_weight: float = 1.0, class_weight=None, num_classes: int = 2,
                  fmri_encoder: Optional[nn.Module] = None, bank_size: int = 0, bank_warmup: int = 0, fmri_augment=None,
                  ema_decay: float = 0.0, ema_warmup: bool = True, lr_scale=None, no_decay: bool = False, freeze=(),
-                 eeg_time_augment=None, key_encoder: bool = False):
+                 eeg_time_augment=None, key_encoder: bool = False, neighbour_radius: int = 0):
         """``eeg_encoder``: the EEG branch when it is not the default ``EnhancedERPEncoder(eeg_channels, hidden_dim,
         num_layers, num_heads, dropout)`` - an ``EnhancedPowerEncoder`` (enhanced_models_v4.py:196-285) or a
         ``MultiScaleSTFTPowerEncoder`` (BASELINE config #5: raw EEG -> multi-scale STFT power -> a4); it must end in
@@ -137,8 +137,22 @@ class BridgeTrainer(TrainerCheckpointMixin, TrainerStagingMixin, nn.Module):
         keys); gradients flow through the online rows - the queries - only.  Each encoder's key pass is issued in front
         of its online pass on that branch's stream: it reads the BatchNorm running statistics as they stood before this
         step's update, and step t's keys come from the average after step t - 1.  During ``bank_warmup`` the same kernel
-        runs with no valid bank row (decided on the device): the step is captured once.  False (default): unchanged."""
+        runs with no valid bank row (decided on the device): the step is captured once.  False (default): unchanged.
+        ``neighbour_radius`` = R > 0: the ``groups=`` ids are positions on a timeline (`bridge_utils.timeline_ids`) and a
+        pair whose id is within R of the query's, and not equal to it, is IGNORED by the contrastive loss - out of the
+        softmax normaliser, out of the positive set, exactly zero gradient (mm_clip_loss_own_rows_masked /
+        mm_sigmoid_loss_own_rows_masked in place of the grouped launch): consecutive epochs of a
+        recording, which share most of their input, stop being pushed apart.  `train_step`, `forward` and `evaluate`
+        then need ``groups=`` (ValueError otherwise); no bank and no key encoder (ValueError: their kernels have no
+        ignore relation).  `evaluate_retrieval` still ranks neighbours.  0 (default): unchanged."""
         super().__init__()
+        self.neighbour_radius = int(neighbour_radius)
+        if self.neighbour_radius < 0:
+            raise ValueError(f"BridgeTrainer: neighbour_radius must be >= 0 (got {neighbour_radius})")
+        if self.neighbour_radius and (bank_size > 0 or key_encoder):
+            raise ValueError(f"BridgeTrainer: neighbour_radius={self.neighbour_radius} cannot be combined with bank_size > 0 or "
+                             "key_encoder=True: the bank kernels (mm_clip_bank_loss, mm_clip_key_loss) have no ignore "
+                             "relation yet, so a neighbour in the bank would still be a negative")
         self._frozen = self._check_freeze(freeze, group)
         self._lr_scale = self._check_lr_scale(lr_scale)
         self.no_decay = bool(no_decay)
@@ -511,9 +525,11 @@ class BridgeTrainer(TrainerCheckpointMixin, TrainerStagingMixin, nn.Module):
         streams (autograd replays each backward on its forward stream), so the
         many sub-chip kernels of one branch overlap the other's latency.
         ``groups``: (B,) integer ids, pairs with equal ids are positives of each other (ops.clip_loss)."""
-        gid = ops.group_ids(groups, eeg.shape[0], eeg.device, "BridgeTrainer")
+        gid = self._need_groups(ops.group_ids(groups, eeg.shape[0], eeg.device, "BridgeTrainer"), "forward")
         fe, ff = self._encode(eeg, fmri)
-        return self.head(fe, ff, self.group, gid)
+        if not self.neighbour_radius:
+            return self.head(fe, ff, self.group, gid)
+        return self.head(fe, ff, self.group, gid, self.neighbour_radius)
 
     # ------------------------------------------------------------------ step
     def _labels(self, labels, B: int, device, who: str):
@@ -523,6 +539,14 @@ class BridgeTrainer(TrainerCheckpointMixin, TrainerStagingMixin, nn.Module):
         if labels is not None and not self.classify:
             raise ValueError(f"{who}: labels= needs a trainer built with classify=True")
         return ops.class_labels(labels, B, self.num_classes, device, who)
+
+    def _need_groups(self, gid, who: str):
+        """``gid`` - or, for a trainer with ``neighbour_radius > 0`` called without ``groups=``, ``ValueError``: the ids
+        are the timeline positions the radius is measured on"""
+        if self.neighbour_radius and gid is None:
+            raise ValueError(f"{who}: this trainer was built with neighbour_radius={self.neighbour_radius} and needs groups= "
+                             "(the pairs' timeline ids, bridge_utils.timeline_ids)")
+        return gid
 
     def _check_fmri(self, shape, training: bool, who: str):
         """the fMRI batch's shape, before the first launch of a step (or of its capture): ``ValueError`` otherwise"""
@@ -555,7 +579,8 @@ class BridgeTrainer(TrainerCheckpointMixin, TrainerStagingMixin, nn.Module):
             self._fmri.capture_words(self.fmri_encoder, fmri.device)   # the forward launch's words exist before any capture
             if self._key is not None and "fmri_encoder" in self._key:
                 self._fmri.capture_words(self._key["fmri_encoder"], fmri.device)
-        gid = ops.group_ids(groups, eeg.shape[0], None if self.mode == "graph" else eeg.device, "train_step")
+        gid = self._need_groups(ops.group_ids(groups, eeg.shape[0], None if self.mode == "graph" else eeg.device, "train_step"),
+                                "train_step")
         lab = self._labels(labels, eeg.shape[0], None if self.mode == "graph" else eeg.device, "train_step")
         if self._bank_size:
             self._bank_prepare(eeg.shape[0], gid is not None, "train_step")
@@ -627,6 +652,10 @@ class BridgeTrainer(TrainerCheckpointMixin, TrainerStagingMixin, nn.Module):
         A bank trainer's training step (``training``; everything else keeps the in-batch loss) scores against the bank
         (`ClipBankLossFn`: the bank is a constant of the tape), then pushes its own rows - detached: nothing of it is on
         the tape.  ``keys``: a key trainer's key rows (`_encode_with_keys`) - the batch's keys and what is pushed"""
+        if self.neighbour_radius:                      # (no bank: refused at construction)
+            if self.loss == "sigmoid":
+                return ops.sigmoid_loss(ze, zf, self.head.logit_scale, self.head.logit_bias, self.group, gid, self.neighbour_radius)
+            return ops.clip_loss(ze, zf, self.head.logit_scale, self.group, gid, self.neighbour_radius)
         if self.loss == "sigmoid":
             return ops.sigmoid_loss(ze, zf, self.head.logit_scale, self.head.logit_bias, self.group, gid)
         if not (training and self._bank_size):
@@ -740,10 +769,18 @@ class BridgeTrainer(TrainerCheckpointMixin, TrainerStagingMixin, nn.Module):
         ``gid_all``: the gathered int32 group ids -> the grouped loss (``mm_clip_loss_own_rows_grouped``).
         ``loss="sigmoid"``: the pairwise sigmoid loss on the same inputs (``mm_sigmoid_loss_own_rows``), ``scal`` 5 floats.
         ``bank_size > 0``: the loss against the batch and the valid bank rows (``mm_clip_bank_loss``), then the push of the
-        step's rows (``mm_clip_bank_push``) behind it on the same stream."""
+        step's rows (``mm_clip_bank_push``) behind it on the same stream.
+        ``neighbour_radius > 0``: the masked form of either loss (``mm_clip_loss_own_rows_masked``,
+        ``mm_sigmoid_loss_own_rows_masked``) in place of the grouped launch."""
         ls = self.head.logit_scale.detach().reshape(1)
         B, row0 = dz.shape[0], dp.rank(self.group) * dz.shape[0]
-        if self.loss == "sigmoid":
+        if self.neighbour_radius:                      # (no bank: refused at construction)
+            if self.loss == "sigmoid":
+                ops.sigmoid_loss_own_rows(z_all, gid_all, ls, self.head.logit_bias.detach().reshape(1), scal, dz, B, row0,
+                                          self.neighbour_radius)
+            else:
+                ops.clip_loss_own_rows(z_all, gid_all, ls, scal, dz, B, row0, self.neighbour_radius)
+        elif self.loss == "sigmoid":
             ops.sigmoid_loss_own_rows(z_all, gid_all, ls, self.head.logit_bias.detach().reshape(1), scal, dz, B, row0)
         elif self._key_encoder:                        # the keys of the batch and the rows pushed are the key encoder's
             ops.clip_key_loss(z_all, self._key_rows, gid_all, self._bank, ls, scal, dz, self._bank_warmup)
@@ -1222,7 +1259,7 @@ class BridgeTrainer(TrainerCheckpointMixin, TrainerStagingMixin, nn.Module):
             if lab is None:
                 loss, acc_e, acc_f = self.forward(eeg, fmri, groups)
                 return {"loss": loss, "top1_e2f": acc_e, "top1_f2e": acc_f}
-            gid = ops.group_ids(groups, eeg.shape[0], eeg.device, "evaluate")
+            gid = self._need_groups(ops.group_ids(groups, eeg.shape[0], eeg.device, "evaluate"), "evaluate")
             br = self.head.bridge
             fe, ff = self._encode(eeg, fmri)
             z, sv_h = ops.contrastive_embed_impl(br, fe, ff, False)

@@ -97,16 +97,48 @@ class EEGfMRIContrastiveBridge(nn.Module):
         """L2-normalised (ze, zf), each (B, bridge_dim) fp32."""
         return ops.contrastive_embed(self.bridge, eeg_feats, fmri_feats, self.training)
 
-    def forward(self, eeg_feats, fmri_feats, group=None, groups=None):
+    def forward(self, eeg_feats, fmri_feats, group=None, groups=None, radius: int = 0):
         """-> (loss, top1_eeg_to_fmri, top1_fmri_to_eeg).  With a process
         ``group`` the columns are the all-gathered global batch.  ``groups``:
         (B,) integer ids (e.g. subjects); pairs with equal ids are positives of
-        each other (ops.clip_loss / ops.sigmoid_loss)."""
+        each other (ops.clip_loss / ops.sigmoid_loss).  ``radius`` > 0: the ids
+        are timeline positions (`timeline_ids`) and pairs within ``radius`` of
+        each other are ignored, neither positives nor negatives."""
         gid = ops.group_ids(groups, eeg_feats.shape[0], eeg_feats.device, "EEGfMRIContrastiveBridge")
         ze, zf = self.embed(eeg_feats, fmri_feats)
         if self.loss == "sigmoid":
-            return ops.sigmoid_loss(ze, zf, self.logit_scale, self.logit_bias, group, gid)
-        return ops.clip_loss(ze, zf, self.logit_scale, group, gid)
+            return ops.sigmoid_loss(ze, zf, self.logit_scale, self.logit_bias, group, gid, radius)
+        return ops.clip_loss(ze, zf, self.logit_scale, group, gid, radius)
+
+
+def timeline_ids(runs, times, radius: int) -> torch.Tensor:
+    """int32 ids for the ``groups=`` of a loss with ignored temporal neighbours (``radius``; ops.clip_loss,
+    BridgeTrainer(neighbour_radius=)): ``runs`` (B,) integer run / recording labels, ``times`` (B,) integer positions of
+    the pairs within their run (epoch or TR index).  id = run_index * stride + (t - t_min) with run_index the rank of
+    the run label among the distinct labels and stride = (t_max - t_min) + radius + 1: rows of different runs are never
+    within ``radius`` of each other, rows of one run keep their distances, equal (run, t) stay positives of each other.
+    Only differences between the ids of one (gathered) batch matter; build the ids once for the whole dataset and index
+    them per batch, so that every rank of a process group measures on the same timeline.  ``ValueError`` if the ids do
+    not fit in int32."""
+    radius = int(radius)
+    if radius < 0:
+        raise ValueError(f"timeline_ids: radius must be >= 0 (got {radius})")
+    runs, times = torch.as_tensor(runs), torch.as_tensor(times)
+    for name, t in (("runs", runs), ("times", times)):
+        if t.dim() != 1 or t.dtype.is_floating_point or t.dtype.is_complex or t.dtype == torch.bool:
+            raise ValueError(f"timeline_ids: {name} must be a 1-D integer tensor (got {tuple(t.shape)}, {t.dtype})")
+    if runs.shape != times.shape:
+        raise ValueError(f"timeline_ids: {runs.shape[0]} runs but {times.shape[0]} times")
+    if runs.numel() == 0:
+        return torch.empty(0, dtype=torch.int32, device=times.device)
+    run_index = torch.unique(runs.cpu(), return_inverse=True)[1].long()
+    t = times.cpu().long()
+    span = int(t.max() - t.min())
+    stride = span + radius + 1
+    if int(run_index.max()) * stride + span > 2 ** 31 - 1:
+        raise ValueError(f"timeline_ids: {int(run_index.max()) + 1} runs of span {span} with radius {radius} need ids up to "
+                         f"{int(run_index.max()) * stride + span}: they do not fit in int32")
+    return (run_index * stride + (t - t.min())).to(torch.int32).to(times.device)
 
 
 def rank_summary(ranks: torch.Tensor, ks=(1, 5, 10)) -> dict:

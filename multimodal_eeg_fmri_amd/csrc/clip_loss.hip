@@ -1,7 +1,8 @@
 // The fused batch-pairwise cosine-similarity / symmetric InfoNCE loss of the contrastive bridge with its gradients, for
-// plain and for subject-grouped positives: one kernel pair, four entry points; and the pairwise sigmoid (SigLIP) loss on
-// the same inputs and helpers: two kernels, two entry points.  Callers: ops.clip_loss_own_rows*, ops.clip_loss*_ws_floats,
-// ops.sigmoid_loss_own_rows and ops.sigmoid_loss_ws_floats (bridge_trainer.py's step, autograd.py's tape).
+// plain, for subject-grouped positives and for grouped positives with ignored temporal neighbours (MASKED): one kernel pair,
+// six entry points; and the pairwise sigmoid (SigLIP) loss on the same inputs and helpers in the same three modes: two
+// kernels, four entry points.  Callers: ops.clip_loss_own_rows*, ops.clip_loss*_ws_floats, ops.sigmoid_loss_own_rows and
+// ops.sigmoid_loss_ws_floats (bridge_trainer.py's step, autograd.py's tape).
 #include "common.h"
 
 namespace {
@@ -33,7 +34,32 @@ namespace {
 // With all-distinct ids every positive-set LSE is s C[r][r] + log 1 and the result is the ungrouped one (in exact
 // arithmetic: the ungrouped instantiation keeps its own formulas).  gid is the LAST kernel argument: the ungrouped
 // instantiation never reads it (null there), and its other arguments keep their offsets.
+//
+// MASKED: the ids are positions on a timeline and a third relation joins positive and negative.  With the radius R >= 0 and
+// d = |gid_j - gid_r| (as an unsigned difference: INT_MIN and INT_MAX are 2^32 - 1 apart, see clip_id_dist):
+//   d == 0 positive (P(r), as GROUPED)      0 < d <= R ignored      d > R negative      A(r) = {j : d == 0 or d > R}
+//   l_row(r) = LSE_{j in A(r)}(s C[r][j]) - LSE_{j in P(r)}(s C[r][j]),  l_col(r) the same over column r
+//   dL/dC[r][j] = 0.5/B * s * ([j in A(r)] (P_row + P_col) - [d == 0] (Q_row + Q_col))[r][j]
+// P_row / P_col normalised over the admitted sets (the relation is symmetric: j in A(r) <=> r in A(j), so P_col[r][j] is
+// only ever formed for a member of column j's sum).  An ignored key takes no part in any maximum, sum or top-1 test and its
+// coefficient is stored as 0.f, not computed.  ws[11][Bg]: the eight rows of GROUPED with the admitted-set maximum / LSE in
+// place of the all-keys one + one flag per row, 1.f when the row admits no negative (A = P; the relation is symmetric, so
+// the flag serves row and column, and every member of P(r) carries it too) + l_row and l_col of every row.  A flagged
+// row's loss, d / d logit_scale and every coefficient are STORED as 0.f: LSE_A - LSE_P evaluated in fp32 is only 0 to
+// rounding (the compiler contracts s C - LSE into an FMA at some uses and not at others), the
+// contract asks for exactly 0.  The same cancellation is kept out of a trained row's positives and of d / d logit_scale
+// (see the two comments in the kernels): ignoring the near neighbours leaves rows whose admitted negatives are all far.
+// The radius follows gid as the last kernel argument (unread in the other two modes).
 // ---------------------------------------------------------------------------
+enum { CLIP_PLAIN = 0, CLIP_GROUPED = 1, CLIP_MASKED = 2 };
+// |a - b| of two int32 ids in [0, 2^32): the unsigned difference of the larger and the smaller cannot wrap
+__device__ __forceinline__ unsigned clip_id_dist(int a, int b) {
+    return a >= b ? (unsigned)a - (unsigned)b : (unsigned)b - (unsigned)a;
+}
+__device__ __forceinline__ bool clip_ignored(int a, int b, int radius) {
+    const unsigned d = clip_id_dist(a, b);
+    return d != 0u && d <= (unsigned)radius;
+}
 struct ClipShared {
     float *qe, *qf, *cr, *cc, *red;
 };
@@ -117,9 +143,11 @@ __device__ __forceinline__ void clip_dz_row(const float* __restrict__ z_all, con
     }
 }
 
-template <bool GROUPED>
+template <int MODE>
 __global__ __launch_bounds__(256) void clip_lse_kernel(const float* __restrict__ z_all, const float* __restrict__ logit_scale,
-                                                       float* __restrict__ ws, int Bg, int N, const int* __restrict__ gid) {
+                                                       float* __restrict__ ws, int Bg, int N, const int* __restrict__ gid,
+                                                       int radius) {
+    constexpr bool GROUPED = MODE != CLIP_PLAIN, MASKED = MODE == CLIP_MASKED;
     extern __shared__ float sm[];
     const ClipShared sh = clip_shared(sm, N, Bg);
     const int r = blockIdx.x, tid = threadIdx.x;
@@ -129,14 +157,32 @@ __global__ __launch_bounds__(256) void clip_lse_kernel(const float* __restrict__
     float mxr, mxc;
     clip_cosines(z_all, r, Bg, N, sh, mxr, mxc);
     float pmr = -INFINITY, pmc = -INFINITY;                  // maxima over the positive set (the top-1 test and the stable LSE)
-    if constexpr (GROUPED) {
+    bool no_negative = false;                                // MASKED: A(r) = P(r)
+    if constexpr (MASKED) {                                  // and over the admitted set, in place of those over all keys
+        mxr = -INFINITY; mxc = -INFINITY;
+        float negative = 0.f, none = 0.f;                    // (a flag through the maximum the file already has)
+        for (int j = tid; j < Bg; j += 256) {
+            const int gj = gid[j];
+            if (clip_ignored(gj, gr, radius)) continue;
+            mxr = fmaxf(mxr, sh.cr[j]); mxc = fmaxf(mxc, sh.cc[j]);
+            if (gj == gr) { pmr = fmaxf(pmr, sh.cr[j]); pmc = fmaxf(pmc, sh.cc[j]); }
+            else negative = 1.f;
+        }
+        clip_max2(negative, none, sh.red);
+        no_negative = negative == 0.f;
+        clip_max2(mxr, mxc, sh.red);
+        clip_max2(pmr, pmc, sh.red);
+    } else if constexpr (GROUPED) {
         for (int j = tid; j < Bg; j += 256)
             if (gid[j] == gr) { pmr = fmaxf(pmr, sh.cr[j]); pmc = fmaxf(pmc, sh.cc[j]); }
         clip_max2(pmr, pmc, sh.red);
     }
-    float se = 0.f, sf = 0.f, ee = 0.f, ef = 0.f;           // all columns: sum exp, sum exp * cos
+    float se = 0.f, sf = 0.f, ee = 0.f, ef = 0.f;           // all (MASKED: admitted) columns: sum exp, sum exp * cos
     float qe = 0.f, qf = 0.f, qee = 0.f, qef = 0.f;         // the positive set
     for (int j = tid; j < Bg; j += 256) {
+        if constexpr (MASKED) {
+            if (clip_ignored(gid[j], gr, radius)) continue;
+        }
         const float a = sh.cr[j], c = sh.cc[j];
         const float pa = __expf(s * (a - mxr)), pc = __expf(s * (c - mxc));
         se += pa; sf += pc; ee += pa * a; ef += pc * c;
@@ -153,6 +199,19 @@ __global__ __launch_bounds__(256) void clip_lse_kernel(const float* __restrict__
         clip_sum2(qe, qf, sh.red);
         clip_sum2(qee, qef, sh.red);
     }
+    // MASKED: E_A[cos] - E_P[cos] = sum over the admitted NEGATIVES of P_j (cos_j - E_P[cos]) (the positives' terms cancel
+    // exactly): small terms summed, not the difference of two means near 1, whose rounding times s exceeds a trained loss
+    float ne = 0.f, nf = 0.f;
+    if constexpr (MASKED) {
+        const float mu_r = qee / qe, mu_c = qef / qf;
+        for (int j = tid; j < Bg; j += 256) {
+            const int gj = gid[j];
+            if (gj == gr || clip_ignored(gj, gr, radius)) continue;
+            const float a = sh.cr[j], c = sh.cc[j];
+            ne += __expf(s * (a - mxr)) * (a - mu_r); nf += __expf(s * (c - mxc)) * (c - mu_c);
+        }
+        clip_sum2(ne, nf, sh.red);
+    }
     if (tid == 0) {
         // the row's loss = LSE - LSE_P as s (max - max_P) + (log sum - log sum_P), ungrouped s (max - diag) + log sum: never
         // the difference of two numbers near s, whose rounding (4e-6 at s = 100) is the size of a trained model's loss
@@ -164,9 +223,16 @@ __global__ __launch_bounds__(256) void clip_lse_kernel(const float* __restrict__
             ws[2 * Bg + r] = 0.5f * ((s * (mxr - pmr) + (lg_r - lq_r)) + (s * (mxc - pmc) + (lg_c - lq_c)));
             ws[3 * Bg + r] = pmr >= mxr ? 1.f : 0.f;         // the best positive reaches the row maximum (a tie counts FOR it)
             ws[4 * Bg + r] = pmc >= mxc ? 1.f : 0.f;
-            ws[5 * Bg + r] = s * 0.5f * ((ee / se - qee / qe) + (ef / sf - qef / qf));
+            if constexpr (MASKED) ws[5 * Bg + r] = no_negative ? 0.f : s * 0.5f * (ne / se + nf / sf);
+            else ws[5 * Bg + r] = s * 0.5f * ((ee / se - qee / qe) + (ef / sf - qef / qf));
             ws[6 * Bg + r] = lsp_r;
             ws[7 * Bg + r] = lsp_c;
+            if constexpr (MASKED) {
+                ws[8 * Bg + r] = no_negative ? 1.f : 0.f;
+                if (no_negative) ws[2 * Bg + r] = 0.f;
+                ws[9 * Bg + r] = s * (mxr - pmr) + (lg_r - lq_r);       // l_row(r), l_col(r): LSE_A - LSE_P without cancellation
+                ws[10 * Bg + r] = s * (mxc - pmc) + (lg_c - lq_c);
+            }
         } else {
             const float diag = sh.cr[r];
             const float lg_r = __logf(se), lg_c = __logf(sf);
@@ -183,11 +249,12 @@ __global__ __launch_bounds__(256) void clip_lse_kernel(const float* __restrict__
     }
 }
 
-template <bool GROUPED>
+template <int MODE>
 __global__ __launch_bounds__(256) void clip_rows_kernel(const float* __restrict__ z_all, const float* __restrict__ logit_scale,
                                                         const float* __restrict__ ws, float* __restrict__ scal,
                                                         float* __restrict__ dz, int B, int Bg, int N, int row0,
-                                                        const int* __restrict__ gid) {
+                                                        const int* __restrict__ gid, int radius) {
+    constexpr bool GROUPED = MODE != CLIP_PLAIN, MASKED = MODE == CLIP_MASKED;
     extern __shared__ float sm[];
     const ClipShared sh = clip_shared(sm, N, Bg);
     const int i = blockIdx.x, gi = row0 + i, tid = threadIdx.x, LD = 2 * N;
@@ -214,16 +281,34 @@ __global__ __launch_bounds__(256) void clip_rows_kernel(const float* __restrict_
     int gg = 0;
     if constexpr (GROUPED) { lsp_rg = ws[6 * Bg + gi]; lsp_cg = ws[7 * Bg + gi]; gg = gid[gi]; }
     const float k = 0.5f * invB * s;
+    bool no_negative = false;
+    float l_rg = 0.f, l_cg = 0.f;
+    if constexpr (MASKED) {
+        no_negative = ws[8 * Bg + gi] != 0.f;                            // A(gi) = P(gi): uniform over the workgroup
+        l_rg = ws[9 * Bg + gi]; l_cg = ws[10 * Bg + gi];
+    }
     for (int j = tid; j < Bg; j += 256) {
+        if constexpr (MASKED) {                                          // an ignored pair: exactly no gradient, either way;
+            if (no_negative || clip_ignored(gid[j], gg, radius)) { sh.cr[j] = 0.f; sh.cc[j] = 0.f; continue; }   // A = P: P - Q = 0
+            if (gid[j] == gg) {
+                // a positive key: P - Q = Q (exp(-(LSE_A - LSE_P)) - 1) = Q expm1(-l) with l from the lse kernel's split form,
+                // not exp(a - LSE_A) - exp(a - LSE_P): two numbers near 1 whose roundings (ulp(s) each) are a trained row's gradient
+                const float a = s * sh.cr[j], c = s * sh.cc[j];
+                const float ga = __expf(a - lsp_rg) * expm1f(-l_rg) + __expf(a - ws[7 * Bg + j]) * expm1f(-ws[10 * Bg + j]);
+                const float gc = __expf(c - ws[6 * Bg + j]) * expm1f(-ws[9 * Bg + j]) + __expf(c - lsp_cg) * expm1f(-l_cg);
+                sh.cr[j] = k * ga; sh.cc[j] = k * gc;
+                continue;
+            }
+        }
         const float a = s * sh.cr[j], c = s * sh.cc[j];
         float ga = __expf(a - lse_rg) + __expf(a - ws[Bg + j]);          // P_row[gi][j] + P_col[gi][j]
         float gc = __expf(c - ws[j]) + __expf(c - lse_cg);               // P_row[j][gi] + P_col[j][gi]
-        if constexpr (GROUPED) {
+        if constexpr (GROUPED && !MASKED) {
             if (gid[j] == gg) {
                 ga -= __expf(a - lsp_rg) + __expf(a - ws[7 * Bg + j]);   // Q_row[gi][j] + Q_col[gi][j]
                 gc -= __expf(c - ws[6 * Bg + j]) + __expf(c - lsp_cg);   // Q_row[j][gi] + Q_col[j][gi]
             }
-        } else {
+        } else if constexpr (!GROUPED) {
             if (j == gi) { ga -= 2.f; gc -= 2.f; }
         }
         sh.cr[j] = k * ga; sh.cc[j] = k * gc;
@@ -245,6 +330,8 @@ __global__ __launch_bounds__(256) void clip_rows_kernel(const float* __restrict_
 //   last-arriving workgroup: stream order is the only ordering the result then depends on.
 // softplus(x) = max(x, 0) + log1p(exp(-|x|)) and sigmoid(x) from the same exp(-|x|); expf / log1pf, not the fast forms:
 // well-separated pairs have losses of 1e-7 each, which log(1 + e) would quantise to multiples of 2^-24.
+// MASKED (relations as for InfoNCE above): an ignored pair has l = 0 and G = 0, stored, not computed, and takes no part in
+// the maximum of the top-1 test; everything else, the 1/B included, as GROUPED.
 // ---------------------------------------------------------------------------
 __device__ __forceinline__ void sigmoid_pair(float u, bool pos, float& l, float& dl_du) {
     const float x = pos ? -u : u;                             // -y u
@@ -254,11 +341,12 @@ __device__ __forceinline__ void sigmoid_pair(float u, bool pos, float& l, float&
     dl_du = pos ? -sg : sg;                                   // -y sigmoid(-y u)
 }
 
-template <bool GROUPED>
+template <int MODE>
 __global__ __launch_bounds__(256) void sigmoid_rows_kernel(const float* __restrict__ z_all, const float* __restrict__ logit_scale,
                                                            const float* __restrict__ logit_bias, float* __restrict__ ws,
                                                            float* __restrict__ dz, int B, int Bg, int N, int row0,
-                                                           const int* __restrict__ gid) {
+                                                           const int* __restrict__ gid, int radius) {
+    constexpr bool GROUPED = MODE != CLIP_PLAIN, MASKED = MODE == CLIP_MASKED;
     extern __shared__ float sm[];
     const ClipShared sh = clip_shared(sm, N, Bg);
     const int i = blockIdx.x, gi = row0 + i, tid = threadIdx.x;
@@ -269,7 +357,17 @@ __global__ __launch_bounds__(256) void sigmoid_rows_kernel(const float* __restri
     float mxr, mxc;
     clip_cosines(z_all, gi, Bg, N, sh, mxr, mxc);
     float pmr = -INFINITY, pmc = -INFINITY;                  // maxima over the positive set (the top-1 test, as for InfoNCE)
-    if constexpr (GROUPED) {
+    if constexpr (MASKED) {                                  // and over the admitted set, in place of those over all keys
+        mxr = -INFINITY; mxc = -INFINITY;
+        for (int j = tid; j < Bg; j += 256) {
+            const int gj = gid[j];
+            if (clip_ignored(gj, gg, radius)) continue;
+            mxr = fmaxf(mxr, sh.cr[j]); mxc = fmaxf(mxc, sh.cc[j]);
+            if (gj == gg) { pmr = fmaxf(pmr, sh.cr[j]); pmc = fmaxf(pmc, sh.cc[j]); }
+        }
+        clip_max2(mxr, mxc, sh.red);
+        clip_max2(pmr, pmc, sh.red);
+    } else if constexpr (GROUPED) {
         for (int j = tid; j < Bg; j += 256)
             if (gid[j] == gg) { pmr = fmaxf(pmr, sh.cr[j]); pmc = fmaxf(pmc, sh.cc[j]); }
         clip_max2(pmr, pmc, sh.red);
@@ -279,6 +377,12 @@ __global__ __launch_bounds__(256) void sigmoid_rows_kernel(const float* __restri
     }
     float loss = 0.f, ds = 0.f, db = 0.f, none = 0.f;
     for (int j = tid; j < Bg; j += 256) {
+        if constexpr (MASKED) {                              // an ignored pair: no loss, exactly no gradient, either way
+            if (clip_ignored(gid[j], gg, radius)) {
+                if (dz) { sh.cr[j] = 0.f; sh.cc[j] = 0.f; }
+                continue;
+            }
+        }
         const float a = sh.cr[j], c = sh.cc[j];
         bool pos;
         if constexpr (GROUPED) pos = gid[j] == gg; else pos = j == gi;
@@ -320,7 +424,7 @@ __global__ __launch_bounds__(64) void sigmoid_sum_kernel(const float* __restrict
 
 extern "C" {
 // floats-per-Bg rows of the loss workspace: the only place the count is written (layout: see clip_lse_kernel)
-static int clip_ws_rows(bool grouped) { return grouped ? 8 : 6; }
+static int clip_ws_rows(bool grouped, bool masked = false) { return masked ? 11 : grouped ? 8 : 6; }
 
 // the shape checks of every loss entry point of this file -> the launches' LDS bytes (ClipShared)
 static int clip_check_shape(const char* who, int B, int Bg, int N, int row0, size_t* lds) {
@@ -331,20 +435,21 @@ static int clip_check_shape(const char* who, int B, int Bg, int N, int row0, siz
     return 0;
 }
 
-// the checks and the two launches of both InfoNCE entry points; gid = nullptr: the ungrouped loss
+// the checks and the two launches of the three InfoNCE entry points; gid = nullptr: the ungrouped loss, radius < 0: no
+// ignore relation (the grouped loss), radius >= 0: the masked one
 static int clip_loss_launch(const char* who, const float* z_all, const int* gid, const float* logit_scale, float* scal4,
-                            float* dz_local, float* ws, int B, int Bg, int N, int row0, hipStream_t st) {
+                            float* dz_local, float* ws, int B, int Bg, int N, int row0, int radius, hipStream_t st) {
     size_t lds;
     int rc = clip_check_shape(who, B, Bg, N, row0, &lds);
     if (rc) return rc;
-    const auto lse = gid ? clip_lse_kernel<true> : clip_lse_kernel<false>;
-    const auto rows = gid ? clip_rows_kernel<true> : clip_rows_kernel<false>;
-    hipLaunchKernelGGL(lse, dim3(Bg), dim3(256), lds, st, z_all, logit_scale, ws, Bg, N, gid);
+    const auto lse = !gid ? clip_lse_kernel<CLIP_PLAIN> : radius < 0 ? clip_lse_kernel<CLIP_GROUPED> : clip_lse_kernel<CLIP_MASKED>;
+    const auto rows = !gid ? clip_rows_kernel<CLIP_PLAIN> : radius < 0 ? clip_rows_kernel<CLIP_GROUPED> : clip_rows_kernel<CLIP_MASKED>;
+    hipLaunchKernelGGL(lse, dim3(Bg), dim3(256), lds, st, z_all, logit_scale, ws, Bg, N, gid, radius);
     char what[64];
     snprintf(what, sizeof what, "%s(lse)", who);
     rc = mm_check_launch(what);
     if (rc) return rc;
-    hipLaunchKernelGGL(rows, dim3(B), dim3(256), lds, st, z_all, logit_scale, ws, scal4, dz_local, B, Bg, N, row0, gid);
+    hipLaunchKernelGGL(rows, dim3(B), dim3(256), lds, st, z_all, logit_scale, ws, scal4, dz_local, B, Bg, N, row0, gid, radius);
     snprintf(what, sizeof what, "%s(rows)", who);
     return mm_check_launch(what);
 }
@@ -358,7 +463,7 @@ int mm_clip_loss_ws_floats(int B, int Bg, int* floats_host, hipStream_t) {
 int mm_clip_loss_own_rows(const float* z_all, const float* logit_scale, float* scal4, float* dz_local, float* ws, int B,
                           int Bg, int N, int row0, hipStream_t st) {
     MM_REQUIRE(z_all && logit_scale && scal4 && ws, "clip_loss_own_rows: null");
-    return clip_loss_launch("clip_loss_own_rows", z_all, nullptr, logit_scale, scal4, dz_local, ws, B, Bg, N, row0, st);
+    return clip_loss_launch("clip_loss_own_rows", z_all, nullptr, logit_scale, scal4, dz_local, ws, B, Bg, N, row0, -1, st);
 }
 
 int mm_clip_loss_grouped_ws_floats(int B, int Bg, int* floats_host, hipStream_t) {
@@ -370,7 +475,20 @@ int mm_clip_loss_grouped_ws_floats(int B, int Bg, int* floats_host, hipStream_t)
 int mm_clip_loss_own_rows_grouped(const float* z_all, const int* gid_all, const float* logit_scale, float* scal4, float* dz_local,
                                   float* ws, int B, int Bg, int N, int row0, hipStream_t st) {
     MM_REQUIRE(z_all && gid_all && logit_scale && scal4 && ws, "clip_loss_own_rows_grouped: null");
-    return clip_loss_launch("clip_loss_own_rows_grouped", z_all, gid_all, logit_scale, scal4, dz_local, ws, B, Bg, N, row0, st);
+    return clip_loss_launch("clip_loss_own_rows_grouped", z_all, gid_all, logit_scale, scal4, dz_local, ws, B, Bg, N, row0, -1, st);
+}
+
+int mm_clip_loss_masked_ws_floats(int B, int Bg, int* floats_host, hipStream_t) {
+    MM_REQUIRE(floats_host && B > 0 && Bg >= B, "clip_loss_masked_ws_floats: bad args");
+    *floats_host = clip_ws_rows(true, true) * Bg;
+    return 0;
+}
+
+int mm_clip_loss_own_rows_masked(const float* z_all, const int* gid_all, const float* logit_scale, float* scal4, float* dz_local,
+                                 float* ws, int B, int Bg, int N, int row0, int radius, hipStream_t st) {
+    MM_REQUIRE(z_all && gid_all && logit_scale && scal4 && ws, "clip_loss_own_rows_masked: null");
+    MM_REQUIRE(radius >= 0, "clip_loss_own_rows_masked: radius=%d must be >= 0", radius);
+    return clip_loss_launch("clip_loss_own_rows_masked", z_all, gid_all, logit_scale, scal4, dz_local, ws, B, Bg, N, row0, radius, st);
 }
 
 int mm_sigmoid_loss_ws_floats(int B, int Bg, int* floats_host, hipStream_t) {
@@ -379,17 +497,43 @@ int mm_sigmoid_loss_ws_floats(int B, int Bg, int* floats_host, hipStream_t) {
     return 0;
 }
 
+// the shape checks and the two launches of both sigmoid entry points; gid / radius as for clip_loss_launch
+static int sigmoid_loss_launch(const char* who, const float* z_all, const int* gid, const float* logit_scale,
+                               const float* logit_bias, float* scal5, float* dz_local, float* ws, int B, int Bg, int N, int row0,
+                               int radius, hipStream_t st) {
+    size_t lds;
+    int rc = clip_check_shape(who, B, Bg, N, row0, &lds);
+    if (rc) return rc;
+    const auto rows = !gid ? sigmoid_rows_kernel<CLIP_PLAIN> : radius < 0 ? sigmoid_rows_kernel<CLIP_GROUPED> : sigmoid_rows_kernel<CLIP_MASKED>;
+    hipLaunchKernelGGL(rows, dim3(B), dim3(256), lds, st, z_all, logit_scale, logit_bias, ws, dz_local, B, Bg, N, row0, gid, radius);
+    char what[64];
+    snprintf(what, sizeof what, "%s(rows)", who);
+    rc = mm_check_launch(what);
+    if (rc) return rc;
+    hipLaunchKernelGGL(sigmoid_sum_kernel, dim3(1), dim3(64), 0, st, ws, scal5, B);
+    snprintf(what, sizeof what, "%s(sum)", who);
+    return mm_check_launch(what);
+}
+
 int mm_sigmoid_loss_own_rows(const float* z_all, const int* gid_all, const float* logit_scale, const float* logit_bias,
                              float* scal5, float* dz_local, float* ws, int B, int Bg, int N, int row0, hipStream_t st) {
     MM_REQUIRE(z_all && logit_scale && logit_bias && scal5 && ws, "sigmoid_loss_own_rows: null");
-    size_t lds;
-    int rc = clip_check_shape("sigmoid_loss_own_rows", B, Bg, N, row0, &lds);
-    if (rc) return rc;
-    const auto rows = gid_all ? sigmoid_rows_kernel<true> : sigmoid_rows_kernel<false>;
-    hipLaunchKernelGGL(rows, dim3(B), dim3(256), lds, st, z_all, logit_scale, logit_bias, ws, dz_local, B, Bg, N, row0, gid_all);
-    rc = mm_check_launch("sigmoid_loss_own_rows(rows)");
-    if (rc) return rc;
-    hipLaunchKernelGGL(sigmoid_sum_kernel, dim3(1), dim3(64), 0, st, ws, scal5, B);
-    return mm_check_launch("sigmoid_loss_own_rows(sum)");
+    return sigmoid_loss_launch("sigmoid_loss_own_rows", z_all, gid_all, logit_scale, logit_bias, scal5, dz_local, ws, B, Bg, N,
+                               row0, -1, st);
+}
+
+int mm_sigmoid_loss_masked_ws_floats(int B, int Bg, int* floats_host, hipStream_t) {
+    MM_REQUIRE(floats_host && B > 0 && Bg >= B, "sigmoid_loss_masked_ws_floats: bad args");
+    *floats_host = 5 * B;                                    // the layout of mm_sigmoid_loss_ws_floats
+    return 0;
+}
+
+int mm_sigmoid_loss_own_rows_masked(const float* z_all, const int* gid_all, const float* logit_scale, const float* logit_bias,
+                                    float* scal5, float* dz_local, float* ws, int B, int Bg, int N, int row0, int radius,
+                                    hipStream_t st) {
+    MM_REQUIRE(z_all && gid_all && logit_scale && logit_bias && scal5 && ws, "sigmoid_loss_own_rows_masked: null");
+    MM_REQUIRE(radius >= 0, "sigmoid_loss_own_rows_masked: radius=%d must be >= 0", radius);
+    return sigmoid_loss_launch("sigmoid_loss_own_rows_masked", z_all, gid_all, logit_scale, logit_bias, scal5, dz_local, ws, B,
+                               Bg, N, row0, radius, st);
 }
 }  // extern "C"

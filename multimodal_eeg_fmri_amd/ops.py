@@ -635,10 +635,30 @@ def clip_loss_grouped_ws_floats(B: int, Bg: int) -> int:
     return clip_loss_ws_floats(B, Bg, grouped=True)
 
 
-def clip_loss_own_rows(z_all, gid_all, logit_scale1, scal, dz, B: int, row0: int):
+def clip_loss_masked_ws_floats(B: int, Bg: int) -> int:
+    """floats of the scratch of mm_clip_loss_own_rows_masked for B own rows of a Bg-row gathered batch"""
+    return _hip.host_int("mm_clip_loss_masked_ws_floats", B, Bg)
+
+
+def _loss_radius(radius, gid_all, who: str) -> int:
+    """``radius`` of the loss entry points as an int >= 0; a radius > 0 needs ids: ``ValueError`` otherwise"""
+    radius = int(radius)
+    if radius < 0:
+        raise ValueError(f"{who}: radius must be >= 0 (got {radius})")
+    if radius > 0 and gid_all is None:
+        raise ValueError(f"{who}: radius={radius} needs group ids (groups=): the ids are the timeline positions")
+    return radius
+
+
+def clip_loss_own_rows(z_all, gid_all, logit_scale1, scal, dz, B: int, row0: int, radius: int = 0):
     """symmetric InfoNCE of rows [row0, row0 + B) of the gathered batch z_all (Bg, 2N) -> scal (4,), dz (B, 2N) or None;
-    gid_all (Bg,) int32 group ids: the grouped loss, None: pair i is its own positive.  Allocates the workspace."""
+    gid_all (Bg,) int32 group ids: the grouped loss, None: pair i is its own positive.  ``radius`` > 0: keys whose id is
+    within ``radius`` of the query's (and not equal) are ignored (mm_clip_loss_own_rows_masked).  Allocates the workspace."""
     Bg, N2 = z_all.shape
+    if _loss_radius(radius, gid_all, "clip_loss_own_rows"):
+        ws = _empty((clip_loss_masked_ws_floats(B, Bg),), _F32, z_all)
+        _hip.call("mm_clip_loss_own_rows_masked", z_all, gid_all, logit_scale1, scal, dz, ws, B, Bg, N2 // 2, row0, int(radius))
+        return
     ws = _empty((clip_loss_ws_floats(B, Bg, gid_all is not None),), _F32, z_all)
     if gid_all is None:
         _hip.call("mm_clip_loss_own_rows", z_all, logit_scale1, scal, dz, ws, B, Bg, N2 // 2, row0)
@@ -651,10 +671,21 @@ def sigmoid_loss_ws_floats(B: int, Bg: int) -> int:
     return _hip.host_int("mm_sigmoid_loss_ws_floats", B, Bg)
 
 
-def sigmoid_loss_own_rows(z_all, gid_all, logit_scale1, logit_bias1, scal, dz, B: int, row0: int):
+def sigmoid_loss_masked_ws_floats(B: int, Bg: int) -> int:
+    """floats of the scratch of mm_sigmoid_loss_own_rows_masked for B own rows of a Bg-row gathered batch"""
+    return _hip.host_int("mm_sigmoid_loss_masked_ws_floats", B, Bg)
+
+
+def sigmoid_loss_own_rows(z_all, gid_all, logit_scale1, logit_bias1, scal, dz, B: int, row0: int, radius: int = 0):
     """pairwise sigmoid loss of rows [row0, row0 + B) of the gathered batch z_all (Bg, 2N) -> scal (5,), dz (B, 2N) or None;
-    gid_all (Bg,) int32 group ids: pairs with equal ids are positives, None: pair i only.  Allocates the workspace."""
+    gid_all (Bg,) int32 group ids: pairs with equal ids are positives, None: pair i only.  ``radius`` > 0: pairs whose ids
+    differ by at most ``radius`` are ignored (mm_sigmoid_loss_own_rows_masked).  Allocates the workspace."""
     Bg, N2 = z_all.shape
+    if _loss_radius(radius, gid_all, "sigmoid_loss_own_rows"):
+        ws = _empty((sigmoid_loss_masked_ws_floats(B, Bg),), _F32, z_all)
+        _hip.call("mm_sigmoid_loss_own_rows_masked", z_all, gid_all, logit_scale1, logit_bias1, scal, dz, ws, B, Bg, N2 // 2,
+                  row0, int(radius))
+        return
     ws = _empty((sigmoid_loss_ws_floats(B, Bg),), _F32, z_all)
     _hip.call("mm_sigmoid_loss_own_rows", z_all, gid_all, logit_scale1, logit_bias1, scal, dz, ws, B, Bg, N2 // 2, row0)
 
@@ -2049,14 +2080,17 @@ def contrastive_embed(bridge, eeg, fmri, training):
     return z[:, :N], z[:, N:]
 
 
-def clip_loss(ze, zf, logit_scale, group=None, groups=None):
+def clip_loss(ze, zf, logit_scale, group=None, groups=None, radius: int = 0):
     """symmetric InfoNCE over the (all-gathered) batch -> (loss, top1 e->f, top1 f->e).  ``groups`` (B,) integer ids
     (``group_ids``): pairs with equal ids are positives of each other (mm_clip_loss_own_rows_grouped); None: pair i is
-    the only positive of query i."""
+    the only positive of query i.  ``radius`` > 0 (needs ``groups``): the ids are timeline positions
+    (`bridge_utils.timeline_ids`) and a key within ``radius`` of the query, not equal to it, is ignored: neither positive
+    nor negative, no gradient (mm_clip_loss_own_rows_masked)."""
     _need_gpu(ze)
     gid = group_ids(groups, ze.shape[0], ze.device, "clip_loss")
+    radius = _loss_radius(radius, gid, "clip_loss")
     from .autograd import ClipLossFn
-    return ClipLossFn.apply(_packed_pair(ze, zf), logit_scale, group, gid)
+    return ClipLossFn.apply(_packed_pair(ze, zf), logit_scale, group, gid, radius)
 
 
 def clip_loss_bank(ze, zf, logit_scale, bank: ClipBank, groups=None, warmup: int = 0):
@@ -2078,13 +2112,15 @@ def clip_loss_key(ze, zf, keys, logit_scale, bank: ClipBank, groups=None, warmup
     return ClipKeyLossFn.apply(_packed_pair(ze, zf), keys, logit_scale, bank, gid, warmup)
 
 
-def sigmoid_loss(ze, zf, logit_scale, logit_bias, group=None, groups=None):
+def sigmoid_loss(ze, zf, logit_scale, logit_bias, group=None, groups=None, radius: int = 0):
     """pairwise sigmoid loss over the (all-gathered) batch (mm_sigmoid_loss_own_rows) -> (loss, top1 e->f, top1 f->e).
-    ``groups`` as in `clip_loss`: pairs with equal ids are positives of each other."""
+    ``groups`` as in `clip_loss`: pairs with equal ids are positives of each other; ``radius`` as there: pairs within it
+    are ignored (mm_sigmoid_loss_own_rows_masked)."""
     _need_gpu(ze)
     gid = group_ids(groups, ze.shape[0], ze.device, "sigmoid_loss")
+    radius = _loss_radius(radius, gid, "sigmoid_loss")
     from .autograd import SigmoidLossFn
-    return SigmoidLossFn.apply(_packed_pair(ze, zf), logit_scale, logit_bias, group, gid)
+    return SigmoidLossFn.apply(_packed_pair(ze, zf), logit_scale, logit_bias, group, gid, radius)
 
 
 def _packed_pair(ze: torch.Tensor, zf: torch.Tensor) -> torch.Tensor:

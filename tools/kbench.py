@@ -458,6 +458,36 @@ def groups_case(step_iters=30):
     print(f"C2 graph step B=32: ungrouped {tu:7.1f} us  grouped {tg:7.1f} us  ({100 * (tg / tu - 1):+.2f} %)")
 
 
+def neighbours_case(rounds=5):
+    """ignored temporal neighbours: the masked launches against the same build's grouped launches of both losses at the C2
+    loss shape (B = Bg = 32, N = 128) and at Bg = 256, graph-replayed in the same run, medians of interleaved rounds.
+    Timeline ids (a shuffled 0 .. Bg - 1), radius 2: 2 to 4 ignored keys per row; the grouped launches get the same ids"""
+    for B, Bg, N in ((32, 32, 128), (32, 256, 128)):
+        z = torch.nn.functional.normalize(torch.randn(Bg, 2 * N, device="cuda"), dim=1).contiguous()
+        gid = torch.randperm(Bg, device="cuda").to(torch.int32).contiguous()
+        ls = torch.full((1,), math.log(1 / 0.07), device="cuda")
+        lsig, lb = torch.full((1,), math.log(10.0), device="cuda"), torch.full((1,), -10.0, device="cuda")
+        scal, dz = torch.empty(5, device="cuda"), torch.empty(B, 2 * N, device="cuda")
+        ws_g = torch.empty(ops.clip_loss_ws_floats(B, Bg, grouped=True), device="cuda")
+        ws_m = torch.empty(ops.clip_loss_masked_ws_floats(B, Bg), device="cuda")
+        ws_s = torch.empty(ops.sigmoid_loss_ws_floats(B, Bg), device="cuda")
+        ws_t = torch.empty(ops.sigmoid_loss_masked_ws_floats(B, Bg), device="cuda")
+        cases = [
+            ("clip grouped", lambda: _hip.call("mm_clip_loss_own_rows_grouped", z, gid, ls, scal, dz, ws_g, B, Bg, N, 0)),
+            ("clip masked", lambda: _hip.call("mm_clip_loss_own_rows_masked", z, gid, ls, scal, dz, ws_m, B, Bg, N, 0, 2)),
+            ("sigmoid grouped", lambda: _hip.call("mm_sigmoid_loss_own_rows", z, gid, lsig, lb, scal, dz, ws_s, B, Bg, N, 0)),
+            ("sigmoid masked", lambda: _hip.call("mm_sigmoid_loss_own_rows_masked", z, gid, lsig, lb, scal, dz, ws_t, B, Bg, N, 0, 2))]
+        times = {name: [] for name, _ in cases}
+        for _ in range(rounds):
+            for name, fn in cases:
+                times[name].append(graph_time(fn))
+        for name, _ in cases:
+            print(f"neighbours B={B} Bg={Bg} N={N}: {name:16s} {_spread(times[name])}")
+        for kind in ("clip", "sigmoid"):
+            g, m = statistics.median(times[f"{kind} grouped"]), statistics.median(times[f"{kind} masked"])
+            print(f"neighbours B={B} Bg={Bg} N={N}: {kind} masked - grouped {m - g:+6.2f} us")
+
+
 def bank_case(B=32, N=128, step_iters=30, rounds=5):
     """the cross-batch negative bank: the loss section's launches, graph-replayed in the same run - the in-batch InfoNCE
     pair against mm_clip_bank_loss + mm_clip_bank_push on a full bank of K = 1024 and 4096 rows (and the loss's two
@@ -1430,6 +1460,9 @@ def main():
         return
     if flt == "bank":
         bank_case()
+        return
+    if flt == "neighbours":
+        neighbours_case()
         return
     if flt == "key":
         key_case()
