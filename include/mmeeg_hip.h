@@ -883,6 +883,30 @@ int mm_retrieval_ws_floats(int Nq, int Ng, int D, int k, int* floats_host, hipSt
 int mm_retrieval_grouped(const float* Q, const float* G, const int* qgid, const int* ggid, int* ranks, float* ws,
                          int Nq, int Ng, int D, hipStream_t stream);
 int mm_retrieval_grouped_ws_floats(int Nq, int Ng, int D, int* floats_host, hipStream_t stream);
+/* ranks and top-k with ignored temporal neighbours: the ids are positions on a timeline (bridge_utils.timeline_ids) and
+ * d(q, j) = |ggid[j] - qgid[q]|, the unsigned difference of the larger and the smaller id (ids -2^31 and 2^31 - 1 are
+ * 2^32 - 1 apart), as in mm_clip_loss_own_rows_masked.  radius >= 0.  d == 0: positive; 0 < d <= radius: IGNORED (neither a
+ * positive nor a negative; what the row holds - any finite value, NaN - changes nothing for that query); d > radius:
+ * negative; A(q) = {j : d == 0 or d > radius} is the admitted set.  s*(q) as mm_retrieval_grouped (same MFMA chain, NaN
+ * scores skipped).
+ * ranks (nullable when k > 0) int32 [Nq]: 1 + #{ j : d > radius, s(q, j) >= s*(q) }; a tie counts AGAINST the query; a
+ *        query without a positive, or with only NaN positive scores, ranks Ng.
+ * negatives (nullable) int32 [Nq]: #{ j : d > radius } - ids only, no score enters: the query's effective gallery minus
+ *        its positives.
+ * topk_idx / topk_score [Nq][k] (required when k > 0): the k best rows of A(q) - positives included, ignored rows never -
+ *        in mm_retrieval's order (score descending, then index ascending; NaN never selected; unfilled (-1, -inf)).
+ * radius = 0: ranks are mm_retrieval_grouped's and top-k is mm_retrieval's, bit for bit.
+ * ws = mm_retrieval_masked_ws_floats(Nq, Ng, D, k) = Nq (1 + S (2 + 2 k)) floats, no initialisation, S = the number of
+ * gallery slices: with QB = ceil(Nq / 128) and T = ceil(Ng / 128), W = max(1, min(T, ceil(512 / QB))), S = ceil(T /
+ * ceil(T / W)).  Layout: s* [Nq] | per-slice maxima, then counts [S][Nq] | per-slice id-only counts [S][Nq] (written only
+ * with negatives) | list scores [S][Nq][k] | list indices [S][Nq][k].  Shape limits, alignment and the int-overflow check
+ * as mm_retrieval; null Q, G, qgid, ggid or ws, radius < 0, and ranks == NULL with k == 0 are errors before any launch.
+ * At most four launches on `stream` (maxima sweep, best, counting / top-k sweep, finish; two with ranks == NULL).
+ * Integer counts, no float atomics: deterministic. */
+int mm_retrieval_masked(const float* Q, const float* G, const int* qgid, const int* ggid, int radius, int* ranks,
+                        int* negatives, int* topk_idx, float* topk_score, float* ws, int Nq, int Ng, int D, int k,
+                        hipStream_t stream);
+int mm_retrieval_masked_ws_floats(int Nq, int Ng, int D, int k, int* floats_host, hipStream_t stream);
 
 /* ---- EnhancedPowerEncoder: its three Conv1d(C -> 64, k = 3 | 5 | 7) + BatchNorm1d(64) branches
  * (enhanced_models_v4.py:210-234, forward :258-266: torch.cat of the three) as ONE Conv1d(C -> 192, k = 7, p = 3) +

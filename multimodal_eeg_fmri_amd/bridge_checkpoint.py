@@ -497,12 +497,12 @@ class TrainerCheckpointMixin:
             self.bucket.ema.copy_(ema)
         ops.weights_changed()
 
-    def _validate(self, val, monitor, batch_size, use_ema: bool = False):
+    def _validate(self, val, monitor, batch_size, use_ema: bool = False, radius: int = 0):
         from .bridge_utils import retrieval_metrics
         s0 = ops._seed_state["step"]
         with (self.ema_weights() if use_ema else contextlib.nullcontext()):
             ze, zf = self.embed(val[0], val[1], batch_size)
-            metrics = retrieval_metrics(ze, zf, groups=val[2] if len(val) > 2 else None)
+            metrics = retrieval_metrics(ze, zf, groups=val[2] if len(val) > 2 else None, radius=radius)
             if len(val) > 3 and val[3] is not None:       # class labels: the reference's evaluate_bridge metrics as well
                 metrics["classification"] = self.evaluate_classification(val[0], val[1], val[3], batch_size)
         assert ops._seed_state["step"] == s0, "validation drew dropout seeds"
@@ -511,7 +511,7 @@ class TrainerCheckpointMixin:
     def fit(self, train, epochs: int, *, val=None, warmup_epochs: int = 3, min_lr: float = 1e-6,
             monitor: Union[str, Callable[[dict], float]] = "mean_R@1", mode: str = "max", patience: int = 15,
             min_delta: float = 1e-3, eval_every: int = 1, checkpoint_dir: Optional[str] = None, resume: bool = False,
-            val_batch_size: int = 256, validate_with: Optional[str] = None):
+            val_batch_size: int = 256, validate_with: Optional[str] = None, val_radius: int = 0):
         """The reference's epoch loop (run_training_lite.py:465-520) on the contrastive step -> per-epoch history.
 
         ``train``: an iterable of (eeg, fmri) or (eeg, fmri, groups) batches re-iterated every epoch, or ``epoch ->
@@ -523,7 +523,10 @@ class TrainerCheckpointMixin:
         A classify trainer takes (eeg, fmri, groups_or_None, labels) batches; ``val = (eeg, fmri, groups_or_None, labels)``
         adds ``metrics["classification"]`` (`evaluate_classification`), e.g. ``monitor="classification.Accuracy"``.
         ``val = (eeg, fmri[, groups])``: every ``eval_every`` epochs (and after the last) `embed` + `retrieval_metrics`
-        (grouped ranks with ``groups``); the
+        (grouped ranks with ``groups``; ``val_radius`` = R > 0: ``groups`` are timeline ids and a pair within R of the
+        query's id is ignored by the validation ranks, `retrieval_metrics(radius=R)` - what a trainer built with
+        ``neighbour_radius=R`` should be selected on; it is an argument like the others, not part of a checkpoint, so
+        ``resume=True`` needs the same value again); the
         monitored value (``monitor_value``; ``mode`` "max" or "min") drives `EarlyStopping(patience, min_delta)` and the
         best state: on a strict improvement a device copy of the parameters and buffers is kept (and ``best.pt`` written
         when ``checkpoint_dir`` is set); the best model is restored in place at the end (the optimizer state is not,
@@ -552,6 +555,11 @@ class TrainerCheckpointMixin:
         if validate_with == "ema" and not averaging:
             raise ValueError("fit: validate_with='ema' needs a trainer built with ema_decay > 0")
         use_ema = validate_with == "ema"
+        val_radius = int(val_radius)
+        if val_radius < 0:
+            raise ValueError(f"fit: val_radius must be >= 0 (got {val_radius})")
+        if val_radius > 0 and (val is None or len(val) < 3 or val[2] is None):
+            raise ValueError(f"fit: val_radius={val_radius} needs val = (eeg, fmri, groups) with timeline ids")
         if checkpoint_dir is not None and dp.rank(self.group) == 0:
             os.makedirs(checkpoint_dir, exist_ok=True)
         last = os.path.join(checkpoint_dir, "last.pt") if checkpoint_dir else None
@@ -587,7 +595,7 @@ class TrainerCheckpointMixin:
                 entry = {"epoch": epoch, "lr": lr, "steps": n, "train_loss": total.item() / max(n, 1),
                          "val": None, "monitor": None, "improved": False, "stop": False}
                 if val is not None and (epoch % eval_every == 0 or epoch == epochs):
-                    entry.update(self._decide(val, monitor, mode, val_batch_size, stopper, best_score, use_ema))
+                    entry.update(self._decide(val, monitor, mode, val_batch_size, stopper, best_score, use_ema, val_radius))
                     if entry["improved"]:
                         best_score, best_epoch = entry["monitor"], epoch
                         best = self._best_copy()
@@ -606,12 +614,12 @@ class TrainerCheckpointMixin:
             self._restore_best(best)
         return history
 
-    def _decide(self, val, monitor, mode, batch_size, stopper, best_score, use_ema: bool = False) -> dict:
+    def _decide(self, val, monitor, mode, batch_size, stopper, best_score, use_ema: bool = False, radius: int = 0) -> dict:
         """rank 0 validates (``use_ema``: with the averaged weights); every rank takes rank 0's metrics, monitored value,
         improvement and stop"""
         metrics = score = None
         if dp.rank(self.group) == 0:
-            metrics, score = self._validate(val, monitor, batch_size, use_ema)
+            metrics, score = self._validate(val, monitor, batch_size, use_ema, radius)
         if dp.world_size(self.group) > 1:
             import torch.distributed as dist
             ctrl = dp._control_group(self.group)

@@ -144,7 +144,8 @@ class BridgeTrainer(TrainerCheckpointMixin, TrainerStagingMixin, nn.Module):
         mm_sigmoid_loss_own_rows_masked in place of the grouped launch): consecutive epochs of a
         recording, which share most of their input, stop being pushed apart.  `train_step`, `forward` and `evaluate`
         then need ``groups=`` (ValueError otherwise); no bank and no key encoder (ValueError: their kernels have no
-        ignore relation).  `evaluate_retrieval` still ranks neighbours.  0 (default): unchanged."""
+        ignore relation).  `evaluate_retrieval` by default still ranks neighbours; with ``radius=`` it does not (pass
+        ``radius=trainer.neighbour_radius``; `fit(val_radius=)` for validation).  0 (default): unchanged."""
         super().__init__()
         self.neighbour_radius = int(neighbour_radius)
         if self.neighbour_radius < 0:
@@ -1349,19 +1350,32 @@ class BridgeTrainer(TrainerCheckpointMixin, TrainerStagingMixin, nn.Module):
         return {k: torch.cat([p[k] for p in parts]) for k in parts[0]}
 
     @torch.no_grad()
-    def evaluate_retrieval(self, eeg, fmri, batch_size: int = 256, ks=(1, 5, 10), k: int = 0, groups=None):
+    def evaluate_retrieval(self, eeg, fmri, batch_size: int = 256, ks=(1, 5, 10), k: int = 0, groups=None, radius: int = 0):
         """held-out gallery retrieval: ``embed`` both modalities, then ``retrieval_metrics`` (pair i is the positive of
         query i, both directions; with ``groups`` (N,) every pair of the query's group, the best-placed one ranked).
-        k > 0 adds ``topk``: {"eeg_to_fmri": (idx, score), "fmri_to_eeg": (idx, score)}, each (N, k).  Single process
-        only: a sharded gallery is not supported."""
+        k > 0 adds ``topk``: {"eeg_to_fmri": (idx, score), "fmri_to_eeg": (idx, score)}, each (N, k).
+        ``radius`` > 0 (needs ``groups``, timeline ids): a pair within ``radius`` of the query's id, not equal to it, is
+        ignored - it does not count against the rank and never appears in ``topk`` (``retrieval_metrics(radius=)``,
+        mm_retrieval_masked).  The default 0 ranks neighbours as before, whatever the trainer's ``neighbour_radius``:
+        pass ``radius=trainer.neighbour_radius`` to evaluate the way the trainer trains.  Single process only: a sharded
+        gallery is not supported."""
         if self.world > 1:
             raise ValueError("evaluate_retrieval: the gallery is not sharded; run it on one process (world size 1)")
         if eeg.shape[0] != fmri.shape[0]:
             raise ValueError(f"evaluate_retrieval: {eeg.shape[0]} EEG epochs but {fmri.shape[0]} fMRI volumes")
+        radius = int(radius)
+        if radius < 0:
+            raise ValueError(f"evaluate_retrieval: radius must be >= 0 (got {radius})")
+        if radius > 0 and groups is None:
+            raise ValueError(f"evaluate_retrieval: radius={radius} needs groups= (timeline ids, bridge_utils.timeline_ids)")
         ops.group_ids(groups, eeg.shape[0], None, "evaluate_retrieval")      # bad ids fail before the encoders run
         ze, zf = self.embed(eeg, fmri, batch_size)
-        out = retrieval_metrics(ze, zf, ks, groups)
-        if k > 0:
+        out = retrieval_metrics(ze, zf, ks, groups, radius)
+        if k > 0 and radius > 0:
+            _, ie, se = ops.retrieval(ze, zf, k=k, ranks=False, q_groups=groups, g_groups=groups, radius=radius)
+            _, if_, sf = ops.retrieval(zf, ze, k=k, ranks=False, q_groups=groups, g_groups=groups, radius=radius)
+            out["topk"] = {"eeg_to_fmri": (ie, se), "fmri_to_eeg": (if_, sf)}
+        elif k > 0:
             _, ie, se = ops.retrieval(ze, zf, k=k, ranks=False)
             _, if_, sf = ops.retrieval(zf, ze, k=k, ranks=False)
             out["topk"] = {"eeg_to_fmri": (ie, se), "fmri_to_eeg": (if_, sf)}

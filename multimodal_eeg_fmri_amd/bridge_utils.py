@@ -152,21 +152,42 @@ def rank_summary(ranks: torch.Tensor, ks=(1, 5, 10)) -> dict:
     return out
 
 
-def retrieval_metrics(ze: torch.Tensor, zf: torch.Tensor, ks=(1, 5, 10), groups=None) -> dict:
+def retrieval_metrics(ze: torch.Tensor, zf: torch.Tensor, ks=(1, 5, 10), groups=None, radius: int = 0) -> dict:
     """Gallery-scale CLIP-style retrieval of paired embeddings: pair i is the positive of query i.  Every EEG
     embedding queries all fMRI embeddings and vice versa (mm_retrieval twice, Q and G swapped; no N x N score matrix).
     A tie with the positive counts against the query (a collapsed encoder ranks N, not 1).
     ``groups`` (N,) integer ids (e.g. subjects): every pair of the query's group is a positive, and both directions rank
     the best-placed one (ops.retrieval with q_groups = g_groups = groups).
-    -> {"eeg_to_fmri": {R@k..., median_rank, mean_rank, mrr}, "fmri_to_eeg": {...}, "n": N, "chance": 1 / N}"""
+    -> {"eeg_to_fmri": {R@k..., median_rank, mean_rank, mrr}, "fmri_to_eeg": {...}, "n": N, "chance": 1 / N}
+    ``radius`` > 0 (needs ``groups``, then positions on a timeline: `timeline_ids`): a gallery row within ``radius`` of
+    the query's id, not equal to it, is ignored in both directions (ops.retrieval(radius=)); the dict gains "radius" and
+    per direction "ignored_mean" (ignored gallery rows per query, mean) and "chance_R@1" (the mean over queries of
+    1 / (negatives + 1): the R@1 of a random score against each query's own effective gallery).  0: today's dict."""
     if ze.shape != zf.shape or ze.dim() != 2:
         raise ValueError(f"retrieval_metrics: ze {tuple(ze.shape)} and zf {tuple(zf.shape)} must be equal (N, D)")
+    radius = int(radius)
+    if radius < 0:
+        raise ValueError(f"retrieval_metrics: radius must be >= 0 (got {radius})")
+    if radius > 0 and groups is None:
+        raise ValueError(f"retrieval_metrics: radius={radius} needs groups (timeline ids)")
     gid = ops.group_ids(groups, ze.shape[0], ze.device, "retrieval_metrics")
     ze, zf = ze.detach().float().contiguous(), zf.detach().float().contiguous()
-    r_ef, _, _ = ops.retrieval(ze, zf, q_groups=gid, g_groups=gid)
-    r_fe, _, _ = ops.retrieval(zf, ze, q_groups=gid, g_groups=gid)
     n = ze.shape[0]
-    return {"eeg_to_fmri": rank_summary(r_ef, ks), "fmri_to_eeg": rank_summary(r_fe, ks), "n": n, "chance": 1.0 / n}
+    if radius == 0:
+        r_ef, _, _ = ops.retrieval(ze, zf, q_groups=gid, g_groups=gid)
+        r_fe, _, _ = ops.retrieval(zf, ze, q_groups=gid, g_groups=gid)
+        return {"eeg_to_fmri": rank_summary(r_ef, ks), "fmri_to_eeg": rank_summary(r_fe, ks), "n": n, "chance": 1.0 / n}
+    out = {"n": n, "chance": 1.0 / n, "radius": radius}
+    # the relation is symmetric and both directions carry the same ids, so positives + ignored + negatives = N for both
+    _, inverse, counts = gid.cpu().unique(return_inverse=True, return_counts=True)
+    positives = counts[inverse].double()
+    for key, q, g in (("eeg_to_fmri", ze, zf), ("fmri_to_eeg", zf, ze)):
+        r, _, _, neg = ops.retrieval(q, g, q_groups=gid, g_groups=gid, radius=radius, return_negatives=True)
+        out[key] = rank_summary(r, ks)
+        neg = neg.cpu().double()
+        out[key]["ignored_mean"] = (n - neg - positives).mean().item()
+        out[key]["chance_R@1"] = (1.0 / (neg + 1.0)).mean().item()
+    return out
 
 
 class BridgeFeatureDataset(Dataset):

@@ -22,6 +22,12 @@
 // GRP_MAX>): per (slice, query) the maximum score over the slice's positives; retr_best_kernel folds the slices into
 // s*(q).  The counting sweep (GRP_COUNT) then counts {j : ggid[j] != qgid[q], s >= s*} and pass 3 is unchanged.  Both
 // sweeps score with the same MFMA chain, so a duplicate of the best positive ties with it bit for bit.
+//
+// Ignored temporal neighbours (mm_retrieval_masked): the ids are positions on a timeline and, with the radius R >= 0 and
+// d = |ggid[j] - qgid[q]| (an unsigned difference, retr_id_dist), d == 0 is a positive, 0 < d <= R is ignored and d > R a
+// negative.  The maxima sweep is the grouped one (equality needs no radius).  The counting sweep runs in a fourth mode
+// (GRP_MASK): it counts {j : d > R, s >= s*} and, with NEG, {j : d > R} (ids only), and - for the first time together with
+// group ids - keeps top-k lists, which a candidate enters only when d == 0 or d > R.  Pass 3 also adds the second count.
 #include "common.h"
 #include "mmeeg_hip.h"
 #include <limits.h>
@@ -37,7 +43,7 @@ constexpr int KMAX = MM_RETRIEVAL_KMAX;
 constexpr int LSTR = KMAX + 1;          // per-row list stride in LDS (odd: one thread per row, no 16-way conflicts)
 constexpr int CAP = 16;                 // top-k candidates per row per merge round
 constexpr int TARGET_WG = 512;          // 2 workgroups per CU on 256 CUs
-constexpr int GRP_NONE = 0, GRP_MAX = 1, GRP_COUNT = 2;     // retr_tile_kernel's group modes (see the file comment)
+constexpr int GRP_NONE = 0, GRP_MAX = 1, GRP_COUNT = 2, GRP_MASK = 3;     // retr_tile_kernel's group modes (see the file comment)
 
 // max that ignores NaN: a NaN b leaves a; NaN only when both are
 __device__ __forceinline__ float nanmax(float a, float b) { return (b > a || a != a) ? b : a; }
@@ -45,6 +51,12 @@ __device__ __forceinline__ float half32_nanmax(float v) {      // over each alig
 #pragma unroll
     for (int o = 1; o < 32; o <<= 1) v = nanmax(v, __shfl_xor(v, o, 64));
     return v;
+}
+
+// |a - b| of two int32 ids in [0, 2^32): the unsigned difference of the larger and the smaller cannot wrap (clip_loss.hip's
+// clip_id_dist)
+__device__ __forceinline__ unsigned retr_id_dist(int a, int b) {
+    return a >= b ? (unsigned)a - (unsigned)b : (unsigned)b - (unsigned)a;
 }
 
 __device__ __forceinline__ bool beats(float s, int j, float ts, int tj) {
@@ -105,15 +117,18 @@ static RetrPlan retr_plan(int Nq, int Ng) {
 
 struct RetrArgs {
     const float* Q; const float* G; const int* pos; const float* spos;
-    const int* qgid; const int* ggid;       // grouped positives (GRP_MAX / GRP_COUNT), else null
+    const int* qgid; const int* ggid;       // grouped positives (GRP_MAX / GRP_COUNT / GRP_MASK), else null
     float* smax;       // [nslices][Nq] per-slice maxima over the positives (GRP_MAX)
     int* cnt;          // [nslices][Nq]
     float* tks;        // [nslices][Nq][k]
     int* tki;          // [nslices][Nq][k]
     int Nq, Ng, D, k, tps, ntiles;
+    int radius;        // GRP_MASK: 0 < d <= radius is ignored (unread in the other modes)
+    int* ncnt;         // [nslices][Nq] per-slice #{j : d > radius} (NEG)
+    int* negatives;    // [Nq] (NEG)
 };
 
-template <bool RANK, bool TOPK, int GRP = GRP_NONE>
+template <bool RANK, bool TOPK, int GRP = GRP_NONE, bool NEG = false>
 __global__ __launch_bounds__(256, TOPK ? 1 : 2) void retr_tile_kernel(RetrArgs a) {
     __shared__ float qs[KC * LDS_STRIDE];
     __shared__ float gs[KC * LDS_STRIDE];
@@ -126,6 +141,8 @@ __global__ __launch_bounds__(256, TOPK ? 1 : 2) void retr_tile_kernel(RetrArgs a
     __shared__ float sp_s[RANK ? QB : 1];
     __shared__ int pq_s[RANK || GRP ? QB : 1];         // the positive's index, or the query's group id
     __shared__ float pmax[GRP == GRP_MAX ? 2 * QB : 1];
+    __shared__ int npart[NEG ? 2 * QB : 1];
+    static_assert(!NEG || GRP == GRP_MASK, "the id-only count belongs to the masked sweep");
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int li = lane & 31, h = lane >> 5;
@@ -139,6 +156,7 @@ __global__ __launch_bounds__(256, TOPK ? 1 : 2) void retr_tile_kernel(RetrArgs a
     // rows this lane's accumulator registers hold: tile row of (rt, reg) = wr * 64 + 32 rt + (reg & 3) + 8 (reg >> 2) + 4 h.
     // Positive score / index per row in LDS (read per tile: registers go to the accumulators and the counts)
     int cnt[2][16];
+    int ncnt[2][16];
     float mx[2][16];
     if constexpr (GRP == GRP_MAX) {
         if (tid < QB) pq_s[tid] = a.qgid[min(q0 + tid, a.Nq - 1)];
@@ -147,11 +165,20 @@ __global__ __launch_bounds__(256, TOPK ? 1 : 2) void retr_tile_kernel(RetrArgs a
 #pragma unroll
             for (int r = 0; r < 16; ++r) mx[rt][r] = __builtin_nanf("");
     }
+    if constexpr (GRP == GRP_MASK) {
+        if (!RANK && tid < QB) pq_s[tid] = a.qgid[min(q0 + tid, a.Nq - 1)];
+        if constexpr (NEG) {
+#pragma unroll
+            for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) ncnt[rt][r] = 0;
+        }
+    }
     if (RANK) {
         if (tid < QB) {
             const int q = min(q0 + tid, a.Nq - 1);
             sp_s[tid] = a.spos[q];
-            if constexpr (GRP == GRP_COUNT) pq_s[tid] = a.qgid[q];
+            if constexpr (GRP == GRP_COUNT || GRP == GRP_MASK) pq_s[tid] = a.qgid[q];
             else pq_s[tid] = a.pos ? a.pos[q] : q;
         }
 #pragma unroll
@@ -217,7 +244,24 @@ __global__ __launch_bounds__(256, TOPK ? 1 : 2) void retr_tile_kernel(RetrArgs a
             }
         }
         const int jb = t * GB + wc * 64 + li;          // gallery index of column tile ct: jb + 32 ct
-        if (RANK) {
+        if constexpr (GRP == GRP_MASK && (RANK || NEG)) {
+            const bool in0 = jb < a.Ng, in1 = jb + 32 < a.Ng;
+            const unsigned R = (unsigned)a.radius;
+#pragma unroll
+            for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int row = wr * 64 + 32 * rt + (r & 3) + 8 * (r >> 2) + 4 * h;
+                    const int pq = pq_s[row];
+                    const bool far0 = in0 & (retr_id_dist(gg[0], pq) > R), far1 = in1 & (retr_id_dist(gg[1], pq) > R);
+                    if (RANK) {
+                        const float sp = sp_s[row];
+                        cnt[rt][r] += (far0 & (acc[rt][0][r] >= sp)) + (far1 & (acc[rt][1][r] >= sp));
+                    }
+                    if constexpr (NEG) ncnt[rt][r] += far0 + far1;
+                }
+        }
+        if (RANK && GRP != GRP_MASK) {
             const bool in0 = jb < a.Ng, in1 = jb + 32 < a.Ng;
 #pragma unroll
             for (int rt = 0; rt < 2; ++rt)
@@ -252,6 +296,16 @@ __global__ __launch_bounds__(256, TOPK ? 1 : 2) void retr_tile_kernel(RetrArgs a
                     const int j = jb + 32 * ct;
                     const int rbase = wr * 64 + 32 * rt + 4 * h;
                     unsigned pend = (j < a.Ng) ? 0xFFFFu : 0u;
+                    if constexpr (GRP == GRP_MASK) {       // an ignored row (0 < d <= radius) is never a candidate
+                        const unsigned R = (unsigned)a.radius;
+                        unsigned adm = 0u;
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) {
+                            const unsigned d = retr_id_dist(gg[ct], pq_s[rbase + (r & 3) + 8 * (r >> 2)]);
+                            adm |= (unsigned)(d == 0u || d > R) << r;
+                        }
+                        pend &= adm;
+                    }
                     while (true) {
 #pragma unroll
                         for (int r = 0; r < 16; ++r) {
@@ -295,6 +349,17 @@ __global__ __launch_bounds__(256, TOPK ? 1 : 2) void retr_tile_kernel(RetrArgs a
         __syncthreads();
         if (tid < QB && q0 + tid < a.Nq) a.cnt[(size_t)slice * a.Nq + q0 + tid] = part[tid] + part[QB + tid];
     }
+    if constexpr (NEG) {
+#pragma unroll
+        for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const float v = half32_sum((float)ncnt[rt][r]);
+                if (li == 0) npart[wc * QB + wr * 64 + 32 * rt + (r & 3) + 8 * (r >> 2) + 4 * h] = (int)v;
+            }
+        __syncthreads();
+        if (tid < QB && q0 + tid < a.Nq) a.ncnt[(size_t)slice * a.Nq + q0 + tid] = npart[tid] + npart[QB + tid];
+    }
     if constexpr (GRP == GRP_MAX) {
         // the 32 lanes of a half hold the same rows: fold over them, then over the two column waves
 #pragma unroll
@@ -320,13 +385,20 @@ __global__ __launch_bounds__(256, TOPK ? 1 : 2) void retr_tile_kernel(RetrArgs a
     }
 }
 
-// one thread per query: ranks = 1 + the slices' counts (Ng for a NaN positive score); top-k = the slices' lists merged
+// one thread per query: ranks = 1 + the slices' counts (Ng for a NaN positive score); top-k = the slices' lists merged;
+// NEG: negatives = the slices' id-only counts, in slice order
+template <bool NEG = false>
 __global__ __launch_bounds__(64) void retr_finish_kernel(RetrArgs a, int nslices, int* __restrict__ ranks,
                                                          int* __restrict__ topk_idx, float* __restrict__ topk_score) {
     __shared__ float ls[64 * LSTR];
     __shared__ int lj[64 * LSTR];
     const int q = blockIdx.x * 64 + threadIdx.x;
     if (q >= a.Nq) return;
+    if constexpr (NEG) {
+        int n = 0;
+        for (int s = 0; s < nslices; ++s) n += a.ncnt[(size_t)s * a.Nq + q];
+        a.negatives[q] = n;
+    }
     if (ranks) {
         int n = 0;
         for (int s = 0; s < nslices; ++s) n += a.cnt[(size_t)s * a.Nq + q];
@@ -363,17 +435,18 @@ __global__ __launch_bounds__(64) void retr_best_kernel(const float* __restrict__
     spos[q] = v;
 }
 
-static int64_t retr_ws(const RetrPlan& p, int Nq, int k) {
-    return (int64_t)Nq * (1 + (int64_t)p.nslices * (1 + 2 * (int64_t)k));
+// masked: one more per-slice count (the id-only count behind `negatives`)
+static int64_t retr_ws(const RetrPlan& p, int Nq, int k, bool masked = false) {
+    return (int64_t)Nq * (1 + (int64_t)p.nslices * (1 + (masked ? 1 : 0) + 2 * (int64_t)k));
 }
 
-static int retr_check_shape(const char* who, int Nq, int Ng, int D, int k) {
+static int retr_check_shape(const char* who, int Nq, int Ng, int D, int k, bool masked = false) {
     MM_REQUIRE(Nq >= 1 && Nq <= MM_RETRIEVAL_NMAX && Ng >= 1 && Ng <= MM_RETRIEVAL_NMAX,
                "%s: need 1 <= Nq, Ng <= %d (got Nq=%d Ng=%d)", who, MM_RETRIEVAL_NMAX, Nq, Ng);
     MM_REQUIRE(D >= 4 && D <= 1024 && D % 4 == 0, "%s: D must be a multiple of 4 in [4, 1024] (got %d)", who, D);
     MM_REQUIRE(k >= 0 && k <= MM_RETRIEVAL_KMAX && k <= Ng, "%s: k must be in [0, min(%d, Ng)] (got k=%d, Ng=%d)",
                who, MM_RETRIEVAL_KMAX, k, Ng);
-    const int64_t ws = retr_ws(retr_plan(Nq, Ng), Nq, k);
+    const int64_t ws = retr_ws(retr_plan(Nq, Ng), Nq, k, masked);
     MM_REQUIRE(ws <= INT_MAX, "%s: workspace of %lld floats overflows int", who, (long long)ws);
     return MM_OK;
 }
@@ -399,7 +472,7 @@ extern "C" int mm_retrieval(const float* Q, const float* G, const int* pos, int*
     MM_REQUIRE(((uintptr_t)Q % 16) == 0 && ((uintptr_t)G % 16) == 0, "mm_retrieval: Q and G must be 16-byte aligned");
 
     const RetrPlan p = retr_plan(Nq, Ng);
-    RetrArgs a;
+    RetrArgs a = {};
     a.Q = Q; a.G = G; a.pos = pos;
     float* spos = ws;
     int* cnt = reinterpret_cast<int*>(ws + Nq);
@@ -417,7 +490,7 @@ extern "C" int mm_retrieval(const float* Q, const float* G, const int* pos, int*
     else if (ranks) retr_tile_kernel<true, false><<<grid, 256, 0, stream>>>(a);
     else retr_tile_kernel<false, true><<<grid, 256, 0, stream>>>(a);
     if (int e = mm_check_launch("mm_retrieval: tiles")) return e;
-    retr_finish_kernel<<<ceil_div(Nq, 64), 64, 0, stream>>>(a, p.nslices, ranks, k > 0 ? topk_idx : nullptr, topk_score);
+    retr_finish_kernel<false><<<ceil_div(Nq, 64), 64, 0, stream>>>(a, p.nslices, ranks, k > 0 ? topk_idx : nullptr, topk_score);
     return mm_check_launch("mm_retrieval: finish");
 }
 
@@ -454,6 +527,68 @@ extern "C" int mm_retrieval_grouped(const float* Q, const float* G, const int* q
     if (int e = mm_check_launch("mm_retrieval_grouped: best positive")) return e;
     retr_tile_kernel<true, false, GRP_COUNT><<<grid, 256, 0, stream>>>(a);
     if (int e = mm_check_launch("mm_retrieval_grouped: tiles")) return e;
-    retr_finish_kernel<<<ceil_div(Nq, 64), 64, 0, stream>>>(a, p.nslices, ranks, nullptr, nullptr);
+    retr_finish_kernel<false><<<ceil_div(Nq, 64), 64, 0, stream>>>(a, p.nslices, ranks, nullptr, nullptr);
     return mm_check_launch("mm_retrieval_grouped: finish");
+}
+
+extern "C" int mm_retrieval_masked_ws_floats(int Nq, int Ng, int D, int k, int* floats_host, hipStream_t) {
+    MM_REQUIRE(floats_host, "mm_retrieval_masked_ws_floats: null floats_host");
+    const int rc = retr_check_shape("mm_retrieval_masked_ws_floats", Nq, Ng, D, k, true);
+    if (rc) return rc;
+    *floats_host = (int)retr_ws(retr_plan(Nq, Ng), Nq, k, true);
+    return MM_OK;
+}
+
+namespace {
+
+// the counting sweep of mm_retrieval_masked: RANK and / or TOPK, with or without the id-only count
+template <bool NEG>
+static void retr_masked_sweep(const RetrArgs& a, bool rank, dim3 grid, hipStream_t stream) {
+    if (rank && a.k > 0) retr_tile_kernel<true, true, GRP_MASK, NEG><<<grid, 256, 0, stream>>>(a);
+    else if (rank) retr_tile_kernel<true, false, GRP_MASK, NEG><<<grid, 256, 0, stream>>>(a);
+    else retr_tile_kernel<false, true, GRP_MASK, NEG><<<grid, 256, 0, stream>>>(a);
+}
+
+}  // namespace
+
+extern "C" int mm_retrieval_masked(const float* Q, const float* G, const int* qgid, const int* ggid, int radius, int* ranks,
+                                   int* negatives, int* topk_idx, float* topk_score, float* ws, int Nq, int Ng, int D, int k,
+                                   hipStream_t stream) {
+    MM_REQUIRE(Q && G && qgid && ggid && ws, "mm_retrieval_masked: null Q, G, qgid, ggid or ws");
+    MM_REQUIRE(radius >= 0, "mm_retrieval_masked: radius=%d must be >= 0", radius);
+    MM_REQUIRE(ranks || k > 0, "mm_retrieval_masked: nothing to compute (ranks is null and k == 0)");
+    MM_REQUIRE(k == 0 || (topk_idx && topk_score), "mm_retrieval_masked: k = %d needs topk_idx and topk_score", k);
+    const int rc = retr_check_shape("mm_retrieval_masked", Nq, Ng, D, k, true);
+    if (rc) return rc;
+    MM_REQUIRE(((uintptr_t)Q % 16) == 0 && ((uintptr_t)G % 16) == 0, "mm_retrieval_masked: Q and G must be 16-byte aligned");
+
+    const RetrPlan p = retr_plan(Nq, Ng);
+    const size_t per_slice = (size_t)p.nslices * Nq;
+    RetrArgs a = {};
+    a.Q = Q; a.G = G; a.qgid = qgid; a.ggid = ggid; a.radius = radius;
+    // ws: spos [Nq] | maxima, then counts [nslices][Nq] (one region, as mm_retrieval_grouped) | id-only counts [nslices][Nq] |
+    // list scores [nslices][Nq][k] | list indices [nslices][Nq][k]
+    float* spos = ws;
+    a.spos = spos;
+    a.smax = ws + Nq;
+    a.cnt = reinterpret_cast<int*>(ws + Nq);
+    a.ncnt = reinterpret_cast<int*>(ws + Nq + per_slice);
+    a.tks = ws + Nq + 2 * per_slice;
+    a.tki = reinterpret_cast<int*>(a.tks + per_slice * k);
+    a.negatives = negatives;
+    a.Nq = Nq; a.Ng = Ng; a.D = D; a.k = k; a.tps = p.tps; a.ntiles = p.ntiles;
+
+    const dim3 grid(p.qblocks, p.nslices);
+    if (ranks) {
+        retr_tile_kernel<false, false, GRP_MAX><<<grid, 256, 0, stream>>>(a);
+        if (int e = mm_check_launch("mm_retrieval_masked: positive maxima")) return e;
+        retr_best_kernel<<<ceil_div(Nq, 64), 64, 0, stream>>>(a.smax, spos, p.nslices, Nq);
+        if (int e = mm_check_launch("mm_retrieval_masked: best positive")) return e;
+    }
+    if (negatives) retr_masked_sweep<true>(a, ranks != nullptr, grid, stream);
+    else retr_masked_sweep<false>(a, ranks != nullptr, grid, stream);
+    if (int e = mm_check_launch("mm_retrieval_masked: tiles")) return e;
+    if (negatives) retr_finish_kernel<true><<<ceil_div(Nq, 64), 64, 0, stream>>>(a, p.nslices, ranks, k > 0 ? topk_idx : nullptr, topk_score);
+    else retr_finish_kernel<false><<<ceil_div(Nq, 64), 64, 0, stream>>>(a, p.nslices, ranks, k > 0 ? topk_idx : nullptr, topk_score);
+    return mm_check_launch("mm_retrieval_masked: finish");
 }

@@ -2002,8 +2002,14 @@ def retrieval_grouped_ws_floats(nq: int, ng: int, d: int) -> int:
     return _hip.host_int("mm_retrieval_grouped_ws_floats", nq, ng, d)
 
 
+def retrieval_masked_ws_floats(nq: int, ng: int, d: int, k: int) -> int:
+    """floats of mm_retrieval_masked's scratch (mm_retrieval_masked_ws_floats)"""
+    return _hip.host_int("mm_retrieval_masked_ws_floats", nq, ng, d, k)
+
+
 def retrieval(q: torch.Tensor, g: torch.Tensor, positives: Optional[torch.Tensor] = None, k: int = 0,
-              ranks: bool = True, q_groups: Optional[torch.Tensor] = None, g_groups: Optional[torch.Tensor] = None):
+              ranks: bool = True, q_groups: Optional[torch.Tensor] = None, g_groups: Optional[torch.Tensor] = None,
+              radius: int = 0, return_negatives: bool = False):
     """Rank of each query's positive among all gallery rows and / or its top-k matches (mm_retrieval), without an
     Nq x Ng score matrix.  q (Nq, D), g (Ng, D): contiguous fp32 on the GPU (L2-normalised rows for cosine retrieval).
     positives: int tensor (Nq,) of gallery indices (None: query i's positive is gallery row i).  Scores are exact fp32
@@ -2012,14 +2018,27 @@ def retrieval(q: torch.Tensor, g: torch.Tensor, positives: Optional[torch.Tensor
     descending, equal scores by lower index, unfilled slots (-1, -inf).
     q_groups (Nq,) / g_groups (Ng,) integer group ids (both or neither; not with ``positives``; ranks only, k = 0): every
     gallery row of the query's group is a positive, and the rank is that of the best-placed one (mm_retrieval_grouped:
-    1 + #{j outside the group : s_j >= max over the group}; a query without a positive ranks Ng)."""
+    1 + #{j outside the group : s_j >= max over the group}; a query without a positive ranks Ng).
+    ``radius`` > 0 (needs both id vectors): the ids are timeline positions (`bridge_utils.timeline_ids`) and a gallery row
+    within ``radius`` of the query's id, not equal to it, is ignored - it never counts against the rank and never enters
+    the top-k (mm_retrieval_masked; ``k > 0`` and ``ranks=False`` are allowed here).  ``return_negatives=True`` (needs the
+    ids; also mm_retrieval_masked) appends the int64 (Nq,) number of gallery rows further than ``radius`` from each query
+    to the tuple.  ``radius=0`` without it: the calls above, unchanged."""
     grouped = q_groups is not None or g_groups is not None
+    radius = int(radius)
+    if radius < 0:
+        raise ValueError(f"retrieval: radius must be >= 0 (got {radius})")
+    if radius > 0 and (q_groups is None or g_groups is None):
+        raise ValueError(f"retrieval: radius={radius} needs group ids (q_groups and g_groups: positions on a timeline)")
+    if return_negatives and (q_groups is None or g_groups is None):
+        raise ValueError("retrieval: return_negatives=True needs group ids (q_groups and g_groups)")
+    masked = radius > 0 or bool(return_negatives)          # radius = 0 without the count: today's calls
     if grouped:
         if q_groups is None or g_groups is None:
             raise ValueError("retrieval: give both q_groups and g_groups, or neither")
         if positives is not None:
             raise ValueError("retrieval: positives and group ids are exclusive")
-        if not ranks or int(k) != 0:
+        if not masked and (not ranks or int(k) != 0):
             raise ValueError("retrieval: with group ids only ranks are computed (ranks=True, k = 0; top-k does not depend on groups)")
     for name, t in (("q", q), ("g", g)):
         if not isinstance(t, torch.Tensor) or t.dim() != 2:
@@ -2037,6 +2056,23 @@ def retrieval(q: torch.Tensor, g: torch.Tensor, positives: Optional[torch.Tensor
         raise ValueError(f"retrieval: q has D = {d}, g has D = {g.shape[1]}")
     if q.device != g.device:
         raise ValueError("retrieval: q and g are on different devices")
+    if masked:
+        k = int(k)
+        if not 0 <= k <= min(retrieval_kmax(), ng):
+            raise ValueError(f"retrieval: k must be in [0, min({retrieval_kmax()}, Ng = {ng})] (got {k})")
+        if not ranks and k == 0:
+            raise ValueError("retrieval: nothing to compute (ranks=False and k = 0)")
+        qg = group_ids(q_groups, nq, q.device, "retrieval: q_groups")
+        gg = group_ids(g_groups, ng, q.device, "retrieval: g_groups")
+        ws = torch.empty(retrieval_masked_ws_floats(nq, ng, d, k), dtype=_F32, device=q.device)
+        r32 = torch.empty(nq, dtype=torch.int32, device=q.device) if ranks else None
+        n32 = torch.empty(nq, dtype=torch.int32, device=q.device) if return_negatives else None
+        ti = torch.empty((nq, k), dtype=torch.int32, device=q.device) if k else None
+        ts = torch.empty((nq, k), dtype=_F32, device=q.device) if k else None
+        with torch.cuda.device(q.device):
+            _hip.call("mm_retrieval_masked", q, g, qg, gg, radius, r32, n32, ti, ts, ws, nq, ng, d, k)
+        out = (r32.long() if ranks else None, ti.long() if k else None, ts)
+        return out + (n32.long(),) if return_negatives else out
     if grouped:
         qg = group_ids(q_groups, nq, q.device, "retrieval: q_groups")
         gg = group_ids(g_groups, ng, q.device, "retrieval: g_groups")

@@ -488,6 +488,47 @@ def neighbours_case(rounds=5):
             print(f"neighbours B={B} Bg={Bg} N={N}: {kind} masked - grouped {m - g:+6.2f} us")
 
 
+def retrieval_masked_case(rounds=5, iters=10):
+    """retrieval with ignored temporal neighbours: mm_retrieval_masked against the same build's mm_retrieval_grouped (ranks
+    only, k = 0) and mm_retrieval (top-k only, k = 10) at (Nq, Ng, D) = (4096, 4096, 128) and (512, 65536, 128), on
+    preallocated buffers (the entry points alone), HIP events, medians of interleaved rounds [min .. max].  Timeline ids (a
+    shuffled 0 .. Ng - 1; the queries take the first Nq), radius 2: 2 to 4 ignored rows per query; the grouped launch
+    gets the same ids, the ungrouped one needs none"""
+    for nq, ng, d in ((4096, 4096, 128), (512, 65536, 128)):
+        gen = torch.Generator(device="cuda").manual_seed(7)
+        q = torch.nn.functional.normalize(torch.randn(nq, d, device="cuda", generator=gen), dim=1).contiguous()
+        g = torch.nn.functional.normalize(torch.randn(ng, d, device="cuda", generator=gen), dim=1).contiguous()
+        gg = torch.randperm(ng, device="cuda").to(torch.int32).contiguous()
+        qg = gg[:nq].contiguous()
+        k = 10
+        r, n = (torch.empty(nq, dtype=torch.int32, device="cuda") for _ in range(2))
+        ti, ts = torch.empty(nq, k, dtype=torch.int32, device="cuda"), torch.empty(nq, k, device="cuda")
+        ws_g = torch.empty(ops.retrieval_grouped_ws_floats(nq, ng, d), device="cuda")
+        ws_u = torch.empty(ops.retrieval_ws_floats(nq, ng, d, k), device="cuda")
+        ws_m = torch.empty(ops.retrieval_masked_ws_floats(nq, ng, d, k), device="cuda")
+        cases = [
+            ("ranks grouped", lambda: _hip.call("mm_retrieval_grouped", q, g, qg, gg, r, ws_g, nq, ng, d)),
+            ("ranks masked", lambda: _hip.call("mm_retrieval_masked", q, g, qg, gg, 2, r, None, None, None, ws_m, nq, ng, d, 0)),
+            ("ranks+neg masked", lambda: _hip.call("mm_retrieval_masked", q, g, qg, gg, 2, r, n, None, None, ws_m, nq, ng, d, 0)),
+            ("top-k ungrouped", lambda: _hip.call("mm_retrieval", q, g, None, None, ti, ts, ws_u, nq, ng, d, k)),
+            ("top-k masked", lambda: _hip.call("mm_retrieval_masked", q, g, qg, gg, 2, None, None, ti, ts, ws_m, nq, ng, d, k)),
+            ("all masked", lambda: _hip.call("mm_retrieval_masked", q, g, qg, gg, 2, r, n, ti, ts, ws_m, nq, ng, d, k))]
+        times = {name: [] for name, _ in cases}
+        for _ in range(rounds):
+            for name, fn in cases:
+                times[name].append(timeit(fn, iters=iters, rounds=1))
+        tag = f"retrieval_masked Nq={nq} Ng={ng} D={d}"
+        for name, _ in cases:
+            print(f"{tag}: {name:16s} {_spread(times[name])}")
+        med = {name: statistics.median(t) for name, t in times.items()}
+        print(f"{tag}: ranks masked - grouped {med['ranks masked'] - med['ranks grouped']:+7.1f} us "
+              f"({100 * (med['ranks masked'] / med['ranks grouped'] - 1):+.2f} %), with negatives "
+              f"{med['ranks+neg masked'] - med['ranks grouped']:+7.1f} us; top-k (k = {k}) masked - ungrouped "
+              f"{med['top-k masked'] - med['top-k ungrouped']:+7.1f} us ({100 * (med['top-k masked'] / med['top-k ungrouped'] - 1):+.2f} %); "
+              f"ranks, negatives and top-k in one call {med['all masked']:7.1f} us against "
+              f"{med['ranks grouped'] + med['top-k ungrouped']:7.1f} us for the grouped and the ungrouped call")
+
+
 def bank_case(B=32, N=128, step_iters=30, rounds=5):
     """the cross-batch negative bank: the loss section's launches, graph-replayed in the same run - the in-batch InfoNCE
     pair against mm_clip_bank_loss + mm_clip_bank_push on a full bank of K = 1024 and 4096 rows (and the loss's two
@@ -1463,6 +1504,9 @@ def main():
         return
     if flt == "neighbours":
         neighbours_case()
+        return
+    if flt == "retrieval_masked":
+        retrieval_masked_case()
         return
     if flt == "key":
         key_case()
